@@ -13,17 +13,27 @@ resident in HBM before the timed region.  Prints ONE JSON line on rank 0.
 Workload selection (for parity-sized runs, never for the headline):
   --workload rmat10m (default) | rmat1m | laplace4096 | rmat:<n>:<nnz_per_row>
   --workload spgemm_uniform   the reference's own bench shape (sprs-benches/src/main.rs:148-163): uniform density, 2.5M x 2.5M,
-                        4 entries per row, oracle at Fixed(1) and Automatic, whole-product parity; also an object of the default line
+                        4 entries per row, oracle at Fixed(1) and Automatic, whole-product parity; also an object of the --full line
   --workload spgemm5    BASELINE config 5: C = A * A, R-MAT 1M x 1M ~8 nnz/row (smmp::mul_csr_csr twin); a step is one
                         whole product; prints its own JSON line (seconds per product, compulsory-bytes roofline,
                         CPU baseline = the oracle's mul_csr_csr with sprs' chunking at T = 1 and Automatic on sampled
-                        row blocks, row-block parity).  The default SpMV line carries a short "spgemm5" object too
-                        (--no-secondary skips it).
+                        row blocks, row-block parity).  The default SpMV line with --full carries a short "spgemm5" object
+                        too (--no-secondary skips it).
   --idx-bytes 8 (default, sprs usize) | 4
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, the configuration and the roofline of the timed kernels).  Everything else the benchmark measures or checks
+runs only with --full: the CPU baseline and the comparison with the oracle, the u32 / SpMM / configs 2, 3 and 5 /
+sparse-dense / sprs-benches objects of the default line, the other exchange routes for N > 1 and, for the SpGEMM
+workloads, the row-block parity, the CPU baseline and the unordered-adds timing.
+
+  --dump-outputs DIR    after the timed steps, write what the last step computed as DIR/<name>.npy (float64, at most
+                        64 MB in all): a fixed, seeded sample of the rows of y (SpMV) or of C (SpGEMM) and the row ids
 """
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -34,6 +44,53 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
+
+DUMP_SAMPLE = 1 << 21   # --dump-outputs: values per written array (16 MiB as float64)
+DUMP_SEED = 2024
+
+
+def sample_rows(n, k=DUMP_SAMPLE, seed=DUMP_SEED):
+    """a fixed, seeded sample of k distinct rows of n in increasing order (every row when n <= k)"""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+def write_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float64"""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
+def vector_outputs(y):
+    """the result vector of an SpMV step (torch, on the device): a seeded sample of its rows and the row ids"""
+    rows = sample_rows(y.numel())
+    vals = y[torch.from_numpy(rows).to(y.device)].cpu().numpy()
+    return {"y_sample": vals, "y_sample_rows": rows}
+
+
+def csmat_outputs(c, block_rows=16, max_blocks=1024, max_entries=DUMP_SAMPLE, seed=DUMP_SEED):
+    """the product of an SpGEMM step (DeviceCsMat): whole rows from blocks of consecutive rows at seeded starts, until
+    max_blocks blocks or max_entries stored entries — the rows, their lengths, their column indices and their values"""
+    n = c.rows()
+    starts = np.random.default_rng(seed).permutation(max(1, -(-n // block_rows)))[:max_blocks] * block_rows
+    rows, lens, idx, val, total = [], [], [], [], 0
+    for r0 in starts:
+        r1 = min(n, int(r0) + block_rows)
+        ip, ix, dt = c.slice_outer_to_host(int(r0), r1)
+        ip = ip.astype(np.int64) - int(ip[0])
+        ln = np.diff(ip)
+        keep = int(np.searchsorted(np.cumsum(ln), max_entries - total, side="right"))   # whole rows that still fit
+        rows.append(np.arange(r0, r0 + keep, dtype=np.int64))
+        lens.append(ln[:keep])
+        idx.append(ix[:ip[keep]].astype(np.int64))
+        val.append(dt[:ip[keep]])
+        total += int(ip[keep])
+        if keep < r1 - r0:
+            break
+    return {"c_sample_rows": np.concatenate(rows), "c_sample_row_nnz": np.concatenate(lens),
+            "c_sample_indices": np.concatenate(idx), "c_sample_data": np.concatenate(val)}
 
 
 def algorithmic_bytes(rows, cols, nnz, idx_bytes, iptr_bytes, accumulate=False):
@@ -63,9 +120,10 @@ def csrc_sha16(part=None):
     return h.hexdigest()[:16]
 
 
-def spgemm5(dev, idx_bytes, steps, warmup, check_rows, cpu_blocks, cpu_block_rows, with_cpu=True):
+def spgemm5(dev, idx_bytes, steps, warmup, check_rows, cpu_blocks, cpu_block_rows, with_cpu=True, full=True, dump_dir=None):
     """BASELINE config 5: C = A * A for R-MAT 1M x 1M, ~8 nnz/row (7.78e6 entries; nnz(C) = 3.3e9, 5.5e9 products).
-    Returns the JSON object of the workload.  SURVEY 8(d): compulsory bytes = (nnzA + nnzB + nnzC)(V + S_I) + 3 (n + 1) S_P."""
+    Returns the JSON object of the workload.  SURVEY 8(d): compulsory bytes = (nnzA + nnzB + nnzC)(V + S_I) + 3 (n + 1) S_P.
+    full = False: the timed products only (no row-block parity, CPU baseline or unordered-adds timing)."""
     import sprs_amd
     from sprs_amd import gen, smmp
     from sprs_amd.device import DeviceCsMat
@@ -117,6 +175,10 @@ def spgemm5(dev, idx_bytes, steps, warmup, check_rows, cpu_blocks, cpu_block_row
                     out["roofline"]["traffic"] = e["traffic_bytes"]
     except (OSError, KeyError, ValueError):
         pass
+    if dump_dir:
+        write_outputs(dump_dir, csmat_outputs(c))
+    if not full:
+        return out
     # ---- parity and CPU baseline on row blocks: the oracle is the checker and the timed CPU port, never the product -------
     from oracle import oracle
     npi = np.uint64 if idx_bytes == 8 else np.uint32
@@ -291,7 +353,7 @@ def spmv_config(dev, wl, steps=30, warmup=4, with_oracle=True):
     return res
 
 
-def spgemm_uniform(dev, n=2_500_000, nnz_over_rows=4, steps=3, with_cpu=True):
+def spgemm_uniform(dev, n=2_500_000, nnz_over_rows=4, steps=3, with_cpu=True, dump_dir=None):
     """The largest product of the reference's own bench (sprs-benches/src/main.rs:148-163, 178-186, 211-260): m1 (n x n) *
     m2 (n x n), both from the uniform generator at density nnz_over_rows / n (sprs-rand `rand_csr`, here gen.uniform_csr),
     timed at ThreadingStrategy::Fixed(1) and ::Automatic on the CPU (the C restatement of smmp::mul_csr_csr; the reference
@@ -309,14 +371,18 @@ def spgemm_uniform(dev, n=2_500_000, nnz_over_rows=4, steps=3, with_cpu=True):
     c = smmp.mul_csr_csr(a, b)
     torch.cuda.synchronize()
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
+    t0 = time.perf_counter()
     for p_, q_ in ev:
         c = None
         p_.record(stream)
         c = smmp.mul_csr_csr(a, b)
         q_.record(stream)
     torch.cuda.synchronize()
+    wall = (time.perf_counter() - t0) / steps
     ms = [p_.elapsed_time(q_) for p_, q_ in ev]
     sec = float(np.mean(ms)) * 1e-3
+    if dump_dir:
+        write_outputs(dump_dir, csmat_outputs(c))
     nnz_a, nnz_b, nnz_c = int(a_ix.numel()), int(b_ix.numel()), int(c.nnz())
     b_len = (b_ip[1:] - b_ip[:-1]).to(torch.float64)
     products = float(b_len[a_ix.long()].sum().item())
@@ -324,6 +390,7 @@ def spgemm_uniform(dev, n=2_500_000, nnz_over_rows=4, steps=3, with_cpu=True):
     out = {"workload": "sprs-benches shape bench, largest shape: (%d x %d) * (%d x %d), uniform density %d / cols, values N(0,1), usize indices"
                        % (n, n, n, n, nnz_over_rows),
            "seconds_per_product": round(sec, 6), "kernel_ms_min": round(float(np.min(ms)), 3), "steps": steps,
+           "ms_per_step": round(wall * 1e3, 3),
            "nnz_a": nnz_a, "nnz_b": nnz_b, "nnz_c": nnz_c, "products": products, "gflops": round(2 * products / sec / 1e9, 2),
            "compulsory_bytes": comp, "achieved_GBs": round(comp / sec / 1e9, 1), "roofline_frac": round(comp / sec / 1e9 / HBM_PEAK_GBS, 4)}
     if with_cpu:
@@ -396,7 +463,7 @@ def sparse_dense_micro(dev, with_oracle=True):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 50; 5 for the SpGEMM workloads)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="rmat10m")
     ap.add_argument("--idx-bytes", type=int, default=8, choices=(4, 8))
@@ -430,6 +497,11 @@ def main():
     ap.add_argument("--cold-cache", action="store_true",
                     help="stream a 1 GiB scratch buffer between steps (outside the per-step kernel events): the matrix and x "
                          "then come from HBM, not from the 256 MiB Infinity Cache (SURVEY 8d, config 2)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: CPU baseline, oracle parity, the secondary objects of the default "
+                         "line, the other exchange routes (N > 1), the SpGEMM workloads' parity / CPU baseline / unordered adds")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (a seeded sample, float64)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -442,7 +514,7 @@ def main():
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         sys.stdout.flush()
-        os.execv(sys.executable, cmd)
+        sys.exit(subprocess.call(cmd))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -485,7 +557,8 @@ def main():
     if args.workload == "spgemm_uniform":
         if world != 1:
             sys.exit("spgemm_uniform is single-GPU (north star: SpGEMM stays on one GPU)")
-        out = spgemm_uniform(dev, steps=args.steps if args.steps != 50 else 5, with_cpu=not args.no_cpu_baseline)
+        out = spgemm_uniform(dev, steps=args.steps if args.steps is not None else 5, with_cpu=args.full and not args.no_cpu_baseline,
+                             dump_dir=args.dump_outputs)
         out.update({"metric": "CSR x CSR SpGEMM seconds per product (sprs-benches shape)", "value": out["seconds_per_product"], "unit": "s",
                     "higher_is_better": False, "n_gpus": 1, "scaling": "replicas only", "vs_baseline": None, "dtype": "f64", "data": "synthetic"})
         print(json.dumps(out))
@@ -493,14 +566,16 @@ def main():
     if args.workload == "spgemm5":
         if world != 1:
             sys.exit("spgemm5 is single-GPU (north star: SpGEMM stays on one GPU)")
-        steps = args.steps if args.steps != 50 else 5
+        steps = args.steps if args.steps is not None else 5
         out = spgemm5(dev, args.idx_bytes, steps, min(args.warmup, 2), check_rows=100, cpu_blocks=16, cpu_block_rows=1500,
-                      with_cpu=not args.no_cpu_baseline)
+                      with_cpu=not args.no_cpu_baseline, full=args.full, dump_dir=args.dump_outputs)
         out.update({"n_gpus": 1, "scaling": "replicas only", "vs_baseline": None})
         print(json.dumps(out))
         return
 
     # ---- workload -----------------------------------------------------------
+    if args.steps is None:
+        args.steps = 50
     idt = torch.int64 if args.idx_bytes == 8 else torch.int32
     t0 = time.time()
     wl = args.workload
@@ -736,10 +811,12 @@ def main():
         t_total = float(tt.item())
     kern_ms = [a.elapsed_time(b) for a, b in ev]
     kern_avg_ms = float(np.mean(kern_ms))
+    if args.dump_outputs and rank == 0:                 # y of the last timed step (N > 1: the gathered vector)
+        write_outputs(args.dump_outputs, vector_outputs(sh.y))
 
     # ---- N > 1: the other exchange route and the multiply alone, after the K timed steps (with and without the gather) ----
     exchange_times = None
-    if world > 1:
+    if world > 1 and args.full:
         import torch.distributed as dist
 
         def timed_ms(fn, k):
@@ -844,6 +921,8 @@ def main():
             "plan": {1: "nnz tiles", 2: "xcd-sliced copy", 3: "banded copy (hot columns from LDS)"}.get(plan_kind, "none"),
             "plan_bytes": plan_bytes,
             "cold_cache": bool(args.cold_cache),
+            # N > 1 on the library's route without --full: the multiply alone is not timed, kernel_ms_avg holds multiply + exchange
+            "includes_exchange": bool(world > 1 and use_lib and not isinstance((exchange_times or {}).get("multiply_only_ms"), float)),
         },
     }
 
@@ -854,7 +933,7 @@ def main():
 
     # ---- N > 1: parity of the distributed result (every rank checks ITS row block against the oracle on that block, and that the
     # gathered y is the same vector on every rank) — the checker only, after the timed region ------------------------------------
-    if world > 1 and not args.no_cpu_baseline:
+    if world > 1 and args.full and not args.no_cpu_baseline:
         import torch.distributed as dist
         try:
             from oracle import oracle   # test infrastructure: the checker, never the product
@@ -884,7 +963,7 @@ def main():
                          "gathered_y_identical": same, "ok": bool(float(t_rel.item()) <= 1e-10 and same)}
 
     # ---- CPU baseline (rank 0, N = 1): the oracle on the host cores -------------
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import oracle   # test infrastructure: the checker + the timed CPU port, never the product
         npdt = np.uint64 if args.idx_bytes == 8 else np.uint32
         ip_h = sh.block[2].cpu().numpy().view(npdt)
@@ -938,7 +1017,7 @@ def main():
             out["config"]["h2d_upload_s"] = "failed: " + repr(e)[:120]
 
     # ---- the same matrix with u32 indices and indptr (a second line, 12 B per entry, never mixed with the headline) ----
-    if rank == 0 and world == 1 and wl == "rmat10m" and args.idx_bytes == 8 and not args.no_secondary:
+    if rank == 0 and world == 1 and args.full and wl == "rmat10m" and args.idx_bytes == 8 and not args.no_secondary:
         try:
             ip4, ix4, dt4 = gen.rmat_csr(n, 32, device=dev, idx_dtype=torch.int32, ptr_dtype=torch.int32)
             a4 = DeviceCsMat.wrap_torch((n, n), ip4, ix4, dt4)
@@ -972,7 +1051,7 @@ def main():
             out["spmv_u32"] = {"error": repr(e)[:200]}
 
     # ---- SpMM on the headline matrix (prod::csr_mulacc_dense_rowmaj, k = 8 and 16 rhs columns) -----------------------
-    if rank == 0 and world == 1 and wl == "rmat10m" and args.idx_bytes == 8 and not args.no_secondary and handles:
+    if rank == 0 and world == 1 and args.full and wl == "rmat10m" and args.idx_bytes == 8 and not args.no_secondary and handles:
         try:
             import ctypes as C
             a8 = handles[id(sh.block)]
@@ -1033,7 +1112,7 @@ def main():
 
     # ---- BASELINE configs 2 and 3 beside the headline (the driver's line must carry them) and the reference's own
     # bench shape for the SpGEMM (sprs-benches: uniform density, 2.5M x 2.5M, 4 entries per row) ------------------------------------
-    if rank == 0 and world == 1 and wl == "rmat10m" and args.idx_bytes == 8 and not args.no_secondary:
+    if rank == 0 and world == 1 and args.full and wl == "rmat10m" and args.idx_bytes == 8 and not args.no_secondary:
         out["configs"] = {}
         for cfg in ("rmat1m", "laplace4096"):
             try:
@@ -1052,7 +1131,7 @@ def main():
         torch.cuda.empty_cache()
 
     # ---- BASELINE config 5 beside the headline (rank 0, N = 1, default workload): a short SpGEMM object -----------
-    if rank == 0 and world == 1 and wl == "rmat10m" and not args.no_secondary and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and wl == "rmat10m" and not args.no_secondary and not args.no_cpu_baseline:
         try:
             del sh
             handles.clear()
@@ -1062,7 +1141,7 @@ def main():
                               "roofline_frac": sg["roofline"]["frac"], "compulsory_bytes": sg["roofline"]["algorithmic_bytes_per_launch"],
                               "traffic": sg["roofline"]["traffic"], "parity": sg["parity"], "cpu_baseline": sg["cpu_baseline"],
                               "unordered_adds": sg.get("unordered_adds"),
-                              "note": "python bench.py --workload spgemm5 prints the full line"}
+                              "note": "python bench.py --full --workload spgemm5 prints the full line"}
         except Exception as e:   # the headline line must not depend on the secondary measurement
             out["spgemm5"] = {"error": repr(e)[:200]}
 

@@ -6,7 +6,7 @@
 #   tests                 the driver's GPU suite (pytest -m gpu) + smoke()
 #   gate:<expr>           pytest -m gpu -k "<expr>" under a short timeout; a failure or a hang ENDS the session (first run of a new kernel)
 #   tests:<expr>          pytest -m gpu -k "<expr>"
-#   bench[:args]          bench.py [args]  (default workload R-MAT 10M SpMV; e.g. bench:--workload\ spgemm5)
+#   bench[:args]          bench.py --full [args]  (default workload R-MAT 10M SpMV; e.g. bench:--workload\ spgemm5)
 #   (SWEEP_ARGS="--workload rmat1m" / "--row-block 3/8" in the environment: the matrix of the sweep / trace steps)
 #   sweep:<configs>       scripts/spmv_sweep.py on R-MAT 10M; configs separated by '|', each name:opt=val,opt=val
 #   trace:<config>        rocprofv3 --kernel-trace of one sweep config, per-kernel means and the dispatch sequence
@@ -18,7 +18,7 @@
 #   spgemm_pmc[:env]      SQ / TCC counter passes over SpGEMM config 5 (per kernel means) -> spgemm_pmc.txt
 #   spgemm_traffic        FETCH_SIZE / WRITE_SIZE pass over SpGEMM config 5 -> spgemm_traffic.txt (scripts/spgemm_traffic.py)
 #   spmm[:args]           SpMM on R-MAT 10M (scripts/spmm_bench.py [n nnz_per_row k ...]) + its kernel stats
-#   spgemm_uniform[:args] bench.py --workload spgemm_uniform (sprs-benches shape) + its kernel stats (small_rows_kernel throughput)
+#   spgemm_uniform[:args] bench.py --full --workload spgemm_uniform (sprs-benches shape) + its kernel stats (small_rows_kernel throughput)
 #   spgemm_uniform_seq    dispatch sequence (offsets, durations, gaps) of one uniform product -> spgemm_uniform_seq.txt
 #   py:<file>             python <file> (an ad-hoc measurement script kept under scripts/)
 #   pmcsq:<config>        SQ counter passes (instruction mix, busy / wait cycles) over one sweep config, per kernel means -> pmcsq.txt
@@ -39,7 +39,7 @@ for step in "$@"; do
       else timeout 1800 python -m pytest tests -m gpu -x -q --durations=6 2>&1 | tail -14; timeout 300 python __graft_entry__.py smoke 2>&1 | grep -v amdgpu | tail -3; fi ;;
     gate)   timeout 300 python -m pytest tests -m gpu -x -q -k "$arg" 2>&1 | tail -6
             if [ "${PIPESTATUS[0]}" != 0 ]; then echo "gate failed: session ends here"; exit 1; fi ;;
-    bench)  timeout 900 python bench.py $arg 2>/dev/null | tee -a $OUT/bench.jsonl ;;
+    bench)  timeout 900 python bench.py --full $arg 2>/dev/null | tee -a $OUT/bench.jsonl ;;
     sweep)  IFS='|' read -ra CFG <<< "$arg"; timeout 900 python scripts/spmv_sweep.py --steps 30 --oracle $SWEEP_ARGS "${CFG[@]}" 2>&1 | grep -v amdgpu.ids | cut -c1-400 | tee -a $OUT/sweep.jsonl ;;
     trace)  ( cd /tmp && rm -rf /tmp/st && timeout 600 rocprofv3 --kernel-trace -d /tmp/st -o s -- python $ROOT/scripts/spmv_sweep.py --steps 10 $SWEEP_ARGS "$arg" > /dev/null 2>&1; python3 $ROOT/scripts/rocprof_seq.py $(prof_db /tmp/st) band_ spmv_ ) 2>&1 | cut -c1-200 | tee -a $OUT/kernel_seq.txt ;;
     stats)  ( cd /tmp && rm -rf /tmp/st && timeout -s KILL 300 rocprofv3 --kernel-trace --stats -d /tmp/st -o s -- python $ROOT/bench.py --no-cpu-baseline $arg > $OUT/stats_bench.json 2>/dev/null; f=$(prof_db /tmp/st); python3 $ROOT/scripts/rocprof_summary.py $f sprs_hip | grep -E "^kernel|^#|sprs_hip" | cut -c1-190; python3 $ROOT/scripts/rocprof_seq.py $f band_ | cut -c1-200 ) 2>&1 | tee -a $OUT/kernel_stats.txt ;;
@@ -103,7 +103,7 @@ for step in "$@"; do
     spmm)   timeout 600 python scripts/spmm_bench.py $arg 2>&1 | grep -E "^\{" | tee -a $OUT/spmm.jsonl
             ( cd /tmp && rm -rf /tmp/st && timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/st -o s -- python $ROOT/scripts/spmm_bench.py ${arg:-10000000 32 16} > /dev/null 2>&1; python3 $ROOT/scripts/rocprof_summary.py $(prof_db /tmp/st) sprs_hip ) 2>&1 | grep -E "^kernel|spmm" | cut -c1-200 | head -8 | tee -a $OUT/spmm_kernels.txt ;;
     spgemm_uniform) # the reference's own bench shape (uniform 2.5M x 2.5M, 4 per row): the line, then per-kernel times of the same command
-            timeout 600 python bench.py --workload spgemm_uniform $arg 2>/dev/null | tee -a $OUT/spgemm_uniform.jsonl
+            timeout 600 python bench.py --full --workload spgemm_uniform $arg 2>/dev/null | tee -a $OUT/spgemm_uniform.jsonl
             ( cd /tmp && rm -rf /tmp/st && timeout -s KILL 300 rocprofv3 --kernel-trace --stats -d /tmp/st -o s -- python $ROOT/bench.py --workload spgemm_uniform --no-cpu-baseline --steps 3 $arg > /dev/null 2>&1; python3 $ROOT/scripts/rocprof_summary.py $(prof_db /tmp/st) sprs_hip ) 2>&1 | grep -E "^kernel|^#|sprs_hip" | cut -c1-200 | head -24 | tee -a $OUT/spgemm_uniform_kernel_stats.txt ;;
     spgemm_uniform_seq) # dispatch sequence of ONE uniform product with the gaps between its kernels
             ( cd /tmp && rm -rf /tmp/st && timeout -s KILL 300 rocprofv3 --kernel-trace -d /tmp/st -o s -- python $ROOT/bench.py --workload spgemm_uniform --no-cpu-baseline --steps 3 $arg > /dev/null 2>&1; python3 $ROOT/scripts/rocprof_seq.py $(prof_db /tmp/st) start=pack_cols sprs_hip ) 2>&1 | cut -c1-200 | tee $OUT/spgemm_uniform_seq.txt ;;

@@ -252,7 +252,7 @@ def test_bench_n_ranks_on_this_gpu(hip, world):
     agreement, the timed loop, the secondary timings and every JSON key — the y blocks travel through host memory instead of
     xGMI.  The distributed result is checked against the oracle block by block inside the run (`parity`)."""
     out, err = _run_bench(["--gpus", str(world), "--backend", "gloo", "--devices", ",".join(["0"] * world),
-                           "--workload", "rmat:400000:24", "--steps", "4", "--warmup", "1"])
+                           "--workload", "rmat:400000:24", "--steps", "4", "--warmup", "1", "--full"])
     assert out["n_gpus"] == world and out["steps"] == 4 and out["warmup"] == 1
     assert out["metric"] == "CSR SpMV GFLOP/s" and out["unit"] == "GFLOP/s" and out["value"] > 0 and out["ms_per_step"] > 0
     assert out["scaling"] == "strong" and out["higher_is_better"] is True and out["dtype"] == "f64"
@@ -274,9 +274,36 @@ def test_bench_n_ranks_on_this_gpu(hip, world):
 
 def test_bench_single_rank_keys(hip):
     """the N = 1 line of the driver's contract on a small workload: roofline + cpu_baseline + parity objects present"""
-    out, _ = _run_bench(["--workload", "rmat:300000:16", "--steps", "5", "--warmup", "2"])
+    out, _ = _run_bench(["--workload", "rmat:300000:16", "--steps", "5", "--warmup", "2", "--full"])
     assert out["n_gpus"] == 1 and out["config"]["partition"] == "single GPU"
     for key in ("roofline", "cpu_baseline", "parity"):
         assert key in out
     assert out["cpu_baseline"]["kind"] == "port" and out["cpu_baseline"]["cores"] == 1 and out["parity"]["ok"]
     assert set(("bound", "achieved", "peak", "unit", "frac", "traffic")) <= set(out["roofline"])
+
+
+def test_bench_plain_run_and_dump_outputs(hip, tmp_path):
+    """a plain run (no --full) times exactly --steps steps and prints the headline keys without the CPU baseline or the oracle;
+    --dump-outputs writes a seeded sample of the last step's y, which must match the oracle on those rows and be the same
+    from run to run"""
+    from oracle import oracle
+    from sprs_amd import gen
+    n = 300000
+    dumps = [tmp_path / "a", tmp_path / "b"]
+    for d, steps in zip(dumps, ("3", "6")):
+        out, _ = _run_bench(["--workload", "rmat:%d:16" % n, "--steps", steps, "--warmup", "1", "--dump-outputs", str(d)])
+        assert out["steps"] == int(steps) and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+        assert out["metric"] == "CSR SpMV GFLOP/s" and out["unit"] == "GFLOP/s" and out["higher_is_better"] is True and out["dtype"] == "f64"
+        assert "cpu_baseline" not in out and "parity" not in out
+    files = sorted(p.name for p in dumps[0].iterdir())
+    assert files == ["y_sample.npy", "y_sample_rows.npy"] and sorted(p.name for p in dumps[1].iterdir()) == files
+    assert sum((dumps[0] / f).stat().st_size for f in files) <= 64 << 20
+    y, rows = np.load(dumps[0] / "y_sample.npy"), np.load(dumps[0] / "y_sample_rows.npy")
+    assert y.dtype == np.float64 and rows.dtype == np.float64 and y.shape == rows.shape == (n,)
+    for f in files:
+        assert np.array_equal(np.load(dumps[0] / f), np.load(dumps[1] / f))
+    indptr, indices, data = gen.rmat_csr(n, 16)
+    ref = np.zeros(n)
+    oracle.mul_acc_mat_vec_csr((n, n), indptr.numpy().astype(np.uint64), indices.numpy().astype(np.uint64), data.numpy(),
+                               gen.dense_vector(n, seed=3).numpy(), ref)
+    assert rel_err(y, ref[rows.astype(np.int64)]) <= 1e-10
