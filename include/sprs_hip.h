@@ -355,6 +355,50 @@ int32_t sprs_hip_csmat_to_other_storage(const sprs_hip_csmat *m, sprs_hip_csmat 
  * of the host mirrors call.  Status codes as sprs_hip_spgemm_f64 and sprs_hip_csmat_to_other_storage. */
 int32_t sprs_hip_csmat_mul_csmat(const sprs_hip_csmat *lhs, const sprs_hip_csmat *rhs, sprs_hip_csmat **out);
 
+/* ---- device sparse vector: twin of CsVecBase (sparse.rs:165-173) and its products with sparse matrices ---- */
+
+typedef struct sprs_hip_csvec sprs_hip_csvec;
+
+/* Copies a host sparse vector (dim, nnz sorted indices of idx_bytes = 2, 4 or 8 each, nnz values) into device buffers OWNED
+ * by the handle.  validate != 0 checks the invariants of CsVec::try_new (vec.rs:440-491, sorted_indices sparse.rs:360-369) —
+ * on the host for small vectors, on the device for large ones — in the reference's order:
+ *   dim does not fit the index width        SPRS_HIP_INDEX_OVERFLOW  "Index size is too small"
+ *   indices not strictly increasing         SPRS_HIP_BAD_STRUCTURE   "Unsorted indices"
+ *   last index >= dim                       SPRS_HIP_BAD_STRUCTURE   "indices larger than vector size"
+ * (indices and data of unequal lengths — "indices and data do not have compatible lengths" — cannot reach this entry: it takes
+ * one nnz.)  validate == 0 is new_trusted.  2-byte indices are widened to 4 on the device and narrowed on download. */
+int32_t sprs_hip_csvec_upload(sprs_hip_csvec **out, uint64_t dim, uint64_t nnz, const void *indices, int32_t idx_bytes,
+                              const double *data, int32_t validate);
+/* Borrows device buffers (torch tensors, ...): NOT owned, must outlive the handle; idx_bytes 4 or 8; not validated
+ * (new_trusted); the products never write outside their own tables whatever the indices hold. */
+int32_t sprs_hip_csvec_wrap_device(sprs_hip_csvec **out, uint64_t dim, uint64_t nnz, const void *dev_indices, int32_t idx_bytes,
+                                   const double *dev_data);
+/* dim (vec.rs:681), nnz (vec.rs:686) and the declared index width; any out pointer may be NULL */
+int32_t sprs_hip_csvec_info(const sprs_hip_csvec *v, uint64_t *dim, uint64_t *nnz, int32_t *idx_bytes);
+/* raw device pointers (into_raw_storage, vec.rs:675), still owned by the handle */
+int32_t sprs_hip_csvec_device_ptrs(const sprs_hip_csvec *v, const void **indices, const double **data);
+/* indices (nnz entries of the declared width) and data (nnz doubles) to host buffers; either may be NULL */
+int32_t sprs_hip_csvec_download(const sprs_hip_csvec *v, void *indices, double *data);
+int32_t sprs_hip_csvec_free(sprs_hip_csvec *v);
+/* CsVec::scatter / to_dense (vec.rs:621, 965): out_dev[i] = v[i] for stored i, 0.0 elsewhere.  out_len must equal dim
+ * (SPRS_HIP_DIM_MISMATCH).  Asynchronous on `stream`. */
+int32_t sprs_hip_csvec_scatter_f64(const sprs_hip_csvec *v, double *out_dev, uint64_t out_len, void *stream);
+
+/* `&CsMat * &CsVec` (vec.rs:1104-1131): NEW owning vector of dimension a.rows (index width: a's declared one).
+ *   CSR a: prod::csr_mul_csvec (prod.rs:161-184) — entry o = the ordered dot of row o with v (dot_acc merge, vec.rs:846-880),
+ *          kept only where val != 0 (both signed zeros dropped, NaN kept); v.dim == 0 gives an empty vector of dimension 0
+ *          whatever a.cols is (prod.rs:171-174);
+ *   CSC a: a * v.col_view() (csmat_mul_csmat, csmat.rs:1944-1947) — the same sums, STRUCTURAL: every o with a matched index,
+ *          explicit zeros kept.
+ * Every sum starts from +0.0 and adds unfused products by ascending inner index: bit-identical to the reference.
+ * SPRS_HIP_DIM_MISMATCH "Dimension mismatch" unless a.cols == v.dim (prod.rs:175); SPRS_HIP_INDEX_OVERFLOW when a result index
+ * does not fit the declared width.  Runs on `stream` and blocks until the result is complete there. */
+int32_t sprs_hip_csmat_mul_csvec_f64(const sprs_hip_csmat *a, const sprs_hip_csvec *v, sprs_hip_csvec **out, void *stream);
+/* `&CsVec * &CsMat` (vec.rs:1084-1102): (v.row_view() * b).outer_view(0) — NEW owning vector of dimension b.cols, entry o =
+ * sum over i ascending of v[i] * b[i, o] (mul_csr_csr, smmp.rs), structural.  SPRS_HIP_DIM_MISMATCH unless v.dim == b.rows.
+ * Index width, stream and blocking as sprs_hip_csmat_mul_csvec_f64. */
+int32_t sprs_hip_csvec_mul_csmat_f64(const sprs_hip_csvec *v, const sprs_hip_csmat *b, sprs_hip_csvec **out, void *stream);
+
 /* ---- row-sharded SpMV over the GPUs of one node (one process per GPU, RCCL over xGMI) ----
  * The reference has no distributed code; the shard is its slice_outer (slicing.rs:65-89) with a rebased indptr
  * (indptr.rs:206-214): rank g owns rows [row_starts[g], row_starts[g+1]) and a full replica of x; one exchange, an

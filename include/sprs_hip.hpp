@@ -308,6 +308,76 @@ inline DeviceCsMat operator*(const DeviceCsMat &a, const DeviceCsMat &b) {
     return DeviceCsMat(c);
 }
 
+// Device twin of CsVecI<f64, I> (sparse.rs:165-173): dim, sorted indices, data.
+class DeviceCsVec {
+public:
+    // CsVec::new (validate = true, vec.rs:430-434) or new_trusted (validate = false); I of 2, 4 or 8 bytes
+    template <typename I>
+    DeviceCsVec(uint64_t dim, const std::vector<I> &indices, const std::vector<double> &data, bool validate = true) {
+        static_assert(std::is_integral<I>::value, "SpIndex type");
+        static_assert(sizeof(I) == 2 || sizeof(I) == 4 || sizeof(I) == 8, "I must be 2, 4 or 8 bytes");
+        if (indices.size() != data.size()) throw Error(SPRS_HIP_BAD_STRUCTURE, "indices and data do not have compatible lengths");
+        check(sprs_hip_csvec_upload(&h_, dim, indices.size(), indices.data(), (int32_t)sizeof(I), data.data(), validate ? 1 : 0));
+    }
+    explicit DeviceCsVec(sprs_hip_csvec *h) : h_(h) {}
+    DeviceCsVec(DeviceCsVec &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    DeviceCsVec(const DeviceCsVec &) = delete;
+    DeviceCsVec &operator=(const DeviceCsVec &) = delete;
+    ~DeviceCsVec() {
+        if (h_) sprs_hip_csvec_free(h_);
+    }
+
+    uint64_t dim() const { return info().dim; }      // vec.rs:681
+    uint64_t nnz() const { return info().nnz; }      // vec.rs:686
+    const sprs_hip_csvec *handle() const { return h_; }
+
+    // into_raw_storage (vec.rs:675) for 8-byte handles
+    void to_host(std::vector<uint64_t> &indices, std::vector<double> &data) const {
+        const Info i = info();
+        if (i.idx_bytes != 8) throw Error(SPRS_HIP_INVALID_ARG, "to_host: 64-bit handles only");
+        indices.resize(i.nnz);
+        data.resize(i.nnz);
+        check(sprs_hip_csvec_download(h_, indices.data(), data.data()));
+    }
+    // CsVec::to_dense (vec.rs:621)
+    DeviceVec to_dense(void *stream = nullptr) const {
+        DeviceVec out(dim());
+        check(sprs_hip_csvec_scatter_f64(h_, out.ptr(), out.dim(), stream));
+        return out;
+    }
+
+private:
+    struct Info {
+        uint64_t dim, nnz;
+        int32_t idx_bytes;
+    };
+    Info info() const {
+        Info i{};
+        check(sprs_hip_csvec_info(h_, &i.dim, &i.nnz, &i.idx_bytes));
+        return i;
+    }
+    sprs_hip_csvec *h_ = nullptr;
+};
+
+// `&CsMat * &CsVec` (vec.rs:1104-1131): csr_mul_csvec for CSR, structural for CSC; `&CsVec * &CsMat` (vec.rs:1084-1102)
+inline DeviceCsVec operator*(const DeviceCsMat &a, const DeviceCsVec &v) {
+    sprs_hip_csvec *c = nullptr;
+    check(sprs_hip_csmat_mul_csvec_f64(a.handle(), v.handle(), &c, nullptr));
+    return DeviceCsVec(c);
+}
+inline DeviceCsVec operator*(const DeviceCsVec &v, const DeviceCsMat &b) {
+    sprs_hip_csvec *c = nullptr;
+    check(sprs_hip_csvec_mul_csmat_f64(v.handle(), b.handle(), &c, nullptr));
+    return DeviceCsVec(c);
+}
+namespace prod {
+// prod::csr_mul_csvec (prod.rs:161-184)
+inline DeviceCsVec csr_mul_csvec(const DeviceCsMat &a, const DeviceCsVec &v) {
+    if (!a.is_csr()) throw Error(SPRS_HIP_STORAGE_MISMATCH, "Storage mismatch");
+    return a * v;
+}
+}  // namespace prod
+
 // TriMatI<f64, usize> (sparse/triplet.rs:26-48) with the device assembly of `to_csr` (triplet.rs:270-276 ->
 // triplet_iter.rs:127-224: rows sorted, duplicates summed).  No dedicated kernel: with n triplets the matrix
 // is the product R * E of R (rows x n, one 1 per column at the triplet's row) and E (n x cols, one value per

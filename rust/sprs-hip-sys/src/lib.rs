@@ -34,6 +34,11 @@ pub struct sprs_hip_csmat {
     _private: [u8; 0],
 }
 
+#[repr(C)]
+pub struct sprs_hip_csvec {
+    _private: [u8; 0],
+}
+
 /// counters of BiCGSTAB::solve (include/sprs_hip.h)
 #[repr(C)]
 #[derive(Debug, Clone, Copy, Default)]
@@ -158,6 +163,23 @@ extern "C" {
     pub fn sprs_hip_dist_route(d: *const sprs_hip_dist, route: *mut i32) -> i32;
     pub fn sprs_hip_dist_free(d: *mut sprs_hip_dist) -> i32;
     pub fn sprs_hip_csmat_mul_csmat(lhs: *const sprs_hip_csmat, rhs: *const sprs_hip_csmat, out: *mut *mut sprs_hip_csmat) -> i32;
+    pub fn sprs_hip_csvec_upload(
+        out: *mut *mut sprs_hip_csvec, dim: u64, nnz: u64, indices: *const c_void, idx_bytes: i32, data: *const f64, validate: i32,
+    ) -> i32;
+    pub fn sprs_hip_csvec_wrap_device(
+        out: *mut *mut sprs_hip_csvec, dim: u64, nnz: u64, dev_indices: *const c_void, idx_bytes: i32, dev_data: *const f64,
+    ) -> i32;
+    pub fn sprs_hip_csvec_info(v: *const sprs_hip_csvec, dim: *mut u64, nnz: *mut u64, idx_bytes: *mut i32) -> i32;
+    pub fn sprs_hip_csvec_device_ptrs(v: *const sprs_hip_csvec, indices: *mut *const c_void, data: *mut *const f64) -> i32;
+    pub fn sprs_hip_csvec_download(v: *const sprs_hip_csvec, indices: *mut c_void, data: *mut f64) -> i32;
+    pub fn sprs_hip_csvec_free(v: *mut sprs_hip_csvec) -> i32;
+    pub fn sprs_hip_csvec_scatter_f64(v: *const sprs_hip_csvec, out_dev: *mut f64, out_len: u64, stream: *mut c_void) -> i32;
+    pub fn sprs_hip_csmat_mul_csvec_f64(
+        a: *const sprs_hip_csmat, v: *const sprs_hip_csvec, out: *mut *mut sprs_hip_csvec, stream: *mut c_void,
+    ) -> i32;
+    pub fn sprs_hip_csvec_mul_csmat_f64(
+        v: *const sprs_hip_csvec, b: *const sprs_hip_csmat, out: *mut *mut sprs_hip_csvec, stream: *mut c_void,
+    ) -> i32;
     pub fn sprs_hip_triplets_to_cs(
         rows: u64, cols: u64, n: u64, row_inds_dev: *const c_void, col_inds_dev: *const c_void, in_idx_bytes: i32,
         data_dev: *const f64, storage: i32, out_idx_bytes: i32, out_iptr_bytes: i32, out: *mut *mut sprs_hip_csmat,

@@ -6,7 +6,7 @@
 //! `DenseVector` / `DenseVectorMut` are sealed in sprs (dense_vector.rs:305-326),
 //! so device buffers cannot be passed to `sprs::prod::*` itself; this crate
 //! offers twins with the same names, argument order and panics.
-use sprs::{CsMatI, CsMatViewI, SpIndex};
+use sprs::{CsMatI, CsMatViewI, CsVecI, CsVecViewI, SpIndex};
 use sprs_hip_sys as sys;
 use std::ffi::CStr;
 use std::os::raw::c_void;
@@ -453,5 +453,81 @@ impl<'a, 'b> std::ops::Mul<&'b DeviceCsMat> for &'a DeviceCsMat {
         let mut h: *mut sys::sprs_hip_csmat = std::ptr::null_mut();
         unsafe { check(sys::sprs_hip_csmat_mul_csmat(self.h, rhs.h, &mut h)) };
         DeviceCsMat { h }
+    }
+}
+
+/// Device twin of `CsVecI<f64, I>` (sprs/src/sparse.rs:165-173).
+pub struct DeviceCsVec {
+    h: *mut sys::sprs_hip_csvec,
+}
+
+unsafe impl Send for DeviceCsVec {}
+unsafe impl Sync for DeviceCsVec {}
+
+impl DeviceCsVec {
+    /// Upload a host sparse vector (any `SpIndex` type of 2, 4 or 8 bytes; its invariants were checked by CsVec::new).
+    pub fn from_view<I: SpIndex>(v: CsVecViewI<f64, I>) -> Self {
+        let mut h = std::ptr::null_mut();
+        unsafe {
+            check(sys::sprs_hip_csvec_upload(
+                &mut h,
+                v.dim() as u64,
+                v.nnz() as u64,
+                v.indices().as_ptr() as *const c_void,
+                std::mem::size_of::<I>() as i32,
+                v.data().as_ptr(),
+                0,
+            ));
+        }
+        Self { h }
+    }
+
+    pub fn dim(&self) -> usize {
+        let mut d = 0u64;
+        unsafe { check(sys::sprs_hip_csvec_info(self.h, &mut d, std::ptr::null_mut(), std::ptr::null_mut())) };
+        d as usize
+    }
+
+    pub fn nnz(&self) -> usize {
+        let mut n = 0u64;
+        unsafe { check(sys::sprs_hip_csvec_info(self.h, std::ptr::null_mut(), &mut n, std::ptr::null_mut())) };
+        n as usize
+    }
+
+    /// Download into a host `CsVecI<f64, I>` (I of the width the vector was made with).
+    pub fn to_host<I: SpIndex>(&self) -> CsVecI<f64, I> {
+        let (mut d, mut n, mut ib) = (0u64, 0u64, 0i32);
+        unsafe { check(sys::sprs_hip_csvec_info(self.h, &mut d, &mut n, &mut ib)) };
+        assert_eq!(ib as usize, std::mem::size_of::<I>(), "index width of the device vector");
+        let mut indices = vec![I::zero(); n as usize];
+        let mut data = vec![0.0f64; n as usize];
+        unsafe { check(sys::sprs_hip_csvec_download(self.h, indices.as_mut_ptr() as *mut c_void, data.as_mut_ptr())) };
+        CsVecI::new(d as usize, indices, data)
+    }
+}
+
+impl Drop for DeviceCsVec {
+    fn drop(&mut self) {
+        unsafe { sys::sprs_hip_csvec_free(self.h) };
+    }
+}
+
+/// `&A * &v` (vec.rs:1104-1131): prod::csr_mul_csvec for CSR, `A * v.col_view()` for CSC — dispatched below the C ABI.
+impl<'a, 'b> std::ops::Mul<&'b DeviceCsVec> for &'a DeviceCsMat {
+    type Output = DeviceCsVec;
+    fn mul(self, rhs: &'b DeviceCsVec) -> DeviceCsVec {
+        let mut h: *mut sys::sprs_hip_csvec = std::ptr::null_mut();
+        unsafe { check(sys::sprs_hip_csmat_mul_csvec_f64(self.h, rhs.h, &mut h, std::ptr::null_mut())) };
+        DeviceCsVec { h }
+    }
+}
+
+/// `&v * &B` (vec.rs:1084-1102): `(v.row_view() * B).outer_view(0)`.
+impl<'a, 'b> std::ops::Mul<&'b DeviceCsMat> for &'a DeviceCsVec {
+    type Output = DeviceCsVec;
+    fn mul(self, rhs: &'b DeviceCsMat) -> DeviceCsVec {
+        let mut h: *mut sys::sprs_hip_csvec = std::ptr::null_mut();
+        unsafe { check(sys::sprs_hip_csvec_mul_csmat_f64(self.h, rhs.h, &mut h, std::ptr::null_mut())) };
+        DeviceCsVec { h }
     }
 }

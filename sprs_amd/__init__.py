@@ -7,7 +7,7 @@ the shared library is absent; nothing here computes on the CPU.
 """
 from . import _ffi
 from ._ffi import CSC, CSR, SprsHipError
-from .device import DeviceCsMat, DeviceVec
+from .device import DeviceCsMat, DeviceCsVec, DeviceVec
 from . import prod, smmp
 
 

@@ -86,6 +86,15 @@ SIGNATURES = {
     "sprs_hip_dist_free": (i32, [vp]),
     "sprs_hip_csmat_mul_csmat": (i32, [vp, vp, P(vp)]),
     "sprs_hip_triplets_to_cs": (i32, [u64, u64, u64, vp, vp, i32, vp, i32, i32, i32, P(vp)]),
+    "sprs_hip_csvec_upload": (i32, [P(vp), u64, u64, vp, i32, vp, i32]),
+    "sprs_hip_csvec_wrap_device": (i32, [P(vp), u64, u64, vp, i32, vp]),
+    "sprs_hip_csvec_info": (i32, [vp, P(u64), P(u64), P(i32)]),
+    "sprs_hip_csvec_device_ptrs": (i32, [vp, P(vp), P(vp)]),
+    "sprs_hip_csvec_download": (i32, [vp, vp, vp]),
+    "sprs_hip_csvec_free": (i32, [vp]),
+    "sprs_hip_csvec_scatter_f64": (i32, [vp, vp, u64, vp]),
+    "sprs_hip_csmat_mul_csvec_f64": (i32, [vp, vp, P(vp), vp]),
+    "sprs_hip_csvec_mul_csmat_f64": (i32, [vp, vp, P(vp), vp]),
     "sprs_hip_set_option": (i32, [C.c_char_p, i64]),
     "sprs_hip_get_option": (i32, [C.c_char_p, P(i64)]),
 }

@@ -545,6 +545,7 @@ static void invalidate_caches(sprs_hip_csmat *m) {
     m->plan.release();
     m->mm.release();
     m->gs.release();
+    m->cv.release();
     if (m->t_view) (void)sprs_hip_csmat_free(m->t_view);
     m->t_view = nullptr;
     if (m->as_other) (void)sprs_hip_csmat_free(m->as_other);
@@ -612,7 +613,7 @@ int32_t sprs_hip_csmat_free(sprs_hip_csmat *m) {
     if (!m) return SPRS_HIP_OK;
     // a kernel launched through a cached copy (as_other, t_view) or a plan copy may still be reading it: a handle that holds
     // any of them waits for the device before they go (refresh does the same; a bare handle frees at once)
-    if (m->t_view || m->as_other || m->plan.built) (void)hipDeviceSynchronize();
+    if (m->t_view || m->as_other || m->plan.built || m->cv.bits) (void)hipDeviceSynchronize();
     invalidate_caches(m);
     if (m->owns) {
         pool_free(m->indptr, m->cap_indptr, m->device);
@@ -1175,6 +1176,186 @@ int32_t sprs_hip_get_option(const char *name, int64_t *value) {
     if (!d) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "unknown option '%s'", name);
     *value = options().*(d->field);
     return SPRS_HIP_OK;
+}
+
+}  // extern "C"
+
+// ---- device sparse vectors (CsVecBase, sparse.rs:165-173) and their products; kernels in csvec.hpp --------------------------
+
+// CsVec::try_new (vec.rs:440-491) on host indices: sorted_indices (sparse.rs:360-369), then the last index against dim
+template <typename I>
+static int32_t check_csvec_host(uint64_t dim, uint64_t nnz, const I *idx) {
+    for (uint64_t i = 1; i < nnz; ++i)
+        if (idx[i] <= idx[i - 1]) SPRS_FAIL(SPRS_HIP_BAD_STRUCTURE, "Unsorted indices");
+    if (nnz && (uint64_t)idx[nnz - 1] >= dim) SPRS_FAIL(SPRS_HIP_BAD_STRUCTURE, "indices larger than vector size");
+    return SPRS_HIP_OK;
+}
+
+// vectors up to this many entries are validated on the host; longer ones by csvec_check_kernel after the upload
+static constexpr uint64_t CSVEC_HOST_CHECK_MAX = 1ull << 16;
+
+extern "C" {
+
+int32_t sprs_hip_csvec_upload(sprs_hip_csvec **out, uint64_t dim, uint64_t nnz, const void *indices, int32_t idx_bytes,
+                              const double *data, int32_t validate) {
+    clear_error();
+    if (!out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    if (idx_bytes != 2 && idx_bytes != 4 && idx_bytes != 8) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "index widths must be 2, 4 or 8 bytes");
+    if (nnz && (!indices || !data)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL indices/data with nnz > 0");
+    if (validate) {
+        // I::from(n) (vec.rs:446-451): the dimension itself must be representable
+        if (dim > width_max(idx_bytes)) SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "Index size is too small");
+        if (nnz <= CSVEC_HOST_CHECK_MAX) {
+            int32_t st = SPRS_HIP_OK;
+            if (idx_bytes == 2) st = check_csvec_host(dim, nnz, (const uint16_t *)indices);
+            else if (idx_bytes == 4) st = check_csvec_host(dim, nnz, (const uint32_t *)indices);
+            else st = check_csvec_host(dim, nnz, (const uint64_t *)indices);
+            SPRS_TRY(st);
+        }
+    }
+    std::vector<uint32_t> wide;
+    const void *src = indices;
+    const int32_t dev_bytes = idx_bytes == 2 ? 4 : idx_bytes;
+    if (idx_bytes == 2) {                       // u16 / i16 (indexing.rs:124-130): widened to 4 bytes for the device
+        wide.resize(nnz ? nnz : 1);
+        for (uint64_t i = 0; i < nnz; ++i) wide[i] = ((const uint16_t *)indices)[i];
+        src = wide.data();
+    }
+    sprs_hip_csvec *v = nullptr;
+    SPRS_TRY(csvec_alloc(&v, dim, nnz, dev_bytes, idx_bytes));
+    hipError_t e = hipSuccess;
+    if (nnz) e = hipMemcpy(v->indices, src, nnz * (uint64_t)dev_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && nnz) e = hipMemcpy(v->data, data, nnz * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        csvec_release(v);
+        return fail_hip(e, "csvec_upload");
+    }
+    if (validate && nnz > CSVEC_HOST_CHECK_MAX) {
+        const int32_t st = csvec_check_device(v, nullptr);
+        if (st != SPRS_HIP_OK) {
+            const std::string keep = tl_msg;
+            csvec_release(v);
+            set_error(st, "%s", keep.c_str());
+            return st;
+        }
+    }
+    *out = v;
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_csvec_wrap_device(sprs_hip_csvec **out, uint64_t dim, uint64_t nnz, const void *dev_indices, int32_t idx_bytes,
+                                   const double *dev_data) {
+    clear_error();
+    if (!out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    if (idx_bytes != 4 && idx_bytes != 8) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "index widths must be 4 or 8 bytes");
+    if (nnz && (!dev_indices || !dev_data)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL indices/data with nnz > 0");
+    if (((uintptr_t)dev_indices % (uintptr_t)idx_bytes) | ((uintptr_t)dev_data & 7))
+        SPRS_FAIL(SPRS_HIP_INVALID_ARG, "device buffers must be aligned to their element size");
+    auto *v = new sprs_hip_csvec();
+    v->dim = dim;
+    v->nnz = nnz;
+    v->idx_bytes = idx_bytes;
+    v->indices = const_cast<void *>(dev_indices);
+    v->data = const_cast<double *>(dev_data);
+    v->owns = false;
+    hipError_t e = hipGetDevice(&v->device);
+    if (e != hipSuccess) {
+        delete v;
+        return fail_hip(e, "hipGetDevice");
+    }
+    *out = v;
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_csvec_info(const sprs_hip_csvec *v, uint64_t *dim, uint64_t *nnz, int32_t *idx_bytes) {
+    clear_error();
+    if (!v) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if (dim) *dim = v->dim;
+    if (nnz) *nnz = v->nnz;
+    if (idx_bytes) *idx_bytes = v->user_idx_bytes();
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_csvec_device_ptrs(const sprs_hip_csvec *v, const void **indices, const double **data) {
+    clear_error();
+    if (!v) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if (indices) *indices = v->indices;
+    if (data) *data = v->data;
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_csvec_download(const sprs_hip_csvec *v, void *indices, double *data) {
+    clear_error();
+    if (!v) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if (indices && v->nnz) {
+        if (v->user_idx_bytes() == v->idx_bytes) {
+            SPRS_TRY_HIP(hipMemcpy(indices, v->indices, v->nnz * (uint64_t)v->idx_bytes, hipMemcpyDeviceToHost));
+        } else {                                // declared 2 bytes, device 4: narrow (results were range-checked when made)
+            std::vector<uint32_t> wide(v->nnz);
+            SPRS_TRY_HIP(hipMemcpy(wide.data(), v->indices, v->nnz * 4, hipMemcpyDeviceToHost));
+            for (uint64_t i = 0; i < v->nnz; ++i) {
+                if (wide[i] > 0xFFFFu) SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "Index type is not large enough to hold %u", wide[i]);
+                ((uint16_t *)indices)[i] = (uint16_t)wide[i];
+            }
+        }
+    }
+    if (data && v->nnz) SPRS_TRY_HIP(hipMemcpy(data, v->data, v->nnz * sizeof(double), hipMemcpyDeviceToHost));
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_csvec_free(sprs_hip_csvec *v) {
+    clear_error();
+    csvec_release(v);
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_csvec_scatter_f64(const sprs_hip_csvec *v, double *out_dev, uint64_t out_len, void *stream) {
+    clear_error();
+    if (!v) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if (out_len != v->dim) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    if (out_len && !out_dev) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL vector");
+    return csvec_scatter(v, out_dev, (hipStream_t)stream);
+}
+
+// an empty result of dimension `dim` (no kernel)
+static int32_t empty_csvec(sprs_hip_csvec **out, uint64_t dim, const sprs_hip_csmat *like) {
+    return csvec_alloc(out, dim, 0, like->idx_bytes, like->user_idx_bytes());
+}
+
+int32_t sprs_hip_csmat_mul_csvec_f64(const sprs_hip_csmat *a, const sprs_hip_csvec *v, sprs_hip_csvec **out, void *stream) {
+    clear_error();
+    if (!a || !v || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    if (a->storage == SPRS_HIP_CSR) {
+        if (v->dim == 0) return empty_csvec(out, 0, a);               // CsVecI::empty(0) (prod.rs:171-174)
+        if (a->cols != v->dim) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");   // prod.rs:175
+        return csvec_masked_dot(a, v, true, a->idx_bytes, a->user_idx_bytes(), out, (hipStream_t)stream);
+    }
+    // CSC: a * v.col_view() (vec.rs:1127-1129) -> csmat_mul_csmat, structural, on the CSR form of a
+    if (a->cols != v->dim) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    if (a->rows == 0 || v->nnz == 0 || a->nnz == 0) return empty_csvec(out, a->rows, a);
+    sprs_hip_csmat *csr = nullptr;
+    SPRS_TRY(other_form(a, &csr));
+    return csvec_masked_dot(csr, v, false, a->idx_bytes, a->user_idx_bytes(), out, (hipStream_t)stream);
+}
+
+int32_t sprs_hip_csvec_mul_csmat_f64(const sprs_hip_csvec *v, const sprs_hip_csmat *b, sprs_hip_csvec **out, void *stream) {
+    clear_error();
+    if (!v || !b || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    // (v.row_view() * b).outer_view(0) (vec.rs:1098-1100): mul_csr_csr asserts lhs.cols == rhs.rows
+    if (v->dim != b->rows) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    if (b->cols == 0 || v->nnz == 0 || b->nnz == 0) return empty_csvec(out, b->cols, b);
+    // entry o is the ordered dot of COLUMN o of b with v: b itself when CSC, its CSC form when CSR
+    const sprs_hip_csmat *csc = b;
+    if (b->storage == SPRS_HIP_CSR) {
+        sprs_hip_csmat *c = nullptr;
+        SPRS_TRY(other_form(b, &c));
+        csc = c;
+    }
+    return csvec_masked_dot(csc, v, false, b->idx_bytes, b->user_idx_bytes(), out, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -185,7 +185,30 @@ struct GsPlan {
     void release();
 };
 
+// ---- sparse-vector products: per-handle temporaries (csvec.hpp) ------------------------------------
+struct CsvecScratch {
+    uint32_t *bits = nullptr;          // device, ceil(n / 32): presence bitmap of v's indices
+    double *vals = nullptr;            // device, n: v's values at their indices (read only where the bit is set; never cleared)
+    double *sums = nullptr;            // device, outer: the dot of every kept outer slice
+    uint64_t *groups = nullptr;        // device: keep masks (ngroups) | counts (ngroups) | offsets (ngroups + 1) | overflow flag
+    uint64_t n = 0, nouter = 0;
+    void release();
+};
+
 }  // namespace sprs_hip
+
+// Device twin of CsVecBase (sprs/src/sparse.rs:165-173): dim, sorted indices, data.
+struct sprs_hip_csvec {
+    uint64_t dim = 0, nnz = 0;
+    int32_t idx_bytes = 8;             // width of the device indices (4 or 8)
+    int32_t decl_idx_bytes = 0;        // width the caller declared when it differs (2: widened to 4 on upload, narrowed on download)
+    int32_t user_idx_bytes() const { return decl_idx_bytes ? decl_idx_bytes : idx_bytes; }
+    void *indices = nullptr;           // device, nnz entries, strictly increasing
+    double *data = nullptr;            // device, nnz entries
+    bool owns = false;
+    uint64_t cap_indices = 0, cap_data = 0;
+    int device = 0;
+};
 
 // Device twin of CsMatBase (sprs/src/sparse.rs:94-122).
 struct sprs_hip_csmat {
@@ -211,6 +234,7 @@ struct sprs_hip_csmat {
     sprs_hip::SpmvPlan plan;
     sprs_hip::SpmmPlan mm;
     sprs_hip::GsPlan gs;
+    sprs_hip::CsvecScratch cv;           // temporaries of the sparse-vector products that run on this handle (csvec.hpp)
     sprs_hip_csmat *t_view = nullptr;    // transpose view (of the CSC form) kept for dense . sparse products (sprs_hip_dense_dot_csmat_f64): its SpMM / SpMV plans live as long as the values do; dropped with as_other
     sprs_hip_csmat *as_other = nullptr;  // the handle in the OTHER storage order (to_other_storage, csmat.rs:1405-1426): made by the first product that needs it (a CSC operand of a dense product / SpMV runs on its CSR form), dropped by refresh / free
 
@@ -275,6 +299,13 @@ int32_t bicgstab_f64(sprs_hip_csmat *a, const double *x0, const double *b, uint6
 int32_t gauss_seidel_f64(sprs_hip_csmat *a, double *x, const double *rhs, uint64_t n, uint64_t max_iter, double eps,
                          sprs_hip_gauss_seidel_info *info, hipStream_t stream);
 int32_t slice_outer(const sprs_hip_csmat *m, uint64_t start, uint64_t end, sprs_hip_csmat **out);
+// csvec.hpp (compiled in spmv.hip)
+int32_t csvec_alloc(sprs_hip_csvec **out, uint64_t dim, uint64_t nnz, int32_t idx_bytes, int32_t decl_idx_bytes);
+void csvec_release(sprs_hip_csvec *v);
+int32_t csvec_check_device(const sprs_hip_csvec *v, hipStream_t stream);
+int32_t csvec_scatter(const sprs_hip_csvec *v, double *out, hipStream_t stream);
+int32_t csvec_masked_dot(const sprs_hip_csmat *m, const sprs_hip_csvec *v, bool drop_zero, int32_t idx_bytes, int32_t decl_bytes,
+                         sprs_hip_csvec **out, hipStream_t stream);
 // abi.hip
 int32_t alloc_csmat(sprs_hip_csmat **out, int32_t storage, uint64_t rows, uint64_t cols, uint64_t nnz,
                     int32_t iptr_bytes, int32_t idx_bytes);

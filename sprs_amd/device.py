@@ -194,6 +194,8 @@ class DeviceCsMat:
     # -- operators: `&A * &x`, `&A * &B` ---------------------------------------
     def __mul__(self, rhs):
         from . import prod
+        if isinstance(rhs, DeviceCsVec):
+            return prod.csmat_mul_csvec(self, rhs)        # vec.rs:1104-1131
         if isinstance(rhs, DeviceVec):
             return prod.csmat_mul_vec(self, rhs)          # csmat.rs:2119-2160
         if isinstance(rhs, DeviceCsMat):
@@ -208,4 +210,85 @@ class DeviceCsMat:
         h = getattr(self, "_h", None)
         if h is not None and h.value:
             lib.sprs_hip_csmat_free(h)
+            self._h = C.c_void_p(0)
+
+
+def _stream_arg(stream):
+    if stream is None:
+        return None
+    return C.c_void_p(int(getattr(stream, "cuda_stream", stream)))
+
+
+class DeviceCsVec:
+    """A sparse vector whose indices / data live in HBM behind a `sprs_hip_csvec*` handle: twin of CsVecBase
+    (sprs/src/sparse.rs:165-173).  `mat * vec` and `vec * mat` with a DeviceCsMat are the products of vec.rs:1084-1131."""
+
+    def __init__(self, handle, keep=None):
+        self._h = C.c_void_p(handle)
+        self._keep = keep   # objects the handle borrows from
+
+    @classmethod
+    def from_host(cls, dim, indices, data, validate=True):
+        """CsVec::new (vec.rs:430-434) when validate, new_trusted otherwise; indices of 2, 4 or 8 bytes."""
+        indices = np.ascontiguousarray(indices)
+        data = np.ascontiguousarray(data, dtype=np.float64)
+        if indices.dtype.kind not in "iu":
+            raise TypeError("integer index array expected")
+        if indices.size != data.size:    # vec.rs:452-459
+            raise _ffi.SprsHipError(_ffi.BAD_STRUCTURE, "indices and data do not have compatible lengths")
+        h = C.c_void_p()
+        check(lib.sprs_hip_csvec_upload(C.byref(h), int(dim), indices.size, _vp(indices), indices.dtype.itemsize, _vp(data),
+                                        1 if validate else 0))
+        return cls(h.value)
+
+    @classmethod
+    def borrow(cls, dim, indices_t, data_t):
+        """Borrow two contiguous torch CUDA tensors (int32 / int64 indices, float64 data) without a copy (new_trusted)."""
+        assert indices_t.is_cuda and data_t.is_cuda and indices_t.is_contiguous() and data_t.is_contiguous()
+        assert data_t.element_size() == 8 and indices_t.numel() == data_t.numel()
+        h = C.c_void_p()
+        check(lib.sprs_hip_csvec_wrap_device(C.byref(h), int(dim), indices_t.numel(),
+                                             C.c_void_p(indices_t.data_ptr() if indices_t.numel() else 0),
+                                             indices_t.element_size(), C.c_void_p(data_t.data_ptr() if data_t.numel() else 0)))
+        return cls(h.value, keep=(indices_t, data_t))
+
+    def _info(self):
+        d, n, ib = C.c_uint64(), C.c_uint64(), C.c_int32()
+        check(lib.sprs_hip_csvec_info(self._h, C.byref(d), C.byref(n), C.byref(ib)))
+        return d.value, n.value, ib.value
+
+    def dim(self): return self._info()[0]          # vec.rs:681
+    def nnz(self): return self._info()[1]          # vec.rs:686
+    def index_bytes(self): return self._info()[2]
+
+    def to_host(self):
+        """-> (dim, indices, data) numpy arrays (into_raw_storage, vec.rs:675)."""
+        dim, n, ib = self._info()
+        indices = np.empty(n, dtype=_DT[ib])
+        data = np.empty(n, dtype=np.float64)
+        check(lib.sprs_hip_synchronize(None))
+        check(lib.sprs_hip_csvec_download(self._h, _vp(indices), _vp(data)))
+        return dim, indices, data
+
+    def scatter(self, out, stream=None):
+        """CsVec::scatter (vec.rs:965) into a DeviceVec of length dim: zeros, then the stored values."""
+        check(lib.sprs_hip_csvec_scatter_f64(self._h, C.c_void_p(out.ptr), out.n, _stream_arg(stream)))
+        return out
+
+    def to_dense(self, stream=None):
+        """CsVec::to_dense (vec.rs:621) as a DeviceVec."""
+        return self.scatter(DeviceVec(self.dim()), stream)
+
+    def __mul__(self, rhs):
+        from . import prod
+        if isinstance(rhs, DeviceCsMat):
+            return prod.csvec_mul_csmat(self, rhs)        # vec.rs:1084-1102
+        return NotImplemented
+
+    __matmul__ = __mul__
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            lib.sprs_hip_csvec_free(h)
             self._h = C.c_void_p(0)

@@ -5,7 +5,7 @@ import ctypes as C
 
 from . import _ffi
 from ._ffi import CSC, CSR, check, lib
-from .device import DeviceCsMat, DeviceVec
+from .device import DeviceCsMat, DeviceCsVec, DeviceVec
 
 
 def _stream_ptr(stream):
@@ -158,3 +158,27 @@ def csmat_mul_csmat(lhs, rhs):
     h = C.c_void_p()
     check(lib.sprs_hip_csmat_mul_csmat(lhs._h, rhs._h, C.byref(h)))
     return DeviceCsMat(h.value)
+
+
+def csr_mul_csvec(mat, vec, stream=None):
+    """prod::csr_mul_csvec (prod.rs:161-184): CSR x sparse vector; an entry is kept only where its value is != 0.  A vector of
+    dimension 0 gives an empty vector of dimension 0.  A CSC matrix raises "Storage mismatch" (the reference takes a CSR view)."""
+    if mat.is_csc():
+        raise _ffi.SprsHipError(_ffi.STORAGE_MISMATCH, "Storage mismatch")
+    return csmat_mul_csvec(mat, vec, stream)
+
+
+def csmat_mul_csvec(mat, vec, stream=None):
+    """`&CsMat * &CsVec` (vec.rs:1104-1131): csr_mul_csvec for CSR, `mat * vec.col_view()` (structural) for CSC — one call below
+    the C ABI (sprs_hip_csmat_mul_csvec_f64), which returns once the result is complete on `stream`."""
+    h = C.c_void_p()
+    check(lib.sprs_hip_csmat_mul_csvec_f64(mat._h, vec._h, C.byref(h), _stream_ptr(stream)))
+    return DeviceCsVec(h.value)
+
+
+def csvec_mul_csmat(vec, mat, stream=None):
+    """`&CsVec * &CsMat` (vec.rs:1084-1102): `(vec.row_view() * mat).outer_view(0)`, structural, below the C ABI
+    (sprs_hip_csvec_mul_csmat_f64)."""
+    h = C.c_void_p()
+    check(lib.sprs_hip_csvec_mul_csmat_f64(vec._h, mat._h, C.byref(h), _stream_ptr(stream)))
+    return DeviceCsVec(h.value)
