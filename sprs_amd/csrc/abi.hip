@@ -236,6 +236,29 @@ static bool host_widths_ok(int32_t iptr_bytes, int32_t idx_bytes) {     // what 
 
 static uint64_t width_max(int32_t bytes) { return bytes >= 8 ? ~0ull : ((1ull << (8 * bytes)) - 1ull); }
 
+// 2-byte host indices (u16 / i16, indexing.rs:124-130) widened to the 4 bytes the device holds
+static std::vector<uint32_t> widen16(const void *src, uint64_t count) {
+    std::vector<uint32_t> wide(count);
+    for (uint64_t i = 0; i < count; ++i) wide[i] = ((const uint16_t *)src)[i];
+    return wide;
+}
+
+// count device indices to the host at the width the caller declared: a declared 2-byte array lives as 4 bytes on the device
+// and is narrowed here (every value was range-checked when it was made)
+static int32_t download_indices(void *dst, const void *src, uint64_t count, int32_t dev_bytes, int32_t user_bytes) {
+    if (user_bytes == dev_bytes) {
+        SPRS_TRY_HIP(copy_to_host(dst, src, count * (uint64_t)dev_bytes, nullptr));
+        return SPRS_HIP_OK;
+    }
+    std::vector<uint32_t> wide(count);
+    SPRS_TRY_HIP(copy_to_host(wide.data(), src, count * 4, nullptr));
+    for (uint64_t i = 0; i < count; ++i) {
+        if (wide[i] > 0xFFFFu) SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "Index type is not large enough to hold %u", wide[i]);
+        ((uint16_t *)dst)[i] = (uint16_t)wide[i];
+    }
+    return SPRS_HIP_OK;
+}
+
 int32_t inherit_declared_widths(sprs_hip_csmat *result, const sprs_hip_csmat *from) {
     result->decl_idx_bytes = from->decl_idx_bytes;
     result->decl_iptr_bytes = from->decl_iptr_bytes;
@@ -305,13 +328,13 @@ int32_t sprs_hip_free(void *dev_ptr) {
 
 int32_t sprs_hip_memcpy_h2d(void *dev_dst, const void *host_src, uint64_t bytes) {
     clear_error();
-    if (bytes) SPRS_TRY_HIP(hipMemcpy(dev_dst, host_src, bytes, hipMemcpyHostToDevice));
+    if (bytes) SPRS_TRY_HIP(copy_to_device(dev_dst, host_src, bytes, nullptr));
     return SPRS_HIP_OK;
 }
 
 int32_t sprs_hip_memcpy_d2h(void *host_dst, const void *dev_src, uint64_t bytes) {
     clear_error();
-    if (bytes) SPRS_TRY_HIP(hipMemcpy(host_dst, dev_src, bytes, hipMemcpyDeviceToHost));
+    if (bytes) SPRS_TRY_HIP(copy_to_host(host_dst, dev_src, bytes, nullptr));
     return SPRS_HIP_OK;
 }
 
@@ -360,23 +383,12 @@ int32_t sprs_hip_csmat_upload(sprs_hip_csmat **out, int32_t storage, uint64_t ro
         if (nnz16 && (!indices || !data)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL indices/data with nnz > 0");   // before the widening loop reads them
         if (inner && inner - 1 > width_max(idx_bytes)) SPRS_FAIL(SPRS_HIP_BAD_STRUCTURE, "Index type not large enough for this matrix");
         // (a 2-byte indptr cannot hold a count above its own range: nothing to check for Iptr on the way in)
-        std::vector<uint32_t> ip32, ix32;
-        const void *ipp = indptr, *ixp = indices;
-        int32_t ipb = iptr_bytes, ixb = idx_bytes;
-        if (iptr_bytes == 2) {
-            ip32.resize(outer + 1);
-            for (uint64_t i = 0; i <= outer; ++i) ip32[i] = ((const uint16_t *)indptr)[i];
-            ipp = ip32.data();
-            ipb = 4;
-        }
-        if (idx_bytes == 2) {
-            ix32.resize(nnz16 ? nnz16 : 1);
-            const uint16_t *src = (const uint16_t *)indices;   // points at the element addressed by indptr[0]
-            for (uint64_t i = 0; i < nnz16; ++i) ix32[i] = src[i];
-            ixp = nnz16 ? ix32.data() : indices;
-            ixb = 4;
-        }
-        SPRS_TRY(sprs_hip_csmat_upload(out, storage, rows, cols, ipp, ipb, ixp, ixb, data, validate));
+        // (indices points at the element addressed by indptr[0])
+        const std::vector<uint32_t> ip32 = iptr_bytes == 2 ? widen16(indptr, outer + 1) : std::vector<uint32_t>();
+        const std::vector<uint32_t> ix32 = idx_bytes == 2 ? widen16(indices, nnz16) : std::vector<uint32_t>();
+        const void *ipp = iptr_bytes == 2 ? ip32.data() : indptr, *ixp = idx_bytes == 2 && nnz16 ? ix32.data() : indices;
+        SPRS_TRY(sprs_hip_csmat_upload(out, storage, rows, cols, ipp, iptr_bytes == 2 ? 4 : iptr_bytes, ixp, idx_bytes == 2 ? 4 : idx_bytes,
+                                       data, validate));
         (*out)->decl_iptr_bytes = iptr_bytes;
         (*out)->decl_idx_bytes = idx_bytes;
         return SPRS_HIP_OK;
@@ -400,7 +412,7 @@ int32_t sprs_hip_csmat_upload(sprs_hip_csmat **out, int32_t storage, uint64_t ro
     SPRS_TRY(alloc_csmat(&m, storage, rows, cols, nnz, iptr_bytes, idx_bytes));
     hipError_t e = hipSuccess;
     if (first == 0) {
-        e = hipMemcpy(m->indptr, indptr, (outer + 1) * (uint64_t)iptr_bytes, hipMemcpyHostToDevice);
+        e = copy_to_device(m->indptr, indptr, (outer + 1) * (uint64_t)iptr_bytes, nullptr);
     } else {
         // to_proper (sprs/src/sparse/indptr.rs:206-214): rebase on the way in
         std::vector<uint8_t> tmp((outer + 1) * (size_t)iptr_bytes);
@@ -408,10 +420,10 @@ int32_t sprs_hip_csmat_upload(sprs_hip_csmat **out, int32_t storage, uint64_t ro
             if (iptr_bytes == 8) ((uint64_t *)tmp.data())[i] = ip_at(i) - first;
             else ((uint32_t *)tmp.data())[i] = (uint32_t)(ip_at(i) - first);
         }
-        e = hipMemcpy(m->indptr, tmp.data(), tmp.size(), hipMemcpyHostToDevice);
+        e = copy_to_device(m->indptr, tmp.data(), tmp.size(), nullptr);
     }
-    if (e == hipSuccess && nnz) e = hipMemcpy(m->indices, indices, nnz * (uint64_t)idx_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess && nnz) e = hipMemcpy(m->data, data, nnz * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess && nnz) e = copy_to_device(m->indices, indices, nnz * (uint64_t)idx_bytes, nullptr);
+    if (e == hipSuccess && nnz) e = copy_to_device(m->data, data, nnz * sizeof(double), nullptr);
     if (e != hipSuccess) {
         sprs_hip_csmat_free(m);
         return fail_hip(e, "csmat_upload");
@@ -478,22 +490,9 @@ int32_t sprs_hip_csmat_device_ptrs(const sprs_hip_csmat *m, const void **indptr,
 int32_t sprs_hip_csmat_download(const sprs_hip_csmat *m, void *indptr, void *indices, double *data) {
     clear_error();
     if (!m) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
-    auto fetch = [&](void *dst, const void *src, uint64_t count, int32_t dev_bytes, int32_t user_bytes) -> int32_t {
-        if (user_bytes == dev_bytes) {
-            SPRS_TRY_HIP(hipMemcpy(dst, src, count * (uint64_t)dev_bytes, hipMemcpyDeviceToHost));
-            return SPRS_HIP_OK;
-        }
-        std::vector<uint32_t> wide(count ? count : 1);          // declared 2 bytes, device 4: narrow (every value was range-checked when made)
-        SPRS_TRY_HIP(hipMemcpy(wide.data(), src, count * 4, hipMemcpyDeviceToHost));
-        for (uint64_t i = 0; i < count; ++i) {
-            if (wide[i] > 0xFFFFu) SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "Index type is not large enough to hold %u", wide[i]);
-            ((uint16_t *)dst)[i] = (uint16_t)wide[i];
-        }
-        return SPRS_HIP_OK;
-    };
-    if (indptr) SPRS_TRY(fetch(indptr, m->indptr, m->outer() + 1, m->iptr_bytes, m->user_iptr_bytes()));
-    if (indices && m->nnz) SPRS_TRY(fetch(indices, m->indices, m->nnz, m->idx_bytes, m->user_idx_bytes()));
-    if (data && m->nnz) SPRS_TRY_HIP(hipMemcpy(data, m->data, m->nnz * sizeof(double), hipMemcpyDeviceToHost));
+    if (indptr) SPRS_TRY(download_indices(indptr, m->indptr, m->outer() + 1, m->iptr_bytes, m->user_iptr_bytes()));
+    if (indices && m->nnz) SPRS_TRY(download_indices(indices, m->indices, m->nnz, m->idx_bytes, m->user_idx_bytes()));
+    if (data && m->nnz) SPRS_TRY_HIP(copy_to_host(data, m->data, m->nnz * sizeof(double), nullptr));
     return SPRS_HIP_OK;
 }
 
@@ -507,33 +506,20 @@ int32_t sprs_hip_csmat_download_outer(const sprs_hip_csmat *m, uint64_t start, u
     uint64_t lo = 0, hi = 0;
     const uint64_t pb = (uint64_t)m->iptr_bytes;
     if (pb == 8) {
-        SPRS_TRY_HIP(hipMemcpy(&lo, (const uint8_t *)m->indptr + start * pb, 8, hipMemcpyDeviceToHost));
-        SPRS_TRY_HIP(hipMemcpy(&hi, (const uint8_t *)m->indptr + end * pb, 8, hipMemcpyDeviceToHost));
+        SPRS_TRY_HIP(copy_to_host(&lo, (const uint8_t *)m->indptr + start * pb, 8, nullptr));
+        SPRS_TRY_HIP(copy_to_host(&hi, (const uint8_t *)m->indptr + end * pb, 8, nullptr));
     } else {
         uint32_t a = 0, b = 0;
-        SPRS_TRY_HIP(hipMemcpy(&a, (const uint8_t *)m->indptr + start * pb, 4, hipMemcpyDeviceToHost));
-        SPRS_TRY_HIP(hipMemcpy(&b, (const uint8_t *)m->indptr + end * pb, 4, hipMemcpyDeviceToHost));
+        SPRS_TRY_HIP(copy_to_host(&a, (const uint8_t *)m->indptr + start * pb, 4, nullptr));
+        SPRS_TRY_HIP(copy_to_host(&b, (const uint8_t *)m->indptr + end * pb, 4, nullptr));
         lo = a;
         hi = b;
     }
     if (nnz_out) *nnz_out = hi - lo;
-    auto fetch = [&](void *dst, const void *src, uint64_t count, int32_t dev_bytes, int32_t user_bytes) -> int32_t {
-        if (user_bytes == dev_bytes) {
-            SPRS_TRY_HIP(hipMemcpy(dst, src, count * (uint64_t)dev_bytes, hipMemcpyDeviceToHost));
-            return SPRS_HIP_OK;
-        }
-        std::vector<uint32_t> wide(count ? count : 1);          // declared 2 bytes, device 4
-        SPRS_TRY_HIP(hipMemcpy(wide.data(), src, count * 4, hipMemcpyDeviceToHost));
-        for (uint64_t i = 0; i < count; ++i) {
-            if (wide[i] > 0xFFFFu) SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "Index type is not large enough to hold %u", wide[i]);
-            ((uint16_t *)dst)[i] = (uint16_t)wide[i];
-        }
-        return SPRS_HIP_OK;
-    };
-    if (indptr_out) SPRS_TRY(fetch(indptr_out, (const uint8_t *)m->indptr + start * pb, end - start + 1, m->iptr_bytes, m->user_iptr_bytes()));
+    if (indptr_out) SPRS_TRY(download_indices(indptr_out, (const uint8_t *)m->indptr + start * pb, end - start + 1, m->iptr_bytes, m->user_iptr_bytes()));
     if (indices_out && hi > lo)
-        SPRS_TRY(fetch(indices_out, (const uint8_t *)m->indices + lo * (uint64_t)m->idx_bytes, hi - lo, m->idx_bytes, m->user_idx_bytes()));
-    if (data_out && hi > lo) SPRS_TRY_HIP(hipMemcpy(data_out, m->data + lo, (hi - lo) * sizeof(double), hipMemcpyDeviceToHost));
+        SPRS_TRY(download_indices(indices_out, (const uint8_t *)m->indices + lo * (uint64_t)m->idx_bytes, hi - lo, m->idx_bytes, m->user_idx_bytes()));
+    if (data_out && hi > lo) SPRS_TRY_HIP(copy_to_host(data_out, m->data + lo, (hi - lo) * sizeof(double), nullptr));
     return SPRS_HIP_OK;
 }
 
@@ -848,30 +834,22 @@ int32_t sprs_hip_csmat_mul_csmat(const sprs_hip_csmat *lhs, const sprs_hip_csmat
         t.owns = false;
         t.device = m->device;
     };
-    struct Owned {
-        sprs_hip_csmat *h = nullptr;
-        ~Owned() {
-            if (h) sprs_hip_csmat_free(h);
-        }
-    };
     const bool l_csr = lhs->storage == SPRS_HIP_CSR, r_csr = rhs->storage == SPRS_HIP_CSR;
     if (l_csr && r_csr) {                                         // (CSR, CSR)
         SPRS_TRY(spgemm_f64(lhs, rhs, out));
         return finish_result(out, lhs);
     }
+    sprs_hip_csmat *conv = nullptr;
     if (l_csr) {                                                  // (CSR, CSC): rhs.to_other_storage()
-        Owned conv;
-        SPRS_TRY(convert_checked(rhs, &conv.h));
-        SPRS_TRY(spgemm_f64(lhs, conv.h, out));
+        SPRS_TRY(convert_checked(rhs, &conv));
+        OwnedCsmat owned(conv);
+        SPRS_TRY(spgemm_f64(lhs, conv, out));
         return finish_result(out, lhs);
     }
     // lhs is CSC: (rhs^T * lhs^T)^T on the transpose views, which are CSR; transpose_into flips the result back
-    Owned conv;
-    const sprs_hip_csmat *r = rhs;
-    if (r_csr) {                                                  // (CSC, CSR): rhs.to_other_storage() first
-        SPRS_TRY(convert_checked(rhs, &conv.h));
-        r = conv.h;
-    }
+    if (r_csr) SPRS_TRY(convert_checked(rhs, &conv));             // (CSC, CSR): rhs.to_other_storage() first
+    OwnedCsmat owned(conv);
+    const sprs_hip_csmat *r = r_csr ? conv : rhs;
     sprs_hip_csmat rt, lt;
     view_t(r, rt);
     view_t(lhs, lt);
@@ -1214,19 +1192,14 @@ int32_t sprs_hip_csvec_upload(sprs_hip_csvec **out, uint64_t dim, uint64_t nnz, 
             SPRS_TRY(st);
         }
     }
-    std::vector<uint32_t> wide;
-    const void *src = indices;
+    const std::vector<uint32_t> wide = idx_bytes == 2 ? widen16(indices, nnz) : std::vector<uint32_t>();
+    const void *src = idx_bytes == 2 ? wide.data() : indices;
     const int32_t dev_bytes = idx_bytes == 2 ? 4 : idx_bytes;
-    if (idx_bytes == 2) {                       // u16 / i16 (indexing.rs:124-130): widened to 4 bytes for the device
-        wide.resize(nnz ? nnz : 1);
-        for (uint64_t i = 0; i < nnz; ++i) wide[i] = ((const uint16_t *)indices)[i];
-        src = wide.data();
-    }
     sprs_hip_csvec *v = nullptr;
     SPRS_TRY(csvec_alloc(&v, dim, nnz, dev_bytes, idx_bytes));
     hipError_t e = hipSuccess;
-    if (nnz) e = hipMemcpy(v->indices, src, nnz * (uint64_t)dev_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess && nnz) e = hipMemcpy(v->data, data, nnz * sizeof(double), hipMemcpyHostToDevice);
+    if (nnz) e = copy_to_device(v->indices, src, nnz * (uint64_t)dev_bytes, nullptr);
+    if (e == hipSuccess && nnz) e = copy_to_device(v->data, data, nnz * sizeof(double), nullptr);
     if (e != hipSuccess) {
         csvec_release(v);
         return fail_hip(e, "csvec_upload");
@@ -1289,19 +1262,8 @@ int32_t sprs_hip_csvec_device_ptrs(const sprs_hip_csvec *v, const void **indices
 int32_t sprs_hip_csvec_download(const sprs_hip_csvec *v, void *indices, double *data) {
     clear_error();
     if (!v) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
-    if (indices && v->nnz) {
-        if (v->user_idx_bytes() == v->idx_bytes) {
-            SPRS_TRY_HIP(hipMemcpy(indices, v->indices, v->nnz * (uint64_t)v->idx_bytes, hipMemcpyDeviceToHost));
-        } else {                                // declared 2 bytes, device 4: narrow (results were range-checked when made)
-            std::vector<uint32_t> wide(v->nnz);
-            SPRS_TRY_HIP(hipMemcpy(wide.data(), v->indices, v->nnz * 4, hipMemcpyDeviceToHost));
-            for (uint64_t i = 0; i < v->nnz; ++i) {
-                if (wide[i] > 0xFFFFu) SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "Index type is not large enough to hold %u", wide[i]);
-                ((uint16_t *)indices)[i] = (uint16_t)wide[i];
-            }
-        }
-    }
-    if (data && v->nnz) SPRS_TRY_HIP(hipMemcpy(data, v->data, v->nnz * sizeof(double), hipMemcpyDeviceToHost));
+    if (indices && v->nnz) SPRS_TRY(download_indices(indices, v->indices, v->nnz, v->idx_bytes, v->user_idx_bytes()));
+    if (data && v->nnz) SPRS_TRY_HIP(copy_to_host(data, v->data, v->nnz * sizeof(double), nullptr));
     return SPRS_HIP_OK;
 }
 

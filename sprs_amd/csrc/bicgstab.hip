@@ -174,13 +174,6 @@ __global__ void resid_kernel(const double *__restrict__ b, const double *__restr
     r[i] = b[i] - v[i];
 }
 
-struct Work {
-    double *buf = nullptr;
-    ~Work() {
-        if (buf) (void)hipFree(buf);
-    }
-};
-
 }  // namespace
 
 int32_t bicgstab_f64(sprs_hip_csmat *a_in, const double *x0, const double *b, uint64_t n, double tol, uint64_t max_iter,
@@ -191,18 +184,12 @@ int32_t bicgstab_f64(sprs_hip_csmat *a_in, const double *x0, const double *b, ui
         SPRS_TRY(to_other_storage(a_in, &converted));
         a = converted;
     }
-    struct Guard {
-        sprs_hip_csmat *m;
-        ~Guard() {
-            if (m) sprs_hip_csmat_free(m);
-        }
-    } guard{converted};
+    OwnedCsmat owned(converted);
 
     const uint64_t nchunks = (n + DOT_CHUNK - 1) / DOT_CHUNK;
-    Work w;
-    const uint64_t doubles = 7 * n + 2 * nchunks + 8;
-    SPRS_TRY_HIP(hipMalloc((void **)&w.buf, doubles * sizeof(double)));
-    double *r = w.buf, *rhat = r + n, *p = rhat + n, *v = p + n, *s = v + n, *t = s + n, *h = t + n;
+    DevBuf work;
+    SPRS_TRY_HIP(work.alloc((7 * n + 2 * nchunks + 8) * sizeof(double)));
+    double *r = work.as<double>(), *rhat = r + n, *p = rhat + n, *v = p + n, *s = v + n, *t = s + n, *h = t + n;
     double *partial = h + n, *scal = partial + 2 * nchunks;
     const dim3 eg((unsigned)((n + 255) / 256)), eb(256);
 
@@ -218,8 +205,7 @@ int32_t bicgstab_f64(sprs_hip_csmat *a_in, const double *x0, const double *b, ui
         }
         SPRS_TRY_HIP(hipGetLastError());
         double hst[2];
-        SPRS_TRY_HIP(hipMemcpyAsync(hst, scal, 16, hipMemcpyDeviceToHost, stream));
-        SPRS_TRY_HIP(hipStreamSynchronize(stream));
+        SPRS_TRY_HIP(copy_to_host(hst, scal, 16, stream));
         o0 = hst[0];
         o1 = hst[1];
         return SPRS_HIP_OK;

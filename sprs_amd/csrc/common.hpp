@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <unordered_map>
@@ -251,6 +252,59 @@ hipError_t pool_alloc(void **p, uint64_t bytes, uint64_t *cap, int device);
 void pool_free(void *p, uint64_t cap, int device, bool stream_ordered = false);
 uint64_t pool_trim();
 uint64_t pool_cached_bytes();
+
+// A device temporary owned by one call, released when it goes out of scope.
+//   alloc:        a private block (hipMalloc), released with hipFree.
+//   alloc_pooled: a block of the pool, handed back in null-stream order (pool_free above); legal only for work ordered on the
+//                 null stream.
+struct DevBuf {
+    void *p = nullptr;
+    uint64_t cap = 0;
+    int dev = 0;
+    bool pooled = false;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    void release() {
+        if (p && pooled) pool_free(p, cap, dev, true);
+        else if (p) (void)hipFree(p);
+        p = nullptr;
+    }
+    hipError_t alloc(uint64_t bytes) {
+        release();
+        pooled = false;
+        return hipMalloc(&p, bytes ? bytes : 16);
+    }
+    hipError_t alloc_pooled(uint64_t bytes) {
+        release();
+        pooled = true;
+        hipError_t e = hipGetDevice(&dev);
+        if (e != hipSuccess) return e;
+        return pool_alloc(&p, bytes ? bytes : 8, &cap, dev);
+    }
+    template <typename T>
+    T *as() const { return (T *)p; }
+    uint64_t *u64() const { return (uint64_t *)p; }
+};
+
+// Host copies run on the stream of the work around them and are complete when these return: a read-back sees every kernel
+// enqueued on that stream before it.  (A blocking copy would run on the null stream, which a hipStreamNonBlocking stream, as
+// every torch.cuda.Stream is, is not ordered with.)
+inline hipError_t copy_to_host(void *dst, const void *src, uint64_t bytes, hipStream_t stream) {
+    hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream);
+    return e == hipSuccess ? hipStreamSynchronize(stream) : e;
+}
+inline hipError_t copy_to_device(void *dst, const void *src, uint64_t bytes, hipStream_t stream) {
+    hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream);
+    return e == hipSuccess ? hipStreamSynchronize(stream) : e;
+}
+
+// a temporary handle (a converted operand, a slice): freed with the scope that made it
+struct CsmatFree {
+    void operator()(sprs_hip_csmat *m) const { sprs_hip_csmat_free(m); }
+};
+using OwnedCsmat = std::unique_ptr<sprs_hip_csmat, CsmatFree>;
 
 // spmv_band.hip
 int32_t band_build(sprs_hip_csmat *a, hipStream_t stream, BandPlan **out);   // *out stays null when the plan does not apply

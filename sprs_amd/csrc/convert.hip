@@ -192,16 +192,6 @@ __global__ void rebase_ptr_kernel(const PTR *__restrict__ in, uint64_t n, PTR *_
     if (i < n) out[i] = (PTR)(in[i] - in[0]);
 }
 
-struct Tmp {
-    void *p = nullptr;
-    ~Tmp() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(uint64_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-    template <typename T>
-    T *as() { return (T *)p; }
-};
-
 template <typename IDX, typename PTR>
 int32_t convert_impl(const sprs_hip_csmat *m, sprs_hip_csmat **out) {
     hipStream_t stream = nullptr;
@@ -215,13 +205,8 @@ int32_t convert_impl(const sprs_hip_csmat *m, sprs_hip_csmat **out) {
     sprs_hip_csmat *o = nullptr;
     SPRS_TRY(alloc_csmat(&o, m->storage == SPRS_HIP_CSR ? SPRS_HIP_CSC : SPRS_HIP_CSR, m->rows, m->cols, nnz,
                          (int32_t)sizeof(PTR), (int32_t)sizeof(IDX)));
-    struct Guard {
-        sprs_hip_csmat *h;
-        ~Guard() {
-            if (h) sprs_hip_csmat_free(h);
-        }
-    } guard{o};
-    Tmp cnt, optr, cursor, tkeys, tvals, large, nlarge;
+    OwnedCsmat owned(o);
+    DevBuf cnt, optr, cursor, tkeys, tvals, large, nlarge;
     SPRS_TRY_HIP(cnt.alloc(inner * 8));
     SPRS_TRY_HIP(optr.alloc((inner + 1) * 8));
     SPRS_TRY_HIP(cursor.alloc(inner * 8));
@@ -257,7 +242,7 @@ int32_t convert_impl(const sprs_hip_csmat *m, sprs_hip_csmat **out) {
                            optr.as<uint64_t>(), inner, large.as<uint64_t>(), nlarge.as<unsigned long long>());
         SPRS_TRY_HIP(hipGetLastError());
         uint64_t n_large = 0;
-        SPRS_TRY_HIP(hipMemcpy(&n_large, nlarge.p, 8, hipMemcpyDeviceToHost));
+        SPRS_TRY_HIP(copy_to_host(&n_large, nlarge.p, 8, stream));
         if (n_large) {
             hipLaunchKernelGGL(sort_large_rows_kernel<IDX>, dim3((unsigned)n_large), dim3(LG_BLOCK), 0, stream,
                                large.as<uint64_t>(), optr.as<uint64_t>(), outer, tkeys.as<uint32_t>(),
@@ -266,8 +251,7 @@ int32_t convert_impl(const sprs_hip_csmat *m, sprs_hip_csmat **out) {
         }
     }
     SPRS_TRY_HIP(hipStreamSynchronize(stream));
-    guard.h = nullptr;
-    *out = o;
+    *out = owned.release();
     return SPRS_HIP_OK;
 }
 
@@ -275,8 +259,8 @@ template <typename IDX, typename PTR>
 int32_t slice_impl(const sprs_hip_csmat *m, uint64_t start, uint64_t end, sprs_hip_csmat **out) {
     hipStream_t stream = nullptr;
     PTR lo = 0, hi = 0;
-    SPRS_TRY_HIP(hipMemcpy(&lo, (const PTR *)m->indptr + start, sizeof(PTR), hipMemcpyDeviceToHost));
-    SPRS_TRY_HIP(hipMemcpy(&hi, (const PTR *)m->indptr + end, sizeof(PTR), hipMemcpyDeviceToHost));
+    SPRS_TRY_HIP(copy_to_host(&lo, (const PTR *)m->indptr + start, sizeof(PTR), stream));
+    SPRS_TRY_HIP(copy_to_host(&hi, (const PTR *)m->indptr + end, sizeof(PTR), stream));
     const uint64_t nnz = (uint64_t)hi - (uint64_t)lo, n = end - start;
     sprs_hip_csmat *o = nullptr;
     const bool csr = m->storage == SPRS_HIP_CSR;

@@ -284,22 +284,20 @@ void csvec_release(sprs_hip_csvec *v) {
 
 int32_t csvec_check_device(const sprs_hip_csvec *v, hipStream_t s) {
     if (v->nnz == 0) return SPRS_HIP_OK;
-    uint64_t *bad = nullptr;
-    SPRS_TRY_HIP(hipMalloc((void **)&bad, 16));
+    DevBuf bad;
+    SPRS_TRY_HIP(bad.alloc(16));
     uint64_t host[2] = {~0ull, 0};
-    hipError_t e = hipMemcpyAsync(bad, host, 16, hipMemcpyHostToDevice, s);
+    hipError_t e = hipMemcpyAsync(bad.p, host, 16, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) {
         if (v->idx_bytes == 8)
             hipLaunchKernelGGL(cv::csvec_check_kernel<uint64_t>, dim3(cv::blocks_for(v->nnz)), dim3(cv::CV_BLOCK), 0, s,
-                               (const uint64_t *)v->indices, v->nnz, v->dim, bad);
+                               (const uint64_t *)v->indices, v->nnz, v->dim, bad.u64());
         else
             hipLaunchKernelGGL(cv::csvec_check_kernel<uint32_t>, dim3(cv::blocks_for(v->nnz)), dim3(cv::CV_BLOCK), 0, s,
-                               (const uint32_t *)v->indices, v->nnz, v->dim, bad);
+                               (const uint32_t *)v->indices, v->nnz, v->dim, bad.u64());
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(host, bad, 16, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(bad);
+    if (e == hipSuccess) e = copy_to_host(host, bad.p, 16, s);
     if (e != hipSuccess) return fail_hip(e, "csvec_check");
     if (host[0] != ~0ull) SPRS_FAIL(SPRS_HIP_BAD_STRUCTURE, "Unsorted indices");
     if (host[1]) SPRS_FAIL(SPRS_HIP_BAD_STRUCTURE, "indices larger than vector size");
@@ -359,8 +357,7 @@ int32_t csvec_masked_dot(const sprs_hip_csmat *mc, const sprs_hip_csvec *v, bool
     SPRS_TRY(exclusive_scan_u64(s.groups + ngroups, offs, ngroups, st));
     // the result's nnz, read back in the caller's stream order (a non-blocking stream does not wait for the null stream)
     uint64_t nnz = 0;
-    SPRS_TRY_HIP(hipMemcpyAsync(&nnz, offs + ngroups, 8, hipMemcpyDeviceToHost, st));
-    SPRS_TRY_HIP(hipStreamSynchronize(st));
+    SPRS_TRY_HIP(copy_to_host(&nnz, offs + ngroups, 8, st));
     sprs_hip_csvec *res = nullptr;
     SPRS_TRY(csvec_alloc(&res, nouter, nnz, idx_bytes, decl_bytes));
     if (nnz) {
@@ -377,8 +374,7 @@ int32_t csvec_masked_dot(const sprs_hip_csmat *mc, const sprs_hip_csvec *v, bool
                                    offs, s.sums, nouter, limit, (uint32_t *)res->indices, res->data, overflow);
             e = hipGetLastError();
         }
-        if (e == hipSuccess) e = hipMemcpyAsync(&flag, overflow, 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e == hipSuccess) e = copy_to_host(&flag, overflow, 4, st);
         if (e != hipSuccess) {
             csvec_release(res);
             return fail_hip(e, "csvec product");

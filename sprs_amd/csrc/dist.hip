@@ -199,10 +199,10 @@ int32_t dist_create(sprs_hip_dist **out, const void *unique_id128, int32_t world
     if (nsub > 1) {
         std::vector<uint64_t> ip(lrows + 1);
         if (local_block->iptr_bytes == 8) {
-            SPRS_TRY_HIP(hipMemcpy(ip.data(), local_block->indptr, (lrows + 1) * 8, hipMemcpyDeviceToHost));
+            SPRS_TRY_HIP(copy_to_host(ip.data(), local_block->indptr, (lrows + 1) * 8, nullptr));
         } else {
             std::vector<uint32_t> ip32(lrows + 1);
-            SPRS_TRY_HIP(hipMemcpy(ip32.data(), local_block->indptr, (lrows + 1) * 4, hipMemcpyDeviceToHost));
+            SPRS_TRY_HIP(copy_to_host(ip32.data(), local_block->indptr, (lrows + 1) * 4, nullptr));
             for (uint64_t i = 0; i <= lrows; ++i) ip[i] = ip32[i];
         }
         const double total = (double)ip[lrows] + 8.0 * (double)lrows;
@@ -247,13 +247,10 @@ int32_t dist_create(sprs_hip_dist **out, const void *unique_id128, int32_t world
         const size_t tab = (size_t)nsub_req + 1;
         std::vector<uint64_t> mine(tab, d->sub_starts.back());
         for (size_t i = 0; i < d->sub_starts.size() && i < tab; ++i) mine[i] = d->sub_starts[i];
-        uint64_t *dev = nullptr;
-        SPRS_TRY_HIP(hipMalloc((void **)&dev, (size_t)world * tab * 8));
-        struct Free {
-            void *p;
-            ~Free() { (void)hipFree(p); }
-        } fr{dev};
-        SPRS_TRY_HIP(hipMemcpy(dev + (size_t)rank * tab, mine.data(), tab * 8, hipMemcpyHostToDevice));
+        DevBuf buf;
+        SPRS_TRY_HIP(buf.alloc((size_t)world * tab * 8));
+        uint64_t *dev = buf.u64();
+        SPRS_TRY_HIP(copy_to_device(dev + (size_t)rank * tab, mine.data(), tab * 8, d->comm_stream));
         SPRS_TRY_NCCL(R, R->GroupStart());
         {
             GroupStatus g;
@@ -266,7 +263,7 @@ int32_t dist_create(sprs_hip_dist **out, const void *unique_id128, int32_t world
         }
         SPRS_TRY_HIP(hipStreamSynchronize(d->comm_stream));
         std::vector<uint64_t> all((size_t)world * tab);
-        SPRS_TRY_HIP(hipMemcpy(all.data(), dev, all.size() * 8, hipMemcpyDeviceToHost));
+        SPRS_TRY_HIP(copy_to_host(all.data(), dev, all.size() * 8, d->comm_stream));
         d->peer_starts.resize(world);
         for (int32_t p = 0; p < world; ++p) {
             d->peer_starts[p].assign(all.begin() + (size_t)p * tab, all.begin() + (size_t)(p + 1) * tab);
@@ -379,7 +376,7 @@ int32_t peer_alloc_window(sprs_hip_dist *d) {
     }
 #endif
     if (!d->window) SPRS_TRY_HIP(hipMalloc(&d->window, bytes));
-    SPRS_TRY_HIP(hipMemset(d->window, 0, bytes));
+    SPRS_TRY_HIP(hipMemsetAsync(d->window, 0, bytes, nullptr));
     SPRS_TRY_HIP(hipDeviceSynchronize());
     SPRS_TRY_HIP(hipHostMalloc((void **)&d->peer_status, sizeof(int), hipHostMallocMapped));
     *d->peer_status = 0;

@@ -339,22 +339,12 @@ __global__ void gs_order_kernel(const uint64_t *__restrict__ vals, uint64_t n, u
     if (i < n) order[i] = (uint32_t)vals[i];
 }
 
-struct DevTmp {
-    void *p = nullptr;
-    ~DevTmp() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(uint64_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-    template <typename T>
-    T *as() { return (T *)p; }
-};
-
 template <typename IDX, typename PTR>
 int32_t gs_plan_build(sprs_hip_csmat *a) {
     GsPlan &pl = a->gs;
     const uint64_t n = a->rows;
     hipStream_t stream = nullptr;
-    DevTmp level, words, keys, vals;
+    DevBuf level, words, keys, vals;
     SPRS_TRY_HIP(level.alloc(n * sizeof(unsigned int)));
     SPRS_TRY_HIP(words.alloc(64));
     SPRS_TRY_HIP(keys.alloc(n * 8));
@@ -378,7 +368,7 @@ int32_t gs_plan_build(sprs_hip_csmat *a) {
         SPRS_TRY_HIP(hipGetLastError());
     }
     unsigned int hw[6] = {0, 0, 0, 0, 0, 0};
-    SPRS_TRY_HIP(hipMemcpy(hw, words.p, sizeof(hw), hipMemcpyDeviceToHost));
+    SPRS_TRY_HIP(copy_to_host(hw, words.p, sizeof(hw), stream));
     if (hw[1] & GS_TIMEOUT) SPRS_FAIL(SPRS_HIP_HIP_ERROR, "Gauss-Seidel plan: the level recurrence did not finish");
     const uint32_t top = hw[2];
     int bits = 1;
@@ -668,17 +658,6 @@ __global__ __launch_bounds__(GB_BLOCK) void gs_band_kernel(const PTR *__restrict
     }
 }
 
-struct Work {
-    double *buf = nullptr;
-    unsigned int *words = nullptr;
-    hipStream_t stream = nullptr;
-    ~Work() {
-        (void)hipStreamSynchronize(stream);     // an early return must not leave copies into this frame's variables in flight
-        if (buf) (void)hipFree(buf);
-        if (words) (void)hipFree(words);
-    }
-};
-
 template <typename IDX, typename PTR>
 int32_t gs_impl(sprs_hip_csmat *a, double *x, const double *rhs, uint64_t n, uint64_t max_iter, double eps,
                 sprs_hip_gauss_seidel_info *info, hipStream_t stream) {
@@ -701,15 +680,14 @@ int32_t gs_impl(sprs_hip_csmat *a, double *x, const double *rhs, uint64_t n, uin
         // an explicit choice, gauss_seidel_chain = S.)
         if (want > 1 && want < n) {
             if (a->gs.chain_tried != want) {
-                DevTmp flag;
+                DevBuf flag;
                 SPRS_TRY_HIP(flag.alloc(4));
                 SPRS_TRY_HIP(hipMemsetAsync(flag.p, 0, 4, stream));
                 hipLaunchKernelGGL((gs_band_check_kernel<IDX, PTR>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const PTR *)a->indptr,
                                    (const IDX *)a->indices, n, want, flag.as<unsigned int>());
                 SPRS_TRY_HIP(hipGetLastError());
                 unsigned int bad = 0;
-                SPRS_TRY_HIP(hipMemcpyAsync(&bad, flag.p, 4, hipMemcpyDeviceToHost, stream));
-                SPRS_TRY_HIP(hipStreamSynchronize(stream));
+                SPRS_TRY_HIP(copy_to_host(&bad, flag.p, 4, stream));
                 a->gs.chain_tried = want;
                 a->gs.chain_ok = bad == 0;
             }
@@ -726,22 +704,24 @@ int32_t gs_impl(sprs_hip_csmat *a, double *x, const double *rhs, uint64_t n, uin
                   (unsigned long long)no_diag_row);
 
     const uint64_t nchunks = (n + SUM_CHUNK - 1) / SUM_CHUNK;
-    unsigned int sweep_words[2] = {0, 0};      // (declared before `w`: its destructor drains the stream that may still write them)
+    unsigned int sweep_words[2] = {0, 0};
     double h_sum = 0.0;
-    Work w;
-    w.stream = stream;
-    SPRS_TRY_HIP(hipMalloc((void **)&w.buf, (2 * n + nchunks + 8) * sizeof(double)));
-    SPRS_TRY_HIP(hipMalloc((void **)&w.words, 64));
-    double *other = w.buf, *v = other + n, *partial = v + n, *scal = partial + nchunks;
-    unsigned int *next_chunk = w.words, *status = w.words + 1;
+    DevBuf buf, words;
+    struct Drain {                              // declared last, so it runs first: an early return must not leave copies into this
+        hipStream_t s;                          // frame's variables (sweep_words) or kernels on buf / words in flight
+        ~Drain() { (void)hipStreamSynchronize(s); }
+    } drain{stream};
+    SPRS_TRY_HIP(buf.alloc((2 * n + nchunks + 8) * sizeof(double)));
+    SPRS_TRY_HIP(words.alloc(64));
+    double *other = buf.as<double>(), *v = other + n, *partial = v + n, *scal = partial + nchunks;
+    unsigned int *next_chunk = words.as<unsigned int>(), *status = next_chunk + 1;
 
     auto residual_error = [&](const double *xc, double &err) -> int32_t {      // (&mat * &x - rhs).sum().sqrt()
         SPRS_TRY(spmv_f64(a, xc, v, false, stream));
         hipLaunchKernelGGL(gs_resid_partial_kernel, dim3((unsigned)nchunks), dim3(GS_BLOCK), 0, stream, v, rhs, n, partial);
         hipLaunchKernelGGL(gs_resid_final_kernel, dim3(1), dim3(GS_BLOCK), 0, stream, partial, nchunks, scal);
         SPRS_TRY_HIP(hipGetLastError());
-        SPRS_TRY_HIP(hipMemcpyAsync(&h_sum, scal, sizeof(double), hipMemcpyDeviceToHost, stream));
-        SPRS_TRY_HIP(hipStreamSynchronize(stream));
+        SPRS_TRY_HIP(copy_to_host(&h_sum, scal, sizeof(double), stream));
         err = std::sqrt(h_sum);
         return SPRS_HIP_OK;
     };
@@ -768,7 +748,7 @@ int32_t gs_impl(sprs_hip_csmat *a, double *x, const double *rhs, uint64_t n, uin
     if (max_iter == 0) SPRS_TRY(residual_error(cur, error));                   // heat.rs:111: what Err(error) holds then
     for (uint64_t it = 0; it < max_iter; ++it) {
         SPRS_TRY_HIP(hipMemsetAsync(nxt, 0xFF, n * sizeof(double), stream));   // every row of the next iterate "pending"
-        SPRS_TRY_HIP(hipMemsetAsync(w.words, 0, 64, stream));
+        SPRS_TRY_HIP(hipMemsetAsync(words.p, 0, 64, stream));
         if (chain_S) {     // one workgroup per band, bands drawn in order
             uint64_t nbands = (n + 64 * chain_S - 1) / (64 * chain_S);
             if (nbands > (uint64_t)(ncu > 0 ? ncu : 1)) nbands = (uint64_t)(ncu > 0 ? ncu : 1);
@@ -784,7 +764,7 @@ int32_t gs_impl(sprs_hip_csmat *a, double *x, const double *rhs, uint64_t n, uin
                                (const IDX *)a->indices, (const double *)a->data, order, (const double *)cur,
                                (unsigned long long *)nxt, rhs, n, next_chunk, status, max_naps);
         SPRS_TRY_HIP(hipGetLastError());
-        SPRS_TRY_HIP(hipMemcpyAsync(sweep_words, w.words, sizeof(sweep_words), hipMemcpyDeviceToHost, stream));   // [0] chunks drawn, [1] status
+        SPRS_TRY_HIP(hipMemcpyAsync(sweep_words, words.p, sizeof(sweep_words), hipMemcpyDeviceToHost, stream));   // [0] chunks drawn, [1] status
         double *t = cur;
         cur = nxt;
         nxt = t;

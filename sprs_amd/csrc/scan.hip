@@ -70,23 +70,15 @@ int32_t exclusive_scan_u64(const uint64_t *in, uint64_t *out, uint64_t n, hipStr
         return SPRS_HIP_OK;
     }
     const uint64_t nblocks = (n + SCAN_TILE - 1) / SCAN_TILE;
-    // block sums: on the null stream from the library's pool, handed back in null-stream order (pool_free, common.hpp: the pool's
-    // blocks may still be in use by earlier null-stream work); on any other stream a block of its own, freed behind that stream
-    uint64_t *sums = nullptr, cap = 0;
-    int dev = 0;
-    SPRS_TRY_HIP(hipGetDevice(&dev));
-    if (stream == nullptr) SPRS_TRY_HIP(pool_alloc((void **)&sums, (nblocks + 1) * sizeof(uint64_t), &cap, dev));
-    else SPRS_TRY_HIP(hipMalloc((void **)&sums, (nblocks + 1) * sizeof(uint64_t)));
-    hipLaunchKernelGGL(scan_partial_kernel, dim3((unsigned)nblocks), dim3(SCAN_BLOCK), 0, stream, in, n, sums);
-    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(1024), 0, stream, sums, nblocks);
-    hipLaunchKernelGGL(scan_final_kernel, dim3((unsigned)nblocks), dim3(SCAN_BLOCK), 0, stream, in, n, sums, nblocks, out);
+    // block sums: from the pool on the null stream (DevBuf, common.hpp); on any other stream a block of its own, freed behind
+    // that stream
+    DevBuf sums;
+    SPRS_TRY_HIP(stream == nullptr ? sums.alloc_pooled((nblocks + 1) * sizeof(uint64_t)) : sums.alloc((nblocks + 1) * sizeof(uint64_t)));
+    hipLaunchKernelGGL(scan_partial_kernel, dim3((unsigned)nblocks), dim3(SCAN_BLOCK), 0, stream, in, n, sums.u64());
+    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(1024), 0, stream, sums.u64(), nblocks);
+    hipLaunchKernelGGL(scan_final_kernel, dim3((unsigned)nblocks), dim3(SCAN_BLOCK), 0, stream, in, n, sums.u64(), nblocks, out);
     hipError_t e = hipGetLastError();
-    if (stream == nullptr) {
-        pool_free(sums, cap, dev, true);
-    } else {
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        (void)hipFree(sums);
-    }
+    if (e == hipSuccess && stream != nullptr) e = hipStreamSynchronize(stream);
     if (e != hipSuccess) return fail_hip(e, "exclusive_scan_u64");
     return SPRS_HIP_OK;
 }

@@ -92,36 +92,16 @@ int32_t radix_sort_pairs(uint64_t *keys, uint64_t *vals, uint64_t n, const std::
         for (int b = 0; b < f.second; b += 8) passes.push_back({f.first + b, (1u << (f.second - b < 8 ? f.second - b : 8)) - 1u});
     if (passes.empty()) return SPRS_HIP_OK;
     const uint64_t nchunks = (n + RS_CHUNK - 1) / RS_CHUNK;
-    // temporaries: on the null stream from the library's pool, handed back in null-stream order (the pool's blocks may still be in
-    // use by earlier null-stream work); on any other stream blocks of their own, freed behind that stream
-    uint64_t *tk = nullptr, *tv = nullptr, *hist = nullptr, *offs = nullptr;
-    uint64_t cap_tk = 0, cap_tv = 0, cap_hist = 0, cap_offs = 0;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    const bool pooled = stream == nullptr;
-    auto take = [&](uint64_t **p, uint64_t bytes, uint64_t *cap) {
-        return pooled ? pool_alloc((void **)p, bytes, cap, dev) : hipMalloc((void **)p, bytes);
-    };
-    auto drop = [&](uint64_t *p, uint64_t cap) {
-        if (!p) return;
-        if (pooled) pool_free(p, cap, dev, true);
-        else (void)hipFree(p);
-    };
-    auto cleanup = [&]() {
-        if (!pooled) (void)hipStreamSynchronize(stream);
-        drop(tk, cap_tk);
-        drop(tv, cap_tv);
-        drop(hist, cap_hist);
-        drop(offs, cap_offs);
-    };
-    if (e == hipSuccess) e = take(&tk, n * 8, &cap_tk);
-    if (e == hipSuccess) e = take(&tv, n * 8, &cap_tv);
-    if (e == hipSuccess) e = take(&hist, (RS_BINS * nchunks + 1) * 8, &cap_hist);
-    if (e == hipSuccess) e = take(&offs, (RS_BINS * nchunks + 1) * 8, &cap_offs);
-    if (e != hipSuccess) {
-        cleanup();
-        return fail_hip(e, "radix_sort_pairs");
-    }
+    // temporaries: from the pool on the null stream (DevBuf, common.hpp); on any other stream blocks of their own, freed behind
+    // that stream
+    DevBuf btk, btv, bhist, boffs;
+    auto take = [&](DevBuf &b, uint64_t bytes) { return stream == nullptr ? b.alloc_pooled(bytes) : b.alloc(bytes); };
+    hipError_t e = take(btk, n * 8);
+    if (e == hipSuccess) e = take(btv, n * 8);
+    if (e == hipSuccess) e = take(bhist, (RS_BINS * nchunks + 1) * 8);
+    if (e == hipSuccess) e = take(boffs, (RS_BINS * nchunks + 1) * 8);
+    if (e != hipSuccess) return fail_hip(e, "radix_sort_pairs");
+    uint64_t *tk = btk.u64(), *tv = btv.u64(), *hist = bhist.u64(), *offs = boffs.u64();
     uint64_t *ik = keys, *iv = vals, *ok = tk, *ov = tv;
     const dim3 grid((unsigned)((nchunks + RS_WAVES - 1) / RS_WAVES)), block(RS_BLOCK);
     int32_t st = SPRS_HIP_OK;
@@ -139,12 +119,11 @@ int32_t radix_sort_pairs(uint64_t *keys, uint64_t *vals, uint64_t n, const std::
         if (e == hipSuccess) e = hipMemcpyAsync(vals, iv, n * 8, hipMemcpyDeviceToDevice, stream);
         if (e != hipSuccess) st = fail_hip(e, "radix_sort_pairs copy back");
     }
-    if (st == SPRS_HIP_OK) {
-        e = hipGetLastError();
-        if (e == hipSuccess && stream != nullptr) e = hipStreamSynchronize(stream);   // (the temporaries go back to the pool below, in null-stream order)
-        if (e != hipSuccess) st = fail_hip(e, "radix_sort_pairs");
+    if (st == SPRS_HIP_OK && (e = hipGetLastError()) != hipSuccess) st = fail_hip(e, "radix_sort_pairs");
+    if (stream != nullptr) {                    // private blocks are freed behind their stream (pooled ones in null-stream order)
+        e = hipStreamSynchronize(stream);
+        if (st == SPRS_HIP_OK && e != hipSuccess) st = fail_hip(e, "radix_sort_pairs");
     }
-    cleanup();
     return st;
 }
 

@@ -1795,26 +1795,6 @@ __global__ void compare_indptr_kernel(const uint64_t *__restrict__ first_task, c
     if ((uint64_t)indptr[r] != off[first_task[r]]) atomicOr(mismatch, 1u);
 }
 
-// temporaries come from the library's block pool (abi.hip): a product per iteration no longer pays ~15 hipMalloc / hipFree
-struct DevBuf {
-    void *p = nullptr;
-    uint64_t cap = 0;
-    int dev = 0;
-    ~DevBuf() { release(); }
-    void release() {
-        if (p) pool_free(p, cap, dev, true);      // (every kernel of this file runs on the null stream or on the aux stream joined back to it)
-        p = nullptr;
-    }
-    hipError_t alloc(uint64_t bytes) {
-        release();
-        hipError_t e = hipGetDevice(&dev);
-        if (e != hipSuccess) return e;
-        return pool_alloc(&p, bytes ? bytes : 8, &cap, dev);
-    }
-    template <typename T>
-    T *as() { return (T *)p; }
-};
-
 }  // namespace
 
 int32_t radix_sort_pairs(uint64_t *keys, uint64_t *vals, uint64_t n, const std::vector<std::pair<int, int>> &fields, hipStream_t stream);   // sort.hip
@@ -1870,6 +1850,31 @@ AuxStream *aux_stream() {
     return &a;
 }
 
+// One phase's fork: the wave kernels go to `wave`, the aux stream forked from `main` (on `main` itself when the overlap is off
+// or the fork cannot be recorded).  join() makes `main` wait for them; the destructor joins on every other exit, so no early
+// return hands the plan's pooled DevBufs back while aux kernels may still write them.
+struct AuxFork {
+    hipStream_t main, wave;
+    AuxStream *aux = nullptr;
+    explicit AuxFork(hipStream_t stream) : main(stream), wave(stream) {
+        AuxStream *a = options().spgemm_overlap && !options().spgemm_prof ? aux_stream() : nullptr;
+        if (a && hipEventRecord(a->fork, main) == hipSuccess && hipStreamWaitEvent(a->s, a->fork, 0) == hipSuccess) {
+            aux = a;
+            wave = a->s;
+        }
+    }
+    hipError_t join() {
+        if (!aux) return hipSuccess;
+        AuxStream *a = aux;
+        aux = nullptr;
+        hipError_t e = hipEventRecord(a->join, a->s);
+        if (e == hipSuccess) e = hipStreamWaitEvent(main, a->join, 0);
+        if (e != hipSuccess) (void)hipStreamSynchronize(a->s);     // (no join on the device: the host waits instead)
+        return e;
+    }
+    ~AuxFork() { (void)join(); }
+};
+
 // ---- the lane-order probe -----------------------------------------------------------------------------------
 // add_lanes() relies on a property of the LDS that the ISA manual does not state: the lanes of ONE ds_add_f64 that hit the
 // same address are applied in ascending lane order.  Floating-point sums make the order observable, so the library checks it
@@ -1916,11 +1921,11 @@ bool lds_lane_order_ok() {
         }
     bool ok = false;
     DevBuf dv, ds, dout;
-    if (dv.alloc(v.size() * 8) == hipSuccess && ds.alloc(slot.size() * 4) == hipSuccess && dout.alloc(got.size() * 8) == hipSuccess &&
-        hipMemcpy(dv.p, v.data(), v.size() * 8, hipMemcpyHostToDevice) == hipSuccess &&
-        hipMemcpy(ds.p, slot.data(), slot.size() * 4, hipMemcpyHostToDevice) == hipSuccess) {
+    if (dv.alloc_pooled(v.size() * 8) == hipSuccess && ds.alloc_pooled(slot.size() * 4) == hipSuccess && dout.alloc_pooled(got.size() * 8) == hipSuccess &&
+        copy_to_device(dv.p, v.data(), v.size() * 8, nullptr) == hipSuccess &&
+        copy_to_device(ds.p, slot.data(), slot.size() * 4, nullptr) == hipSuccess) {
         hipLaunchKernelGGL(lane_order_probe_kernel, dim3(TRIALS), dim3(WAVE), 0, nullptr, dv.as<double>(), ds.as<uint32_t>(), dout.as<double>());
-        if (hipGetLastError() == hipSuccess && hipMemcpy(got.data(), dout.p, got.size() * 8, hipMemcpyDeviceToHost) == hipSuccess)
+        if (hipGetLastError() == hipSuccess && copy_to_host(got.data(), dout.p, got.size() * 8, nullptr) == hipSuccess)
             ok = memcmp(got.data(), ref.data(), got.size() * 8) == 0;
     }
     (void)hipGetLastError();
@@ -1960,7 +1965,7 @@ int32_t plan_build(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_sp
         const uint64_t b_bytes = b->nnz * (8 + sizeof(IDX)) + (b->rows + 1) * sizeof(PTR);
         if (options().spgemm_bucket && b->rows && b->nnz > b->rows && bytes <= (8ull << 30) &&
             (bytes <= (4ull << 30) || bytes <= 4 * b_bytes + (64ull << 20))) {
-            if (pl->bucket.alloc(bytes) == hipSuccess) {
+            if (pl->bucket.alloc_pooled(bytes) == hipSuccess) {
                 uint64_t blocks = (b->rows + 3) / 4;
                 if (blocks > 256 * 64) blocks = 256 * 64;
                 hipLaunchKernelGGL((build_bucket_kernel<IDX, PTR>), dim3((unsigned)blocks), dim3(256), 0, stream, B.indptr,
@@ -1979,7 +1984,7 @@ int32_t plan_build(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_sp
     if (sizeof(IDX) == 4) {
         B.col32 = (const uint32_t *)b->indices;
     } else {
-        SPRS_TRY_HIP(pl->bcol32.alloc((b->nnz ? b->nnz : 1) * sizeof(uint32_t)));
+        SPRS_TRY_HIP(pl->bcol32.alloc_pooled((b->nnz ? b->nnz : 1) * sizeof(uint32_t)));
         if (b->nnz) {
             hipLaunchKernelGGL((pack_cols_kernel<IDX>), dim3(2048), dim3(256), 0, stream, B.indices, b->nnz, pl->bcol32.as<uint32_t>());
             SPRS_TRY_HIP(hipGetLastError());
@@ -1989,21 +1994,21 @@ int32_t plan_build(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_sp
 
     DevBuf large_key, mid_key, cls, class_sums, class_totals;
     DevBuf &pos_large = pl->large_slot;      // slot of a large row's bitmap = position of its first task in the (unsorted) large list
-    SPRS_TRY_HIP(pl->ub.alloc(rows * 8));
-    SPRS_TRY_HIP(pl->wlog.alloc(rows));
-    SPRS_TRY_HIP(pl->ntasks.alloc(rows * 8));
-    SPRS_TRY_HIP(pl->first_task.alloc((rows + 1) * 8));
-    SPRS_TRY_HIP(cls.alloc(rows));
-    SPRS_TRY_HIP(pos_large.alloc((rows + 1) * 8));
+    SPRS_TRY_HIP(pl->ub.alloc_pooled(rows * 8));
+    SPRS_TRY_HIP(pl->wlog.alloc_pooled(rows));
+    SPRS_TRY_HIP(pl->ntasks.alloc_pooled(rows * 8));
+    SPRS_TRY_HIP(pl->first_task.alloc_pooled((rows + 1) * 8));
+    SPRS_TRY_HIP(cls.alloc_pooled(rows));
+    SPRS_TRY_HIP(pos_large.alloc_pooled((rows + 1) * 8));
     // micro rows (lane groups): columns of B below EMPTY, entries of B below 2^40 (the extent word of an entry of A)
     const bool micro = options().spgemm_micro != 2 && b_cols < 0xFFFFFFFFull && (uint64_t)b->nnz <= EXT_START;
-    if (micro) SPRS_TRY_HIP(pl->ent_ext.alloc((a->nnz ? a->nnz : 1) * sizeof(uint64_t)));
+    if (micro) SPRS_TRY_HIP(pl->ent_ext.alloc_pooled((a->nnz ? a->nnz : 1) * sizeof(uint64_t)));
     // blocks of the class counts (see class_counts_kernel): 2048 rows each, more when that would be more than 65 536 blocks
     uint64_t cls_rb = 2048;
     while ((rows + cls_rb - 1) / cls_rb > 65536) cls_rb *= 2;
     const uint64_t cls_blocks = rows ? (rows + cls_rb - 1) / cls_rb : 1;
-    SPRS_TRY_HIP(class_sums.alloc(cls_blocks * CLS_NV * 8));
-    SPRS_TRY_HIP(class_totals.alloc(CLS_NV * 8));
+    SPRS_TRY_HIP(class_sums.alloc_pooled(cls_blocks * CLS_NV * 8));
+    SPRS_TRY_HIP(class_totals.alloc_pooled(CLS_NV * 8));
     if (rows) {
         uint64_t blocks = (rows + 3) / 4;
         if (blocks > 256 * 64) blocks = 256 * 64;
@@ -2024,7 +2029,7 @@ int32_t plan_build(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_sp
                        class_totals.as<uint64_t>(), pl->first_task.as<uint64_t>(), rows);
     SPRS_TRY_HIP(hipGetLastError());
     uint64_t totals[CLS_NV];
-    SPRS_TRY_HIP(hipMemcpy(totals, class_totals.p, sizeof(totals), hipMemcpyDeviceToHost));     // the one read-back that sizes the lists
+    SPRS_TRY_HIP(copy_to_host(totals, class_totals.p, sizeof(totals), stream));     // the one read-back that sizes the lists
     pl->ntask_total = totals[0];
     pl->n_large = totals[1];
     pl->n_tiny = totals[2];
@@ -2032,18 +2037,18 @@ int32_t plan_build(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_sp
     pl->n_mid = totals[4];
     for (int m = 0; m < 3; ++m) pl->n_micro[m] = totals[5 + m];
     const uint64_t ntask_total = pl->ntask_total, n_small = pl->n_small, n_mid = pl->n_mid, n_large = pl->n_large, n_tiny = pl->n_tiny;
-    for (int m = 0; m < 3; ++m) SPRS_TRY_HIP(pl->micro_list[m].alloc((pl->n_micro[m] ? pl->n_micro[m] : 1) * sizeof(MicroRec)));
+    for (int m = 0; m < 3; ++m) SPRS_TRY_HIP(pl->micro_list[m].alloc_pooled((pl->n_micro[m] ? pl->n_micro[m] : 1) * sizeof(MicroRec)));
     if (n_large > 0x7fffffffull) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "too many SpGEMM tasks for one launch");
 
-    SPRS_TRY_HIP(pl->task_row.alloc(ntask_total * 8));
-    SPRS_TRY_HIP(pl->tiny_list.alloc(n_tiny * 8));
-    SPRS_TRY_HIP(pl->small_list.alloc(n_small * 8));
-    SPRS_TRY_HIP(pl->mid_list.alloc(n_mid * 8));
-    SPRS_TRY_HIP(pl->large_list.alloc(n_large * 8));
-    SPRS_TRY_HIP(large_key.alloc(n_large * 8));
-    SPRS_TRY_HIP(mid_key.alloc(n_mid * 8));
-    SPRS_TRY_HIP(pl->count.alloc(ntask_total * 8));
-    SPRS_TRY_HIP(pl->off.alloc((ntask_total + 1) * 8));
+    SPRS_TRY_HIP(pl->task_row.alloc_pooled(ntask_total * 8));
+    SPRS_TRY_HIP(pl->tiny_list.alloc_pooled(n_tiny * 8));
+    SPRS_TRY_HIP(pl->small_list.alloc_pooled(n_small * 8));
+    SPRS_TRY_HIP(pl->mid_list.alloc_pooled(n_mid * 8));
+    SPRS_TRY_HIP(pl->large_list.alloc_pooled(n_large * 8));
+    SPRS_TRY_HIP(large_key.alloc_pooled(n_large * 8));
+    SPRS_TRY_HIP(mid_key.alloc_pooled(n_mid * 8));
+    SPRS_TRY_HIP(pl->count.alloc_pooled(ntask_total * 8));
+    SPRS_TRY_HIP(pl->off.alloc_pooled((ntask_total + 1) * 8));
     if (rows) {
         ClassLists lists{pl->task_row.as<uint64_t>(), pl->first_task.as<uint64_t>(), pos_large.as<uint64_t>(), pl->tiny_list.as<uint64_t>(),
                          pl->small_list.as<uint64_t>(), pl->mid_list.as<uint64_t>(), pl->large_list.as<uint64_t>(), large_key.as<uint64_t>(),
@@ -2061,12 +2066,8 @@ int32_t plan_build(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_sp
         SPRS_TRY(radix_sort_pairs(mid_key.as<uint64_t>(), pl->mid_list.as<uint64_t>(), n_mid, {{0, 6}}, stream));
 
     // large rows first on the main stream (the long tasks start at once), the wave kernels beside them on the second stream
-    AuxStream *aux = options().spgemm_overlap && !options().spgemm_prof ? aux_stream() : nullptr;
-    hipStream_t wstream = aux ? aux->s : stream;
-    if (aux) {
-        SPRS_TRY_HIP(hipEventRecord(aux->fork, stream));
-        SPRS_TRY_HIP(hipStreamWaitEvent(aux->s, aux->fork, 0));
-    }
+    AuxFork aux(stream);
+    const hipStream_t wstream = aux.wave;
     // ONE launch for all large tasks, in the LDS layout of the window width (option spgemm_winlog)
     if (n_large) {
         const dim3 g((unsigned)n_large), blk(LG_BLOCK);
@@ -2084,7 +2085,7 @@ int32_t plan_build(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_sp
             const uint64_t bytes = n_large * words_row * 8;
             size_t free_b = 0, total_b = 0;
             if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && bytes <= (16ull << 30) && bytes <= free_b / 4 &&
-                pl->kept_bm.alloc(bytes) == hipSuccess) {
+                pl->kept_bm.alloc_pooled(bytes) == hipSuccess) {
                 pl->kept_words = words_row;
             } else {
                 (void)hipGetLastError();
@@ -2151,7 +2152,7 @@ int32_t plan_build(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_sp
                        pl->mid_list.as<uint64_t>(), n_mid, pl->task_row.as<uint64_t>(), pl->count.as<uint64_t>(),    \
                        (const uint64_t *)nullptr, (IDX *)nullptr, (double *)nullptr, (unsigned long long *)nullptr, (const uint64_t *)nullptr, \
                        pl->counters.as<unsigned int>(), 0u)
-        SPRS_TRY_HIP(pl->counters.alloc(64));
+        SPRS_TRY_HIP(pl->counters.alloc_pooled(64));
         SPRS_TRY_HIP(hipMemsetAsync(pl->counters.p, 0, 64, wstream));
         // the counting kernel has no accumulators: windows of 2^16 columns (four times fewer window prologues per row)
         const bool k16 = options().spgemm_mid_keep_sym >= 16;
@@ -2160,13 +2161,10 @@ int32_t plan_build(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_sp
 #undef SPRS_MID_SYM
         SPRS_TRY_HIP(hipGetLastError());
     }
-    if (aux) {
-        SPRS_TRY_HIP(hipEventRecord(aux->join, aux->s));
-        SPRS_TRY_HIP(hipStreamWaitEvent(stream, aux->join, 0));
-    }
+    SPRS_TRY_HIP(aux.join());
     // ---- prefix sum of the counts -> offsets, C.indptr (smmp.rs:320-331) ----
     SPRS_TRY(exclusive_scan_u64(pl->count.as<uint64_t>(), pl->off.as<uint64_t>(), ntask_total, stream));
-    SPRS_TRY_HIP(hipMemcpy(&pl->c_nnz, pl->off.as<uint64_t>() + ntask_total, 8, hipMemcpyDeviceToHost));
+    SPRS_TRY_HIP(copy_to_host(&pl->c_nnz, pl->off.as<uint64_t>() + ntask_total, 8, stream));
     if (sizeof(PTR) == 4 && pl->c_nnz > 0xFFFFFFFFull)
         SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "Index type is not large enough to hold the nnz of the product (%llu)",
                   (unsigned long long)pl->c_nnz);   // Iptr::from_usize, smmp.rs:121
@@ -2184,7 +2182,7 @@ int32_t plan_run(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, const sprs_h
     B.col32 = sizeof(IDX) == 4 ? (const uint32_t *)b->indices : pl->bcol32.as<uint32_t>();
     if (values && (pl->n_mid || pl->n_large)) {
         // {column, value} records of B for the value walks; rebuilt per call: the values of b may have changed since the plan was made
-        SPRS_TRY_HIP(pl->bpack.alloc((b->nnz ? b->nnz : 1) * sizeof(BRec)));
+        SPRS_TRY_HIP(pl->bpack.alloc_pooled((b->nnz ? b->nnz : 1) * sizeof(BRec)));
         if (b->nnz) {
             hipLaunchKernelGGL((pack_entries_kernel<IDX>), dim3(2048), dim3(256), 0, stream, B.indices, B.data, b->nnz, pl->bpack.as<BRec>());
             SPRS_TRY_HIP(hipGetLastError());
@@ -2199,12 +2197,8 @@ int32_t plan_run(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, const sprs_h
         if (g > 256 * 32) g = 256 * 32;
         return dim3((unsigned)g);
     };
-    AuxStream *aux = options().spgemm_overlap && !options().spgemm_prof ? aux_stream() : nullptr;
-    hipStream_t wstream = aux ? aux->s : stream;
-    if (aux) {
-        SPRS_TRY_HIP(hipEventRecord(aux->fork, stream));
-        SPRS_TRY_HIP(hipStreamWaitEvent(aux->s, aux->fork, 0));
-    }
+    AuxFork aux(stream);
+    const hipStream_t wstream = aux.wave;
     if (n_large) {
         const dim3 g((unsigned)n_large), blk(LG_BLOCK);
         // bit 2: the adds of a workgroup's waves are NOT put in the reference's order (option spgemm_ordered = 0: every C(i,j) still
@@ -2222,7 +2216,7 @@ int32_t plan_run(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, const sprs_h
                        pl->large_slot.as<uint64_t>(), pl->kept_words ? pl->kept_bm.as<unsigned long long>() : (unsigned long long *)nullptr, pl->kept_words)
         DevBuf prof;
         if (DEVTOOLS && options().spgemm_prof) {
-            SPRS_TRY_HIP(prof.alloc((n_large + 40) * 8));
+            SPRS_TRY_HIP(prof.alloc_pooled((n_large + 40) * 8));
             SPRS_TRY_HIP(hipMemsetAsync(prof.p, 0, (n_large + 40) * 8, stream));
         }
         const bool occ3 = options().spgemm_occupancy != 2;
@@ -2237,19 +2231,19 @@ int32_t plan_run(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, const sprs_h
             // debug: 100 MHz ticks per large task, by block (= position in the launch order)
             SPRS_TRY_HIP(hipStreamSynchronize(stream));
             unsigned long long phs[40];
-            (void)hipMemcpy(phs, (char *)prof.p + n_large * 8, 320, hipMemcpyDeviceToHost);
+            (void)copy_to_host(phs, (char *)prof.p + n_large * 8, 320, stream);
             for (int c = 0; c < 5; ++c)
                 fprintf(stderr, "[spgemm_prof] class %d, thread-0 time by phase (ms of workgroup time): prologue %.1f, stage+bits %.1f, prefix %.1f, "
                                 "emit %.1f, values %.1f, flush+clear %.1f\n", c, phs[c * 8 + 0] / 1e5, phs[c * 8 + 1] / 1e5, phs[c * 8 + 2] / 1e5,
                         phs[c * 8 + 3] / 1e5, phs[c * 8 + 4] / 1e5, phs[c * 8 + 5] / 1e5);
             std::vector<unsigned long long> tk(n_large), lst(n_large), trow(pl->ntask_total), ubv(pl->rows), ntk(pl->rows);
-            (void)hipMemcpy(tk.data(), prof.p, n_large * 8, hipMemcpyDeviceToHost);
-            (void)hipMemcpy(lst.data(), pl->large_list.p, n_large * 8, hipMemcpyDeviceToHost);
-            (void)hipMemcpy(trow.data(), pl->task_row.p, pl->ntask_total * 8, hipMemcpyDeviceToHost);
-            (void)hipMemcpy(ubv.data(), pl->ub.p, pl->rows * 8, hipMemcpyDeviceToHost);
-            (void)hipMemcpy(ntk.data(), pl->ntasks.p, pl->rows * 8, hipMemcpyDeviceToHost);
+            (void)copy_to_host(tk.data(), prof.p, n_large * 8, stream);
+            (void)copy_to_host(lst.data(), pl->large_list.p, n_large * 8, stream);
+            (void)copy_to_host(trow.data(), pl->task_row.p, pl->ntask_total * 8, stream);
+            (void)copy_to_host(ubv.data(), pl->ub.p, pl->rows * 8, stream);
+            (void)copy_to_host(ntk.data(), pl->ntasks.p, pl->rows * 8, stream);
             std::vector<uint64_t> a_ip(pl->rows + 1);
-            if (sizeof(PTR) == 8) (void)hipMemcpy(a_ip.data(), a->indptr, (pl->rows + 1) * 8, hipMemcpyDeviceToHost);
+            if (sizeof(PTR) == 8) (void)copy_to_host(a_ip.data(), a->indptr, (pl->rows + 1) * 8, stream);
             double sum = 0;
             unsigned long long mx = 0;
             // classes by products per task: < 2^13, < 2^15, < 2^17, < 2^19, rest
@@ -2318,7 +2312,7 @@ int32_t plan_run(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, const sprs_h
         if (g > 256 * 12) g = 256 * 12;
         DevBuf mprof;
         if (DEVTOOLS && options().spgemm_prof) {
-            SPRS_TRY_HIP(mprof.alloc(256));
+            SPRS_TRY_HIP(mprof.alloc_pooled(256));
             SPRS_TRY_HIP(hipMemsetAsync(mprof.p, 0, 256, stream));
         }
 #define SPRS_MID_NUM(WL, KP)                                                                                             \
@@ -2335,7 +2329,7 @@ int32_t plan_run(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, const sprs_h
         if (DEVTOOLS && mprof.p) {
             unsigned long long h[32];
             SPRS_TRY_HIP(hipStreamSynchronize(stream));
-            (void)hipMemcpy(h, mprof.p, 256, hipMemcpyDeviceToHost);
+            (void)copy_to_host(h, mprof.p, 256, stream);
             fprintf(stderr, "[spgemm_prof] mid rows by products (< 2048, < 8192, < 32768, rest): %llu rows %.1f ms | %llu rows %.1f ms | %llu rows %.1f ms | "
                             "%llu rows %.1f ms of wave time; longest row %.3f ms; waves %llu, mean wave %.3f ms, longest wave %.3f ms\n",
                     h[9], h[8] / 1e5, h[11], h[10] / 1e5, h[13], h[12] / 1e5, h[15], h[14] / 1e5, h[16] / 1e5, h[19],
@@ -2345,10 +2339,7 @@ int32_t plan_run(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, const sprs_h
                     h[4] / 1e5, h[5] / 1e5);
         }
     }
-    if (aux) {
-        SPRS_TRY_HIP(hipEventRecord(aux->join, aux->s));
-        SPRS_TRY_HIP(hipStreamWaitEvent(stream, aux->join, 0));
-    }
+    SPRS_TRY_HIP(aux.join());
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e != hipSuccess) return fail_hip(e, "spgemm numeric");
@@ -2366,12 +2357,12 @@ int32_t plan_indptr(sprs_hip_spgemm_plan *pl, sprs_hip_csmat *c, bool compare) {
         return SPRS_HIP_OK;
     }
     DevBuf flag;
-    SPRS_TRY_HIP(flag.alloc(4));
+    SPRS_TRY_HIP(flag.alloc_pooled(4));
     SPRS_TRY_HIP(hipMemsetAsync(flag.p, 0, 4, stream));
     hipLaunchKernelGGL((compare_indptr_kernel<PTR>), g, b, 0, stream, pl->first_task.as<uint64_t>(), pl->off.as<uint64_t>(),
                        pl->rows, (const PTR *)c->indptr, flag.as<unsigned int>());
     unsigned int bad = 0;
-    SPRS_TRY_HIP(hipMemcpy(&bad, flag.p, 4, hipMemcpyDeviceToHost));
+    SPRS_TRY_HIP(copy_to_host(&bad, flag.p, 4, stream));
     if (bad) SPRS_FAIL(SPRS_HIP_BAD_STRUCTURE, "numeric: the indptr of C is not the product's");
     return SPRS_HIP_OK;
 }

@@ -478,15 +478,6 @@ __global__ __launch_bounds__(MM_BLOCK) void spmm_stream_fixup_kernel(const PTR *
     }
 }
 
-struct Tmp {
-    void *p = nullptr;
-    ~Tmp() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(uint64_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-    uint64_t *u64() { return (uint64_t *)p; }
-};
-
 template <typename PTR>
 int32_t build_spmm_plan(sprs_hip_csmat *a, bool stream_mode, hipStream_t stream) {
     SpmmPlan &pl = a->mm;
@@ -504,7 +495,7 @@ int32_t build_spmm_plan(sprs_hip_csmat *a, bool stream_mode, hipStream_t stream)
         pl.built = true;
         return SPRS_HIP_OK;
     }
-    Tmp nch, mflag, mpos;
+    DevBuf nch, mflag, mpos;
     SPRS_TRY_HIP(nch.alloc(rows * 8));
     SPRS_TRY_HIP(mflag.alloc(rows * 8));
     SPRS_TRY_HIP(mpos.alloc((rows + 1) * 8));
@@ -514,8 +505,8 @@ int32_t build_spmm_plan(sprs_hip_csmat *a, bool stream_mode, hipStream_t stream)
     SPRS_TRY_HIP(hipGetLastError());
     SPRS_TRY(exclusive_scan_u64(nch.u64(), pl.first_chunk, rows, stream));
     SPRS_TRY(exclusive_scan_u64(mflag.u64(), mpos.u64(), rows, stream));
-    SPRS_TRY_HIP(hipMemcpy(&pl.nchunks, pl.first_chunk + rows, 8, hipMemcpyDeviceToHost));
-    SPRS_TRY_HIP(hipMemcpy(&pl.n_multi, mpos.u64() + rows, 8, hipMemcpyDeviceToHost));
+    SPRS_TRY_HIP(copy_to_host(&pl.nchunks, pl.first_chunk + rows, 8, stream));
+    SPRS_TRY_HIP(copy_to_host(&pl.n_multi, mpos.u64() + rows, 8, stream));
     SPRS_TRY_HIP(hipMalloc((void **)&pl.chunk_row, (pl.nchunks ? pl.nchunks : 1) * 8));
     SPRS_TRY_HIP(hipMalloc((void **)&pl.multi_rows, (pl.n_multi ? pl.n_multi : 1) * 8));
     hipLaunchKernelGGL(fill_chunks_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, pl.first_chunk,

@@ -491,8 +491,8 @@ static int32_t make_tile_rows(CsrPiece &pc, uint32_t TILE, hipStream_t stream) {
 
 // re-layout of the long rows / short rows into plan-owned pieces whose column ids are CIDX
 template <typename IDX, typename PTR, typename CIDX>
-static int32_t build_sliced(sprs_hip_csmat *a, uint64_t nnz_short, uint64_t n_long, TmpBuf &long_flag,
-                            TmpBuf &short_ptr, TmpBuf &long_pos, hipStream_t stream) {
+static int32_t build_sliced(sprs_hip_csmat *a, uint64_t nnz_short, uint64_t n_long, DevBuf &long_flag,
+                            DevBuf &short_ptr, DevBuf &long_pos, hipStream_t stream) {
     SpmvPlan &pl = a->plan;
     const uint64_t rows = a->rows;
     const PTR *ip = (const PTR *)a->indptr;
@@ -520,7 +520,7 @@ static int32_t build_sliced(sprs_hip_csmat *a, uint64_t nnz_short, uint64_t n_lo
     SPRS_TRY_HIP(hipGetLastError());
 
     // ---- long part: count, scan, scatter ------------------------------------------
-    TmpBuf cnt;
+    DevBuf cnt;
     SPRS_TRY_HIP(cnt.alloc(XCS_SLICES * n_long * 8));
     uint64_t wblocks = (n_long + NWAVES - 1) / NWAVES;
     if (wblocks > 256 * 64) wblocks = 256 * 64;
@@ -534,7 +534,7 @@ static int32_t build_sliced(sprs_hip_csmat *a, uint64_t nnz_short, uint64_t n_lo
         sl.owns = true;
         SPRS_TRY_HIP(hipMalloc(&sl.indptr, (n_long + 1) * sizeof(uint64_t)));
         SPRS_TRY(exclusive_scan_u64(cnt.u64() + (uint64_t)s * n_long, (uint64_t *)sl.indptr, n_long, stream));
-        SPRS_TRY_HIP(hipMemcpy(&sl.nnz, (uint64_t *)sl.indptr + n_long, 8, hipMemcpyDeviceToHost));
+        SPRS_TRY_HIP(copy_to_host(&sl.nnz, (uint64_t *)sl.indptr + n_long, 8, stream));
         SPRS_TRY_HIP(hipMalloc(&sl.indices, (sl.nnz ? sl.nnz : 4) * sizeof(CIDX)));
         SPRS_TRY_HIP(hipMalloc((void **)&sl.data, (sl.nnz ? sl.nnz : 2) * sizeof(double)));
         so.ptr[s] = (const uint64_t *)sl.indptr;
@@ -621,7 +621,7 @@ static int32_t build_plan(sprs_hip_csmat *a, hipStream_t stream, bool light = fa
             return SPRS_HIP_OK;
         }
     }
-    TmpBuf short_len, long_flag, short_ptr, long_pos;
+    DevBuf short_len, long_flag, short_ptr, long_pos;
     uint64_t nnz_short = 0, n_long = 0;
     if (want) {
         SPRS_TRY_HIP(short_len.alloc(rows * 8));
@@ -633,8 +633,8 @@ static int32_t build_plan(sprs_hip_csmat *a, hipStream_t stream, bool light = fa
         SPRS_TRY_HIP(hipGetLastError());
         SPRS_TRY(exclusive_scan_u64(short_len.u64(), short_ptr.u64(), rows, stream));
         SPRS_TRY(exclusive_scan_u64(long_flag.u64(), long_pos.u64(), rows, stream));
-        SPRS_TRY_HIP(hipMemcpy(&nnz_short, short_ptr.u64() + rows, 8, hipMemcpyDeviceToHost));
-        SPRS_TRY_HIP(hipMemcpy(&n_long, long_pos.u64() + rows, 8, hipMemcpyDeviceToHost));
+        SPRS_TRY_HIP(copy_to_host(&nnz_short, short_ptr.u64() + rows, 8, stream));
+        SPRS_TRY_HIP(copy_to_host(&n_long, long_pos.u64() + rows, 8, stream));
         // auto mode: slice only if the long rows carry most of the entries
         if (n_long == 0 || (o.spmv_xcs == 0 && (nnz - nnz_short) * 2 < nnz)) want = false;
     }
@@ -677,14 +677,14 @@ static int32_t get_scratch(SpmvPlan &pl, hipStream_t stream, SpmvScratch **out) 
             SPRS_TRY_HIP(hipMalloc((void **)&sc.partial, poff + sizeof(SlicedArgs)));
             // a slice without entries launches no tile, so nobody ever writes its partials: they must read as
             // zero (fresh hipMalloc memory usually does, recycled memory does not)
-            SPRS_TRY_HIP(hipMemset(sc.partial, 0, poff));
+            SPRS_TRY_HIP(hipMemsetAsync(sc.partial, 0, poff, stream));
             SlicedArgs sa;
             for (int s = 0; s < XCS_SLICES; ++s) {
                 const CsrPiece &sl = pl.slice[s];
                 sa.p[s] = TileArgs{sl.indptr, sl.indices, sl.data, sl.pos, sl.tile_row, sc.carry_slices + pl.slice_tile_off[s],
                                    sc.partial + (uint64_t)s * pl.n_long, sl.nnz, sl.ntiles};
             }
-            SPRS_TRY_HIP(hipMemcpy((uint8_t *)sc.partial + poff, &sa, sizeof sa, hipMemcpyHostToDevice));
+            SPRS_TRY_HIP(copy_to_device((uint8_t *)sc.partial + poff, &sa, sizeof sa, stream));
         }
         it = pl.scratch.emplace((void *)stream, sc).first;
     }

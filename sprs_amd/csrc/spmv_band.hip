@@ -441,7 +441,7 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, BandPlan **out) {
     const uint64_t XT = 1ull << xt_log2;
 
     // ---- row classes --------------------------------------------------------------------
-    TmpBuf short_flag, short_len, long_flag, short_pos, short_ptr, long_pos;
+    DevBuf short_flag, short_len, long_flag, short_pos, short_ptr, long_pos;
     SPRS_TRY_HIP(short_flag.alloc(rows * 8));
     SPRS_TRY_HIP(short_len.alloc(rows * 8));
     SPRS_TRY_HIP(long_flag.alloc(rows * 8));
@@ -455,9 +455,9 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, BandPlan **out) {
     SPRS_TRY(exclusive_scan_u64(short_len.u64(), short_ptr.u64(), rows, stream));
     SPRS_TRY(exclusive_scan_u64(long_flag.u64(), long_pos.u64(), rows, stream));
     uint64_t n_short_rows = 0, nnz_short = 0, n_long = 0;
-    SPRS_TRY_HIP(hipMemcpy(&n_short_rows, short_pos.u64() + rows, 8, hipMemcpyDeviceToHost));
-    SPRS_TRY_HIP(hipMemcpy(&nnz_short, short_ptr.u64() + rows, 8, hipMemcpyDeviceToHost));
-    SPRS_TRY_HIP(hipMemcpy(&n_long, long_pos.u64() + rows, 8, hipMemcpyDeviceToHost));
+    SPRS_TRY_HIP(copy_to_host(&n_short_rows, short_pos.u64() + rows, 8, stream));
+    SPRS_TRY_HIP(copy_to_host(&nnz_short, short_ptr.u64() + rows, 8, stream));
+    SPRS_TRY_HIP(copy_to_host(&n_long, long_pos.u64() + rows, 8, stream));
     if (!n_long) return SPRS_HIP_OK;
     // auto mode: only when the long rows carry most of the entries (as the XCD-sliced plan)
     if (o.spmv_band == 0 && (nnz - nnz_short) * 2 < nnz) return SPRS_HIP_OK;
@@ -516,14 +516,14 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, BandPlan **out) {
     SPRS_TRY_HIP(hipMalloc((void **)&bp->long_rows, n_long * 4));
 
     // ---- long rows: count per piece, scans, placement --------------------------------------------
-    TmpBuf cnt, nz, pos, pair, starts_d, pb_d;
+    DevBuf cnt, nz, pos, pair, starts_d, pb_d;
     SPRS_TRY_HIP(cnt.alloc(flat * 8));
     SPRS_TRY_HIP(nz.alloc(flat * 8));
     SPRS_TRY_HIP(pos.alloc((flat + 1) * 8));
     SPRS_TRY_HIP(pair.alloc((flat + 1) * 8));
     // long_rows is needed by the count kernel: fill it (and the short piece's row lists) first; the short piece's entries
     // follow once the cold arrays exist
-    TmpBuf s_rowidx_t, s_ptr_t;
+    DevBuf s_rowidx_t, s_ptr_t;
     SPRS_TRY_HIP(s_rowidx_t.alloc((n_short_rows + 1) * 4));
     SPRS_TRY_HIP(s_ptr_t.alloc((n_short_rows + 1) * 4));
     hipLaunchKernelGGL((bp_fill_short_kernel<IDX, PTR>), dim3((unsigned)((rows + 256) / 256)), dim3(256), 0, stream, ip, ix,
@@ -542,7 +542,7 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, BandPlan **out) {
                        starts_d.u64());
     SPRS_TRY_HIP(hipGetLastError());
     std::vector<uint64_t> starts(2 * (NP + 1));
-    SPRS_TRY_HIP(hipMemcpy(starts.data(), starts_d.p, starts.size() * 8, hipMemcpyDeviceToHost));
+    SPRS_TRY_HIP(copy_to_host(starts.data(), starts_d.p, starts.size() * 8, stream));
 
     std::vector<PieceBuild> pb(NP);
     bp->host_pieces.assign(NP + 1, BandPiece());
@@ -557,7 +557,7 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, BandPlan **out) {
         for (uint32_t k = (uint32_t)nh; k < NP; ++k) gather_tiles += (starts[k + 1] - starts[k] + WT - 1) / WT;
         if (o.spmv_band_cold_tiles <= 0 && gather_tiles < 128ull * (uint64_t)ncu_dev) bp->cold_tiles = 1;
     }
-    TmpBuf bucket0_d;
+    DevBuf bucket0_d;
     ShortBuckets sbk{nullptr, 1, 1};
     uint64_t nnz_short_padded = nnz_short;
     {
@@ -569,7 +569,7 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, BandPlan **out) {
                                rows, Rp, nb, bucket0_d.u64());
             SPRS_TRY_HIP(hipGetLastError());
             uint64_t last0 = 0;
-            SPRS_TRY_HIP(hipMemcpy(&last0, bucket0_d.u64() + (nb - 1), 8, hipMemcpyDeviceToHost));
+            SPRS_TRY_HIP(copy_to_host(&last0, bucket0_d.u64() + (nb - 1), 8, stream));
             sbk = ShortBuckets{(const uint64_t *)bucket0_d.u64(), Rp, R};
             nnz_short_padded = (nb - 1) * R + (nnz_short - last0);          // (the last bucket may be empty: its first row is then "the end")
             if (nnz_short_padded >= 0xFFFFFFFFull) return SPRS_HIP_OK;
@@ -635,7 +635,7 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, BandPlan **out) {
     // xp[cols] is never written and stays 0.0, so a padding product is 0 * 0 whatever x holds
     SPRS_TRY_HIP(hipMemsetAsync(bp->vals_cold, 0, (cold_ent + WT) * 8, stream));
     SPRS_TRY_HIP(hipMemsetD32Async((hipDeviceptr_t)bp->cid_cold, (int)(uint32_t)cols, cold_ent + WT, stream));
-    TmpBuf ptr_all;                                                // entry offsets of the compact rows: only the build reads them
+    DevBuf ptr_all;                                                // entry offsets of the compact rows: only the build reads them
     SPRS_TRY_HIP(ptr_all.alloc((ptr_off + n_short_rows + 2) * 4));
     SPRS_TRY_HIP(hipMalloc((void **)&bp->rowidx_all, (row_off + n_short_rows + 1) * 4));
     SPRS_TRY_HIP(hipMalloc((void **)&bp->tile_row_all, (tile_off + 1) * 4));
@@ -684,7 +684,7 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, BandPlan **out) {
         d.tile_row = bp->tile_row_all + tile_row_off[k];
         jobs[k] = TileRowJob{(const uint32_t *)ptr_all.p + po, bp->tile_row_all + tile_row_off[k], d.nr, d.ntiles, (uint32_t)WT};
     }
-    TmpBuf jobs_d;
+    DevBuf jobs_d;
     SPRS_TRY_HIP(jobs_d.alloc(jobs.size() * sizeof(TileRowJob)));
     SPRS_TRY_HIP(hipMemcpyAsync(jobs_d.p, jobs.data(), jobs.size() * sizeof(TileRowJob), hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(bp_tile_rows_kernel, dim3((max_tiles + 256) / 256, NP + 1), dim3(256), 0, stream,
@@ -727,9 +727,8 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, BandPlan **out) {
         std::vector<uint64_t> cost_pre;                               // cost of the hot tiles before tile t (slice after slice)
         const bool balance = o.spmv_band_balance == 1 || (o.spmv_band_balance == 0 && small_hot);
         if (balance && o.spmv_band_share <= 0) {
-            SPRS_TRY_HIP(hipStreamSynchronize(stream));               // bp_tile_rows_kernel
-            std::vector<uint32_t> tr(tile_off + 1);
-            SPRS_TRY_HIP(hipMemcpy(tr.data(), bp->tile_row_all, tr.size() * 4, hipMemcpyDeviceToHost));
+            std::vector<uint32_t> tr(tile_off + 1);                    // (after bp_tile_rows_kernel: same stream)
+            SPRS_TRY_HIP(copy_to_host(tr.data(), bp->tile_row_all, tr.size() * 4, stream));
             cost_pre.assign(1, 0ull);
             for (uint32_t k = 0; k < nh; ++k) {
                 const uint32_t *t = tr.data() + tile_row_off[k];
@@ -799,8 +798,7 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, BandPlan **out) {
         SPRS_TRY_HIP(hipMalloc((void **)&bp->wg_first, (wf.size() + 1) * sizeof(HotSeg)));
         SPRS_TRY_HIP(hipMemcpyAsync(bp->wg_first, wf.data(), wf.size() * sizeof(HotSeg), hipMemcpyHostToDevice, stream));
         SPRS_TRY_HIP(hipMalloc((void **)&bp->hsegs, (hs.size() + 1) * sizeof(HotSeg)));
-        SPRS_TRY_HIP(hipMemcpyAsync(bp->hsegs, hs.data(), hs.size() * sizeof(HotSeg), hipMemcpyHostToDevice, stream));
-        SPRS_TRY_HIP(hipStreamSynchronize(stream));                      // (hs goes out of scope)
+        SPRS_TRY_HIP(copy_to_device(bp->hsegs, hs.data(), hs.size() * sizeof(HotSeg), stream));   // (wf and hs go out of scope)
         bp->bytes += (hs.size() + wf.size()) * sizeof(HotSeg);
     }
 
@@ -828,14 +826,14 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, BandPlan **out) {
     }
     // ---- rows that run on from one range into the next: one record per run -----------------------------------------------
     if (nranges) {
-        TmpBuf pcs_d, poff_d, cnt_d;
+        DevBuf pcs_d, poff_d, cnt_d;
         SPRS_TRY_HIP(pcs_d.alloc(bp->host_pieces.size() * sizeof(BandPiece)));
         SPRS_TRY_HIP(poff_d.alloc(bp->pair_off.size() * 8));
         SPRS_TRY_HIP(cnt_d.alloc(8));
         SPRS_TRY_HIP(hipMemcpyAsync(pcs_d.p, bp->host_pieces.data(), bp->host_pieces.size() * sizeof(BandPiece), hipMemcpyHostToDevice, stream));
         SPRS_TRY_HIP(hipMemcpyAsync(poff_d.p, bp->pair_off.data(), bp->pair_off.size() * 8, hipMemcpyHostToDevice, stream));
         SPRS_TRY_HIP(hipMemsetAsync(cnt_d.p, 0, 8, stream));
-        TmpBuf sp_tmp;                                                                       // the long rows' records, as found (any order)
+        DevBuf sp_tmp;                                                                       // the long rows' records, as found (any order)
         SPRS_TRY_HIP(sp_tmp.alloc(((uint64_t)nranges + 1) * sizeof(Spill)));                 // at most one per range
         SPRS_TRY_HIP(hipMalloc(&bp->spills_y, ((uint64_t)nranges + 1) * sizeof(Spill)));
         hipLaunchKernelGGL(bp_spill_kernel, dim3((nranges + 255) / 256), dim3(256), 0, stream, (const Seg *)bp->segs, bp->nsegs, nranges,
@@ -844,14 +842,14 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, BandPlan **out) {
                            (unsigned int *)cnt_d.p);
         SPRS_TRY_HIP(hipGetLastError());
         uint32_t counts[2] = {0, 0};
-        SPRS_TRY_HIP(hipMemcpy(counts, cnt_d.p, 8, hipMemcpyDeviceToHost));
+        SPRS_TRY_HIP(copy_to_host(counts, cnt_d.p, 8, stream));
         bp->nspills_y = counts[0];
         bp->nspills = counts[1];
         if (bp->nspills) {
             // the reduction reads them by row block: sorted by (long row, first carry slot) — the slot order is the order of the
             // ranges, so a row's heads are added piece by piece, tile by tile — and indexed per block of 64 long rows
             std::vector<Spill> found(bp->nspills);
-            SPRS_TRY_HIP(hipMemcpy(found.data(), sp_tmp.p, found.size() * sizeof(Spill), hipMemcpyDeviceToHost));
+            SPRS_TRY_HIP(copy_to_host(found.data(), sp_tmp.p, found.size() * sizeof(Spill), stream));
             std::sort(found.begin(), found.end(), [](const Spill &a, const Spill &b) { return a.j != b.j ? a.j < b.j : a.first < b.first; });
             const uint32_t nwb = (uint32_t)((n_long + WAVE - 1) / WAVE);
             // (a lane adds the carries of its record one after the other: a hub row's run of 40 ranges is cut into records of 8)
@@ -867,8 +865,8 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, BandPlan **out) {
             for (uint32_t w = 0; w < nwb; ++w) off[w + 1] += off[w];
             SPRS_TRY_HIP(hipMalloc(&bp->rspills, recs.size() * sizeof(RSpill)));
             SPRS_TRY_HIP(hipMalloc((void **)&bp->rsp_off, off.size() * 4));
-            SPRS_TRY_HIP(hipMemcpy(bp->rspills, recs.data(), recs.size() * sizeof(RSpill), hipMemcpyHostToDevice));
-            SPRS_TRY_HIP(hipMemcpy(bp->rsp_off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
+            SPRS_TRY_HIP(copy_to_device(bp->rspills, recs.data(), recs.size() * sizeof(RSpill), stream));
+            SPRS_TRY_HIP(copy_to_device(bp->rsp_off, off.data(), off.size() * 4, stream));
             bp->bytes += recs.size() * sizeof(RSpill) + off.size() * 4;
         }
         bp->bytes += (uint64_t)counts[0] * sizeof(Spill);
@@ -899,11 +897,11 @@ int32_t band_scratch(BandPlan *bp, hipStream_t stream, BandScratch **out) {
         SPRS_TRY_HIP(hipMalloc((void **)&sc.partial, (bp->total_pairs + 1) * 8));   // every pair is written by every SpMV
         SPRS_TRY_HIP(hipMalloc((void **)&sc.carry, ((uint64_t)bp->nranges + 1) * 8));
         SPRS_TRY_HIP(hipMalloc((void **)&sc.xp, bp->cols_pad * 8));
-        SPRS_TRY_HIP(hipMemset(sc.xp, 0, bp->cols_pad * 8));      // the padding behind the last column is read into LDS
+        SPRS_TRY_HIP(hipMemsetAsync(sc.xp, 0, bp->cols_pad * 8, stream));      // the padding behind the last column is read into LDS
         std::vector<BandPiece> pcs = bp->host_pieces;
         for (uint32_t k = 0; k <= bp->npieces; ++k) pcs[k].out = k < bp->npieces ? sc.partial + bp->pair_off[k] : nullptr;
         SPRS_TRY_HIP(hipMalloc((void **)&sc.pieces, pcs.size() * sizeof(BandPiece)));
-        SPRS_TRY_HIP(hipMemcpy(sc.pieces, pcs.data(), pcs.size() * sizeof(BandPiece), hipMemcpyHostToDevice));
+        SPRS_TRY_HIP(copy_to_device(sc.pieces, pcs.data(), pcs.size() * sizeof(BandPiece), stream));
         SPRS_TRY_HIP(hipStreamCreateWithFlags(&sc.aux, hipStreamNonBlocking));
         SPRS_TRY_HIP(hipEventCreateWithFlags(&sc.fork, hipEventDisableTiming));
         SPRS_TRY_HIP(hipEventCreateWithFlags(&sc.join, hipEventDisableTiming));
@@ -999,9 +997,8 @@ int32_t band_spmv(sprs_hip_csmat *a, BandPlan *bp, const double *x, double *y, b
                                (uint32_t)options().spmv_band_debug, prof, xcd_shares);
         SPRS_TRY_HIP(hipGetLastError());
         if (DEVTOOLS && prof && getenv("SPRS_HIP_HOTPROF")) {      // (synchronous: a developer printout, not a timing run)
-            SPRS_TRY_HIP(hipStreamSynchronize(stream));
             std::vector<unsigned long long> t((size_t)bp->hot_wgs * 3);
-            SPRS_TRY_HIP(hipMemcpy(t.data(), prof, t.size() * 8, hipMemcpyDeviceToHost));
+            SPRS_TRY_HIP(copy_to_host(t.data(), prof, t.size() * 8, stream));
             unsigned long long t0 = ~0ull, t1 = 0;
             for (uint32_t b = 0; b < bp->hot_wgs; ++b) {
                 t0 = std::min(t0, t[3 * b]);

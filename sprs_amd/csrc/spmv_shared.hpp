@@ -118,15 +118,6 @@ __device__ __forceinline__ uint32_t x_slice(uint64_t col) {
     return (uint32_t)(((col >> 4) * 0x9E3779B97F4A7C15ull) >> 61);
 }
 
-struct TmpBuf {
-    void *p = nullptr;
-    ~TmpBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(uint64_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-    uint64_t *u64() { return (uint64_t *)p; }
-};
-
 
 // perm[col] = label of the column: popularity classes, most referenced first (see the rl_* kernels).
 // Allocates *perm (cols entries); the caller owns it.
@@ -134,7 +125,7 @@ template <typename IDX>
 static int32_t build_column_labels(const IDX *indices, uint64_t nnz, uint64_t cols, hipStream_t stream, uint32_t **perm,
                                    uint64_t *nref = nullptr) {
     const uint64_t nchunks = (cols + RL_CHUNK - 1) / RL_CHUNK;
-    TmpBuf ccount, hist, base;
+    DevBuf ccount, hist, base;
     SPRS_TRY_HIP(ccount.alloc(cols * 4));
     SPRS_TRY_HIP(hist.alloc((RL_DIGITS * nchunks + 1) * 8));
     SPRS_TRY_HIP(base.alloc((RL_DIGITS * nchunks + 1) * 8));
@@ -150,7 +141,7 @@ static int32_t build_column_labels(const IDX *indices, uint64_t nnz, uint64_t co
                        (const uint64_t *)base.u64(), *perm);
     SPRS_TRY_HIP(hipGetLastError());
     // the columns nobody references are the last class: its first label = the number of referenced columns
-    if (nref) SPRS_TRY_HIP(hipMemcpy(nref, base.u64() + (uint64_t)(RL_DIGITS - 1) * nchunks, 8, hipMemcpyDeviceToHost));
+    if (nref) SPRS_TRY_HIP(copy_to_host(nref, base.u64() + (uint64_t)(RL_DIGITS - 1) * nchunks, 8, stream));
     SPRS_TRY_HIP(hipStreamSynchronize(stream));   // the temporaries go away here
     return SPRS_HIP_OK;
 }

@@ -16,15 +16,6 @@ int32_t radix_sort_pairs(uint64_t *keys, uint64_t *vals, uint64_t n, const std::
 
 namespace {
 
-struct Buf {
-    void *p = nullptr;
-    ~Buf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(uint64_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-    uint64_t *u64() { return (uint64_t *)p; }
-};
-
 template <typename I>
 __global__ void tri_keys_kernel(const I *__restrict__ outer, const I *__restrict__ inner, const double *__restrict__ data, uint64_t n,
                                 uint64_t n_outer, uint64_t n_inner, uint64_t *__restrict__ keys, uint64_t *__restrict__ vals,
@@ -96,7 +87,7 @@ int32_t assemble(uint64_t rows, uint64_t cols, uint64_t n, const I *row_inds, co
         *out = c;
         return SPRS_HIP_OK;
     }
-    Buf keys, vals, head, gidx, bad;
+    DevBuf keys, vals, head, gidx, bad;
     SPRS_TRY_HIP(keys.alloc(n * 8));
     SPRS_TRY_HIP(vals.alloc(n * 8));
     SPRS_TRY_HIP(head.alloc(n * 8));
@@ -107,14 +98,14 @@ int32_t assemble(uint64_t rows, uint64_t cols, uint64_t n, const I *row_inds, co
     hipLaunchKernelGGL(tri_keys_kernel<I>, g1, b1, 0, stream, outer, inner, data, n, n_outer, n_inner, keys.u64(), vals.u64(), (unsigned int *)bad.p);
     SPRS_TRY_HIP(hipGetLastError());
     unsigned int isbad = 0;
-    SPRS_TRY_HIP(hipMemcpy(&isbad, bad.p, 4, hipMemcpyDeviceToHost));
+    SPRS_TRY_HIP(copy_to_host(&isbad, bad.p, 4, stream));
     if (isbad) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "triplet index out of bounds");
     SPRS_TRY(radix_sort_pairs(keys.u64(), vals.u64(), n, {{0, bits_for(n_inner)}, {32, bits_for(n_outer)}}, stream));
     hipLaunchKernelGGL(tri_heads_kernel, g1, b1, 0, stream, (const uint64_t *)keys.u64(), n, head.u64());
     SPRS_TRY_HIP(hipGetLastError());
     SPRS_TRY(exclusive_scan_u64(head.u64(), gidx.u64(), n, stream));
     uint64_t ngroups = 0;
-    SPRS_TRY_HIP(hipMemcpy(&ngroups, gidx.u64() + n, 8, hipMemcpyDeviceToHost));
+    SPRS_TRY_HIP(copy_to_host(&ngroups, gidx.u64() + n, 8, stream));
     if (out_iptr_bytes == 4 && ngroups > 0xFFFFFFFFull)
         SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "Index type is not large enough to hold the nnz of the matrix (%llu)", (unsigned long long)ngroups);
     SPRS_TRY(alloc_csmat(&c, storage, rows, cols, ngroups, out_iptr_bytes, out_idx_bytes));

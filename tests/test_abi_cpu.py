@@ -205,3 +205,17 @@ def test_product_never_imports_oracle():
             if f.endswith((".py", ".hip", ".hpp", ".cpp", ".h")):
                 text = open(os.path.join(dirpath, f)).read()
                 assert "oracle" not in text.lower(), "%s mentions the oracle" % os.path.join(dirpath, f)
+
+
+def test_host_copies_and_temporaries_go_through_common_hpp():
+    """Host copies run on the stream of the surrounding work (copy_to_host / copy_to_device, common.hpp) and device temporaries
+    are DevBufs: no blocking hipMemcpy / hipMemset outside those helpers, no file-local temporary-buffer struct."""
+    csrc = os.path.join(ROOT, "sprs_amd", "csrc")
+    helpers = re.compile(r"inline hipError_t copy_to_(?:host|device)\(.*?\n}\n", re.S)
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".hpp")):
+            continue
+        text = helpers.sub("", open(os.path.join(csrc, f)).read())
+        assert not re.search(r"\bhipMem(?:cpy|set)\(", text), "%s: blocking host copy outside copy_to_host / copy_to_device" % f
+        m = re.search(r"\bstruct\s+(Tmp|DevTmp|Buf|TmpBuf|Work|Free)\b", text)
+        assert not m, "%s defines its own temporary-buffer struct %s (use DevBuf, common.hpp)" % (f, m and m.group(1))

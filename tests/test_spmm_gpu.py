@@ -377,3 +377,31 @@ def test_dense_dispatch_below_the_abi(hip):
     torch.cuda.synchronize()
     _ffi.check(_ffi.lib.sprs_hip_csmat_refresh(w._h))
     assert rel_err((w * xv).to_host(), 2.0 * (m @ x)) <= TOL
+
+
+@pytest.mark.parametrize("stream_mode", [1, 0], ids=["stream", "chunks"])
+def test_plan_built_on_a_nonblocking_stream(hip, stream_mode):
+    """the SpMM plan made by a product on a torch stream (hipStreamNonBlocking: not ordered with the null stream) and used there
+    at once is the plan of the null stream — the read-backs that size the chunk lists wait for that stream's kernels: same bits
+    as a handle planned on the null stream"""
+    import torch
+    from sprs_amd import gen, prod
+    from sprs_amd.device import DeviceCsMat
+    n, k = 30000, 8
+    indptr, indices, data = gen.rmat_csr(n, 10, seed=13)
+    ip, ix, dt = indptr.numpy().astype(np.uint64), indices.numpy().astype(np.uint64), data.numpy()
+    rhs = prod.DeviceMat.from_host(np.random.default_rng(5).random((n, k)) + 0.5)
+    s = torch.cuda.Stream(device=torch.device("cuda", 0))
+    out = []
+    hip.set_option("spmm_stream", stream_mode)
+    try:
+        for stream in (s, None):
+            a = DeviceCsMat.from_host((n, n), ip, ix, dt)
+            res = prod.DeviceMat.from_host(np.zeros((n, k)))
+            prod.csr_mulacc_dense_rowmaj(a, rhs, res, stream=stream)    # the plan is built and used on `stream`
+            if stream is not None:
+                stream.synchronize()
+            out.append(res.to_host())
+    finally:
+        hip.set_option("spmm_stream", 1)
+    assert np.array_equal(out[0], out[1])

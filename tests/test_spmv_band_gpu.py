@@ -6,6 +6,8 @@ prod::mul_acc_mat_vec_csr, sprs/src/sparse/prod.rs:103-127.
 The shapes below are chosen to hit the plan's corner cases at sizes the oracle handles in seconds:
 rows spanning several hot tiles, ranges and workgroups (register and head carries), tiles full of row starts,
 hot slices without entries, a cold rest in several label ranges, every index-width combination."""
+import os
+
 import numpy as np
 import pytest
 
@@ -195,3 +197,37 @@ def test_random_shapes_and_plan_options(hip, seed):
                 split=int(rng.choice([2, 8, 24, 40])))
     with band_options(hip, hot, int(rng.integers(1, 4)), **opts):
         check_band(hip, shape, ip, ix, dt, seed=seed)
+
+
+@pytest.mark.skipif(bool(os.environ.get("SPRS_HIP_LIBRARY")), reason="torch streams: real device only")   # (the emulator run)
+@pytest.mark.parametrize("kind,opts", [(3, dict(spmv_band=1)), (2, dict(spmv_band=2, spmv_xcs=1))], ids=["banded", "sliced"])
+def test_plan_built_on_a_nonblocking_stream(hip, kind, opts):
+    """a plan prepared on a torch stream (hipStreamNonBlocking: not ordered with the null stream) and multiplied there at once
+    is the plan the null stream builds — its read-backs wait for the kernels of that stream: same kind, same bytes, same bits.
+    The banded plan of this R-MAT lays its short rows out in buckets (split 8, one wave tile per cold tile)"""
+    import torch
+    from sprs_amd import gen, prod
+    from sprs_amd.device import DeviceCsMat, DeviceVec
+    n = 200000
+    indptr, indices, data = gen.rmat_csr(n, 16, seed=5)
+    ip, ix, dt = indptr.numpy().astype(np.uint64), indices.numpy().astype(np.uint64), data.numpy()
+    assert (np.diff(ip.astype(np.int64)) < 8).any()                    # short rows: the bucketed short piece is in use
+    x = DeviceVec.from_host(gen.dense_vector(n, seed=6).numpy())
+    s = torch.cuda.Stream(device=torch.device("cuda", 0))
+    out = []
+    try:
+        for k, v in opts.items():
+            hip.set_option(k, v)
+        for stream in (s, None):
+            a = DeviceCsMat.from_host((n, n), ip, ix, dt).prepare(stream=stream)
+            y = DeviceVec.from_host(np.zeros(n))
+            prod.mul_acc_mat_vec_csr(a, x, y, stream=stream)            # no host synchronise since prepare
+            if stream is not None:
+                stream.synchronize()
+            out.append((a.spmv_plan_info(), y.to_host()))
+    finally:
+        for k in opts:
+            hip.set_option(k, 0)
+    (info_s, y_s), (info_0, y_0) = out
+    assert info_s[0] == kind and info_s == info_0
+    assert np.array_equal(y_s, y_0)
