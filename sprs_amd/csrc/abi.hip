@@ -401,12 +401,9 @@ int32_t sprs_hip_csmat_upload(sprs_hip_csmat **out, int32_t storage, uint64_t ro
     const uint64_t nnz = last - first;
     if (nnz && (!indices || !data)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL indices/data with nnz > 0");
     if (validate) {
-        int32_t st;
-        if (iptr_bytes == 8 && idx_bytes == 8) st = check_structure(inner, outer, (const uint64_t *)indptr, (const uint64_t *)indices);
-        else if (iptr_bytes == 8) st = check_structure(inner, outer, (const uint64_t *)indptr, (const uint32_t *)indices);
-        else if (idx_bytes == 8) st = check_structure(inner, outer, (const uint32_t *)indptr, (const uint64_t *)indices);
-        else st = check_structure(inner, outer, (const uint32_t *)indptr, (const uint32_t *)indices);
-        SPRS_TRY(st);
+        SPRS_TRY(dispatch_widths(idx_bytes, iptr_bytes, [&](auto i, auto p) {
+            return check_structure(inner, outer, (const typename decltype(p)::type *)indptr, (const typename decltype(i)::type *)indices);
+        }));
     }
     sprs_hip_csmat *m = nullptr;
     SPRS_TRY(alloc_csmat(&m, storage, rows, cols, nnz, iptr_bytes, idx_bytes));

@@ -300,6 +300,26 @@ inline hipError_t copy_to_device(void *dst, const void *src, uint64_t bytes, hip
     return e == hipSuccess ? hipStreamSynchronize(stream) : e;
 }
 
+// ---- index-width dispatch ------------------------------------------------------------------------------
+// A handle's indices (I) and indptr (Iptr) are 4 or 8 bytes wide.  dispatch_widths calls f(TypeTag<IDX>{}, TypeTag<PTR>{})
+// with the two types — a generic lambda names them as `typename decltype(i)::type` — and returns what f returns; every pair
+// other than (8, 8), (4, 8), (8, 4) takes (4, 4).  dispatch_width is the same for one width.
+template <typename T>
+struct TypeTag {
+    using type = T;
+};
+template <typename F>
+auto dispatch_widths(int32_t idx_bytes, int32_t iptr_bytes, F &&f) {
+    if (idx_bytes == 8 && iptr_bytes == 8) return f(TypeTag<uint64_t>{}, TypeTag<uint64_t>{});
+    if (idx_bytes == 4 && iptr_bytes == 8) return f(TypeTag<uint32_t>{}, TypeTag<uint64_t>{});
+    if (idx_bytes == 8 && iptr_bytes == 4) return f(TypeTag<uint64_t>{}, TypeTag<uint32_t>{});
+    return f(TypeTag<uint32_t>{}, TypeTag<uint32_t>{});
+}
+template <typename F>
+auto dispatch_width(int32_t bytes, F &&f) {
+    return bytes == 8 ? f(TypeTag<uint64_t>{}) : f(TypeTag<uint32_t>{});
+}
+
 // a temporary handle (a converted operand, a slice): freed with the scope that made it
 struct CsmatFree {
     void operator()(sprs_hip_csmat *m) const { sprs_hip_csmat_free(m); }

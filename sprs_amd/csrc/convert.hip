@@ -285,17 +285,15 @@ int32_t slice_impl(const sprs_hip_csmat *m, uint64_t start, uint64_t end, sprs_h
 }  // namespace
 
 int32_t to_other_storage(const sprs_hip_csmat *m, sprs_hip_csmat **out) {
-    if (m->idx_bytes == 8 && m->iptr_bytes == 8) return convert_impl<uint64_t, uint64_t>(m, out);
-    if (m->idx_bytes == 4 && m->iptr_bytes == 8) return convert_impl<uint32_t, uint64_t>(m, out);
-    if (m->idx_bytes == 8 && m->iptr_bytes == 4) return convert_impl<uint64_t, uint32_t>(m, out);
-    return convert_impl<uint32_t, uint32_t>(m, out);
+    return dispatch_widths(m->idx_bytes, m->iptr_bytes, [&](auto i, auto p) {
+        return convert_impl<typename decltype(i)::type, typename decltype(p)::type>(m, out);
+    });
 }
 
 int32_t slice_outer(const sprs_hip_csmat *m, uint64_t start, uint64_t end, sprs_hip_csmat **out) {
-    if (m->idx_bytes == 8 && m->iptr_bytes == 8) return slice_impl<uint64_t, uint64_t>(m, start, end, out);
-    if (m->idx_bytes == 4 && m->iptr_bytes == 8) return slice_impl<uint32_t, uint64_t>(m, start, end, out);
-    if (m->idx_bytes == 8 && m->iptr_bytes == 4) return slice_impl<uint64_t, uint32_t>(m, start, end, out);
-    return slice_impl<uint32_t, uint32_t>(m, start, end, out);
+    return dispatch_widths(m->idx_bytes, m->iptr_bytes, [&](auto i, auto p) {
+        return slice_impl<typename decltype(i)::type, typename decltype(p)::type>(m, start, end, out);
+    });
 }
 
 }  // namespace sprs_hip

@@ -289,12 +289,11 @@ int32_t csvec_check_device(const sprs_hip_csvec *v, hipStream_t s) {
     uint64_t host[2] = {~0ull, 0};
     hipError_t e = hipMemcpyAsync(bad.p, host, 16, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) {
-        if (v->idx_bytes == 8)
-            hipLaunchKernelGGL(cv::csvec_check_kernel<uint64_t>, dim3(cv::blocks_for(v->nnz)), dim3(cv::CV_BLOCK), 0, s,
-                               (const uint64_t *)v->indices, v->nnz, v->dim, bad.u64());
-        else
-            hipLaunchKernelGGL(cv::csvec_check_kernel<uint32_t>, dim3(cv::blocks_for(v->nnz)), dim3(cv::CV_BLOCK), 0, s,
-                               (const uint32_t *)v->indices, v->nnz, v->dim, bad.u64());
+        dispatch_width(v->idx_bytes, [&](auto i) {
+            using I = typename decltype(i)::type;
+            hipLaunchKernelGGL(cv::csvec_check_kernel<I>, dim3(cv::blocks_for(v->nnz)), dim3(cv::CV_BLOCK), 0, s, (const I *)v->indices,
+                               v->nnz, v->dim, bad.u64());
+        });
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = copy_to_host(host, bad.p, 16, s);
@@ -307,12 +306,11 @@ int32_t csvec_check_device(const sprs_hip_csvec *v, hipStream_t s) {
 int32_t csvec_scatter(const sprs_hip_csvec *v, double *out, hipStream_t s) {
     if (v->dim) SPRS_TRY_HIP(hipMemsetAsync(out, 0, v->dim * 8, s));
     if (v->nnz) {
-        if (v->idx_bytes == 8)
-            hipLaunchKernelGGL(cv::csvec_scatter_kernel<uint64_t>, dim3(cv::blocks_for(v->nnz)), dim3(cv::CV_BLOCK), 0, s,
-                               (const uint64_t *)v->indices, v->data, v->nnz, v->dim, out);
-        else
-            hipLaunchKernelGGL(cv::csvec_scatter_kernel<uint32_t>, dim3(cv::blocks_for(v->nnz)), dim3(cv::CV_BLOCK), 0, s,
-                               (const uint32_t *)v->indices, v->data, v->nnz, v->dim, out);
+        dispatch_width(v->idx_bytes, [&](auto i) {
+            using I = typename decltype(i)::type;
+            hipLaunchKernelGGL(cv::csvec_scatter_kernel<I>, dim3(cv::blocks_for(v->nnz)), dim3(cv::CV_BLOCK), 0, s, (const I *)v->indices,
+                               v->data, v->nnz, v->dim, out);
+        });
         SPRS_TRY_HIP(hipGetLastError());
     }
     return SPRS_HIP_OK;
@@ -337,19 +335,17 @@ int32_t csvec_masked_dot(const sprs_hip_csmat *mc, const sprs_hip_csvec *v, bool
     const CsvecScratch &s = m->cv;
     if (n) SPRS_TRY_HIP(hipMemsetAsync(s.bits, 0, (n + 31) / 32 * 4, st));
     if (v->nnz) {
-        if (v->idx_bytes == 8)
-            hipLaunchKernelGGL(cv::csvec_mark_kernel<uint64_t>, dim3(cv::blocks_for(v->nnz)), dim3(cv::CV_BLOCK), 0, st,
-                               (const uint64_t *)v->indices, v->data, v->nnz, n, s.bits, s.vals);
-        else
-            hipLaunchKernelGGL(cv::csvec_mark_kernel<uint32_t>, dim3(cv::blocks_for(v->nnz)), dim3(cv::CV_BLOCK), 0, st,
-                               (const uint32_t *)v->indices, v->data, v->nnz, n, s.bits, s.vals);
+        dispatch_width(v->idx_bytes, [&](auto i) {
+            using I = typename decltype(i)::type;
+            hipLaunchKernelGGL(cv::csvec_mark_kernel<I>, dim3(cv::blocks_for(v->nnz)), dim3(cv::CV_BLOCK), 0, st, (const I *)v->indices,
+                               v->data, v->nnz, n, s.bits, s.vals);
+        });
     }
     if (ngroups) {
         const int dz = drop_zero ? 1 : 0;
-        if (m->iptr_bytes == 8 && m->idx_bytes == 8) launch_dot<uint64_t, uint64_t>(m, n, s, dz, st);
-        else if (m->iptr_bytes == 8) launch_dot<uint64_t, uint32_t>(m, n, s, dz, st);
-        else if (m->idx_bytes == 8) launch_dot<uint32_t, uint64_t>(m, n, s, dz, st);
-        else launch_dot<uint32_t, uint32_t>(m, n, s, dz, st);
+        dispatch_widths(m->idx_bytes, m->iptr_bytes, [&](auto i, auto p) {
+            launch_dot<typename decltype(p)::type, typename decltype(i)::type>(m, n, s, dz, st);     // (indptr type first)
+        });
     }
     SPRS_TRY_HIP(hipGetLastError());
     uint64_t *offs = s.groups + 2 * ngroups;
@@ -366,12 +362,11 @@ int32_t csvec_masked_dot(const sprs_hip_csmat *mc, const sprs_hip_csvec *v, bool
         uint32_t flag = 0;
         hipError_t e = hipMemsetAsync(overflow, 0, 4, st);
         if (e == hipSuccess) {
-            if (idx_bytes == 8)
-                hipLaunchKernelGGL(cv::csvec_emit_kernel<uint64_t>, dim3(cv::blocks_for(nouter)), dim3(cv::CV_BLOCK), 0, st, s.groups,
-                                   offs, s.sums, nouter, limit, (uint64_t *)res->indices, res->data, overflow);
-            else
-                hipLaunchKernelGGL(cv::csvec_emit_kernel<uint32_t>, dim3(cv::blocks_for(nouter)), dim3(cv::CV_BLOCK), 0, st, s.groups,
-                                   offs, s.sums, nouter, limit, (uint32_t *)res->indices, res->data, overflow);
+            dispatch_width(idx_bytes, [&](auto i) {
+                using I = typename decltype(i)::type;
+                hipLaunchKernelGGL(cv::csvec_emit_kernel<I>, dim3(cv::blocks_for(nouter)), dim3(cv::CV_BLOCK), 0, st, s.groups, offs, s.sums,
+                                   nouter, limit, (I *)res->indices, res->data, overflow);
+            });
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = copy_to_host(&flag, overflow, 4, st);

@@ -804,10 +804,9 @@ int32_t gauss_seidel_f64(sprs_hip_csmat *a, double *x, const double *rhs, uint64
         if (info) *info = sprs_hip_gauss_seidel_info{max_iter && !(0.0 < eps) ? max_iter : 0, 0.0, (max_iter && 0.0 < eps) ? 1 : 0, 0};
         return SPRS_HIP_OK;
     }
-    if (a->idx_bytes == 8 && a->iptr_bytes == 8) return gs_impl<uint64_t, uint64_t>(a, x, rhs, n, max_iter, eps, info, stream);
-    if (a->idx_bytes == 4 && a->iptr_bytes == 8) return gs_impl<uint32_t, uint64_t>(a, x, rhs, n, max_iter, eps, info, stream);
-    if (a->idx_bytes == 8 && a->iptr_bytes == 4) return gs_impl<uint64_t, uint32_t>(a, x, rhs, n, max_iter, eps, info, stream);
-    return gs_impl<uint32_t, uint32_t>(a, x, rhs, n, max_iter, eps, info, stream);
+    return dispatch_widths(a->idx_bytes, a->iptr_bytes, [&](auto i, auto p) {
+        return gs_impl<typename decltype(i)::type, typename decltype(p)::type>(a, x, rhs, n, max_iter, eps, info, stream);
+    });
 }
 
 }  // namespace sprs_hip

@@ -1936,6 +1936,143 @@ bool lds_lane_order_ok() {
 // what the wave kernels are told about the adds (bit 0: one ds_add_f64 per wave instruction)
 uint32_t add_flags() { return options().spgemm_lane_order != 2 && lds_lane_order_ok() ? 1u : 0u; }
 
+// ---- the launches of one phase ------------------------------------------------------------------------------------
+// Counting (plan_build, NUMERIC = false) and numeric (plan_run, NUMERIC = true) launch the same kernel families over the plan's task
+// lists.  PhaseArgs holds what differs between them; a launch_* picks its instantiation from the plan and the options.
+template <typename IDX, typename PTR>
+struct PhaseArgs {
+    CsrView<IDX, PTR> A, B;                // (numeric: B with its {column, value} records)
+    const uint64_t *off = nullptr;         // offsets of the tasks' outputs (numeric)
+    const uint64_t *ub = nullptr;          // products per row for the workgroup and wave-per-row kernels (numeric; the hash kernels always read the plan's)
+    IDX *c_indices = nullptr;              // (null: not written)
+    double *c_values = nullptr;
+    uint32_t large_flags = 0, hash_flags = 0, bin_shift = 0, mid_flags = 0;
+    unsigned long long *large_prof = nullptr, *mid_prof = nullptr;      // developer build, option spgemm_prof
+    uint32_t counter_slot = 0;             // the word of pl->counters the wave-per-row kernel draws its rows from
+};
+
+// pl->counters, made by plan_build: the counting kernel draws from word 0 and the whole block is cleared in front of it; the
+// numeric kernel draws from word NUMERIC_COUNTER and only that word is cleared, so a kept plan runs numeric any number of times
+constexpr uint32_t COUNTER_BYTES = 64, NUMERIC_COUNTER = 4;
+
+template <int V>
+using Int = std::integral_constant<int, V>;
+
+dim3 small_grid(uint64_t n_tasks) {
+    uint64_t g = (n_tasks + SM_WAVES - 1) / SM_WAVES;
+    if (g > 256 * 32) g = 256 * 32;
+    return dim3((unsigned)g);
+}
+dim3 micro_grid(uint64_t n_rows, int per_wave) {
+    uint64_t g = ((n_rows + per_wave - 1) / per_wave + 3) / 4;       // four waves per block
+    if (g > 256 * 8) g = 256 * 8;                                    // what the chip holds at once; the waves stride over the list
+    return dim3((unsigned)g);
+}
+dim3 mid_grid(uint64_t n_tasks) {
+    uint64_t g = (n_tasks + MID_WAVES - 1) / MID_WAVES;
+    if (g > 256 * 12) g = 256 * 12;          // what fits the CUs at once; the waves stride over the (cost-sorted) list
+    return dim3((unsigned)g);
+}
+
+// ONE launch for all large tasks, in the LDS layout of the window width (option spgemm_winlog)
+template <bool NUMERIC, typename IDX, typename PTR>
+int32_t launch_large(const sprs_hip_spgemm_plan *pl, const PhaseArgs<IDX, PTR> &ph, hipStream_t stream) {
+    if (!pl->n_large) return SPRS_HIP_OK;
+    auto go = [&](auto wl, auto occ) {
+        hipLaunchKernelGGL((large_rows_kernel<decltype(wl)::value, IDX, PTR, NUMERIC, decltype(occ)::value>), dim3((unsigned)pl->n_large),
+                           dim3(LG_BLOCK), 0, stream, ph.A, ph.B, pl->b_cols, pl->large_list.u64(), pl->task_row.u64(), pl->first_task.u64(),
+                           pl->ntasks.u64(), pl->wlog.as<uint8_t>(), pl->count.u64(), ph.off, ph.c_indices, ph.c_values, pl->xcd_chunk,
+                           ph.large_flags, ph.large_prof, ph.ub, pl->large_slot.u64(),
+                           pl->kept_words ? pl->kept_bm.as<unsigned long long>() : nullptr, pl->kept_words);
+    };
+    if constexpr (NUMERIC) {
+        const bool occ3 = options().spgemm_occupancy != 2;
+        switch (pl->winlog) {
+            case 16: if (occ3) go(Int<16>{}, Int<6>{}); else go(Int<16>{}, Int<4>{}); break;
+            case 18: go(Int<18>{}, Int<1>{}); break;
+            case 19: go(Int<19>{}, Int<1>{}); break;
+            default: if (occ3) go(Int<17>{}, Int<6>{}); else go(Int<17>{}, Int<4>{}); break;
+        }
+    } else {
+        switch (pl->winlog) {                    // (counting: one layout wider than the numeric kernel's)
+            case 16: go(Int<17>{}, Int<1>{}); break;
+            case 18: go(Int<19>{}, Int<1>{}); break;
+            case 19: go(Int<19>{}, Int<1>{}); break;
+            default: go(Int<18>{}, Int<1>{}); break;
+        }
+    }
+    SPRS_TRY_HIP(hipGetLastError());
+    return SPRS_HIP_OK;
+}
+
+// the micro rows: class list 0 / 1 / 2 on groups of 16 / 32 / 64 lanes
+template <bool NUMERIC, typename IDX, typename PTR>
+int32_t launch_micro(const sprs_hip_spgemm_plan *pl, const PhaseArgs<IDX, PTR> &ph, hipStream_t stream) {
+    auto go = [&](int m, auto group, auto key) -> int32_t {
+        constexpr int G = decltype(group)::value;
+        if (!pl->n_micro[m]) return SPRS_HIP_OK;
+        hipLaunchKernelGGL((micro_rows_kernel<IDX, PTR, NUMERIC, G, typename decltype(key)::type>), micro_grid(pl->n_micro[m], WAVE / G),
+                           dim3(256), 0, stream, ph.A, ph.B, pl->ent_ext.u64(), pl->micro_list[m].as<MicroRec>(), pl->n_micro[m],
+                           pl->count.u64(), ph.off, ph.c_indices, ph.c_values);
+        SPRS_TRY_HIP(hipGetLastError());
+        return SPRS_HIP_OK;
+    };
+    // (column, position) sort keys of one word while they fit
+    return dispatch_width(pl->b_cols <= MICRO_KEY32_COLS ? 4 : 8, [&](auto key) -> int32_t {
+        SPRS_TRY(go(0, Int<16>{}, key));
+        SPRS_TRY(go(1, Int<32>{}, key));
+        return go(2, Int<64>{}, key);
+    });
+}
+
+// the hash rows of one list: tiny (TAB = TINY_TAB) or small (SMALL_TAB)
+template <bool NUMERIC, int TAB, typename IDX, typename PTR>
+int32_t launch_hash(const sprs_hip_spgemm_plan *pl, const PhaseArgs<IDX, PTR> &ph, const DevBuf &list, uint64_t n, hipStream_t stream) {
+    if (!n) return SPRS_HIP_OK;
+    hipLaunchKernelGGL((small_rows_kernel<IDX, PTR, NUMERIC, TAB>), small_grid(n), dim3(SM_BLOCK), 0, stream, ph.A, ph.B, list.u64(), n,
+                       pl->task_row.u64(), pl->ub.u64(), pl->count.u64(), ph.off, ph.c_indices, ph.c_values, ph.bin_shift, ph.hash_flags);
+    SPRS_TRY_HIP(hipGetLastError());
+    return SPRS_HIP_OK;
+}
+
+// the wave-per-row rows (the counting kernel has no accumulators: windows of up to 2^16 columns, four times fewer prologues per row)
+template <bool NUMERIC, typename IDX, typename PTR>
+int32_t launch_mid(const sprs_hip_spgemm_plan *pl, const PhaseArgs<IDX, PTR> &ph, hipStream_t stream) {
+    if (!pl->n_mid) return SPRS_HIP_OK;
+    unsigned int *counter = pl->counters.as<unsigned int>() + ph.counter_slot;
+    SPRS_TRY_HIP(hipMemsetAsync(counter, 0, NUMERIC ? 4 : COUNTER_BYTES, stream));
+    auto go = [&](auto wl, auto keep) {
+        hipLaunchKernelGGL((mid_rows_kernel<IDX, PTR, NUMERIC, decltype(wl)::value, decltype(keep)::value>), mid_grid(pl->n_mid),
+                           dim3(MID_BLOCK), 0, stream, ph.A, ph.B, pl->b_cols, pl->mid_list.u64(), pl->n_mid, pl->task_row.u64(),
+                           pl->count.u64(), ph.off, ph.c_indices, ph.c_values, ph.mid_prof, ph.ub, counter, ph.mid_flags);
+    };
+    if constexpr (NUMERIC) {
+        const bool k8 = options().spgemm_mid_keep >= 8;
+        if (pl->midwin >= 15) { if (k8) go(Int<15>{}, Int<8>{}); else go(Int<15>{}, Int<4>{}); }
+        else { if (k8) go(Int<14>{}, Int<8>{}); else go(Int<14>{}, Int<4>{}); }
+    } else {
+        const bool k16 = options().spgemm_mid_keep_sym >= 16;
+        if (options().spgemm_midwin_sym >= 15) { if (k16) go(Int<16>{}, Int<16>{}); else go(Int<16>{}, Int<8>{}); }
+        else { if (k16) go(Int<14>{}, Int<16>{}); else go(Int<14>{}, Int<8>{}); }
+    }
+    SPRS_TRY_HIP(hipGetLastError());
+    return SPRS_HIP_OK;
+}
+
+// All launches of one phase: the large rows first on the main stream (the long tasks start at once), the wave kernels beside
+// them on the second stream (option spgemm_overlap), joined before this returns.
+template <bool NUMERIC, typename IDX, typename PTR>
+int32_t launch_phase(const sprs_hip_spgemm_plan *pl, const PhaseArgs<IDX, PTR> &ph, hipStream_t stream) {
+    AuxFork aux(stream);
+    SPRS_TRY(launch_large<NUMERIC>(pl, ph, stream));
+    SPRS_TRY(launch_micro<NUMERIC>(pl, ph, aux.wave));
+    SPRS_TRY((launch_hash<NUMERIC, TINY_TAB>(pl, ph, pl->tiny_list, pl->n_tiny, aux.wave)));
+    SPRS_TRY((launch_hash<NUMERIC, SMALL_TAB>(pl, ph, pl->small_list, pl->n_small, aux.wave)));
+    SPRS_TRY(launch_mid<NUMERIC>(pl, ph, aux.wave));
+    SPRS_TRY_HIP(aux.join());
+    return SPRS_HIP_OK;
+}
+
 // ---- symbolic phase: counts, offsets, task lists ---------------------------------------------------------
 template <typename IDX, typename PTR>
 int32_t plan_build(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_spgemm_plan *pl) {
@@ -1953,6 +2090,7 @@ int32_t plan_build(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_sp
     pl->b_indptr = b->indptr;
     pl->b_indices = b->indices;
     pl->winlog = options().spgemm_winlog;
+    pl->midwin = options().spgemm_midwin;
     pl->xcd_chunk = options().spgemm_xcd_chunk < 0 ? 0xFFFFFFFFu : (uint32_t)options().spgemm_xcd_chunk;
     CsrView<IDX, PTR> A = view_of<IDX, PTR>(a), B = view_of<IDX, PTR>(b);
     // column-bucket table of B (4 bytes per 2048 columns per row; config 5: 1.96 GB): bounded — up to 4 GiB outright
@@ -2065,103 +2203,23 @@ int32_t plan_build(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_sp
     if (n_mid > 1 && options().spgemm_task_order != 2)
         SPRS_TRY(radix_sort_pairs(mid_key.as<uint64_t>(), pl->mid_list.as<uint64_t>(), n_mid, {{0, 6}}, stream));
 
-    // large rows first on the main stream (the long tasks start at once), the wave kernels beside them on the second stream
-    AuxFork aux(stream);
-    const hipStream_t wstream = aux.wave;
-    // ONE launch for all large tasks, in the LDS layout of the window width (option spgemm_winlog)
-    if (n_large) {
-        const dim3 g((unsigned)n_large), blk(LG_BLOCK);
-#define SPRS_LG_SYM(WL)                                                                                              \
-    hipLaunchKernelGGL((large_rows_kernel<WL, IDX, PTR, false, 1>), g, blk, 0, stream, A, B, b_cols,                    \
-                       pl->large_list.as<uint64_t>(), pl->task_row.as<uint64_t>(), pl->first_task.as<uint64_t>(),    \
-                       pl->ntasks.as<uint64_t>(), (const uint8_t *)pl->wlog.as<uint8_t>(), pl->count.as<uint64_t>(), (const uint64_t *)nullptr, (IDX *)nullptr, \
-                       (double *)nullptr, pl->xcd_chunk, 0u, (unsigned long long *)nullptr, (const uint64_t *)nullptr,       \
-                       pl->large_slot.as<uint64_t>(), pl->kept_words ? pl->kept_bm.as<unsigned long long>() : (unsigned long long *)nullptr, pl->kept_words)
-        // bitmaps of the large rows, kept for the numeric phase (one bit per column per large task slot; config 5: 3.8 GB):
-        // bounded by 16 GiB and by a quarter of the free device memory, otherwise the numeric kernel walks for its bits
-        pl->kept_words = 0;
-        if (options().spgemm_keep_bits) {
-            const uint64_t words_row = ((b_cols + SUPER_WORDS * 64 - 1) / (SUPER_WORDS * 64)) * SUPER_WORDS;
-            const uint64_t bytes = n_large * words_row * 8;
-            size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && bytes <= (16ull << 30) && bytes <= free_b / 4 &&
-                pl->kept_bm.alloc_pooled(bytes) == hipSuccess) {
-                pl->kept_words = words_row;
-            } else {
-                (void)hipGetLastError();
-                clear_error();
-            }
+    // bitmaps of the large rows, kept for the numeric phase (one bit per column per large task slot; config 5: 3.8 GB):
+    // bounded by 16 GiB and by a quarter of the free device memory, otherwise the numeric kernel walks for its bits
+    pl->kept_words = 0;
+    if (n_large && options().spgemm_keep_bits) {
+        const uint64_t words_row = ((b_cols + SUPER_WORDS * 64 - 1) / (SUPER_WORDS * 64)) * SUPER_WORDS;
+        const uint64_t bytes = n_large * words_row * 8;
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && bytes <= (16ull << 30) && bytes <= free_b / 4 &&
+            pl->kept_bm.alloc_pooled(bytes) == hipSuccess) {
+            pl->kept_words = words_row;
+        } else {
+            (void)hipGetLastError();
+            clear_error();
         }
-        switch (pl->winlog) {                    // (counting: one layout wider than the numeric kernel's)
-            case 16: SPRS_LG_SYM(17); break;
-            case 18: SPRS_LG_SYM(19); break;
-            case 19: SPRS_LG_SYM(19); break;
-            default: SPRS_LG_SYM(18); break;
-        }
-#undef SPRS_LG_SYM
-        SPRS_TRY_HIP(hipGetLastError());
     }
-    auto small_grid = [&](uint64_t n_tasks) {
-        uint64_t g = (n_tasks + SM_WAVES - 1) / SM_WAVES;
-        if (g > 256 * 32) g = 256 * 32;
-        return dim3((unsigned)g);
-    };
-    auto micro_grid = [&](uint64_t n_rows, int per_wave) {
-        uint64_t g = ((n_rows + per_wave - 1) / per_wave + 3) / 4;       // four waves per block
-        if (g > 256 * 8) g = 256 * 8;                                    // what the chip holds at once; the waves stride over the list
-        return dim3((unsigned)g);
-    };
-#define SPRS_MICRO_SYM(M, GV, KV)                                                                                                     \
-    if (pl->n_micro[M]) {                                                                                                           \
-        hipLaunchKernelGGL((micro_rows_kernel<IDX, PTR, false, GV, KV>), micro_grid(pl->n_micro[M], WAVE / GV), dim3(256), 0, wstream, A, B, (const uint64_t *)pl->ent_ext.as<uint64_t>(), \
-                           (const MicroRec *)pl->micro_list[M].as<MicroRec>(), pl->n_micro[M], pl->count.as<uint64_t>(),             \
-                           (const uint64_t *)nullptr, (IDX *)nullptr, (double *)nullptr);                                            \
-        SPRS_TRY_HIP(hipGetLastError());                                                                                            \
-    }
-    if (b_cols <= MICRO_KEY32_COLS) {                                   // (column, position) sort keys of one word
-        SPRS_MICRO_SYM(0, 16, uint32_t)
-        SPRS_MICRO_SYM(1, 32, uint32_t)
-        SPRS_MICRO_SYM(2, 64, uint32_t)
-    } else {
-        SPRS_MICRO_SYM(0, 16, uint64_t)
-        SPRS_MICRO_SYM(1, 32, uint64_t)
-        SPRS_MICRO_SYM(2, 64, uint64_t)
-    }
-#undef SPRS_MICRO_SYM
-    if (n_tiny) {
-        hipLaunchKernelGGL((small_rows_kernel<IDX, PTR, false, TINY_TAB>), small_grid(n_tiny), dim3(SM_BLOCK), 0, wstream,
-                           A, B, pl->tiny_list.as<uint64_t>(), n_tiny, pl->task_row.as<uint64_t>(), pl->ub.as<uint64_t>(),
-                           pl->count.as<uint64_t>(), (const uint64_t *)nullptr, (IDX *)nullptr, (double *)nullptr, 0u, 0u);
-        SPRS_TRY_HIP(hipGetLastError());
-    }
-    if (n_small) {
-        hipLaunchKernelGGL((small_rows_kernel<IDX, PTR, false, SMALL_TAB>), small_grid(n_small), dim3(SM_BLOCK), 0, wstream,
-                           A, B, pl->small_list.as<uint64_t>(), n_small, pl->task_row.as<uint64_t>(), pl->ub.as<uint64_t>(),
-                           pl->count.as<uint64_t>(), (const uint64_t *)nullptr, (IDX *)nullptr, (double *)nullptr, 0u, 0u);
-        SPRS_TRY_HIP(hipGetLastError());
-    }
-    pl->midwin = options().spgemm_midwin;
-    auto mid_grid = [&](uint64_t n_tasks) {
-        uint64_t g = (n_tasks + MID_WAVES - 1) / MID_WAVES;
-        if (g > 256 * 12) g = 256 * 12;          // what fits the CUs at once; the waves stride over the (cost-sorted) list
-        return dim3((unsigned)g);
-    };
-    if (n_mid) {
-#define SPRS_MID_SYM(WL, KP)                                                                                             \
-    hipLaunchKernelGGL((mid_rows_kernel<IDX, PTR, false, WL, KP>), mid_grid(n_mid), dim3(MID_BLOCK), 0, wstream, A, B, b_cols, \
-                       pl->mid_list.as<uint64_t>(), n_mid, pl->task_row.as<uint64_t>(), pl->count.as<uint64_t>(),    \
-                       (const uint64_t *)nullptr, (IDX *)nullptr, (double *)nullptr, (unsigned long long *)nullptr, (const uint64_t *)nullptr, \
-                       pl->counters.as<unsigned int>(), 0u)
-        SPRS_TRY_HIP(pl->counters.alloc_pooled(64));
-        SPRS_TRY_HIP(hipMemsetAsync(pl->counters.p, 0, 64, wstream));
-        // the counting kernel has no accumulators: windows of 2^16 columns (four times fewer window prologues per row)
-        const bool k16 = options().spgemm_mid_keep_sym >= 16;
-        if (options().spgemm_midwin_sym >= 15) { if (k16) SPRS_MID_SYM(16, 16); else SPRS_MID_SYM(16, 8); }
-        else { if (k16) SPRS_MID_SYM(14, 16); else SPRS_MID_SYM(14, 8); }
-#undef SPRS_MID_SYM
-        SPRS_TRY_HIP(hipGetLastError());
-    }
-    SPRS_TRY_HIP(aux.join());
+    if (n_mid) SPRS_TRY_HIP(pl->counters.alloc_pooled(COUNTER_BYTES));
+    SPRS_TRY(launch_phase<false>(pl, PhaseArgs<IDX, PTR>{A, B}, stream));
     // ---- prefix sum of the counts -> offsets, C.indptr (smmp.rs:320-331) ----
     SPRS_TRY(exclusive_scan_u64(pl->count.as<uint64_t>(), pl->off.as<uint64_t>(), ntask_total, stream));
     SPRS_TRY_HIP(copy_to_host(&pl->c_nnz, pl->off.as<uint64_t>() + ntask_total, 8, stream));
@@ -2169,6 +2227,68 @@ int32_t plan_build(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_sp
         SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "Index type is not large enough to hold the nnz of the product (%llu)",
                   (unsigned long long)pl->c_nnz);   // Iptr::from_usize, smmp.rs:121
     return SPRS_HIP_OK;
+}
+
+// ---- option spgemm_prof (developer build): what the numeric kernels' timers say ----------------------------------
+// 100 MHz ticks per large task, by block (= position in the launch order)
+void print_large_prof(const sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, const DevBuf &prof, hipStream_t stream) {
+    const uint64_t n_large = pl->n_large;
+    unsigned long long phs[40];
+    (void)copy_to_host(phs, (char *)prof.p + n_large * 8, 320, stream);
+    for (int c = 0; c < 5; ++c)
+        fprintf(stderr, "[spgemm_prof] class %d, thread-0 time by phase (ms of workgroup time): prologue %.1f, stage+bits %.1f, prefix %.1f, "
+                        "emit %.1f, values %.1f, flush+clear %.1f\n", c, phs[c * 8 + 0] / 1e5, phs[c * 8 + 1] / 1e5, phs[c * 8 + 2] / 1e5,
+                phs[c * 8 + 3] / 1e5, phs[c * 8 + 4] / 1e5, phs[c * 8 + 5] / 1e5);
+    std::vector<unsigned long long> tk(n_large), lst(n_large), trow(pl->ntask_total), ubv(pl->rows), ntk(pl->rows);
+    (void)copy_to_host(tk.data(), prof.p, n_large * 8, stream);
+    (void)copy_to_host(lst.data(), pl->large_list.p, n_large * 8, stream);
+    (void)copy_to_host(trow.data(), pl->task_row.p, pl->ntask_total * 8, stream);
+    (void)copy_to_host(ubv.data(), pl->ub.p, pl->rows * 8, stream);
+    (void)copy_to_host(ntk.data(), pl->ntasks.p, pl->rows * 8, stream);
+    std::vector<uint64_t> a_ip(pl->rows + 1);
+    if (pl->iptr_bytes == 8) (void)copy_to_host(a_ip.data(), a->indptr, (pl->rows + 1) * 8, stream);
+    double sum = 0;
+    unsigned long long mx = 0;
+    // classes by products per task: < 2^13, < 2^15, < 2^17, < 2^19, rest
+    double csum[5] = {0, 0, 0, 0, 0}, cprod[5] = {0, 0, 0, 0, 0};
+    unsigned long long cn[5] = {0, 0, 0, 0, 0};
+    std::vector<std::pair<unsigned long long, uint64_t>> top;
+    for (uint64_t i = 0; i < n_large; ++i) {
+        const uint64_t r = trow[lst[i]];
+        const double per = (double)ubv[r] / (double)ntk[r];
+        const int c = per < 8192 ? 0 : per < 32768 ? 1 : per < 131072 ? 2 : per < 524288 ? 3 : 4;
+        csum[c] += (double)tk[i];
+        cprod[c] += per;
+        ++cn[c];
+        sum += (double)tk[i];
+        if (tk[i] > mx) mx = tk[i];
+        top.push_back({tk[i], i});
+    }
+    std::partial_sort(top.begin(), top.begin() + (top.size() < 8 ? top.size() : 8), top.end(),
+                      [](const auto &x, const auto &y) { return x.first > y.first; });
+    fprintf(stderr, "[spgemm_prof] large tasks %llu: sum %.1f ms of workgroup time, longest %.3f ms\n",
+            (unsigned long long)n_large, sum / 1e5, (double)mx / 1e5);
+    for (int c = 0; c < 5; ++c)
+        fprintf(stderr, "[spgemm_prof]   class %d: %llu tasks, %.3e products, %.1f ms of workgroup time (%.2f us per task, %.2f ns per product)\n",
+                c, cn[c], cprod[c], csum[c] / 1e5, cn[c] ? csum[c] / 1e2 / (double)cn[c] : 0.0, cprod[c] ? csum[c] * 10.0 / cprod[c] : 0.0);
+    for (size_t j = 0; j < top.size() && j < 8; ++j) {
+        const uint64_t i = top[j].second, r = trow[lst[i]];
+        fprintf(stderr, "[spgemm_prof]   top %zu: block %llu row %llu products %llu tasks of the row %llu k's %llu: %.3f ms\n", j,
+                (unsigned long long)i, (unsigned long long)r, ubv[r], ntk[r],
+                pl->iptr_bytes == 8 ? (unsigned long long)(a_ip[r + 1] - a_ip[r]) : 0ull, (double)top[j].first / 1e5);
+    }
+}
+
+void print_mid_prof(const sprs_hip_spgemm_plan *pl, const DevBuf &mprof, hipStream_t stream) {
+    unsigned long long h[32];
+    (void)copy_to_host(h, mprof.p, 256, stream);
+    fprintf(stderr, "[spgemm_prof] mid rows by products (< 2048, < 8192, < 32768, rest): %llu rows %.1f ms | %llu rows %.1f ms | %llu rows %.1f ms | "
+                    "%llu rows %.1f ms of wave time; longest row %.3f ms; waves %llu, mean wave %.3f ms, longest wave %.3f ms\n",
+            h[9], h[8] / 1e5, h[11], h[10] / 1e5, h[13], h[12] / 1e5, h[15], h[14] / 1e5, h[16] / 1e5, h[19],
+            h[19] ? h[18] / 1e5 / (double)h[19] : 0.0, h[17] / 1e5);
+    fprintf(stderr, "[spgemm_prof] mid rows %llu, lane-0 time by phase (ms of wave time): row prologue %.1f, bounds+scan %.1f, stage+loads+bits %.1f, "
+                    "prefix %.1f, emit %.1f, values+flush %.1f\n", (unsigned long long)pl->n_mid, h[0] / 1e5, h[1] / 1e5, h[2] / 1e5, h[3] / 1e5,
+            h[4] / 1e5, h[5] / 1e5);
 }
 
 // ---- numeric phase: indices (optional) and values into a matrix of the product's structure -------------------------
@@ -2189,160 +2309,43 @@ int32_t plan_run(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, const sprs_h
         }
         B.pack = pl->bpack.as<BRec>();
     }
-    const uint64_t n_tiny = pl->n_tiny, n_small = pl->n_small, n_mid = pl->n_mid, n_large = pl->n_large;
-    double *c_values = values ? c->data : nullptr;
-    IDX *c_indices = indices ? (IDX *)c->indices : nullptr;
-    auto small_grid = [&](uint64_t n_tasks) {
-        uint64_t g = (n_tasks + SM_WAVES - 1) / SM_WAVES;
-        if (g > 256 * 32) g = 256 * 32;
-        return dim3((unsigned)g);
-    };
-    AuxFork aux(stream);
-    const hipStream_t wstream = aux.wave;
-    if (n_large) {
-        const dim3 g((unsigned)n_large), blk(LG_BLOCK);
-        // bit 2: the adds of a workgroup's waves are NOT put in the reference's order (option spgemm_ordered = 0: every C(i,j) still
-        // is the sum of the same products, added by LDS atomics in whatever order the waves arrive — rounding-level differences,
-        // not reproducible run to run; structure unaffected).  Needs the atomic form of the add.
-        const bool unordered = options().spgemm_ordered == 0;
-        const uint32_t flags = ((options().spgemm_lds_atomic || unordered) ? 1u : 0u) |                                (unordered ? 4u : 0u) | ((uint32_t)(options().spgemm_debug & 3) << 2) |
-                               ((options().spgemm_tokens >= 4 ? 2u : options().spgemm_tokens >= 2 ? 1u : 0u) << 4) |
-                               ((options().spgemm_lds_atomic || unordered) && add_flags() ? 64u : 0u);
-#define SPRS_LG_NUM(WL, OCC)                                                                                         \
-    hipLaunchKernelGGL((large_rows_kernel<WL, IDX, PTR, true, OCC>), g, blk, 0, stream, A, B, pl->b_cols,            \
-                       pl->large_list.as<uint64_t>(), pl->task_row.as<uint64_t>(), pl->first_task.as<uint64_t>(),    \
-                       pl->ntasks.as<uint64_t>(), (const uint8_t *)pl->wlog.as<uint8_t>(), pl->count.as<uint64_t>(), pl->off.as<uint64_t>(), c_indices, \
-                       c_values, pl->xcd_chunk, flags, prof.as<unsigned long long>(), pl->ub.as<uint64_t>(),                      \
-                       pl->large_slot.as<uint64_t>(), pl->kept_words ? pl->kept_bm.as<unsigned long long>() : (unsigned long long *)nullptr, pl->kept_words)
-        DevBuf prof;
-        if (DEVTOOLS && options().spgemm_prof) {
-            SPRS_TRY_HIP(prof.alloc_pooled((n_large + 40) * 8));
-            SPRS_TRY_HIP(hipMemsetAsync(prof.p, 0, (n_large + 40) * 8, stream));
-        }
-        const bool occ3 = options().spgemm_occupancy != 2;
-        switch (pl->winlog) {
-            case 16: if (occ3) SPRS_LG_NUM(16, 6); else SPRS_LG_NUM(16, 4); break;
-            case 18: SPRS_LG_NUM(18, 1); break;
-            case 19: SPRS_LG_NUM(19, 1); break;
-            default: if (occ3) SPRS_LG_NUM(17, 6); else SPRS_LG_NUM(17, 4); break;
-        }
-#undef SPRS_LG_NUM
-        if (DEVTOOLS && prof.p) {
-            // debug: 100 MHz ticks per large task, by block (= position in the launch order)
-            SPRS_TRY_HIP(hipStreamSynchronize(stream));
-            unsigned long long phs[40];
-            (void)copy_to_host(phs, (char *)prof.p + n_large * 8, 320, stream);
-            for (int c = 0; c < 5; ++c)
-                fprintf(stderr, "[spgemm_prof] class %d, thread-0 time by phase (ms of workgroup time): prologue %.1f, stage+bits %.1f, prefix %.1f, "
-                                "emit %.1f, values %.1f, flush+clear %.1f\n", c, phs[c * 8 + 0] / 1e5, phs[c * 8 + 1] / 1e5, phs[c * 8 + 2] / 1e5,
-                        phs[c * 8 + 3] / 1e5, phs[c * 8 + 4] / 1e5, phs[c * 8 + 5] / 1e5);
-            std::vector<unsigned long long> tk(n_large), lst(n_large), trow(pl->ntask_total), ubv(pl->rows), ntk(pl->rows);
-            (void)copy_to_host(tk.data(), prof.p, n_large * 8, stream);
-            (void)copy_to_host(lst.data(), pl->large_list.p, n_large * 8, stream);
-            (void)copy_to_host(trow.data(), pl->task_row.p, pl->ntask_total * 8, stream);
-            (void)copy_to_host(ubv.data(), pl->ub.p, pl->rows * 8, stream);
-            (void)copy_to_host(ntk.data(), pl->ntasks.p, pl->rows * 8, stream);
-            std::vector<uint64_t> a_ip(pl->rows + 1);
-            if (sizeof(PTR) == 8) (void)copy_to_host(a_ip.data(), a->indptr, (pl->rows + 1) * 8, stream);
-            double sum = 0;
-            unsigned long long mx = 0;
-            // classes by products per task: < 2^13, < 2^15, < 2^17, < 2^19, rest
-            double csum[5] = {0, 0, 0, 0, 0}, cprod[5] = {0, 0, 0, 0, 0};
-            unsigned long long cn[5] = {0, 0, 0, 0, 0};
-            std::vector<std::pair<unsigned long long, uint64_t>> top;
-            for (uint64_t i = 0; i < n_large; ++i) {
-                const uint64_t r = trow[lst[i]];
-                const double per = (double)ubv[r] / (double)ntk[r];
-                const int c = per < 8192 ? 0 : per < 32768 ? 1 : per < 131072 ? 2 : per < 524288 ? 3 : 4;
-                csum[c] += (double)tk[i];
-                cprod[c] += per;
-                ++cn[c];
-                sum += (double)tk[i];
-                if (tk[i] > mx) mx = tk[i];
-                top.push_back({tk[i], i});
-            }
-            std::partial_sort(top.begin(), top.begin() + (top.size() < 8 ? top.size() : 8), top.end(),
-                              [](const auto &x, const auto &y) { return x.first > y.first; });
-            fprintf(stderr, "[spgemm_prof] large tasks %llu: sum %.1f ms of workgroup time, longest %.3f ms\n",
-                    (unsigned long long)n_large, sum / 1e5, (double)mx / 1e5);
-            for (int c = 0; c < 5; ++c)
-                fprintf(stderr, "[spgemm_prof]   class %d: %llu tasks, %.3e products, %.1f ms of workgroup time (%.2f us per task, %.2f ns per product)\n",
-                        c, cn[c], cprod[c], csum[c] / 1e5, cn[c] ? csum[c] / 1e2 / (double)cn[c] : 0.0, cprod[c] ? csum[c] * 10.0 / cprod[c] : 0.0);
-            for (size_t j = 0; j < top.size() && j < 8; ++j) {
-                const uint64_t i = top[j].second, r = trow[lst[i]];
-                fprintf(stderr, "[spgemm_prof]   top %zu: block %llu row %llu products %llu tasks of the row %llu k's %llu: %.3f ms\n", j,
-                        (unsigned long long)i, (unsigned long long)r, ubv[r], ntk[r],
-                        sizeof(PTR) == 8 ? (unsigned long long)(a_ip[r + 1] - a_ip[r]) : 0ull, (double)top[j].first / 1e5);
-            }
-        }
-    }
+    PhaseArgs<IDX, PTR> ph{A, B};
+    ph.off = pl->off.u64();
+    ph.ub = pl->ub.u64();
+    ph.c_indices = indices ? (IDX *)c->indices : nullptr;
+    ph.c_values = values ? c->data : nullptr;
+    // large rows, bit 2: the adds of a workgroup's waves are NOT put in the reference's order (option spgemm_ordered = 0: every C(i,j) still
+    // is the sum of the same products, added by LDS atomics in whatever order the waves arrive — rounding-level differences,
+    // not reproducible run to run; structure unaffected).  Needs the atomic form of the add.
+    const bool unordered = options().spgemm_ordered == 0, atomic = options().spgemm_lds_atomic || unordered;
+    if (pl->n_large)
+        ph.large_flags = (atomic ? 1u : 0u) | (unordered ? 4u : 0u) | ((uint32_t)(options().spgemm_debug & 3) << 2) |
+                         ((options().spgemm_tokens >= 4 ? 2u : options().spgemm_tokens >= 2 ? 1u : 0u) << 4) |
+                         (atomic && add_flags() ? 64u : 0u);
     // bins of the hash kernels' rank pass: the column space cut into SM_NBIN equal power-of-two ranges
-    uint32_t bin_shift = 0;
-    while (bin_shift < 32 && ((pl->b_cols - (pl->b_cols ? 1 : 0)) >> bin_shift) >= (uint64_t)SM_NBIN) ++bin_shift;
-    const uint32_t small_flags = add_flags();
-#define SPRS_MICRO_NUM(M, GV, KV)                                                                                                     \
-    if (pl->n_micro[M]) {                                                                                                           \
-        uint64_t mg = ((pl->n_micro[M] + (WAVE / GV) - 1) / (WAVE / GV) + 3) / 4;                                                     \
-        if (mg > 256 * 8) mg = 256 * 8;                                                                                             \
-        hipLaunchKernelGGL((micro_rows_kernel<IDX, PTR, true, GV, KV>), dim3((unsigned)mg), dim3(256), 0, wstream, A, B, (const uint64_t *)pl->ent_ext.as<uint64_t>(), \
-                           (const MicroRec *)pl->micro_list[M].as<MicroRec>(), pl->n_micro[M], pl->count.as<uint64_t>(),             \
-                           (const uint64_t *)pl->off.as<uint64_t>(), c_indices, c_values);                                           \
-        SPRS_TRY_HIP(hipGetLastError());                                                                                            \
-    }
-    if (pl->b_cols <= MICRO_KEY32_COLS) {                                   // (column, position) sort keys of one word
-        SPRS_MICRO_NUM(0, 16, uint32_t)
-        SPRS_MICRO_NUM(1, 32, uint32_t)
-        SPRS_MICRO_NUM(2, 64, uint32_t)
-    } else {
-        SPRS_MICRO_NUM(0, 16, uint64_t)
-        SPRS_MICRO_NUM(1, 32, uint64_t)
-        SPRS_MICRO_NUM(2, 64, uint64_t)
-    }
-#undef SPRS_MICRO_NUM
-    if (n_tiny)
-        hipLaunchKernelGGL((small_rows_kernel<IDX, PTR, true, TINY_TAB>), small_grid(n_tiny), dim3(SM_BLOCK), 0, wstream, A,
-                           B, pl->tiny_list.as<uint64_t>(), n_tiny, pl->task_row.as<uint64_t>(), pl->ub.as<uint64_t>(),
-                           pl->count.as<uint64_t>(), pl->off.as<uint64_t>(), c_indices, c_values, bin_shift, small_flags);
-    if (n_small)
-        hipLaunchKernelGGL((small_rows_kernel<IDX, PTR, true, SMALL_TAB>), small_grid(n_small), dim3(SM_BLOCK), 0, wstream,
-                           A, B, pl->small_list.as<uint64_t>(), n_small, pl->task_row.as<uint64_t>(), pl->ub.as<uint64_t>(),
-                           pl->count.as<uint64_t>(), pl->off.as<uint64_t>(), c_indices, c_values, bin_shift, small_flags);
-    if (n_mid) {
-        uint64_t g = (n_mid + MID_WAVES - 1) / MID_WAVES;
-        if (g > 256 * 12) g = 256 * 12;
-        DevBuf mprof;
-        if (DEVTOOLS && options().spgemm_prof) {
+    while (ph.bin_shift < 32 && ((pl->b_cols - (pl->b_cols ? 1 : 0)) >> ph.bin_shift) >= (uint64_t)SM_NBIN) ++ph.bin_shift;
+    ph.hash_flags = add_flags();
+    if (pl->n_mid) ph.mid_flags = add_flags() | (DEVTOOLS ? (uint32_t)options().spgemm_debug << 2 : 0u);
+    ph.counter_slot = NUMERIC_COUNTER;
+    DevBuf prof, mprof;
+    if (DEVTOOLS && options().spgemm_prof) {
+        if (pl->n_large) {
+            SPRS_TRY_HIP(prof.alloc_pooled((pl->n_large + 40) * 8));
+            SPRS_TRY_HIP(hipMemsetAsync(prof.p, 0, (pl->n_large + 40) * 8, stream));
+            ph.large_prof = prof.as<unsigned long long>();
+        }
+        if (pl->n_mid) {
             SPRS_TRY_HIP(mprof.alloc_pooled(256));
             SPRS_TRY_HIP(hipMemsetAsync(mprof.p, 0, 256, stream));
-        }
-#define SPRS_MID_NUM(WL, KP)                                                                                             \
-    hipLaunchKernelGGL((mid_rows_kernel<IDX, PTR, true, WL, KP>), dim3((unsigned)g), dim3(MID_BLOCK), 0, wstream, A, B, pl->b_cols, \
-                       pl->mid_list.as<uint64_t>(), n_mid, pl->task_row.as<uint64_t>(), pl->count.as<uint64_t>(),    \
-                       pl->off.as<uint64_t>(), c_indices, c_values, mprof.as<unsigned long long>(), pl->ub.as<uint64_t>(),   \
-                       pl->counters.as<unsigned int>() + 4, wave_flags)
-        SPRS_TRY_HIP(hipMemsetAsync(pl->counters.as<unsigned int>() + 4, 0, 4, wstream));
-        const uint32_t wave_flags = add_flags() | (DEVTOOLS ? (uint32_t)options().spgemm_debug << 2 : 0u);
-        const bool k8 = options().spgemm_mid_keep >= 8;
-        if (pl->midwin >= 15) { if (k8) SPRS_MID_NUM(15, 8); else SPRS_MID_NUM(15, 4); }
-        else { if (k8) SPRS_MID_NUM(14, 8); else SPRS_MID_NUM(14, 4); }
-#undef SPRS_MID_NUM
-        if (DEVTOOLS && mprof.p) {
-            unsigned long long h[32];
-            SPRS_TRY_HIP(hipStreamSynchronize(stream));
-            (void)copy_to_host(h, mprof.p, 256, stream);
-            fprintf(stderr, "[spgemm_prof] mid rows by products (< 2048, < 8192, < 32768, rest): %llu rows %.1f ms | %llu rows %.1f ms | %llu rows %.1f ms | "
-                            "%llu rows %.1f ms of wave time; longest row %.3f ms; waves %llu, mean wave %.3f ms, longest wave %.3f ms\n",
-                    h[9], h[8] / 1e5, h[11], h[10] / 1e5, h[13], h[12] / 1e5, h[15], h[14] / 1e5, h[16] / 1e5, h[19],
-                    h[19] ? h[18] / 1e5 / (double)h[19] : 0.0, h[17] / 1e5);
-            fprintf(stderr, "[spgemm_prof] mid rows %llu, lane-0 time by phase (ms of wave time): row prologue %.1f, bounds+scan %.1f, stage+loads+bits %.1f, "
-                            "prefix %.1f, emit %.1f, values+flush %.1f\n", (unsigned long long)n_mid, h[0] / 1e5, h[1] / 1e5, h[2] / 1e5, h[3] / 1e5,
-                    h[4] / 1e5, h[5] / 1e5);
+            ph.mid_prof = mprof.as<unsigned long long>();
         }
     }
-    SPRS_TRY_HIP(aux.join());
+    SPRS_TRY(launch_phase<true>(pl, ph, stream));
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e != hipSuccess) return fail_hip(e, "spgemm numeric");
+    if (DEVTOOLS && prof.p) print_large_prof(pl, a, prof, stream);
+    if (DEVTOOLS && mprof.p) print_mid_prof(pl, mprof, stream);
     return SPRS_HIP_OK;
 }
 
@@ -2367,27 +2370,27 @@ int32_t plan_indptr(sprs_hip_spgemm_plan *pl, sprs_hip_csmat *c, bool compare) {
     return SPRS_HIP_OK;
 }
 
-#define SPRS_SPGEMM_DISPATCH(pl, CALL)                                                   \
-    ((pl)->idx_bytes == 8 && (pl)->iptr_bytes == 8   ? CALL(uint64_t, uint64_t)          \
-     : (pl)->idx_bytes == 4 && (pl)->iptr_bytes == 8 ? CALL(uint32_t, uint64_t)          \
-     : (pl)->idx_bytes == 8                          ? CALL(uint64_t, uint32_t)          \
-                                                     : CALL(uint32_t, uint32_t))
+int32_t plan_indptr(sprs_hip_spgemm_plan *pl, sprs_hip_csmat *c, bool compare) {
+    return dispatch_width(pl->iptr_bytes, [&](auto p) { return plan_indptr<typename decltype(p)::type>(pl, c, compare); });
+}
+
+int32_t plan_run(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat *c, bool values, bool indices) {
+    return dispatch_widths(pl->idx_bytes, pl->iptr_bytes, [&](auto i, auto p) {
+        return plan_run<typename decltype(i)::type, typename decltype(p)::type>(pl, a, b, c, values, indices);
+    });
+}
+
+using OwnedPlan = std::unique_ptr<sprs_hip_spgemm_plan, decltype(&spgemm_plan_free)>;
 
 }  // namespace
 
 int32_t spgemm_plan_create(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_spgemm_plan **out) {
     if (b->cols > 0xFFFFFFFEull) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "SpGEMM: more than 2^32-2 columns is not supported");
-    auto *pl = new sprs_hip_spgemm_plan();
-    pl->idx_bytes = a->idx_bytes;
-    pl->iptr_bytes = a->iptr_bytes;
-#define SPRS_CALL(I, P) plan_build<I, P>(a, b, pl)
-    const int32_t st = SPRS_SPGEMM_DISPATCH(pl, SPRS_CALL);
-#undef SPRS_CALL
-    if (st != SPRS_HIP_OK) {
-        delete pl;
-        return st;
-    }
-    *out = pl;
+    OwnedPlan pl(new sprs_hip_spgemm_plan(), spgemm_plan_free);
+    SPRS_TRY(dispatch_widths(a->idx_bytes, a->iptr_bytes, [&](auto i, auto p) {
+        return plan_build<typename decltype(i)::type, typename decltype(p)::type>(a, b, pl.get());
+    }));
+    *out = pl.release();
     return SPRS_HIP_OK;
 }
 
@@ -2405,21 +2408,14 @@ static int32_t plan_matches(const sprs_hip_spgemm_plan *pl, const sprs_hip_csmat
 int32_t spgemm_plan_structure(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat **out,
                               bool with_values) {
     SPRS_TRY(plan_matches(pl, a, b));
-    sprs_hip_csmat *c = nullptr;
-    SPRS_TRY(alloc_csmat(&c, SPRS_HIP_CSR, pl->rows, pl->b_cols, pl->c_nnz, pl->iptr_bytes, pl->idx_bytes));
-    int32_t st = pl->iptr_bytes == 8 ? plan_indptr<uint64_t>(pl, c, false) : plan_indptr<uint32_t>(pl, c, false);
-    if (st == SPRS_HIP_OK && !with_values) {
-        const hipError_t e = hipMemsetAsync(c->data, 0, (pl->c_nnz ? pl->c_nnz : 1) * sizeof(double), nullptr);
-        if (e != hipSuccess) st = fail_hip(e, "spgemm structure");
-    }
-#define SPRS_CALL(I, P) plan_run<I, P>(pl, a, b, c, with_values, true)
-    if (st == SPRS_HIP_OK) st = SPRS_SPGEMM_DISPATCH(pl, SPRS_CALL);
-#undef SPRS_CALL
-    if (st != SPRS_HIP_OK) {
-        sprs_hip_csmat_free(c);
-        return st;
-    }
-    *out = c;
+    sprs_hip_csmat *raw = nullptr;
+    SPRS_TRY(alloc_csmat(&raw, SPRS_HIP_CSR, pl->rows, pl->b_cols, pl->c_nnz, pl->iptr_bytes, pl->idx_bytes));
+    OwnedCsmat c(raw);
+    SPRS_TRY(plan_indptr(pl, c.get(), false));
+    const hipError_t e = with_values ? hipSuccess : hipMemsetAsync(c->data, 0, (pl->c_nnz ? pl->c_nnz : 1) * sizeof(double), nullptr);
+    if (e != hipSuccess) return fail_hip(e, "spgemm structure");
+    SPRS_TRY(plan_run(pl, a, b, c.get(), with_values, true));
+    *out = c.release();
     return SPRS_HIP_OK;
 }
 
@@ -2430,38 +2426,33 @@ int32_t spgemm_plan_numeric(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, c
     if (c->nnz != pl->c_nnz)
         SPRS_FAIL(SPRS_HIP_BAD_STRUCTURE, "numeric: C holds %llu entries, the product has %llu", (unsigned long long)c->nnz,
                   (unsigned long long)pl->c_nnz);
-    SPRS_TRY(pl->iptr_bytes == 8 ? plan_indptr<uint64_t>(pl, c, true) : plan_indptr<uint32_t>(pl, c, true));
-#define SPRS_CALL(I, P) plan_run<I, P>(pl, a, b, c, true, false)
-    return SPRS_SPGEMM_DISPATCH(pl, SPRS_CALL);
-#undef SPRS_CALL
+    SPRS_TRY(plan_indptr(pl, c, true));
+    return plan_run(pl, a, b, c, true, false);
 }
 
 uint64_t spgemm_plan_nnz(const sprs_hip_spgemm_plan *pl) { return pl->c_nnz; }
 
-int32_t spgemm_f64(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat **c) {
+// a product that keeps no plan: f(plan) runs on one that lives for this call
+template <typename F>
+static int32_t with_temporary_plan(const sprs_hip_csmat *a, const sprs_hip_csmat *b, F &&f) {
     sprs_hip_spgemm_plan *pl = nullptr;
     SPRS_TRY(spgemm_plan_create(a, b, &pl));
-    const int32_t st = spgemm_plan_structure(pl, a, b, c, true);
-    spgemm_plan_free(pl);
-    return st;
+    OwnedPlan own(pl, spgemm_plan_free);
+    return f(pl);
+}
+
+int32_t spgemm_f64(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat **c) {
+    return with_temporary_plan(a, b, [&](sprs_hip_spgemm_plan *pl) { return spgemm_plan_structure(pl, a, b, c, true); });
 }
 
 // smmp::symbolic (smmp.rs:81-131): structure only; the values of the result are zero
 int32_t spgemm_symbolic(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat **c) {
-    sprs_hip_spgemm_plan *pl = nullptr;
-    SPRS_TRY(spgemm_plan_create(a, b, &pl));
-    const int32_t st = spgemm_plan_structure(pl, a, b, c, false);
-    spgemm_plan_free(pl);
-    return st;
+    return with_temporary_plan(a, b, [&](sprs_hip_spgemm_plan *pl) { return spgemm_plan_structure(pl, a, b, c, false); });
 }
 
 // smmp::numeric (smmp.rs:151-189) without a kept plan: the symbolic phase is redone to check c and to cut the work
 int32_t spgemm_numeric(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat *c) {
-    sprs_hip_spgemm_plan *pl = nullptr;
-    SPRS_TRY(spgemm_plan_create(a, b, &pl));
-    const int32_t st = spgemm_plan_numeric(pl, a, b, c);
-    spgemm_plan_free(pl);
-    return st;
+    return with_temporary_plan(a, b, [&](sprs_hip_spgemm_plan *pl) { return spgemm_plan_numeric(pl, a, b, c); });
 }
 
 }  // namespace sprs_hip

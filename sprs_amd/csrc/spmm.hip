@@ -24,6 +24,8 @@
 #include "common.hpp"
 #include "scan.hpp"
 
+#include <type_traits>
+
 namespace sprs_hip {
 
 namespace {
@@ -551,22 +553,21 @@ int32_t launch_stream(sprs_hip_csmat *a, const double *rhs, uint64_t ld_rhs, uin
         ld_rhs = KP;
         cs_rhs = 1;
     }
-#define SPRS_STREAM(ACCV, RLV)                                                                                                         \
-    hipLaunchKernelGGL((spmm_stream_kernel<IDX, PTR, KP, ACCV, RLV>), grid, block, 0, stream, (const PTR *)a->indptr,                   \
-                       (const IDX *)a->indices, a->data, a->rows, a->nnz, pl.tile_row, pl.ntiles, rhs, ld_rhs, cs_rhs, k, out, ld_out, \
-                       cs_out, carry, dbg)
+    auto go = [&](auto accv, auto rlv) {
+        constexpr bool ACCV = decltype(accv)::value, RLV = decltype(rlv)::value;
+        hipLaunchKernelGGL((spmm_stream_kernel<IDX, PTR, KP, ACCV, RLV>), grid, block, 0, stream, (const PTR *)a->indptr,
+                           (const IDX *)a->indices, a->data, a->rows, a->nnz, pl.tile_row, pl.ntiles, rhs, ld_rhs, cs_rhs, k, out, ld_out,
+                           cs_out, carry, dbg);
+        hipLaunchKernelGGL((spmm_stream_fixup_kernel<PTR, KP, ACCV>), fgrid, block, 0, stream, (const PTR *)a->indptr, pl.tile_row, pl.ntiles,
+                           carry, k, out, ld_out, cs_out);
+    };
     if (acc) {
-        if (relaid) SPRS_STREAM(true, true);
-        else SPRS_STREAM(true, false);
-        hipLaunchKernelGGL((spmm_stream_fixup_kernel<PTR, KP, true>), fgrid, block, 0, stream, (const PTR *)a->indptr, pl.tile_row, pl.ntiles,
-                           carry, k, out, ld_out, cs_out);
+        if (relaid) go(std::true_type{}, std::true_type{});
+        else go(std::true_type{}, std::false_type{});
     } else {
-        if (relaid) SPRS_STREAM(false, true);
-        else SPRS_STREAM(false, false);
-        hipLaunchKernelGGL((spmm_stream_fixup_kernel<PTR, KP, false>), fgrid, block, 0, stream, (const PTR *)a->indptr, pl.tile_row, pl.ntiles,
-                           carry, k, out, ld_out, cs_out);
+        if (relaid) go(std::false_type{}, std::true_type{});
+        else go(std::false_type{}, std::false_type{});
     }
-#undef SPRS_STREAM
     SPRS_TRY_HIP(hipGetLastError());
     return SPRS_HIP_OK;
 }
@@ -720,10 +721,9 @@ void SpmmPlan::release() {
 int32_t spmm_strided_f64(sprs_hip_csmat *a, const double *rhs, uint64_t k, uint64_t rs_rhs, uint64_t cs_rhs, double *out,
                          uint64_t rs_out, uint64_t cs_out, bool accumulate, hipStream_t stream) {
     if (a->rows == 0 || k == 0) return SPRS_HIP_OK;
-    if (a->idx_bytes == 8 && a->iptr_bytes == 8) return spmm_impl<uint64_t, uint64_t>(a, rhs, k, rs_rhs, cs_rhs, out, rs_out, cs_out, accumulate, stream);
-    if (a->idx_bytes == 4 && a->iptr_bytes == 8) return spmm_impl<uint32_t, uint64_t>(a, rhs, k, rs_rhs, cs_rhs, out, rs_out, cs_out, accumulate, stream);
-    if (a->idx_bytes == 8 && a->iptr_bytes == 4) return spmm_impl<uint64_t, uint32_t>(a, rhs, k, rs_rhs, cs_rhs, out, rs_out, cs_out, accumulate, stream);
-    return spmm_impl<uint32_t, uint32_t>(a, rhs, k, rs_rhs, cs_rhs, out, rs_out, cs_out, accumulate, stream);
+    return dispatch_widths(a->idx_bytes, a->iptr_bytes, [&](auto i, auto p) {
+        return spmm_impl<typename decltype(i)::type, typename decltype(p)::type>(a, rhs, k, rs_rhs, cs_rhs, out, rs_out, cs_out, accumulate, stream);
+    });
 }
 
 int32_t spmm_rowmaj_f64(sprs_hip_csmat *a, const double *rhs, uint64_t k, uint64_t ld_rhs, double *out,

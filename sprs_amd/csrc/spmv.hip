@@ -808,10 +808,9 @@ int32_t spmv_prepare(sprs_hip_csmat *a, hipStream_t stream) {
     a->prepared = true;
     if (a->rows == 0 || a->nnz == 0 || options().spmv_kernel == 2) return SPRS_HIP_OK;
     if (a->plan.built && !a->plan.light && a->plan.opt_sig == plan_signature(options())) return SPRS_HIP_OK;
-    if (a->idx_bytes == 8 && a->iptr_bytes == 8) return build_plan<uint64_t, uint64_t>(a, stream);
-    if (a->idx_bytes == 4 && a->iptr_bytes == 8) return build_plan<uint32_t, uint64_t>(a, stream);
-    if (a->idx_bytes == 8 && a->iptr_bytes == 4) return build_plan<uint64_t, uint32_t>(a, stream);
-    return build_plan<uint32_t, uint32_t>(a, stream);
+    return dispatch_widths(a->idx_bytes, a->iptr_bytes, [&](auto i, auto p) {
+        return build_plan<typename decltype(i)::type, typename decltype(p)::type>(a, stream);
+    });
 }
 
 int32_t spmv_f64(sprs_hip_csmat *a, const double *x, double *y, bool accumulate, hipStream_t stream) {
@@ -821,10 +820,9 @@ int32_t spmv_f64(sprs_hip_csmat *a, const double *x, double *y, bool accumulate,
         if (!accumulate) SPRS_TRY_HIP(hipMemsetAsync(y, 0, a->rows * sizeof(double), stream));
         return SPRS_HIP_OK;
     }
-    if (a->idx_bytes == 8 && a->iptr_bytes == 8) return dispatch<uint64_t, uint64_t>(a, x, y, accumulate, stream);
-    if (a->idx_bytes == 4 && a->iptr_bytes == 8) return dispatch<uint32_t, uint64_t>(a, x, y, accumulate, stream);
-    if (a->idx_bytes == 8 && a->iptr_bytes == 4) return dispatch<uint64_t, uint32_t>(a, x, y, accumulate, stream);
-    return dispatch<uint32_t, uint32_t>(a, x, y, accumulate, stream);
+    return dispatch_widths(a->idx_bytes, a->iptr_bytes, [&](auto i, auto p) {
+        return dispatch<typename decltype(i)::type, typename decltype(p)::type>(a, x, y, accumulate, stream);
+    });
 }
 
 }  // namespace sprs_hip

@@ -915,10 +915,9 @@ int32_t band_scratch(BandPlan *bp, hipStream_t stream, BandScratch **out) {
 }  // namespace
 
 int32_t band_build(sprs_hip_csmat *a, hipStream_t stream, BandPlan **out) {
-    if (a->idx_bytes == 8 && a->iptr_bytes == 8) return band_build_t<uint64_t, uint64_t>(a, stream, out);
-    if (a->idx_bytes == 4 && a->iptr_bytes == 8) return band_build_t<uint32_t, uint64_t>(a, stream, out);
-    if (a->idx_bytes == 8 && a->iptr_bytes == 4) return band_build_t<uint64_t, uint32_t>(a, stream, out);
-    return band_build_t<uint32_t, uint32_t>(a, stream, out);
+    return dispatch_widths(a->idx_bytes, a->iptr_bytes, [&](auto i, auto p) {
+        return band_build_t<typename decltype(i)::type, typename decltype(p)::type>(a, stream, out);
+    });
 }
 
 uint64_t band_plan_bytes(const BandPlan *bp) { return bp ? bp->bytes : 0; }

@@ -77,8 +77,10 @@ int32_t assemble(uint64_t rows, uint64_t cols, uint64_t n, const I *row_inds, co
     sprs_hip_csmat *c = nullptr;
     if (n == 0) {
         SPRS_TRY(alloc_csmat(&c, storage, rows, cols, 0, out_iptr_bytes, out_idx_bytes));
-        if (out_iptr_bytes == 8) hipLaunchKernelGGL(tri_empty_indptr_kernel<uint64_t>, dim3((unsigned)((n_outer + 256) / 256)), dim3(256), 0, stream, (uint64_t *)c->indptr, n_outer);
-        else hipLaunchKernelGGL(tri_empty_indptr_kernel<uint32_t>, dim3((unsigned)((n_outer + 256) / 256)), dim3(256), 0, stream, (uint32_t *)c->indptr, n_outer);
+        dispatch_width(out_iptr_bytes, [&](auto p) {
+            using PT = typename decltype(p)::type;
+            hipLaunchKernelGGL(tri_empty_indptr_kernel<PT>, dim3((unsigned)((n_outer + 256) / 256)), dim3(256), 0, stream, (PT *)c->indptr, n_outer);
+        });
         hipError_t e = hipStreamSynchronize(stream);
         if (e != hipSuccess) {
             sprs_hip_csmat_free(c);
@@ -109,15 +111,13 @@ int32_t assemble(uint64_t rows, uint64_t cols, uint64_t n, const I *row_inds, co
     if (out_iptr_bytes == 4 && ngroups > 0xFFFFFFFFull)
         SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "Index type is not large enough to hold the nnz of the matrix (%llu)", (unsigned long long)ngroups);
     SPRS_TRY(alloc_csmat(&c, storage, rows, cols, ngroups, out_iptr_bytes, out_idx_bytes));
-#define SPRS_TRI_FOLD(IT, PT)                                                                                                   \
-    hipLaunchKernelGGL((tri_fold_kernel<IT, PT>), g1, b1, 0, stream, (const uint64_t *)keys.u64(), (const uint64_t *)vals.u64(), \
-                       (const uint64_t *)head.u64(), (const uint64_t *)gidx.u64(), n, n_outer, ngroups, (PT *)c->indptr,          \
-                       (IT *)c->indices, c->data)
-    if (out_idx_bytes == 8 && out_iptr_bytes == 8) SPRS_TRI_FOLD(uint64_t, uint64_t);
-    else if (out_idx_bytes == 4 && out_iptr_bytes == 8) SPRS_TRI_FOLD(uint32_t, uint64_t);
-    else if (out_idx_bytes == 8) SPRS_TRI_FOLD(uint64_t, uint32_t);
-    else SPRS_TRI_FOLD(uint32_t, uint32_t);
-#undef SPRS_TRI_FOLD
+    dispatch_widths(out_idx_bytes, out_iptr_bytes, [&](auto i, auto p) {
+        using IT = typename decltype(i)::type;
+        using PT = typename decltype(p)::type;
+        hipLaunchKernelGGL((tri_fold_kernel<IT, PT>), g1, b1, 0, stream, (const uint64_t *)keys.u64(), (const uint64_t *)vals.u64(),
+                           (const uint64_t *)head.u64(), (const uint64_t *)gidx.u64(), n, n_outer, ngroups, (PT *)c->indptr,
+                           (IT *)c->indices, c->data);
+    });
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e != hipSuccess) {
@@ -133,9 +133,10 @@ int32_t assemble(uint64_t rows, uint64_t cols, uint64_t n, const I *row_inds, co
 int32_t triplets_to_cs(uint64_t rows, uint64_t cols, uint64_t n, const void *row_inds, const void *col_inds, int32_t in_idx_bytes,
                        const double *data, int32_t storage, int32_t out_idx_bytes, int32_t out_iptr_bytes, sprs_hip_csmat **out) {
     if (rows > 0xFFFFFFFFull || cols > 0xFFFFFFFFull) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "triplet assembly: more than 2^32 rows or columns is not supported");
-    if (in_idx_bytes == 8)
-        return assemble<uint64_t>(rows, cols, n, (const uint64_t *)row_inds, (const uint64_t *)col_inds, data, storage, out_idx_bytes, out_iptr_bytes, out);
-    return assemble<uint32_t>(rows, cols, n, (const uint32_t *)row_inds, (const uint32_t *)col_inds, data, storage, out_idx_bytes, out_iptr_bytes, out);
+    return dispatch_width(in_idx_bytes, [&](auto i) {
+        using I = typename decltype(i)::type;
+        return assemble<I>(rows, cols, n, (const I *)row_inds, (const I *)col_inds, data, storage, out_idx_bytes, out_iptr_bytes, out);
+    });
 }
 
 }  // namespace sprs_hip

@@ -219,3 +219,18 @@ def test_host_copies_and_temporaries_go_through_common_hpp():
         assert not re.search(r"\bhipMem(?:cpy|set)\(", text), "%s: blocking host copy outside copy_to_host / copy_to_device" % f
         m = re.search(r"\bstruct\s+(Tmp|DevTmp|Buf|TmpBuf|Work|Free)\b", text)
         assert not m, "%s defines its own temporary-buffer struct %s (use DevBuf, common.hpp)" % (f, m and m.group(1))
+
+
+def test_no_macro_wraps_a_kernel_launch():
+    """Kernel launches are written in ordinary (template) functions: no #define in sprs_amd/csrc has hipLaunchKernelGGL in its
+    body (continuation lines included), and the four-way index-width ladder is written out in common.hpp only (dispatch_widths)."""
+    csrc = os.path.join(ROOT, "sprs_amd", "csrc")
+    define = re.compile(r"^[ \t]*#[ \t]*define\b(?:.*\\\n)*.*$", re.M)
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".hpp")):
+            continue
+        text = open(os.path.join(csrc, f)).read()
+        for m in define.finditer(text):
+            assert "hipLaunchKernelGGL" not in m.group(0), "%s: macro around a kernel launch: %s" % (f, m.group(0).splitlines()[0])
+        if f != "common.hpp":
+            assert not re.search(r"== 8 && .*iptr_bytes == 8", text), "%s writes the index-width ladder out (use dispatch_widths)" % f

@@ -243,12 +243,9 @@ def test_order_of_additions_stress(hip):
                 hip.set_option("spgemm_lds_atomic", 1)
 
 
-@pytest.mark.parametrize("idx,ptr", IDX_COMBOS)
-def test_row_class_boundaries(hip, idx, ptr):
-    """Rows sitting exactly on the thresholds that route them (row_work_kernel): 64 / 65 and 512 / 513 products (hash
-    tables), 64 / 65 k's and `spgemm_mid` products (wave-per-row vs workgroup kernel), `spgemm_heavy` (one task per
-    window), with B wider than one 2^17-column window and columns on the window / bucket edges, empty rows of B among the
-    k's, for every index type."""
+def _row_class_operands(idx, ptr):
+    """The operands of test_row_class_boundaries: 13 rows of A over 200 rows of B of 2 * 2^17 + 4321 columns.  Returns A, B and,
+    per row of A, its products and its k's (what row_work_kernel routes by)."""
     rng = np.random.default_rng(5)
     cols = (1 << 17) * 2 + 4321
     n_b = 200
@@ -287,6 +284,16 @@ def test_row_class_boundaries(hip, idx, ptr):
     a_dt = rng.standard_normal(a_ix.size) * 10.0 ** rng.integers(-4, 5, size=a_ix.size)
     A = ((len(a_rows), n_b), a_ip.astype(ptr), a_ix.astype(idx), a_dt)
     ub = [int(lens[r].sum()) for r in a_rows]
+    return A, B, ub, [int(r.size) for r in a_rows]
+
+
+@pytest.mark.parametrize("idx,ptr", IDX_COMBOS)
+def test_row_class_boundaries(hip, idx, ptr):
+    """Rows sitting exactly on the thresholds that route them (row_work_kernel): 64 / 65 and 512 / 513 products (hash
+    tables), 64 / 65 k's and `spgemm_mid` products (wave-per-row vs workgroup kernel), `spgemm_heavy` (one task per
+    window), with B wider than one 2^17-column window and columns on the window / bucket edges, empty rows of B among the
+    k's, for every index type."""
+    A, B, ub, _ = _row_class_operands(idx, ptr)
     assert 64 in ub and 65 in ub and 512 in ub and 513 in ub
     for mid, heavy in ((65536, 131072), (max(ub[3] - 1, 513), 131072), (ub[3], 1024), (0, 2048)):
         hip.set_option("spgemm_mid", mid)
@@ -296,6 +303,88 @@ def test_row_class_boundaries(hip, idx, ptr):
         finally:
             hip.set_option("spgemm_mid", 65536)
             hip.set_option("spgemm_heavy", 131072)
+
+
+def _row_classes(ub, nk, mid_max, micro):
+    """The routing of row_work_kernel restated: the kernel family every row of A goes to, from its products (ub) and k's (nk).
+    mid_max is option spgemm_mid (it holds when B has its column-bucket table), micro whether the lane-group kernels are on."""
+    out = []
+    for p, k in zip(ub, nk):
+        if p == 0:
+            c = "none"
+        elif p <= 64:                                   # TINY_MAX
+            c = "tiny"
+            if micro:
+                if p <= 16 and k <= 16:
+                    c = "micro16"
+                elif p <= 32 and k <= 32:
+                    c = "micro32"
+                elif k <= 64:
+                    c = "micro64"
+        elif p <= 512:                                  # SMALL_MAX
+            c = "small"
+        elif k <= 64 and p <= mid_max:
+            c = "mid"
+        else:
+            c = "large"
+        out.append(c)
+    return out
+
+
+# one option off its default at a time (every option of the launches that no other test sets); the last two also run the
+# kept-plan path (plan, structure, numeric into that structure)
+_LAUNCH_VARIANTS = [
+    ({"spgemm_occupancy": 2}, False),
+    ({"spgemm_midwin": 14}, False),
+    ({"spgemm_mid_keep": 4}, True),
+    ({"spgemm_midwin_sym": 16}, False),
+    ({"spgemm_mid_keep_sym": 16}, False),
+    ({"spgemm_tokens": 2}, False),
+    ({"spgemm_tokens": 4}, False),
+    ({"spgemm_overlap": 1}, True),
+    ({"spgemm_keep_bits": 0}, False),
+    ({"spgemm_xcd_chunk": -1}, False),
+    ({"spgemm_winlog": 16, "spgemm_occupancy": 2}, False),
+    ({"spgemm_micro": 2}, False),
+]
+
+
+@pytest.mark.parametrize("idx,ptr", [(np.uint64, np.uint64), (np.uint32, np.uint32)])
+def test_launch_variants_match_the_oracle(hip, idx, ptr):
+    """Every option that picks a kernel instantiation, a flag word or a stream of the SpGEMM launches, off its default one at a
+    time, on the operands of test_row_class_boundaries: structure and value bits against the oracle, for the counting and the
+    numeric launches of one product and, under two variants, for the kept plan (numeric into an existing structure: no index
+    emission).  Each run must route rows to every kernel family — lane groups (the tiny hash table under spgemm_micro = 2,
+    which exists to send them there), hash tables, wave per row, workgroup — or the variant would prove nothing."""
+    from oracle import oracle
+    from sprs_amd import smmp
+    from sprs_amd.device import DeviceCsMat
+    A, B, ub, nk = _row_class_operands(idx, ptr)
+    assert B[2].size > B[0][0] and hip.get_option("spgemm_bucket") == 1        # B gets its bucket table: spgemm_mid holds
+    ref = oracle.mul_csr_csr(*A, *B, threads=1)
+    for opts, kept in _LAUNCH_VARIANTS:
+        defaults = {name: hip.get_option(name) for name in opts}
+        try:
+            for name, value in opts.items():
+                assert value != defaults[name], name
+                hip.set_option(name, value)
+            classes = set(_row_classes(ub, nk, hip.get_option("spgemm_mid"), hip.get_option("spgemm_micro") != 2))
+            short = {"tiny"} if opts.get("spgemm_micro") == 2 else {"micro16", "micro32", "micro64"}
+            assert classes & short and classes & {"tiny", "small"} and "mid" in classes and "large" in classes, (opts, classes)
+            check_against_oracle(A, B, exact_values=True, ref=ref)
+            if kept:
+                da, db = DeviceCsMat.from_host(*A), DeviceCsMat.from_host(*B)
+                plan = smmp.SpgemmPlan(da, db)
+                st = plan.structure()
+                _, sip, six, sdt = st.to_host()
+                assert np.array_equal(sip, ref[1]) and np.array_equal(six, ref[2]) and not sdt.any()
+                plan.numeric(st)                                     # value kernels only, into the existing structure
+                _, sip, six, sdt = st.to_host()
+                assert np.array_equal(sip, ref[1]) and np.array_equal(six, ref[2])
+                assert np.array_equal(sdt.view(np.uint64), ref[3].view(np.uint64)), opts
+        finally:
+            for name, value in defaults.items():
+                hip.set_option(name, value)
 
 
 def test_hub_rows_of_the_work_pass(hip):
