@@ -48,10 +48,16 @@ extern "C" {
 #define SPRS_HIP_HIP_ERROR 7
 /* no usable gfx950 device: the product path never falls back to the CPU */
 #define SPRS_HIP_NO_DEVICE 8
+/* LinalgError::SingularMatrix(SingularMatrixInfo { index, reason }), errors.rs:59-92: the triangular solves.
+ * sprs_hip_last_error() carries the reference's text, "Singular matrix at index {} ({reason})" */
+#define SPRS_HIP_SINGULAR_MATRIX 9
 
 /* CompressedStorage, sprs/src/sparse.rs:30-40 */
 #define SPRS_HIP_CSR 0
 #define SPRS_HIP_CSC 1
+/* which triangle sprs_hip_trisolve_f64 solves with: lsolve_* or usolve_* (sprs/src/sparse/linalg/trisolve.rs) */
+#define SPRS_HIP_LOWER 0
+#define SPRS_HIP_UPPER 1
 /* dense operands: C order (ndarray's standard layout) or Fortran order (`.f()`), with a leading dimension */
 #define SPRS_HIP_ROW_MAJOR 0
 #define SPRS_HIP_COL_MAJOR 1
@@ -298,6 +304,51 @@ typedef struct sprs_hip_gauss_seidel_info {
 int32_t sprs_hip_gauss_seidel_f64(sprs_hip_csmat *a, double *x_dev, const double *rhs_dev, uint64_t n,
                                   uint64_t max_iter, double eps, sprs_hip_gauss_seidel_info *info,
                                   void *stream);
+
+/* ---- sparse triangular solves (sprs::linalg::trisolve) --------------------- */
+
+/* levels = length of the longest chain of unknowns that must be solved one after the other (what bounds a solve on
+ * the device).  After SPRS_HIP_SINGULAR_MATRIX: singular_index = the index the reference reports, singular_reason =
+ * 1 "a numeric 0" (a stored diagonal == 0; also a CSR diagonal that is not stored, which the CSR functions do not
+ * tell apart) or 2 "a structural 0" (CSC only: the diagonal is not stored).  Otherwise UINT64_MAX and 0. */
+typedef struct sprs_hip_trisolve_info {
+    uint64_t levels;
+    uint64_t singular_index;
+    int32_t singular_reason;
+} sprs_hip_trisolve_info;
+
+/* Twins of the four dense-rhs solves of sprs/src/sparse/linalg/trisolve.rs, in place on the n doubles of x_dev (the
+ * right-hand side on entry, the solution on return).  The handle's storage selects the CSR or the CSC function, uplo
+ * lsolve (SPRS_HIP_LOWER) or usolve (SPRS_HIP_UPPER):
+ *
+ *   solve        order of unknowns   subtractions into unknown r, in this order          singular when
+ *   lsolve_csr   0 .. n-1            stored entries of row r with c < r, stored order    diagonal not stored or == 0
+ *                (trisolve.rs:30-73)                                                      ("diagonal element is 0")
+ *   usolve_csr   n-1 .. 0            stored entries of row r with c > r, stored order    the same ("diagonal element is a
+ *                (trisolve.rs:219-262)                                                    numeric 0")
+ *   lsolve_csc   0 .. n-1            entries (r, c) with c < r, ascending c              not stored: "a structural 0";
+ *                (trisolve.rs:85-149)                                                     stored and == 0: "a numeric 0"
+ *   usolve_csc   n-1 .. 0            entries (r, c) with c > r, DESCENDING c             as lsolve_csc
+ *                (trisolve.rs:161-210)
+ *
+ * The matrix need not be triangular: the other triangle is skipped.  Every update is x -= val * x[c] with a rounded
+ * multiply and a rounded subtract, the last step one IEEE division by the diagonal: the solution is bit-identical to
+ * the reference's (usolve_csr and usolve_csc differ in bits from each other, as they do there).  -0.0 on the diagonal
+ * counts as zero, NaN does not.  On the device the unknowns run in dependency-level order (computed once per handle
+ * and triangle; the lower order is the Gauss-Seidel one) and a row reads an earlier unknown as soon as it has been
+ * published.  A CSC handle is solved on its cached CSR form; a transpose view of a CSR factor L is a CSC handle, so
+ * L^T x = b needs no copy of the caller's making.
+ * Indices must be sorted inside each outer slice, as every validated handle has them: an unvalidated unsorted handle
+ * gets no promise about the result.
+ * SPRS_HIP_DIM_MISMATCH unless A.rows == A.cols ("Non square matrix passed to solver") == n ("Dimension mismatch")
+ * (check_solver_dimensions, trisolve.rs:10-21); SPRS_HIP_INVALID_ARG for a NULL handle or vector, another uplo, or
+ * n >= 2^32; n == 0 is OK with no work.
+ * SPRS_HIP_SINGULAR_MATRIX where the reference returns Err(SingularMatrix): the index is the first singular one in
+ * the reference's processing order (the smallest for SPRS_HIP_LOWER, the largest for SPRS_HIP_UPPER); the contents of
+ * x_dev are unspecified then.
+ * Blocks until done (the singular report needs a read-back); runs its work on `stream`.  Deterministic. */
+int32_t sprs_hip_trisolve_f64(sprs_hip_csmat *a, int32_t uplo, double *x_dev, uint64_t n,
+                              sprs_hip_trisolve_info *info, void *stream);
 
 /* ---- SpGEMM ------------------------------------------------------------- */
 

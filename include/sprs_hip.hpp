@@ -454,6 +454,42 @@ inline GaussSeidelResult gauss_seidel(const DeviceCsMat &mat, DeviceVec &x, cons
                                     nullptr));
     return GaussSeidelResult{info.converged != 0, info.iterations, info.error, info.levels};
 }
+
+// The four dense-rhs solves of sprs::linalg::trisolve (sprs/src/sparse/linalg/trisolve.rs), in place on rhs.  Where the
+// reference panics (check_solver_dimensions, "Storage mismatch") Error is thrown with its text; where it returns
+// Err(LinalgError::SingularMatrix) SingularMatrix is thrown, with the reference's index and message.
+struct SingularMatrix : Error {
+    uint64_t index;
+    int32_t reason;       // 1 a numeric zero (also a CSR diagonal that is not stored), 2 a structural zero (CSC only)
+    SingularMatrix(const std::string &m, uint64_t i, int32_t r) : Error(SPRS_HIP_SINGULAR_MATRIX, m), index(i), reason(r) {}
+};
+struct TriSolveResult {
+    uint64_t levels;      // longest chain of unknowns that must be solved one after the other (device-side information)
+};
+namespace detail {
+inline TriSolveResult trisolve(const DeviceCsMat &mat, DeviceVec &rhs, bool csr, int32_t uplo) {
+    if (mat.rows() != mat.cols()) throw Error(SPRS_HIP_DIM_MISMATCH, "Non square matrix passed to solver");
+    if (mat.cols() != rhs.dim()) throw Error(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    if (mat.is_csr() != csr) throw Error(SPRS_HIP_STORAGE_MISMATCH, "Storage mismatch");
+    sprs_hip_trisolve_info info{};
+    const int32_t status = sprs_hip_trisolve_f64(const_cast<sprs_hip_csmat *>(mat.handle()), uplo, rhs.ptr(), rhs.dim(), &info, nullptr);
+    if (status == SPRS_HIP_SINGULAR_MATRIX) throw SingularMatrix(sprs_hip_last_error(), info.singular_index, info.singular_reason);
+    check(status);
+    return TriSolveResult{info.levels};
+}
+}  // namespace detail
+inline TriSolveResult lsolve_csr_dense_rhs(const DeviceCsMat &lower_tri_mat, DeviceVec &rhs) {   // trisolve.rs:30-73
+    return detail::trisolve(lower_tri_mat, rhs, true, SPRS_HIP_LOWER);
+}
+inline TriSolveResult lsolve_csc_dense_rhs(const DeviceCsMat &lower_tri_mat, DeviceVec &rhs) {   // trisolve.rs:85-149
+    return detail::trisolve(lower_tri_mat, rhs, false, SPRS_HIP_LOWER);
+}
+inline TriSolveResult usolve_csc_dense_rhs(const DeviceCsMat &upper_tri_mat, DeviceVec &rhs) {   // trisolve.rs:161-210
+    return detail::trisolve(upper_tri_mat, rhs, false, SPRS_HIP_UPPER);
+}
+inline TriSolveResult usolve_csr_dense_rhs(const DeviceCsMat &upper_tri_mat, DeviceVec &rhs) {   // trisolve.rs:219-262
+    return detail::trisolve(upper_tri_mat, rhs, true, SPRS_HIP_UPPER);
+}
 }  // namespace linalg
 
 // Result blocks released by ~DeviceCsMat stay in the library's pool for the next result (sprs_hip.h);

@@ -12,6 +12,9 @@ pub const SPRS_HIP_INVALID_ARG: i32 = 5;
 pub const SPRS_HIP_OUT_OF_MEMORY: i32 = 6;
 pub const SPRS_HIP_HIP_ERROR: i32 = 7;
 pub const SPRS_HIP_NO_DEVICE: i32 = 8;
+pub const SPRS_HIP_SINGULAR_MATRIX: i32 = 9;
+pub const SPRS_HIP_LOWER: i32 = 0;
+pub const SPRS_HIP_UPPER: i32 = 1;
 pub const SPRS_HIP_CSR: i32 = 0;
 pub const SPRS_HIP_CSC: i32 = 1;
 pub const SPRS_HIP_ROW_MAJOR: i32 = 0;
@@ -61,6 +64,16 @@ pub struct sprs_hip_gauss_seidel_info {
     pub levels: u64,
 }
 
+/// result of sprs_hip_trisolve_f64 (include/sprs_hip.h; the reference's sparse/linalg/trisolve.rs).  Filled in by the
+/// library before any use: singular_index = u64::MAX and singular_reason = 0 unless the matrix is singular
+#[repr(C)]
+#[derive(Debug, Clone, Copy, Default)]
+pub struct sprs_hip_trisolve_info {
+    pub levels: u64,
+    pub singular_index: u64,
+    pub singular_reason: i32,
+}
+
 extern "C" {
     pub fn sprs_hip_last_error() -> *const c_char;
     pub fn sprs_hip_last_hip_code() -> i32;
@@ -80,6 +93,8 @@ extern "C" {
                                  info: *mut sprs_hip_bicgstab_info, stream: *mut c_void) -> i32;
     pub fn sprs_hip_gauss_seidel_f64(a: *mut sprs_hip_csmat, x_dev: *mut f64, rhs_dev: *const f64, n: u64, max_iter: u64,
                                      eps: f64, info: *mut sprs_hip_gauss_seidel_info, stream: *mut c_void) -> i32;
+    pub fn sprs_hip_trisolve_f64(a: *mut sprs_hip_csmat, uplo: i32, x_dev: *mut f64, n: u64,
+                                 info: *mut sprs_hip_trisolve_info, stream: *mut c_void) -> i32;
     pub fn sprs_hip_csmat_upload(
         out: *mut *mut sprs_hip_csmat, storage: i32, rows: u64, cols: u64,
         indptr: *const c_void, iptr_bytes: i32, indices: *const c_void, idx_bytes: i32,

@@ -393,6 +393,53 @@ pub mod linalg {
         }
         if info.converged != 0 { Ok((info.iterations as usize, info.error)) } else { Err(info.error) }
     }
+
+    /// The four dense-rhs solves of `sprs::linalg::trisolve` (sparse/linalg/trisolve.rs) with a device-resident `rhs`,
+    /// solved in place: the same panics ("Non square matrix passed to solver", "Dimension mismatch", "Storage mismatch"),
+    /// the same `Err(LinalgError::SingularMatrix)` with the reference's index and reason, bit-identical solutions.
+    fn trisolve(mat: &DeviceCsMat, rhs: &mut DeviceVec, csr: bool, uplo: i32, csr_reason: &'static str)
+        -> Result<(), sprs::errors::LinalgError> {
+        let (rows, cols, _, _, _, st) = mat.info();
+        // check_solver_dimensions (trisolve.rs:10-21) comes before the storage assert in all four functions
+        assert_eq!(cols, rows, "Non square matrix passed to solver");
+        assert_eq!(cols, rhs.len, "Dimension mismatch");
+        assert!((st == sys::SPRS_HIP_CSR) == csr, "Storage mismatch");
+        let mut info = sys::sprs_hip_trisolve_info::default();
+        let status = unsafe { sys::sprs_hip_trisolve_f64(mat.h, uplo, rhs.ptr, rhs.len as u64, &mut info, std::ptr::null_mut()) };
+        if status == sys::SPRS_HIP_SINGULAR_MATRIX {
+            let reason = match (csr, info.singular_reason) {
+                (true, _) => csr_reason,
+                (false, 2) => "diagonal element is a structural 0",
+                (false, _) => "diagonal element is a numeric 0",
+            };
+            return Err(sprs::errors::LinalgError::SingularMatrix(sprs::errors::SingularMatrixInfo {
+                index: info.singular_index as usize,
+                reason,
+            }));
+        }
+        check(status);
+        Ok(())
+    }
+
+    /// Twin of `lsolve_csr_dense_rhs` (trisolve.rs:30-73); the upper triangle of `lower_tri_mat` is ignored.
+    pub fn lsolve_csr_dense_rhs(lower_tri_mat: &DeviceCsMat, rhs: &mut DeviceVec) -> Result<(), sprs::errors::LinalgError> {
+        trisolve(lower_tri_mat, rhs, true, sys::SPRS_HIP_LOWER, "diagonal element is 0")
+    }
+
+    /// Twin of `lsolve_csc_dense_rhs` (trisolve.rs:85-149).
+    pub fn lsolve_csc_dense_rhs(lower_tri_mat: &DeviceCsMat, rhs: &mut DeviceVec) -> Result<(), sprs::errors::LinalgError> {
+        trisolve(lower_tri_mat, rhs, false, sys::SPRS_HIP_LOWER, "")
+    }
+
+    /// Twin of `usolve_csc_dense_rhs` (trisolve.rs:161-210).
+    pub fn usolve_csc_dense_rhs(upper_tri_mat: &DeviceCsMat, rhs: &mut DeviceVec) -> Result<(), sprs::errors::LinalgError> {
+        trisolve(upper_tri_mat, rhs, false, sys::SPRS_HIP_UPPER, "")
+    }
+
+    /// Twin of `usolve_csr_dense_rhs` (trisolve.rs:219-262); the lower triangle of `upper_tri_mat` is ignored.
+    pub fn usolve_csr_dense_rhs(upper_tri_mat: &DeviceCsMat, rhs: &mut DeviceVec) -> Result<(), sprs::errors::LinalgError> {
+        trisolve(upper_tri_mat, rhs, true, sys::SPRS_HIP_UPPER, "diagonal element is a numeric 0")
+    }
 }
 
 /// Result blocks released by `Drop for DeviceCsMat` stay pooled inside the library; this returns them to

@@ -14,8 +14,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SPRS_HIP_LIBRARY") or os.path.join(_HERE, "libsprs_hip.so")
 
 OK, DIM_MISMATCH, STORAGE_MISMATCH, INDEX_OVERFLOW, BAD_STRUCTURE, INVALID_ARG, \
-    OUT_OF_MEMORY, HIP_ERROR, NO_DEVICE = range(9)
+    OUT_OF_MEMORY, HIP_ERROR, NO_DEVICE, SINGULAR_MATRIX = range(10)
 CSR, CSC = 0, 1
+LOWER, UPPER = 0, 1
 ROW_MAJOR, COL_MAJOR = 0, 1
 ROUTE_RCCL, ROUTE_PEER = 0, 1
 
@@ -23,6 +24,7 @@ STATUS_NAMES = {
     OK: "OK", DIM_MISMATCH: "DIM_MISMATCH", STORAGE_MISMATCH: "STORAGE_MISMATCH",
     INDEX_OVERFLOW: "INDEX_OVERFLOW", BAD_STRUCTURE: "BAD_STRUCTURE", INVALID_ARG: "INVALID_ARG",
     OUT_OF_MEMORY: "OUT_OF_MEMORY", HIP_ERROR: "HIP_ERROR", NO_DEVICE: "NO_DEVICE",
+    SINGULAR_MATRIX: "SINGULAR_MATRIX",
 }
 
 u64, i32, i64, vp = C.c_uint64, C.c_int32, C.c_int64, C.c_void_p
@@ -59,6 +61,7 @@ SIGNATURES = {
     "sprs_hip_spgemm_plan_free": (i32, [vp]),
     "sprs_hip_bicgstab_f64": (i32, [vp, vp, vp, u64, C.c_double, u64, C.c_double, vp, vp, vp]),
     "sprs_hip_gauss_seidel_f64": (i32, [vp, vp, vp, u64, u64, C.c_double, vp, vp]),
+    "sprs_hip_trisolve_f64": (i32, [vp, i32, vp, u64, vp, vp]),
     "sprs_hip_csmat_upload": (i32, [P(vp), i32, u64, u64, vp, i32, vp, i32, vp, i32]),
     "sprs_hip_csmat_wrap_device": (i32, [P(vp), i32, u64, u64, u64, vp, i32, vp, i32, vp]),
     "sprs_hip_csmat_info": (i32, [vp, P(u64), P(u64), P(u64), P(i32), P(i32), P(i32)]),

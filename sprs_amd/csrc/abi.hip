@@ -520,7 +520,7 @@ int32_t sprs_hip_csmat_download_outer(const sprs_hip_csmat *m, uint64_t start, u
     return SPRS_HIP_OK;
 }
 
-// Everything a handle derives from its arrays: the SpMV / SpMM / Gauss-Seidel plans (they copy values), the copy in the other
+// Everything a handle derives from its arrays: the SpMV / SpMM plans (they copy values), the Gauss-Seidel / triangular-solve row orders, the copy in the other
 // storage order and the transpose view kept for dense . sparse products.  Called whenever the values (or the arrays) change:
 // refresh, free and BOTH numeric SpGEMM entries, which rewrite C's values in place (a stale CSC copy of C
 // would otherwise serve later products).
@@ -528,6 +528,7 @@ static void invalidate_caches(sprs_hip_csmat *m) {
     m->plan.release();
     m->mm.release();
     m->gs.release();
+    m->tri_upper.release();
     m->cv.release();
     if (m->t_view) (void)sprs_hip_csmat_free(m->t_view);
     m->t_view = nullptr;
@@ -923,6 +924,26 @@ int32_t sprs_hip_csmat_prepare(sprs_hip_csmat *m, void *stream) {
     }
     SPRS_TRY(csr_form(m, &csr));               // a CSC handle multiplies through its CSR copy: that is the handle to prepare
     return spmv_prepare(csr, (hipStream_t)stream);
+}
+
+// The four dense-rhs solves of sprs::linalg::trisolve behind one entry: the handle's storage selects the CSR or CSC function, uplo
+// lsolve or usolve.  A CSC handle is solved on its CSR form (the as_other copy above), where the row orders then live; a->mu is
+// held for the whole (blocking) call, so a refresh on another thread cannot drop that copy under the solve.
+int32_t sprs_hip_trisolve_f64(sprs_hip_csmat *a, int32_t uplo, double *x_dev, uint64_t n, sprs_hip_trisolve_info *info, void *stream) {
+    clear_error();
+    if (!a) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if (uplo != SPRS_HIP_LOWER && uplo != SPRS_HIP_UPPER) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "uplo must be SPRS_HIP_LOWER or SPRS_HIP_UPPER");
+    // check_solver_dimensions, trisolve.rs:10-21
+    if (a->rows != a->cols) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Non square matrix passed to solver");
+    if (a->cols != n) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    if (n && !x_dev) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL vector");
+    if (n >= (1ull << 32)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "triangular solve: 2^32 rows or more are not supported");
+    if (info) *info = sprs_hip_trisolve_info{0, UINT64_MAX, 0};
+    if (n == 0) return SPRS_HIP_OK;
+    std::lock_guard<std::recursive_mutex> lock(a->mu);
+    sprs_hip_csmat *csr = nullptr;
+    SPRS_TRY(csr_form(a, &csr));
+    return trisolve_f64(csr, uplo == SPRS_HIP_UPPER, a->storage == SPRS_HIP_CSC, x_dev, n, info, (hipStream_t)stream);
 }
 
 static int32_t vec_args_ok(const double *x_dev, uint64_t x_len, double *y_dev, uint64_t y_len) {

@@ -234,7 +234,8 @@ struct sprs_hip_csmat {
     std::recursive_mutex mu;   // guards plan / mm: held from the look-up (or rebuild) of a plan until the kernels that read it are launched
     sprs_hip::SpmvPlan plan;
     sprs_hip::SpmmPlan mm;
-    sprs_hip::GsPlan gs;
+    sprs_hip::GsPlan gs;                 // rows by the levels of the stored c < row: Gauss-Seidel and the lower triangular solves
+    sprs_hip::GsPlan tri_upper;          // the mirror (stored c > row, levels rising from the last row): the upper triangular solves (trisolve.hpp)
     sprs_hip::CsvecScratch cv;           // temporaries of the sparse-vector products that run on this handle (csvec.hpp)
     sprs_hip_csmat *t_view = nullptr;    // transpose view (of the CSC form) kept for dense . sparse products (sprs_hip_dense_dot_csmat_f64): its SpMM / SpMV plans live as long as the values do; dropped with as_other
     sprs_hip_csmat *as_other = nullptr;  // the handle in the OTHER storage order (to_other_storage, csmat.rs:1405-1426): made by the first product that needs it (a CSC operand of a dense product / SpMV runs on its CSR form), dropped by refresh / free
@@ -372,6 +373,8 @@ int32_t bicgstab_f64(sprs_hip_csmat *a, const double *x0, const double *b, uint6
 // gauss_seidel.hip
 int32_t gauss_seidel_f64(sprs_hip_csmat *a, double *x, const double *rhs, uint64_t n, uint64_t max_iter, double eps,
                          sprs_hip_gauss_seidel_info *info, hipStream_t stream);
+// trisolve.hpp (compiled in gauss_seidel.hip): csr = the CSR form of the caller's handle, csc = that handle is CSC
+int32_t trisolve_f64(sprs_hip_csmat *csr, bool upper, bool csc, double *x, uint64_t n, sprs_hip_trisolve_info *info, hipStream_t stream);
 int32_t slice_outer(const sprs_hip_csmat *m, uint64_t start, uint64_t end, sprs_hip_csmat **out);
 // csvec.hpp (compiled in spmv.hip)
 int32_t csvec_alloc(sprs_hip_csvec **out, uint64_t dim, uint64_t nnz, int32_t idx_bytes, int32_t decl_idx_bytes);

@@ -66,6 +66,42 @@ __device__ __forceinline__ unsigned long long gs_peek(const unsigned long long *
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// the next 64 positions of the order a kernel walks: one atomic per wave, handed to its lanes (shared by the sweep, the level
+// recurrence and the triangular solves of trisolve.hpp)
+__device__ __forceinline__ uint64_t gs_draw(unsigned int *next_chunk, uint32_t lane) {
+    unsigned int q = 0;
+    if (lane == 0) q = atomicAdd(next_chunk, 1u);
+    return (uint64_t)(unsigned int)__builtin_amdgcn_readfirstlane((int)q) * 64u;
+}
+
+// The spin guard of every polling loop here, called once per round by the whole wave while some lane still waits.  `spins`
+// counts the rounds in which NO lane of the wave got anywhere (a lane that has finished its row would otherwise count every
+// round its neighbours are still busy with theirs and raise the timeout on a healthy sweep); past GS_SPIN_LIMIT the wave raises
+// GS_TIMEOUT in the status word, which every wave looks at every 64 idle rounds.  Returns true when the wave must leave the
+// kernel; otherwise backs off (at most max_naps pauses, growing with the wait) when nobody moved, so the publishers run.
+__device__ __forceinline__ bool gs_spin_guard(bool moved, uint32_t &spins, unsigned int *status, uint32_t max_naps) {
+    spins = __ballot(moved) != 0ull ? 0u : spins + 1u;
+    unsigned int st = 0;
+    if ((spins & 63u) == 63u) st = __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (spins > GS_SPIN_LIMIT) {
+        atomicOr(status, GS_TIMEOUT);
+        st = GS_TIMEOUT;
+    }
+    if (__ballot((st & GS_TIMEOUT) != 0u) != 0ull) return true;
+    if (__ballot(moved) == 0ull) {
+        uint32_t naps = spins < 8u ? 1u : spins < 32u ? 2u : spins < 128u ? 4u : 8u;
+        if (naps > max_naps) naps = max_naps;
+        for (uint32_t q = 0; q < naps; ++q) SPRS_POLL_PAUSE();
+    }
+    return false;
+}
+
+// a call's temporaries must outlive the work enqueued on them: declared after them, it drains the stream before they go
+struct StreamDrain {
+    hipStream_t s;
+    ~StreamDrain() { (void)hipStreamSynchronize(s); }
+};
+
 // the XCD (accelerator die: its own L2) this wave runs on, from the hardware register
 __device__ __forceinline__ uint32_t gs_xcc_id() {
 #ifdef SPRS_HIP_EMU
@@ -88,12 +124,7 @@ __global__ __launch_bounds__(GS_BLOCK) void gs_sweep_kernel(const PTR *__restric
                                                             unsigned int *next_chunk, unsigned int *status, uint32_t max_naps) {
     const uint32_t lane = threadIdx.x & 63u;
     if (ONE_XCD && gs_xcc_id() != 0u) return;
-    auto draw = [&]() -> uint64_t {
-        unsigned int q = 0;
-        if (lane == 0) q = atomicAdd(next_chunk, 1u);
-        return (uint64_t)(unsigned int)__builtin_amdgcn_readfirstlane((int)q) * 64u;
-    };
-    for (uint64_t base = draw(); base < n; base = draw()) {
+    for (uint64_t base = gs_draw(next_chunk, lane); base < n; base = gs_draw(next_chunk, lane)) {
         const uint64_t pos = base + lane;
         bool done = pos >= n;
         uint32_t row = 0;
@@ -183,23 +214,7 @@ __global__ __launch_bounds__(GS_BLOCK) void gs_sweep_kernel(const PTR *__restric
                 }
             }
             more = __ballot(!done) != 0ull;
-            if (more) {
-                // rounds in which NO lane of the wave got anywhere (a lane that has finished its row would otherwise count every
-                // round its neighbours are still busy with theirs and raise the timeout on a healthy sweep)
-                spins = __ballot(moved) != 0ull ? 0u : spins + 1u;
-                unsigned int st = 0;
-                if ((spins & 63u) == 63u) st = __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (spins > GS_SPIN_LIMIT) {
-                    atomicOr(status, GS_TIMEOUT);
-                    st = GS_TIMEOUT;
-                }
-                if (__ballot((st & GS_TIMEOUT) != 0u) != 0ull) return;
-                if (__ballot(moved) == 0ull) {                         // nobody got anywhere: let the publishers run, and back off
-                    uint32_t naps = spins < 8u ? 1u : spins < 32u ? 2u : spins < 128u ? 4u : 8u;
-                    if (naps > max_naps) naps = max_naps;
-                    for (uint32_t q = 0; q < naps; ++q) SPRS_POLL_PAUSE();
-                }
-            }
+            if (more && gs_spin_guard(moved, spins, status, max_naps)) return;
         }
     }
 }
@@ -251,50 +266,54 @@ __global__ __launch_bounds__(GS_BLOCK) void gs_resid_final_kernel(const double *
 // lower lane of the same wave, which the polling loop serves first) — no grid barrier, no deadlock.  Then one stable radix sort
 // of (level, row).  Rounds 1 to 3 downloaded the structure and ran this recurrence serially on the host: 0.41 s for the 1.7e7
 // rows of the 4096 x 4096 heat system.
+// UPPER is the mirror, for the upper triangular solves (trisolve.hpp): level(i) = 1 + max level(c) over the stored c > i.  The
+// rows are drawn from the END (position q is row n - 1 - q) and a row is read from its last entry backwards, so the argument
+// stands as it is: every row a wave can wait for has a LARGER number, i.e. a smaller position — drawn by a wave that already
+// runs, or a lower lane of the same wave.
 constexpr unsigned int LV_PENDING = 0xFFFFFFFFu;
 
-template <typename IDX, typename PTR>
+template <typename IDX, typename PTR, bool UPPER>
 __global__ __launch_bounds__(GS_BLOCK) void gs_level_kernel(const PTR *__restrict__ indptr, const IDX *__restrict__ indices, uint64_t n,
                                                             unsigned int *level, unsigned int *next_chunk, unsigned int *status,
                                                             unsigned int *top, unsigned long long *no_diag) {
     const uint32_t lane = threadIdx.x & 63u;
-    auto draw = [&]() -> uint64_t {
-        unsigned int q = 0;
-        if (lane == 0) q = atomicAdd(next_chunk, 1u);
-        return (uint64_t)(unsigned int)__builtin_amdgcn_readfirstlane((int)q) * 64u;
-    };
-    for (uint64_t base = draw(); base < n; base = draw()) {
-        const uint64_t row = base + lane;
-        bool done = row >= n, diag = false;
-        uint64_t p = 0, end = 0, c = row;
+    for (uint64_t base = gs_draw(next_chunk, lane); base < n; base = gs_draw(next_chunk, lane)) {
+        const uint64_t pos = base + lane;
+        const uint64_t row = UPPER ? n - 1 - pos : pos;        // (wraps past the end for pos >= n: such a lane is done from the start)
+        bool done = pos >= n, diag = false;
+        uint64_t p = 0, end = 0, c = row;                      // the entries still to look at: [p, end), taken from the front (from the back: UPPER)
         uint32_t lv = 0, spins = 0;
         if (!done) {
             p = (uint64_t)indptr[row];
             end = (uint64_t)indptr[row + 1];
-            if (p < end) c = (uint64_t)indices[p];      // the column the lane waits for stays in a register between the rounds
+            if (p < end) c = (uint64_t)indices[UPPER ? end - 1 : p];      // the column the lane waits for stays in a register between the rounds
         }
         // One dependency per lane and round.  A dependency on a row of this very wave (the left neighbour of a grid row, say) is
         // answered by a shuffle — through memory the 64 lanes of a chunk of a chain would be 64 round trips one after the other
         // (first version: 1.6 s for the 4096 x 4096 heat system, slower than the host pass it replaces) — everything else by an
-        // L1-bypassing load of the level word.  Columns ascend inside a row: the first c >= row ends the row's dependencies.
+        // L1-bypassing load of the level word.  Columns ascend inside a row: the first c >= row (c <= row from the back: UPPER)
+        // ends the row's dependencies.
         while (__ballot(!done) != 0ull) {
             bool moved = false;
             const bool want = !done && p < end;
-            const bool in_wave = want && c < row && c >= base;
+            const bool dep = want && (UPPER ? c > row : c < row);
+            const uint64_t c_pos = UPPER ? n - 1 - c : c;      // the position at which row c was drawn
+            const bool in_wave = dep && c_pos >= base;
             const unsigned int mine = done ? lv : LV_PENDING;
-            const unsigned int from_wave = (unsigned int)__shfl((int)mine, in_wave ? (int)(c - base) : (int)lane, 64);
+            const unsigned int from_wave = (unsigned int)__shfl((int)mine, in_wave ? (int)(c_pos - base) : (int)lane, 64);
             if (want) {
-                if (c < row) {
+                if (dep) {
                     const unsigned int l = in_wave ? from_wave : __hip_atomic_load(level + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     if (l != LV_PENDING) {
                         if (l + 1u > lv) lv = l + 1u;
-                        ++p;
-                        if (p < end) c = (uint64_t)indices[p];
+                        if (UPPER) --end;
+                        else ++p;
+                        if (p < end) c = (uint64_t)indices[UPPER ? end - 1 : p];
                         moved = true;
                     }
                 } else {
                     diag = c == row;
-                    p = end;                      // the rest of the row lies above the diagonal
+                    p = end;                      // the rest of the row lies on the other side of the diagonal
                     moved = true;
                 }
             }
@@ -305,19 +324,11 @@ __global__ __launch_bounds__(GS_BLOCK) void gs_level_kernel(const PTR *__restric
                 moved = true;
             }
             if (__ballot(!done) == 0ull) break;
-            spins = __ballot(moved) != 0ull ? 0u : spins + 1u;          // rounds in which no lane of the wave got anywhere
-            unsigned int st = 0;
-            if ((spins & 63u) == 63u) st = __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (spins > GS_SPIN_LIMIT) {
-                atomicOr(status, GS_TIMEOUT);
-                st = GS_TIMEOUT;
-            }
-            if (__ballot((st & GS_TIMEOUT) != 0u) != 0ull) return;
-            if (__ballot(moved) == 0ull) SPRS_POLL_PAUSE();
+            if (gs_spin_guard(moved, spins, status, 1u)) return;
         }
         // the highest level of the chunk: ONE atomic per wave (one per row — 1.7e7 atomics on a single word — was the whole
         // second of the first version)
-        uint32_t wmax = row < n ? lv : 0u;
+        uint32_t wmax = pos < n ? lv : 0u;
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) {
             const uint32_t o = (uint32_t)__shfl_down((int)wmax, off, 64);
@@ -339,9 +350,8 @@ __global__ void gs_order_kernel(const uint64_t *__restrict__ vals, uint64_t n, u
     if (i < n) order[i] = (uint32_t)vals[i];
 }
 
-template <typename IDX, typename PTR>
-int32_t gs_plan_build(sprs_hip_csmat *a) {
-    GsPlan &pl = a->gs;
+template <typename IDX, typename PTR, bool UPPER>
+int32_t gs_plan_build(sprs_hip_csmat *a, GsPlan &pl) {
     const uint64_t n = a->rows;
     hipStream_t stream = nullptr;
     DevBuf level, words, keys, vals;
@@ -360,7 +370,7 @@ int32_t gs_plan_build(sprs_hip_csmat *a) {
         uint64_t grid = (uint64_t)(ncu > 0 ? ncu : 1) * 4;
         const uint64_t need = (n + GS_BLOCK - 1) / GS_BLOCK;
         if (grid > need) grid = need;
-        hipLaunchKernelGGL((gs_level_kernel<IDX, PTR>), dim3((unsigned)grid), dim3(GS_BLOCK), 0, stream, (const PTR *)a->indptr,
+        hipLaunchKernelGGL((gs_level_kernel<IDX, PTR, UPPER>), dim3((unsigned)grid), dim3(GS_BLOCK), 0, stream, (const PTR *)a->indptr,
                            (const IDX *)a->indices, n, level.as<unsigned int>(), w, w + 1, w + 2, (unsigned long long *)(w + 4));
         SPRS_TRY_HIP(hipGetLastError());
         hipLaunchKernelGGL(gs_level_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const unsigned int *)level.as<unsigned int>(), n,
@@ -664,7 +674,7 @@ int32_t gs_impl(sprs_hip_csmat *a, double *x, const double *rhs, uint64_t n, uin
     // held for the whole solve: the level order (and the SpMV plan of the residual) must outlive every launch that reads them;
     // sprs_hip_csmat_refresh / _free on another thread wait (recursive: the SpMV of the residual locks again)
     std::lock_guard<std::recursive_mutex> lock(a->mu);
-    if (!a->gs.built) SPRS_TRY((gs_plan_build<IDX, PTR>(a)));
+    if (!a->gs.built) SPRS_TRY((gs_plan_build<IDX, PTR, false>(a, a->gs)));
     const uint32_t *order = a->gs.order;
     const uint64_t nlevels = a->gs.nlevels, no_diag_row = a->gs.no_diag_row;
     // ---- the band schedule, when the matrix fits one ----
@@ -707,10 +717,8 @@ int32_t gs_impl(sprs_hip_csmat *a, double *x, const double *rhs, uint64_t n, uin
     unsigned int sweep_words[2] = {0, 0};
     double h_sum = 0.0;
     DevBuf buf, words;
-    struct Drain {                              // declared last, so it runs first: an early return must not leave copies into this
-        hipStream_t s;                          // frame's variables (sweep_words) or kernels on buf / words in flight
-        ~Drain() { (void)hipStreamSynchronize(s); }
-    } drain{stream};
+    StreamDrain drain{stream};                  // declared last, so it runs first: an early return must not leave copies into this
+                                                // frame's variables (sweep_words) or kernels on buf / words in flight
     SPRS_TRY_HIP(buf.alloc((2 * n + nchunks + 8) * sizeof(double)));
     SPRS_TRY_HIP(words.alloc(64));
     double *other = buf.as<double>(), *v = other + n, *partial = v + n, *scal = partial + nchunks;
@@ -796,6 +804,10 @@ int32_t gs_impl(sprs_hip_csmat *a, double *x, const double *rhs, uint64_t n, uin
 }
 
 }  // namespace
+
+// sparse triangular solves (lsolve / usolve): the same recurrence without the previous iterate.  Kernel and launcher live in
+// trisolve.hpp, compiled here: they share the level plan and the device helpers above
+#include "trisolve.hpp"
 
 int32_t gauss_seidel_f64(sprs_hip_csmat *a, double *x, const double *rhs, uint64_t n, uint64_t max_iter, double eps,
                          sprs_hip_gauss_seidel_info *info, hipStream_t stream) {

@@ -1,7 +1,8 @@
 """Host mirror of the reference's two callers that loop on the SpMV, over the device path:
 sprs::linalg::bicgstab (sprs/src/sparse/linalg/bicgstab.rs) behind `sprs_hip_bicgstab_f64` (every vector resident
 in HBM: two SpMVs, four fused element-wise kernels and three dot launches per iteration) and the Gauss-Seidel
-solver of the heat example (sprs/examples/heat.rs:103-139) behind `sprs_hip_gauss_seidel_f64`."""
+solver of the heat example (sprs/examples/heat.rs:103-139) behind `sprs_hip_gauss_seidel_f64`; and of the four dense-rhs
+triangular solves of sprs::linalg::trisolve (sprs/src/sparse/linalg/trisolve.rs) behind `sprs_hip_trisolve_f64`."""
 import ctypes as C
 
 from . import _ffi
@@ -98,3 +99,60 @@ def gauss_seidel(mat, x, rhs, max_iter, eps, stream=None):
     check(lib.sprs_hip_gauss_seidel_f64(mat._h, C.c_void_p(x.ptr), C.c_void_p(rhs.ptr), x.n, int(max_iter), float(eps),
                                         C.byref(info), C.c_void_p(int(stream) if stream else 0)))
     return GaussSeidelResult(info)
+
+
+class _TriInfo(C.Structure):
+    _fields_ = [("levels", C.c_uint64), ("singular_index", C.c_uint64), ("singular_reason", C.c_int32)]
+
+
+class TriSolveResult:
+    """`Ok(())` of a triangular solve.  `levels` is the length of the longest chain of unknowns that have to be solved one
+    after the other (device-side information)."""
+
+    def __init__(self, info):
+        self.levels = int(info.levels)
+
+    def __repr__(self):
+        return "Ok(())"
+
+
+_SINGULAR_REASONS = {1: "numeric", 2: "structural"}
+
+
+def _trisolve(mat, rhs, storage, uplo, stream):
+    if mat.storage() != storage:                    # assert!(mat.is_csr() / is_csc(), "Storage mismatch"): trisolve.rs:42, 98, 174, 232
+        raise _ffi.SprsHipError(_ffi.STORAGE_MISMATCH, "Storage mismatch")
+    info = _TriInfo()
+    status = lib.sprs_hip_trisolve_f64(mat._h, uplo, C.c_void_p(rhs.ptr), rhs.n, C.byref(info),
+                                       C.c_void_p(int(stream) if stream else 0))
+    if status == _ffi.SINGULAR_MATRIX:              # Err(LinalgError::SingularMatrix(SingularMatrixInfo { index, reason }))
+        err = _ffi.SprsHipError(status, lib.sprs_hip_last_error().decode("utf-8", "replace"))
+        err.index = int(info.singular_index)
+        err.reason = _SINGULAR_REASONS[int(info.singular_reason)]
+        raise err
+    check(status)
+    return TriSolveResult(info)
+
+
+def lsolve_csr_dense_rhs(mat, rhs, stream=None):
+    """lsolve_csr_dense_rhs(lower_tri_mat, rhs) (trisolve.rs:30-73): mat a square CSR DeviceCsMat (its upper triangle is
+    ignored), rhs a DeviceVec solved in place.  Raises SprsHipError: DIM_MISMATCH / STORAGE_MISMATCH like the reference's
+    asserts, SINGULAR_MATRIX (with `.index` and `.reason`, "numeric" or "structural") where it returns Err."""
+    return _trisolve(mat, rhs, _ffi.CSR, _ffi.LOWER, stream)
+
+
+def usolve_csr_dense_rhs(mat, rhs, stream=None):
+    """usolve_csr_dense_rhs(upper_tri_mat, rhs) (trisolve.rs:219-262): as lsolve_csr_dense_rhs, with the upper triangle."""
+    return _trisolve(mat, rhs, _ffi.CSR, _ffi.UPPER, stream)
+
+
+def lsolve_csc_dense_rhs(mat, rhs, stream=None):
+    """lsolve_csc_dense_rhs(lower_tri_mat, rhs) (trisolve.rs:85-149): mat a square CSC DeviceCsMat; a diagonal that is not
+    stored is reported as "structural", a stored zero as "numeric"."""
+    return _trisolve(mat, rhs, _ffi.CSC, _ffi.LOWER, stream)
+
+
+def usolve_csc_dense_rhs(mat, rhs, stream=None):
+    """usolve_csc_dense_rhs(upper_tri_mat, rhs) (trisolve.rs:161-210): every unknown receives its subtractions by DESCENDING
+    column, so the bits differ from usolve_csr_dense_rhs on the same matrix, as they do in the reference."""
+    return _trisolve(mat, rhs, _ffi.CSC, _ffi.UPPER, stream)
