@@ -450,6 +450,37 @@ int32_t sprs_hip_csmat_mul_csvec_f64(const sprs_hip_csmat *a, const sprs_hip_csv
  * Index width, stream and blocking as sprs_hip_csmat_mul_csvec_f64. */
 int32_t sprs_hip_csvec_mul_csmat_f64(const sprs_hip_csvec *v, const sprs_hip_csmat *b, sprs_hip_csvec **out, void *stream);
 
+/* ---- sparse +, -, elementwise * and scale (sprs/src/sparse/binop.rs) ----------------------------------------------------
+ * One merge of the two sorted index lists of every outer slice (nnz_or_zip): an index only in lhs gives op(l, +0.0), only in
+ * rhs op(+0.0, r), in both op(l, r) — the operation is performed, never a copy.  Every result entry is ONE IEEE operation:
+ * indptr, indices and value bits are the reference's (NaN results too wherever the reference's own bits are defined: x - NaN
+ * hands the NaN on with its sign, as subsd / fsub do; with NaNs on BOTH sides of + or * a host compiler may hand on either).
+ * All five return a NEW owning handle, run on `stream` and block until the result is complete there; the operands are const
+ * (no plan, no cached other-storage copy is touched). */
+#define SPRS_HIP_BINOP_ADD 0
+#define SPRS_HIP_BINOP_SUB 1
+#define SPRS_HIP_BINOP_MUL 2
+/* csmat_binop (binop.rs:178-271) with op = ADD | SUB | MUL (MUL: binop::mul_mat_same_storage, binop.rs:115-130).  An entry is
+ * kept iff !(val == 0.0): +0.0 and -0.0 are dropped — explicit zeros of an operand and exact cancellations vanish, an index on
+ * one side only vanishes under MUL — and NaN is kept (inf * 0.0).  Result: lhs' shape, storage and index types, proper indptr.
+ * SPRS_HIP_INVALID_ARG for another op; SPRS_HIP_DIM_MISMATCH "Dimension mismatch" unless the shapes are equal;
+ * SPRS_HIP_STORAGE_MISMATCH "Storage mismatch" unless the storages are, and when the declared index types differ (the
+ * reference's generics force one I and one Iptr); SPRS_HIP_INDEX_OVERFLOW when the result's nnz does not fit Iptr. */
+int32_t sprs_hip_csmat_binop_f64(const sprs_hip_csmat *lhs, const sprs_hip_csmat *rhs, int32_t op, sprs_hip_csmat **out,
+                                 void *stream);
+/* `&lhs + &rhs` and `&lhs - &rhs` (binop.rs:52-64, 99-111): csmat_binop after rhs.to_other_storage() when the storages
+ * differ (done below this boundary; the copy lives for the call).  The result has lhs' storage. */
+int32_t sprs_hip_csmat_add_csmat_f64(const sprs_hip_csmat *lhs, const sprs_hip_csmat *rhs, sprs_hip_csmat **out, void *stream);
+int32_t sprs_hip_csmat_sub_csmat_f64(const sprs_hip_csmat *lhs, const sprs_hip_csmat *rhs, sprs_hip_csmat **out, void *stream);
+/* `&m * alpha` (binop.rs:132-163) = m.map(|x| x * alpha): the structure is copied unchanged and nothing is dropped — a stored
+ * 0.0 stays stored, x * 0.0 is stored as +-0.0. */
+int32_t sprs_hip_csmat_scale_f64(const sprs_hip_csmat *m, double alpha, sprs_hip_csmat **out, void *stream);
+/* csvec_binop (binop.rs:442-479): the same merge, but EVERY merged index is appended, zeros included (-0.0 + 0.0 = +0.0 is
+ * stored).  csvec_fix_zeros: an operand of dimension 0 takes the other's dimension; afterwards unequal dimensions are
+ * SPRS_HIP_DIM_MISMATCH "Dimension mismatch".  Unequal declared index widths: SPRS_HIP_STORAGE_MISMATCH. */
+int32_t sprs_hip_csvec_binop_f64(const sprs_hip_csvec *lhs, const sprs_hip_csvec *rhs, int32_t op, sprs_hip_csvec **out,
+                                 void *stream);
+
 /* ---- row-sharded SpMV over the GPUs of one node (one process per GPU, RCCL over xGMI) ----
  * The reference has no distributed code; the shard is its slice_outer (slicing.rs:65-89) with a rebased indptr
  * (indptr.rs:206-214): rank g owns rows [row_starts[g], row_starts[g+1]) and a full replica of x; one exchange, an

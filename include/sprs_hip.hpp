@@ -378,6 +378,47 @@ inline DeviceCsVec csr_mul_csvec(const DeviceCsMat &a, const DeviceCsVec &v) {
 }
 }  // namespace prod
 
+// Twin of sprs::binop (sprs/src/sparse/binop.rs): one IEEE operation per result entry, the reference's bits.
+namespace binop {
+// csmat_binop (binop.rs:178-223), op = SPRS_HIP_BINOP_ADD | _SUB | _MUL: equal shapes and storages, entries with val == 0 dropped
+inline DeviceCsMat csmat_binop(const DeviceCsMat &lhs, const DeviceCsMat &rhs, int32_t op, void *stream = nullptr) {
+    sprs_hip_csmat *c = nullptr;
+    check(sprs_hip_csmat_binop_f64(lhs.handle(), rhs.handle(), op, &c, stream));
+    return DeviceCsMat(c);
+}
+// mul_mat_same_storage (binop.rs:115-130): the elementwise product
+inline DeviceCsMat mul_mat_same_storage(const DeviceCsMat &lhs, const DeviceCsMat &rhs, void *stream = nullptr) {
+    return csmat_binop(lhs, rhs, SPRS_HIP_BINOP_MUL, stream);
+}
+// csvec_binop (binop.rs:442-467): every merged index is kept; a dimension of 0 takes the other operand's
+inline DeviceCsVec csvec_binop(const DeviceCsVec &lhs, const DeviceCsVec &rhs, int32_t op, void *stream = nullptr) {
+    sprs_hip_csvec *c = nullptr;
+    check(sprs_hip_csvec_binop_f64(lhs.handle(), rhs.handle(), op, &c, stream));
+    return DeviceCsVec(c);
+}
+}  // namespace binop
+
+// `&A + &B`, `&A - &B` (binop.rs:52-64, 99-111): rhs.to_other_storage() first when the storages differ, below the C ABI
+inline DeviceCsMat operator+(const DeviceCsMat &a, const DeviceCsMat &b) {
+    sprs_hip_csmat *c = nullptr;
+    check(sprs_hip_csmat_add_csmat_f64(a.handle(), b.handle(), &c, nullptr));
+    return DeviceCsMat(c);
+}
+inline DeviceCsMat operator-(const DeviceCsMat &a, const DeviceCsMat &b) {
+    sprs_hip_csmat *c = nullptr;
+    check(sprs_hip_csmat_sub_csmat_f64(a.handle(), b.handle(), &c, nullptr));
+    return DeviceCsMat(c);
+}
+// `&A * s` (binop.rs:132-163): A.map(|x| x * s), the structure unchanged
+inline DeviceCsMat operator*(const DeviceCsMat &a, double s) {
+    sprs_hip_csmat *c = nullptr;
+    check(sprs_hip_csmat_scale_f64(a.handle(), s, &c, nullptr));
+    return DeviceCsMat(c);
+}
+// `&v + &w`, `&v - &w` (vec.rs:1133-1226)
+inline DeviceCsVec operator+(const DeviceCsVec &v, const DeviceCsVec &w) { return binop::csvec_binop(v, w, SPRS_HIP_BINOP_ADD); }
+inline DeviceCsVec operator-(const DeviceCsVec &v, const DeviceCsVec &w) { return binop::csvec_binop(v, w, SPRS_HIP_BINOP_SUB); }
+
 // TriMatI<f64, usize> (sparse/triplet.rs:26-48) with the device assembly of `to_csr` (triplet.rs:270-276 ->
 // triplet_iter.rs:127-224: rows sorted, duplicates summed).  No dedicated kernel: with n triplets the matrix
 // is the product R * E of R (rows x n, one 1 per column at the triplet's row) and E (n x cols, one value per

@@ -21,6 +21,9 @@ pub const SPRS_HIP_ROW_MAJOR: i32 = 0;
 pub const SPRS_HIP_COL_MAJOR: i32 = 1;
 pub const SPRS_HIP_ROUTE_RCCL: i32 = 0;
 pub const SPRS_HIP_ROUTE_PEER: i32 = 1;
+pub const SPRS_HIP_BINOP_ADD: i32 = 0;
+pub const SPRS_HIP_BINOP_SUB: i32 = 1;
+pub const SPRS_HIP_BINOP_MUL: i32 = 2;
 
 #[repr(C)]
 pub struct sprs_hip_spgemm_plan {
@@ -194,6 +197,19 @@ extern "C" {
     ) -> i32;
     pub fn sprs_hip_csvec_mul_csmat_f64(
         v: *const sprs_hip_csvec, b: *const sprs_hip_csmat, out: *mut *mut sprs_hip_csvec, stream: *mut c_void,
+    ) -> i32;
+    pub fn sprs_hip_csmat_binop_f64(
+        lhs: *const sprs_hip_csmat, rhs: *const sprs_hip_csmat, op: i32, out: *mut *mut sprs_hip_csmat, stream: *mut c_void,
+    ) -> i32;
+    pub fn sprs_hip_csmat_add_csmat_f64(
+        lhs: *const sprs_hip_csmat, rhs: *const sprs_hip_csmat, out: *mut *mut sprs_hip_csmat, stream: *mut c_void,
+    ) -> i32;
+    pub fn sprs_hip_csmat_sub_csmat_f64(
+        lhs: *const sprs_hip_csmat, rhs: *const sprs_hip_csmat, out: *mut *mut sprs_hip_csmat, stream: *mut c_void,
+    ) -> i32;
+    pub fn sprs_hip_csmat_scale_f64(m: *const sprs_hip_csmat, alpha: f64, out: *mut *mut sprs_hip_csmat, stream: *mut c_void) -> i32;
+    pub fn sprs_hip_csvec_binop_f64(
+        lhs: *const sprs_hip_csvec, rhs: *const sprs_hip_csvec, op: i32, out: *mut *mut sprs_hip_csvec, stream: *mut c_void,
     ) -> i32;
     pub fn sprs_hip_triplets_to_cs(
         rows: u64, cols: u64, n: u64, row_inds_dev: *const c_void, col_inds_dev: *const c_void, in_idx_bytes: i32,

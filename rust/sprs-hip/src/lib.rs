@@ -578,3 +578,82 @@ impl<'a, 'b> std::ops::Mul<&'b DeviceCsMat> for &'a DeviceCsVec {
         DeviceCsVec { h }
     }
 }
+
+/// Twin of `sprs::binop` (sprs/src/sparse/binop.rs) for device operands: one IEEE operation per result entry.
+pub mod binop {
+    use super::{check, sys, DeviceCsMat, DeviceCsVec};
+
+    /// The operation of `csmat_binop` / `csvec_binop` (the reference takes a closure; the device offers the three it uses).
+    #[derive(Clone, Copy, Debug, PartialEq, Eq)]
+    pub enum Op {
+        Add = sys::SPRS_HIP_BINOP_ADD as isize,
+        Sub = sys::SPRS_HIP_BINOP_SUB as isize,
+        Mul = sys::SPRS_HIP_BINOP_MUL as isize,
+    }
+
+    /// `binop::csmat_binop` (binop.rs:178-223): equal shapes ("Dimension mismatch") and storages ("Storage mismatch");
+    /// an entry is kept iff `!val.is_zero()`.
+    pub fn csmat_binop(lhs: &DeviceCsMat, rhs: &DeviceCsMat, op: Op) -> DeviceCsMat {
+        let mut h: *mut sys::sprs_hip_csmat = std::ptr::null_mut();
+        unsafe { check(sys::sprs_hip_csmat_binop_f64(lhs.h, rhs.h, op as i32, &mut h, std::ptr::null_mut())) };
+        DeviceCsMat { h }
+    }
+
+    /// `binop::mul_mat_same_storage` (binop.rs:115-130).
+    pub fn mul_mat_same_storage(lhs: &DeviceCsMat, rhs: &DeviceCsMat) -> DeviceCsMat {
+        csmat_binop(lhs, rhs, Op::Mul)
+    }
+
+    /// `binop::csvec_binop` (binop.rs:442-467): every merged index is kept; a dimension of 0 takes the other operand's.
+    pub fn csvec_binop(lhs: &DeviceCsVec, rhs: &DeviceCsVec, op: Op) -> DeviceCsVec {
+        let mut h: *mut sys::sprs_hip_csvec = std::ptr::null_mut();
+        unsafe { check(sys::sprs_hip_csvec_binop_f64(lhs.h, rhs.h, op as i32, &mut h, std::ptr::null_mut())) };
+        DeviceCsVec { h }
+    }
+}
+
+/// `&A + &B` (binop.rs:52-64): `rhs.to_other_storage()` first when the storages differ — done below the C ABI.
+impl<'a, 'b> std::ops::Add<&'b DeviceCsMat> for &'a DeviceCsMat {
+    type Output = DeviceCsMat;
+    fn add(self, rhs: &'b DeviceCsMat) -> DeviceCsMat {
+        let mut h: *mut sys::sprs_hip_csmat = std::ptr::null_mut();
+        unsafe { check(sys::sprs_hip_csmat_add_csmat_f64(self.h, rhs.h, &mut h, std::ptr::null_mut())) };
+        DeviceCsMat { h }
+    }
+}
+
+/// `&A - &B` (binop.rs:99-111).
+impl<'a, 'b> std::ops::Sub<&'b DeviceCsMat> for &'a DeviceCsMat {
+    type Output = DeviceCsMat;
+    fn sub(self, rhs: &'b DeviceCsMat) -> DeviceCsMat {
+        let mut h: *mut sys::sprs_hip_csmat = std::ptr::null_mut();
+        unsafe { check(sys::sprs_hip_csmat_sub_csmat_f64(self.h, rhs.h, &mut h, std::ptr::null_mut())) };
+        DeviceCsMat { h }
+    }
+}
+
+/// `&A * s` (binop.rs:132-163): `A.map(|x| x * s)`, the structure unchanged.
+impl<'a> std::ops::Mul<f64> for &'a DeviceCsMat {
+    type Output = DeviceCsMat;
+    fn mul(self, rhs: f64) -> DeviceCsMat {
+        let mut h: *mut sys::sprs_hip_csmat = std::ptr::null_mut();
+        unsafe { check(sys::sprs_hip_csmat_scale_f64(self.h, rhs, &mut h, std::ptr::null_mut())) };
+        DeviceCsMat { h }
+    }
+}
+
+/// `&v + &w` (vec.rs:1133-1205).
+impl<'a, 'b> std::ops::Add<&'b DeviceCsVec> for &'a DeviceCsVec {
+    type Output = DeviceCsVec;
+    fn add(self, rhs: &'b DeviceCsVec) -> DeviceCsVec {
+        binop::csvec_binop(self, rhs, binop::Op::Add)
+    }
+}
+
+/// `&v - &w` (vec.rs:1207-1226).
+impl<'a, 'b> std::ops::Sub<&'b DeviceCsVec> for &'a DeviceCsVec {
+    type Output = DeviceCsVec;
+    fn sub(self, rhs: &'b DeviceCsVec) -> DeviceCsVec {
+        binop::csvec_binop(self, rhs, binop::Op::Sub)
+    }
+}

@@ -8,7 +8,7 @@ the shared library is absent; nothing here computes on the CPU.
 from . import _ffi
 from ._ffi import CSC, CSR, SprsHipError
 from .device import DeviceCsMat, DeviceCsVec, DeviceVec
-from . import prod, smmp, linalg
+from . import prod, smmp, linalg, binop
 from .linalg import lsolve_csc_dense_rhs, lsolve_csr_dense_rhs, usolve_csc_dense_rhs, usolve_csr_dense_rhs
 
 

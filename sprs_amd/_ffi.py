@@ -19,6 +19,7 @@ CSR, CSC = 0, 1
 LOWER, UPPER = 0, 1
 ROW_MAJOR, COL_MAJOR = 0, 1
 ROUTE_RCCL, ROUTE_PEER = 0, 1
+BINOP_ADD, BINOP_SUB, BINOP_MUL = 0, 1, 2
 
 STATUS_NAMES = {
     OK: "OK", DIM_MISMATCH: "DIM_MISMATCH", STORAGE_MISMATCH: "STORAGE_MISMATCH",
@@ -98,6 +99,11 @@ SIGNATURES = {
     "sprs_hip_csvec_scatter_f64": (i32, [vp, vp, u64, vp]),
     "sprs_hip_csmat_mul_csvec_f64": (i32, [vp, vp, P(vp), vp]),
     "sprs_hip_csvec_mul_csmat_f64": (i32, [vp, vp, P(vp), vp]),
+    "sprs_hip_csmat_binop_f64": (i32, [vp, vp, i32, P(vp), vp]),
+    "sprs_hip_csmat_add_csmat_f64": (i32, [vp, vp, P(vp), vp]),
+    "sprs_hip_csmat_sub_csmat_f64": (i32, [vp, vp, P(vp), vp]),
+    "sprs_hip_csmat_scale_f64": (i32, [vp, C.c_double, P(vp), vp]),
+    "sprs_hip_csvec_binop_f64": (i32, [vp, vp, i32, P(vp), vp]),
     "sprs_hip_set_option": (i32, [C.c_char_p, i64]),
     "sprs_hip_get_option": (i32, [C.c_char_p, P(i64)]),
 }

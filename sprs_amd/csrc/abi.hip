@@ -1339,3 +1339,81 @@ int32_t sprs_hip_csvec_mul_csmat_f64(const sprs_hip_csvec *v, const sprs_hip_csm
 }
 
 }  // extern "C"
+
+// ---- sparse +, -, elementwise * and scale (binop.rs); kernels in binop.hpp -----------------------------------------------------
+
+static int32_t binop_op_ok(int32_t op) {
+    if (op != SPRS_HIP_BINOP_ADD && op != SPRS_HIP_BINOP_SUB && op != SPRS_HIP_BINOP_MUL)
+        SPRS_FAIL(SPRS_HIP_INVALID_ARG, "op must be SPRS_HIP_BINOP_ADD, SPRS_HIP_BINOP_SUB or SPRS_HIP_BINOP_MUL");
+    return SPRS_HIP_OK;
+}
+
+// csmat_binop's asserts (binop.rs:194-198) and the one I / Iptr of its signature
+static int32_t binop_contract(const sprs_hip_csmat *lhs, const sprs_hip_csmat *rhs, bool same_storage) {
+    if (lhs->rows != rhs->rows || lhs->cols != rhs->cols) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    if (same_storage && lhs->storage != rhs->storage) SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "Storage mismatch");
+    if (lhs->user_iptr_bytes() != rhs->user_iptr_bytes() || lhs->user_idx_bytes() != rhs->user_idx_bytes())
+        SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "operands must share index types (binop.rs:178-182)");
+    return SPRS_HIP_OK;
+}
+
+// `&lhs op &rhs` (binop.rs:52-64, 99-111): rhs.to_other_storage() first when the storages differ
+static int32_t csmat_operator(const sprs_hip_csmat *lhs, const sprs_hip_csmat *rhs, int32_t op, sprs_hip_csmat **out, void *stream) {
+    if (!lhs || !rhs || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    SPRS_TRY(binop_contract(lhs, rhs, false));
+    sprs_hip_csmat *conv = nullptr;
+    if (lhs->storage != rhs->storage) {
+        // the conversion runs on the null stream: what the caller's stream still has to write into rhs comes first
+        if (stream) SPRS_TRY_HIP(hipStreamSynchronize((hipStream_t)stream));
+        SPRS_TRY(convert_checked(rhs, &conv));
+    }
+    OwnedCsmat owned(conv);
+    SPRS_TRY(csmat_binop_f64(lhs, conv ? conv : rhs, op, out, (hipStream_t)stream));
+    return finish_result(out, lhs);
+}
+
+extern "C" {
+
+int32_t sprs_hip_csmat_binop_f64(const sprs_hip_csmat *lhs, const sprs_hip_csmat *rhs, int32_t op, sprs_hip_csmat **out, void *stream) {
+    clear_error();
+    SPRS_TRY(binop_op_ok(op));
+    if (!lhs || !rhs || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    SPRS_TRY(binop_contract(lhs, rhs, true));
+    SPRS_TRY(csmat_binop_f64(lhs, rhs, op, out, (hipStream_t)stream));
+    return finish_result(out, lhs);
+}
+
+int32_t sprs_hip_csmat_add_csmat_f64(const sprs_hip_csmat *lhs, const sprs_hip_csmat *rhs, sprs_hip_csmat **out, void *stream) {
+    clear_error();
+    return csmat_operator(lhs, rhs, SPRS_HIP_BINOP_ADD, out, stream);
+}
+
+int32_t sprs_hip_csmat_sub_csmat_f64(const sprs_hip_csmat *lhs, const sprs_hip_csmat *rhs, sprs_hip_csmat **out, void *stream) {
+    clear_error();
+    return csmat_operator(lhs, rhs, SPRS_HIP_BINOP_SUB, out, stream);
+}
+
+int32_t sprs_hip_csmat_scale_f64(const sprs_hip_csmat *m, double alpha, sprs_hip_csmat **out, void *stream) {
+    clear_error();
+    if (!m || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    SPRS_TRY(csmat_scale_f64(m, alpha, out, (hipStream_t)stream));
+    return finish_result(out, m);
+}
+
+int32_t sprs_hip_csvec_binop_f64(const sprs_hip_csvec *lhs, const sprs_hip_csvec *rhs, int32_t op, sprs_hip_csvec **out, void *stream) {
+    clear_error();
+    SPRS_TRY(binop_op_ok(op));
+    if (!lhs || !rhs || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    // csvec_fix_zeros (binop.rs:469-479): a dimension of 0 takes the other operand's
+    const uint64_t ldim = lhs->dim ? lhs->dim : rhs->dim, rdim = rhs->dim ? rhs->dim : lhs->dim;
+    if (ldim != rdim) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    if (lhs->user_idx_bytes() != rhs->user_idx_bytes())
+        SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "operands must share the index type (binop.rs:442-446)");
+    return csvec_binop_f64(lhs, rhs, op, ldim, out, (hipStream_t)stream);
+}
+
+}  // extern "C"

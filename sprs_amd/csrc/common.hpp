@@ -105,6 +105,7 @@ constexpr bool DEVTOOLS = false;
     X(gauss_seidel_debug, 0, 0, 255, 1) /* TIMING EXPERIMENTS ONLY (wrong results): band kernel without 1 any pipeline work, 2 operand loads, 4 entry loads, 8 index loads */ \
     X(gauss_seidel_xcd, 0, 0, 2, 0)     /* sweep kernel: 1 only the workgroups that find themselves on XCD 0 take part (hand-offs through ONE L2), 0 / 2 every XCD (measured: one XCD is not faster) */ \
     X(gauss_seidel_naps, 0, 0, 64, 0)   /* longest pause of a wave whose rows all wait, in s_sleep(1) units, growing with the wait (0 = default 1) */ \
+    X(binop_tile, 2048, 2048, 2048, 0)  /* slots (entries of both operands) per workgroup of the sparse +, -, elementwise * kernels (binop.hpp): fixed, published so that tests can place tile edges */ \
     X(pool, 1, 0, 1, 0)                 /* keep released result blocks (>= 1 MiB) for the next result instead of hipFree */        \
     X(pool_max_bytes, 128ll << 30, 0, INT64_MAX, 0) /* cap on the bytes the pool may hold */
 
@@ -367,6 +368,10 @@ int32_t triplets_to_cs(uint64_t rows, uint64_t cols, uint64_t n, const void *row
                        const double *data, int32_t storage, int32_t out_idx_bytes, int32_t out_iptr_bytes, sprs_hip_csmat **out);
 // convert.hip
 int32_t to_other_storage(const sprs_hip_csmat *m, sprs_hip_csmat **out);
+// binop.hpp (compiled in convert.hip): operands of equal shape, storage and index widths; complete on `stream` at return
+int32_t csmat_binop_f64(const sprs_hip_csmat *a, const sprs_hip_csmat *b, int32_t op, sprs_hip_csmat **out, hipStream_t stream);
+int32_t csvec_binop_f64(const sprs_hip_csvec *v, const sprs_hip_csvec *w, int32_t op, uint64_t dim, sprs_hip_csvec **out, hipStream_t stream);
+int32_t csmat_scale_f64(const sprs_hip_csmat *m, double alpha, sprs_hip_csmat **out, hipStream_t stream);
 // bicgstab.hip
 int32_t bicgstab_f64(sprs_hip_csmat *a, const double *x0, const double *b, uint64_t n, double tol, uint64_t max_iter,
                      double soft_restart_threshold, double *x, sprs_hip_bicgstab_info *info, hipStream_t stream);

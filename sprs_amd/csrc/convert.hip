@@ -297,3 +297,5 @@ int32_t slice_outer(const sprs_hip_csmat *m, uint64_t start, uint64_t end, sprs_
 }
 
 }  // namespace sprs_hip
+
+#include "binop.hpp"   // sparse +, -, elementwise * and scale

@@ -202,9 +202,34 @@ class DeviceCsMat:
             return prod.csmat_mul_csmat(self, rhs)        # csmat.rs:1866-1949
         if isinstance(rhs, prod.DeviceMat):
             return prod.csmat_mul_dense(self, rhs)        # csmat.rs:1989-2048
+        if isinstance(rhs, (float, np.floating)):
+            from . import binop
+            return binop.scale(self, rhs)                 # binop.rs:132-163
         return NotImplemented
 
-    __matmul__ = __mul__
+    def __matmul__(self, rhs):
+        if isinstance(rhs, (float, np.floating)):
+            return NotImplemented
+        return self.__mul__(rhs)
+
+    def __rmul__(self, lhs):
+        """`s * A` for a Python or numpy float: the same map as `&A * s` (x * s and s * x are one IEEE product)"""
+        if isinstance(lhs, (float, np.floating)):
+            from . import binop
+            return binop.scale(self, lhs)
+        return NotImplemented
+
+    def __add__(self, rhs):
+        if isinstance(rhs, DeviceCsMat):
+            from . import binop
+            return binop.add_mat(self, rhs)               # binop.rs:52-64
+        return NotImplemented
+
+    def __sub__(self, rhs):
+        if isinstance(rhs, DeviceCsMat):
+            from . import binop
+            return binop.sub_mat(self, rhs)               # binop.rs:99-111
+        return NotImplemented
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -286,6 +311,18 @@ class DeviceCsVec:
         return NotImplemented
 
     __matmul__ = __mul__
+
+    def __add__(self, rhs):
+        if isinstance(rhs, DeviceCsVec):
+            from . import binop
+            return binop.csvec_binop(self, rhs, _ffi.BINOP_ADD)   # vec.rs:1133-1179
+        return NotImplemented
+
+    def __sub__(self, rhs):
+        if isinstance(rhs, DeviceCsVec):
+            from . import binop
+            return binop.csvec_binop(self, rhs, _ffi.BINOP_SUB)   # vec.rs:1181-1226
+        return NotImplemented
 
     def __del__(self):
         h = getattr(self, "_h", None)
