@@ -481,6 +481,62 @@ int32_t sprs_hip_csmat_scale_f64(const sprs_hip_csmat *m, double alpha, sprs_hip
 int32_t sprs_hip_csvec_binop_f64(const sprs_hip_csvec *lhs, const sprs_hip_csvec *rhs, int32_t op, sprs_hip_csvec **out,
                                  void *stream);
 
+/* ---- permutations (sprs/src/sparse/permutation.rs) -------------------------------------------------------------------------
+ * sprs_hip_perm is the device twin of PermOwned: the Identity variant (a dimension, no arrays) or the arrays perm and perm_inv,
+ * perm_inv[perm[i]] = i, both owned by the handle.  The matrix functions are ONE algorithm (permutation.rs:296-591): result
+ * outer slice r' is outer slice o[r'] of the operand, every inner index j becomes g[j], each slice is sorted by the new index:
+ *                                   CSR: o, g                 CSC: o, g
+ *   permute_rows(A, p)              p.perm, identity          identity, p.perm_inv
+ *   permute_cols(A, q)              identity, q.perm_inv      q.perm, identity
+ *   transform_mat_paq(A, p, q)      p.perm, q.perm_inv        q.perm, p.perm_inv
+ *   transform_mat_papt(A, p)        p.perm, p.perm_inv        the same (permutation.rs:453-454)
+ * Values are moved, never computed: indptr, indices and value bits are the reference's, no tolerance anywhere. */
+typedef struct sprs_hip_perm sprs_hip_perm;
+
+/* PermOwned::new (permutation.rs:52-66) from a host array of dim indices of idx_bytes = 2, 4 or 8 each (2-byte indices are
+ * widened to 4 on the device and narrowed on download).  validate != 0 runs perm_is_valid (permutation.rs:39-49: every value
+ * in [0, dim), none twice) — on the host for small dim, on the device for large — and fails with SPRS_HIP_BAD_STRUCTURE
+ * "invalid permutation".  The inverse is built on the device. */
+int32_t sprs_hip_perm_upload(sprs_hip_perm **out, uint64_t dim, const void *perm, int32_t idx_bytes, int32_t validate);
+/* The same from a DEVICE array (idx_bytes 4 or 8; a torch argsort, ...), which is COPIED on `stream`: the handle owns both of
+ * its arrays.  Validation runs on the device (range test, scatter inv[p[i]] = i of the values in range, test inv[p[i]] == i: of
+ * two equal values one always loses); nothing is written out of range whatever the array holds. */
+int32_t sprs_hip_perm_from_device(sprs_hip_perm **out, uint64_t dim, const void *dev_perm, int32_t idx_bytes, int32_t validate,
+                                  void *stream);
+/* Permutation::identity (permutation.rs:113-118): the Identity variant, no arrays, no device needed; idx_bytes 2, 4 or 8 */
+int32_t sprs_hip_perm_identity(sprs_hip_perm **out, uint64_t dim, int32_t idx_bytes);
+/* dim, the declared index width, and whether the handle is the Identity VARIANT; any out pointer may be NULL */
+int32_t sprs_hip_perm_info(const sprs_hip_perm *p, uint64_t *dim, int32_t *idx_bytes, int32_t *identity_variant);
+/* PermOwned::is_identity (permutation.rs:144-152), the ELEMENTWISE test: 1 for the Identity variant and for stored arrays
+ * equal to 0..dim.  Runs on `stream` and blocks until the answer is there. */
+int32_t sprs_hip_perm_is_identity(const sprs_hip_perm *p, int32_t *flag, void *stream);
+/* raw device pointers, still owned by the handle; NULLs for the Identity variant */
+int32_t sprs_hip_perm_device_ptrs(const sprs_hip_perm *p, const void **perm, const void **perm_inv);
+/* vec() / inv_vec() (permutation.rs:211-226) to host buffers of dim entries of the declared width; either may be NULL; the
+ * Identity variant gives 0..dim */
+int32_t sprs_hip_perm_download(const sprs_hip_perm *p, void *perm, void *perm_inv);
+/* inv() (permutation.rs:120-137): a NEW owning handle with the two arrays swapped (Identity gives Identity) */
+int32_t sprs_hip_perm_inv(const sprs_hip_perm *p, sprs_hip_perm **out);
+int32_t sprs_hip_perm_free(sprs_hip_perm *p);
+/* `&P * x` (permutation.rs:255-278): y_dev[i] = x_dev[p[i]], Identity copies.  Asynchronous on `stream`.  n != dim is
+ * SPRS_HIP_DIM_MISMATCH "Dimension mismatch", overlapping x_dev / y_dev SPRS_HIP_INVALID_ARG. */
+int32_t sprs_hip_perm_mul_vec_f64(const sprs_hip_perm *p, const double *x_dev, double *y_dev, uint64_t n, void *stream);
+/* transform_mat_paq (permutation.rs:496-591); with one side NULL or the Identity variant it is permute_rows / permute_cols
+ * (permutation.rs:296-436), with both a plain copy — as it is when rows == 0 or cols == 0.  (Departure: the reference's
+ * permute_rows / permute_cols reach unreachable!() when handed the Identity variant directly; here they copy.)
+ * NEW owning handle with m's shape, storage and declared index widths; every step runs on `stream` and the call blocks until
+ * the result is complete there; m is const (no plan, no cached other-storage copy is touched).  Before any device work:
+ *   NULL m / out                                            SPRS_HIP_INVALID_ARG
+ *   row_perm.dim != rows or col_perm.dim != cols             SPRS_HIP_DIM_MISMATCH     "Dimension mismatch"
+ *   a permutation's declared index width != m's              SPRS_HIP_STORAGE_MISMATCH (the reference's generics force one I)
+ * m's slices must be sorted, as in every validated handle; an unvalidated handle with unsorted, duplicated or out-of-range
+ * indices gets an unspecified result but never an access outside the arrays. */
+int32_t sprs_hip_csmat_transform_paq(const sprs_hip_csmat *m, const sprs_hip_perm *row_perm, const sprs_hip_perm *col_perm,
+                                     sprs_hip_csmat **out, void *stream);
+/* transform_mat_papt (permutation.rs:439-491): P A P^T.  SPRS_HIP_DIM_MISMATCH unless m is square and rows == p.dim; a plain
+ * copy when p.is_identity() — the elementwise test, so a stored permutation equal to 0..dim counts.  Otherwise as above. */
+int32_t sprs_hip_csmat_transform_papt(const sprs_hip_csmat *m, const sprs_hip_perm *p, sprs_hip_csmat **out, void *stream);
+
 /* ---- row-sharded SpMV over the GPUs of one node (one process per GPU, RCCL over xGMI) ----
  * The reference has no distributed code; the shard is its slice_outer (slicing.rs:65-89) with a rebased indptr
  * (indptr.rs:206-214): rank g owns rows [row_starts[g], row_starts[g+1]) and a full replica of x; one exchange, an

@@ -419,6 +419,104 @@ inline DeviceCsMat operator*(const DeviceCsMat &a, double s) {
 inline DeviceCsVec operator+(const DeviceCsVec &v, const DeviceCsVec &w) { return binop::csvec_binop(v, w, SPRS_HIP_BINOP_ADD); }
 inline DeviceCsVec operator-(const DeviceCsVec &v, const DeviceCsVec &w) { return binop::csvec_binop(v, w, SPRS_HIP_BINOP_SUB); }
 
+// Device twin of PermOwnedI<I> (sparse/permutation.rs:12-28): the Identity variant or perm and perm_inv on the device.
+class DevicePerm {
+public:
+    // PermOwned::new (permutation.rs:52-66); validate = true throws "invalid permutation" where the reference's assert fires
+    template <typename I>
+    explicit DevicePerm(const std::vector<I> &perm, bool validate = true) {
+        static_assert(std::is_integral<I>::value, "SpIndex type");
+        static_assert(sizeof(I) == 2 || sizeof(I) == 4 || sizeof(I) == 8, "I must be 2, 4 or 8 bytes");
+        check(sprs_hip_perm_upload(&h_, perm.size(), perm.data(), (int32_t)sizeof(I), validate ? 1 : 0));
+    }
+    explicit DevicePerm(sprs_hip_perm *h) : h_(h) {}
+    // Permutation::identity (permutation.rs:113-118): no arrays
+    static DevicePerm identity(uint64_t dim, int32_t idx_bytes = 8) {
+        sprs_hip_perm *h = nullptr;
+        check(sprs_hip_perm_identity(&h, dim, idx_bytes));
+        return DevicePerm(h);
+    }
+    // a copy of dim indices (4 or 8 bytes each) that already live on the device
+    static DevicePerm from_device(uint64_t dim, const void *dev_perm, int32_t idx_bytes, bool validate = true, void *stream = nullptr) {
+        sprs_hip_perm *h = nullptr;
+        check(sprs_hip_perm_from_device(&h, dim, dev_perm, idx_bytes, validate ? 1 : 0, stream));
+        return DevicePerm(h);
+    }
+    DevicePerm(DevicePerm &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    DevicePerm(const DevicePerm &) = delete;
+    DevicePerm &operator=(const DevicePerm &) = delete;
+    ~DevicePerm() {
+        if (h_) sprs_hip_perm_free(h_);
+    }
+
+    uint64_t dim() const {                           // permutation.rs:139
+        uint64_t d = 0;
+        check(sprs_hip_perm_info(h_, &d, nullptr, nullptr));
+        return d;
+    }
+    bool is_identity(void *stream = nullptr) const {  // permutation.rs:144-152: the elementwise test
+        int32_t flag = 0;
+        check(sprs_hip_perm_is_identity(h_, &flag, stream));
+        return flag != 0;
+    }
+    DevicePerm inv() const {                         // permutation.rs:120-137, as a new owning handle
+        sprs_hip_perm *h = nullptr;
+        check(sprs_hip_perm_inv(h_, &h));
+        return DevicePerm(h);
+    }
+    // vec() / inv_vec() (permutation.rs:211-226) for 8-byte handles
+    std::vector<uint64_t> vec() const { return download(false); }
+    std::vector<uint64_t> inv_vec() const { return download(true); }
+    const sprs_hip_perm *handle() const { return h_; }
+
+private:
+    std::vector<uint64_t> download(bool inverse) const {
+        uint64_t d = 0;
+        int32_t ib = 0;
+        check(sprs_hip_perm_info(h_, &d, &ib, nullptr));
+        if (ib != 8) throw Error(SPRS_HIP_INVALID_ARG, "vec: 64-bit handles only");
+        std::vector<uint64_t> out(d);
+        check(sprs_hip_perm_download(h_, inverse ? nullptr : out.data(), inverse ? out.data() : nullptr));
+        return out;
+    }
+    sprs_hip_perm *h_ = nullptr;
+};
+
+// `&P * x` (permutation.rs:255-278): y[i] = x[p[i]]
+inline DeviceVec operator*(const DevicePerm &p, const DeviceVec &x) {
+    DeviceVec y(x.dim());
+    check(sprs_hip_perm_mul_vec_f64(p.handle(), x.ptr(), y.ptr(), x.dim(), nullptr));
+    return y;
+}
+
+// Twin of sprs::sparse::permutation (sprs/src/sparse/permutation.rs:296-581): values are moved, never computed.
+namespace permutation {
+// transform_mat_paq (permutation.rs:496-581): P * A * Q
+inline DeviceCsMat transform_mat_paq(const DeviceCsMat &mat, const DevicePerm &row_perm, const DevicePerm &col_perm, void *stream = nullptr) {
+    sprs_hip_csmat *c = nullptr;
+    check(sprs_hip_csmat_transform_paq(mat.handle(), row_perm.handle(), col_perm.handle(), &c, stream));
+    return DeviceCsMat(c);
+}
+// permute_rows (permutation.rs:407-420): P * A.  (The Identity variant gives a copy; the reference is unreachable!() there.)
+inline DeviceCsMat permute_rows(const DeviceCsMat &mat, const DevicePerm &perm, void *stream = nullptr) {
+    sprs_hip_csmat *c = nullptr;
+    check(sprs_hip_csmat_transform_paq(mat.handle(), perm.handle(), nullptr, &c, stream));
+    return DeviceCsMat(c);
+}
+// permute_cols (permutation.rs:423-436): A * P
+inline DeviceCsMat permute_cols(const DeviceCsMat &mat, const DevicePerm &perm, void *stream = nullptr) {
+    sprs_hip_csmat *c = nullptr;
+    check(sprs_hip_csmat_transform_paq(mat.handle(), nullptr, perm.handle(), &c, stream));
+    return DeviceCsMat(c);
+}
+// transform_mat_papt (permutation.rs:439-491): P * A * P^T, A square and of the permutation's dimension
+inline DeviceCsMat transform_mat_papt(const DeviceCsMat &mat, const DevicePerm &perm, void *stream = nullptr) {
+    sprs_hip_csmat *c = nullptr;
+    check(sprs_hip_csmat_transform_papt(mat.handle(), perm.handle(), &c, stream));
+    return DeviceCsMat(c);
+}
+}  // namespace permutation
+
 // TriMatI<f64, usize> (sparse/triplet.rs:26-48) with the device assembly of `to_csr` (triplet.rs:270-276 ->
 // triplet_iter.rs:127-224: rows sorted, duplicates summed).  No dedicated kernel: with n triplets the matrix
 // is the product R * E of R (rows x n, one 1 per column at the triplet's row) and E (n x cols, one value per

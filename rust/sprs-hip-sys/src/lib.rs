@@ -45,6 +45,11 @@ pub struct sprs_hip_csvec {
     _private: [u8; 0],
 }
 
+#[repr(C)]
+pub struct sprs_hip_perm {
+    _private: [u8; 0],
+}
+
 /// counters of BiCGSTAB::solve (include/sprs_hip.h)
 #[repr(C)]
 #[derive(Debug, Clone, Copy, Default)]
@@ -210,6 +215,25 @@ extern "C" {
     pub fn sprs_hip_csmat_scale_f64(m: *const sprs_hip_csmat, alpha: f64, out: *mut *mut sprs_hip_csmat, stream: *mut c_void) -> i32;
     pub fn sprs_hip_csvec_binop_f64(
         lhs: *const sprs_hip_csvec, rhs: *const sprs_hip_csvec, op: i32, out: *mut *mut sprs_hip_csvec, stream: *mut c_void,
+    ) -> i32;
+    pub fn sprs_hip_perm_upload(out: *mut *mut sprs_hip_perm, dim: u64, perm: *const c_void, idx_bytes: i32, validate: i32) -> i32;
+    pub fn sprs_hip_perm_from_device(
+        out: *mut *mut sprs_hip_perm, dim: u64, dev_perm: *const c_void, idx_bytes: i32, validate: i32, stream: *mut c_void,
+    ) -> i32;
+    pub fn sprs_hip_perm_identity(out: *mut *mut sprs_hip_perm, dim: u64, idx_bytes: i32) -> i32;
+    pub fn sprs_hip_perm_info(p: *const sprs_hip_perm, dim: *mut u64, idx_bytes: *mut i32, identity_variant: *mut i32) -> i32;
+    pub fn sprs_hip_perm_is_identity(p: *const sprs_hip_perm, flag: *mut i32, stream: *mut c_void) -> i32;
+    pub fn sprs_hip_perm_device_ptrs(p: *const sprs_hip_perm, perm: *mut *const c_void, perm_inv: *mut *const c_void) -> i32;
+    pub fn sprs_hip_perm_download(p: *const sprs_hip_perm, perm: *mut c_void, perm_inv: *mut c_void) -> i32;
+    pub fn sprs_hip_perm_inv(p: *const sprs_hip_perm, out: *mut *mut sprs_hip_perm) -> i32;
+    pub fn sprs_hip_perm_free(p: *mut sprs_hip_perm) -> i32;
+    pub fn sprs_hip_perm_mul_vec_f64(p: *const sprs_hip_perm, x_dev: *const f64, y_dev: *mut f64, n: u64, stream: *mut c_void) -> i32;
+    pub fn sprs_hip_csmat_transform_paq(
+        m: *const sprs_hip_csmat, row_perm: *const sprs_hip_perm, col_perm: *const sprs_hip_perm, out: *mut *mut sprs_hip_csmat,
+        stream: *mut c_void,
+    ) -> i32;
+    pub fn sprs_hip_csmat_transform_papt(
+        m: *const sprs_hip_csmat, p: *const sprs_hip_perm, out: *mut *mut sprs_hip_csmat, stream: *mut c_void,
     ) -> i32;
     pub fn sprs_hip_triplets_to_cs(
         rows: u64, cols: u64, n: u64, row_inds_dev: *const c_void, col_inds_dev: *const c_void, in_idx_bytes: i32,

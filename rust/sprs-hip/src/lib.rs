@@ -657,3 +657,130 @@ impl<'a, 'b> std::ops::Sub<&'b DeviceCsVec> for &'a DeviceCsVec {
         binop::csvec_binop(self, rhs, binop::Op::Sub)
     }
 }
+
+/// Device twin of `PermOwnedI<I>` (sprs/src/sparse/permutation.rs:12-28): the Identity variant, or `perm` and `perm_inv` in HBM.
+pub struct DevicePerm {
+    h: *mut sys::sprs_hip_perm,
+}
+
+unsafe impl Send for DevicePerm {}
+unsafe impl Sync for DevicePerm {}
+
+impl DevicePerm {
+    /// `PermOwned::new` (permutation.rs:52-66): panics with "invalid permutation" where the reference's assert fires.
+    pub fn new<I: SpIndex>(perm: &[I]) -> Self {
+        let mut h = std::ptr::null_mut();
+        unsafe { check(sys::sprs_hip_perm_upload(&mut h, perm.len() as u64, perm.as_ptr() as *const c_void, std::mem::size_of::<I>() as i32, 1)) };
+        Self { h }
+    }
+
+    /// From a host permutation whose invariants `PermOwned::new` already checked.
+    pub fn from_view<I: SpIndex>(perm: sprs::PermViewI<I>) -> Self {
+        let v = perm.vec();
+        let mut h = std::ptr::null_mut();
+        unsafe { check(sys::sprs_hip_perm_upload(&mut h, v.len() as u64, v.as_ptr() as *const c_void, std::mem::size_of::<I>() as i32, 0)) };
+        Self { h }
+    }
+
+    /// `Permutation::identity` (permutation.rs:113-118): no arrays.
+    pub fn identity<I: SpIndex>(dim: usize) -> Self {
+        let mut h = std::ptr::null_mut();
+        unsafe { check(sys::sprs_hip_perm_identity(&mut h, dim as u64, std::mem::size_of::<I>() as i32)) };
+        Self { h }
+    }
+
+    pub fn dim(&self) -> usize {
+        let mut d = 0u64;
+        unsafe { check(sys::sprs_hip_perm_info(self.h, &mut d, std::ptr::null_mut(), std::ptr::null_mut())) };
+        d as usize
+    }
+
+    /// permutation.rs:144-152: the elementwise test.
+    pub fn is_identity(&self) -> bool {
+        let mut flag = 0i32;
+        unsafe { check(sys::sprs_hip_perm_is_identity(self.h, &mut flag, std::ptr::null_mut())) };
+        flag != 0
+    }
+
+    /// permutation.rs:120-137, as a new owning handle.
+    pub fn inv(&self) -> DevicePerm {
+        let mut h = std::ptr::null_mut();
+        unsafe { check(sys::sprs_hip_perm_inv(self.h, &mut h)) };
+        DevicePerm { h }
+    }
+
+    fn download<I: SpIndex>(&self, inverse: bool) -> Vec<I> {
+        let (mut d, mut ib) = (0u64, 0i32);
+        unsafe { check(sys::sprs_hip_perm_info(self.h, &mut d, &mut ib, std::ptr::null_mut())) };
+        assert_eq!(ib as usize, std::mem::size_of::<I>(), "index width of the device permutation");
+        let mut out = vec![I::zero(); d as usize];
+        let p = out.as_mut_ptr() as *mut c_void;
+        let null = std::ptr::null_mut();
+        unsafe { check(sys::sprs_hip_perm_download(self.h, if inverse { null } else { p }, if inverse { p } else { null })) };
+        out
+    }
+
+    /// permutation.rs:211-217
+    pub fn vec<I: SpIndex>(&self) -> Vec<I> {
+        self.download(false)
+    }
+
+    /// permutation.rs:219-226
+    pub fn inv_vec<I: SpIndex>(&self) -> Vec<I> {
+        self.download(true)
+    }
+}
+
+impl Drop for DevicePerm {
+    fn drop(&mut self) {
+        unsafe { sys::sprs_hip_perm_free(self.h) };
+    }
+}
+
+/// `&P * &x` (permutation.rs:255-278): `y[i] = x[p[i]]`.
+impl<'a, 'b> std::ops::Mul<&'b DeviceVec> for &'a DevicePerm {
+    type Output = DeviceVec;
+    fn mul(self, rhs: &'b DeviceVec) -> DeviceVec {
+        let y = DeviceVec::zeros(rhs.len);
+        unsafe {
+            check(sys::sprs_hip_perm_mul_vec_f64(self.h, rhs.ptr as *const f64, y.ptr, rhs.len as u64, std::ptr::null_mut()));
+            check(sys::sprs_hip_synchronize(std::ptr::null_mut()));
+        }
+        y
+    }
+}
+
+/// Twin of `sprs::sparse::permutation` (sprs/src/sparse/permutation.rs:296-581) for device operands: one algorithm — result
+/// outer slice r' is outer slice o[r'], inner index j becomes g[j], slices sorted — so results are the reference's bit for bit.
+pub mod permutation {
+    use super::{check, sys, DeviceCsMat, DevicePerm};
+
+    /// `transform_mat_paq` (permutation.rs:496-581): P * A * Q.
+    pub fn transform_mat_paq(mat: &DeviceCsMat, row_perm: &DevicePerm, col_perm: &DevicePerm) -> DeviceCsMat {
+        let mut h: *mut sys::sprs_hip_csmat = std::ptr::null_mut();
+        unsafe { check(sys::sprs_hip_csmat_transform_paq(mat.h, row_perm.h, col_perm.h, &mut h, std::ptr::null_mut())) };
+        DeviceCsMat { h }
+    }
+
+    /// `permute_rows` (permutation.rs:407-420): P * A.  (The Identity variant gives a copy; the reference is unreachable!() there.)
+    pub fn permute_rows(mat: &DeviceCsMat, perm: &DevicePerm) -> DeviceCsMat {
+        let mut h: *mut sys::sprs_hip_csmat = std::ptr::null_mut();
+        unsafe { check(sys::sprs_hip_csmat_transform_paq(mat.h, perm.h, std::ptr::null(), &mut h, std::ptr::null_mut())) };
+        DeviceCsMat { h }
+    }
+
+    /// `permute_cols` (permutation.rs:423-436): A * P.
+    pub fn permute_cols(mat: &DeviceCsMat, perm: &DevicePerm) -> DeviceCsMat {
+        let mut h: *mut sys::sprs_hip_csmat = std::ptr::null_mut();
+        unsafe { check(sys::sprs_hip_csmat_transform_paq(mat.h, std::ptr::null(), perm.h, &mut h, std::ptr::null_mut())) };
+        DeviceCsMat { h }
+    }
+
+    /// `transform_mat_papt` (permutation.rs:439-491): P * A * P^T; panics with "Dimension mismatch" unless A is square and of
+    /// the permutation's dimension.
+    pub fn transform_mat_papt(mat: &DeviceCsMat, perm: &DevicePerm) -> DeviceCsMat {
+        let mut h: *mut sys::sprs_hip_csmat = std::ptr::null_mut();
+        unsafe { check(sys::sprs_hip_csmat_transform_papt(mat.h, perm.h, &mut h, std::ptr::null_mut())) };
+        DeviceCsMat { h }
+    }
+}

@@ -104,6 +104,18 @@ SIGNATURES = {
     "sprs_hip_csmat_sub_csmat_f64": (i32, [vp, vp, P(vp), vp]),
     "sprs_hip_csmat_scale_f64": (i32, [vp, C.c_double, P(vp), vp]),
     "sprs_hip_csvec_binop_f64": (i32, [vp, vp, i32, P(vp), vp]),
+    "sprs_hip_perm_upload": (i32, [P(vp), u64, vp, i32, i32]),
+    "sprs_hip_perm_from_device": (i32, [P(vp), u64, vp, i32, i32, vp]),
+    "sprs_hip_perm_identity": (i32, [P(vp), u64, i32]),
+    "sprs_hip_perm_info": (i32, [vp, P(u64), P(i32), P(i32)]),
+    "sprs_hip_perm_is_identity": (i32, [vp, P(i32), vp]),
+    "sprs_hip_perm_device_ptrs": (i32, [vp, P(vp), P(vp)]),
+    "sprs_hip_perm_download": (i32, [vp, vp, vp]),
+    "sprs_hip_perm_inv": (i32, [vp, P(vp)]),
+    "sprs_hip_perm_free": (i32, [vp]),
+    "sprs_hip_perm_mul_vec_f64": (i32, [vp, vp, vp, u64, vp]),
+    "sprs_hip_csmat_transform_paq": (i32, [vp, vp, vp, P(vp), vp]),
+    "sprs_hip_csmat_transform_papt": (i32, [vp, vp, P(vp), vp]),
     "sprs_hip_set_option": (i32, [C.c_char_p, i64]),
     "sprs_hip_get_option": (i32, [C.c_char_p, P(i64)]),
 }

@@ -1417,3 +1417,231 @@ int32_t sprs_hip_csvec_binop_f64(const sprs_hip_csvec *lhs, const sprs_hip_csvec
 }
 
 }  // extern "C"
+
+// ---- permutations (permutation.rs); kernels in perm.hpp ----------------------------------------------------------------------
+
+// perm_is_valid (permutation.rs:39-49) on a host array
+template <typename I>
+static bool perm_is_valid_host(uint64_t dim, const I *perm) {
+    std::vector<bool> seen(dim, false);
+    for (uint64_t i = 0; i < dim; ++i) {
+        const uint64_t v = (uint64_t)perm[i];
+        if (v >= dim || seen[v]) return false;
+        seen[v] = true;
+    }
+    return true;
+}
+
+// permutations up to this many entries are validated on the host; longer ones on the device after the upload
+static constexpr uint64_t PERM_HOST_CHECK_MAX = 1ull << 16;
+
+// a handle whose perm array is already on the device: the inverse (and the validation); releases the handle on failure
+static int32_t perm_finish(sprs_hip_perm *p, bool validate, hipStream_t stream, sprs_hip_perm **out) {
+    const int32_t st = perm_build_inverse(p, validate, stream);
+    if (st != SPRS_HIP_OK) {
+        const std::string keep = tl_msg;
+        const int32_t code = tl_hip_code;
+        perm_release(p);
+        tl_msg = keep;
+        tl_hip_code = code;
+        return st;
+    }
+    *out = p;
+    return SPRS_HIP_OK;
+}
+
+static sprs_hip_perm *identity_perm(uint64_t dim, int32_t idx_bytes) {
+    auto *p = new sprs_hip_perm();
+    p->dim = dim;
+    p->idx_bytes = idx_bytes == 2 ? 4 : idx_bytes;
+    p->decl_idx_bytes = idx_bytes == 2 ? 2 : 0;
+    p->identity = true;
+    return p;
+}
+
+// the array a side of the algorithm reads: null for "no permutation" and for the Identity variant
+static const void *perm_array(const sprs_hip_perm *p, bool inverse) {
+    if (!p || p->identity) return nullptr;
+    return inverse ? p->perm_inv : p->perm;
+}
+
+// the reference's generics force one I on the matrix and its permutations
+static int32_t perm_width_ok(const sprs_hip_csmat *m, const sprs_hip_perm *p) {
+    if (p && p->user_idx_bytes() != m->user_idx_bytes())
+        SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "the permutation must have the matrix's index type (permutation.rs:296-304)");
+    return SPRS_HIP_OK;
+}
+
+extern "C" {
+
+int32_t sprs_hip_perm_upload(sprs_hip_perm **out, uint64_t dim, const void *perm, int32_t idx_bytes, int32_t validate) {
+    clear_error();
+    if (!out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    if (idx_bytes != 2 && idx_bytes != 4 && idx_bytes != 8) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "index widths must be 2, 4 or 8 bytes");
+    if (dim && !perm) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL perm with dim > 0");
+    if (validate && dim <= PERM_HOST_CHECK_MAX) {
+        const bool ok = idx_bytes == 2   ? perm_is_valid_host(dim, (const uint16_t *)perm)
+                        : idx_bytes == 4 ? perm_is_valid_host(dim, (const uint32_t *)perm)
+                                         : perm_is_valid_host(dim, (const uint64_t *)perm);
+        if (!ok) SPRS_FAIL(SPRS_HIP_BAD_STRUCTURE, "invalid permutation");
+    }
+    const std::vector<uint32_t> wide = idx_bytes == 2 ? widen16(perm, dim) : std::vector<uint32_t>();
+    const void *src = idx_bytes == 2 ? wide.data() : perm;
+    const int32_t dev_bytes = idx_bytes == 2 ? 4 : idx_bytes;
+    sprs_hip_perm *p = nullptr;
+    SPRS_TRY(perm_alloc(&p, dim, dev_bytes, idx_bytes));
+    if (dim) {
+        const hipError_t e = copy_to_device(p->perm, src, dim * (uint64_t)dev_bytes, nullptr);
+        if (e != hipSuccess) {
+            perm_release(p);
+            return fail_hip(e, "perm_upload");
+        }
+    }
+    return perm_finish(p, validate && dim > PERM_HOST_CHECK_MAX, nullptr, out);
+}
+
+int32_t sprs_hip_perm_from_device(sprs_hip_perm **out, uint64_t dim, const void *dev_perm, int32_t idx_bytes, int32_t validate,
+                                  void *stream) {
+    clear_error();
+    if (!out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    if (idx_bytes != 4 && idx_bytes != 8) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "index widths must be 4 or 8 bytes");
+    if (dim && !dev_perm) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL perm with dim > 0");
+    if ((uintptr_t)dev_perm % (uintptr_t)idx_bytes) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "device buffers must be aligned to their element size");
+    sprs_hip_perm *p = nullptr;
+    SPRS_TRY(perm_alloc(&p, dim, idx_bytes, idx_bytes));
+    if (dim) {
+        const hipError_t e = hipMemcpyAsync(p->perm, dev_perm, dim * (uint64_t)idx_bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+        if (e != hipSuccess) {
+            perm_release(p);
+            return fail_hip(e, "perm_from_device");
+        }
+    }
+    return perm_finish(p, validate != 0, (hipStream_t)stream, out);
+}
+
+int32_t sprs_hip_perm_identity(sprs_hip_perm **out, uint64_t dim, int32_t idx_bytes) {
+    clear_error();
+    if (!out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    if (idx_bytes != 2 && idx_bytes != 4 && idx_bytes != 8) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "index widths must be 2, 4 or 8 bytes");
+    *out = identity_perm(dim, idx_bytes);
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_perm_info(const sprs_hip_perm *p, uint64_t *dim, int32_t *idx_bytes, int32_t *identity_variant) {
+    clear_error();
+    if (!p) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if (dim) *dim = p->dim;
+    if (idx_bytes) *idx_bytes = p->user_idx_bytes();
+    if (identity_variant) *identity_variant = p->identity ? 1 : 0;
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_perm_is_identity(const sprs_hip_perm *p, int32_t *flag, void *stream) {
+    clear_error();
+    if (!p || !flag) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    return perm_is_identity(p, flag, (hipStream_t)stream);
+}
+
+int32_t sprs_hip_perm_device_ptrs(const sprs_hip_perm *p, const void **perm, const void **perm_inv) {
+    clear_error();
+    if (!p) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if (perm) *perm = p->identity ? nullptr : p->perm;
+    if (perm_inv) *perm_inv = p->identity ? nullptr : p->perm_inv;
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_perm_download(const sprs_hip_perm *p, void *perm, void *perm_inv) {
+    clear_error();
+    if (!p) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    void *dst[2] = {perm, perm_inv};
+    const void *src[2] = {p->perm, p->perm_inv};
+    for (int k = 0; k < 2; ++k) {
+        if (!dst[k] || !p->dim) continue;
+        if (!p->identity) {
+            SPRS_TRY(download_indices(dst[k], src[k], p->dim, p->idx_bytes, p->user_idx_bytes()));
+            continue;
+        }
+        const int32_t w = p->user_idx_bytes();      // (0..dim).collect() (permutation.rs:211-226)
+        if (p->dim - 1 > width_max(w)) SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "Index type is not large enough to hold %llu", (unsigned long long)(p->dim - 1));
+        for (uint64_t i = 0; i < p->dim; ++i) {
+            if (w == 2) ((uint16_t *)dst[k])[i] = (uint16_t)i;
+            else if (w == 4) ((uint32_t *)dst[k])[i] = (uint32_t)i;
+            else ((uint64_t *)dst[k])[i] = i;
+        }
+    }
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_perm_inv(const sprs_hip_perm *p, sprs_hip_perm **out) {
+    clear_error();
+    if (!p || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    if (p->identity) {
+        *out = identity_perm(p->dim, p->user_idx_bytes());
+        return SPRS_HIP_OK;
+    }
+    sprs_hip_perm *q = nullptr;
+    SPRS_TRY(perm_alloc(&q, p->dim, p->idx_bytes, p->user_idx_bytes()));
+    if (p->dim) {
+        const uint64_t bytes = p->dim * (uint64_t)p->idx_bytes;
+        hipError_t e = hipMemcpyAsync(q->perm, p->perm_inv, bytes, hipMemcpyDeviceToDevice, nullptr);
+        if (e == hipSuccess) e = hipMemcpyAsync(q->perm_inv, p->perm, bytes, hipMemcpyDeviceToDevice, nullptr);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        if (e != hipSuccess) {
+            perm_release(q);
+            return fail_hip(e, "perm_inv");
+        }
+    }
+    *out = q;
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_perm_free(sprs_hip_perm *p) {
+    clear_error();
+    perm_release(p);
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_perm_mul_vec_f64(const sprs_hip_perm *p, const double *x_dev, double *y_dev, uint64_t n, void *stream) {
+    clear_error();
+    if (!p) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if (n != p->dim) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    if (n && (!x_dev || !y_dev)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL vector");
+    if (n && (uintptr_t)x_dev < (uintptr_t)(y_dev + n) && (uintptr_t)y_dev < (uintptr_t)(x_dev + n))
+        SPRS_FAIL(SPRS_HIP_INVALID_ARG, "x and y must not overlap");
+    return perm_mul_vec_f64(p, x_dev, y_dev, (hipStream_t)stream);
+}
+
+int32_t sprs_hip_csmat_transform_paq(const sprs_hip_csmat *m, const sprs_hip_perm *row_perm, const sprs_hip_perm *col_perm,
+                                     sprs_hip_csmat **out, void *stream) {
+    clear_error();
+    if (!m || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    if ((row_perm && row_perm->dim != m->rows) || (col_perm && col_perm->dim != m->cols))
+        SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");   // permutation.rs:506-507
+    SPRS_TRY(perm_width_ok(m, row_perm));
+    SPRS_TRY(perm_width_ok(m, col_perm));
+    const bool csr = m->storage == SPRS_HIP_CSR, empty = m->rows == 0 || m->cols == 0;
+    // CSR: (p, q_); CSC: (q, p_) (permutation.rs:544-547)
+    const void *o = empty ? nullptr : perm_array(csr ? row_perm : col_perm, false);
+    const void *g = empty ? nullptr : perm_array(csr ? col_perm : row_perm, true);
+    SPRS_TRY(csmat_permute(m, o, g, out, (hipStream_t)stream));
+    return finish_result(out, m);
+}
+
+int32_t sprs_hip_csmat_transform_papt(const sprs_hip_csmat *m, const sprs_hip_perm *p, sprs_hip_csmat **out, void *stream) {
+    clear_error();
+    if (!m || !p || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    if (m->rows != m->cols || m->rows != p->dim) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");   // permutation.rs:448-449
+    SPRS_TRY(perm_width_ok(m, p));
+    int32_t ident = 1;
+    if (m->rows) SPRS_TRY(perm_is_identity(p, &ident, (hipStream_t)stream));   // perm.is_identity() || mat.rows() == 0 (permutation.rs:450)
+    SPRS_TRY(csmat_permute(m, ident ? nullptr : p->perm, ident ? nullptr : p->perm_inv, out, (hipStream_t)stream));
+    return finish_result(out, m);
+}
+
+}  // extern "C"

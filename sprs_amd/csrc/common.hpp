@@ -106,6 +106,8 @@ constexpr bool DEVTOOLS = false;
     X(gauss_seidel_xcd, 0, 0, 2, 0)     /* sweep kernel: 1 only the workgroups that find themselves on XCD 0 take part (hand-offs through ONE L2), 0 / 2 every XCD (measured: one XCD is not faster) */ \
     X(gauss_seidel_naps, 0, 0, 64, 0)   /* longest pause of a wave whose rows all wait, in s_sleep(1) units, growing with the wait (0 = default 1) */ \
     X(binop_tile, 2048, 2048, 2048, 0)  /* slots (entries of both operands) per workgroup of the sparse +, -, elementwise * kernels (binop.hpp): fixed, published so that tests can place tile edges */ \
+    X(perm_tile, 2048, 2048, 2048, 0)   /* result entries per workgroup of the outer-permutation copy kernel (perm.hpp): fixed, published so that tests can place tile edges */ \
+    X(perm_cap, 4096, 4096, 4096, 0)    /* longest row a relabelling permutation sorts in LDS by one workgroup (perm.hpp); longer rows go through the radix sort: fixed, published for the tests */ \
     X(pool, 1, 0, 1, 0)                 /* keep released result blocks (>= 1 MiB) for the next result instead of hipFree */        \
     X(pool_max_bytes, 128ll << 30, 0, INT64_MAX, 0) /* cap on the bytes the pool may hold */
 
@@ -209,6 +211,19 @@ struct sprs_hip_csvec {
     double *data = nullptr;            // device, nnz entries
     bool owns = false;
     uint64_t cap_indices = 0, cap_data = 0;
+    int device = 0;
+};
+
+// Device twin of PermOwned (sprs/src/sparse/permutation.rs:12-28): the Identity variant (no arrays) or perm and perm_inv.
+struct sprs_hip_perm {
+    uint64_t dim = 0;
+    int32_t idx_bytes = 8;             // width of the device arrays (4 or 8)
+    int32_t decl_idx_bytes = 0;        // width the caller declared when it differs (2: widened to 4 on upload, narrowed on download)
+    int32_t user_idx_bytes() const { return decl_idx_bytes ? decl_idx_bytes : idx_bytes; }
+    bool identity = false;             // PermOwned::Identity: both arrays null
+    void *perm = nullptr;              // device, dim entries
+    void *perm_inv = nullptr;          // device, dim entries: perm_inv[perm[i]] = i
+    uint64_t cap_perm = 0, cap_inv = 0;
     int device = 0;
 };
 
@@ -372,6 +387,13 @@ int32_t to_other_storage(const sprs_hip_csmat *m, sprs_hip_csmat **out);
 int32_t csmat_binop_f64(const sprs_hip_csmat *a, const sprs_hip_csmat *b, int32_t op, sprs_hip_csmat **out, hipStream_t stream);
 int32_t csvec_binop_f64(const sprs_hip_csvec *v, const sprs_hip_csvec *w, int32_t op, uint64_t dim, sprs_hip_csvec **out, hipStream_t stream);
 int32_t csmat_scale_f64(const sprs_hip_csmat *m, double alpha, sprs_hip_csmat **out, hipStream_t stream);
+// perm.hpp (compiled in convert.hip): o / g = device arrays of m's index type (outer / inner entries) or null for the identity
+int32_t csmat_permute(const sprs_hip_csmat *m, const void *o, const void *g, sprs_hip_csmat **out, hipStream_t stream);
+int32_t perm_alloc(sprs_hip_perm **out, uint64_t dim, int32_t idx_bytes, int32_t decl_idx_bytes);
+void perm_release(sprs_hip_perm *p);
+int32_t perm_build_inverse(sprs_hip_perm *p, bool validate, hipStream_t stream);
+int32_t perm_is_identity(const sprs_hip_perm *p, int32_t *flag, hipStream_t stream);
+int32_t perm_mul_vec_f64(const sprs_hip_perm *p, const double *x, double *y, hipStream_t stream);
 // bicgstab.hip
 int32_t bicgstab_f64(sprs_hip_csmat *a, const double *x0, const double *b, uint64_t n, double tol, uint64_t max_iter,
                      double soft_restart_threshold, double *x, sprs_hip_bicgstab_info *info, hipStream_t stream);

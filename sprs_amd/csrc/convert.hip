@@ -299,3 +299,4 @@ int32_t slice_outer(const sprs_hip_csmat *m, uint64_t start, uint64_t end, sprs_
 }  // namespace sprs_hip
 
 #include "binop.hpp"   // sparse +, -, elementwise * and scale
+#include "perm.hpp"    // permutations: PermOwned, P * x, permute_rows / permute_cols, P A P^T, P A Q
