@@ -1,11 +1,13 @@
-// C ABI of libsprs_hip.so (include/sprs_hip.h): handle lifecycle, raw device
-// buffers, status / error plumbing.  Kernels live in spmv.hip and spgemm.hip.
+// C ABI of libsprs_hip.so (include/sprs_hip.h): the thread-local status / error state, argument checking and the reference's
+// contracts (which operands a call accepts, in which order it tests them, what a result inherits) around the internal
+// functions, raw device buffers, options.  Handles are made and released in handle.hpp, where the pool lives; results arrive
+// here inside their owners and are released to the caller's raw pointer in the extern "C" function.  Kernels live in the other
+// translation units.
 #include <cstdarg>
 #include <cstring>
 #include <vector>
 
 #include "common.hpp"
-#include <map>
 
 namespace sprs_hip {
 
@@ -50,162 +52,6 @@ Options &options() {
     return o;
 }
 
-// ---- pool of released result blocks ------------------------------------------------------------
-// A product like config 5's is 2 x 26.5 GB.  The driver hands such blocks out in ~30 ms the first
-// time, but takes SECONDS when the same amount has just been released (measured 2.0-3.4 s for the
-// second A*A of a process, against 0.23 s of kernels: profiles/r01z_spgemm_v3_sweep.txt) — a loop
-// that forms a product per iteration would spend 90 % of its time there.  Owned blocks of >= 1 MiB
-// therefore go back to a per-device pool and the next result takes the best fit (<= 25 % slack).
-// hipFree synchronises the device before a block can be reused; so does pool_free.
-namespace {
-struct Pool {
-    std::mutex mu;
-    std::multimap<std::pair<int, uint64_t>, void *> blocks;   // (device, bytes) -> block
-    uint64_t cached = 0;
-};
-Pool &pool() {
-    static Pool p;
-    return p;
-}
-constexpr uint64_t POOL_MIN = 1ull << 20;      // from here on: best fit with <= 25 % slack
-constexpr uint64_t POOL_SMALL = 256;            // below POOL_MIN: size classes, powers of two from this one
-}  // namespace
-
-uint64_t pool_trim() {
-    Pool &p = pool();
-    std::lock_guard<std::mutex> g(p.mu);
-    const uint64_t freed = p.cached;
-    for (auto &kv : p.blocks) (void)hipFree(kv.second);
-    p.blocks.clear();
-    p.cached = 0;
-    return freed;
-}
-
-uint64_t pool_cached_bytes() {
-    Pool &p = pool();
-    std::lock_guard<std::mutex> g(p.mu);
-    return p.cached;
-}
-
-hipError_t pool_alloc(void **out, uint64_t bytes, uint64_t *cap, int device) {
-    if (bytes == 0) bytes = 8;       // hipMalloc(0) returns nullptr; kernels never see NULL
-    // small blocks (task lists of a few entries, block sums of a scan, key arrays) are pooled in power-of-two classes from 256 B:
-    // a product made ~15 of them, each a hipMalloc and a hipFree (which waits for the device) of its own
-    if (bytes < POOL_MIN) {
-        uint64_t cls = POOL_SMALL;
-        while (cls < bytes) cls <<= 1;
-        bytes = cls;
-    }
-    if (options().pool) {
-        Pool &p = pool();
-        std::lock_guard<std::mutex> g(p.mu);
-        auto it = p.blocks.lower_bound({device, bytes});
-        if (it != p.blocks.end() && it->first.first == device && it->first.second <= bytes + bytes / 4) {
-            *out = it->second;
-            *cap = it->first.second;
-            p.cached -= it->first.second;
-            p.blocks.erase(it);
-            return hipSuccess;
-        }
-    }
-    hipError_t e = hipMalloc(out, bytes);
-    if (e == hipErrorOutOfMemory && pool_trim()) {
-        (void)hipGetLastError();
-        e = hipMalloc(out, bytes);
-    }
-    *cap = bytes;
-    return e;
-}
-
-void pool_free(void *ptr, uint64_t cap, int device, bool stream_ordered) {
-    if (!ptr) return;
-    int current = -1;
-    // a block of ANOTHER device than the calling thread's current one goes straight back to the driver:
-    // the synchronisation below would wait on the wrong device
-    if (options().pool && cap >= POOL_SMALL && hipGetDevice(&current) == hipSuccess && current == device) {
-        Pool &p = pool();
-        // the block may still be read by kernels in flight: same guarantee as hipFree — unless the caller vouches that all of
-        // them, and every later use of a pooled block, are ordered by the null stream (the SpGEMM plan's temporaries: a product
-        // dropped ~25 blocks, each behind its own device synchronisation)
-        if (stream_ordered || hipDeviceSynchronize() == hipSuccess) {
-            std::lock_guard<std::mutex> g(p.mu);
-            if (p.cached + cap <= (uint64_t)options().pool_max_bytes) {
-                p.blocks.insert({{device, cap}, ptr});
-                p.cached += cap;
-                return;
-            }
-        }
-    }
-    (void)hipFree(ptr);
-}
-
-void SpmvPlan::release() {
-    auto drop = [](void *p) {
-        if (p) (void)hipFree(p);
-    };
-    band_free(band);
-    band = nullptr;
-    drop(main.tile_row);
-    drop(main.pos);
-    if (main.owns) {
-        drop(main.indptr);
-        drop(main.indices);
-        drop(main.data);
-    }
-    main = CsrPiece();
-    for (auto &sl : slice) {
-        drop(sl.tile_row);
-        drop(sl.pos);
-        if (sl.owns) {
-            drop(sl.indptr);
-            drop(sl.indices);
-            drop(sl.data);
-        }
-        sl = CsrPiece();
-    }
-    drop(long_rows);
-    drop(slab);
-    drop(perm);
-    perm = nullptr;
-    long_rows = nullptr;
-    slab = nullptr;
-    for (auto &kv : scratch) {
-        drop(kv.second.carry_main);
-        drop(kv.second.carry_slices);
-        drop(kv.second.partial);
-        drop(kv.second.xp);
-    }
-    scratch.clear();
-    n_long = 0;
-    built = false;
-    xcs = false;
-}
-
-int32_t alloc_csmat(sprs_hip_csmat **out, int32_t storage, uint64_t rows, uint64_t cols, uint64_t nnz,
-                    int32_t iptr_bytes, int32_t idx_bytes) {
-    auto *m = new sprs_hip_csmat();
-    m->storage = storage;
-    m->rows = rows;
-    m->cols = cols;
-    m->nnz = nnz;
-    m->iptr_bytes = iptr_bytes;
-    m->idx_bytes = idx_bytes;
-    m->owns = true;
-    hipError_t e = hipGetDevice(&m->device);
-    if (e == hipSuccess) e = pool_alloc(&m->indptr, (m->outer() + 1) * (uint64_t)iptr_bytes, &m->cap_indptr, m->device);
-    if (e == hipSuccess) e = pool_alloc(&m->indices, nnz * (uint64_t)idx_bytes, &m->cap_indices, m->device);
-    if (e == hipSuccess) e = pool_alloc((void **)&m->data, nnz * sizeof(double), &m->cap_data, m->device);
-    if (e != hipSuccess) {
-        pool_free(m->indptr, m->cap_indptr, m->device);
-        pool_free(m->indices, m->cap_indices, m->device);
-        pool_free(m->data, m->cap_data, m->device);
-        delete m;
-        return fail_hip(e, "alloc_csmat");
-    }
-    *out = m;
-    return SPRS_HIP_OK;
-}
-
 // utils::check_compressed_structure (sprs/src/sparse.rs:300-358) on host arrays.
 template <typename I, typename P>
 static int32_t check_structure(uint64_t inner, uint64_t outer, const P *indptr, const I *indices) {
@@ -236,11 +82,26 @@ static bool host_widths_ok(int32_t iptr_bytes, int32_t idx_bytes) {     // what 
 
 static uint64_t width_max(int32_t bytes) { return bytes >= 8 ? ~0ull : ((1ull << (8 * bytes)) - 1ull); }
 
-// 2-byte host indices (u16 / i16, indexing.rs:124-130) widened to the 4 bytes the device holds
-static std::vector<uint32_t> widen16(const void *src, uint64_t count) {
-    std::vector<uint32_t> wide(count);
-    for (uint64_t i = 0; i < count; ++i) wide[i] = ((const uint16_t *)src)[i];
-    return wide;
+// A host index array as the device holds it: 2-byte indices (u16 / i16, indexing.rs:124-130) widened to 4 bytes, any other
+// width as it is.
+struct HostIndices {
+    std::vector<uint32_t> wide;
+    const void *p;
+    int32_t bytes;                 // width on the device
+    HostIndices(const HostIndices &) = delete;                    // p may point into wide
+    HostIndices &operator=(const HostIndices &) = delete;
+    HostIndices(const void *src, uint64_t count, int32_t decl_bytes) : p(src), bytes(decl_bytes == 2 ? 4 : decl_bytes) {
+        if (decl_bytes != 2 || !count) return;
+        wide.resize(count);
+        for (uint64_t i = 0; i < count; ++i) wide[i] = ((const uint16_t *)src)[i];
+        p = wide.data();
+    }
+    hipError_t upload(void *dst, uint64_t count) const { return count ? copy_to_device(dst, p, count * (uint64_t)bytes, nullptr) : hipSuccess; }
+};
+
+// element i of a host index array of the given width
+static uint64_t host_index_at(const void *a, int32_t bytes, uint64_t i) {
+    return dispatch_host_width(bytes, [&](auto t) { return (uint64_t)((const typename decltype(t)::type *)a)[i]; });
 }
 
 // count device indices to the host at the width the caller declared: a declared 2-byte array lives as 4 bytes on the device
@@ -275,16 +136,62 @@ int32_t inherit_declared_widths(sprs_hip_csmat *result, const sprs_hip_csmat *fr
 
 using namespace sprs_hip;
 
-// a freshly made result takes the declared index widths of the operand it derives from; on overflow it is released
-static int32_t finish_result(sprs_hip_csmat **res, const sprs_hip_csmat *from) {
-    const int32_t st = inherit_declared_widths(*res, from);
-    if (st != SPRS_HIP_OK) {
-        const std::string keep = sprs_hip_last_error();
-        sprs_hip_csmat_free(*res);
-        *res = nullptr;
-        set_error(st, "%s", keep.c_str());
+// the ABI boundary of a result: it takes the declared index widths of the operand it derives from and leaves its owner (on
+// overflow it goes with it)
+static int32_t finish_result(OwnedCsmat &res, const sprs_hip_csmat *from, sprs_hip_csmat **out) {
+    SPRS_TRY(inherit_declared_widths(res.get(), from));
+    *out = res.release();
+    return SPRS_HIP_OK;
+}
+
+// CsMat::new / new_csc on host arrays (the checks of sprs_hip_csmat_upload that follow its argument checks)
+static int32_t csmat_upload(OwnedCsmat &out, int32_t storage, uint64_t rows, uint64_t cols, const void *indptr, int32_t iptr_bytes,
+                            const void *indices, int32_t idx_bytes, const double *data, int32_t validate) {
+    if (storage != SPRS_HIP_CSR && storage != SPRS_HIP_CSC) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "bad storage tag %d", storage);
+    if (!host_widths_ok(iptr_bytes, idx_bytes)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "index widths must be 2, 4 or 8 bytes");
+    const uint64_t outer = storage == SPRS_HIP_CSR ? rows : cols;
+    const uint64_t inner = storage == SPRS_HIP_CSR ? cols : rows;
+    const uint64_t first = host_index_at(indptr, iptr_bytes, 0), last = host_index_at(indptr, iptr_bytes, outer);
+    if (last < first) SPRS_FAIL(SPRS_HIP_BAD_STRUCTURE, "Unsorted indptr");
+    const uint64_t nnz = last - first;
+    if (nnz && (!indices || !data)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL indices/data with nnz > 0");   // before the widening loop reads them
+    // 2-byte index types (u16 / i16 in sprs): widened to 4 bytes for the device, the declared widths remembered.  The inner
+    // dimension is tested against the declared index width here, whatever `validate` says; check_structure below sees the
+    // widened arrays, so inner == 65536 passes with u16 indices.
+    // (a 2-byte indptr cannot hold a count above its own range: nothing to check for Iptr on the way in)
+    const bool narrow = iptr_bytes == 2 || idx_bytes == 2;
+    if (narrow && inner && inner - 1 > width_max(idx_bytes)) SPRS_FAIL(SPRS_HIP_BAD_STRUCTURE, "Index type not large enough for this matrix");
+    // (indices points at the element addressed by indptr[0])
+    const HostIndices ip(indptr, outer + 1, iptr_bytes), ix(indices, nnz, idx_bytes);
+    if (validate) {
+        SPRS_TRY(dispatch_widths(ix.bytes, ip.bytes, [&](auto i, auto p) {
+            return check_structure(inner, outer, (const typename decltype(p)::type *)ip.p, (const typename decltype(i)::type *)ix.p);
+        }));
     }
-    return st;
+    OwnedCsmat m;
+    SPRS_TRY(make_csmat(m, storage, rows, cols, nnz, ip.bytes, ix.bytes));
+    hipError_t e = hipSuccess;
+    if (first == 0) {
+        e = ip.upload(m->indptr, outer + 1);
+    } else {
+        // to_proper (sprs/src/sparse/indptr.rs:206-214): rebase on the way in
+        std::vector<uint8_t> tmp((outer + 1) * (size_t)ip.bytes);
+        for (uint64_t i = 0; i <= outer; ++i) {
+            const uint64_t v = host_index_at(ip.p, ip.bytes, i) - first;
+            if (ip.bytes == 8) ((uint64_t *)tmp.data())[i] = v;
+            else ((uint32_t *)tmp.data())[i] = (uint32_t)v;
+        }
+        e = copy_to_device(m->indptr, tmp.data(), tmp.size(), nullptr);
+    }
+    if (e == hipSuccess) e = ix.upload(m->indices, nnz);
+    if (e == hipSuccess && nnz) e = copy_to_device(m->data, data, nnz * sizeof(double), nullptr);
+    if (e != hipSuccess) return fail_hip(e, "csmat_upload");
+    if (narrow) {
+        m->decl_iptr_bytes = iptr_bytes;
+        m->decl_idx_bytes = idx_bytes;
+    }
+    out = std::move(m);
+    return SPRS_HIP_OK;
 }
 
 extern "C" {
@@ -370,62 +277,9 @@ int32_t sprs_hip_csmat_upload(sprs_hip_csmat **out, int32_t storage, uint64_t ro
     clear_error();
     if (!out || !indptr) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
     *out = nullptr;
-    if (storage != SPRS_HIP_CSR && storage != SPRS_HIP_CSC) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "bad storage tag %d", storage);
-    if (!host_widths_ok(iptr_bytes, idx_bytes)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "index widths must be 2, 4 or 8 bytes");
-    const uint64_t outer = storage == SPRS_HIP_CSR ? rows : cols;
-    const uint64_t inner = storage == SPRS_HIP_CSR ? cols : rows;
-    if (iptr_bytes == 2 || idx_bytes == 2) {
-        // 2-byte index types (u16 / i16 in sprs): widened to 4 bytes for the device, the declared widths remembered
-        const uint64_t first16 = iptr_bytes == 2 ? ((const uint16_t *)indptr)[0] : iptr_bytes == 4 ? ((const uint32_t *)indptr)[0] : ((const uint64_t *)indptr)[0];
-        const uint64_t last16 = iptr_bytes == 2 ? ((const uint16_t *)indptr)[outer] : iptr_bytes == 4 ? ((const uint32_t *)indptr)[outer] : ((const uint64_t *)indptr)[outer];
-        if (last16 < first16) SPRS_FAIL(SPRS_HIP_BAD_STRUCTURE, "Unsorted indptr");
-        const uint64_t nnz16 = last16 - first16;
-        if (nnz16 && (!indices || !data)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL indices/data with nnz > 0");   // before the widening loop reads them
-        if (inner && inner - 1 > width_max(idx_bytes)) SPRS_FAIL(SPRS_HIP_BAD_STRUCTURE, "Index type not large enough for this matrix");
-        // (a 2-byte indptr cannot hold a count above its own range: nothing to check for Iptr on the way in)
-        // (indices points at the element addressed by indptr[0])
-        const std::vector<uint32_t> ip32 = iptr_bytes == 2 ? widen16(indptr, outer + 1) : std::vector<uint32_t>();
-        const std::vector<uint32_t> ix32 = idx_bytes == 2 ? widen16(indices, nnz16) : std::vector<uint32_t>();
-        const void *ipp = iptr_bytes == 2 ? ip32.data() : indptr, *ixp = idx_bytes == 2 && nnz16 ? ix32.data() : indices;
-        SPRS_TRY(sprs_hip_csmat_upload(out, storage, rows, cols, ipp, iptr_bytes == 2 ? 4 : iptr_bytes, ixp, idx_bytes == 2 ? 4 : idx_bytes,
-                                       data, validate));
-        (*out)->decl_iptr_bytes = iptr_bytes;
-        (*out)->decl_idx_bytes = idx_bytes;
-        return SPRS_HIP_OK;
-    }
-    auto ip_at = [&](uint64_t i) -> uint64_t {
-        return iptr_bytes == 8 ? ((const uint64_t *)indptr)[i] : ((const uint32_t *)indptr)[i];
-    };
-    const uint64_t first = ip_at(0), last = ip_at(outer);
-    if (last < first) SPRS_FAIL(SPRS_HIP_BAD_STRUCTURE, "Unsorted indptr");
-    const uint64_t nnz = last - first;
-    if (nnz && (!indices || !data)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL indices/data with nnz > 0");
-    if (validate) {
-        SPRS_TRY(dispatch_widths(idx_bytes, iptr_bytes, [&](auto i, auto p) {
-            return check_structure(inner, outer, (const typename decltype(p)::type *)indptr, (const typename decltype(i)::type *)indices);
-        }));
-    }
-    sprs_hip_csmat *m = nullptr;
-    SPRS_TRY(alloc_csmat(&m, storage, rows, cols, nnz, iptr_bytes, idx_bytes));
-    hipError_t e = hipSuccess;
-    if (first == 0) {
-        e = copy_to_device(m->indptr, indptr, (outer + 1) * (uint64_t)iptr_bytes, nullptr);
-    } else {
-        // to_proper (sprs/src/sparse/indptr.rs:206-214): rebase on the way in
-        std::vector<uint8_t> tmp((outer + 1) * (size_t)iptr_bytes);
-        for (uint64_t i = 0; i <= outer; ++i) {
-            if (iptr_bytes == 8) ((uint64_t *)tmp.data())[i] = ip_at(i) - first;
-            else ((uint32_t *)tmp.data())[i] = (uint32_t)(ip_at(i) - first);
-        }
-        e = copy_to_device(m->indptr, tmp.data(), tmp.size(), nullptr);
-    }
-    if (e == hipSuccess && nnz) e = copy_to_device(m->indices, indices, nnz * (uint64_t)idx_bytes, nullptr);
-    if (e == hipSuccess && nnz) e = copy_to_device(m->data, data, nnz * sizeof(double), nullptr);
-    if (e != hipSuccess) {
-        sprs_hip_csmat_free(m);
-        return fail_hip(e, "csmat_upload");
-    }
-    *out = m;
+    OwnedCsmat m;
+    SPRS_TRY(csmat_upload(m, storage, rows, cols, indptr, iptr_bytes, indices, idx_bytes, data, validate));
+    *out = m.release();
     return SPRS_HIP_OK;
 }
 
@@ -441,23 +295,10 @@ int32_t sprs_hip_csmat_wrap_device(sprs_hip_csmat **out, int32_t storage, uint64
     if (nnz && (!dev_indices || !dev_data)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL indices/data with nnz > 0");
     if (((uintptr_t)dev_indptr | (uintptr_t)dev_indices | (uintptr_t)dev_data) & 15)
         SPRS_FAIL(SPRS_HIP_INVALID_ARG, "device buffers must be 16-byte aligned");
-    auto *m = new sprs_hip_csmat();
-    m->storage = storage;
-    m->rows = rows;
-    m->cols = cols;
-    m->nnz = nnz;
-    m->iptr_bytes = iptr_bytes;
-    m->idx_bytes = idx_bytes;
-    m->indptr = const_cast<void *>(dev_indptr);
-    m->indices = const_cast<void *>(dev_indices);
-    m->data = const_cast<double *>(dev_data);
-    m->owns = false;
-    hipError_t e = hipGetDevice(&m->device);
-    if (e != hipSuccess) {
-        delete m;
-        return fail_hip(e, "hipGetDevice");
-    }
-    *out = m;
+    int device = 0;
+    const hipError_t e = hipGetDevice(&device);
+    if (e != hipSuccess) return fail_hip(e, "hipGetDevice");
+    *out = view_csmat(storage, rows, cols, nnz, dev_indptr, iptr_bytes, dev_indices, idx_bytes, dev_data, device);
     return SPRS_HIP_OK;
 }
 
@@ -520,22 +361,6 @@ int32_t sprs_hip_csmat_download_outer(const sprs_hip_csmat *m, uint64_t start, u
     return SPRS_HIP_OK;
 }
 
-// Everything a handle derives from its arrays: the SpMV / SpMM plans (they copy values), the Gauss-Seidel / triangular-solve row orders, the copy in the other
-// storage order and the transpose view kept for dense . sparse products.  Called whenever the values (or the arrays) change:
-// refresh, free and BOTH numeric SpGEMM entries, which rewrite C's values in place (a stale CSC copy of C
-// would otherwise serve later products).
-static void invalidate_caches(sprs_hip_csmat *m) {
-    m->plan.release();
-    m->mm.release();
-    m->gs.release();
-    m->tri_upper.release();
-    m->cv.release();
-    if (m->t_view) (void)sprs_hip_csmat_free(m->t_view);
-    m->t_view = nullptr;
-    if (m->as_other) (void)sprs_hip_csmat_free(m->as_other);
-    m->as_other = nullptr;
-}
-
 int32_t sprs_hip_csmat_refresh(sprs_hip_csmat *m) {
     clear_error();
     if (!m) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
@@ -574,36 +399,12 @@ int32_t sprs_hip_csmat_spmv_plan_info(const sprs_hip_csmat *m, int32_t *kind, ui
 int32_t sprs_hip_csmat_transpose_view(const sprs_hip_csmat *m, sprs_hip_csmat **out) {
     clear_error();
     if (!m || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
-    auto *t = new sprs_hip_csmat();
-    t->storage = m->storage == SPRS_HIP_CSR ? SPRS_HIP_CSC : SPRS_HIP_CSR;
-    t->rows = m->cols;
-    t->cols = m->rows;
-    t->nnz = m->nnz;
-    t->iptr_bytes = m->iptr_bytes;
-    t->idx_bytes = m->idx_bytes;
-    t->decl_iptr_bytes = m->decl_iptr_bytes;
-    t->decl_idx_bytes = m->decl_idx_bytes;
-    t->indptr = m->indptr;
-    t->indices = m->indices;
-    t->data = m->data;
-    t->owns = false;
-    t->device = m->device;
-    *out = t;
+    *out = view_csmat(m, true);
     return SPRS_HIP_OK;
 }
 
 int32_t sprs_hip_csmat_free(sprs_hip_csmat *m) {
     clear_error();
-    if (!m) return SPRS_HIP_OK;
-    // a kernel launched through a cached copy (as_other, t_view) or a plan copy may still be reading it: a handle that holds
-    // any of them waits for the device before they go (refresh does the same; a bare handle frees at once)
-    if (m->t_view || m->as_other || m->plan.built || m->cv.bits) (void)hipDeviceSynchronize();
-    invalidate_caches(m);
-    if (m->owns) {
-        pool_free(m->indptr, m->cap_indptr, m->device);
-        pool_free(m->indices, m->cap_indices, m->device);
-        pool_free(m->data, m->cap_data, m->device);
-    }
     delete m;
     return SPRS_HIP_OK;
 }
@@ -628,8 +429,9 @@ int32_t sprs_hip_spmv_f64_host(uint64_t rows, uint64_t cols, const void *indptr,
                                uint64_t y_len, int32_t accumulate) {
     clear_error();
     if (cols != x_len || rows != y_len) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
-    sprs_hip_csmat *m = nullptr;
-    SPRS_TRY(sprs_hip_csmat_upload(&m, SPRS_HIP_CSR, rows, cols, indptr, iptr_bytes, indices, idx_bytes, data, 0));
+    if (!indptr) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    OwnedCsmat m;
+    SPRS_TRY(csmat_upload(m, SPRS_HIP_CSR, rows, cols, indptr, iptr_bytes, indices, idx_bytes, data, 0));
     double *dx = nullptr, *dy = nullptr;
     int32_t st = sprs_hip_malloc((void **)&dx, x_len * 8);
     if (st == SPRS_HIP_OK) st = sprs_hip_malloc((void **)&dy, y_len * 8);
@@ -638,19 +440,12 @@ int32_t sprs_hip_spmv_f64_host(uint64_t rows, uint64_t cols, const void *indptr,
     // one multiply, then the handle goes: nothing would amortise a re-laid-out copy of the matrix (the banded plan takes
     // ~0.1 s to build on R-MAT 10M for a 1 ms SpMV), so this entry multiplies on the plain nnz-tiled plan
     m->one_shot = true;
-    if (st == SPRS_HIP_OK) st = sprs_hip_spmv_f64(m, dx, x_len, dy, y_len, accumulate, nullptr);
+    if (st == SPRS_HIP_OK) st = sprs_hip_spmv_f64(m.get(), dx, x_len, dy, y_len, accumulate, nullptr);
     if (st == SPRS_HIP_OK) st = sprs_hip_synchronize(nullptr);
     if (st == SPRS_HIP_OK) st = sprs_hip_memcpy_d2h(y, dy, y_len * 8);
-    std::string keep = tl_msg;
-    int32_t keep_code = tl_hip_code;
     (void)hipFree(dx);
     (void)hipFree(dy);
-    sprs_hip_csmat_free(m);
-    if (st != SPRS_HIP_OK) {
-        tl_msg = keep;
-        tl_hip_code = keep_code;
-    }
-    return st;
+    return st;         // (m goes with this scope: releasing a handle leaves the error state alone)
 }
 
 int32_t sprs_hip_spmm_rowmaj_f64(const sprs_hip_csmat *a, const double *rhs_dev, uint64_t rhs_rows, uint64_t k,
@@ -675,12 +470,15 @@ static int32_t spgemm_contract(const sprs_hip_csmat *a, const sprs_hip_csmat *b)
     return SPRS_HIP_OK;
 }
 
-static int32_t numeric_target_ok(const sprs_hip_csmat *a, const sprs_hip_csmat *b, const sprs_hip_csmat *c) {
-    // smmp.rs:161-166: the asserts of numeric() on the shape of c
+// C as the target of a numeric phase: the asserts of numeric() on its shape (smmp.rs:161-166); then, under C's lock (which
+// the caller holds until the kernels are launched), everything derived from its values goes
+static int32_t numeric_target(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat *c) {
     if (c->rows != a->rows || c->cols != b->cols) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
     if (c->storage != SPRS_HIP_CSR) SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "Storage mismatch");
     if (c->user_iptr_bytes() != a->user_iptr_bytes() || c->user_idx_bytes() != a->user_idx_bytes())
         SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "C must share the operands' index types");
+    SPRS_TRY_HIP(hipDeviceSynchronize());   // nothing in flight may still read the copies that go away
+    invalidate_caches(c);                   // values are about to change: plans copy them, and so does the copy in the other storage order
     return SPRS_HIP_OK;
 }
 
@@ -689,18 +487,17 @@ int32_t sprs_hip_spgemm_symbolic(const sprs_hip_csmat *a, const sprs_hip_csmat *
     if (!a || !b || !c) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
     *c = nullptr;
     SPRS_TRY(spgemm_contract(a, b));
-    SPRS_TRY(spgemm_symbolic(a, b, c));
-    return finish_result(c, a);
+    OwnedCsmat res;
+    SPRS_TRY(spgemm_symbolic(a, b, res));
+    return finish_result(res, a, c);
 }
 
 int32_t sprs_hip_spgemm_numeric(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat *c) {
     clear_error();
     if (!a || !b || !c) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
     SPRS_TRY(spgemm_contract(a, b));
-    SPRS_TRY(numeric_target_ok(a, b, c));
     std::lock_guard<std::recursive_mutex> lock(c->mu);
-    SPRS_TRY_HIP(hipDeviceSynchronize());   // nothing in flight may still read the copies that go away
-    invalidate_caches(c);                   // values are about to change: plans copy them, and so does the copy in the other storage order
+    SPRS_TRY(numeric_target(a, b, c));
     return spgemm_numeric(a, b, c);
 }
 
@@ -724,8 +521,9 @@ int32_t sprs_hip_spgemm_plan_structure(sprs_hip_spgemm_plan *plan, const sprs_hi
     clear_error();
     if (!plan || !a || !b || !c_structure) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
     *c_structure = nullptr;
-    SPRS_TRY(spgemm_plan_structure(plan, a, b, c_structure, false));
-    return finish_result(c_structure, a);
+    OwnedCsmat res;
+    SPRS_TRY(spgemm_plan_structure(plan, a, b, res, false));
+    return finish_result(res, a, c_structure);
 }
 
 int32_t sprs_hip_spgemm_plan_product(sprs_hip_spgemm_plan *plan, const sprs_hip_csmat *a, const sprs_hip_csmat *b,
@@ -733,18 +531,17 @@ int32_t sprs_hip_spgemm_plan_product(sprs_hip_spgemm_plan *plan, const sprs_hip_
     clear_error();
     if (!plan || !a || !b || !c) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
     *c = nullptr;
-    SPRS_TRY(spgemm_plan_structure(plan, a, b, c, true));
-    return finish_result(c, a);
+    OwnedCsmat res;
+    SPRS_TRY(spgemm_plan_structure(plan, a, b, res, true));
+    return finish_result(res, a, c);
 }
 
 int32_t sprs_hip_spgemm_plan_numeric(sprs_hip_spgemm_plan *plan, const sprs_hip_csmat *a, const sprs_hip_csmat *b,
                                      sprs_hip_csmat *c) {
     clear_error();
     if (!plan || !a || !b || !c) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
-    SPRS_TRY(numeric_target_ok(a, b, c));
     std::lock_guard<std::recursive_mutex> lock(c->mu);
-    SPRS_TRY_HIP(hipDeviceSynchronize());   // nothing in flight may still read the copies that go away
-    invalidate_caches(c);                   // values are about to change: plans copy them, and so does the copy in the other storage order
+    SPRS_TRY(numeric_target(a, b, c));
     return spgemm_plan_numeric(plan, a, b, c);
 }
 
@@ -784,28 +581,29 @@ int32_t sprs_hip_spgemm_f64(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sp
     clear_error();
     if (!a || !b || !c) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
     *c = nullptr;
-    if (a->cols != b->rows) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");   // smmp.rs:207
-    if (a->storage != SPRS_HIP_CSR || b->storage != SPRS_HIP_CSR) SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "Storage mismatch");
-    if (a->user_iptr_bytes() != b->user_iptr_bytes() || a->user_idx_bytes() != b->user_idx_bytes())
-        SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "operands must share index types (smmp.rs:196-199)");
-    SPRS_TRY(spgemm_f64(a, b, c));
-    return finish_result(c, a);
+    SPRS_TRY(spgemm_contract(a, b));
+    OwnedCsmat res;
+    SPRS_TRY(spgemm_f64(a, b, res));
+    return finish_result(res, a, c);
 }
 
 // to_other_storage with the index-type check of the reference on the DECLARED widths (csmat.rs:1794-1797)
-static int32_t convert_checked(const sprs_hip_csmat *m, sprs_hip_csmat **out) {
+static int32_t convert_checked(const sprs_hip_csmat *m, OwnedCsmat &out) {
     if (m->rows > width_max(m->user_idx_bytes()))
         SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "Index type is not large enough to hold the number of rows requested (required %llu)",
                   (unsigned long long)m->rows);
     SPRS_TRY(to_other_storage(m, out));
-    return finish_result(out, m);
+    return inherit_declared_widths(out.get(), m);
 }
 
 int32_t sprs_hip_csmat_to_other_storage(const sprs_hip_csmat *m, sprs_hip_csmat **out) {
     clear_error();
     if (!m || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
     *out = nullptr;
-    return convert_checked(m, out);
+    OwnedCsmat res;
+    SPRS_TRY(convert_checked(m, res));
+    *out = res.release();
+    return SPRS_HIP_OK;
 }
 
 // `&lhs * &rhs` for two sparse matrices: csmat_mul_csmat (csmat.rs:1895-1949) — the storage dispatch around
@@ -817,45 +615,22 @@ int32_t sprs_hip_csmat_mul_csmat(const sprs_hip_csmat *lhs, const sprs_hip_csmat
     if (lhs->cols != rhs->rows) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
     if (lhs->user_iptr_bytes() != rhs->user_iptr_bytes() || lhs->user_idx_bytes() != rhs->user_idx_bytes())
         SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "operands must share index types (smmp.rs:196-199)");
-    auto view_t = [](const sprs_hip_csmat *m, sprs_hip_csmat &t) {      // transpose_view (csmat.rs:982-991): free, flips the tag
-        t.storage = m->storage == SPRS_HIP_CSR ? SPRS_HIP_CSC : SPRS_HIP_CSR;
-        t.rows = m->cols;
-        t.cols = m->rows;
-        t.nnz = m->nnz;
-        t.iptr_bytes = m->iptr_bytes;
-        t.idx_bytes = m->idx_bytes;
-        t.decl_iptr_bytes = m->decl_iptr_bytes;
-        t.decl_idx_bytes = m->decl_idx_bytes;
-        t.indptr = m->indptr;
-        t.indices = m->indices;
-        t.data = m->data;
-        t.owns = false;
-        t.device = m->device;
-    };
     const bool l_csr = lhs->storage == SPRS_HIP_CSR, r_csr = rhs->storage == SPRS_HIP_CSR;
-    if (l_csr && r_csr) {                                         // (CSR, CSR)
-        SPRS_TRY(spgemm_f64(lhs, rhs, out));
-        return finish_result(out, lhs);
+    OwnedCsmat conv, c;                                           // rhs.to_other_storage() where the storages call for it; the product
+    if (l_csr) {                                                  // (CSR, CSR) and (CSR, CSC)
+        if (!r_csr) SPRS_TRY(convert_checked(rhs, conv));
+        SPRS_TRY(spgemm_f64(lhs, r_csr ? rhs : conv.get(), c));
+        return finish_result(c, lhs, out);
     }
-    sprs_hip_csmat *conv = nullptr;
-    if (l_csr) {                                                  // (CSR, CSC): rhs.to_other_storage()
-        SPRS_TRY(convert_checked(rhs, &conv));
-        OwnedCsmat owned(conv);
-        SPRS_TRY(spgemm_f64(lhs, conv, out));
-        return finish_result(out, lhs);
-    }
-    // lhs is CSC: (rhs^T * lhs^T)^T on the transpose views, which are CSR; transpose_into flips the result back
-    if (r_csr) SPRS_TRY(convert_checked(rhs, &conv));             // (CSC, CSR): rhs.to_other_storage() first
-    OwnedCsmat owned(conv);
-    const sprs_hip_csmat *r = r_csr ? conv : rhs;
-    sprs_hip_csmat rt, lt;
-    view_t(r, rt);
-    view_t(lhs, lt);
-    SPRS_TRY(spgemm_f64(&rt, &lt, out));
-    sprs_hip_csmat *c = *out;                                     // transpose_into: same buffers, other tag
-    c->storage = SPRS_HIP_CSC;
+    // lhs is CSC: (rhs^T * lhs^T)^T on the transpose views (csmat.rs:982-991), which are CSR; transpose_into flips the result back
+    if (r_csr) SPRS_TRY(convert_checked(rhs, conv));              // (CSC, CSR): rhs.to_other_storage() first
+    sprs_hip_csmat rt, lt;                                        // stack views: their destructors find no plan and no block to release
+    view_csmat(r_csr ? conv.get() : rhs, true, &rt);
+    view_csmat(lhs, true, &lt);
+    SPRS_TRY(spgemm_f64(&rt, &lt, c));
+    c->storage = SPRS_HIP_CSC;                                    // transpose_into: same buffers, other tag
     std::swap(c->rows, c->cols);
-    return finish_result(out, lhs);
+    return finish_result(c, lhs, out);
 }
 
 int32_t sprs_hip_csmat_slice_outer(const sprs_hip_csmat *m, uint64_t start, uint64_t end, sprs_hip_csmat **out) {
@@ -863,8 +638,9 @@ int32_t sprs_hip_csmat_slice_outer(const sprs_hip_csmat *m, uint64_t start, uint
     if (!m || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
     *out = nullptr;
     if (start > end || end > m->outer()) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "slice_outer range out of bounds");
-    SPRS_TRY(slice_outer(m, start, end, out));
-    return finish_result(out, m);
+    OwnedCsmat res;
+    SPRS_TRY(slice_outer(m, start, end, res));
+    return finish_result(res, m, out);
 }
 
 int32_t sprs_hip_dist_unique_id(void *id_128_bytes) {
@@ -898,7 +674,9 @@ static int32_t other_form(const sprs_hip_csmat *m, sprs_hip_csmat **out) {
     auto *mm = const_cast<sprs_hip_csmat *>(m);
     std::lock_guard<std::recursive_mutex> lock(mm->mu);
     if (!mm->as_other) {
-        SPRS_TRY(to_other_storage(m, &mm->as_other));
+        OwnedCsmat other;
+        SPRS_TRY(to_other_storage(m, other));
+        mm->as_other = other.release();
         // the plan policy (prepare flag, multiplies so far) is the OWNER's: a copy rebuilt after a refresh keeps it
         mm->as_other->prepared = mm->prepared;
         mm->as_other->spmv_calls = mm->spmv_calls;
@@ -1056,7 +834,7 @@ int32_t sprs_hip_dense_dot_csmat_f64(const double *lhs_dev, uint64_t lhs_rows, u
     // view in invalidate_caches (behind a device synchronise), and must not do so between the look-up and the launches.
     sprs_hip_csmat *owner = const_cast<sprs_hip_csmat *>(rhs);
     std::lock_guard<std::recursive_mutex> lock(owner->mu);
-    if (!owner->t_view) SPRS_TRY(sprs_hip_csmat_transpose_view(src, &owner->t_view));
+    if (!owner->t_view) owner->t_view = view_csmat(src, true);
     sprs_hip_csmat *rt = owner->t_view;
     int32_t lay_t = 0;
     // lhs^T: lhs_cols x lhs_rows, the other layout over the same memory
@@ -1116,7 +894,10 @@ int32_t sprs_hip_triplets_to_cs(uint64_t rows, uint64_t cols, uint64_t n, const 
     const uint64_t inner = storage == SPRS_HIP_CSR ? cols : rows, outer = storage == SPRS_HIP_CSR ? rows : cols;
     if (out_idx_bytes == 4 && inner > 0xFFFFFFFFull) SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "Index type not large enough for this matrix");
     if (out_iptr_bytes == 4 && outer + 1 > 0xFFFFFFFFull) SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "Iptr type not large enough for this matrix");
-    return triplets_to_cs(rows, cols, n, row_inds_dev, col_inds_dev, in_idx_bytes, data_dev, storage, out_idx_bytes, out_iptr_bytes, out);
+    OwnedCsmat res;
+    SPRS_TRY(triplets_to_cs(rows, cols, n, row_inds_dev, col_inds_dev, in_idx_bytes, data_dev, storage, out_idx_bytes, out_iptr_bytes, res));
+    *out = res.release();
+    return SPRS_HIP_OK;
 }
 
 namespace {
@@ -1203,35 +984,17 @@ int32_t sprs_hip_csvec_upload(sprs_hip_csvec **out, uint64_t dim, uint64_t nnz, 
         // I::from(n) (vec.rs:446-451): the dimension itself must be representable
         if (dim > width_max(idx_bytes)) SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "Index size is too small");
         if (nnz <= CSVEC_HOST_CHECK_MAX) {
-            int32_t st = SPRS_HIP_OK;
-            if (idx_bytes == 2) st = check_csvec_host(dim, nnz, (const uint16_t *)indices);
-            else if (idx_bytes == 4) st = check_csvec_host(dim, nnz, (const uint32_t *)indices);
-            else st = check_csvec_host(dim, nnz, (const uint64_t *)indices);
-            SPRS_TRY(st);
+            SPRS_TRY(dispatch_host_width(idx_bytes, [&](auto t) { return check_csvec_host(dim, nnz, (const typename decltype(t)::type *)indices); }));
         }
     }
-    const std::vector<uint32_t> wide = idx_bytes == 2 ? widen16(indices, nnz) : std::vector<uint32_t>();
-    const void *src = idx_bytes == 2 ? wide.data() : indices;
-    const int32_t dev_bytes = idx_bytes == 2 ? 4 : idx_bytes;
-    sprs_hip_csvec *v = nullptr;
-    SPRS_TRY(csvec_alloc(&v, dim, nnz, dev_bytes, idx_bytes));
-    hipError_t e = hipSuccess;
-    if (nnz) e = copy_to_device(v->indices, src, nnz * (uint64_t)dev_bytes, nullptr);
+    const HostIndices ix(indices, nnz, idx_bytes);
+    OwnedCsvec v;
+    SPRS_TRY(make_csvec(v, dim, nnz, ix.bytes, idx_bytes));
+    hipError_t e = ix.upload(v->indices, nnz);
     if (e == hipSuccess && nnz) e = copy_to_device(v->data, data, nnz * sizeof(double), nullptr);
-    if (e != hipSuccess) {
-        csvec_release(v);
-        return fail_hip(e, "csvec_upload");
-    }
-    if (validate && nnz > CSVEC_HOST_CHECK_MAX) {
-        const int32_t st = csvec_check_device(v, nullptr);
-        if (st != SPRS_HIP_OK) {
-            const std::string keep = tl_msg;
-            csvec_release(v);
-            set_error(st, "%s", keep.c_str());
-            return st;
-        }
-    }
-    *out = v;
+    if (e != hipSuccess) return fail_hip(e, "csvec_upload");
+    if (validate && nnz > CSVEC_HOST_CHECK_MAX) SPRS_TRY(csvec_check_device(v.get(), nullptr));
+    *out = v.release();
     return SPRS_HIP_OK;
 }
 
@@ -1244,19 +1007,10 @@ int32_t sprs_hip_csvec_wrap_device(sprs_hip_csvec **out, uint64_t dim, uint64_t 
     if (nnz && (!dev_indices || !dev_data)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL indices/data with nnz > 0");
     if (((uintptr_t)dev_indices % (uintptr_t)idx_bytes) | ((uintptr_t)dev_data & 7))
         SPRS_FAIL(SPRS_HIP_INVALID_ARG, "device buffers must be aligned to their element size");
-    auto *v = new sprs_hip_csvec();
-    v->dim = dim;
-    v->nnz = nnz;
-    v->idx_bytes = idx_bytes;
-    v->indices = const_cast<void *>(dev_indices);
-    v->data = const_cast<double *>(dev_data);
-    v->owns = false;
-    hipError_t e = hipGetDevice(&v->device);
-    if (e != hipSuccess) {
-        delete v;
-        return fail_hip(e, "hipGetDevice");
-    }
-    *out = v;
+    int device = 0;
+    const hipError_t e = hipGetDevice(&device);
+    if (e != hipSuccess) return fail_hip(e, "hipGetDevice");
+    *out = view_csvec(dim, nnz, dev_indices, idx_bytes, dev_data, device);
     return SPRS_HIP_OK;
 }
 
@@ -1287,7 +1041,7 @@ int32_t sprs_hip_csvec_download(const sprs_hip_csvec *v, void *indices, double *
 
 int32_t sprs_hip_csvec_free(sprs_hip_csvec *v) {
     clear_error();
-    csvec_release(v);
+    delete v;
     return SPRS_HIP_OK;
 }
 
@@ -1299,26 +1053,34 @@ int32_t sprs_hip_csvec_scatter_f64(const sprs_hip_csvec *v, double *out_dev, uin
     return csvec_scatter(v, out_dev, (hipStream_t)stream);
 }
 
+// a vector result leaves its owner at the ABI boundary
+static int32_t finish_csvec(int32_t status, OwnedCsvec &res, sprs_hip_csvec **out) {
+    if (status == SPRS_HIP_OK) *out = res.release();
+    return status;
+}
+
 // an empty result of dimension `dim` (no kernel)
 static int32_t empty_csvec(sprs_hip_csvec **out, uint64_t dim, const sprs_hip_csmat *like) {
-    return csvec_alloc(out, dim, 0, like->idx_bytes, like->user_idx_bytes());
+    OwnedCsvec res;
+    return finish_csvec(make_csvec(res, dim, 0, like->idx_bytes, like->user_idx_bytes()), res, out);
 }
 
 int32_t sprs_hip_csmat_mul_csvec_f64(const sprs_hip_csmat *a, const sprs_hip_csvec *v, sprs_hip_csvec **out, void *stream) {
     clear_error();
     if (!a || !v || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
     *out = nullptr;
+    OwnedCsvec res;
     if (a->storage == SPRS_HIP_CSR) {
         if (v->dim == 0) return empty_csvec(out, 0, a);               // CsVecI::empty(0) (prod.rs:171-174)
         if (a->cols != v->dim) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");   // prod.rs:175
-        return csvec_masked_dot(a, v, true, a->idx_bytes, a->user_idx_bytes(), out, (hipStream_t)stream);
+        return finish_csvec(csvec_masked_dot(a, v, true, a->idx_bytes, a->user_idx_bytes(), res, (hipStream_t)stream), res, out);
     }
     // CSC: a * v.col_view() (vec.rs:1127-1129) -> csmat_mul_csmat, structural, on the CSR form of a
     if (a->cols != v->dim) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
     if (a->rows == 0 || v->nnz == 0 || a->nnz == 0) return empty_csvec(out, a->rows, a);
     sprs_hip_csmat *csr = nullptr;
     SPRS_TRY(other_form(a, &csr));
-    return csvec_masked_dot(csr, v, false, a->idx_bytes, a->user_idx_bytes(), out, (hipStream_t)stream);
+    return finish_csvec(csvec_masked_dot(csr, v, false, a->idx_bytes, a->user_idx_bytes(), res, (hipStream_t)stream), res, out);
 }
 
 int32_t sprs_hip_csvec_mul_csmat_f64(const sprs_hip_csvec *v, const sprs_hip_csmat *b, sprs_hip_csvec **out, void *stream) {
@@ -1335,7 +1097,8 @@ int32_t sprs_hip_csvec_mul_csmat_f64(const sprs_hip_csvec *v, const sprs_hip_csm
         SPRS_TRY(other_form(b, &c));
         csc = c;
     }
-    return csvec_masked_dot(csc, v, false, b->idx_bytes, b->user_idx_bytes(), out, (hipStream_t)stream);
+    OwnedCsvec res;
+    return finish_csvec(csvec_masked_dot(csc, v, false, b->idx_bytes, b->user_idx_bytes(), res, (hipStream_t)stream), res, out);
 }
 
 }  // extern "C"
@@ -1362,15 +1125,14 @@ static int32_t csmat_operator(const sprs_hip_csmat *lhs, const sprs_hip_csmat *r
     if (!lhs || !rhs || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
     *out = nullptr;
     SPRS_TRY(binop_contract(lhs, rhs, false));
-    sprs_hip_csmat *conv = nullptr;
+    OwnedCsmat conv, res;
     if (lhs->storage != rhs->storage) {
         // the conversion runs on the null stream: what the caller's stream still has to write into rhs comes first
         if (stream) SPRS_TRY_HIP(hipStreamSynchronize((hipStream_t)stream));
-        SPRS_TRY(convert_checked(rhs, &conv));
+        SPRS_TRY(convert_checked(rhs, conv));
     }
-    OwnedCsmat owned(conv);
-    SPRS_TRY(csmat_binop_f64(lhs, conv ? conv : rhs, op, out, (hipStream_t)stream));
-    return finish_result(out, lhs);
+    SPRS_TRY(csmat_binop_f64(lhs, conv ? conv.get() : rhs, op, res, (hipStream_t)stream));
+    return finish_result(res, lhs, out);
 }
 
 extern "C" {
@@ -1381,8 +1143,9 @@ int32_t sprs_hip_csmat_binop_f64(const sprs_hip_csmat *lhs, const sprs_hip_csmat
     if (!lhs || !rhs || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
     *out = nullptr;
     SPRS_TRY(binop_contract(lhs, rhs, true));
-    SPRS_TRY(csmat_binop_f64(lhs, rhs, op, out, (hipStream_t)stream));
-    return finish_result(out, lhs);
+    OwnedCsmat res;
+    SPRS_TRY(csmat_binop_f64(lhs, rhs, op, res, (hipStream_t)stream));
+    return finish_result(res, lhs, out);
 }
 
 int32_t sprs_hip_csmat_add_csmat_f64(const sprs_hip_csmat *lhs, const sprs_hip_csmat *rhs, sprs_hip_csmat **out, void *stream) {
@@ -1399,8 +1162,9 @@ int32_t sprs_hip_csmat_scale_f64(const sprs_hip_csmat *m, double alpha, sprs_hip
     clear_error();
     if (!m || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
     *out = nullptr;
-    SPRS_TRY(csmat_scale_f64(m, alpha, out, (hipStream_t)stream));
-    return finish_result(out, m);
+    OwnedCsmat res;
+    SPRS_TRY(csmat_scale_f64(m, alpha, res, (hipStream_t)stream));
+    return finish_result(res, m, out);
 }
 
 int32_t sprs_hip_csvec_binop_f64(const sprs_hip_csvec *lhs, const sprs_hip_csvec *rhs, int32_t op, sprs_hip_csvec **out, void *stream) {
@@ -1413,7 +1177,8 @@ int32_t sprs_hip_csvec_binop_f64(const sprs_hip_csvec *lhs, const sprs_hip_csvec
     if (ldim != rdim) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
     if (lhs->user_idx_bytes() != rhs->user_idx_bytes())
         SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "operands must share the index type (binop.rs:442-446)");
-    return csvec_binop_f64(lhs, rhs, op, ldim, out, (hipStream_t)stream);
+    OwnedCsvec res;
+    return finish_csvec(csvec_binop_f64(lhs, rhs, op, ldim, res, (hipStream_t)stream), res, out);
 }
 
 }  // extern "C"
@@ -1435,28 +1200,11 @@ static bool perm_is_valid_host(uint64_t dim, const I *perm) {
 // permutations up to this many entries are validated on the host; longer ones on the device after the upload
 static constexpr uint64_t PERM_HOST_CHECK_MAX = 1ull << 16;
 
-// a handle whose perm array is already on the device: the inverse (and the validation); releases the handle on failure
-static int32_t perm_finish(sprs_hip_perm *p, bool validate, hipStream_t stream, sprs_hip_perm **out) {
-    const int32_t st = perm_build_inverse(p, validate, stream);
-    if (st != SPRS_HIP_OK) {
-        const std::string keep = tl_msg;
-        const int32_t code = tl_hip_code;
-        perm_release(p);
-        tl_msg = keep;
-        tl_hip_code = code;
-        return st;
-    }
-    *out = p;
+// a handle whose perm array is already on the device: the inverse (and the validation), then it leaves its owner
+static int32_t perm_finish(OwnedPerm &p, bool validate, hipStream_t stream, sprs_hip_perm **out) {
+    SPRS_TRY(perm_build_inverse(p.get(), validate, stream));
+    *out = p.release();
     return SPRS_HIP_OK;
-}
-
-static sprs_hip_perm *identity_perm(uint64_t dim, int32_t idx_bytes) {
-    auto *p = new sprs_hip_perm();
-    p->dim = dim;
-    p->idx_bytes = idx_bytes == 2 ? 4 : idx_bytes;
-    p->decl_idx_bytes = idx_bytes == 2 ? 2 : 0;
-    p->identity = true;
-    return p;
 }
 
 // the array a side of the algorithm reads: null for "no permutation" and for the Identity variant
@@ -1481,23 +1229,14 @@ int32_t sprs_hip_perm_upload(sprs_hip_perm **out, uint64_t dim, const void *perm
     if (idx_bytes != 2 && idx_bytes != 4 && idx_bytes != 8) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "index widths must be 2, 4 or 8 bytes");
     if (dim && !perm) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL perm with dim > 0");
     if (validate && dim <= PERM_HOST_CHECK_MAX) {
-        const bool ok = idx_bytes == 2   ? perm_is_valid_host(dim, (const uint16_t *)perm)
-                        : idx_bytes == 4 ? perm_is_valid_host(dim, (const uint32_t *)perm)
-                                         : perm_is_valid_host(dim, (const uint64_t *)perm);
+        const bool ok = dispatch_host_width(idx_bytes, [&](auto t) { return perm_is_valid_host(dim, (const typename decltype(t)::type *)perm); });
         if (!ok) SPRS_FAIL(SPRS_HIP_BAD_STRUCTURE, "invalid permutation");
     }
-    const std::vector<uint32_t> wide = idx_bytes == 2 ? widen16(perm, dim) : std::vector<uint32_t>();
-    const void *src = idx_bytes == 2 ? wide.data() : perm;
-    const int32_t dev_bytes = idx_bytes == 2 ? 4 : idx_bytes;
-    sprs_hip_perm *p = nullptr;
-    SPRS_TRY(perm_alloc(&p, dim, dev_bytes, idx_bytes));
-    if (dim) {
-        const hipError_t e = copy_to_device(p->perm, src, dim * (uint64_t)dev_bytes, nullptr);
-        if (e != hipSuccess) {
-            perm_release(p);
-            return fail_hip(e, "perm_upload");
-        }
-    }
+    const HostIndices host(perm, dim, idx_bytes);
+    OwnedPerm p;
+    SPRS_TRY(make_perm(p, dim, host.bytes, idx_bytes));
+    const hipError_t e = host.upload(p->perm, dim);
+    if (e != hipSuccess) return fail_hip(e, "perm_upload");
     return perm_finish(p, validate && dim > PERM_HOST_CHECK_MAX, nullptr, out);
 }
 
@@ -1509,14 +1248,11 @@ int32_t sprs_hip_perm_from_device(sprs_hip_perm **out, uint64_t dim, const void 
     if (idx_bytes != 4 && idx_bytes != 8) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "index widths must be 4 or 8 bytes");
     if (dim && !dev_perm) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL perm with dim > 0");
     if ((uintptr_t)dev_perm % (uintptr_t)idx_bytes) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "device buffers must be aligned to their element size");
-    sprs_hip_perm *p = nullptr;
-    SPRS_TRY(perm_alloc(&p, dim, idx_bytes, idx_bytes));
+    OwnedPerm p;
+    SPRS_TRY(make_perm(p, dim, idx_bytes, idx_bytes));
     if (dim) {
         const hipError_t e = hipMemcpyAsync(p->perm, dev_perm, dim * (uint64_t)idx_bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
-        if (e != hipSuccess) {
-            perm_release(p);
-            return fail_hip(e, "perm_from_device");
-        }
+        if (e != hipSuccess) return fail_hip(e, "perm_from_device");
     }
     return perm_finish(p, validate != 0, (hipStream_t)stream, out);
 }
@@ -1566,11 +1302,10 @@ int32_t sprs_hip_perm_download(const sprs_hip_perm *p, void *perm, void *perm_in
         }
         const int32_t w = p->user_idx_bytes();      // (0..dim).collect() (permutation.rs:211-226)
         if (p->dim - 1 > width_max(w)) SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "Index type is not large enough to hold %llu", (unsigned long long)(p->dim - 1));
-        for (uint64_t i = 0; i < p->dim; ++i) {
-            if (w == 2) ((uint16_t *)dst[k])[i] = (uint16_t)i;
-            else if (w == 4) ((uint32_t *)dst[k])[i] = (uint32_t)i;
-            else ((uint64_t *)dst[k])[i] = i;
-        }
+        dispatch_host_width(w, [&](auto t) {
+            using I = typename decltype(t)::type;
+            for (uint64_t i = 0; i < p->dim; ++i) ((I *)dst[k])[i] = (I)i;
+        });
     }
     return SPRS_HIP_OK;
 }
@@ -1583,25 +1318,22 @@ int32_t sprs_hip_perm_inv(const sprs_hip_perm *p, sprs_hip_perm **out) {
         *out = identity_perm(p->dim, p->user_idx_bytes());
         return SPRS_HIP_OK;
     }
-    sprs_hip_perm *q = nullptr;
-    SPRS_TRY(perm_alloc(&q, p->dim, p->idx_bytes, p->user_idx_bytes()));
+    OwnedPerm q;
+    SPRS_TRY(make_perm(q, p->dim, p->idx_bytes, p->user_idx_bytes()));
     if (p->dim) {
         const uint64_t bytes = p->dim * (uint64_t)p->idx_bytes;
         hipError_t e = hipMemcpyAsync(q->perm, p->perm_inv, bytes, hipMemcpyDeviceToDevice, nullptr);
         if (e == hipSuccess) e = hipMemcpyAsync(q->perm_inv, p->perm, bytes, hipMemcpyDeviceToDevice, nullptr);
         if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-        if (e != hipSuccess) {
-            perm_release(q);
-            return fail_hip(e, "perm_inv");
-        }
+        if (e != hipSuccess) return fail_hip(e, "perm_inv");
     }
-    *out = q;
+    *out = q.release();
     return SPRS_HIP_OK;
 }
 
 int32_t sprs_hip_perm_free(sprs_hip_perm *p) {
     clear_error();
-    perm_release(p);
+    delete p;
     return SPRS_HIP_OK;
 }
 
@@ -1628,8 +1360,9 @@ int32_t sprs_hip_csmat_transform_paq(const sprs_hip_csmat *m, const sprs_hip_per
     // CSR: (p, q_); CSC: (q, p_) (permutation.rs:544-547)
     const void *o = empty ? nullptr : perm_array(csr ? row_perm : col_perm, false);
     const void *g = empty ? nullptr : perm_array(csr ? col_perm : row_perm, true);
-    SPRS_TRY(csmat_permute(m, o, g, out, (hipStream_t)stream));
-    return finish_result(out, m);
+    OwnedCsmat res;
+    SPRS_TRY(csmat_permute(m, o, g, res, (hipStream_t)stream));
+    return finish_result(res, m, out);
 }
 
 int32_t sprs_hip_csmat_transform_papt(const sprs_hip_csmat *m, const sprs_hip_perm *p, sprs_hip_csmat **out, void *stream) {
@@ -1640,8 +1373,13 @@ int32_t sprs_hip_csmat_transform_papt(const sprs_hip_csmat *m, const sprs_hip_pe
     SPRS_TRY(perm_width_ok(m, p));
     int32_t ident = 1;
     if (m->rows) SPRS_TRY(perm_is_identity(p, &ident, (hipStream_t)stream));   // perm.is_identity() || mat.rows() == 0 (permutation.rs:450)
-    SPRS_TRY(csmat_permute(m, ident ? nullptr : p->perm, ident ? nullptr : p->perm_inv, out, (hipStream_t)stream));
-    return finish_result(out, m);
+    OwnedCsmat res;
+    SPRS_TRY(csmat_permute(m, ident ? nullptr : p->perm, ident ? nullptr : p->perm_inv, res, (hipStream_t)stream));
+    return finish_result(res, m, out);
 }
 
 }  // extern "C"
+
+// the pool and the handle constructors live in handle.hpp, compiled here so that the library and its emulator build (tests/emu,
+// a fixed list of translation units) both carry them
+#include "handle.hpp"

@@ -179,12 +179,12 @@ __global__ void resid_kernel(const double *__restrict__ b, const double *__restr
 int32_t bicgstab_f64(sprs_hip_csmat *a_in, const double *x0, const double *b, uint64_t n, double tol, uint64_t max_iter,
                      double soft_restart_threshold, double *x, sprs_hip_bicgstab_info *info, hipStream_t stream) {
     // `&a * &x` of a CSC matrix (csmat.rs:1866-1949 route) == CSR SpMV of its CSR form: convert once
-    sprs_hip_csmat *a = a_in, *converted = nullptr;
+    sprs_hip_csmat *a = a_in;
+    OwnedCsmat converted;
     if (a_in->storage != SPRS_HIP_CSR) {
-        SPRS_TRY(to_other_storage(a_in, &converted));
-        a = converted;
+        SPRS_TRY(to_other_storage(a_in, converted));
+        a = converted.get();
     }
-    OwnedCsmat owned(converted);
 
     const uint64_t nchunks = (n + DOT_CHUNK - 1) / DOT_CHUNK;
     DevBuf work;

@@ -350,7 +350,7 @@ int32_t run(const Operands &o, const Alloc &alloc, hipStream_t st) {
     if (ntiles > 0x7FFFFFFFull) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "binop: operands of more than 2^42 entries are not supported");
     // cut_a | cut_r | cut_first (ntiles + 1 each) | counts (ntiles) | offsets (ntiles + 1)
     DevBuf tmp;
-    SPRS_TRY_HIP(st == nullptr ? tmp.alloc_pooled((5 * ntiles + 4) * 8) : tmp.alloc((5 * ntiles + 4) * 8));
+    SPRS_TRY_HIP(tmp.alloc_for(st, (5 * ntiles + 4) * 8));
     uint64_t *cut_a = tmp.u64(), *cut_r = cut_a + ntiles + 1, *cut_first = cut_r + ntiles + 1;
     uint64_t *counts = cut_first + ntiles + 1, *offs = counts + ntiles;
     const Ptrs<P> pa{(const P *)o.ipa, o.nnza}, pb{(const P *)o.ipb, o.nnzb};
@@ -379,59 +379,42 @@ int32_t run(const Operands &o, const Alloc &alloc, hipStream_t st) {
 
 // csmat_binop (binop.rs:178-223) on two handles of equal shape, storage and index widths (checked by the caller): a new
 // handle in that storage, proper indptr, entries with !(val == 0.0).  Blocks until it is complete on `st`.
-int32_t csmat_binop_f64(const sprs_hip_csmat *a, const sprs_hip_csmat *b, int32_t op, sprs_hip_csmat **out, hipStream_t st) {
+int32_t csmat_binop_f64(const sprs_hip_csmat *a, const sprs_hip_csmat *b, int32_t op, OwnedCsmat &res, hipStream_t st) {
     bo::Operands o{a->indptr, b->indptr, a->indices, b->indices, a->data, b->data, a->outer(), a->nnz, b->nnz, op, true};
-    sprs_hip_csmat *res = nullptr;
     const bo::Alloc alloc = [&](uint64_t nnz, void **ip, void **ix, double **v) {
-        SPRS_TRY(alloc_csmat(&res, a->storage, a->rows, a->cols, nnz, a->iptr_bytes, a->idx_bytes));
+        SPRS_TRY(make_csmat(res, a->storage, a->rows, a->cols, nnz, a->iptr_bytes, a->idx_bytes));
         *ip = res->indptr;
         *ix = res->indices;
         *v = res->data;
         return (int32_t)SPRS_HIP_OK;
     };
-    const int32_t status = dispatch_widths(a->idx_bytes, a->iptr_bytes, [&](auto i, auto p) {
+    return dispatch_widths(a->idx_bytes, a->iptr_bytes, [&](auto i, auto p) {
         return bo::run<typename decltype(p)::type, typename decltype(i)::type>(o, alloc, st);
     });
-    if (status != SPRS_HIP_OK) {
-        if (res) sprs_hip_csmat_free(res);
-        return status;
-    }
-    *out = res;
-    return SPRS_HIP_OK;
 }
 
 // csvec_binop (binop.rs:442-467) on two vectors of equal index width: the same kernels with one outer slice and the drop
 // test off — every merged index is appended.  `dim`: the result's dimension (after csvec_fix_zeros).
-int32_t csvec_binop_f64(const sprs_hip_csvec *v, const sprs_hip_csvec *w, int32_t op, uint64_t dim, sprs_hip_csvec **out, hipStream_t st) {
+int32_t csvec_binop_f64(const sprs_hip_csvec *v, const sprs_hip_csvec *w, int32_t op, uint64_t dim, OwnedCsvec &res, hipStream_t st) {
     bo::Operands o{nullptr, nullptr, v->indices, w->indices, v->data, w->data, 1, v->nnz, w->nnz, op, false};
-    sprs_hip_csvec *res = nullptr;
     const bo::Alloc alloc = [&](uint64_t nnz, void **ip, void **ix, double **d) {
-        SPRS_TRY(csvec_alloc(&res, dim, nnz, v->idx_bytes, v->user_idx_bytes()));
+        SPRS_TRY(make_csvec(res, dim, nnz, v->idx_bytes, v->user_idx_bytes()));
         *ip = nullptr;
         *ix = res->indices;
         *d = res->data;
         return (int32_t)SPRS_HIP_OK;
     };
-    const int32_t status = dispatch_widths(v->idx_bytes, 8, [&](auto i, auto p) {
+    return dispatch_widths(v->idx_bytes, 8, [&](auto i, auto p) {
         return bo::run<typename decltype(p)::type, typename decltype(i)::type>(o, alloc, st);
     });
-    if (status != SPRS_HIP_OK) {
-        if (res) csvec_release(res);
-        return status;
-    }
-    *out = res;
-    return SPRS_HIP_OK;
 }
 
 // `&m * alpha` (binop.rs:145-147, CsMatBase::map): the structure copied as it is, every stored value times alpha — stored
 // zeros stay stored.  Blocks until the result is complete on `st`.
-int32_t csmat_scale_f64(const sprs_hip_csmat *m, double alpha, sprs_hip_csmat **out, hipStream_t st) {
-    sprs_hip_csmat *res = nullptr;
-    SPRS_TRY(alloc_csmat(&res, m->storage, m->rows, m->cols, m->nnz, m->iptr_bytes, m->idx_bytes));
-    OwnedCsmat owned(res);
-    SPRS_TRY_HIP(hipMemcpyAsync(res->indptr, m->indptr, (m->outer() + 1) * (uint64_t)m->iptr_bytes, hipMemcpyDeviceToDevice, st));
+int32_t csmat_scale_f64(const sprs_hip_csmat *m, double alpha, OwnedCsmat &out, hipStream_t st) {
+    OwnedCsmat res;
+    SPRS_TRY(copy_csmat(m, false, res, st));
     if (m->nnz) {
-        SPRS_TRY_HIP(hipMemcpyAsync(res->indices, m->indices, m->nnz * (uint64_t)m->idx_bytes, hipMemcpyDeviceToDevice, st));
         uint64_t blocks = (m->nnz / 2 + bo::BO_BLOCK) / bo::BO_BLOCK;
         if (blocks > 256 * 32) blocks = 256 * 32;
         hipLaunchKernelGGL(bo::scale_kernel, dim3((unsigned)blocks), dim3(bo::BO_BLOCK), 0, st, (const double *)m->data, m->nnz, alpha,
@@ -439,7 +422,7 @@ int32_t csmat_scale_f64(const sprs_hip_csmat *m, double alpha, sprs_hip_csmat **
         SPRS_TRY_HIP(hipGetLastError());
     }
     SPRS_TRY_HIP(hipStreamSynchronize(st));
-    *out = owned.release();
+    out = std::move(res);
     return SPRS_HIP_OK;
 }
 

@@ -199,6 +199,33 @@ struct CsvecScratch {
     void release();
 };
 
+// handle.hpp: result-block pool
+hipError_t pool_alloc(void **p, uint64_t bytes, uint64_t *cap, int device);
+// stream_ordered = true: the block was only ever touched by work enqueued on the NULL stream (or on streams joined back to it)
+// and every later user of the pool enqueues there too, so it goes back without waiting for the device
+void pool_free(void *p, uint64_t cap, int device, bool stream_ordered = false);
+uint64_t pool_trim();
+uint64_t pool_cached_bytes();
+
+// One block of the pool and its owner: the block goes back (pool_free, which waits for the device) with the owner.  The handles
+// below hold one per array they own; a borrowed handle or a view has its array pointers set and its owners empty.
+struct PoolBlock {
+    void *p = nullptr;
+    uint64_t cap = 0;              // bytes of the block (>= what was asked for: blocks come from the pool)
+    int dev = 0;
+    PoolBlock() = default;
+    PoolBlock(PoolBlock &&o) noexcept : p(o.p), cap(o.cap), dev(o.dev) { o.p = nullptr; }
+    PoolBlock &operator=(PoolBlock &&o) noexcept {
+        std::swap(p, o.p), std::swap(cap, o.cap), std::swap(dev, o.dev);
+        return *this;
+    }
+    ~PoolBlock() { pool_free(p, cap, dev); }
+    hipError_t alloc(uint64_t bytes, int device) {   // (on an empty owner)
+        dev = device;
+        return pool_alloc(&p, bytes, &cap, dev);
+    }
+};
+
 }  // namespace sprs_hip
 
 // Device twin of CsVecBase (sprs/src/sparse.rs:165-173): dim, sorted indices, data.
@@ -209,8 +236,7 @@ struct sprs_hip_csvec {
     int32_t user_idx_bytes() const { return decl_idx_bytes ? decl_idx_bytes : idx_bytes; }
     void *indices = nullptr;           // device, nnz entries, strictly increasing
     double *data = nullptr;            // device, nnz entries
-    bool owns = false;
-    uint64_t cap_indices = 0, cap_data = 0;
+    sprs_hip::PoolBlock own_data, own_indices;   // the blocks behind the arrays when the handle owns them (released indices first)
     int device = 0;
 };
 
@@ -223,7 +249,7 @@ struct sprs_hip_perm {
     bool identity = false;             // PermOwned::Identity: both arrays null
     void *perm = nullptr;              // device, dim entries
     void *perm_inv = nullptr;          // device, dim entries: perm_inv[perm[i]] = i
-    uint64_t cap_perm = 0, cap_inv = 0;
+    sprs_hip::PoolBlock own_inv, own_perm;   // the blocks behind the arrays: every stored permutation owns them (released perm first)
     int device = 0;
 };
 
@@ -241,11 +267,10 @@ struct sprs_hip_csmat {
     void *indptr = nullptr;    // device, outer+1 entries, zero based
     void *indices = nullptr;   // device, nnz entries
     double *data = nullptr;    // device, nnz entries
-    bool owns = false;
     uint64_t spmv_calls = 0;   // multiplies so far: the re-laid-out plan copies (banded / XCD-sliced) are built at the SECOND one (or by sprs_hip_csmat_prepare)
     bool prepared = false;     // sprs_hip_csmat_prepare was called: the copy plans may be built at once
     bool one_shot = false;     // the handle multiplies once (sprs_hip_spmv_f64_host): plain plan, no copies of the matrix
-    uint64_t cap_indptr = 0, cap_indices = 0, cap_data = 0;   // bytes of the owned blocks (>= what nnz needs: blocks come from the pool)
+    sprs_hip::PoolBlock own_data, own_indices, own_indptr;    // the blocks behind the arrays when the handle owns them (released indptr first)
     int device = 0;
     std::recursive_mutex mu;   // guards plan / mm: held from the look-up (or rebuild) of a plan until the kernels that read it are launched
     sprs_hip::SpmvPlan plan;
@@ -258,22 +283,16 @@ struct sprs_hip_csmat {
 
     uint64_t outer() const { return storage == SPRS_HIP_CSR ? rows : cols; }
     uint64_t inner() const { return storage == SPRS_HIP_CSR ? cols : rows; }
+    ~sprs_hip_csmat();         // handle.hpp: waits for the device when cached copies are held, drops them, then the blocks
 };
 
 namespace sprs_hip {
-
-// abi.hip: result-block pool
-hipError_t pool_alloc(void **p, uint64_t bytes, uint64_t *cap, int device);
-// stream_ordered = true: the block was only ever touched by work enqueued on the NULL stream (or on streams joined back to it)
-// and every later user of the pool enqueues there too, so it goes back without waiting for the device
-void pool_free(void *p, uint64_t cap, int device, bool stream_ordered = false);
-uint64_t pool_trim();
-uint64_t pool_cached_bytes();
 
 // A device temporary owned by one call, released when it goes out of scope.
 //   alloc:        a private block (hipMalloc), released with hipFree.
 //   alloc_pooled: a block of the pool, handed back in null-stream order (pool_free above); legal only for work ordered on the
 //                 null stream.
+//   alloc_for:    alloc_pooled for work on the null stream, alloc for any other.
 struct DevBuf {
     void *p = nullptr;
     uint64_t cap = 0;
@@ -300,6 +319,8 @@ struct DevBuf {
         if (e != hipSuccess) return e;
         return pool_alloc(&p, bytes ? bytes : 8, &cap, dev);
     }
+    // the temporary of work on `stream`: only null-stream work may take (and hand back) a block of the pool
+    hipError_t alloc_for(hipStream_t stream, uint64_t bytes) { return stream == nullptr ? alloc_pooled(bytes) : alloc(bytes); }
     template <typename T>
     T *as() const { return (T *)p; }
     uint64_t *u64() const { return (uint64_t *)p; }
@@ -337,11 +358,18 @@ auto dispatch_width(int32_t bytes, F &&f) {
     return bytes == 8 ? f(TypeTag<uint64_t>{}) : f(TypeTag<uint32_t>{});
 }
 
-// a temporary handle (a converted operand, a slice): freed with the scope that made it
-struct CsmatFree {
-    void operator()(sprs_hip_csmat *m) const { sprs_hip_csmat_free(m); }
-};
-using OwnedCsmat = std::unique_ptr<sprs_hip_csmat, CsmatFree>;
+// the same for a HOST index array, which may also be 2 bytes wide (u16 / i16, indexing.rs:124-130)
+template <typename F>
+auto dispatch_host_width(int32_t bytes, F &&f) {
+    return bytes == 2 ? f(TypeTag<uint16_t>{}) : dispatch_width(bytes, f);
+}
+
+// A handle and its owner: results travel as these below the ABI and are released to a raw pointer only in the extern "C"
+// function; a temporary (a converted operand, a slice) goes with the scope that made it.  `delete` is the whole release and
+// leaves the thread's error state alone.
+using OwnedCsmat = std::unique_ptr<sprs_hip_csmat>;
+using OwnedCsvec = std::unique_ptr<sprs_hip_csvec>;
+using OwnedPerm = std::unique_ptr<sprs_hip_perm>;
 
 // spmv_band.hip
 int32_t band_build(sprs_hip_csmat *a, hipStream_t stream, BandPlan **out);   // *out stays null when the plan does not apply
@@ -352,11 +380,11 @@ uint64_t band_plan_bytes(const BandPlan *bp);
 int32_t spmv_prepare(sprs_hip_csmat *a, hipStream_t stream);   // builds the full SpMV plan now (sprs_hip_csmat_prepare)
 int32_t spmv_f64(sprs_hip_csmat *a, const double *x, double *y, bool accumulate, hipStream_t stream);
 // spgemm.hip
-int32_t spgemm_f64(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat **c);
-int32_t spgemm_symbolic(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat **c);
+int32_t spgemm_f64(const sprs_hip_csmat *a, const sprs_hip_csmat *b, OwnedCsmat &c);
+int32_t spgemm_symbolic(const sprs_hip_csmat *a, const sprs_hip_csmat *b, OwnedCsmat &c);
 int32_t spgemm_numeric(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat *c);
 int32_t spgemm_plan_create(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_spgemm_plan **out);
-int32_t spgemm_plan_structure(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat **out, bool with_values);
+int32_t spgemm_plan_structure(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, const sprs_hip_csmat *b, OwnedCsmat &out, bool with_values);
 int32_t spgemm_plan_numeric(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat *c);
 uint64_t spgemm_plan_nnz(const sprs_hip_spgemm_plan *pl);
 void spgemm_plan_free(sprs_hip_spgemm_plan *pl);
@@ -380,17 +408,15 @@ int32_t dist_set_route(sprs_hip_dist *d, int32_t route);
 int32_t dist_route(const sprs_hip_dist *d, int32_t *route);
 // triplet.hip
 int32_t triplets_to_cs(uint64_t rows, uint64_t cols, uint64_t n, const void *row_inds, const void *col_inds, int32_t in_idx_bytes,
-                       const double *data, int32_t storage, int32_t out_idx_bytes, int32_t out_iptr_bytes, sprs_hip_csmat **out);
+                       const double *data, int32_t storage, int32_t out_idx_bytes, int32_t out_iptr_bytes, OwnedCsmat &out);
 // convert.hip
-int32_t to_other_storage(const sprs_hip_csmat *m, sprs_hip_csmat **out);
+int32_t to_other_storage(const sprs_hip_csmat *m, OwnedCsmat &out);
 // binop.hpp (compiled in convert.hip): operands of equal shape, storage and index widths; complete on `stream` at return
-int32_t csmat_binop_f64(const sprs_hip_csmat *a, const sprs_hip_csmat *b, int32_t op, sprs_hip_csmat **out, hipStream_t stream);
-int32_t csvec_binop_f64(const sprs_hip_csvec *v, const sprs_hip_csvec *w, int32_t op, uint64_t dim, sprs_hip_csvec **out, hipStream_t stream);
-int32_t csmat_scale_f64(const sprs_hip_csmat *m, double alpha, sprs_hip_csmat **out, hipStream_t stream);
+int32_t csmat_binop_f64(const sprs_hip_csmat *a, const sprs_hip_csmat *b, int32_t op, OwnedCsmat &out, hipStream_t stream);
+int32_t csvec_binop_f64(const sprs_hip_csvec *v, const sprs_hip_csvec *w, int32_t op, uint64_t dim, OwnedCsvec &out, hipStream_t stream);
+int32_t csmat_scale_f64(const sprs_hip_csmat *m, double alpha, OwnedCsmat &out, hipStream_t stream);
 // perm.hpp (compiled in convert.hip): o / g = device arrays of m's index type (outer / inner entries) or null for the identity
-int32_t csmat_permute(const sprs_hip_csmat *m, const void *o, const void *g, sprs_hip_csmat **out, hipStream_t stream);
-int32_t perm_alloc(sprs_hip_perm **out, uint64_t dim, int32_t idx_bytes, int32_t decl_idx_bytes);
-void perm_release(sprs_hip_perm *p);
+int32_t csmat_permute(const sprs_hip_csmat *m, const void *o, const void *g, OwnedCsmat &out, hipStream_t stream);
 int32_t perm_build_inverse(sprs_hip_perm *p, bool validate, hipStream_t stream);
 int32_t perm_is_identity(const sprs_hip_perm *p, int32_t *flag, hipStream_t stream);
 int32_t perm_mul_vec_f64(const sprs_hip_perm *p, const double *x, double *y, hipStream_t stream);
@@ -402,17 +428,31 @@ int32_t gauss_seidel_f64(sprs_hip_csmat *a, double *x, const double *rhs, uint64
                          sprs_hip_gauss_seidel_info *info, hipStream_t stream);
 // trisolve.hpp (compiled in gauss_seidel.hip): csr = the CSR form of the caller's handle, csc = that handle is CSC
 int32_t trisolve_f64(sprs_hip_csmat *csr, bool upper, bool csc, double *x, uint64_t n, sprs_hip_trisolve_info *info, hipStream_t stream);
-int32_t slice_outer(const sprs_hip_csmat *m, uint64_t start, uint64_t end, sprs_hip_csmat **out);
+int32_t slice_outer(const sprs_hip_csmat *m, uint64_t start, uint64_t end, OwnedCsmat &out);
 // csvec.hpp (compiled in spmv.hip)
-int32_t csvec_alloc(sprs_hip_csvec **out, uint64_t dim, uint64_t nnz, int32_t idx_bytes, int32_t decl_idx_bytes);
-void csvec_release(sprs_hip_csvec *v);
 int32_t csvec_check_device(const sprs_hip_csvec *v, hipStream_t stream);
 int32_t csvec_scatter(const sprs_hip_csvec *v, double *out, hipStream_t stream);
 int32_t csvec_masked_dot(const sprs_hip_csmat *m, const sprs_hip_csvec *v, bool drop_zero, int32_t idx_bytes, int32_t decl_bytes,
-                         sprs_hip_csvec **out, hipStream_t stream);
+                         OwnedCsvec &out, hipStream_t stream);
+// handle.hpp: the one place that makes handles
+// an owned matrix / vector / permutation with uninitialised arrays of the given sizes on the current device
+int32_t make_csmat(OwnedCsmat &out, int32_t storage, uint64_t rows, uint64_t cols, uint64_t nnz, int32_t iptr_bytes, int32_t idx_bytes);
+int32_t make_csvec(OwnedCsvec &out, uint64_t dim, uint64_t nnz, int32_t idx_bytes, int32_t decl_idx_bytes);
+int32_t make_perm(OwnedPerm &out, uint64_t dim, int32_t idx_bytes, int32_t decl_idx_bytes);
+// non-owning handles over arrays of the caller's: a matrix (`into` = a stack object to fill, or null for a new heap handle), a
+// vector, the Identity permutation (2-byte declared width: 4 on the device)
+sprs_hip_csmat *view_csmat(int32_t storage, uint64_t rows, uint64_t cols, uint64_t nnz, const void *indptr, int32_t iptr_bytes,
+                           const void *indices, int32_t idx_bytes, const double *data, int device, sprs_hip_csmat *into = nullptr);
+sprs_hip_csvec *view_csvec(uint64_t dim, uint64_t nnz, const void *indices, int32_t idx_bytes, const double *data, int device);
+sprs_hip_perm *identity_perm(uint64_t dim, int32_t idx_bytes);
+// a view of m's arrays with m's declared widths and device; transpose: transpose_view (csmat.rs:982-991) — free, flips the tag
+sprs_hip_csmat *view_csmat(const sprs_hip_csmat *m, bool transpose, sprs_hip_csmat *into = nullptr);
+// an owned matrix of m's storage, shape and widths whose indptr, indices and (with_data) values are copies of m's, enqueued
+// device to device on `stream` (not waited for)
+int32_t copy_csmat(const sprs_hip_csmat *m, bool with_data, OwnedCsmat &out, hipStream_t stream);
+// everything a handle derives from its arrays (plans, row orders, the copy in the other storage order, the transpose view)
+void invalidate_caches(sprs_hip_csmat *m);
 // abi.hip
-int32_t alloc_csmat(sprs_hip_csmat **out, int32_t storage, uint64_t rows, uint64_t cols, uint64_t nnz,
-                    int32_t iptr_bytes, int32_t idx_bytes);
 // a result inherits the declared index widths of its operand; INDEX_OVERFLOW where a value would not fit them
 int32_t inherit_declared_widths(sprs_hip_csmat *result, const sprs_hip_csmat *from);
 

@@ -193,7 +193,7 @@ __global__ void rebase_ptr_kernel(const PTR *__restrict__ in, uint64_t n, PTR *_
 }
 
 template <typename IDX, typename PTR>
-int32_t convert_impl(const sprs_hip_csmat *m, sprs_hip_csmat **out) {
+int32_t convert_impl(const sprs_hip_csmat *m, OwnedCsmat &out) {
     hipStream_t stream = nullptr;
     const uint64_t outer = m->outer(), inner = m->inner(), nnz = m->nnz;
     // the reference tests mat.rows() against I whatever the storage (csmat.rs:1794-1797)
@@ -202,10 +202,9 @@ int32_t convert_impl(const sprs_hip_csmat *m, sprs_hip_csmat **out) {
                   "Index type is not large enough to hold the number of rows requested (required %llu)",
                   (unsigned long long)m->rows);
     if (outer > 0xFFFFFFFEull) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "to_other_storage: outer dimension above 2^32-2 is not supported");
-    sprs_hip_csmat *o = nullptr;
-    SPRS_TRY(alloc_csmat(&o, m->storage == SPRS_HIP_CSR ? SPRS_HIP_CSC : SPRS_HIP_CSR, m->rows, m->cols, nnz,
-                         (int32_t)sizeof(PTR), (int32_t)sizeof(IDX)));
-    OwnedCsmat owned(o);
+    OwnedCsmat o;
+    SPRS_TRY(make_csmat(o, m->storage == SPRS_HIP_CSR ? SPRS_HIP_CSC : SPRS_HIP_CSR, m->rows, m->cols, nnz,
+                        (int32_t)sizeof(PTR), (int32_t)sizeof(IDX)));
     DevBuf cnt, optr, cursor, tkeys, tvals, large, nlarge;
     SPRS_TRY_HIP(cnt.alloc(inner * 8));
     SPRS_TRY_HIP(optr.alloc((inner + 1) * 8));
@@ -251,21 +250,21 @@ int32_t convert_impl(const sprs_hip_csmat *m, sprs_hip_csmat **out) {
         }
     }
     SPRS_TRY_HIP(hipStreamSynchronize(stream));
-    *out = owned.release();
+    out = std::move(o);
     return SPRS_HIP_OK;
 }
 
 template <typename IDX, typename PTR>
-int32_t slice_impl(const sprs_hip_csmat *m, uint64_t start, uint64_t end, sprs_hip_csmat **out) {
+int32_t slice_impl(const sprs_hip_csmat *m, uint64_t start, uint64_t end, OwnedCsmat &out) {
     hipStream_t stream = nullptr;
     PTR lo = 0, hi = 0;
     SPRS_TRY_HIP(copy_to_host(&lo, (const PTR *)m->indptr + start, sizeof(PTR), stream));
     SPRS_TRY_HIP(copy_to_host(&hi, (const PTR *)m->indptr + end, sizeof(PTR), stream));
     const uint64_t nnz = (uint64_t)hi - (uint64_t)lo, n = end - start;
-    sprs_hip_csmat *o = nullptr;
+    OwnedCsmat o;
     const bool csr = m->storage == SPRS_HIP_CSR;
-    SPRS_TRY(alloc_csmat(&o, m->storage, csr ? n : m->rows, csr ? m->cols : n, nnz, (int32_t)sizeof(PTR),
-                         (int32_t)sizeof(IDX)));
+    SPRS_TRY(make_csmat(o, m->storage, csr ? n : m->rows, csr ? m->cols : n, nnz, (int32_t)sizeof(PTR),
+                        (int32_t)sizeof(IDX)));
     hipLaunchKernelGGL(rebase_ptr_kernel<PTR>, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, stream,
                        (const PTR *)m->indptr + start, n + 1, (PTR *)o->indptr);
     hipError_t e = hipGetLastError();
@@ -274,23 +273,20 @@ int32_t slice_impl(const sprs_hip_csmat *m, uint64_t start, uint64_t end, sprs_h
     if (e == hipSuccess && nnz)
         e = hipMemcpyAsync(o->data, m->data + lo, nnz * sizeof(double), hipMemcpyDeviceToDevice, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) {
-        sprs_hip_csmat_free(o);
-        return fail_hip(e, "slice_outer");
-    }
-    *out = o;
+    if (e != hipSuccess) return fail_hip(e, "slice_outer");
+    out = std::move(o);
     return SPRS_HIP_OK;
 }
 
 }  // namespace
 
-int32_t to_other_storage(const sprs_hip_csmat *m, sprs_hip_csmat **out) {
+int32_t to_other_storage(const sprs_hip_csmat *m, OwnedCsmat &out) {
     return dispatch_widths(m->idx_bytes, m->iptr_bytes, [&](auto i, auto p) {
         return convert_impl<typename decltype(i)::type, typename decltype(p)::type>(m, out);
     });
 }
 
-int32_t slice_outer(const sprs_hip_csmat *m, uint64_t start, uint64_t end, sprs_hip_csmat **out) {
+int32_t slice_outer(const sprs_hip_csmat *m, uint64_t start, uint64_t end, OwnedCsmat &out) {
     return dispatch_widths(m->idx_bytes, m->iptr_bytes, [&](auto i, auto p) {
         return slice_impl<typename decltype(i)::type, typename decltype(p)::type>(m, start, end, out);
     });

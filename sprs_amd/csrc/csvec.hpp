@@ -253,35 +253,6 @@ static int32_t csvec_scratch(sprs_hip_csmat *m, uint64_t n) {
     return SPRS_HIP_OK;
 }
 
-int32_t csvec_alloc(sprs_hip_csvec **out, uint64_t dim, uint64_t nnz, int32_t idx_bytes, int32_t decl_idx_bytes) {
-    auto *v = new sprs_hip_csvec();
-    v->dim = dim;
-    v->nnz = nnz;
-    v->idx_bytes = idx_bytes;
-    v->decl_idx_bytes = decl_idx_bytes == idx_bytes ? 0 : decl_idx_bytes;
-    v->owns = true;
-    hipError_t e = hipGetDevice(&v->device);
-    if (e == hipSuccess) e = pool_alloc(&v->indices, nnz * (uint64_t)idx_bytes, &v->cap_indices, v->device);
-    if (e == hipSuccess) e = pool_alloc((void **)&v->data, nnz * sizeof(double), &v->cap_data, v->device);
-    if (e != hipSuccess) {
-        pool_free(v->indices, v->cap_indices, v->device);
-        pool_free(v->data, v->cap_data, v->device);
-        delete v;
-        return fail_hip(e, "csvec_alloc");
-    }
-    *out = v;
-    return SPRS_HIP_OK;
-}
-
-void csvec_release(sprs_hip_csvec *v) {
-    if (!v) return;
-    if (v->owns) {
-        pool_free(v->indices, v->cap_indices, v->device);
-        pool_free(v->data, v->cap_data, v->device);
-    }
-    delete v;
-}
-
 int32_t csvec_check_device(const sprs_hip_csvec *v, hipStream_t s) {
     if (v->nnz == 0) return SPRS_HIP_OK;
     DevBuf bad;
@@ -327,7 +298,7 @@ static void launch_dot(const sprs_hip_csmat *m, uint64_t n, const CsvecScratch &
 // The masked ordered dot of every outer slice of m with v (m->inner() == v->dim, checked by the caller).  The result has
 // dimension m->outer(), index width idx_bytes on the device (declared decl_bytes).  Blocks until it is complete on `st`.
 int32_t csvec_masked_dot(const sprs_hip_csmat *mc, const sprs_hip_csvec *v, bool drop_zero, int32_t idx_bytes, int32_t decl_bytes,
-                         sprs_hip_csvec **out, hipStream_t st) {
+                         OwnedCsvec &out, hipStream_t st) {
     auto *m = const_cast<sprs_hip_csmat *>(mc);
     std::lock_guard<std::recursive_mutex> lock(m->mu);         // the handle's scratch serves one product at a time
     const uint64_t n = v->dim, nouter = m->outer(), ngroups = (nouter + 63) / 64;
@@ -354,8 +325,8 @@ int32_t csvec_masked_dot(const sprs_hip_csmat *mc, const sprs_hip_csvec *v, bool
     // the result's nnz, read back in the caller's stream order (a non-blocking stream does not wait for the null stream)
     uint64_t nnz = 0;
     SPRS_TRY_HIP(copy_to_host(&nnz, offs + ngroups, 8, st));
-    sprs_hip_csvec *res = nullptr;
-    SPRS_TRY(csvec_alloc(&res, nouter, nnz, idx_bytes, decl_bytes));
+    OwnedCsvec res;
+    SPRS_TRY(make_csvec(res, nouter, nnz, idx_bytes, decl_bytes));
     if (nnz) {
         const uint64_t decl = decl_bytes ? decl_bytes : idx_bytes;
         const uint64_t limit = decl >= 8 ? ~0ull : (1ull << (8 * decl)) - 1ull;
@@ -370,17 +341,12 @@ int32_t csvec_masked_dot(const sprs_hip_csmat *mc, const sprs_hip_csvec *v, bool
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = copy_to_host(&flag, overflow, 4, st);
-        if (e != hipSuccess) {
-            csvec_release(res);
-            return fail_hip(e, "csvec product");
-        }
-        if (flag) {
-            csvec_release(res);
+        if (e != hipSuccess) return fail_hip(e, "csvec product");
+        if (flag)
             SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "Index type is not large enough to hold the index of a result entry (dimension %llu)",
                       (unsigned long long)nouter);
-        }
     }
-    *out = res;
+    out = std::move(res);
     return SPRS_HIP_OK;
 }
 

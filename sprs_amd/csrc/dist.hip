@@ -157,7 +157,7 @@ void dist_free(sprs_hip_dist *d) {
 #else
         (void)p;
 #endif
-    for (auto *m : d->sub) sprs_hip_csmat_free(m);
+    for (auto *m : d->sub) delete m;
     for (auto e : d->done)
         if (e) (void)hipEventDestroy(e);
     if (d->gathered) (void)hipEventDestroy(d->gathered);
@@ -219,8 +219,9 @@ int32_t dist_create(sprs_hip_dist **out, const void *unique_id128, int32_t world
     }
     cuts.push_back(lrows);
     for (size_t s = 0; s + 1 < cuts.size(); ++s) {
-        sprs_hip_csmat *m = nullptr;
-        SPRS_TRY(slice_outer(local_block, cuts[s], cuts[s + 1], &m));
+        OwnedCsmat piece;
+        SPRS_TRY(slice_outer(local_block, cuts[s], cuts[s + 1], piece));
+        sprs_hip_csmat *m = piece.release();
         d->sub.push_back(m);
         // an iterative caller by construction: the final plan is built now, so that the first collective multiply already runs
         // on it (and multiply #1 and #2 of a solver give the same bits; plan policy, sprs_hip.h)

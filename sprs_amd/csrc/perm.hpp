@@ -416,10 +416,9 @@ int32_t run(const sprs_hip_csmat *m, const void *o_, const void *g_, sprs_hip_cs
     I *ix_out = (I *)res->indices;
     uint64_t *v_out = (uint64_t *)res->data;
     if (outer >= 0xFFFFFFFFull * PM_BLOCK) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "permutation: more than 2^40 outer slices are not supported");
-    auto take = [&](DevBuf &b, uint64_t bytes) { return st == nullptr ? b.alloc_pooled(bytes) : b.alloc(bytes); };
     // lens (outer) | offs (outer + 1) | counts, cursors (PM_CLASSES each)
     DevBuf tmp, listb;
-    SPRS_TRY_HIP(take(tmp, (2 * outer + 1 + 2 * PM_CLASSES) * 8));
+    SPRS_TRY_HIP(tmp.alloc_for(st, (2 * outer + 1 + 2 * PM_CLASSES) * 8));
     uint64_t *lens = tmp.u64(), *offs = lens + outer;
     unsigned long long *counts = (unsigned long long *)(offs + outer + 1), *cursor = counts + PM_CLASSES;
     const bool sorting = g != nullptr && nnz != 0;
@@ -445,7 +444,7 @@ int32_t run(const sprs_hip_csmat *m, const void *o_, const void *g_, sprs_hip_cs
         return SPRS_HIP_OK;
     }
     if (inner > (1ull << PM_HUB_SHIFT)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "permutation: an inner dimension above 2^40 is not supported");
-    SPRS_TRY_HIP(take(listb, outer * 8));
+    SPRS_TRY_HIP(listb.alloc_for(st, outer * 8));
     uint64_t *list = listb.u64();
     hipLaunchKernelGGL(perm_list_kernel, dim3(chunks_for(outer)), dim3(PM_BLOCK), 0, st, (const uint64_t *)offs, outer,
                        (const unsigned long long *)counts, cursor, list);
@@ -483,7 +482,7 @@ int32_t run(const sprs_hip_csmat *m, const void *o_, const void *g_, sprs_hip_cs
         const uint64_t *hubs = list + base[5];
         // hub_len (nhubs) | first (nhubs + 1)
         DevBuf hb, keys, srcs;
-        SPRS_TRY_HIP(take(hb, (2 * nhubs + 1) * 8));
+        SPRS_TRY_HIP(hb.alloc_for(st, (2 * nhubs + 1) * 8));
         uint64_t *hub_len = hb.u64(), *first = hub_len + nhubs;
         hipLaunchKernelGGL(perm_hub_len_kernel, dim3(blocks_for(nhubs)), dim3(PM_BLOCK), 0, st, hubs, nhubs, (const uint64_t *)offs, outer, hub_len);
         SPRS_TRY_HIP(hipGetLastError());
@@ -491,8 +490,8 @@ int32_t run(const sprs_hip_csmat *m, const void *o_, const void *g_, sprs_hip_cs
         uint64_t n = 0;
         SPRS_TRY_HIP(copy_to_host(&n, first + nhubs, 8, st));
         if (n > nnz) SPRS_FAIL(SPRS_HIP_HIP_ERROR, "permutation: inconsistent hub count");
-        SPRS_TRY_HIP(take(keys, n * 8));
-        SPRS_TRY_HIP(take(srcs, n * 8));
+        SPRS_TRY_HIP(keys.alloc_for(st, n * 8));
+        SPRS_TRY_HIP(srcs.alloc_for(st, n * 8));
         hipLaunchKernelGGL((perm_hub_keys_kernel<P, I>), dim3(blocks_for(n)), dim3(PM_BLOCK), 0, st, hubs, nhubs, (const uint64_t *)first, n, ip, o,
                            g, ix, outer, inner, nnz, keys.u64(), srcs.u64());
         SPRS_TRY_HIP(hipGetLastError());
@@ -511,54 +510,22 @@ int32_t run(const sprs_hip_csmat *m, const void *o_, const void *g_, sprs_hip_cs
 // The one algorithm of permutation.rs:296-591 on a handle: result outer slice r' = outer slice o[r'] of m, inner index j -> g[j],
 // slices sorted.  o / g: device arrays of m's index type with outer / inner entries, or null for the identity.  A new handle
 // in m's storage and widths; m is only read.  Blocks until the result is complete on `st`.
-int32_t csmat_permute(const sprs_hip_csmat *m, const void *o, const void *g, sprs_hip_csmat **out, hipStream_t st) {
-    sprs_hip_csmat *res = nullptr;
-    SPRS_TRY(alloc_csmat(&res, m->storage, m->rows, m->cols, m->nnz, m->iptr_bytes, m->idx_bytes));
-    OwnedCsmat owned(res);
+int32_t csmat_permute(const sprs_hip_csmat *m, const void *o, const void *g, OwnedCsmat &out, hipStream_t st) {
+    OwnedCsmat res;
     if (!o && !g) {                                 // the reference's shortcuts: a plain copy
-        SPRS_TRY_HIP(hipMemcpyAsync(res->indptr, m->indptr, (m->outer() + 1) * (uint64_t)m->iptr_bytes, hipMemcpyDeviceToDevice, st));
-        if (m->nnz) {
-            SPRS_TRY_HIP(hipMemcpyAsync(res->indices, m->indices, m->nnz * (uint64_t)m->idx_bytes, hipMemcpyDeviceToDevice, st));
-            SPRS_TRY_HIP(hipMemcpyAsync(res->data, m->data, m->nnz * sizeof(double), hipMemcpyDeviceToDevice, st));
-        }
+        SPRS_TRY(copy_csmat(m, true, res, st));
         SPRS_TRY_HIP(hipStreamSynchronize(st));
     } else {
+        SPRS_TRY(make_csmat(res, m->storage, m->rows, m->cols, m->nnz, m->iptr_bytes, m->idx_bytes));
         SPRS_TRY(dispatch_widths(m->idx_bytes, m->iptr_bytes, [&](auto i, auto p) {
-            return pm::run<typename decltype(p)::type, typename decltype(i)::type>(m, o, g, res, st);
+            return pm::run<typename decltype(p)::type, typename decltype(i)::type>(m, o, g, res.get(), st);
         }));
     }
-    *out = owned.release();
+    out = std::move(res);
     return SPRS_HIP_OK;
 }
 
 // ---- PermOwned ---------------------------------------------------------------------------------------------------------------
-
-int32_t perm_alloc(sprs_hip_perm **out, uint64_t dim, int32_t idx_bytes, int32_t decl_idx_bytes) {
-    auto *p = new sprs_hip_perm();
-    p->dim = dim;
-    p->idx_bytes = idx_bytes;
-    p->decl_idx_bytes = decl_idx_bytes == idx_bytes ? 0 : decl_idx_bytes;
-    hipError_t e = hipGetDevice(&p->device);
-    if (e == hipSuccess) e = pool_alloc(&p->perm, dim * (uint64_t)idx_bytes, &p->cap_perm, p->device);
-    if (e == hipSuccess) e = pool_alloc(&p->perm_inv, dim * (uint64_t)idx_bytes, &p->cap_inv, p->device);
-    if (e != hipSuccess) {
-        pool_free(p->perm, p->cap_perm, p->device);
-        pool_free(p->perm_inv, p->cap_inv, p->device);
-        delete p;
-        return fail_hip(e, "perm_alloc");
-    }
-    *out = p;
-    return SPRS_HIP_OK;
-}
-
-void perm_release(sprs_hip_perm *p) {
-    if (!p) return;
-    if (!p->identity) {
-        pool_free(p->perm, p->cap_perm, p->device);
-        pool_free(p->perm_inv, p->cap_inv, p->device);
-    }
-    delete p;
-}
 
 // perm_inv[perm[i]] = i (permutation.rs:52-66) and, with `validate`, perm_is_valid (permutation.rs:39-49) on the device
 int32_t perm_build_inverse(sprs_hip_perm *p, bool validate, hipStream_t st) {

@@ -73,7 +73,7 @@ int32_t exclusive_scan_u64(const uint64_t *in, uint64_t *out, uint64_t n, hipStr
     // block sums: from the pool on the null stream (DevBuf, common.hpp); on any other stream a block of its own, freed behind
     // that stream
     DevBuf sums;
-    SPRS_TRY_HIP(stream == nullptr ? sums.alloc_pooled((nblocks + 1) * sizeof(uint64_t)) : sums.alloc((nblocks + 1) * sizeof(uint64_t)));
+    SPRS_TRY_HIP(sums.alloc_for(stream, (nblocks + 1) * sizeof(uint64_t)));
     hipLaunchKernelGGL(scan_partial_kernel, dim3((unsigned)nblocks), dim3(SCAN_BLOCK), 0, stream, in, n, sums.u64());
     hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(1024), 0, stream, sums.u64(), nblocks);
     hipLaunchKernelGGL(scan_final_kernel, dim3((unsigned)nblocks), dim3(SCAN_BLOCK), 0, stream, in, n, sums.u64(), nblocks, out);

@@ -95,11 +95,10 @@ int32_t radix_sort_pairs(uint64_t *keys, uint64_t *vals, uint64_t n, const std::
     // temporaries: from the pool on the null stream (DevBuf, common.hpp); on any other stream blocks of their own, freed behind
     // that stream
     DevBuf btk, btv, bhist, boffs;
-    auto take = [&](DevBuf &b, uint64_t bytes) { return stream == nullptr ? b.alloc_pooled(bytes) : b.alloc(bytes); };
-    hipError_t e = take(btk, n * 8);
-    if (e == hipSuccess) e = take(btv, n * 8);
-    if (e == hipSuccess) e = take(bhist, (RS_BINS * nchunks + 1) * 8);
-    if (e == hipSuccess) e = take(boffs, (RS_BINS * nchunks + 1) * 8);
+    hipError_t e = btk.alloc_for(stream, n * 8);
+    if (e == hipSuccess) e = btv.alloc_for(stream, n * 8);
+    if (e == hipSuccess) e = bhist.alloc_for(stream, (RS_BINS * nchunks + 1) * 8);
+    if (e == hipSuccess) e = boffs.alloc_for(stream, (RS_BINS * nchunks + 1) * 8);
     if (e != hipSuccess) return fail_hip(e, "radix_sort_pairs");
     uint64_t *tk = btk.u64(), *tv = btv.u64(), *hist = bhist.u64(), *offs = boffs.u64();
     uint64_t *ik = keys, *iv = vals, *ok = tk, *ov = tv;

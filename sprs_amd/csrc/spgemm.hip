@@ -2405,17 +2405,16 @@ static int32_t plan_matches(const sprs_hip_spgemm_plan *pl, const sprs_hip_csmat
 }
 
 // structure of the product as a new matrix (values zero): what smmp::symbolic returns
-int32_t spgemm_plan_structure(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat **out,
+int32_t spgemm_plan_structure(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, const sprs_hip_csmat *b, OwnedCsmat &out,
                               bool with_values) {
     SPRS_TRY(plan_matches(pl, a, b));
-    sprs_hip_csmat *raw = nullptr;
-    SPRS_TRY(alloc_csmat(&raw, SPRS_HIP_CSR, pl->rows, pl->b_cols, pl->c_nnz, pl->iptr_bytes, pl->idx_bytes));
-    OwnedCsmat c(raw);
+    OwnedCsmat c;
+    SPRS_TRY(make_csmat(c, SPRS_HIP_CSR, pl->rows, pl->b_cols, pl->c_nnz, pl->iptr_bytes, pl->idx_bytes));
     SPRS_TRY(plan_indptr(pl, c.get(), false));
     const hipError_t e = with_values ? hipSuccess : hipMemsetAsync(c->data, 0, (pl->c_nnz ? pl->c_nnz : 1) * sizeof(double), nullptr);
     if (e != hipSuccess) return fail_hip(e, "spgemm structure");
     SPRS_TRY(plan_run(pl, a, b, c.get(), with_values, true));
-    *out = c.release();
+    out = std::move(c);
     return SPRS_HIP_OK;
 }
 
@@ -2441,12 +2440,12 @@ static int32_t with_temporary_plan(const sprs_hip_csmat *a, const sprs_hip_csmat
     return f(pl);
 }
 
-int32_t spgemm_f64(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat **c) {
+int32_t spgemm_f64(const sprs_hip_csmat *a, const sprs_hip_csmat *b, OwnedCsmat &c) {
     return with_temporary_plan(a, b, [&](sprs_hip_spgemm_plan *pl) { return spgemm_plan_structure(pl, a, b, c, true); });
 }
 
 // smmp::symbolic (smmp.rs:81-131): structure only; the values of the result are zero
-int32_t spgemm_symbolic(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat **c) {
+int32_t spgemm_symbolic(const sprs_hip_csmat *a, const sprs_hip_csmat *b, OwnedCsmat &c) {
     return with_temporary_plan(a, b, [&](sprs_hip_spgemm_plan *pl) { return spgemm_plan_structure(pl, a, b, c, false); });
 }
 

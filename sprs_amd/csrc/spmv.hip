@@ -580,6 +580,49 @@ static uint64_t plan_signature(const Options &o) {
     return h | 1ull;
 }
 
+// everything the plan owns goes back; the plan is as new
+void SpmvPlan::release() {
+    auto drop = [](void *p) {
+        if (p) (void)hipFree(p);
+    };
+    band_free(band);
+    band = nullptr;
+    drop(main.tile_row);
+    drop(main.pos);
+    if (main.owns) {
+        drop(main.indptr);
+        drop(main.indices);
+        drop(main.data);
+    }
+    main = CsrPiece();
+    for (auto &sl : slice) {
+        drop(sl.tile_row);
+        drop(sl.pos);
+        if (sl.owns) {
+            drop(sl.indptr);
+            drop(sl.indices);
+            drop(sl.data);
+        }
+        sl = CsrPiece();
+    }
+    drop(long_rows);
+    drop(slab);
+    drop(perm);
+    perm = nullptr;
+    long_rows = nullptr;
+    slab = nullptr;
+    for (auto &kv : scratch) {
+        drop(kv.second.carry_main);
+        drop(kv.second.carry_slices);
+        drop(kv.second.partial);
+        drop(kv.second.xp);
+    }
+    scratch.clear();
+    n_long = 0;
+    built = false;
+    xcs = false;
+}
+
 // light: the handle's first multiply — a plan that COPIES the matrix (banded, XCD-sliced) is not built yet unless the options
 // force it; pl.light then says that the next multiply should come back here.  A handle that multiplies once (`&a * &x` on a
 // temporary) never pays the ~0.1 s of a copy plan; one that iterates pays it at its second multiply.

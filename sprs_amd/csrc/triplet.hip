@@ -69,24 +69,21 @@ int bits_for(uint64_t n) {       // bits needed for values < n
 
 template <typename I>
 int32_t assemble(uint64_t rows, uint64_t cols, uint64_t n, const I *row_inds, const I *col_inds, const double *data, int32_t storage,
-                 int32_t out_idx_bytes, int32_t out_iptr_bytes, sprs_hip_csmat **out) {
+                 int32_t out_idx_bytes, int32_t out_iptr_bytes, OwnedCsmat &out) {
     hipStream_t stream = nullptr;
     const bool csr = storage == SPRS_HIP_CSR;
     const uint64_t n_outer = csr ? rows : cols, n_inner = csr ? cols : rows;
     const I *outer = csr ? row_inds : col_inds, *inner = csr ? col_inds : row_inds;
-    sprs_hip_csmat *c = nullptr;
+    OwnedCsmat c;
     if (n == 0) {
-        SPRS_TRY(alloc_csmat(&c, storage, rows, cols, 0, out_iptr_bytes, out_idx_bytes));
+        SPRS_TRY(make_csmat(c, storage, rows, cols, 0, out_iptr_bytes, out_idx_bytes));
         dispatch_width(out_iptr_bytes, [&](auto p) {
             using PT = typename decltype(p)::type;
             hipLaunchKernelGGL(tri_empty_indptr_kernel<PT>, dim3((unsigned)((n_outer + 256) / 256)), dim3(256), 0, stream, (PT *)c->indptr, n_outer);
         });
-        hipError_t e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) {
-            sprs_hip_csmat_free(c);
-            return fail_hip(e, "triplets_to_cs");
-        }
-        *out = c;
+        const hipError_t e = hipStreamSynchronize(stream);
+        if (e != hipSuccess) return fail_hip(e, "triplets_to_cs");
+        out = std::move(c);
         return SPRS_HIP_OK;
     }
     DevBuf keys, vals, head, gidx, bad;
@@ -110,7 +107,7 @@ int32_t assemble(uint64_t rows, uint64_t cols, uint64_t n, const I *row_inds, co
     SPRS_TRY_HIP(copy_to_host(&ngroups, gidx.u64() + n, 8, stream));
     if (out_iptr_bytes == 4 && ngroups > 0xFFFFFFFFull)
         SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "Index type is not large enough to hold the nnz of the matrix (%llu)", (unsigned long long)ngroups);
-    SPRS_TRY(alloc_csmat(&c, storage, rows, cols, ngroups, out_iptr_bytes, out_idx_bytes));
+    SPRS_TRY(make_csmat(c, storage, rows, cols, ngroups, out_iptr_bytes, out_idx_bytes));
     dispatch_widths(out_idx_bytes, out_iptr_bytes, [&](auto i, auto p) {
         using IT = typename decltype(i)::type;
         using PT = typename decltype(p)::type;
@@ -120,18 +117,15 @@ int32_t assemble(uint64_t rows, uint64_t cols, uint64_t n, const I *row_inds, co
     });
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) {
-        sprs_hip_csmat_free(c);
-        return fail_hip(e, "triplets_to_cs");
-    }
-    *out = c;
+    if (e != hipSuccess) return fail_hip(e, "triplets_to_cs");
+    out = std::move(c);
     return SPRS_HIP_OK;
 }
 
 }  // namespace
 
 int32_t triplets_to_cs(uint64_t rows, uint64_t cols, uint64_t n, const void *row_inds, const void *col_inds, int32_t in_idx_bytes,
-                       const double *data, int32_t storage, int32_t out_idx_bytes, int32_t out_iptr_bytes, sprs_hip_csmat **out) {
+                       const double *data, int32_t storage, int32_t out_idx_bytes, int32_t out_iptr_bytes, OwnedCsmat &out) {
     if (rows > 0xFFFFFFFFull || cols > 0xFFFFFFFFull) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "triplet assembly: more than 2^32 rows or columns is not supported");
     return dispatch_width(in_idx_bytes, [&](auto i) {
         using I = typename decltype(i)::type;

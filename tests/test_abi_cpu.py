@@ -221,6 +221,36 @@ def test_host_copies_and_temporaries_go_through_common_hpp():
         assert not m, "%s defines its own temporary-buffer struct %s (use DevBuf, common.hpp)" % (f, m and m.group(1))
 
 
+def test_handles_are_made_and_released_in_one_place():
+    """Handles are made in handle.hpp and released by `delete` (their destructors and block owners, common.hpp): no other file
+    says `new sprs_hip_...` or pool_free, no internal code goes through the public free entries (they clear the error state),
+    and only set_error / fail_hip / clear_error write the thread-local error state."""
+    csrc = os.path.join(ROOT, "sprs_amd", "csrc")
+    owners = re.compile(r"^struct (?:PoolBlock|DevBuf) \{.*?^\};\n", re.S | re.M)
+    writers = re.compile(r"^(?:void|int32_t) (?:set_error|fail_hip|clear_error)\(.*?^\}\n", re.S | re.M)
+    frees = 0
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".hpp")):
+            continue
+        text = re.sub(r"//.*", "", open(os.path.join(csrc, f)).read())
+        if f != "handle.hpp":
+            m = re.search(r"\bnew\s+sprs_hip_(?:csmat|csvec|perm)\b", text)
+            assert not m, "%s makes a handle itself: %s (use the constructors of handle.hpp)" % (f, m and m.group(0))
+            rest = owners.sub("", text).replace("void pool_free(void *p, uint64_t cap, int device, bool stream_ordered = false);", "")
+            assert "pool_free(" not in rest, "%s: pool_free outside handle.hpp, PoolBlock and DevBuf" % f
+        for name in ("sprs_hip_csmat_free", "sprs_hip_csvec_free", "sprs_hip_perm_free"):
+            calls = len(re.findall(r"\b%s\(" % name, text))
+            defs = len(re.findall(r"^int32_t %s\(" % name, text, re.M))
+            assert calls == defs and (f == "abi.hip" or not calls), "%s calls %s (delete the handle: the entry clears the error state)" % (f, name)
+            frees += defs
+        if f == "abi.hip":
+            assert len(writers.findall(text)) == 3
+            text = writers.sub("", text).replace("static thread_local int32_t tl_hip_code = 0;", "")
+        m = re.search(r"\btl_(?:msg|hip_code)\s*(?:=(?!=)|\.(?:clear|assign|append|swap)\b)", text)
+        assert not m, "%s writes the thread-local error state outside set_error / fail_hip / clear_error: %s" % (f, m and m.group(0))
+    assert frees == 3
+
+
 def test_no_macro_wraps_a_kernel_launch():
     """Kernel launches are written in ordinary (template) functions: no #define in sprs_amd/csrc has hipLaunchKernelGGL in its
     body (continuation lines included), and the four-way index-width ladder is written out in common.hpp only (dispatch_widths)."""

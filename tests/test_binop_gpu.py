@@ -434,6 +434,25 @@ def test_result_nnz_overflows_the_declared_indptr_type():
     _check(_binop(da, da, SUB), ((2, n), [0, 0, 0], [], []))
 
 
+def test_overflow_message_survives_the_converted_rhs():
+    """the same sum with a CSC rhs: `&lhs + &rhs` converts it first (binop.rs:52-64), and releasing that temporary on the way
+    out of the failed call must leave the status AND the message the CSR rhs gives"""
+    from sprs_amd import SprsHipError, _ffi
+    n = 40000
+    a = ((2, n), np.array([0, n, n]), np.arange(n), np.ones(n))
+    b = ((2, n), np.array([0, 0, n]), np.arange(n), np.ones(n))
+    b_csc = ((2, n), np.arange(n + 1), np.ones(n, dtype=np.int64), np.ones(n))      # the same matrix by columns
+    da = _mat(a, 0, np.uint16, np.uint16)
+    seen = []
+    for db in (_mat(b, 0, np.uint16, np.uint16), _mat(b_csc, 1, np.uint16, np.uint16)):
+        with pytest.raises(SprsHipError) as e:
+            da + db
+        assert e.value.status == _ffi.INDEX_OVERFLOW
+        seen.append(str(e.value))
+    assert seen[0].endswith("nnz of the result (80000)")
+    assert seen[1] == seen[0]
+
+
 # ---- real device only -----------------------------------------------------------------------------------------------------------
 
 @pytest.fixture(scope="module")

@@ -632,6 +632,26 @@ def test_iptr_overflow_u32(hip):
     assert e.value.status == _ffi.INDEX_OVERFLOW
 
 
+def test_overflow_message_survives_the_converted_rhs(hip):
+    """`&lhs * &rhs` with all index types u16: 300 x 1 times 1 x 300 of ones has 90000 > 65535 entries (Iptr::from_usize,
+    smmp.rs:121).  A CSC rhs goes through rhs.to_other_storage() first (csmat.rs:1895-1949); releasing that temporary on the
+    way out of the failed call must leave the status AND the message the CSR rhs gives."""
+    from sprs_amd import SprsHipError, _ffi
+    from sprs_amd.device import DeviceCsMat
+    n, u16 = 300, np.uint16
+    lhs = DeviceCsMat.from_host((n, 1), np.arange(n + 1, dtype=u16), np.zeros(n, dtype=u16), np.ones(n))
+    row = ((1, n), np.array([0, n], dtype=u16), np.arange(n, dtype=u16), np.ones(n))
+    col = ((1, n), np.arange(n + 1, dtype=u16), np.zeros(n, dtype=u16), np.ones(n))
+    seen = []
+    for rhs in (DeviceCsMat.from_host(*row), DeviceCsMat.from_host(*col, storage=_ffi.CSC)):
+        with pytest.raises(SprsHipError) as e:
+            lhs * rhs
+        assert e.value.status == _ffi.INDEX_OVERFLOW
+        seen.append(str(e.value))
+    assert seen[0].endswith("hold the nnz of the result (90000)")
+    assert seen[1] == seen[0]
+
+
 def test_deterministic_and_operator(hip):
     from sprs_amd import gen
     from sprs_amd.device import DeviceCsMat
