@@ -30,3 +30,11 @@ def ragged_csr(row_lengths, cols, seed=0, idx=np.uint64, ptr=np.uint64, positive
             indices[indptr[r]:indptr[r + 1]] = np.sort(c)
     data = rng.random(indptr[-1]) + 0.5 if positive else rng.standard_normal(indptr[-1])
     return (len(row_lengths), cols), indptr.astype(ptr), indices.astype(idx), data
+
+
+def fresh_blocks():
+    """Hand the library's cached device blocks back to the driver, so that the next results land in fresh blocks (poisoned:
+    conftest.py on the device, every block in the kernel emulator) and not in recycled ones that still hold an earlier result
+    — which may equal the expected one exactly where a kernel forgets to write."""
+    from sprs_amd import _ffi
+    _ffi.check(_ffi.lib.sprs_hip_pool_trim(None))

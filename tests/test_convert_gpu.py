@@ -1,13 +1,16 @@
 """GPU parity tests: to_other_storage (csmat.rs:1405-1426, 1782-1829), slice_outer
 (slicing.rs:65-89), transpose_view (csmat.rs:982-991) and the storage dispatch of
 csmat_mul_csmat (csmat.rs:1895-1949) against the oracle / golden fixtures."""
+import os
+
 import numpy as np
 import pytest
 
 from conftest import IDX_COMBOS, as_csr
-from helpers import ragged_csr
+from helpers import fresh_blocks, ragged_csr
 
 pytestmark = pytest.mark.gpu
+EMULATED = bool(os.environ.get("SPRS_HIP_LIBRARY"))   # the kernel emulator of tests/emu (tests/test_convert_emu_cpu.py)
 
 
 @pytest.fixture(scope="module")
@@ -57,7 +60,7 @@ def test_to_other_storage_golden(hip, golden, idx, ptr):
 def test_to_other_storage_rmat_and_long_columns(hip):
     from oracle import oracle
     from sprs_amd import gen
-    n = 40000
+    n = 10000 if EMULATED else 40000
     indptr, indices, data = gen.rmat_csr(n, 12, seed=9)      # hub columns exceed the 1024-entry wave path
     ip, ix, dt = indptr.numpy().astype(np.uint64), indices.numpy().astype(np.uint64), data.numpy()
     o = dev(((n, n), ip, ix, dt)).to_other_storage()
@@ -117,8 +120,15 @@ def test_slice_outer_and_transpose_view(hip, golden):
         a.slice_outer(3, 9)
     t = a.transpose_view()
     assert t.is_csc() and t.shape() == (5, 5)
-    # (A^T)^T stored as CSR again equals to_other_storage of the CSC view's arrays
-    assert same(t.to_other_storage().transpose_view().to_other_storage().transpose_view(), golden["mat1"]) or True
+    # link by link: A^T as CSC shares A's arrays; converted, A^T as CSR holds the arrays of A as CSC; its transpose view
+    # IS A as CSC; one more conversion is A as CSR again
+    assert all(np.array_equal(x, y) for x, y in zip(t.to_host()[1:], e[1:]))
+    tc = t.to_other_storage()
+    c = as_csr(golden["mat1_csc"])
+    assert tc.is_csr() and tc.shape() == (5, 5) and all(np.array_equal(x, y) for x, y in zip(tc.to_host()[1:], c[1:]))
+    a_csc = tc.transpose_view()
+    assert same(a_csc, golden["mat1_csc"])
+    assert same(a_csc.to_other_storage(), golden["mat1"])
     # SpMV on a materialised slice == rows of the full product
     from sprs_amd.device import DeviceVec
     x = np.array([1.0, 2.0, 3.0, 4.0, 5.0])
@@ -207,3 +217,156 @@ def test_two_byte_index_types(hip, golden, idx, ptr):
         with pytest.raises(hip.SprsHipError) as e:
             band * band
         assert e.value.status == hip._ffi.INDEX_OVERFLOW
+
+
+# ---- seams of the conversion, the scan behind it and slice_outer: bit-exact against the oracle ---------------------
+
+def csr_from_cells(outer, inner, o, c, seed, idx=np.uint64, ptr=np.uint64):
+    """CSR arrays of the distinct cells (o, c), normal values"""
+    o, c = np.asarray(o, dtype=np.int64), np.asarray(c, dtype=np.int64)
+    order = np.lexsort((c, o))
+    o, c = o[order], c[order]
+    assert not np.any((o[1:] == o[:-1]) & (c[1:] == c[:-1]))
+    ip = np.zeros(outer + 1, dtype=np.int64)
+    np.cumsum(np.bincount(o, minlength=outer), out=ip[1:])
+    return (outer, inner), ip.astype(ptr), c.astype(idx), np.random.default_rng(seed).standard_normal(c.size)
+
+
+def check_conversion(m, idx, ptr, storage=None):
+    """to_other_storage of the (outer x inner) arrays m == the oracle's, dtypes included, and the way back gives m's bits.
+    Returns the converted arrays."""
+    from oracle import oracle
+    from sprs_amd import _ffi
+    storage = _ffi.CSR if storage is None else storage
+    (outer, inner), ip, ix, dt = m
+    assert ip.dtype == np.dtype(ptr) and ix.dtype == np.dtype(idx)
+    shape = (outer, inner) if storage == _ffi.CSR else (inner, outer)
+    fresh_blocks()
+    o = dev((shape, ip, ix, dt), storage=storage).to_other_storage()
+    rip, rix, rdt = oracle.convert_storage(outer, inner, ip, ix, dt, mat_rows=shape[0])
+    s2, gip, gix, gdt = o.to_host()
+    assert tuple(s2) == shape and o.storage() == (_ffi.CSC if storage == _ffi.CSR else _ffi.CSR)
+    assert gip.dtype == np.dtype(ptr) and gix.dtype == np.dtype(idx) and gip.size == inner + 1
+    assert np.array_equal(gip, rip)
+    assert np.array_equal(gix, rix)
+    assert np.array_equal(gdt.view(np.uint64), rdt.view(np.uint64))
+    fresh_blocks()
+    back = o.to_other_storage()
+    s3, bip, bix, bdt = back.to_host()
+    assert tuple(s3) == shape and back.storage() == storage
+    assert bip.dtype == ip.dtype and bix.dtype == ix.dtype
+    assert np.array_equal(bip, ip) and np.array_equal(bix, ix) and np.array_equal(bdt.view(np.uint64), dt.view(np.uint64))
+    return gip, gix, gdt
+
+
+ROW_CLASSES = [0, 1, 2, 3, 63, 64, 65, 127, 128, 129, 1023, 1024, 1025, 0, 1500, 0]
+
+
+@pytest.mark.parametrize("idx,ptr", IDX_COMBOS)
+def test_output_row_length_classes(hip, idx, ptr):
+    """output rows of 0 / 1 entries (shortcuts), around the bitonic sort's power-of-two paddings, and on both sides of the
+    1024-entry switch from the one-wave kernel to the workgroup kernel"""
+    rng = np.random.default_rng(41)
+    rows = 1600
+    o = np.concatenate([rng.permutation(rows)[:k] for k in ROW_CLASSES])
+    c = np.repeat(np.arange(len(ROW_CLASSES)), ROW_CLASSES)
+    gip, gix, _ = check_conversion(csr_from_cells(rows, len(ROW_CLASSES), o, c, 42, idx, ptr), idx, ptr)
+    assert np.diff(gip.astype(np.int64)).tolist() == ROW_CLASSES
+    for j in range(len(ROW_CLASSES)):                          # independent of the oracle: every output row sorted, no entry lost
+        assert np.array_equal(gix[int(gip[j]):int(gip[j + 1])], np.sort(o[c == j]).astype(idx))
+
+
+@pytest.mark.parametrize("idx,ptr", IDX_COMBOS)
+@pytest.mark.parametrize("shape", [(0, 5), (5, 0), (5, 7)])
+def test_degenerate_shapes(hip, shape, idx, ptr):
+    from sprs_amd import _ffi
+    for storage in (_ffi.CSR, _ffi.CSC):
+        outer, inner = shape if storage == _ffi.CSR else shape[::-1]
+        fresh_blocks()
+        o = dev((shape, np.zeros(outer + 1, dtype=ptr), np.zeros(0, dtype=idx), np.zeros(0)), storage=storage).to_other_storage()
+        s2, gip, gix, gdt = o.to_host()
+        assert tuple(s2) == shape and o.storage() == (_ffi.CSC if storage == _ffi.CSR else _ffi.CSR) and o.nnz() == 0
+        assert gip.dtype == np.dtype(ptr) and gix.dtype == np.dtype(idx)
+        assert gip.tolist() == [0] * (inner + 1) and gix.size == 0 and gdt.size == 0
+
+
+def rows_over_inner(n_rows, inner, per_row, forced, seed):
+    rng = np.random.default_rng(seed)
+    o, c = [], []
+    for r in range(n_rows):
+        cols = rng.permutation(inner)[:per_row] if inner < 10000 else rng.integers(0, inner, per_row)
+        cols = np.unique(np.concatenate([cols, forced if r in (0, n_rows - 1) else []]).astype(np.int64))
+        o.append(np.full(cols.size, r))
+        c.append(cols)
+    return np.concatenate(o), np.concatenate(c)
+
+
+@pytest.mark.parametrize("idx,ptr", IDX_COMBOS)
+@pytest.mark.parametrize("inner", [255, 256, 257, 512, 2047, 2048, 2049, 4096, 4097])
+def test_scan_seams_over_inner(hip, inner, idx, ptr):
+    """the histogram is scanned over `inner`: one below, on and one above the scan's 256-thread and 2048-element tiles (and
+    the 256-thread grids of the indptr kernels); the first and the last column are occupied"""
+    n_rows = 3 + inner % 2
+    o, c = rows_over_inner(n_rows, inner, min(inner, 300), [0, inner - 1], seed=inner)
+    gip, _, _ = check_conversion(csr_from_cells(n_rows, inner, o, c, inner + 1, idx, ptr), idx, ptr)
+    assert int(gip[1]) >= 2 and int(gip[-1]) - int(gip[-2]) >= 2 and int(gip[-1]) == o.size   # first and last row hold them
+
+
+def test_scan_third_level_over_inner(hip):
+    """inner = 2^21 + 4097 = 1027 scan tiles: scan_sums_kernel goes round its loop twice and carries the first 1024 block
+    sums into the second round; entries on both sides of element 2^21"""
+    inner = (1 << 21) + 4097
+    forced = [0, (1 << 21) - 1, 1 << 21, (1 << 21) + 1, inner - 1]
+    o, c = rows_over_inner(3, inner, 4000, forced, seed=5)
+    gip, _, _ = check_conversion(csr_from_cells(3, inner, o, c, 6), np.uint64, np.uint64)
+    for j in forced:
+        assert int(gip[j + 1]) - int(gip[j]) >= 2              # rows 0 and 2 hold them
+    assert int(gip[1 << 21]) > 0 and int(gip[-1]) == o.size
+
+
+@pytest.mark.parametrize("idx,ptr", [(np.uint64, np.uint64), (np.uint32, np.uint32)])
+def test_hub_column_over_three_bitmap_windows(hip, idx, ptr):
+    """a column of ~350 k entries over 2 * 2^19 + 5000 rows: the workgroup kernel walks three 2^19-row bitmap windows, with
+    entries on the last row of a window and the first two of the next; beside it a second long column and a short one"""
+    w = 1 << 19
+    rows = 2 * w + 5000
+    c1 = np.unique(np.concatenate([np.arange(0, rows, 3), [w - 1, w, w + 1, 2 * w - 1, 2 * w, 2 * w + 1, rows - 1]]))
+    c0 = np.arange(5, rows, 7)
+    c2 = np.arange(0, rows, 1500)
+    assert c0.size > 1024 and 1 < c2.size <= 1024
+    o = np.concatenate([c0, c1, c2])
+    c = np.repeat([0, 1, 2], [c0.size, c1.size, c2.size])
+    gip, gix, _ = check_conversion(csr_from_cells(rows, 3, o, c, 8, idx, ptr), idx, ptr)
+    assert gip.tolist() == [0, c0.size, c0.size + c1.size, o.size]
+    assert np.array_equal(gix, np.concatenate([c0, c1, c2]).astype(idx))
+
+
+def check_slice(m, d, storage, start, end):
+    from sprs_amd import _ffi
+    (outer, inner), ip, ix, dt = m
+    fresh_blocks()
+    s = d.slice_outer(start, end)
+    shape, gip, gix, gdt = s.to_host()
+    n = end - start
+    lo, hi = int(ip[start]), int(ip[end])
+    assert s.storage() == storage and tuple(shape) == ((n, inner) if storage == _ffi.CSR else (inner, n))
+    assert gip.dtype == ip.dtype and gix.dtype == ix.dtype and gip.size == n + 1 and s.nnz() == hi - lo
+    assert int(gip[0]) == 0 and np.array_equal(gip.astype(np.int64), ip[start:end + 1].astype(np.int64) - lo)
+    assert np.array_equal(gix, ix[lo:hi]) and np.array_equal(gdt.view(np.uint64), dt[lo:hi].view(np.uint64))
+
+
+@pytest.mark.parametrize("idx,ptr", IDX_COMBOS)
+@pytest.mark.parametrize("k", [255, 256, 257, 512])
+def test_slice_outer_seams(hip, k, idx, ptr):
+    """slices of k outer slices: k + 1 indptr entries on both sides of the 256-thread grid of the rebase kernel"""
+    from sprs_amd import _ffi
+    outer, inner = k + 40, 50
+    lens = np.random.default_rng(k).integers(0, 9, outer)
+    lens[[7, 12, 20, outer - 1]] = 0                            # empty outer slices at the cuts below
+    lens[[6, 8, 11, 13, 19, 21]] = 3
+    m = ragged_csr(lens, inner, seed=k + 1, idx=idx, ptr=ptr, positive=False)
+    for storage in (_ffi.CSR, _ffi.CSC):
+        d = dev(((outer, inner) if storage == _ffi.CSR else (inner, outer),) + m[1:], storage=storage)
+        for start, end in [(7, 7 + k), (0, outer), (0, k), (outer - k, outer), (k, k), (0, 0), (outer, outer),
+                           (7, 13), (8, 12), (12, 20), (13, 21), (12, 13)]:
+            check_slice(m, d, storage, start, end)
