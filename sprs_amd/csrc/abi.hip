@@ -560,7 +560,13 @@ int32_t sprs_hip_bicgstab_f64(sprs_hip_csmat *a, const double *x0_dev, const dou
     if (n && (!x0_dev || !b_dev || !x_dev)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL vector");
     if (x_dev == x0_dev || x_dev == b_dev) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "x_dev may not alias x0_dev / b_dev");
     if (n == 0) {
-        if (info) *info = sprs_hip_bicgstab_info{0, 0, 0, 0.0, 0.0, 1};
+        // what solve() does with empty vectors (bicgstab.rs:158-172): every norm is sqrt(0) = 0.  Without an iteration the loop
+        // falls through to Err; otherwise the first step's err = 0 passes any tol > 0, the hard restart confirms it: Ok after
+        // one iteration and one hard restart.  With tol <= 0 (or NaN) nothing passes and the iterations run out: Err.
+        // (|rho| / err^2 = 0 / 0 is below no threshold: no soft restart.)
+        const bool passes = max_iter > 0 && 0.0 < tol;
+        const uint64_t it = passes ? 1 : max_iter;
+        if (info) *info = sprs_hip_bicgstab_info{it, 0, passes ? 1ull : 0ull, 0.0, 0.0, passes ? 1 : 0};
         return SPRS_HIP_OK;
     }
     return bicgstab_f64(a, x0_dev, b_dev, n, tol, max_iter, soft_restart_threshold, x_dev, info, (hipStream_t)stream);
