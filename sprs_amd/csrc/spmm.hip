@@ -463,7 +463,7 @@ __global__ __launch_bounds__(MM_BLOCK) void spmm_stream_fixup_kernel(const PTR *
         }
     }
     uint64_t todo = __ballot(is_long && j == 0);
-    while (todo) {
+    while (todo) {                                       // (at most one turn: a wave owns G <= 8 consecutive boundaries, a long row spans more than FIX_SPAN = 8 tiles)
         const int src = __ffsll((unsigned long long)todo) - 1;
         todo &= todo - 1;
         const uint64_t lt = __shfl(t, src, WAVE), ltb = __shfl(tb, src, WAVE), lr = __shfl(r, src, WAVE);
@@ -669,9 +669,12 @@ int32_t spmm_impl(sprs_hip_csmat *a, const double *rhs, uint64_t k, uint64_t ld_
     if (a->nnz == 0) {
         // nothing stored: the operator form is all zeros (csmat.rs:2004), the accumulate form leaves `out` alone
         if (!acc) {
-            if (cs_out != 1) SPRS_TRY_HIP(hipMemset2DAsync(out, cs_out * sizeof(double), 0, a->rows * sizeof(double), k, stream));   // column-major: k columns of `rows` doubles
-            else if (ld_out == k) SPRS_TRY_HIP(hipMemsetAsync(out, 0, a->rows * k * sizeof(double), stream));
-            else SPRS_TRY_HIP(hipMemset2DAsync(out, ld_out * sizeof(double), 0, k * sizeof(double), a->rows, stream));
+            // (one row or one column is contiguous whatever the other stride says: the column-major 1 x k result of the operator
+            // form has cs_out == rows == 1 and ld_out == 1, which is no pitch for rows of k doubles)
+            if (cs_out == 1 && (ld_out == k || a->rows == 1)) SPRS_TRY_HIP(hipMemsetAsync(out, 0, a->rows * k * sizeof(double), stream));
+            else if (ld_out == 1 && (cs_out == a->rows || k == 1)) SPRS_TRY_HIP(hipMemsetAsync(out, 0, a->rows * k * sizeof(double), stream));
+            else if (cs_out == 1) SPRS_TRY_HIP(hipMemset2DAsync(out, ld_out * sizeof(double), 0, k * sizeof(double), a->rows, stream));
+            else SPRS_TRY_HIP(hipMemset2DAsync(out, cs_out * sizeof(double), 0, a->rows * sizeof(double), k, stream));   // column-major: k columns of `rows` doubles
         }
         return SPRS_HIP_OK;
     }

@@ -379,7 +379,11 @@ hipError_t hipMalloc(void **p, size_t bytes) {
     if (base == MAP_FAILED) return hipErrorOutOfMemory;
     mprotect((char *)base + data, page, PROT_NONE);
     char *ptr = (char *)base + (data - b16);
-    memset(base, 0xFF, data);                       // "device" memory is never zero by accident
+    // "device" memory is never zero by accident.  HIPEMU_POISON=<byte> fills with another byte: a value that a kernel forgot to
+    // write can be harmless as all-ones (an index past every bound) and wrong as zero
+    static const char *poison_env = getenv("HIPEMU_POISON");
+    static const int poison = poison_env ? (int)(strtol(poison_env, nullptr, 0) & 0xff) : 0xFF;
+    memset(base, poison, data);
     std::lock_guard<std::mutex> g(g_alloc_mu);
     g_allocs[ptr] = Alloc{base, data + page, bytes};
     *p = ptr;
@@ -414,6 +418,7 @@ hipError_t hipMemsetD32Async(hipDeviceptr_t dst, int v, size_t count, hipStream_
     return hipSuccess;
 }
 hipError_t hipMemset2DAsync(void *dst, size_t pitch, int v, size_t width, size_t height, hipStream_t) {
+    if (width > pitch) return hipErrorInvalidValue;  // (as the runtime does)
     for (size_t r = 0; r < height; ++r) memset((char *)dst + r * pitch, v, width);
     return hipSuccess;
 }

@@ -65,12 +65,19 @@ def test_gauss_seidel_sweep_in_the_emulator(emu_lib, order):
 
 def test_spmm_stream_kernel_in_the_emulator(emu_lib):
     """the entry-stream SpMM kernel (tiles of 256 entries, rows by marks + max-scan, runs per lane group, fix-up of the rows that
-    cross tiles) at its seams, and the reference's golden dense products, on the CPU"""
+    cross tiles) at its seams, and the reference's golden dense products, on the CPU; and the exact-arithmetic seam cases of all
+    four summation modes — the small ones at one index width pair, the 65 k-entry tile-count cases at k = 8 with rows after the
+    crossing row, the chunk kernel's grid cap.  (The rows kernel's grid cap takes 25 - 140 s per case here and runs on the
+    device only.)  The tile-count case with ntiles = 256 runs once more on ZERO-filled blocks: a tile_row[ntiles] that nobody
+    wrote acts as `rows` while it is all-ones."""
     env = dict(os.environ, SPRS_HIP_LIBRARY=emu_lib)
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_spmm_gpu.py"), "-x", "-q", "-m", "gpu",
-                        "-k", "stream_tiles or golden or ragged", "-p", "no:cacheprovider"], cwd=ROOT, env=env, capture_output=True, text=True,
-                       timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
+    sel = ("stream_tiles or golden or ragged or chunk_grid_cap or (launch_seams and rows-after-8-uint32-uint32)"
+           " or (exact and uint64-uint64 and not launch_seams and not rows_grid_cap)")
+    for sel, extra in ((sel, {}), ("launch_seams and 65536-rows-after-8-uint32-uint32", {"HIPEMU_POISON": "0"})):
+        r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_spmm_gpu.py"), "-x", "-q", "-m", "gpu",
+                            "-k", sel, "-p", "no:cacheprovider"], cwd=ROOT, env=dict(env, **extra), capture_output=True, text=True,
+                           timeout=900)
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
 
 
 def test_differential_fuzzer_in_the_emulator(emu_lib):
