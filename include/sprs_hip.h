@@ -537,6 +537,36 @@ int32_t sprs_hip_csmat_transform_paq(const sprs_hip_csmat *m, const sprs_hip_per
  * copy when p.is_identity() — the elementwise test, so a stored permutation equal to 0..dim counts.  Otherwise as above. */
 int32_t sprs_hip_csmat_transform_papt(const sprs_hip_csmat *m, const sprs_hip_perm *p, sprs_hip_csmat **out, void *stream);
 
+/* ---- construction (sprs/src/sparse/kronecker.rs, construct.rs) -----------------------------------------------------------
+ * New owning handles assembled on the device; indptr, indices and value bits are the reference's.  All operands of one call
+ * must declare the same index and indptr widths (the reference's one I / Iptr): SPRS_HIP_STORAGE_MISMATCH otherwise.  The
+ * result takes them.  `stream` as for the binops: the kernels run there and the result is complete on return; an operand
+ * that has to change its storage first goes through sprs_hip_csmat_to_other_storage (null stream, after a wait for `stream`).
+ * *out is written on success only.
+ *
+ * kronecker_product (kronecker.rs:50-99): the result has a's storage (b is converted when it has the other one); outer slice
+ * ia * outer(b) + ib holds the products of the stored entries of slice ia of a and slice ib of b in stored order, index
+ * ai * inner(b) + bi, value av * bv — one multiply, nothing dropped.  SPRS_HIP_INDEX_OVERFLOW, decided by SHAPE before
+ * anything is allocated: a shape product that overflows 64 bits, inner(a) * inner(b) - 1 that does not fit the index width,
+ * nnz(a) * nnz(b) that does not fit the indptr width.  (The reference panics only when a STORED index does not fit.) */
+int32_t sprs_hip_csmat_kronecker_f64(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat **out, void *stream);
+/* same_storage_fast_stack (construct.rs:10-45): the n matrices one after the other along their outer axis, in their storage.
+ * `mats` is a host array of n handles.  In the reference's order: n == 0 SPRS_HIP_INVALID_ARG "Empty stacking list", unequal
+ * inner dimensions SPRS_HIP_DIM_MISMATCH "Dimension mismatch", unequal storages SPRS_HIP_STORAGE_MISMATCH "Storage mismatch". */
+int32_t sprs_hip_csmat_same_storage_fast_stack(const sprs_hip_csmat **mats, uint64_t n, sprs_hip_csmat **out, void *stream);
+/* vstack / hstack (construct.rs:48-81): the fast stack of the CSR / CSC forms of the operands; the result is always CSR for
+ * vstack and CSC for hstack.  Errors as above (unequal column / row counts are "Dimension mismatch"). */
+int32_t sprs_hip_csmat_vstack(const sprs_hip_csmat **mats, uint64_t n, sprs_hip_csmat **out, void *stream);
+int32_t sprs_hip_csmat_hstack(const sprs_hip_csmat **mats, uint64_t n, sprs_hip_csmat **out, void *stream);
+/* bmat (construct.rs:94-160): `blocks` is a host array of super_rows * super_cols handles, row-major, NULL = None (a zero block
+ * of the super-row's largest row count by the super-column's largest column count).  The result is CSR.  In the reference's
+ * order: no super-row or no super-column SPRS_HIP_INVALID_ARG "Empty stacking list", a super-row of NULLs "Empty bmat row", a
+ * super-column of NULLs "Empty bmat col" (both SPRS_HIP_INVALID_ARG), then SPRS_HIP_DIM_MISMATCH "Dimension mismatch" as the
+ * reference's hstack of every super-row and vstack of the results find it: the present blocks of a super-row must have equal
+ * row counts, and the super-rows equal TOTAL column counts — a block's column offset is the sum of the ACTUAL column counts to
+ * its left in its own super-row (a NULL counts the super-column's maximum), so [2 | 3] over [3 | 2] columns is accepted. */
+int32_t sprs_hip_csmat_bmat(const sprs_hip_csmat **blocks, uint64_t super_rows, uint64_t super_cols, sprs_hip_csmat **out, void *stream);
+
 /* ---- row-sharded SpMV over the GPUs of one node (one process per GPU, RCCL over xGMI) ----
  * The reference has no distributed code; the shard is its slice_outer (slicing.rs:65-89) with a rebased indptr
  * (indptr.rs:206-214): rank g owns rows [row_starts[g], row_starts[g+1]) and a full replica of x; one exchange, an

@@ -517,6 +517,51 @@ inline DeviceCsMat transform_mat_papt(const DeviceCsMat &mat, const DevicePerm &
 }
 }  // namespace permutation
 
+// sprs::kronecker_product (kronecker.rs:50-99) and sprs::sparse::construct (construct.rs:10-160) on device handles.  The
+// reference's panics arrive as exceptions with its text; kronecker_product refuses by shape (SPRS_HIP_INDEX_OVERFLOW) what
+// the reference refuses by stored index.
+namespace construct {
+namespace detail {
+inline std::vector<const sprs_hip_csmat *> handles(const std::vector<const DeviceCsMat *> &mats) {
+    std::vector<const sprs_hip_csmat *> h;
+    for (const DeviceCsMat *m : mats) h.push_back(m ? m->handle() : nullptr);
+    return h;
+}
+}  // namespace detail
+// the result has the storage of a; nothing is dropped
+inline DeviceCsMat kronecker_product(const DeviceCsMat &a, const DeviceCsMat &b, void *stream = nullptr) {
+    sprs_hip_csmat *c = nullptr;
+    check(sprs_hip_csmat_kronecker_f64(a.handle(), b.handle(), &c, stream));
+    return DeviceCsMat(c);
+}
+inline DeviceCsMat same_storage_fast_stack(const std::vector<const DeviceCsMat *> &mats, void *stream = nullptr) {
+    std::vector<const sprs_hip_csmat *> h = detail::handles(mats);
+    sprs_hip_csmat *c = nullptr;
+    check(sprs_hip_csmat_same_storage_fast_stack(h.data(), h.size(), &c, stream));
+    return DeviceCsMat(c);
+}
+inline DeviceCsMat vstack(const std::vector<const DeviceCsMat *> &mats, void *stream = nullptr) {   // always CSR
+    std::vector<const sprs_hip_csmat *> h = detail::handles(mats);
+    sprs_hip_csmat *c = nullptr;
+    check(sprs_hip_csmat_vstack(h.data(), h.size(), &c, stream));
+    return DeviceCsMat(c);
+}
+inline DeviceCsMat hstack(const std::vector<const DeviceCsMat *> &mats, void *stream = nullptr) {   // always CSC
+    std::vector<const sprs_hip_csmat *> h = detail::handles(mats);
+    sprs_hip_csmat *c = nullptr;
+    check(sprs_hip_csmat_hstack(h.data(), h.size(), &c, stream));
+    return DeviceCsMat(c);
+}
+// blocks row-major, super_rows x super_cols, nullptr = None; the result is CSR
+inline DeviceCsMat bmat(const std::vector<const DeviceCsMat *> &blocks, uint64_t super_rows, uint64_t super_cols, void *stream = nullptr) {
+    if (blocks.size() != super_rows * super_cols) throw std::invalid_argument("Dimension mismatch");
+    std::vector<const sprs_hip_csmat *> h = detail::handles(blocks);
+    sprs_hip_csmat *c = nullptr;
+    check(sprs_hip_csmat_bmat(h.data(), super_rows, super_cols, &c, stream));
+    return DeviceCsMat(c);
+}
+}  // namespace construct
+
 // TriMatI<f64, usize> (sparse/triplet.rs:26-48) with the device assembly of `to_csr` (triplet.rs:270-276 ->
 // triplet_iter.rs:127-224: rows sorted, duplicates summed).  No dedicated kernel: with n triplets the matrix
 // is the product R * E of R (rows x n, one 1 per column at the triplet's row) and E (n x cols, one value per

@@ -235,6 +235,17 @@ extern "C" {
     pub fn sprs_hip_csmat_transform_papt(
         m: *const sprs_hip_csmat, p: *const sprs_hip_perm, out: *mut *mut sprs_hip_csmat, stream: *mut c_void,
     ) -> i32;
+    pub fn sprs_hip_csmat_kronecker_f64(
+        a: *const sprs_hip_csmat, b: *const sprs_hip_csmat, out: *mut *mut sprs_hip_csmat, stream: *mut c_void,
+    ) -> i32;
+    pub fn sprs_hip_csmat_same_storage_fast_stack(
+        mats: *mut *const sprs_hip_csmat, n: u64, out: *mut *mut sprs_hip_csmat, stream: *mut c_void,
+    ) -> i32;
+    pub fn sprs_hip_csmat_vstack(mats: *mut *const sprs_hip_csmat, n: u64, out: *mut *mut sprs_hip_csmat, stream: *mut c_void) -> i32;
+    pub fn sprs_hip_csmat_hstack(mats: *mut *const sprs_hip_csmat, n: u64, out: *mut *mut sprs_hip_csmat, stream: *mut c_void) -> i32;
+    pub fn sprs_hip_csmat_bmat(
+        blocks: *mut *const sprs_hip_csmat, super_rows: u64, super_cols: u64, out: *mut *mut sprs_hip_csmat, stream: *mut c_void,
+    ) -> i32;
     pub fn sprs_hip_triplets_to_cs(
         rows: u64, cols: u64, n: u64, row_inds_dev: *const c_void, col_inds_dev: *const c_void, in_idx_bytes: i32,
         data_dev: *const f64, storage: i32, out_idx_bytes: i32, out_iptr_bytes: i32, out: *mut *mut sprs_hip_csmat,

@@ -784,3 +784,61 @@ pub mod permutation {
         DeviceCsMat { h }
     }
 }
+
+/// Twins of `sprs::kronecker_product` (kronecker.rs:50-99) and of `sprs::sparse::construct` (construct.rs:10-160) on device
+/// handles: same names, same argument order, the reference's panic texts.  One departure: `kronecker_product` panics by SHAPE
+/// (inner(a) * inner(b) - 1 or nnz(a) * nnz(b) beyond the index types) where the reference panics on a stored index.
+pub mod construct {
+    use super::{check, sys, DeviceCsMat};
+
+    fn handles(mats: &[&DeviceCsMat]) -> Vec<*const sys::sprs_hip_csmat> {
+        mats.iter().map(|m| m.h as *const sys::sprs_hip_csmat).collect()
+    }
+
+    /// `kronecker_product`: the result has the storage of `a`; nothing is dropped.
+    pub fn kronecker_product(a: &DeviceCsMat, b: &DeviceCsMat) -> DeviceCsMat {
+        let mut h: *mut sys::sprs_hip_csmat = std::ptr::null_mut();
+        unsafe { check(sys::sprs_hip_csmat_kronecker_f64(a.h, b.h, &mut h, std::ptr::null_mut())) };
+        DeviceCsMat { h }
+    }
+
+    /// `same_storage_fast_stack` (construct.rs:10-45).
+    pub fn same_storage_fast_stack(mats: &[&DeviceCsMat]) -> DeviceCsMat {
+        let mut hs = handles(mats);
+        let mut h: *mut sys::sprs_hip_csmat = std::ptr::null_mut();
+        unsafe { check(sys::sprs_hip_csmat_same_storage_fast_stack(hs.as_mut_ptr(), hs.len() as u64, &mut h, std::ptr::null_mut())) };
+        DeviceCsMat { h }
+    }
+
+    /// `vstack` (construct.rs:48-63): always CSR.
+    pub fn vstack(mats: &[&DeviceCsMat]) -> DeviceCsMat {
+        let mut hs = handles(mats);
+        let mut h: *mut sys::sprs_hip_csmat = std::ptr::null_mut();
+        unsafe { check(sys::sprs_hip_csmat_vstack(hs.as_mut_ptr(), hs.len() as u64, &mut h, std::ptr::null_mut())) };
+        DeviceCsMat { h }
+    }
+
+    /// `hstack` (construct.rs:66-81): always CSC.
+    pub fn hstack(mats: &[&DeviceCsMat]) -> DeviceCsMat {
+        let mut hs = handles(mats);
+        let mut h: *mut sys::sprs_hip_csmat = std::ptr::null_mut();
+        unsafe { check(sys::sprs_hip_csmat_hstack(hs.as_mut_ptr(), hs.len() as u64, &mut h, std::ptr::null_mut())) };
+        DeviceCsMat { h }
+    }
+
+    /// `bmat` (construct.rs:94-160): `None` is a zero block.  The ragged list panics here with "Dimension mismatch", between
+    /// "Empty stacking list" and "Empty bmat row" as in the reference; the C entry only sees rectangles.
+    pub fn bmat<'a, Row: AsRef<[Option<&'a DeviceCsMat>]>>(mats: &[Row]) -> DeviceCsMat {
+        assert_ne!(mats.len(), 0, "Empty stacking list");
+        let super_cols = mats[0].as_ref().len();
+        assert_ne!(super_cols, 0, "Empty stacking list");
+        assert!(mats.iter().all(|r| r.as_ref().len() == super_cols), "Dimension mismatch");
+        let mut hs: Vec<*const sys::sprs_hip_csmat> = mats
+            .iter()
+            .flat_map(|r| r.as_ref().iter().map(|m| m.map_or(std::ptr::null(), |m| m.h as *const sys::sprs_hip_csmat)))
+            .collect();
+        let mut h: *mut sys::sprs_hip_csmat = std::ptr::null_mut();
+        unsafe { check(sys::sprs_hip_csmat_bmat(hs.as_mut_ptr(), mats.len() as u64, super_cols as u64, &mut h, std::ptr::null_mut())) };
+        DeviceCsMat { h }
+    }
+}

@@ -116,6 +116,11 @@ SIGNATURES = {
     "sprs_hip_perm_mul_vec_f64": (i32, [vp, vp, vp, u64, vp]),
     "sprs_hip_csmat_transform_paq": (i32, [vp, vp, vp, P(vp), vp]),
     "sprs_hip_csmat_transform_papt": (i32, [vp, vp, P(vp), vp]),
+    "sprs_hip_csmat_kronecker_f64": (i32, [vp, vp, P(vp), vp]),
+    "sprs_hip_csmat_same_storage_fast_stack": (i32, [P(vp), u64, P(vp), vp]),
+    "sprs_hip_csmat_vstack": (i32, [P(vp), u64, P(vp), vp]),
+    "sprs_hip_csmat_hstack": (i32, [P(vp), u64, P(vp), vp]),
+    "sprs_hip_csmat_bmat": (i32, [P(vp), u64, u64, P(vp), vp]),
     "sprs_hip_set_option": (i32, [C.c_char_p, i64]),
     "sprs_hip_get_option": (i32, [C.c_char_p, P(i64)]),
 }

@@ -3,6 +3,7 @@
 // functions, raw device buffers, options.  Handles are made and released in handle.hpp, where the pool lives; results arrive
 // here inside their owners and are released to the caller's raw pointer in the extern "C" function.  Kernels live in the other
 // translation units.
+#include <algorithm>
 #include <cstdarg>
 #include <cstring>
 #include <vector>
@@ -1382,6 +1383,189 @@ int32_t sprs_hip_csmat_transform_papt(const sprs_hip_csmat *m, const sprs_hip_pe
     OwnedCsmat res;
     SPRS_TRY(csmat_permute(m, ident ? nullptr : p->perm, ident ? nullptr : p->perm_inv, res, (hipStream_t)stream));
     return finish_result(res, m, out);
+}
+
+}  // extern "C"
+
+// ---- construction (kronecker.rs, construct.rs); kernels in construct.hpp --------------------------------------------------------
+
+// the one I / Iptr of the reference's signatures
+static int32_t same_index_types(const sprs_hip_csmat *a, const sprs_hip_csmat *b, const char *where) {
+    if (a->user_iptr_bytes() != b->user_iptr_bytes() || a->user_idx_bytes() != b->user_idx_bytes())
+        SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "operands must share index types (%s)", where);
+    return SPRS_HIP_OK;
+}
+
+static bool mul_overflows(uint64_t x, uint64_t y, uint64_t *prod) { return __builtin_mul_overflow(x, y, prod); }
+
+// the form of m in `storage`: itself, or a to_other_storage() copy kept in `keep`.  The conversion runs on the null stream: what
+// the caller's stream still has to write into m comes first.
+static int32_t in_storage(const sprs_hip_csmat *m, int32_t storage, std::vector<OwnedCsmat> &keep, void *stream, const sprs_hip_csmat **out) {
+    *out = m;
+    if (m->storage == storage) return SPRS_HIP_OK;
+    if (stream) SPRS_TRY_HIP(hipStreamSynchronize((hipStream_t)stream));
+    OwnedCsmat conv;
+    SPRS_TRY(convert_checked(m, conv));
+    *out = conv.get();
+    keep.push_back(std::move(conv));
+    return SPRS_HIP_OK;
+}
+
+// what a stacked result must fit, tested before anything is allocated: I::from_usize on the inner dimension, Iptr::from_usize
+// on the nnz, at the widths the operands declare
+static int32_t stack_fits(const sprs_hip_csmat *like, uint64_t inner, uint64_t nnz) {
+    if (inner && inner - 1 > width_max(like->user_idx_bytes()))
+        SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "Index type is not large enough to hold the number of rows requested (required %llu)",
+                  (unsigned long long)inner);
+    if (nnz > width_max(like->user_iptr_bytes()))
+        SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "Index type is not large enough to hold the nnz of the result (%llu)", (unsigned long long)nnz);
+    return SPRS_HIP_OK;
+}
+
+// same_storage_fast_stack (construct.rs:19-45) on n >= 0 handles
+static int32_t fast_stack(const sprs_hip_csmat *const *mats, uint64_t n, sprs_hip_csmat **out, void *stream) {
+    if (n == 0) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "Empty stacking list");
+    const uint64_t inner = mats[0]->inner();
+    for (uint64_t k = 0; k < n; ++k)
+        if (mats[k]->inner() != inner) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    const int32_t storage = mats[0]->storage;
+    for (uint64_t k = 0; k < n; ++k)
+        if (mats[k]->storage != storage) SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "Storage mismatch");
+    std::vector<StackItem> items(n);
+    std::vector<uint64_t> outer_of(n);
+    uint64_t outer = 0, nnz = 0;
+    for (uint64_t k = 0; k < n; ++k) {
+        items[k] = {mats[k], k, 0};
+        outer_of[k] = mats[k]->outer();
+        if (__builtin_add_overflow(outer, outer_of[k], &outer) || __builtin_add_overflow(nnz, mats[k]->nnz, &nnz))
+            SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "the stacked dimensions overflow 64 bits");
+    }
+    SPRS_TRY(stack_fits(mats[0], inner, nnz));
+    const bool csr = storage == SPRS_HIP_CSR;
+    OwnedCsmat res;
+    SPRS_TRY(csmat_stack(items, outer_of, storage, csr ? outer : inner, csr ? inner : outer, mats[0]->iptr_bytes, mats[0]->idx_bytes, res,
+                         (hipStream_t)stream));
+    SPRS_TRY(inherit_declared_widths(res.get(), mats[0]));
+    *out = res.release();
+    return SPRS_HIP_OK;
+}
+
+// the argument checks the three list entries share
+static int32_t stack_args(const sprs_hip_csmat *const *mats, uint64_t n, sprs_hip_csmat **out) {
+    if (!out || (n && !mats)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    for (uint64_t k = 0; k < n; ++k) {
+        if (!mats[k]) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle in the stacking list");
+        SPRS_TRY(same_index_types(mats[0], mats[k], "construct.rs:10-17"));
+    }
+    return SPRS_HIP_OK;
+}
+
+// vstack / hstack (construct.rs:48-81): every operand in `storage`, then the fast stack
+static int32_t stack_in(const sprs_hip_csmat *const *mats, uint64_t n, int32_t storage, sprs_hip_csmat **out, void *stream) {
+    SPRS_TRY(stack_args(mats, n, out));
+    std::vector<OwnedCsmat> keep;
+    std::vector<const sprs_hip_csmat *> forms(n);
+    for (uint64_t k = 0; k < n; ++k) SPRS_TRY(in_storage(mats[k], storage, keep, stream, &forms[k]));
+    return fast_stack(forms.data(), n, out, stream);
+}
+
+extern "C" {
+
+int32_t sprs_hip_csmat_kronecker_f64(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat **out, void *stream) {
+    clear_error();
+    if (!a || !b || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    SPRS_TRY(same_index_types(a, b, "kronecker.rs:50-58"));
+    // b in a's storage has the inner dimension b has along a's inner axis
+    const uint64_t inner_a = a->inner(), inner_b = a->storage == SPRS_HIP_CSR ? b->cols : b->rows;
+    uint64_t rows, cols, inner, nnz;
+    if (mul_overflows(a->rows, b->rows, &rows) || mul_overflows(a->cols, b->cols, &cols) || rows == UINT64_MAX || cols == UINT64_MAX)
+        SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "the shape of the Kronecker product overflows 64 bits");
+    (void)mul_overflows(inner_a, inner_b, &inner);
+    if (inner && inner - 1 > width_max(a->user_idx_bytes()))
+        SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "Index type is not large enough to hold %llu", (unsigned long long)(inner - 1));
+    if (mul_overflows(a->nnz, b->nnz, &nnz) || nnz > width_max(a->user_iptr_bytes()) || nnz > (UINT64_MAX >> 1))
+        SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "Index type is not large enough to hold the nnz of the result (%llu x %llu)",
+                  (unsigned long long)a->nnz, (unsigned long long)b->nnz);
+    std::vector<OwnedCsmat> keep;
+    const sprs_hip_csmat *bf = nullptr;
+    SPRS_TRY(in_storage(b, a->storage, keep, stream, &bf));
+    OwnedCsmat res;
+    SPRS_TRY(csmat_kronecker_f64(a, bf, res, (hipStream_t)stream));
+    SPRS_TRY(inherit_declared_widths(res.get(), a));
+    *out = res.release();
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_csmat_same_storage_fast_stack(const sprs_hip_csmat **mats, uint64_t n, sprs_hip_csmat **out, void *stream) {
+    clear_error();
+    SPRS_TRY(stack_args(mats, n, out));
+    return fast_stack(mats, n, out, stream);
+}
+
+int32_t sprs_hip_csmat_vstack(const sprs_hip_csmat **mats, uint64_t n, sprs_hip_csmat **out, void *stream) {
+    clear_error();
+    return stack_in(mats, n, SPRS_HIP_CSR, out, stream);
+}
+
+int32_t sprs_hip_csmat_hstack(const sprs_hip_csmat **mats, uint64_t n, sprs_hip_csmat **out, void *stream) {
+    clear_error();
+    return stack_in(mats, n, SPRS_HIP_CSC, out, stream);
+}
+
+int32_t sprs_hip_csmat_bmat(const sprs_hip_csmat **blocks, uint64_t super_rows, uint64_t super_cols, sprs_hip_csmat **out, void *stream) {
+    clear_error();
+    if (!out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    if (super_rows == 0 || super_cols == 0) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "Empty stacking list");   // construct.rs:105-108
+    uint64_t cells;
+    if (!blocks || mul_overflows(super_rows, super_cols, &cells)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    auto at = [&](uint64_t i, uint64_t j) { return blocks[i * super_cols + j]; };
+    const sprs_hip_csmat *first = nullptr;
+    for (uint64_t c = 0; c < cells && !first; ++c) first = blocks[c];
+    for (uint64_t c = 0; c < cells; ++c)
+        if (blocks[c]) SPRS_TRY(same_index_types(first, blocks[c], "construct.rs:94-102"));
+    for (uint64_t i = 0; i < super_rows; ++i) {     // construct.rs:116-119
+        bool any = false;
+        for (uint64_t j = 0; j < super_cols; ++j) any = any || at(i, j);
+        if (!any) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "Empty bmat row");
+    }
+    for (uint64_t j = 0; j < super_cols; ++j) {     // construct.rs:120-123
+        bool any = false;
+        for (uint64_t i = 0; i < super_rows; ++i) any = any || at(i, j);
+        if (!any) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "Empty bmat col");
+    }
+    // the shapes of the None elements (construct.rs:126-142)
+    std::vector<uint64_t> rows_per_row(super_rows, 0), cols_per_col(super_cols, 0);
+    for (uint64_t i = 0; i < super_rows; ++i)
+        for (uint64_t j = 0; j < super_cols; ++j)
+            if (at(i, j)) {
+                rows_per_row[i] = std::max(rows_per_row[i], at(i, j)->rows);
+                cols_per_col[j] = std::max(cols_per_col[j], at(i, j)->cols);
+            }
+    // hstack of every super-row (rows equal: its inner-dimension check), vstack of the results (total columns equal)
+    std::vector<StackItem> items;
+    uint64_t total_rows = 0, total_cols = 0, nnz = 0;
+    for (uint64_t i = 0; i < super_rows; ++i) {
+        uint64_t off = 0;
+        for (uint64_t j = 0; j < super_cols; ++j) {
+            const sprs_hip_csmat *m = at(i, j);
+            if (m && m->rows != rows_per_row[i]) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+            if (m) items.push_back({m, i, off});
+            if (__builtin_add_overflow(off, m ? m->cols : cols_per_col[j], &off) || (m && __builtin_add_overflow(nnz, m->nnz, &nnz)))
+                SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "the stacked dimensions overflow 64 bits");
+        }
+        if (i == 0) total_cols = off;
+        if (off != total_cols) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+        if (__builtin_add_overflow(total_rows, rows_per_row[i], &total_rows))
+            SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "the stacked dimensions overflow 64 bits");
+    }
+    SPRS_TRY(stack_fits(first, total_cols, nnz));
+    std::vector<OwnedCsmat> keep;
+    for (StackItem &it : items) SPRS_TRY(in_storage(it.m, SPRS_HIP_CSR, keep, stream, &it.m));
+    OwnedCsmat res;
+    SPRS_TRY(csmat_stack(items, rows_per_row, SPRS_HIP_CSR, total_rows, total_cols, first->iptr_bytes, first->idx_bytes, res, (hipStream_t)stream));
+    SPRS_TRY(inherit_declared_widths(res.get(), first));
+    *out = res.release();
+    return SPRS_HIP_OK;
 }
 
 }  // extern "C"

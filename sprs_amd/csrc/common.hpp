@@ -9,6 +9,7 @@
 #include <mutex>
 #include <string>
 #include <unordered_map>
+#include <vector>
 
 #include "../../include/sprs_hip.h"
 
@@ -108,6 +109,7 @@ constexpr bool DEVTOOLS = false;
     X(binop_tile, 2048, 2048, 2048, 0)  /* slots (entries of both operands) per workgroup of the sparse +, -, elementwise * kernels (binop.hpp): fixed, published so that tests can place tile edges */ \
     X(perm_tile, 2048, 2048, 2048, 0)   /* result entries per workgroup of the outer-permutation copy kernel (perm.hpp): fixed, published so that tests can place tile edges */ \
     X(perm_cap, 4096, 4096, 4096, 0)    /* longest row a relabelling permutation sorts in LDS by one workgroup (perm.hpp); longer rows go through the radix sort: fixed, published for the tests */ \
+    X(construct_tile, 2048, 2048, 2048, 0) /* result entries (Kronecker product) / block entries (stacking) per workgroup of the construction kernels (construct.hpp): fixed, published so that tests can place tile edges */ \
     X(pool, 1, 0, 1, 0)                 /* keep released result blocks (>= 1 MiB) for the next result instead of hipFree */        \
     X(pool_max_bytes, 128ll << 30, 0, INT64_MAX, 0) /* cap on the bytes the pool may hold */
 
@@ -420,6 +422,15 @@ int32_t csmat_permute(const sprs_hip_csmat *m, const void *o, const void *g, Own
 int32_t perm_build_inverse(sprs_hip_perm *p, bool validate, hipStream_t stream);
 int32_t perm_is_identity(const sprs_hip_perm *p, int32_t *flag, hipStream_t stream);
 int32_t perm_mul_vec_f64(const sprs_hip_perm *p, const double *x, double *y, hipStream_t stream);
+// construct.hpp (compiled in convert.hip): operands of equal storage and index widths; complete on `stream` at return
+int32_t csmat_kronecker_f64(const sprs_hip_csmat *a, const sprs_hip_csmat *b, OwnedCsmat &out, hipStream_t stream);
+// the block assembly behind the four stacking functions: the present blocks by super-row, each with the shift of its inner indices
+struct StackItem {
+    const sprs_hip_csmat *m;
+    uint64_t srow, inner_off;
+};
+int32_t csmat_stack(const std::vector<StackItem> &items, const std::vector<uint64_t> &outer_of, int32_t storage, uint64_t rows, uint64_t cols,
+                    int32_t iptr_bytes, int32_t idx_bytes, OwnedCsmat &out, hipStream_t stream);
 // bicgstab.hip
 int32_t bicgstab_f64(sprs_hip_csmat *a, const double *x0, const double *b, uint64_t n, double tol, uint64_t max_iter,
                      double soft_restart_threshold, double *x, sprs_hip_bicgstab_info *info, hipStream_t stream);
