@@ -53,6 +53,22 @@ def test_spmv_band_kernels_in_the_emulator(emu_lib):
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
 
 
+def test_spmv_tile_and_sliced_plans_in_the_emulator(emu_lib):
+    """the nnz-tile kernel with its head / carry fix-up, the XCD-sliced plan (classify, fill, count, scatter, per-slice tiles and
+    carries, the reduce over eight partials), the column relabelling and the per-tile column sort of sprs_amd/csrc/spmv.hip, on
+    the exact-arithmetic seam cases of tests/test_spmv_seams_gpu.py, whole (under a minute here); the cases that exist for a
+    launch-grid size or a torch stream skip themselves: they run on the device only.  The plain-tile cases run once more with the
+    waves of a workgroup scheduled in reverse: which wave appends to longlist first, and which one takes which long segment, must
+    not matter."""
+    env = dict(os.environ, SPRS_HIP_LIBRARY=emu_lib)
+    for sel, extra in (("", {}), ("plain_tile_seams and uint64-uint64", {"HIPEMU_WAVE_ORDER": "reverse"})):
+        r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_spmv_seams_gpu.py"), "-x", "-q", "-m", "gpu",
+                            "-k", sel, "-p", "no:cacheprovider"], cwd=ROOT, env=dict(env, **extra), capture_output=True, text=True,
+                           timeout=900)
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
+        assert " passed" in r.stdout and " failed" not in r.stdout
+
+
 @pytest.mark.parametrize("order", ["default", "reverse", "rotate"])
 def test_gauss_seidel_sweep_in_the_emulator(emu_lib, order):
     """the sync-free sweep kernel (rows in level order, values handed from wave to wave through the next iterate) on the
