@@ -382,7 +382,7 @@ int32_t sprs_hip_csmat_spmv_plan_info(const sprs_hip_csmat *m, int32_t *kind, ui
     if (pl.built) {
         if (pl.band) {
             k = 3;
-            bytes = band_plan_bytes(pl.band);
+            bytes = band_plan_bytes(pl.band.get());
         } else if (pl.xcs) {
             k = 2;
             bytes = pl.main.nnz * (8 + (uint64_t)pl.idx_bytes);
@@ -433,20 +433,17 @@ int32_t sprs_hip_spmv_f64_host(uint64_t rows, uint64_t cols, const void *indptr,
     if (!indptr) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
     OwnedCsmat m;
     SPRS_TRY(csmat_upload(m, SPRS_HIP_CSR, rows, cols, indptr, iptr_bytes, indices, idx_bytes, data, 0));
-    double *dx = nullptr, *dy = nullptr;
-    int32_t st = sprs_hip_malloc((void **)&dx, x_len * 8);
-    if (st == SPRS_HIP_OK) st = sprs_hip_malloc((void **)&dy, y_len * 8);
-    if (st == SPRS_HIP_OK) st = sprs_hip_memcpy_h2d(dx, x, x_len * 8);
-    if (st == SPRS_HIP_OK && accumulate) st = sprs_hip_memcpy_h2d(dy, y, y_len * 8);
+    DevBuf dx, dy;
+    SPRS_TRY_HIP(dx.alloc(x_len ? x_len * 8 : 8));
+    SPRS_TRY_HIP(dy.alloc(y_len ? y_len * 8 : 8));
+    SPRS_TRY(sprs_hip_memcpy_h2d(dx.p, x, x_len * 8));
+    if (accumulate) SPRS_TRY(sprs_hip_memcpy_h2d(dy.p, y, y_len * 8));
     // one multiply, then the handle goes: nothing would amortise a re-laid-out copy of the matrix (the banded plan takes
     // ~0.1 s to build on R-MAT 10M for a 1 ms SpMV), so this entry multiplies on the plain nnz-tiled plan
     m->one_shot = true;
-    if (st == SPRS_HIP_OK) st = sprs_hip_spmv_f64(m.get(), dx, x_len, dy, y_len, accumulate, nullptr);
-    if (st == SPRS_HIP_OK) st = sprs_hip_synchronize(nullptr);
-    if (st == SPRS_HIP_OK) st = sprs_hip_memcpy_d2h(y, dy, y_len * 8);
-    (void)hipFree(dx);
-    (void)hipFree(dy);
-    return st;         // (m goes with this scope: releasing a handle leaves the error state alone)
+    SPRS_TRY(sprs_hip_spmv_f64(m.get(), dx.as<double>(), x_len, dy.as<double>(), y_len, accumulate, nullptr));
+    SPRS_TRY(sprs_hip_synchronize(nullptr));
+    return sprs_hip_memcpy_d2h(y, dy.p, y_len * 8);   // (the vectors and m go with this scope: releasing them leaves the error state alone)
 }
 
 int32_t sprs_hip_spmm_rowmaj_f64(const sprs_hip_csmat *a, const double *rhs_dev, uint64_t rhs_rows, uint64_t k,

@@ -120,87 +120,6 @@ struct Options {
 };
 Options &options();
 
-// ---- SpMV plan ---------------------------------------------------------------
-constexpr int XCS_SLICES = 8;      // one slice of x lines per XCD (each XCD has a private 4 MiB L2)
-
-// One CSR piece the tile kernel runs over.
-struct CsrPiece {
-    void *indptr = nullptr;        // device; PTR of the handle for `main`, uint64 for slices
-    void *indices = nullptr;       // device
-    double *data = nullptr;        // device
-    uint16_t *pos = nullptr;       // device, plan copies only: tile-local origin of each entry (tiles sorted by column)
-    uint64_t rows = 0, nnz = 0, ntiles = 0;
-    uint64_t *tile_row = nullptr;  // device, ntiles + 1: first row starting at/after tile c
-    bool owns = false;             // arrays allocated by the plan (copies), not borrowed from the handle
-};
-
-struct SpmvScratch {               // per stream: nothing in here is shared between in-flight SpMVs
-    double *carry_main = nullptr;
-    double *carry_slices = nullptr;
-    double *partial = nullptr;     // XCS_SLICES x n_long partial row sums
-    double *xp = nullptr;          // x in the plan's column labelling (relabelled plans)
-};
-
-struct BandPlan;                   // spmv_band.hip
-
-struct SpmvPlan {
-    bool built = false;
-    bool light = false;            // built as the plain tile index although a copy plan would apply (first multiply of the handle): rebuilt at the next one
-    bool xcs = false;
-    BandPlan *band = nullptr;      // banded plan: when set, nothing else below is used
-    uint64_t opt_sig = 0;          // hash of the option values the plan was built with (plan_signature, spmv.hip)
-    uint32_t tile = 0;             // nnz per tile
-    int idx_bytes = 8;             // width of the column ids the kernels read (handle's, or 4 for plan copies)
-    CsrPiece main;                 // the whole matrix (plain plan) or its short rows (sliced plan)
-    CsrPiece slice[XCS_SLICES];    // long rows, entries whose x line hashes to s, rows = n_long
-    uint64_t slice_tile_off[XCS_SLICES + 1] = {0};
-    uint64_t n_long = 0;
-    uint64_t *long_rows = nullptr; // device: original row of long row j
-    uint32_t *perm = nullptr;      // device, cols entries: plan label of column j (relabelled plans), else null
-    uint64_t cols = 0;
-    void *slab = nullptr;          // backing store of all plan-owned arrays
-    std::unordered_map<void *, SpmvScratch> scratch;
-    void release();
-};
-
-int32_t exclusive_scan_u64(const uint64_t *in, uint64_t *out, uint64_t n, hipStream_t stream);   // scan.hip
-
-// ---- SpMM plan: rows cut into chunks of <= 512 entries (spmm.hip) -------------------------------
-struct SpmmPlan {
-    bool built = false;
-    uint64_t nchunks = 0, n_multi = 0, long_row = 0;
-    uint64_t *first_chunk = nullptr;   // device, rows + 1
-    uint64_t *chunk_row = nullptr;     // device, nchunks
-    uint64_t *multi_rows = nullptr;    // device, rows spanning several chunks
-    uint64_t *tile_row = nullptr;      // device, ntiles + 1: the row that holds entry t * 256 (entry-stream kernel)
-    uint64_t ntiles = 0;
-    bool stream = false;               // built for the entry-stream kernel (no chunk lists then)
-    std::unordered_map<void *, std::pair<double *, uint64_t>> partial;   // per stream: buffer, bytes
-    std::unordered_map<void *, std::pair<double *, uint64_t>> relaid;    // per stream: the re-laid-out copy of the rhs (option spmm_relayout)
-    void release();
-};
-
-// ---- Gauss-Seidel plan: the rows in dependency-level order (gauss_seidel.hip) ---------------------
-struct GsPlan {
-    bool built = false;
-    uint32_t *order = nullptr;         // device, rows entries: row swept at position q (levels ascending, rows ascending inside a level)
-    uint64_t nlevels = 0;
-    uint64_t no_diag_row = UINT64_MAX; // first row without a stored diagonal entry (the reference's diag.unwrap() panics there)
-    uint64_t chain_tried = 0;          // stride the band schedule was last checked for (0: never) ...
-    bool chain_ok = false;             // ... and whether every dependency fits it (gs_band_check_kernel)
-    void release();
-};
-
-// ---- sparse-vector products: per-handle temporaries (csvec.hpp) ------------------------------------
-struct CsvecScratch {
-    uint32_t *bits = nullptr;          // device, ceil(n / 32): presence bitmap of v's indices
-    double *vals = nullptr;            // device, n: v's values at their indices (read only where the bit is set; never cleared)
-    double *sums = nullptr;            // device, outer: the dot of every kept outer slice
-    uint64_t *groups = nullptr;        // device: keep masks (ngroups) | counts (ngroups) | offsets (ngroups + 1) | overflow flag
-    uint64_t n = 0, nouter = 0;
-    void release();
-};
-
 // handle.hpp: result-block pool
 hipError_t pool_alloc(void **p, uint64_t bytes, uint64_t *cap, int device);
 // stream_ordered = true: the block was only ever touched by work enqueued on the NULL stream (or on streams joined back to it)
@@ -226,6 +145,154 @@ struct PoolBlock {
         dev = device;
         return pool_alloc(&p, bytes, &cap, dev);
     }
+};
+
+// A device block and its owner: a call's temporary, released when it goes out of scope, or an array that a plan or a
+// per-stream scratch derives from a handle's arrays, released with the plan.  Move-only.
+//   alloc:        a private block (hipMalloc), released with hipFree.
+//   alloc_pooled: a block of the pool, handed back in null-stream order (pool_free above); legal only for work ordered on the
+//                 null stream.
+//   alloc_for:    alloc_pooled for work on the null stream, alloc for any other.
+struct DevBuf {
+    void *p = nullptr;
+    uint64_t cap = 0;              // bytes of the block (a pooled one may be larger than what was asked for)
+    int dev = 0;
+    bool pooled = false;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap), dev(o.dev), pooled(o.pooled) { o.p = nullptr, o.cap = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        std::swap(p, o.p), std::swap(cap, o.cap), std::swap(dev, o.dev), std::swap(pooled, o.pooled);
+        return *this;
+    }
+    ~DevBuf() { release(); }
+    void release() {
+        if (p && pooled) pool_free(p, cap, dev, true);
+        else if (p) (void)hipFree(p);
+        p = nullptr, cap = 0;
+    }
+    hipError_t alloc(uint64_t bytes) {
+        release();
+        pooled = false;
+        if (!bytes) bytes = 16;
+        hipError_t e = hipMalloc(&p, bytes);
+        if (e == hipSuccess) cap = bytes;
+        else p = nullptr;
+        return e;
+    }
+    // a private block of at least `bytes` (0: none): the one held stays when it is large enough, else a new one replaces it
+    // (contents are not kept; on failure the owner is empty)
+    hipError_t reserve(uint64_t bytes) { return cap >= bytes ? hipSuccess : alloc(bytes); }
+    hipError_t alloc_pooled(uint64_t bytes) {
+        release();
+        pooled = true;
+        hipError_t e = hipGetDevice(&dev);
+        if (e != hipSuccess) return e;
+        return pool_alloc(&p, bytes ? bytes : 8, &cap, dev);
+    }
+    // the temporary of work on `stream`: only null-stream work may take (and hand back) a block of the pool
+    hipError_t alloc_for(hipStream_t stream, uint64_t bytes) { return stream == nullptr ? alloc_pooled(bytes) : alloc(bytes); }
+    template <typename T>
+    T *as() const { return (T *)p; }
+    uint64_t *u64() const { return (uint64_t *)p; }
+};
+
+// The arrays of a plan (or of a per-stream scratch) are DevBufs in one list that goes with it.  A new private block of `bytes`
+// at the end of `blocks`; `ptr` = its address as the typed pointer the kernels read (a borrowed array has only the pointer).
+template <typename T>
+hipError_t alloc_block(std::vector<DevBuf> &blocks, T *&ptr, uint64_t bytes) {
+    blocks.emplace_back();
+    hipError_t e = blocks.back().alloc(bytes);
+    ptr = (T *)blocks.back().p;
+    return e;
+}
+
+// ---- SpMV plan ---------------------------------------------------------------
+constexpr int XCS_SLICES = 8;      // one slice of x lines per XCD (each XCD has a private 4 MiB L2)
+
+// One CSR piece the tile kernel runs over: arrays of the handle (borrowed) or blocks of the plan (SpmvPlan::blocks).
+struct CsrPiece {
+    void *indptr = nullptr;        // device; PTR of the handle for `main`, uint64 for slices
+    void *indices = nullptr;       // device
+    double *data = nullptr;        // device
+    uint16_t *pos = nullptr;       // device, plan copies only: tile-local origin of each entry (tiles sorted by column)
+    uint64_t rows = 0, nnz = 0, ntiles = 0;
+    uint64_t *tile_row = nullptr;  // device, ntiles + 1: first row starting at/after tile c
+};
+
+struct SpmvScratch {               // per stream: nothing in here is shared between in-flight SpMVs
+    double *carry_main = nullptr;
+    double *carry_slices = nullptr;
+    double *partial = nullptr;     // XCS_SLICES x n_long partial row sums
+    double *xp = nullptr;          // x in the plan's column labelling (relabelled plans)
+    std::vector<DevBuf> blocks;    // the blocks behind the arrays above
+};
+
+struct BandPlan;                   // spmv_band.hip
+void band_free(BandPlan *bp);
+struct BandDelete {
+    void operator()(BandPlan *bp) const { band_free(bp); }
+};
+using OwnedBandPlan = std::unique_ptr<BandPlan, BandDelete>;   // (BandPlan is complete in spmv_band.hip only: band_free is its `delete`)
+
+// Everything the plan owns goes with it: a plan is reset by assigning a fresh one.
+struct SpmvPlan {
+    bool built = false;
+    bool light = false;            // built as the plain tile index although a copy plan would apply (first multiply of the handle): rebuilt at the next one
+    bool xcs = false;
+    OwnedBandPlan band;            // banded plan: when set, nothing else below is used
+    uint64_t opt_sig = 0;          // hash of the option values the plan was built with (plan_signature, spmv.hip)
+    uint32_t tile = 0;             // nnz per tile
+    int idx_bytes = 8;             // width of the column ids the kernels read (handle's, or 4 for plan copies)
+    CsrPiece main;                 // the whole matrix (plain plan) or its short rows (sliced plan)
+    CsrPiece slice[XCS_SLICES];    // long rows, entries whose x line hashes to s, rows = n_long
+    uint64_t slice_tile_off[XCS_SLICES + 1] = {0};
+    uint64_t n_long = 0;
+    uint64_t *long_rows = nullptr; // device: original row of long row j
+    uint32_t *perm = nullptr;      // device, cols entries: plan label of column j (relabelled plans), else null
+    DevBuf perm_block;             // the block behind perm (build_column_labels hands it over)
+    uint64_t cols = 0;
+    std::vector<DevBuf> blocks;    // the blocks behind every other array the plan made (tile rows, the copies of a sliced plan)
+    std::unordered_map<void *, SpmvScratch> scratch;
+};
+
+int32_t exclusive_scan_u64(const uint64_t *in, uint64_t *out, uint64_t n, hipStream_t stream);   // scan.hip
+
+// ---- SpMM plan: rows cut into chunks of <= 512 entries (spmm.hip) -------------------------------
+struct SpmmPlan {
+    bool built = false;
+    uint64_t nchunks = 0, n_multi = 0, long_row = 0;
+    uint64_t *first_chunk = nullptr;   // device, rows + 1
+    uint64_t *chunk_row = nullptr;     // device, nchunks
+    uint64_t *multi_rows = nullptr;    // device, rows spanning several chunks
+    uint64_t *tile_row = nullptr;      // device, ntiles + 1: the row that holds entry t * 256 (entry-stream kernel)
+    uint64_t ntiles = 0;
+    bool stream = false;               // built for the entry-stream kernel (no chunk lists then)
+    std::vector<DevBuf> blocks;        // the blocks behind the arrays above
+    std::unordered_map<void *, DevBuf> partial;   // per stream: the partial sums / carries of the kernels
+    std::unordered_map<void *, DevBuf> relaid;    // per stream: the re-laid-out copy of the rhs (option spmm_relayout)
+};
+
+// ---- Gauss-Seidel plan: the rows in dependency-level order (gauss_seidel.hip) ---------------------
+struct GsPlan {
+    bool built = false;
+    uint32_t *order = nullptr;         // device, rows entries: row swept at position q (levels ascending, rows ascending inside a level)
+    DevBuf order_block;                // the block behind order
+    uint64_t nlevels = 0;
+    uint64_t no_diag_row = UINT64_MAX; // first row without a stored diagonal entry (the reference's diag.unwrap() panics there)
+    uint64_t chain_tried = 0;          // stride the band schedule was last checked for (0: never) ...
+    bool chain_ok = false;             // ... and whether every dependency fits it (gs_band_check_kernel)
+};
+
+// ---- sparse-vector products: per-handle temporaries (csvec.hpp) ------------------------------------
+struct CsvecScratch {
+    uint32_t *bits = nullptr;          // device, ceil(n / 32): presence bitmap of v's indices
+    double *vals = nullptr;            // device, n: v's values at their indices (read only where the bit is set; never cleared)
+    double *sums = nullptr;            // device, outer: the dot of every kept outer slice
+    uint64_t *groups = nullptr;        // device: keep masks (ngroups) | counts (ngroups) | offsets (ngroups + 1) | overflow flag
+    uint64_t n = 0, nouter = 0;
+    std::vector<DevBuf> blocks;        // the blocks behind the arrays above
 };
 
 }  // namespace sprs_hip
@@ -290,44 +357,6 @@ struct sprs_hip_csmat {
 
 namespace sprs_hip {
 
-// A device temporary owned by one call, released when it goes out of scope.
-//   alloc:        a private block (hipMalloc), released with hipFree.
-//   alloc_pooled: a block of the pool, handed back in null-stream order (pool_free above); legal only for work ordered on the
-//                 null stream.
-//   alloc_for:    alloc_pooled for work on the null stream, alloc for any other.
-struct DevBuf {
-    void *p = nullptr;
-    uint64_t cap = 0;
-    int dev = 0;
-    bool pooled = false;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { release(); }
-    void release() {
-        if (p && pooled) pool_free(p, cap, dev, true);
-        else if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    hipError_t alloc(uint64_t bytes) {
-        release();
-        pooled = false;
-        return hipMalloc(&p, bytes ? bytes : 16);
-    }
-    hipError_t alloc_pooled(uint64_t bytes) {
-        release();
-        pooled = true;
-        hipError_t e = hipGetDevice(&dev);
-        if (e != hipSuccess) return e;
-        return pool_alloc(&p, bytes ? bytes : 8, &cap, dev);
-    }
-    // the temporary of work on `stream`: only null-stream work may take (and hand back) a block of the pool
-    hipError_t alloc_for(hipStream_t stream, uint64_t bytes) { return stream == nullptr ? alloc_pooled(bytes) : alloc(bytes); }
-    template <typename T>
-    T *as() const { return (T *)p; }
-    uint64_t *u64() const { return (uint64_t *)p; }
-};
-
 // Host copies run on the stream of the work around them and are complete when these return: a read-back sees every kernel
 // enqueued on that stream before it.  (A blocking copy would run on the null stream, which a hipStreamNonBlocking stream, as
 // every torch.cuda.Stream is, is not ordered with.)
@@ -374,9 +403,8 @@ using OwnedCsvec = std::unique_ptr<sprs_hip_csvec>;
 using OwnedPerm = std::unique_ptr<sprs_hip_perm>;
 
 // spmv_band.hip
-int32_t band_build(sprs_hip_csmat *a, hipStream_t stream, BandPlan **out);   // *out stays null when the plan does not apply
+int32_t band_build(sprs_hip_csmat *a, hipStream_t stream, OwnedBandPlan &out);   // out stays empty when the plan does not apply
 int32_t band_spmv(sprs_hip_csmat *a, BandPlan *bp, const double *x, double *y, bool accumulate, hipStream_t stream);
-void band_free(BandPlan *bp);
 uint64_t band_plan_bytes(const BandPlan *bp);
 // spmv.hip
 int32_t spmv_prepare(sprs_hip_csmat *a, hipStream_t stream);   // builds the full SpMV plan now (sprs_hip_csmat_prepare)

@@ -220,36 +220,24 @@ inline unsigned blocks_for(uint64_t items) { return (unsigned)((items + CV_BLOCK
 
 }  // namespace cv
 
-void CsvecScratch::release() {
-    auto drop = [](void *p) {
-        if (p) (void)hipFree(p);
-    };
-    drop(bits);
-    drop(vals);
-    drop(sums);
-    drop(groups);
-    *this = CsvecScratch();
-}
-
 // the per-handle temporaries of the products (the table of v, the slice sums, the group masks / counts / offsets), made at
 // the first product of the handle and kept until refresh / free
 static int32_t csvec_scratch(sprs_hip_csmat *m, uint64_t n) {
     CsvecScratch &s = m->cv;
     const uint64_t nouter = m->outer(), ngroups = (nouter + 63) / 64;
     if (s.bits && s.n == n && s.nouter == nouter) return SPRS_HIP_OK;
-    s.release();
-    s.n = n;
-    s.nouter = nouter;
+    s = CsvecScratch();
+    CsvecScratch t;                // complete before the handle takes it
+    t.n = n;
+    t.nouter = nouter;
     const uint64_t words = (n + 31) / 32;
-    hipError_t e = hipMalloc((void **)&s.bits, (words ? words : 1) * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&s.vals, (n ? n : 1) * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&s.sums, (nouter ? nouter : 1) * 8);
+    hipError_t e = alloc_block(t.blocks, t.bits, (words ? words : 1) * 4);
+    if (e == hipSuccess) e = alloc_block(t.blocks, t.vals, (n ? n : 1) * 8);
+    if (e == hipSuccess) e = alloc_block(t.blocks, t.sums, (nouter ? nouter : 1) * 8);
     // masks | counts | offsets (ngroups + 1) | overflow flag
-    if (e == hipSuccess) e = hipMalloc((void **)&s.groups, (3 * ngroups + 2) * 8);
-    if (e != hipSuccess) {
-        s.release();
-        return fail_hip(e, "csvec scratch");
-    }
+    if (e == hipSuccess) e = alloc_block(t.blocks, t.groups, (3 * ngroups + 2) * 8);
+    if (e != hipSuccess) return fail_hip(e, "csvec scratch");
+    s = std::move(t);
     return SPRS_HIP_OK;
 }
 

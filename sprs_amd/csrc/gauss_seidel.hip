@@ -36,16 +36,6 @@ namespace sprs_hip {
 
 int32_t radix_sort_pairs(uint64_t *keys, uint64_t *vals, uint64_t n, const std::vector<std::pair<int, int>> &fields, hipStream_t stream);   // sort.hip
 
-void GsPlan::release() {
-    if (order) (void)hipFree(order);
-    order = nullptr;
-    built = false;
-    nlevels = 0;
-    no_diag_row = UINT64_MAX;
-    chain_tried = 0;
-    chain_ok = false;
-}
-
 namespace {
 
 constexpr int GS_BLOCK = 256;
@@ -384,12 +374,13 @@ int32_t gs_plan_build(sprs_hip_csmat *a, GsPlan &pl) {
     int bits = 1;
     while (bits < 32 && (top >> bits) != 0u) ++bits;
     SPRS_TRY(radix_sort_pairs(keys.as<uint64_t>(), vals.as<uint64_t>(), n, {{0, bits}}, stream));       // stable: rows ascending inside a level
-    SPRS_TRY_HIP(hipMalloc((void **)&pl.order, (n ? n : 1) * sizeof(uint32_t)));
+    SPRS_TRY_HIP(pl.order_block.alloc((n ? n : 1) * sizeof(uint32_t)));
+    pl.order = pl.order_block.as<uint32_t>();
     if (n) {
         hipLaunchKernelGGL(gs_order_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const uint64_t *)vals.as<uint64_t>(), n, pl.order);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) {
-            pl.release();
+            pl = GsPlan();
             return fail_hip(e, "Gauss-Seidel level order");
         }
     }

@@ -211,11 +211,11 @@ int32_t copy_csmat(const sprs_hip_csmat *m, bool with_data, OwnedCsmat &out, hip
 // refresh, delete and BOTH numeric SpGEMM entries, which rewrite C's values in place (a stale CSC copy of C
 // would otherwise serve later products).
 void invalidate_caches(sprs_hip_csmat *m) {
-    m->plan.release();
-    m->mm.release();
-    m->gs.release();
-    m->tri_upper.release();
-    m->cv.release();
+    m->plan = SpmvPlan();
+    m->mm = SpmmPlan();
+    m->gs = GsPlan();
+    m->tri_upper = GsPlan();
+    m->cv = CsvecScratch();
     delete m->t_view;
     m->t_view = nullptr;
     delete m->as_other;

@@ -483,13 +483,13 @@ __global__ __launch_bounds__(MM_BLOCK) void spmm_stream_fixup_kernel(const PTR *
 template <typename PTR>
 int32_t build_spmm_plan(sprs_hip_csmat *a, bool stream_mode, hipStream_t stream) {
     SpmmPlan &pl = a->mm;
-    pl.release();
+    pl = SpmmPlan();
     pl.long_row = options().spmm_long_row >= 0 ? (uint64_t)options().spmm_long_row : LONG_ROW;
     pl.stream = stream_mode;
     const uint64_t rows = a->rows;
     if (stream_mode) {
         pl.ntiles = (a->nnz + ST_TILE - 1) / ST_TILE;
-        SPRS_TRY_HIP(hipMalloc((void **)&pl.tile_row, (pl.ntiles + 1) * 8));
+        SPRS_TRY_HIP(alloc_block(pl.blocks, pl.tile_row, (pl.ntiles + 1) * 8));
         hipLaunchKernelGGL(tile_rows_kernel<PTR>, dim3((unsigned)((pl.ntiles + 256) / 256)), dim3(256), 0, stream, (const PTR *)a->indptr,
                            rows, pl.ntiles, pl.tile_row);
         SPRS_TRY_HIP(hipGetLastError());
@@ -501,7 +501,7 @@ int32_t build_spmm_plan(sprs_hip_csmat *a, bool stream_mode, hipStream_t stream)
     SPRS_TRY_HIP(nch.alloc(rows * 8));
     SPRS_TRY_HIP(mflag.alloc(rows * 8));
     SPRS_TRY_HIP(mpos.alloc((rows + 1) * 8));
-    SPRS_TRY_HIP(hipMalloc((void **)&pl.first_chunk, (rows + 1) * 8));
+    SPRS_TRY_HIP(alloc_block(pl.blocks, pl.first_chunk, (rows + 1) * 8));
     hipLaunchKernelGGL(count_chunks_kernel<PTR>, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream,
                        (const PTR *)a->indptr, rows, pl.long_row, nch.u64(), mflag.u64());
     SPRS_TRY_HIP(hipGetLastError());
@@ -509,8 +509,8 @@ int32_t build_spmm_plan(sprs_hip_csmat *a, bool stream_mode, hipStream_t stream)
     SPRS_TRY(exclusive_scan_u64(mflag.u64(), mpos.u64(), rows, stream));
     SPRS_TRY_HIP(copy_to_host(&pl.nchunks, pl.first_chunk + rows, 8, stream));
     SPRS_TRY_HIP(copy_to_host(&pl.n_multi, mpos.u64() + rows, 8, stream));
-    SPRS_TRY_HIP(hipMalloc((void **)&pl.chunk_row, (pl.nchunks ? pl.nchunks : 1) * 8));
-    SPRS_TRY_HIP(hipMalloc((void **)&pl.multi_rows, (pl.n_multi ? pl.n_multi : 1) * 8));
+    SPRS_TRY_HIP(alloc_block(pl.blocks, pl.chunk_row, (pl.nchunks ? pl.nchunks : 1) * 8));
+    SPRS_TRY_HIP(alloc_block(pl.blocks, pl.multi_rows, (pl.n_multi ? pl.n_multi : 1) * 8));
     hipLaunchKernelGGL(fill_chunks_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, pl.first_chunk,
                        mpos.u64(), rows, pl.chunk_row, pl.multi_rows);
     SPRS_TRY_HIP(hipGetLastError());
@@ -628,15 +628,9 @@ int32_t spmm_impl(sprs_hip_csmat *a, const double *rhs, uint64_t k, uint64_t ld_
         SpmmPlan &pl = a->mm;
         const uint64_t kb = k < 64 ? k : 64;
         const uint64_t need = (stream_mode ? 2 * pl.ntiles : pl.n_multi ? pl.nchunks : 0) * kb * sizeof(double);
-        auto &slot = pl.partial[(void *)stream];
-        if (slot.second < need) {
-            if (slot.first) (void)hipFree(slot.first);
-            slot.first = nullptr;
-            slot.second = 0;
-            SPRS_TRY_HIP(hipMalloc((void **)&slot.first, need));
-            slot.second = need;
-        }
-        partial = slot.first;
+        DevBuf &slot = pl.partial[(void *)stream];
+        SPRS_TRY_HIP(slot.reserve(need));
+        partial = slot.as<double>();
         // the re-laid-out copy of the rhs (option spmm_relayout; auto: a rhs that is not row-major — a column of it is a separate
         // line per entry — or one of 256 MiB and more per column block with 24 and more gathers per row to pay for the copy:
         // R-MAT 4M x 32 2.55 -> 2.20 ms at k = 16, 1M x 16 0.32 -> 0.38 ms, profiles/r11zc)
@@ -651,19 +645,10 @@ int32_t spmm_impl(sprs_hip_csmat *a, const double *rhs, uint64_t k, uint64_t ld_
             const uint64_t rows_pad = (a->cols + RL_MASK) & ~(uint64_t)RL_MASK;
             const uint64_t kp = kb <= 8 ? 8 : kb <= 16 ? 16 : kb <= 32 ? 32 : 64;
             const uint64_t bytes = rows_pad * kp * sizeof(double);
-            auto &rs = pl.relaid[(void *)stream];
-            if (rs.second < bytes) {
-                if (rs.first) (void)hipFree(rs.first);
-                rs.first = nullptr;
-                rs.second = 0;
-                // (no room for a second copy of the rhs: the kernel gathers from the caller's, as with spmm_relayout = 2)
-                if (hipMalloc((void **)&rs.first, bytes) == hipSuccess) rs.second = bytes;
-                else {
-                    rs.first = nullptr;
-                    (void)hipGetLastError();
-                }
-            }
-            relaid = rs.first;
+            DevBuf &rs = pl.relaid[(void *)stream];
+            // (no room for a second copy of the rhs: the kernel gathers from the caller's, as with spmm_relayout = 2)
+            if (rs.reserve(bytes) != hipSuccess) (void)hipGetLastError();
+            relaid = rs.as<double>();
         }
     }
     if (a->nnz == 0) {
@@ -699,24 +684,6 @@ int32_t spmm_impl(sprs_hip_csmat *a, const double *rhs, uint64_t k, uint64_t ld_
 }
 
 }  // namespace
-
-void SpmmPlan::release() {
-    auto drop = [](void *p) {
-        if (p) (void)hipFree(p);
-    };
-    drop(first_chunk);
-    drop(chunk_row);
-    drop(multi_rows);
-    drop(tile_row);
-    first_chunk = chunk_row = multi_rows = tile_row = nullptr;
-    ntiles = 0;
-    for (auto &kv : partial) drop(kv.second.first);
-    partial.clear();
-    for (auto &kv : relaid) drop(kv.second.first);
-    relaid.clear();
-    nchunks = n_multi = 0;
-    built = false;
-}
 
 // General strides: element (r, j) of the rhs at rhs[r * rs_rhs + j * cs_rhs], of out at out[r * rs_out + j * cs_out] — row-major
 // operands have cs = 1, column-major ones rs = 1.  One kernel family serves the four layout pairs `&CsMat * &Array2` can meet

@@ -477,11 +477,11 @@ __global__ __launch_bounds__(BLOCK) void sort_tiles_kernel(CIDX *__restrict__ in
 // host side
 // ---------------------------------------------------------------------------
 template <typename PTR>
-static int32_t make_tile_rows(CsrPiece &pc, uint32_t TILE, hipStream_t stream) {
+static int32_t make_tile_rows(CsrPiece &pc, std::vector<DevBuf> &blocks, uint32_t TILE, hipStream_t stream) {
     pc.ntiles = (pc.nnz + TILE - 1) / TILE;
     if (!pc.ntiles) return SPRS_HIP_OK;
     if (pc.ntiles * XCS_SLICES > 0x7fffffffull) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "too many tiles for one launch");
-    SPRS_TRY_HIP(hipMalloc((void **)&pc.tile_row, (pc.ntiles + 1) * sizeof(uint64_t)));
+    SPRS_TRY_HIP(alloc_block(blocks, pc.tile_row, (pc.ntiles + 1) * sizeof(uint64_t)));
     const uint64_t n = pc.ntiles + 1;
     hipLaunchKernelGGL(build_tile_rows<PTR>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
                        (const PTR *)pc.indptr, pc.rows, pc.ntiles, TILE, pc.tile_row);
@@ -501,7 +501,8 @@ static int32_t build_sliced(sprs_hip_csmat *a, uint64_t nnz_short, uint64_t n_lo
     const Options &o = options();
     pl.cols = a->cols;
     if (o.spmv_relabel != 2 && a->cols <= 0xFFFFFFFFull && a->nnz) {
-        SPRS_TRY(build_column_labels<IDX>(ix, a->nnz, a->cols, stream, &pl.perm));
+        SPRS_TRY(build_column_labels<IDX>(ix, a->nnz, a->cols, stream, pl.perm_block));
+        pl.perm = pl.perm_block.as<uint32_t>();
     }
     // ---- short part + list of long rows --------------------------------------
     pl.xcs = true;
@@ -509,11 +510,10 @@ static int32_t build_sliced(sprs_hip_csmat *a, uint64_t nnz_short, uint64_t n_lo
     pl.idx_bytes = (int)sizeof(CIDX);
     pl.main.rows = rows;
     pl.main.nnz = nnz_short;
-    pl.main.owns = true;
-    SPRS_TRY_HIP(hipMalloc(&pl.main.indptr, (rows + 1) * sizeof(PTR)));
-    SPRS_TRY_HIP(hipMalloc(&pl.main.indices, (nnz_short ? nnz_short : 4) * sizeof(CIDX)));
-    SPRS_TRY_HIP(hipMalloc((void **)&pl.main.data, (nnz_short ? nnz_short : 2) * sizeof(double)));
-    SPRS_TRY_HIP(hipMalloc((void **)&pl.long_rows, n_long * sizeof(uint64_t)));
+    SPRS_TRY_HIP(alloc_block(pl.blocks, pl.main.indptr, (rows + 1) * sizeof(PTR)));
+    SPRS_TRY_HIP(alloc_block(pl.blocks, pl.main.indices, (nnz_short ? nnz_short : 4) * sizeof(CIDX)));
+    SPRS_TRY_HIP(alloc_block(pl.blocks, pl.main.data, (nnz_short ? nnz_short : 2) * sizeof(double)));
+    SPRS_TRY_HIP(alloc_block(pl.blocks, pl.long_rows, n_long * sizeof(uint64_t)));
     hipLaunchKernelGGL((xcs_fill_kernel<IDX, PTR, CIDX>), dim3((unsigned)((rows + 256) / 256)), dim3(256), 0, stream,
                        ip, ix, a->data, rows, long_flag.u64(), short_ptr.u64(), long_pos.u64(), (PTR *)pl.main.indptr,
                        (CIDX *)pl.main.indices, pl.main.data, pl.long_rows, pl.perm);
@@ -531,12 +531,11 @@ static int32_t build_sliced(sprs_hip_csmat *a, uint64_t nnz_short, uint64_t n_lo
     for (int s = 0; s < XCS_SLICES; ++s) {
         CsrPiece &sl = pl.slice[s];
         sl.rows = n_long;
-        sl.owns = true;
-        SPRS_TRY_HIP(hipMalloc(&sl.indptr, (n_long + 1) * sizeof(uint64_t)));
+        SPRS_TRY_HIP(alloc_block(pl.blocks, sl.indptr, (n_long + 1) * sizeof(uint64_t)));
         SPRS_TRY(exclusive_scan_u64(cnt.u64() + (uint64_t)s * n_long, (uint64_t *)sl.indptr, n_long, stream));
         SPRS_TRY_HIP(copy_to_host(&sl.nnz, (uint64_t *)sl.indptr + n_long, 8, stream));
-        SPRS_TRY_HIP(hipMalloc(&sl.indices, (sl.nnz ? sl.nnz : 4) * sizeof(CIDX)));
-        SPRS_TRY_HIP(hipMalloc((void **)&sl.data, (sl.nnz ? sl.nnz : 2) * sizeof(double)));
+        SPRS_TRY_HIP(alloc_block(pl.blocks, sl.indices, (sl.nnz ? sl.nnz : 4) * sizeof(CIDX)));
+        SPRS_TRY_HIP(alloc_block(pl.blocks, sl.data, (sl.nnz ? sl.nnz : 2) * sizeof(double)));
         so.ptr[s] = (const uint64_t *)sl.indptr;
         so.indices[s] = sl.indices;
         so.data[s] = sl.data;
@@ -545,16 +544,16 @@ static int32_t build_sliced(sprs_hip_csmat *a, uint64_t nnz_short, uint64_t n_lo
                        a->data, pl.long_rows, n_long, so, pl.perm);
     SPRS_TRY_HIP(hipGetLastError());
 
-    SPRS_TRY(make_tile_rows<PTR>(pl.main, pl.tile, stream));
+    SPRS_TRY(make_tile_rows<PTR>(pl.main, pl.blocks, pl.tile, stream));
     pl.slice_tile_off[0] = 0;
     for (int s = 0; s < XCS_SLICES; ++s) {
-        SPRS_TRY(make_tile_rows<uint64_t>(pl.slice[s], pl.tile, stream));
+        SPRS_TRY(make_tile_rows<uint64_t>(pl.slice[s], pl.blocks, pl.tile, stream));
         pl.slice_tile_off[s + 1] = pl.slice_tile_off[s] + pl.slice[s].ntiles;
     }
     if (options().spmv_sort_tiles) {
         auto sort_piece = [&](CsrPiece &pc) -> int32_t {
             if (!pc.ntiles) return SPRS_HIP_OK;
-            SPRS_TRY_HIP(hipMalloc((void **)&pc.pos, pc.nnz * sizeof(uint16_t) + 16));
+            SPRS_TRY_HIP(alloc_block(pl.blocks, pc.pos, pc.nnz * sizeof(uint16_t) + 16));
             const dim3 grid((unsigned)pc.ntiles), block(BLOCK);
             if (pl.tile == 2048)
                 hipLaunchKernelGGL((sort_tiles_kernel<CIDX, 2048>), grid, block, 0, stream, (CIDX *)pc.indices, pc.data,
@@ -580,49 +579,6 @@ static uint64_t plan_signature(const Options &o) {
     return h | 1ull;
 }
 
-// everything the plan owns goes back; the plan is as new
-void SpmvPlan::release() {
-    auto drop = [](void *p) {
-        if (p) (void)hipFree(p);
-    };
-    band_free(band);
-    band = nullptr;
-    drop(main.tile_row);
-    drop(main.pos);
-    if (main.owns) {
-        drop(main.indptr);
-        drop(main.indices);
-        drop(main.data);
-    }
-    main = CsrPiece();
-    for (auto &sl : slice) {
-        drop(sl.tile_row);
-        drop(sl.pos);
-        if (sl.owns) {
-            drop(sl.indptr);
-            drop(sl.indices);
-            drop(sl.data);
-        }
-        sl = CsrPiece();
-    }
-    drop(long_rows);
-    drop(slab);
-    drop(perm);
-    perm = nullptr;
-    long_rows = nullptr;
-    slab = nullptr;
-    for (auto &kv : scratch) {
-        drop(kv.second.carry_main);
-        drop(kv.second.carry_slices);
-        drop(kv.second.partial);
-        drop(kv.second.xp);
-    }
-    scratch.clear();
-    n_long = 0;
-    built = false;
-    xcs = false;
-}
-
 // light: the handle's first multiply — a plan that COPIES the matrix (banded, XCD-sliced) is not built yet unless the options
 // force it; pl.light then says that the next multiply should come back here.  A handle that multiplies once (`&a * &x` on a
 // temporary) never pays the ~0.1 s of a copy plan; one that iterates pays it at its second multiply.
@@ -630,7 +586,7 @@ template <typename IDX, typename PTR>
 static int32_t build_plan(sprs_hip_csmat *a, hipStream_t stream, bool light = false) {
     SpmvPlan &pl = a->plan;
     const Options &o = options();
-    pl.release();
+    pl = SpmvPlan();
     pl.opt_sig = plan_signature(o);
     pl.idx_bytes = (int)sizeof(IDX);
     pl.light = false;
@@ -649,13 +605,12 @@ static int32_t build_plan(sprs_hip_csmat *a, hipStream_t stream, bool light = fa
         if (auto_xcs) want = false;
     }
     if (want_band) {
-        const int32_t st = band_build(a, stream, &pl.band);
+        const int32_t st = band_build(a, stream, pl.band);
         // auto mode: a matrix the banded plan cannot be built for (its temporaries did not fit) keeps the plans below;
         // an explicit spmv_band = 1 reports the failure
         if (st == SPRS_HIP_OUT_OF_MEMORY && o.spmv_band == 0) {
             (void)hipGetLastError();
             clear_error();
-            pl.band = nullptr;
         } else if (st != SPRS_HIP_OK) {
             return st;
         }
@@ -692,8 +647,7 @@ static int32_t build_plan(sprs_hip_csmat *a, hipStream_t stream, bool light = fa
         pl.main.data = a->data;
         pl.main.rows = rows;
         pl.main.nnz = nnz;
-        pl.main.owns = false;
-        SPRS_TRY(make_tile_rows<PTR>(pl.main, pl.tile, stream));
+        SPRS_TRY(make_tile_rows<PTR>(pl.main, pl.blocks, pl.tile, stream));
     } else if (sizeof(IDX) == 8 && o.spmv_xcs_idx32 && a->cols <= 0xFFFFFFFFull) {
         // the plan's own copies hold 32-bit column ids: 12 instead of 16 bytes of stream per entry
         SPRS_TRY((build_sliced<IDX, PTR, uint32_t>(a, nnz_short, n_long, long_flag, short_ptr, long_pos, stream)));
@@ -708,16 +662,16 @@ static int32_t build_plan(sprs_hip_csmat *a, hipStream_t stream, bool light = fa
 static int32_t get_scratch(SpmvPlan &pl, hipStream_t stream, SpmvScratch **out) {
     auto it = pl.scratch.find((void *)stream);
     if (it == pl.scratch.end()) {
-        SpmvScratch sc;
-        if (pl.main.ntiles) SPRS_TRY_HIP(hipMalloc((void **)&sc.carry_main, pl.main.ntiles * sizeof(double)));
-        if (pl.perm) SPRS_TRY_HIP(hipMalloc((void **)&sc.xp, (pl.cols ? pl.cols : 1) * sizeof(double)));
+        SpmvScratch sc;                                // complete before it goes into the map: a failure on the way frees what it took
+        if (pl.main.ntiles) SPRS_TRY_HIP(alloc_block(sc.blocks, sc.carry_main, pl.main.ntiles * sizeof(double)));
+        if (pl.perm) SPRS_TRY_HIP(alloc_block(sc.blocks, sc.xp, (pl.cols ? pl.cols : 1) * sizeof(double)));
         if (pl.xcs) {
             const uint64_t nt = pl.slice_tile_off[XCS_SLICES];
-            SPRS_TRY_HIP(hipMalloc((void **)&sc.carry_slices, (nt ? nt : 1) * sizeof(double)));
+            SPRS_TRY_HIP(alloc_block(sc.blocks, sc.carry_slices, (nt ? nt : 1) * sizeof(double)));
             // partials, followed by the device copy of the per-slice argument table
             const uint64_t pbytes = XCS_SLICES * pl.n_long * sizeof(double);
             const uint64_t poff = (pbytes + 255) & ~255ull;
-            SPRS_TRY_HIP(hipMalloc((void **)&sc.partial, poff + sizeof(SlicedArgs)));
+            SPRS_TRY_HIP(alloc_block(sc.blocks, sc.partial, poff + sizeof(SlicedArgs)));
             // a slice without entries launches no tile, so nobody ever writes its partials: they must read as
             // zero (fresh hipMalloc memory usually does, recycled memory does not)
             SPRS_TRY_HIP(hipMemsetAsync(sc.partial, 0, poff, stream));
@@ -729,7 +683,7 @@ static int32_t get_scratch(SpmvPlan &pl, hipStream_t stream, SpmvScratch **out) 
             }
             SPRS_TRY_HIP(copy_to_device((uint8_t *)sc.partial + poff, &sa, sizeof sa, stream));
         }
-        it = pl.scratch.emplace((void *)stream, sc).first;
+        it = pl.scratch.emplace((void *)stream, std::move(sc)).first;
     }
     *out = &it->second;
     return SPRS_HIP_OK;
@@ -815,7 +769,7 @@ static int32_t launch_tiled(sprs_hip_csmat *a, const double *x, double *y, bool 
         if (!pl.band) SPRS_TRY(get_scratch(pl, stream, &sc));
     }
     const SpmvPlan &pl = a->plan;
-    if (pl.band) return band_spmv(a, pl.band, x, y, acc, stream);
+    if (pl.band) return band_spmv(a, pl.band.get(), x, y, acc, stream);
     const bool small_idx = pl.idx_bytes == 4;
     if (pl.tile == 2048) {
         if (small_idx) return launch_pieces<uint32_t, PTR, 2048>(a, sc, x, y, acc, stream);

@@ -336,13 +336,27 @@ __global__ void bp_tile_rows_kernel(const TileRowJob *__restrict__ jobs) {
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-struct BandScratch {        // per stream
+struct BandScratch {        // per stream; move-only: it owns its blocks, its stream and its events
     double *partial = nullptr, *carry = nullptr, *xp = nullptr;
     BandPiece *pieces = nullptr;
+    std::vector<DevBuf> blocks;                    // the blocks behind the arrays above
     // the gather-bound kernels (cold pieces, short rows: L2 -> L1 fills) run beside the HBM-bound hot kernel on a second stream
     hipStream_t aux = nullptr;
     hipEvent_t fork = nullptr, join = nullptr;
     hipEvent_t cold_done = nullptr;                // the cold pieces' partial sums are written (the short rows may still run)
+    BandScratch() = default;
+    BandScratch(BandScratch &&o) noexcept { *this = std::move(o); }
+    BandScratch &operator=(BandScratch &&o) noexcept {
+        std::swap(partial, o.partial), std::swap(carry, o.carry), std::swap(xp, o.xp), std::swap(pieces, o.pieces), std::swap(blocks, o.blocks);
+        std::swap(aux, o.aux), std::swap(fork, o.fork), std::swap(join, o.join), std::swap(cold_done, o.cold_done);
+        return *this;
+    }
+    ~BandScratch() {
+        if (cold_done) (void)hipEventDestroy(cold_done);
+        if (fork) (void)hipEventDestroy(fork);
+        if (join) (void)hipEventDestroy(join);
+        if (aux) (void)hipStreamDestroy(aux);
+    }
 };
 
 struct BandPlan {
@@ -379,59 +393,21 @@ struct BandPlan {
     std::vector<uint64_t> pair_off;
     std::unordered_map<void *, BandScratch> scratch;
     uint64_t bytes = 0;                            // HBM held by the plan (without scratch)
+    DevBuf perm_block;                             // the block behind perm (build_column_labels hands it over)
+    std::vector<DevBuf> blocks;                    // the blocks behind every other array above
 };
 
-void band_free(BandPlan *bp) {
-    if (!bp) return;
-    auto drop = [](void *p) {
-        if (p) (void)hipFree(p);
-    };
-    drop(bp->perm);
-    drop(bp->inv_hot);
-    drop(bp->long_rows);
-    drop(bp->vals_hot);
-    drop(bp->vals_cold);
-    drop(bp->cid_hot);
-    drop(bp->cid_cold);
-    drop(bp->rowidx_all);
-    drop(bp->tile_row_all);
-    drop(bp->segs);
-    drop(bp->hsegs);
-    drop(bp->wg_first);
-    drop(bp->rspills);
-    drop(bp->rsp_off);
-    drop(bp->spills_y);
-    drop(bp->wg_seg);
-    drop(bp->groups);
-    drop(bp->wmask);
-    drop(bp->wbase);
-    for (auto &kv : bp->scratch) {
-        drop(kv.second.partial);
-        drop(kv.second.carry);
-        drop(kv.second.xp);
-        drop(kv.second.pieces);
-        if (kv.second.cold_done) (void)hipEventDestroy(kv.second.cold_done);
-        if (kv.second.fork) (void)hipEventDestroy(kv.second.fork);
-        if (kv.second.join) (void)hipEventDestroy(kv.second.join);
-        if (kv.second.aux) (void)hipStreamDestroy(kv.second.aux);
-    }
-    delete bp;
-}
+void band_free(BandPlan *bp) { delete bp; }
 
 namespace {
 
-struct PlanGuard {
-    BandPlan *p;
-    ~PlanGuard() { band_free(p); }
-};
-
 template <typename IDX, typename PTR>
-int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, BandPlan **out) {
+int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, OwnedBandPlan &out) {
     const Options &o = options();
     const uint64_t rows = a->rows, cols = a->cols, nnz = a->nnz;
     const PTR *ip = (const PTR *)a->indptr;
     const IDX *ix = (const IDX *)a->indices;
-    *out = nullptr;
+    out.reset();
     if (rows >= 0xFFFFFFFFull || cols >= 0x7FFFFFFFull || !nnz) return SPRS_HIP_OK;   // bit 31 of a label flags a row start
     // rows with at least this many entries are "long" (cut into pieces)
     // (24 measured best on R-MAT 10M; a small matrix — fewer than ~400 hot tiles per CU, the `small` plans below — does better
@@ -463,8 +439,7 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, BandPlan **out) {
     if (o.spmv_band == 0 && (nnz - nnz_short) * 2 < nnz) return SPRS_HIP_OK;
     if (nnz - nnz_short >= 0xFFFFFFFFull || nnz_short >= 0xFFFFFFFFull) return SPRS_HIP_OK;   // 32-bit piece offsets
 
-    BandPlan *bp = new BandPlan();
-    PlanGuard guard{bp};
+    OwnedBandPlan bp(new BandPlan());
     bp->cols = cols;
     bp->xt_log2 = xt_log2;
     bp->cols_pad = (cols + XT - 1) / XT * XT + XT;
@@ -502,10 +477,11 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, BandPlan **out) {
 
     // ---- labels ---------------------------------------------------------------------------
     uint64_t nref = 0;
-    SPRS_TRY(build_column_labels<IDX>(ix, nnz, cols, stream, &bp->perm, &nref));
+    SPRS_TRY(build_column_labels<IDX>(ix, nnz, cols, stream, bp->perm_block, &nref));
+    bp->perm = bp->perm_block.as<uint32_t>();
     bp->nref = (uint32_t)nref;
     bp->hot_labels = (uint32_t)(map.hot_labels < bp->cols_pad ? map.hot_labels : bp->cols_pad);
-    SPRS_TRY_HIP(hipMalloc((void **)&bp->inv_hot, (nref + 4) * 4));
+    SPRS_TRY_HIP(alloc_block(bp->blocks, bp->inv_hot, (nref + 4) * 4));
     SPRS_TRY_HIP(hipMemsetAsync(bp->inv_hot, 0, (nref + 4) * 4, stream));
     hipLaunchKernelGGL(bp_inverse_kernel, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, stream, (const uint32_t *)bp->perm,
                        cols, bp->nref, bp->inv_hot);
@@ -513,7 +489,7 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, BandPlan **out) {
 
     // ---- short piece + list of long rows ------------------------------------------------------
     // cold arrays: [short piece | cold pieces], every piece starting at a multiple of 512 entries
-    SPRS_TRY_HIP(hipMalloc((void **)&bp->long_rows, n_long * 4));
+    SPRS_TRY_HIP(alloc_block(bp->blocks, bp->long_rows, n_long * 4));
 
     // ---- long rows: count per piece, scans, placement --------------------------------------------
     DevBuf cnt, nz, pos, pair, starts_d, pb_d;
@@ -625,20 +601,20 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, BandPlan **out) {
 
     // ---- arrays of the plan ----------------------------------------------------------------------
     const uint64_t hot_entries = hot_tiles * WT;
-    SPRS_TRY_HIP(hipMalloc((void **)&bp->vals_hot, (hot_entries + WT) * 8));
-    SPRS_TRY_HIP(hipMalloc((void **)&bp->cid_hot, (hot_entries + WT) * 2));
+    SPRS_TRY_HIP(alloc_block(bp->blocks, bp->vals_hot, (hot_entries + WT) * 8));
+    SPRS_TRY_HIP(alloc_block(bp->blocks, bp->cid_hot, (hot_entries + WT) * 2));
     SPRS_TRY_HIP(hipMemsetAsync(bp->vals_hot, 0, (hot_entries + WT) * 8, stream));
     SPRS_TRY_HIP(hipMemsetAsync(bp->cid_hot, 0, (hot_entries + WT) * 2, stream));
-    SPRS_TRY_HIP(hipMalloc((void **)&bp->vals_cold, (cold_ent + WT) * 8));
-    SPRS_TRY_HIP(hipMalloc((void **)&bp->cid_cold, (cold_ent + WT) * 4));
+    SPRS_TRY_HIP(alloc_block(bp->blocks, bp->vals_cold, (cold_ent + WT) * 8));
+    SPRS_TRY_HIP(alloc_block(bp->blocks, bp->cid_cold, (cold_ent + WT) * 4));
     // the padding of every piece — behind its last entry, and the gaps of the short piece — reads as (label `cols`, value 0):
     // xp[cols] is never written and stays 0.0, so a padding product is 0 * 0 whatever x holds
     SPRS_TRY_HIP(hipMemsetAsync(bp->vals_cold, 0, (cold_ent + WT) * 8, stream));
     SPRS_TRY_HIP(hipMemsetD32Async((hipDeviceptr_t)bp->cid_cold, (int)(uint32_t)cols, cold_ent + WT, stream));
     DevBuf ptr_all;                                                // entry offsets of the compact rows: only the build reads them
     SPRS_TRY_HIP(ptr_all.alloc((ptr_off + n_short_rows + 2) * 4));
-    SPRS_TRY_HIP(hipMalloc((void **)&bp->rowidx_all, (row_off + n_short_rows + 1) * 4));
-    SPRS_TRY_HIP(hipMalloc((void **)&bp->tile_row_all, (tile_off + 1) * 4));
+    SPRS_TRY_HIP(alloc_block(bp->blocks, bp->rowidx_all, (row_off + n_short_rows + 1) * 4));
+    SPRS_TRY_HIP(alloc_block(bp->blocks, bp->tile_row_all, (tile_off + 1) * 4));
     bp->bytes = (hot_entries + WT) * 10 + (cold_ent + WT) * 12 + (row_off + n_short_rows + tile_off) * 4 + cols * 4 + n_long * 4 +
                 ((uint64_t)bp->nref + 4) * 4;
     // short piece: its entries go straight into place (piece 0 of the cold arrays), its row lists are copied
@@ -665,8 +641,8 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, BandPlan **out) {
         bp->total_pairs = row_off;
         bp->np_pad = (NP + (uint32_t)RU - 1u) / (uint32_t)RU * (uint32_t)RU;
         const uint64_t slots = nwb * bp->np_pad;
-        SPRS_TRY_HIP(hipMalloc((void **)&bp->wmask, (slots + WAVE) * 8));
-        SPRS_TRY_HIP(hipMalloc((void **)&bp->wbase, (slots + WAVE) * 4));
+        SPRS_TRY_HIP(alloc_block(bp->blocks, bp->wmask, (slots + WAVE) * 8));
+        SPRS_TRY_HIP(alloc_block(bp->blocks, bp->wbase, (slots + WAVE) * 4));
         SPRS_TRY_HIP(hipMemsetAsync(bp->wmask, 0, (slots + WAVE) * 8, stream));
         SPRS_TRY_HIP(hipMemsetAsync(bp->wbase, 0, (slots + WAVE) * 4, stream));
         const uint64_t waves = nwb * NP;
@@ -776,8 +752,8 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, BandPlan **out) {
     }
     bp->nranges = nranges;
     bp->nsegs = (uint32_t)segs.size();
-    SPRS_TRY_HIP(hipMalloc((void **)&bp->segs, (segs.size() + 1) * sizeof(Seg)));
-    SPRS_TRY_HIP(hipMalloc((void **)&bp->wg_seg, wg_seg.size() * 4));
+    SPRS_TRY_HIP(alloc_block(bp->blocks, bp->segs, (segs.size() + 1) * sizeof(Seg)));
+    SPRS_TRY_HIP(alloc_block(bp->blocks, bp->wg_seg, wg_seg.size() * 4));
     if (!segs.empty()) SPRS_TRY_HIP(hipMemcpyAsync(bp->segs, segs.data(), segs.size() * sizeof(Seg), hipMemcpyHostToDevice, stream));
     SPRS_TRY_HIP(hipMemcpyAsync(bp->wg_seg, wg_seg.data(), wg_seg.size() * 4, hipMemcpyHostToDevice, stream));
     bp->bytes += segs.size() * sizeof(Seg);
@@ -795,9 +771,9 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, BandPlan **out) {
             wf[b].pad0 = wg_seg[b];
             wf[b].pad1 = wg_seg[b + 1];
         }
-        SPRS_TRY_HIP(hipMalloc((void **)&bp->wg_first, (wf.size() + 1) * sizeof(HotSeg)));
+        SPRS_TRY_HIP(alloc_block(bp->blocks, bp->wg_first, (wf.size() + 1) * sizeof(HotSeg)));
         SPRS_TRY_HIP(hipMemcpyAsync(bp->wg_first, wf.data(), wf.size() * sizeof(HotSeg), hipMemcpyHostToDevice, stream));
-        SPRS_TRY_HIP(hipMalloc((void **)&bp->hsegs, (hs.size() + 1) * sizeof(HotSeg)));
+        SPRS_TRY_HIP(alloc_block(bp->blocks, bp->hsegs, (hs.size() + 1) * sizeof(HotSeg)));
         SPRS_TRY_HIP(copy_to_device(bp->hsegs, hs.data(), hs.size() * sizeof(HotSeg), stream));   // (wf and hs go out of scope)
         bp->bytes += (hs.size() + wf.size()) * sizeof(HotSeg);
     }
@@ -821,7 +797,7 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, BandPlan **out) {
     bp->ngroups = (uint32_t)groups.size();
     bp->cold_blocks = blocks;
     if (bp->ngroups) {
-        SPRS_TRY_HIP(hipMalloc((void **)&bp->groups, groups.size() * sizeof(ColdGroup)));
+        SPRS_TRY_HIP(alloc_block(bp->blocks, bp->groups, groups.size() * sizeof(ColdGroup)));
         SPRS_TRY_HIP(hipMemcpyAsync(bp->groups, groups.data(), groups.size() * sizeof(ColdGroup), hipMemcpyHostToDevice, stream));
     }
     // ---- rows that run on from one range into the next: one record per run -----------------------------------------------
@@ -835,7 +811,7 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, BandPlan **out) {
         SPRS_TRY_HIP(hipMemsetAsync(cnt_d.p, 0, 8, stream));
         DevBuf sp_tmp;                                                                       // the long rows' records, as found (any order)
         SPRS_TRY_HIP(sp_tmp.alloc(((uint64_t)nranges + 1) * sizeof(Spill)));                 // at most one per range
-        SPRS_TRY_HIP(hipMalloc(&bp->spills_y, ((uint64_t)nranges + 1) * sizeof(Spill)));
+        SPRS_TRY_HIP(alloc_block(bp->blocks, bp->spills_y, ((uint64_t)nranges + 1) * sizeof(Spill)));
         hipLaunchKernelGGL(bp_spill_kernel, dim3((nranges + 255) / 256), dim3(256), 0, stream, (const Seg *)bp->segs, bp->nsegs, nranges,
                            (const BandPiece *)pcs_d.p, (const uint64_t *)poff_d.p, bp->nh, (const uint16_t *)bp->cid_hot,
                            (const uint32_t *)bp->cid_cold, (Spill *)bp->spills_y, (Spill *)sp_tmp.p,
@@ -863,8 +839,8 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, BandPlan **out) {
                 }
             }
             for (uint32_t w = 0; w < nwb; ++w) off[w + 1] += off[w];
-            SPRS_TRY_HIP(hipMalloc(&bp->rspills, recs.size() * sizeof(RSpill)));
-            SPRS_TRY_HIP(hipMalloc((void **)&bp->rsp_off, off.size() * 4));
+            SPRS_TRY_HIP(alloc_block(bp->blocks, bp->rspills, recs.size() * sizeof(RSpill)));
+            SPRS_TRY_HIP(alloc_block(bp->blocks, bp->rsp_off, off.size() * 4));
             SPRS_TRY_HIP(copy_to_device(bp->rspills, recs.data(), recs.size() * sizeof(RSpill), stream));
             SPRS_TRY_HIP(copy_to_device(bp->rsp_off, off.data(), off.size() * 4, stream));
             bp->bytes += recs.size() * sizeof(RSpill) + off.size() * 4;
@@ -885,28 +861,27 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, BandPlan **out) {
                 bp->hot_wgs, bp->nsegs, (unsigned)(8 * phases), (unsigned long long)cold_nnz, (unsigned long long)cold_pairs, bp->nranges, bp->nspills, bp->nspills_y,
                 (unsigned long long)nnz_short, (unsigned long long)nnz_short_padded, bp->bytes / 1e6);
     }
-    guard.p = nullptr;
-    *out = bp;
+    out = std::move(bp);
     return SPRS_HIP_OK;
 }
 
 int32_t band_scratch(BandPlan *bp, hipStream_t stream, BandScratch **out) {
     auto it = bp->scratch.find((void *)stream);
     if (it == bp->scratch.end()) {
-        BandScratch sc;
-        SPRS_TRY_HIP(hipMalloc((void **)&sc.partial, (bp->total_pairs + 1) * 8));   // every pair is written by every SpMV
-        SPRS_TRY_HIP(hipMalloc((void **)&sc.carry, ((uint64_t)bp->nranges + 1) * 8));
-        SPRS_TRY_HIP(hipMalloc((void **)&sc.xp, bp->cols_pad * 8));
+        BandScratch sc;                                // complete before it goes into the map: a failure on the way frees what it took
+        SPRS_TRY_HIP(alloc_block(sc.blocks, sc.partial, (bp->total_pairs + 1) * 8));   // every pair is written by every SpMV
+        SPRS_TRY_HIP(alloc_block(sc.blocks, sc.carry, ((uint64_t)bp->nranges + 1) * 8));
+        SPRS_TRY_HIP(alloc_block(sc.blocks, sc.xp, bp->cols_pad * 8));
         SPRS_TRY_HIP(hipMemsetAsync(sc.xp, 0, bp->cols_pad * 8, stream));      // the padding behind the last column is read into LDS
         std::vector<BandPiece> pcs = bp->host_pieces;
         for (uint32_t k = 0; k <= bp->npieces; ++k) pcs[k].out = k < bp->npieces ? sc.partial + bp->pair_off[k] : nullptr;
-        SPRS_TRY_HIP(hipMalloc((void **)&sc.pieces, pcs.size() * sizeof(BandPiece)));
+        SPRS_TRY_HIP(alloc_block(sc.blocks, sc.pieces, pcs.size() * sizeof(BandPiece)));
         SPRS_TRY_HIP(copy_to_device(sc.pieces, pcs.data(), pcs.size() * sizeof(BandPiece), stream));
         SPRS_TRY_HIP(hipStreamCreateWithFlags(&sc.aux, hipStreamNonBlocking));
         SPRS_TRY_HIP(hipEventCreateWithFlags(&sc.fork, hipEventDisableTiming));
         SPRS_TRY_HIP(hipEventCreateWithFlags(&sc.join, hipEventDisableTiming));
         SPRS_TRY_HIP(hipEventCreateWithFlags(&sc.cold_done, hipEventDisableTiming));
-        it = bp->scratch.emplace((void *)stream, sc).first;
+        it = bp->scratch.emplace((void *)stream, std::move(sc)).first;
     }
     *out = &it->second;
     return SPRS_HIP_OK;
@@ -914,7 +889,7 @@ int32_t band_scratch(BandPlan *bp, hipStream_t stream, BandScratch **out) {
 
 }  // namespace
 
-int32_t band_build(sprs_hip_csmat *a, hipStream_t stream, BandPlan **out) {
+int32_t band_build(sprs_hip_csmat *a, hipStream_t stream, OwnedBandPlan &out) {
     return dispatch_widths(a->idx_bytes, a->iptr_bytes, [&](auto i, auto p) {
         return band_build_t<typename decltype(i)::type, typename decltype(p)::type>(a, stream, out);
     });
@@ -974,14 +949,9 @@ int32_t band_spmv(sprs_hip_csmat *a, BandPlan *bp, const double *x, double *y, b
 #endif
         unsigned long long *prof = nullptr;
         if (DEVTOOLS && (options().spmv_band_debug & 16)) {
-            static unsigned long long *buf = nullptr;
-            static uint32_t cap = 0;
-            if (cap < bp->hot_wgs) {
-                if (buf) (void)hipFree(buf);
-                cap = bp->hot_wgs;
-                SPRS_TRY_HIP(hipMalloc((void **)&buf, (size_t)cap * 24));
-            }
-            prof = buf;
+            static DevBuf buf;
+            SPRS_TRY_HIP(buf.reserve((uint64_t)bp->hot_wgs * 24));
+            prof = buf.as<unsigned long long>();
         }
         const uint32_t xcd_shares = options().spmv_band_xcd == 1 || (options().spmv_band_xcd == 0 && bp->small) ? 1u : 0u;
         if (bp->xt_log2 == 13)

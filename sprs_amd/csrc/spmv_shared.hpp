@@ -120,16 +120,16 @@ __device__ __forceinline__ uint32_t x_slice(uint64_t col) {
 
 
 // perm[col] = label of the column: popularity classes, most referenced first (see the rl_* kernels).
-// Allocates *perm (cols entries); the caller owns it.
+// On success `perm` holds the block (cols entries); on failure it is left as it was.
 template <typename IDX>
-static int32_t build_column_labels(const IDX *indices, uint64_t nnz, uint64_t cols, hipStream_t stream, uint32_t **perm,
+static int32_t build_column_labels(const IDX *indices, uint64_t nnz, uint64_t cols, hipStream_t stream, DevBuf &perm,
                                    uint64_t *nref = nullptr) {
     const uint64_t nchunks = (cols + RL_CHUNK - 1) / RL_CHUNK;
-    DevBuf ccount, hist, base;
+    DevBuf ccount, hist, base, labels;
     SPRS_TRY_HIP(ccount.alloc(cols * 4));
     SPRS_TRY_HIP(hist.alloc((RL_DIGITS * nchunks + 1) * 8));
     SPRS_TRY_HIP(base.alloc((RL_DIGITS * nchunks + 1) * 8));
-    SPRS_TRY_HIP(hipMalloc((void **)perm, cols * sizeof(uint32_t)));
+    SPRS_TRY_HIP(labels.alloc(cols * sizeof(uint32_t)));
     SPRS_TRY_HIP(hipMemsetAsync(ccount.p, 0, cols * 4, stream));
     hipLaunchKernelGGL(rl_count_kernel<IDX>, dim3(256 * 16), dim3(256), 0, stream, indices, nnz, (uint32_t *)ccount.p);
     SPRS_TRY_HIP(hipGetLastError());
@@ -138,11 +138,12 @@ static int32_t build_column_labels(const IDX *indices, uint64_t nnz, uint64_t co
     SPRS_TRY_HIP(hipGetLastError());
     SPRS_TRY(exclusive_scan_u64(hist.u64(), base.u64(), RL_DIGITS * nchunks, stream));
     hipLaunchKernelGGL(rl_rank_kernel, wgrid, dim3(256), 0, stream, (const uint32_t *)ccount.p, cols, nchunks,
-                       (const uint64_t *)base.u64(), *perm);
+                       (const uint64_t *)base.u64(), labels.as<uint32_t>());
     SPRS_TRY_HIP(hipGetLastError());
     // the columns nobody references are the last class: its first label = the number of referenced columns
     if (nref) SPRS_TRY_HIP(copy_to_host(nref, base.u64() + (uint64_t)(RL_DIGITS - 1) * nchunks, 8, stream));
     SPRS_TRY_HIP(hipStreamSynchronize(stream));   // the temporaries go away here
+    perm = std::move(labels);
     return SPRS_HIP_OK;
 }
 

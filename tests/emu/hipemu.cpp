@@ -328,6 +328,8 @@ struct Alloc {
 };
 static std::map<void *, Alloc> g_allocs;
 static std::mutex g_alloc_mu;
+static long g_live_streams = 0, g_live_events = 0;   // (under g_alloc_mu)
+static long g_fail_in = 0;                           // the g_fail_in-th hipMalloc from now fails (0: none)
 
 static void on_fault(int sig, siginfo_t *si, void *) {
     char buf[512];
@@ -365,9 +367,30 @@ static void install_handler() {
 
 using namespace hipemu;
 
+// ---- test hooks (tests/test_plan_ownership_emu_cpu.py) -------------------------------------------------
+// live device blocks + live streams + live events: what a handle took and did not give back
+extern "C" long hipemu_live_count() {
+    std::lock_guard<std::mutex> g(g_alloc_mu);
+    return (long)g_allocs.size() + g_live_streams + g_live_events;
+}
+// the n-th hipMalloc from now fails with hipErrorOutOfMemory (once); 0 switches it off.  Returns what was left of the last count.
+extern "C" long hipemu_fail_malloc_in(long n) {
+    std::lock_guard<std::mutex> g(g_alloc_mu);
+    const long left = g_fail_in;
+    g_fail_in = n;
+    return left;
+}
+
 hipError_t hipMalloc(void **p, size_t bytes) {
     install_handler();
     if (!p) return hipErrorInvalidValue;
+    {
+        std::lock_guard<std::mutex> g(g_alloc_mu);
+        if (g_fail_in > 0 && --g_fail_in == 0) {
+            *p = nullptr;
+            return hipErrorOutOfMemory;
+        }
+    }
     if (bytes == 0) {
         *p = nullptr;
         return hipSuccess;
@@ -444,18 +467,26 @@ hipError_t hipMemGetInfo(size_t *free_b, size_t *total_b) {
 // streams and events: everything runs synchronously in the emulator
 hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) {
     *s = (hipStream_t)malloc(8);
+    std::lock_guard<std::mutex> g(g_alloc_mu);
+    ++g_live_streams;
     return hipSuccess;
 }
 hipError_t hipStreamDestroy(hipStream_t s) {
     free(s);
+    std::lock_guard<std::mutex> g(g_alloc_mu);
+    --g_live_streams;
     return hipSuccess;
 }
 hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) {
     *e = (hipEvent_t)malloc(8);
+    std::lock_guard<std::mutex> g(g_alloc_mu);
+    ++g_live_events;
     return hipSuccess;
 }
 hipError_t hipEventDestroy(hipEvent_t e) {
     free(e);
+    std::lock_guard<std::mutex> g(g_alloc_mu);
+    --g_live_events;
     return hipSuccess;
 }
 hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
