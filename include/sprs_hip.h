@@ -567,6 +567,48 @@ int32_t sprs_hip_csmat_hstack(const sprs_hip_csmat **mats, uint64_t n, sprs_hip_
  * its left in its own super-row (a NULL counts the super-column's maximum), so [2 | 3] over [3 | 2] columns is accepted. */
 int32_t sprs_hip_csmat_bmat(const sprs_hip_csmat **blocks, uint64_t super_rows, uint64_t super_cols, sprs_hip_csmat **out, void *stream);
 
+/* ---- dense <-> sparse (sprs/src/sparse/csmat.rs:499-549, to_dense.rs, binop.rs:273-433) -----------------------------------
+ * A dense operand is f64 in DEVICE memory, SPRS_HIP_ROW_MAJOR or SPRS_HIP_COL_MAJOR, with a leading dimension ld in elements:
+ * ld >= cols for row-major, ld >= rows for column-major, SPRS_HIP_INVALID_ARG otherwise (also for a bad layout tag or a NULL
+ * array that has elements).  The unit inner stride is the only one: ndarray's general strides (binop.rs' mul_dense_strided
+ * walks s![..;2, ..;2]) are out of scope.  Elements in the padding between the extent and ld are never read into a result and
+ * never written.  `stream` comes last: the kernels run there.  Every result element is one or two IEEE operations without a
+ * reduction, unfused (multiply, then add): results are the reference's bit for bit; a NaN made out of no NaN carries the sign
+ * bit, as on the x86 the reference runs on.
+ *
+ * csr_from_dense / csc_from_dense (csmat.rs:499-549; storage = SPRS_HIP_CSR / SPRS_HIP_CSC): a new owning handle of the elements
+ * with fabs(x) > eps, eps = epsilon > 0 ? epsilon : 0 (a negative or NaN epsilon is 0).  NaN, both zeros and |x| == eps are
+ * dropped, infinities and denormals above eps kept; a kept value's bits are stored unchanged, inner indices ascend, indptr is
+ * proper.  Any layout with any storage (the reference reverses the axes of the view).  iptr_bytes / idx_bytes: 2, 4 or 8, as
+ * sprs_hip_csmat_upload.  SPRS_HIP_INDEX_OVERFLOW where I::from_usize / Iptr::from_usize panic: a KEPT inner index above the
+ * index type's maximum (a wide matrix whose kept entries all fit is fine), a total nnz above the indptr type's.  The result is
+ * complete on return; *out is written on success only. */
+int32_t sprs_hip_csmat_from_dense_f64(sprs_hip_csmat **out, int32_t storage, const double *m_dev, uint64_t rows, uint64_t cols,
+                                      int32_t layout, uint64_t ld, double epsilon, int32_t iptr_bytes, int32_t idx_bytes, void *stream);
+/* assign_to_dense (to_dense.rs:12-30): out[row, col] = value for every stored entry; every other element of out, padding
+ * included, is untouched.  SPRS_HIP_DIM_MISMATCH "Dimension mismatch" unless m is rows x cols (the reference's two asserts).  Any
+ * storage with any layout.  An inner index at or above the inner dimension (an unchecked handle) is skipped — never a store
+ * outside the rows x cols elements; of duplicated indices one survives, unspecified which.  Asynchronous on `stream`. */
+int32_t sprs_hip_csmat_assign_to_dense_f64(const sprs_hip_csmat *m, double *out_dev, uint64_t rows, uint64_t cols, int32_t layout,
+                                           uint64_t ld, void *stream);
+/* CsMat::to_dense (csmat.rs:1127-1134): the rows x cols elements set to +0.0 (not the padding), then assign_to_dense. */
+int32_t sprs_hip_csmat_to_dense_f64(const sprs_hip_csmat *m, double *out_dev, uint64_t rows, uint64_t cols, int32_t layout, uint64_t ld,
+                                    void *stream);
+/* csmat_binop_dense_raw (binop.rs:384-433) with the two closures the reference ships: op = SPRS_HIP_BINOP_ADD writes
+ * (alpha * l) + (beta * r) — add_dense_mat_same_ordering, binop.rs:279-323 —, SPRS_HIP_BINOP_MUL (alpha * l) * r, beta ignored —
+ * mul_dense_mat_same_ordering, binop.rs:331-371 — into EVERY element of out; l is +0.0 where lhs stores nothing and the
+ * operation is performed there too (alpha = -1, r = -0.0 gives -0.0; (alpha * 0) * inf is NaN).  out has the layout of rhs and
+ * the leading dimension out_ld.  Checks in the reference's order (binop.rs:397-412) after the argument checks: lhs is rows x cols
+ * or SPRS_HIP_DIM_MISMATCH "Dimension mismatch"; CSR with row-major / CSC with column-major or SPRS_HIP_STORAGE_MISMATCH "Storage
+ * mismatch".  out overlapping rhs is SPRS_HIP_INVALID_ARG (the reference cannot alias them either).  Asynchronous on `stream`. */
+int32_t sprs_hip_csmat_binop_dense_f64(const sprs_hip_csmat *lhs, const double *rhs_dev, uint64_t rows, uint64_t cols, int32_t layout,
+                                       uint64_t ld, int32_t op, double alpha, double beta, double *out_dev, uint64_t out_ld, void *stream);
+/* `&CsMat + &Array2` (csmat.rs:1951-1987): the binop above with ADD and alpha = beta = 1 into a contiguous out of rhs' layout
+ * (out_ld = cols / rows); a lhs whose storage does not match the layout goes through to_other_storage first (null stream, after a
+ * wait for `stream`; the copy lives for the call, which then returns when the result is complete). */
+int32_t sprs_hip_csmat_add_dense_f64(const sprs_hip_csmat *lhs, const double *rhs_dev, uint64_t rows, uint64_t cols, int32_t layout,
+                                     uint64_t ld, double *out_dev, void *stream);
+
 /* ---- row-sharded SpMV over the GPUs of one node (one process per GPU, RCCL over xGMI) ----
  * The reference has no distributed code; the shard is its slice_outer (slicing.rs:65-89) with a rebased indptr
  * (indptr.rs:206-214): rank g owns rows [row_starts[g], row_starts[g+1]) and a full replica of x; one exchange, an

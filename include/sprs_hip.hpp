@@ -562,6 +562,65 @@ inline DeviceCsMat bmat(const std::vector<const DeviceCsMat *> &blocks, uint64_t
 }
 }  // namespace construct
 
+// The dense <-> sparse boundary on device operands: CsMat::csr_from_dense / csc_from_dense (csmat.rs:499-549), assign_to_dense
+// and CsMat::to_dense (to_dense.rs:12-30, csmat.rs:1127-1134).  Contiguous DeviceMat operands; the C entries also take a
+// leading dimension.
+namespace dense {
+namespace detail {
+inline DeviceCsMat from_dense(int32_t storage, const DeviceMat &m, double epsilon, void *stream) {
+    sprs_hip_csmat *c = nullptr;
+    check(sprs_hip_csmat_from_dense_f64(&c, storage, m.ptr(), m.rows(), m.cols(), m.layout(), m.ld(), epsilon, 8, 8, stream));
+    return DeviceCsMat(c);
+}
+}  // namespace detail
+// the elements with |x| > max(epsilon, 0) (a negative or NaN epsilon is 0), usize indices
+inline DeviceCsMat csr_from_dense(const DeviceMat &m, double epsilon, void *stream = nullptr) { return detail::from_dense(SPRS_HIP_CSR, m, epsilon, stream); }
+inline DeviceCsMat csc_from_dense(const DeviceMat &m, double epsilon, void *stream = nullptr) { return detail::from_dense(SPRS_HIP_CSC, m, epsilon, stream); }
+// array[row, col] = value for every stored entry; the array is not zeroed first
+inline void assign_to_dense(DeviceMat &array, const DeviceCsMat &spmat, void *stream = nullptr) {
+    check(sprs_hip_csmat_assign_to_dense_f64(spmat.handle(), array.ptr(), array.rows(), array.cols(), array.layout(), array.ld(), stream));
+}
+// Array::zeros((rows, cols)) — standard layout — then assign_to_dense
+inline DeviceMat to_dense(const DeviceCsMat &spmat, void *stream = nullptr) {
+    DeviceMat out(spmat.rows(), spmat.cols());
+    check(sprs_hip_csmat_to_dense_f64(spmat.handle(), out.ptr(), out.rows(), out.cols(), out.layout(), out.ld(), stream));
+    return out;
+}
+}  // namespace dense
+
+namespace binop {
+// csmat_binop_dense_raw (binop.rs:384-433) with one of the two closures the reference ships: op = SPRS_HIP_BINOP_ADD writes
+// (alpha * l) + (beta * r), SPRS_HIP_BINOP_MUL (alpha * l) * r, into every element of out; "Dimension mismatch", then "Storage
+// mismatch" unless CSR meets standard layout / CSC meets `.f()` layout in both rhs and out
+inline void csmat_binop_dense_raw(const DeviceCsMat &lhs, const DeviceMat &rhs, int32_t op, DeviceMat &out, double alpha = 1.0, double beta = 1.0,
+                                  void *stream = nullptr) {
+    if (lhs.cols() != rhs.cols() || lhs.cols() != out.cols() || lhs.rows() != rhs.rows() || lhs.rows() != out.rows())
+        throw Error(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    if (rhs.layout() != out.layout()) throw Error(SPRS_HIP_STORAGE_MISMATCH, "Storage mismatch");
+    check(sprs_hip_csmat_binop_dense_f64(lhs.handle(), rhs.ptr(), rhs.rows(), rhs.cols(), rhs.layout(), rhs.ld(), op, alpha, beta, out.ptr(),
+                                         out.ld(), stream));
+}
+// add_dense_mat_same_ordering (binop.rs:279-323): alpha * lhs + beta * rhs in rhs' layout
+inline DeviceMat add_dense_mat_same_ordering(const DeviceCsMat &lhs, const DeviceMat &rhs, double alpha, double beta, void *stream = nullptr) {
+    DeviceMat out(rhs.rows(), rhs.cols(), !rhs.is_standard_layout());
+    csmat_binop_dense_raw(lhs, rhs, SPRS_HIP_BINOP_ADD, out, alpha, beta, stream);
+    return out;
+}
+// mul_dense_mat_same_ordering (binop.rs:331-371): the coefficient-wise alpha * lhs * rhs in rhs' layout
+inline DeviceMat mul_dense_mat_same_ordering(const DeviceCsMat &lhs, const DeviceMat &rhs, double alpha, void *stream = nullptr) {
+    DeviceMat out(rhs.rows(), rhs.cols(), !rhs.is_standard_layout());
+    csmat_binop_dense_raw(lhs, rhs, SPRS_HIP_BINOP_MUL, out, alpha, 1.0, stream);
+    return out;
+}
+}  // namespace binop
+
+// `&A + &D` (csmat.rs:1951-1987): A.to_other_storage() first when its storage does not match D's layout, below the C ABI
+inline DeviceMat operator+(const DeviceCsMat &a, const DeviceMat &d) {
+    DeviceMat out(d.rows(), d.cols(), !d.is_standard_layout());
+    check(sprs_hip_csmat_add_dense_f64(a.handle(), d.ptr(), d.rows(), d.cols(), d.layout(), d.ld(), out.ptr(), nullptr));
+    return out;
+}
+
 // TriMatI<f64, usize> (sparse/triplet.rs:26-48) with the device assembly of `to_csr` (triplet.rs:270-276 ->
 // triplet_iter.rs:127-224: rows sorted, duplicates summed).  No dedicated kernel: with n triplets the matrix
 // is the product R * E of R (rows x n, one 1 per column at the triplet's row) and E (n x cols, one value per

@@ -246,6 +246,23 @@ extern "C" {
     pub fn sprs_hip_csmat_bmat(
         blocks: *mut *const sprs_hip_csmat, super_rows: u64, super_cols: u64, out: *mut *mut sprs_hip_csmat, stream: *mut c_void,
     ) -> i32;
+    pub fn sprs_hip_csmat_from_dense_f64(
+        out: *mut *mut sprs_hip_csmat, storage: i32, m_dev: *const f64, rows: u64, cols: u64, layout: i32, ld: u64, epsilon: f64,
+        iptr_bytes: i32, idx_bytes: i32, stream: *mut c_void,
+    ) -> i32;
+    pub fn sprs_hip_csmat_assign_to_dense_f64(
+        m: *const sprs_hip_csmat, out_dev: *mut f64, rows: u64, cols: u64, layout: i32, ld: u64, stream: *mut c_void,
+    ) -> i32;
+    pub fn sprs_hip_csmat_to_dense_f64(
+        m: *const sprs_hip_csmat, out_dev: *mut f64, rows: u64, cols: u64, layout: i32, ld: u64, stream: *mut c_void,
+    ) -> i32;
+    pub fn sprs_hip_csmat_binop_dense_f64(
+        lhs: *const sprs_hip_csmat, rhs_dev: *const f64, rows: u64, cols: u64, layout: i32, ld: u64, op: i32, alpha: f64, beta: f64,
+        out_dev: *mut f64, out_ld: u64, stream: *mut c_void,
+    ) -> i32;
+    pub fn sprs_hip_csmat_add_dense_f64(
+        lhs: *const sprs_hip_csmat, rhs_dev: *const f64, rows: u64, cols: u64, layout: i32, ld: u64, out_dev: *mut f64, stream: *mut c_void,
+    ) -> i32;
     pub fn sprs_hip_triplets_to_cs(
         rows: u64, cols: u64, n: u64, row_inds_dev: *const c_void, col_inds_dev: *const c_void, in_idx_bytes: i32,
         data_dev: *const f64, storage: i32, out_idx_bytes: i32, out_iptr_bytes: i32, out: *mut *mut sprs_hip_csmat,

@@ -610,6 +610,96 @@ pub mod binop {
         unsafe { check(sys::sprs_hip_csvec_binop_f64(lhs.h, rhs.h, op as i32, &mut h, std::ptr::null_mut())) };
         DeviceCsVec { h }
     }
+
+    /// `binop::csmat_binop_dense_raw` (binop.rs:384-433) with one of the two closures the reference ships: `Op::Add` writes
+    /// `(alpha * l) + (beta * r)`, `Op::Mul` `(alpha * l) * r` into every element of `out`.  The reference's panics in its
+    /// order: "Dimension mismatch", then "Storage mismatch" unless CSR meets standard layout / CSC meets `.f()` layout.
+    pub fn csmat_binop_dense_raw(lhs: &DeviceCsMat, rhs: &super::DeviceMat, op: Op, alpha: f64, beta: f64, out: &mut super::DeviceMat) {
+        let (rows, cols) = lhs.shape();
+        if cols != rhs.cols || cols != out.cols || rows != rhs.rows || rows != out.rows {
+            panic!("Dimension mismatch");
+        }
+        if rhs.col_major != out.col_major {
+            panic!("Storage mismatch");
+        }
+        unsafe {
+            check(sys::sprs_hip_csmat_binop_dense_f64(lhs.h, rhs.buf.ptr, rhs.rows as u64, rhs.cols as u64, rhs.layout(), rhs.ld(), op as i32,
+                                                      alpha, beta, out.buf.ptr, out.ld(), std::ptr::null_mut()));
+        }
+    }
+
+    fn like(rhs: &super::DeviceMat) -> super::DeviceMat {
+        if rhs.col_major { super::DeviceMat::zeros_f(rhs.shape()) } else { super::DeviceMat::zeros(rhs.shape()) }
+    }
+
+    /// `binop::add_dense_mat_same_ordering` (binop.rs:279-323): `alpha * lhs + beta * rhs` in the layout of `rhs`.
+    pub fn add_dense_mat_same_ordering(lhs: &DeviceCsMat, rhs: &super::DeviceMat, alpha: f64, beta: f64) -> super::DeviceMat {
+        let mut out = like(rhs);
+        csmat_binop_dense_raw(lhs, rhs, Op::Add, alpha, beta, &mut out);
+        out
+    }
+
+    /// `binop::mul_dense_mat_same_ordering` (binop.rs:331-371): the coefficient-wise `alpha * lhs * rhs` in the layout of `rhs`.
+    pub fn mul_dense_mat_same_ordering(lhs: &DeviceCsMat, rhs: &super::DeviceMat, alpha: f64) -> super::DeviceMat {
+        let mut out = like(rhs);
+        csmat_binop_dense_raw(lhs, rhs, Op::Mul, alpha, 1.0, &mut out);
+        out
+    }
+}
+
+/// `&A + &D` for a dense `D` (csmat.rs:1951-1987): `A.to_other_storage()` first when its storage does not match the layout of
+/// `D` — done below the C ABI; the result has the layout of `D`.
+impl<'a, 'b> std::ops::Add<&'b DeviceMat> for &'a DeviceCsMat {
+    type Output = DeviceMat;
+    fn add(self, rhs: &'b DeviceMat) -> DeviceMat {
+        let out = if rhs.col_major { DeviceMat::zeros_f(rhs.shape()) } else { DeviceMat::zeros(rhs.shape()) };
+        unsafe {
+            check(sys::sprs_hip_csmat_add_dense_f64(self.h, rhs.buf.ptr, rhs.rows as u64, rhs.cols as u64, rhs.layout(), rhs.ld(), out.buf.ptr,
+                                                    std::ptr::null_mut()));
+        }
+        out
+    }
+}
+
+/// Twin of `sprs::sparse::to_dense` (to_dense.rs:12-30): `array[row, col] = value` for every stored entry; the array is not
+/// zeroed first.  Panics with "Dimension mismatch" like the reference's two asserts.
+pub fn assign_to_dense(array: &mut DeviceMat, spmat: &DeviceCsMat) {
+    unsafe {
+        check(sys::sprs_hip_csmat_assign_to_dense_f64(spmat.h, array.buf.ptr, array.rows as u64, array.cols as u64, array.layout(), array.ld(),
+                                                      std::ptr::null_mut()));
+    }
+}
+
+impl DeviceCsMat {
+    /// `CsMat::to_dense` (csmat.rs:1127-1134): `Array::zeros((rows, cols))`, then `assign_to_dense`.
+    pub fn to_dense(&self) -> DeviceMat {
+        let out = DeviceMat::zeros(self.shape());
+        unsafe {
+            check(sys::sprs_hip_csmat_to_dense_f64(self.h, out.buf.ptr, out.rows as u64, out.cols as u64, out.layout(), out.ld(),
+                                                   std::ptr::null_mut()));
+        }
+        out
+    }
+
+    fn from_dense(storage: i32, m: &DeviceMat, epsilon: f64) -> DeviceCsMat {
+        let mut h: *mut sys::sprs_hip_csmat = std::ptr::null_mut();
+        let w = std::mem::size_of::<usize>() as i32;
+        unsafe {
+            check(sys::sprs_hip_csmat_from_dense_f64(&mut h, storage, m.buf.ptr, m.rows as u64, m.cols as u64, m.layout(), m.ld(), epsilon, w, w,
+                                                     std::ptr::null_mut()));
+        }
+        DeviceCsMat { h }
+    }
+
+    /// `CsMat::csr_from_dense` (csmat.rs:499-539): the elements with `|x| > epsilon`; a negative epsilon is clamped to zero.
+    pub fn csr_from_dense(m: &DeviceMat, epsilon: f64) -> DeviceCsMat {
+        Self::from_dense(sys::SPRS_HIP_CSR, m, epsilon)
+    }
+
+    /// `CsMat::csc_from_dense` (csmat.rs:541-549).
+    pub fn csc_from_dense(m: &DeviceMat, epsilon: f64) -> DeviceCsMat {
+        Self::from_dense(sys::SPRS_HIP_CSC, m, epsilon)
+    }
 }
 
 /// `&A + &B` (binop.rs:52-64): `rhs.to_other_storage()` first when the storages differ — done below the C ABI.

@@ -8,7 +8,7 @@ the shared library is absent; nothing here computes on the CPU.
 from . import _ffi
 from ._ffi import CSC, CSR, SprsHipError
 from .device import DeviceCsMat, DeviceCsVec, DeviceVec
-from . import prod, smmp, linalg, binop, permutation, construct
+from . import prod, smmp, linalg, binop, permutation, construct, to_dense
 from .construct import bmat, hstack, kronecker_product, same_storage_fast_stack, vstack
 from .permutation import DevicePerm
 from .linalg import lsolve_csc_dense_rhs, lsolve_csr_dense_rhs, usolve_csc_dense_rhs, usolve_csr_dense_rhs

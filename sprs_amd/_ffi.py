@@ -121,6 +121,11 @@ SIGNATURES = {
     "sprs_hip_csmat_vstack": (i32, [P(vp), u64, P(vp), vp]),
     "sprs_hip_csmat_hstack": (i32, [P(vp), u64, P(vp), vp]),
     "sprs_hip_csmat_bmat": (i32, [P(vp), u64, u64, P(vp), vp]),
+    "sprs_hip_csmat_from_dense_f64": (i32, [P(vp), i32, vp, u64, u64, i32, u64, C.c_double, i32, i32, vp]),
+    "sprs_hip_csmat_assign_to_dense_f64": (i32, [vp, vp, u64, u64, i32, u64, vp]),
+    "sprs_hip_csmat_to_dense_f64": (i32, [vp, vp, u64, u64, i32, u64, vp]),
+    "sprs_hip_csmat_binop_dense_f64": (i32, [vp, vp, u64, u64, i32, u64, i32, C.c_double, C.c_double, vp, u64, vp]),
+    "sprs_hip_csmat_add_dense_f64": (i32, [vp, vp, u64, u64, i32, u64, vp, vp]),
     "sprs_hip_set_option": (i32, [C.c_char_p, i64]),
     "sprs_hip_get_option": (i32, [C.c_char_p, P(i64)]),
 }

@@ -1567,6 +1567,129 @@ int32_t sprs_hip_csmat_bmat(const sprs_hip_csmat **blocks, uint64_t super_rows, 
 
 }  // extern "C"
 
+// ---- dense <-> sparse (csmat.rs:499-549, to_dense.rs, binop.rs:273-433); kernels in dense.hpp ------------------------------------
+
+// a dense operand of the ABI: layout tag, leading dimension, base pointer
+static int32_t dense_arg_ok(const void *p, uint64_t rows, uint64_t cols, int32_t layout, uint64_t ld, const char *what) {
+    if (layout != SPRS_HIP_ROW_MAJOR && layout != SPRS_HIP_COL_MAJOR) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "bad layout tag");
+    if (ld < (layout == SPRS_HIP_ROW_MAJOR ? cols : rows)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "leading dimension smaller than the extent it strides over");
+    uint64_t n;
+    if (mul_overflows(rows, cols, &n)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "%s: rows * cols overflows 64 bits", what);
+    if (n && !p) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL matrix");
+    return SPRS_HIP_OK;
+}
+
+// elements from the first to the one behind the last of a rows x cols array (0: it has none)
+static uint64_t dense_span(uint64_t rows, uint64_t cols, int32_t layout, uint64_t ld) {
+    if (!rows || !cols) return 0;
+    return layout == SPRS_HIP_ROW_MAJOR ? (rows - 1) * ld + cols : (cols - 1) * ld + rows;
+}
+
+static bool storage_matches(int32_t storage, int32_t layout) { return (storage == SPRS_HIP_CSR) == (layout == SPRS_HIP_ROW_MAJOR); }
+
+// the checks of csmat_binop_dense_raw (binop.rs:397-412) in its order, after the argument checks
+static int32_t binop_dense_contract(const sprs_hip_csmat *lhs, const double *rhs_dev, uint64_t rows, uint64_t cols, int32_t layout, uint64_t ld,
+                                    int32_t op, double *out_dev, uint64_t out_ld, bool same_ordering) {
+    if (op != SPRS_HIP_BINOP_ADD && op != SPRS_HIP_BINOP_MUL) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "op must be SPRS_HIP_BINOP_ADD or SPRS_HIP_BINOP_MUL");
+    SPRS_TRY(dense_arg_ok(rhs_dev, rows, cols, layout, ld, "binop_dense"));
+    SPRS_TRY(dense_arg_ok(out_dev, rows, cols, layout, out_ld, "binop_dense"));
+    if (!lhs) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if (lhs->cols != cols || lhs->rows != rows) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    if (same_ordering && !storage_matches(lhs->storage, layout)) SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "Storage mismatch");
+    const uint64_t span_r = dense_span(rows, cols, layout, ld), span_o = dense_span(rows, cols, layout, out_ld);
+    if (span_r && rhs_dev < out_dev + span_o && out_dev < rhs_dev + span_r)
+        SPRS_FAIL(SPRS_HIP_INVALID_ARG, "the result matrix overlaps the right-hand side");
+    return SPRS_HIP_OK;
+}
+
+extern "C" {
+
+int32_t sprs_hip_csmat_from_dense_f64(sprs_hip_csmat **out, int32_t storage, const double *m_dev, uint64_t rows, uint64_t cols, int32_t layout,
+                                      uint64_t ld, double epsilon, int32_t iptr_bytes, int32_t idx_bytes, void *stream) {
+    clear_error();
+    if (!out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    if (storage != SPRS_HIP_CSR && storage != SPRS_HIP_CSC) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "bad storage tag %d", storage);
+    if (!host_widths_ok(iptr_bytes, idx_bytes)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "index widths must be 2, 4 or 8 bytes");
+    SPRS_TRY(dense_arg_ok(m_dev, rows, cols, layout, ld, "from_dense"));
+    const double eps = epsilon > 0.0 ? epsilon : 0.0;               // csmat.rs:506-510: a negative or NaN epsilon is 0
+    const int32_t dev_iptr = iptr_bytes == 2 ? 4 : iptr_bytes, dev_idx = idx_bytes == 2 ? 4 : idx_bytes;
+    const uint64_t idx_max = width_max(idx_bytes), nnz_max = std::min(width_max(iptr_bytes), UINT64_MAX >> 1);
+    const bool rowmaj = layout == SPRS_HIP_ROW_MAJOR;
+    const uint64_t lines = rowmaj ? rows : cols, width = rowmaj ? cols : rows;
+    OwnedCsmat res;
+    if (storage_matches(storage, layout) || !rows || !cols) {
+        // (an array without elements has no order: the requested storage at once)
+        const bool csr = storage == SPRS_HIP_CSR;
+        SPRS_TRY(csmat_from_dense_f64(m_dev, storage, csr ? rows : cols, csr ? cols : rows, ld, eps, idx_max, UINT64_MAX, nnz_max, dev_iptr,
+                                      dev_idx, res, (hipStream_t)stream));
+    } else {
+        // csr_from_dense of an F-ordered view / csc_from_dense of a C-ordered one: the matched storage of the layout, then
+        // to_other_storage — the same entries in the same order as the reference's strided walk.  The index that has to fit
+        // the index type is the LINE: it becomes the result's inner index.
+        if (dev_idx == 4 && width > (1ull << 32))
+            SPRS_FAIL(SPRS_HIP_INVALID_ARG, "from_dense: 32-bit indices against the layout with more than 2^32 elements per line are not supported");
+        OwnedCsmat matched;
+        SPRS_TRY(csmat_from_dense_f64(m_dev, rowmaj ? SPRS_HIP_CSR : SPRS_HIP_CSC, lines, width, ld, eps, UINT64_MAX, idx_max, nnz_max, dev_iptr,
+                                      dev_idx, matched, (hipStream_t)stream));
+        SPRS_TRY(to_other_storage(matched.get(), res));              // (null stream; `matched` is complete)
+    }
+    if (iptr_bytes == 2 || idx_bytes == 2) {
+        res->decl_iptr_bytes = iptr_bytes;
+        res->decl_idx_bytes = idx_bytes;
+    }
+    *out = res.release();
+    return SPRS_HIP_OK;
+}
+
+static int32_t assign_dense(const sprs_hip_csmat *m, bool zero_first, double *out_dev, uint64_t rows, uint64_t cols, int32_t layout, uint64_t ld,
+                            void *stream) {
+    SPRS_TRY(dense_arg_ok(out_dev, rows, cols, layout, ld, "assign_to_dense"));
+    if (!m) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if (m->cols != cols) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");      // to_dense.rs:20
+    if (m->rows != rows) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");      // to_dense.rs:21
+    return csmat_assign_dense_f64(m, zero_first, out_dev, layout, ld, (hipStream_t)stream);
+}
+
+int32_t sprs_hip_csmat_assign_to_dense_f64(const sprs_hip_csmat *m, double *out_dev, uint64_t rows, uint64_t cols, int32_t layout, uint64_t ld,
+                                           void *stream) {
+    clear_error();
+    return assign_dense(m, false, out_dev, rows, cols, layout, ld, stream);
+}
+
+int32_t sprs_hip_csmat_to_dense_f64(const sprs_hip_csmat *m, double *out_dev, uint64_t rows, uint64_t cols, int32_t layout, uint64_t ld,
+                                    void *stream) {
+    clear_error();
+    return assign_dense(m, true, out_dev, rows, cols, layout, ld, stream);
+}
+
+int32_t sprs_hip_csmat_binop_dense_f64(const sprs_hip_csmat *lhs, const double *rhs_dev, uint64_t rows, uint64_t cols, int32_t layout, uint64_t ld,
+                                       int32_t op, double alpha, double beta, double *out_dev, uint64_t out_ld, void *stream) {
+    clear_error();
+    SPRS_TRY(binop_dense_contract(lhs, rhs_dev, rows, cols, layout, ld, op, out_dev, out_ld, true));
+    return csmat_binop_dense_f64(lhs, rhs_dev, layout, ld, op, alpha, beta, out_dev, out_ld, (hipStream_t)stream);
+}
+
+// `&CsMat + &Array2` (csmat.rs:1951-1987): alpha = beta = 1; lhs.to_other_storage() first when its storage does not match the
+// layout — the copy lives for the call
+int32_t sprs_hip_csmat_add_dense_f64(const sprs_hip_csmat *lhs, const double *rhs_dev, uint64_t rows, uint64_t cols, int32_t layout, uint64_t ld,
+                                     double *out_dev, void *stream) {
+    clear_error();
+    const uint64_t out_ld = layout == SPRS_HIP_ROW_MAJOR ? cols : rows;
+    SPRS_TRY(binop_dense_contract(lhs, rhs_dev, rows, cols, layout, ld, SPRS_HIP_BINOP_ADD, out_dev, out_ld, false));
+    OwnedCsmat conv;
+    if (!storage_matches(lhs->storage, layout)) {
+        // the conversion runs on the null stream: what the caller's stream still has to write into lhs comes first
+        if (stream) SPRS_TRY_HIP(hipStreamSynchronize((hipStream_t)stream));
+        SPRS_TRY(convert_checked(lhs, conv));
+    }
+    SPRS_TRY(csmat_binop_dense_f64(conv ? conv.get() : lhs, rhs_dev, layout, ld, SPRS_HIP_BINOP_ADD, 1.0, 1.0, out_dev, out_ld, (hipStream_t)stream));
+    if (conv) SPRS_TRY_HIP(hipStreamSynchronize((hipStream_t)stream));   // the kernels read the copy: it goes with this call
+    return SPRS_HIP_OK;
+}
+
+}  // extern "C"
+
 // the pool and the handle constructors live in handle.hpp, compiled here so that the library and its emulator build (tests/emu,
 // a fixed list of translation units) both carry them
 #include "handle.hpp"

@@ -110,6 +110,7 @@ constexpr bool DEVTOOLS = false;
     X(perm_tile, 2048, 2048, 2048, 0)   /* result entries per workgroup of the outer-permutation copy kernel (perm.hpp): fixed, published so that tests can place tile edges */ \
     X(perm_cap, 4096, 4096, 4096, 0)    /* longest row a relabelling permutation sorts in LDS by one workgroup (perm.hpp); longer rows go through the radix sort: fixed, published for the tests */ \
     X(construct_tile, 2048, 2048, 2048, 0) /* result entries (Kronecker product) / block entries (stacking) per workgroup of the construction kernels (construct.hpp): fixed, published so that tests can place tile edges */ \
+    X(dense_tile, 2048, 2048, 2048, 0)  /* dense elements (from_dense) / stored entries (assign_to_dense, the sparse-with-dense binops) per workgroup of the dense <-> sparse kernels (dense.hpp): fixed, published so that tests can place tile edges */ \
     X(pool, 1, 0, 1, 0)                 /* keep released result blocks (>= 1 MiB) for the next result instead of hipFree */        \
     X(pool_max_bytes, 128ll << 30, 0, INT64_MAX, 0) /* cap on the bytes the pool may hold */
 
@@ -459,6 +460,13 @@ struct StackItem {
 };
 int32_t csmat_stack(const std::vector<StackItem> &items, const std::vector<uint64_t> &outer_of, int32_t storage, uint64_t rows, uint64_t cols,
                     int32_t iptr_bytes, int32_t idx_bytes, OwnedCsmat &out, hipStream_t stream);
+// dense.hpp (compiled in convert.hip): a dense operand is `lines` lines of `width` f64, ld apart, in the order that matches the
+// sparse storage.  from_dense is complete on `stream` at return; the other two are ordered on it
+int32_t csmat_from_dense_f64(const double *m, int32_t storage, uint64_t lines, uint64_t width, uint64_t ld, double eps, uint64_t c_max,
+                             uint64_t r_max, uint64_t nnz_max, int32_t iptr_bytes, int32_t idx_bytes, OwnedCsmat &out, hipStream_t stream);
+int32_t csmat_assign_dense_f64(const sprs_hip_csmat *m, bool zero_first, double *out, int32_t layout, uint64_t ld, hipStream_t stream);
+int32_t csmat_binop_dense_f64(const sprs_hip_csmat *lhs, const double *rhs, int32_t layout, uint64_t ld, int32_t op, double alpha, double beta,
+                              double *out, uint64_t out_ld, hipStream_t stream);
 // bicgstab.hip
 int32_t bicgstab_f64(sprs_hip_csmat *a, const double *x0, const double *b, uint64_t n, double tol, uint64_t max_iter,
                      double soft_restart_threshold, double *x, sprs_hip_bicgstab_info *info, hipStream_t stream);

@@ -116,6 +116,23 @@ class DeviceCsMat:
         return cls.from_host((dim, dim), np.arange(dim + 1, dtype=ptr_dtype),
                              np.arange(dim, dtype=idx_dtype), np.ones(dim), validate=False)
 
+    @classmethod
+    def csr_from_dense(cls, m, epsilon, idx_dtype=np.uint64, ptr_dtype=np.uint64, stream=None):
+        """CsMat::csr_from_dense (csmat.rs:499-539) of a prod.DeviceMat: the elements with |x| > max(epsilon, 0)."""
+        from . import to_dense
+        return to_dense.csr_from_dense(m, epsilon, idx_dtype, ptr_dtype, stream)
+
+    @classmethod
+    def csc_from_dense(cls, m, epsilon, idx_dtype=np.uint64, ptr_dtype=np.uint64, stream=None):
+        """CsMat::csc_from_dense (csmat.rs:541-549)."""
+        from . import to_dense
+        return to_dense.csc_from_dense(m, epsilon, idx_dtype, ptr_dtype, stream)
+
+    def to_dense(self, out=None, stream=None):
+        """CsMat::to_dense (csmat.rs:1127-1134) as a prod.DeviceMat in standard layout (or into `out`)."""
+        from . import to_dense
+        return to_dense.to_dense(self, out, stream)
+
     # -- accessors ------------------------------------------------------------
     def _info(self):
         r, c, n = C.c_uint64(), C.c_uint64(), C.c_uint64()
@@ -223,6 +240,10 @@ class DeviceCsMat:
         if isinstance(rhs, DeviceCsMat):
             from . import binop
             return binop.add_mat(self, rhs)               # binop.rs:52-64
+        from . import prod
+        if isinstance(rhs, prod.DeviceMat):
+            from . import binop
+            return binop.add_dense(self, rhs)             # csmat.rs:1951-1987
         return NotImplemented
 
     def __sub__(self, rhs):

@@ -32,20 +32,38 @@ class DeviceMat:
     """Dense f64 matrix in HBM in one of ndarray's two contiguous layouts: `Array2` in standard (row-major) order, or
     `Array::zeros(shape.f())` (column-major) — what `&CsMat * &Array2` returns for fewer than 8 columns (csmat.rs:2017-2024)."""
 
-    def __init__(self, rows, cols, vec=None, col_major=False):
+    def __init__(self, rows, cols, vec=None, col_major=False, ld=None):
+        """ld: the leading dimension in elements (None: contiguous) — the lines of the matrix are ld apart in `vec`, which then
+        holds lines * ld elements (the last line's padding included).  Only the dense <-> sparse entries take a padded matrix."""
         self.rows, self.cols, self.col_major = int(rows), int(cols), bool(col_major)
-        self.vec = vec if vec is not None else DeviceVec.zeros(self.rows * self.cols)
-        assert self.vec.n == self.rows * self.cols
+        self._ld = None if ld is None else int(ld)
+        lines = self.cols if self.col_major else self.rows
+        want = self.rows * self.cols if self._ld is None else lines * self._ld
+        self.vec = vec if vec is not None else DeviceVec.zeros(want)
+        assert self.vec.n == want
 
     @classmethod
-    def from_host(cls, arr, col_major=False):
+    def from_host(cls, arr, col_major=False, ld=None, fill=0.0):
+        """ld: pad every line to ld elements; the padding holds `fill` (a float, or an array of lines x (ld - width))"""
         import numpy as np
         arr = np.asarray(arr, dtype=np.float64)
+        if ld is not None:
+            lines = arr.T if col_major else arr
+            if int(ld) < lines.shape[1]:
+                raise _ffi.SprsHipError(_ffi.INVALID_ARG, "leading dimension smaller than the extent it strides over")
+            buf = np.empty((lines.shape[0], int(ld)), dtype=np.float64)
+            buf[:, lines.shape[1]:] = fill
+            buf[:, :lines.shape[1]] = lines
+            return cls(arr.shape[0], arr.shape[1], DeviceVec.from_host(buf.reshape(-1)), col_major, ld)
         flat = np.asfortranarray(arr).reshape(-1, order="F") if col_major else np.ascontiguousarray(arr).reshape(-1)
         return cls(arr.shape[0], arr.shape[1], DeviceVec.from_host(np.ascontiguousarray(flat)), col_major)
 
     def to_host(self):
         flat = self.vec.to_host()
+        if self._ld is not None:
+            lines, width = (self.cols, self.rows) if self.col_major else (self.rows, self.cols)
+            body = flat.reshape(lines, self._ld)[:, :width]
+            return body.T if self.col_major else body
         return flat.reshape(self.cols, self.rows).T if self.col_major else flat.reshape(self.rows, self.cols)
 
     @property
@@ -54,6 +72,8 @@ class DeviceMat:
 
     @property
     def ld(self):
+        if self._ld is not None:
+            return self._ld
         return self.rows if self.col_major else self.cols
 
 
