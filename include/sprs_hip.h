@@ -537,6 +537,49 @@ int32_t sprs_hip_csmat_transform_paq(const sprs_hip_csmat *m, const sprs_hip_per
  * copy when p.is_identity() — the elementwise test, so a stored permutation equal to 0..dim counts.  Otherwise as above. */
 int32_t sprs_hip_csmat_transform_papt(const sprs_hip_csmat *m, const sprs_hip_perm *p, sprs_hip_csmat **out, void *stream);
 
+/* ---- orderings (sprs/src/sparse/linalg/ordering.rs, symmetric.rs, csmat.rs:1188-1216) --------------------------------------
+ * Everything here walks the OUTER dimension as the reference does: a CSC handle is read as the CSR arrays of its transpose.
+ * `stream` comes last: the kernels run there, host results are complete on return.
+ *
+ * is_symmetric (symmetric.rs:7-34): *flag = 1 when the matrix is square and every stored entry (o, i, v) has a stored entry
+ * (i, o) whose value is not `!=` v — a NaN anywhere (the diagonal included) gives 0, -0.0 equals 0.0.  A non-square matrix gives
+ * 0 without a launch. */
+int32_t sprs_hip_csmat_is_symmetric(const sprs_hip_csmat *m, int32_t *flag, void *stream);
+/* CsMat::degrees (csmat.rs:1205-1216): out_dev[o] = stored entries of outer slice o whose index is not o, for a DEVICE array of
+ * outer-dimension uint64_t.  Asynchronous on `stream`.  The slices must be sorted and free of duplicates (a validated handle). */
+int32_t sprs_hip_csmat_degrees(const sprs_hip_csmat *m, uint64_t *out_dev, void *stream);
+/* CsMat::max_outer_nnz (csmat.rs:1188-1193): the longest outer slice, 0 for an empty matrix */
+int32_t sprs_hip_csmat_max_outer_nnz(const sprs_hip_csmat *m, uint64_t *out, void *stream);
+
+/* cuthill_mckee_custom (ordering.rs:440-526).  `start` is the strategy that picks the first vertex of every connected
+ * component (ordering.rs:14-267), reversed != 0 is order::Reversed (position n - 1 - k instead of k, delimiters mirrored),
+ * reverse_cuthill_mckee (ordering.rs:546-559) is (SPRS_HIP_START_PSEUDO_PERIPHERAL, 1).  The result is the reference's own
+ * permutation with ties between vertices of equal degree broken by vertex id — the stable outcome of its
+ * sort_unstable_by_key —, so it is one deterministic permutation whatever the device does first.  Diagonal entries are no
+ * neighbours and count in no degree.  Before any device work:
+ *   NULL m / out, a start other than the three below          SPRS_HIP_INVALID_ARG
+ *   rows != cols                                              SPRS_HIP_DIM_MISMATCH  the text of the reference's assert_eq!
+ *   rows - 1 does not fit m's declared index width             SPRS_HIP_INDEX_OVERFLOW
+ * check_symmetric != 0 runs is_symmetric first (the reference's debug_assert!): SPRS_HIP_BAD_STRUCTURE "matrix is not
+ * symmetric".  Without it a non-symmetric pattern is ordered as the reference's loop orders it: along the stored direction —
+ * its one panic there included: the pseudo-peripheral search can return a vertex of an earlier component, SPRS_HIP_BAD_STRUCTURE
+ * "Vertex returned by starting strategy should always be unvisited" (ordering.rs:488-491).
+ * A 0 x 0 matrix gives an empty permutation and connected_parts == [0].  2^31 or more vertices: SPRS_HIP_INVALID_ARG. */
+#define SPRS_HIP_START_NEXT 0
+#define SPRS_HIP_START_MINIMUM_DEGREE 1
+#define SPRS_HIP_START_PSEUDO_PERIPHERAL 2
+typedef struct sprs_hip_ordering sprs_hip_ordering;
+int32_t sprs_hip_csmat_cuthill_mckee(const sprs_hip_csmat *m, int32_t start, int32_t reversed, int32_t check_symmetric,
+                                     sprs_hip_ordering **out, void *stream);
+/* dim, the number of entries of connected_parts (components + 1), and — stats may be NULL — four counters of the call that
+ * made the ordering: components, levels of the ordering pass, launches (a sort or a scan counts as one), host read-backs */
+int32_t sprs_hip_ordering_info(const sprs_hip_ordering *o, uint64_t *dim, uint64_t *n_parts, uint64_t *stats /* 4 */);
+/* Ordering::perm: a NEW owning permutation handle (perm and perm_inv) with the matrix's declared index width, as PermOwnedI<I> */
+int32_t sprs_hip_ordering_perm(const sprs_hip_ordering *o, sprs_hip_perm **out);
+/* Ordering::connected_parts to a host array of n_parts uint64_t */
+int32_t sprs_hip_ordering_parts(const sprs_hip_ordering *o, uint64_t *parts);
+int32_t sprs_hip_ordering_free(sprs_hip_ordering *o);
+
 /* ---- construction (sprs/src/sparse/kronecker.rs, construct.rs) -----------------------------------------------------------
  * New owning handles assembled on the device; indptr, indices and value bits are the reference's.  All operands of one call
  * must declare the same index and indptr widths (the reference's one I / Iptr): SPRS_HIP_STORAGE_MISMATCH otherwise.  The
@@ -678,6 +721,8 @@ int32_t sprs_hip_triplets_to_cs(uint64_t rows, uint64_t cols, uint64_t n, const 
  *                          level differences, not reproducible run to run; since round 4 no faster: the order costs nothing
  *                          once a wave instruction's products go out as ONE ds_add_f64, option spgemm_lane_order);
  * name = "gauss_seidel_blocks": workgroups of the Gauss-Seidel sweep kernel (0 = default: one per CU), "gauss_seidel_naps";
+ * name = "ordering_narrow_cap": Cuthill-McKee: widest frontier (vertices, default and maximum 1024) the one-workgroup kernel
+ *                          keeps in LDS; wider levels run as a grid; 0: every level does; "ordering_key_bits" (INTEGRATION.md);
  * name = "spgemm_*", "spmm_long_row", "spmm_stream", "pool", "pool_max_bytes": INTEGRATION.md, "Options".
  * The whole table (name, default, range) is SPRS_HIP_OPTIONS in sprs_amd/csrc/common.hpp.  Developer switches — timing
  * experiments with WRONG results (spgemm_debug, spmv_xmask, spmv_band_debug) and the profiling printout spgemm_prof — exist

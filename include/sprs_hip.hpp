@@ -103,6 +103,24 @@ public:
     // build the full SpMV plan now instead of at the handle's second multiply (sprs_hip_csmat_prepare): for callers that iterate
     void prepare(void *stream = nullptr) { check(sprs_hip_csmat_prepare(h_, stream)); }
 
+    // CsMat::degrees (csmat.rs:1205-1216): per outer index the stored entries off the diagonal
+    std::vector<uint64_t> degrees(void *stream = nullptr) const {
+        const Info i = info();
+        const uint64_t outer = i.storage == SPRS_HIP_CSR ? i.rows : i.cols;
+        std::vector<uint64_t> out(outer);
+        DeviceVec buf(outer);                        // (8 bytes per word)
+        check(sprs_hip_csmat_degrees(h_, (uint64_t *)buf.ptr(), stream));
+        check(sprs_hip_synchronize(stream));
+        if (outer) check(sprs_hip_memcpy_d2h(out.data(), buf.ptr(), outer * 8));
+        return out;
+    }
+    // CsMat::max_outer_nnz (csmat.rs:1188-1193)
+    uint64_t max_outer_nnz(void *stream = nullptr) const {
+        uint64_t v = 0;
+        check(sprs_hip_csmat_max_outer_nnz(h_, &v, stream));
+        return v;
+    }
+
     // into_raw_storage (csmat.rs:946-954) for 8-byte handles
     void to_host(std::vector<uint64_t> &indptr, std::vector<uint64_t> &indices, std::vector<double> &data) const {
         const Info i = info();
@@ -516,6 +534,53 @@ inline DeviceCsMat transform_mat_papt(const DeviceCsMat &mat, const DevicePerm &
     return DeviceCsMat(c);
 }
 }  // namespace permutation
+
+// Twin of sprs::sparse::linalg::ordering (linalg/ordering.rs) and of sprs::sparse::symmetric::is_symmetric: the matrix stays on
+// the device and the permutation arrives there, ready for permutation::transform_mat_papt.  The result is the reference's with
+// ties between vertices of equal degree broken by vertex id (the stable outcome of its sort_unstable_by_key).
+namespace ordering {
+enum class Start : int32_t {                         // start::{Next, MinimumDegree, PseudoPeripheral} (ordering.rs:14-267)
+    Next = SPRS_HIP_START_NEXT,
+    MinimumDegree = SPRS_HIP_START_MINIMUM_DEGREE,
+    PseudoPeripheral = SPRS_HIP_START_PSEUDO_PERIPHERAL,
+};
+enum class Order : int32_t { Forward = 0, Reversed = 1 };   // order::{Forward, Reversed} (ordering.rs:269-420)
+
+struct Ordering {                                    // ordering.rs:7-12
+    DevicePerm perm;
+    std::vector<uint64_t> connected_parts;
+    uint64_t stats[4];                               // components, levels of the ordering pass, launches, host read-backs
+};
+
+// cuthill_mckee_custom (ordering.rs:440-526); a non-square matrix throws the text of the reference's assert_eq!,
+// check_symmetric = true is its debug_assert!(is_symmetric(&mat)): "matrix is not symmetric"
+inline Ordering cuthill_mckee_custom(const DeviceCsMat &mat, Start start, Order order, bool check_symmetric = false, void *stream = nullptr) {
+    struct Handle {
+        sprs_hip_ordering *o = nullptr;
+        ~Handle() {
+            if (o) sprs_hip_ordering_free(o);
+        }
+    } h;
+    check(sprs_hip_csmat_cuthill_mckee(mat.handle(), (int32_t)start, (int32_t)order, check_symmetric ? 1 : 0, &h.o, stream));
+    uint64_t n_parts = 0, stats[4] = {0, 0, 0, 0};
+    check(sprs_hip_ordering_info(h.o, nullptr, &n_parts, stats));
+    std::vector<uint64_t> parts(n_parts);
+    check(sprs_hip_ordering_parts(h.o, parts.data()));
+    sprs_hip_perm *p = nullptr;
+    check(sprs_hip_ordering_perm(h.o, &p));
+    return Ordering{DevicePerm(p), std::move(parts), {stats[0], stats[1], stats[2], stats[3]}};
+}
+// reverse_cuthill_mckee (ordering.rs:546-559)
+inline Ordering reverse_cuthill_mckee(const DeviceCsMat &mat, void *stream = nullptr) {
+    return cuthill_mckee_custom(mat, Start::PseudoPeripheral, Order::Reversed, false, stream);
+}
+// is_symmetric (symmetric.rs:7-34)
+inline bool is_symmetric(const DeviceCsMat &mat, void *stream = nullptr) {
+    int32_t flag = 0;
+    check(sprs_hip_csmat_is_symmetric(mat.handle(), &flag, stream));
+    return flag != 0;
+}
+}  // namespace ordering
 
 // sprs::kronecker_product (kronecker.rs:50-99) and sprs::sparse::construct (construct.rs:10-160) on device handles.  The
 // reference's panics arrive as exceptions with its text; kronecker_product refuses by shape (SPRS_HIP_INDEX_OVERFLOW) what

@@ -24,6 +24,9 @@ pub const SPRS_HIP_ROUTE_PEER: i32 = 1;
 pub const SPRS_HIP_BINOP_ADD: i32 = 0;
 pub const SPRS_HIP_BINOP_SUB: i32 = 1;
 pub const SPRS_HIP_BINOP_MUL: i32 = 2;
+pub const SPRS_HIP_START_NEXT: i32 = 0;
+pub const SPRS_HIP_START_MINIMUM_DEGREE: i32 = 1;
+pub const SPRS_HIP_START_PSEUDO_PERIPHERAL: i32 = 2;
 
 #[repr(C)]
 pub struct sprs_hip_spgemm_plan {
@@ -47,6 +50,11 @@ pub struct sprs_hip_csvec {
 
 #[repr(C)]
 pub struct sprs_hip_perm {
+    _private: [u8; 0],
+}
+
+#[repr(C)]
+pub struct sprs_hip_ordering {
     _private: [u8; 0],
 }
 
@@ -235,6 +243,16 @@ extern "C" {
     pub fn sprs_hip_csmat_transform_papt(
         m: *const sprs_hip_csmat, p: *const sprs_hip_perm, out: *mut *mut sprs_hip_csmat, stream: *mut c_void,
     ) -> i32;
+    pub fn sprs_hip_csmat_is_symmetric(m: *const sprs_hip_csmat, flag: *mut i32, stream: *mut c_void) -> i32;
+    pub fn sprs_hip_csmat_degrees(m: *const sprs_hip_csmat, out_dev: *mut u64, stream: *mut c_void) -> i32;
+    pub fn sprs_hip_csmat_max_outer_nnz(m: *const sprs_hip_csmat, out: *mut u64, stream: *mut c_void) -> i32;
+    pub fn sprs_hip_csmat_cuthill_mckee(
+        m: *const sprs_hip_csmat, start: i32, reversed: i32, check_symmetric: i32, out: *mut *mut sprs_hip_ordering, stream: *mut c_void,
+    ) -> i32;
+    pub fn sprs_hip_ordering_info(o: *const sprs_hip_ordering, dim: *mut u64, n_parts: *mut u64, stats: *mut u64) -> i32;
+    pub fn sprs_hip_ordering_perm(o: *const sprs_hip_ordering, out: *mut *mut sprs_hip_perm) -> i32;
+    pub fn sprs_hip_ordering_parts(o: *const sprs_hip_ordering, parts: *mut u64) -> i32;
+    pub fn sprs_hip_ordering_free(o: *mut sprs_hip_ordering) -> i32;
     pub fn sprs_hip_csmat_kronecker_f64(
         a: *const sprs_hip_csmat, b: *const sprs_hip_csmat, out: *mut *mut sprs_hip_csmat, stream: *mut c_void,
     ) -> i32;

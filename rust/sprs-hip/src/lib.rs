@@ -875,6 +875,87 @@ pub mod permutation {
     }
 }
 
+impl DeviceCsMat {
+    /// `CsMat::degrees` (csmat.rs:1205-1216): per outer index the stored entries off the diagonal.
+    pub fn degrees(&self) -> Vec<usize> {
+        let (rows, cols, _, _, _, st) = self.info();
+        let outer = if st == sys::SPRS_HIP_CSR { rows } else { cols };
+        // (the words travel in a DeviceVec: 8 bytes each, released when it goes out of scope — also on a panic)
+        let buf = DeviceVec::zeros(outer);
+        unsafe { check(sys::sprs_hip_csmat_degrees(self.h, buf.ptr as *mut u64, std::ptr::null_mut())) };
+        let host: Vec<u64> = buf.to_vec().into_iter().map(f64::to_bits).collect();
+        host.into_iter().map(|d| d as usize).collect()
+    }
+
+    /// `CsMat::max_outer_nnz` (csmat.rs:1188-1193).
+    pub fn max_outer_nnz(&self) -> usize {
+        let mut v = 0u64;
+        unsafe { check(sys::sprs_hip_csmat_max_outer_nnz(self.h, &mut v, std::ptr::null_mut())) };
+        v as usize
+    }
+}
+
+/// Twin of `sprs::sparse::linalg::ordering` (linalg/ordering.rs) and of `sprs::sparse::symmetric::is_symmetric` for device
+/// operands: the matrix stays in HBM and the permutation arrives there, ready for `permutation::transform_mat_papt`.  The result is
+/// the reference's with ties between vertices of equal degree broken by vertex id (the stable outcome of its
+/// sort_unstable_by_key).  The start strategies and directions are values, not type parameters: the device runs the three
+/// strategies the reference ships.
+pub mod ordering {
+    use super::{check, sys, DeviceCsMat, DevicePerm};
+
+    /// `start::{Next, MinimumDegree, PseudoPeripheral}` (ordering.rs:14-267)
+    #[derive(Debug, Clone, Copy, PartialEq, Eq)]
+    pub enum Start {
+        Next = sys::SPRS_HIP_START_NEXT as isize,
+        MinimumDegree = sys::SPRS_HIP_START_MINIMUM_DEGREE as isize,
+        PseudoPeripheral = sys::SPRS_HIP_START_PSEUDO_PERIPHERAL as isize,
+    }
+
+    /// `order::{Forward, Reversed}` (ordering.rs:269-420)
+    #[derive(Debug, Clone, Copy, PartialEq, Eq)]
+    pub enum Order {
+        Forward = 0,
+        Reversed = 1,
+    }
+
+    /// `Ordering` (ordering.rs:7-12)
+    pub struct Ordering {
+        pub perm: DevicePerm,
+        pub connected_parts: Vec<usize>,
+    }
+
+    /// `cuthill_mckee_custom` (ordering.rs:440-526); panics with the text of the reference's assert_eq! on a non-square matrix.
+    pub fn cuthill_mckee_custom(mat: &DeviceCsMat, start: Start, order: Order) -> Ordering {
+        struct Handle(*mut sys::sprs_hip_ordering);
+        impl Drop for Handle {
+            fn drop(&mut self) {
+                unsafe { sys::sprs_hip_ordering_free(self.0) };
+            }
+        }
+        let mut o = Handle(std::ptr::null_mut());
+        unsafe { check(sys::sprs_hip_csmat_cuthill_mckee(mat.h, start as i32, order as i32, 0, &mut o.0, std::ptr::null_mut())) };
+        let mut n_parts = 0u64;
+        unsafe { check(sys::sprs_hip_ordering_info(o.0, std::ptr::null_mut(), &mut n_parts, std::ptr::null_mut())) };
+        let mut parts = vec![0u64; n_parts as usize];
+        unsafe { check(sys::sprs_hip_ordering_parts(o.0, parts.as_mut_ptr())) };
+        let mut perm: *mut sys::sprs_hip_perm = std::ptr::null_mut();
+        unsafe { check(sys::sprs_hip_ordering_perm(o.0, &mut perm)) };
+        Ordering { perm: DevicePerm { h: perm }, connected_parts: parts.into_iter().map(|p| p as usize).collect() }
+    }
+
+    /// `reverse_cuthill_mckee` (ordering.rs:546-559)
+    pub fn reverse_cuthill_mckee(mat: &DeviceCsMat) -> Ordering {
+        cuthill_mckee_custom(mat, Start::PseudoPeripheral, Order::Reversed)
+    }
+
+    /// `is_symmetric` (symmetric.rs:7-34)
+    pub fn is_symmetric(mat: &DeviceCsMat) -> bool {
+        let mut flag = 0i32;
+        unsafe { check(sys::sprs_hip_csmat_is_symmetric(mat.h, &mut flag, std::ptr::null_mut())) };
+        flag != 0
+    }
+}
+
 /// Twins of `sprs::kronecker_product` (kronecker.rs:50-99) and of `sprs::sparse::construct` (construct.rs:10-160) on device
 /// handles: same names, same argument order, the reference's panic texts.  One departure: `kronecker_product` panics by SHAPE
 /// (inner(a) * inner(b) - 1 or nnz(a) * nnz(b) beyond the index types) where the reference panics on a stored index.

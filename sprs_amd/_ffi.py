@@ -20,6 +20,7 @@ LOWER, UPPER = 0, 1
 ROW_MAJOR, COL_MAJOR = 0, 1
 ROUTE_RCCL, ROUTE_PEER = 0, 1
 BINOP_ADD, BINOP_SUB, BINOP_MUL = 0, 1, 2
+START_NEXT, START_MINIMUM_DEGREE, START_PSEUDO_PERIPHERAL = 0, 1, 2
 
 STATUS_NAMES = {
     OK: "OK", DIM_MISMATCH: "DIM_MISMATCH", STORAGE_MISMATCH: "STORAGE_MISMATCH",
@@ -116,6 +117,14 @@ SIGNATURES = {
     "sprs_hip_perm_mul_vec_f64": (i32, [vp, vp, vp, u64, vp]),
     "sprs_hip_csmat_transform_paq": (i32, [vp, vp, vp, P(vp), vp]),
     "sprs_hip_csmat_transform_papt": (i32, [vp, vp, P(vp), vp]),
+    "sprs_hip_csmat_is_symmetric": (i32, [vp, P(i32), vp]),
+    "sprs_hip_csmat_degrees": (i32, [vp, vp, vp]),
+    "sprs_hip_csmat_max_outer_nnz": (i32, [vp, P(u64), vp]),
+    "sprs_hip_csmat_cuthill_mckee": (i32, [vp, i32, i32, i32, P(vp), vp]),
+    "sprs_hip_ordering_info": (i32, [vp, P(u64), P(u64), P(u64)]),
+    "sprs_hip_ordering_perm": (i32, [vp, P(vp)]),
+    "sprs_hip_ordering_parts": (i32, [vp, vp]),
+    "sprs_hip_ordering_free": (i32, [vp]),
     "sprs_hip_csmat_kronecker_f64": (i32, [vp, vp, P(vp), vp]),
     "sprs_hip_csmat_same_storage_fast_stack": (i32, [P(vp), u64, P(vp), vp]),
     "sprs_hip_csmat_vstack": (i32, [P(vp), u64, P(vp), vp]),

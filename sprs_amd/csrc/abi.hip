@@ -1384,6 +1384,96 @@ int32_t sprs_hip_csmat_transform_papt(const sprs_hip_csmat *m, const sprs_hip_pe
 
 }  // extern "C"
 
+// ---- orderings (linalg/ordering.rs, symmetric.rs, csmat.rs:1188-1216); kernels in ordering.hpp ----------------------------------
+
+extern "C" {
+
+int32_t sprs_hip_csmat_is_symmetric(const sprs_hip_csmat *m, int32_t *flag, void *stream) {
+    clear_error();
+    if (!m || !flag) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    return csmat_is_symmetric(m, flag, (hipStream_t)stream);
+}
+
+int32_t sprs_hip_csmat_degrees(const sprs_hip_csmat *m, uint64_t *out_dev, void *stream) {
+    clear_error();
+    if (!m) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if (m->outer() && !out_dev) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL output");
+    if ((uintptr_t)out_dev % 8) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "device buffers must be aligned to their element size");
+    return csmat_degrees(m, out_dev, (hipStream_t)stream);
+}
+
+int32_t sprs_hip_csmat_max_outer_nnz(const sprs_hip_csmat *m, uint64_t *out, void *stream) {
+    clear_error();
+    if (!m || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    return csmat_max_outer_nnz(m, out, (hipStream_t)stream);
+}
+
+int32_t sprs_hip_csmat_cuthill_mckee(const sprs_hip_csmat *m, int32_t start, int32_t reversed, int32_t check_symmetric,
+                                     sprs_hip_ordering **out, void *stream) {
+    clear_error();
+    if (!m || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    if (start != SPRS_HIP_START_NEXT && start != SPRS_HIP_START_MINIMUM_DEGREE && start != SPRS_HIP_START_PSEUDO_PERIPHERAL)
+        SPRS_FAIL(SPRS_HIP_INVALID_ARG, "bad start strategy %d", start);
+    if (m->cols != m->rows)                          // assert_eq!(mat.cols(), mat.rows()), ordering.rs:453
+        SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "assertion `left == right` failed\n  left: %llu\n right: %llu", (unsigned long long)m->cols,
+                  (unsigned long long)m->rows);
+    if (m->rows && m->rows - 1 > width_max(m->user_idx_bytes()))   // I::from_usize(vertex_index), ordering.rs:333
+        SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "Index type is not large enough to hold %llu", (unsigned long long)(m->rows - 1));
+    if (check_symmetric) {                           // debug_assert!(is_symmetric(&mat)), ordering.rs:452
+        int32_t sym = 0;
+        SPRS_TRY(csmat_is_symmetric(m, &sym, (hipStream_t)stream));
+        if (!sym) SPRS_FAIL(SPRS_HIP_BAD_STRUCTURE, "matrix is not symmetric");
+    }
+    std::unique_ptr<sprs_hip_ordering> o(make_ordering());
+    SPRS_TRY(csmat_cuthill_mckee(m, start, reversed != 0, o.get(), (hipStream_t)stream));
+    *out = o.release();
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_ordering_info(const sprs_hip_ordering *o, uint64_t *dim, uint64_t *n_parts, uint64_t *stats) {
+    clear_error();
+    if (!o) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if (dim) *dim = o->dim;
+    if (n_parts) *n_parts = o->parts.size();
+    if (stats)
+        for (int k = 0; k < 4; ++k) stats[k] = o->stats[k];
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_ordering_perm(const sprs_hip_ordering *o, sprs_hip_perm **out) {
+    clear_error();
+    if (!o || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    const sprs_hip_perm *p = o->perm.get();
+    OwnedPerm q;
+    SPRS_TRY(make_perm(q, p->dim, p->idx_bytes, p->user_idx_bytes()));
+    if (p->dim) {
+        const uint64_t bytes = p->dim * (uint64_t)p->idx_bytes;
+        hipError_t e = hipMemcpyAsync(q->perm, p->perm, bytes, hipMemcpyDeviceToDevice, nullptr);
+        if (e == hipSuccess) e = hipMemcpyAsync(q->perm_inv, p->perm_inv, bytes, hipMemcpyDeviceToDevice, nullptr);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        if (e != hipSuccess) return fail_hip(e, "ordering_perm");
+    }
+    *out = q.release();
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_ordering_parts(const sprs_hip_ordering *o, uint64_t *parts) {
+    clear_error();
+    if (!o || !parts) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    for (size_t k = 0; k < o->parts.size(); ++k) parts[k] = o->parts[k];
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_ordering_free(sprs_hip_ordering *o) {
+    clear_error();
+    delete o;
+    return SPRS_HIP_OK;
+}
+
+}  // extern "C"
+
 // ---- construction (kronecker.rs, construct.rs); kernels in construct.hpp --------------------------------------------------------
 
 // the one I / Iptr of the reference's signatures

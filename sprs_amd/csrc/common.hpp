@@ -111,6 +111,8 @@ constexpr bool DEVTOOLS = false;
     X(perm_cap, 4096, 4096, 4096, 0)    /* longest row a relabelling permutation sorts in LDS by one workgroup (perm.hpp); longer rows go through the radix sort: fixed, published for the tests */ \
     X(construct_tile, 2048, 2048, 2048, 0) /* result entries (Kronecker product) / block entries (stacking) per workgroup of the construction kernels (construct.hpp): fixed, published so that tests can place tile edges */ \
     X(dense_tile, 2048, 2048, 2048, 0)  /* dense elements (from_dense) / stored entries (assign_to_dense, the sparse-with-dense binops) per workgroup of the dense <-> sparse kernels (dense.hpp): fixed, published so that tests can place tile edges */ \
+    X(ordering_narrow_cap, 1024, 0, 1024, 0) /* Cuthill-McKee (ordering.hpp): a frontier of at most this many vertices (and at most 4096 stored entries) is expanded, sorted and committed in LDS by the one-workgroup kernel, which goes on to the next level or component without returning to the host; wider levels run as a grid; 0: every level runs as a grid.  Published so that tests can put the seam at 8 vertices */ \
+    X(ordering_key_bits, 64, 1, 64, 0)  /* Cuthill-McKee, wide levels: the key (owner, degree, id) goes through ONE radix sort when it fits this many bits, else through two stable ones (by id, then by owner and degree); 64 = whenever it fits a word.  Published so that tests can take the second route */ \
     X(pool, 1, 0, 1, 0)                 /* keep released result blocks (>= 1 MiB) for the next result instead of hipFree */        \
     X(pool_max_bytes, 128ll << 30, 0, INT64_MAX, 0) /* cap on the bytes the pool may hold */
 
@@ -323,6 +325,14 @@ struct sprs_hip_perm {
     int device = 0;
 };
 
+// Device twin of Ordering (sprs/src/sparse/linalg/ordering.rs:7-12): the permutation and the component delimiters.
+struct sprs_hip_ordering {
+    uint64_t dim = 0;
+    std::unique_ptr<sprs_hip_perm> perm;           // perm and perm_inv in the matrix's index widths
+    std::vector<uint64_t> parts;                   // connected_parts
+    uint64_t stats[4] = {0, 0, 0, 0};              // components, levels of the ordering pass, launches (a sort or a scan counts as one), host read-backs
+};
+
 // Device twin of CsMatBase (sprs/src/sparse.rs:94-122).
 struct sprs_hip_csmat {
     int32_t storage = SPRS_HIP_CSR;
@@ -451,6 +461,11 @@ int32_t csmat_permute(const sprs_hip_csmat *m, const void *o, const void *g, Own
 int32_t perm_build_inverse(sprs_hip_perm *p, bool validate, hipStream_t stream);
 int32_t perm_is_identity(const sprs_hip_perm *p, int32_t *flag, hipStream_t stream);
 int32_t perm_mul_vec_f64(const sprs_hip_perm *p, const double *x, double *y, hipStream_t stream);
+// ordering.hpp (compiled in convert.hip): everything walks the outer dimension; host results are complete on `stream` at return
+int32_t csmat_is_symmetric(const sprs_hip_csmat *m, int32_t *flag, hipStream_t stream);
+int32_t csmat_degrees(const sprs_hip_csmat *m, uint64_t *out_dev, hipStream_t stream);   // ordered on `stream`
+int32_t csmat_max_outer_nnz(const sprs_hip_csmat *m, uint64_t *out, hipStream_t stream);
+int32_t csmat_cuthill_mckee(const sprs_hip_csmat *m, int32_t strategy, bool reversed, sprs_hip_ordering *o, hipStream_t stream);
 // construct.hpp (compiled in convert.hip): operands of equal storage and index widths; complete on `stream` at return
 int32_t csmat_kronecker_f64(const sprs_hip_csmat *a, const sprs_hip_csmat *b, OwnedCsmat &out, hipStream_t stream);
 // the block assembly behind the four stacking functions: the present blocks by super-row, each with the shift of its inner indices
@@ -492,6 +507,7 @@ sprs_hip_csmat *view_csmat(int32_t storage, uint64_t rows, uint64_t cols, uint64
                            const void *indices, int32_t idx_bytes, const double *data, int device, sprs_hip_csmat *into = nullptr);
 sprs_hip_csvec *view_csvec(uint64_t dim, uint64_t nnz, const void *indices, int32_t idx_bytes, const double *data, int device);
 sprs_hip_perm *identity_perm(uint64_t dim, int32_t idx_bytes);
+sprs_hip_ordering *make_ordering();                 // empty: csmat_cuthill_mckee fills it
 // a view of m's arrays with m's declared widths and device; transpose: transpose_view (csmat.rs:982-991) — free, flips the tag
 sprs_hip_csmat *view_csmat(const sprs_hip_csmat *m, bool transpose, sprs_hip_csmat *into = nullptr);
 // an owned matrix of m's storage, shape and widths whose indptr, indices and (with_data) values are copies of m's, enqueued

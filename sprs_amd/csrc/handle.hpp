@@ -194,6 +194,8 @@ sprs_hip_perm *identity_perm(uint64_t dim, int32_t idx_bytes) {
     return p;
 }
 
+sprs_hip_ordering *make_ordering() { return new sprs_hip_ordering(); }
+
 // ---- device copy ------------------------------------------------------------------------------------
 int32_t copy_csmat(const sprs_hip_csmat *m, bool with_data, OwnedCsmat &out, hipStream_t stream) {
     OwnedCsmat res;

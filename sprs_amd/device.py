@@ -208,6 +208,25 @@ class DeviceCsMat:
         check(lib.sprs_hip_csmat_to_other_storage(self._h, C.byref(h)))
         return DeviceCsMat(h.value)
 
+    def degrees(self, stream=None, out=None):
+        """csmat.rs:1205-1216: per outer index the stored entries off the diagonal, as a host uint64 array.  `out`: a
+        DeviceVec of outer-dimension words that receives the counts instead (they stay on the device; returns out)."""
+        outer = self.rows() if self.is_csr() else self.cols()
+        buf = DeviceVec(outer) if out is None else out
+        check(lib.sprs_hip_csmat_degrees(self._h, C.c_void_p(buf.ptr), _stream_arg(stream)))
+        if out is not None:
+            return out
+        check(lib.sprs_hip_synchronize(_stream_arg(stream)))
+        res = np.empty(outer, dtype=np.uint64)
+        check(lib.sprs_hip_memcpy_d2h(_vp(res), C.c_void_p(buf.ptr), outer * 8))
+        return res
+
+    def max_outer_nnz(self, stream=None):
+        """csmat.rs:1188-1193."""
+        v = C.c_uint64()
+        check(lib.sprs_hip_csmat_max_outer_nnz(self._h, C.byref(v), _stream_arg(stream)))
+        return v.value
+
     # -- operators: `&A * &x`, `&A * &B` ---------------------------------------
     def __mul__(self, rhs):
         from . import prod
