@@ -580,6 +580,63 @@ int32_t sprs_hip_ordering_perm(const sprs_hip_ordering *o, sprs_hip_perm **out);
 int32_t sprs_hip_ordering_parts(const sprs_hip_ordering *o, uint64_t *parts);
 int32_t sprs_hip_ordering_free(sprs_hip_ordering *o);
 
+/* ---- LDL^T factorization (sprs-ldl/src/lib.rs, sprs/src/sparse/linalg.rs:17-29) --------------------------------------------
+ * P A P^T = L D L^T for a symmetric matrix, f64.  Everything walks the OUTER dimension of the handle as the reference does
+ * (outer_iterator_papt, csmat.rs:1170-1185), so a CSR and a CSC handle of a symmetric matrix give the same factors; only for a
+ * non-symmetric matrix with the check off do they differ, as they do in the reference.  colptr, parents, l_indices and every bit
+ * of l_data and d are the reference's: the numeric pass walks the pattern of each row in the order the reference's stack leaves
+ * it in.  `stream` comes last: the kernels run there, handles and host results are complete on return.
+ *
+ * ldl_symbolic (lib.rs:445-496; LdlSymbolic::new_perm, lib.rs:252-284): perm = NULL is the identity.  Before any device work:
+ *   NULL m / out                                              SPRS_HIP_INVALID_ARG
+ *   rows != cols ("matrix should be square"), perm.dim != rows  SPRS_HIP_DIM_MISMATCH
+ *   perm's declared index width differs from m's               SPRS_HIP_STORAGE_MISMATCH
+ * check_symmetry != 0 runs is_symmetric first: SPRS_HIP_BAD_STRUCTURE "Matrix is not symmetric" (lib.rs:461-463).
+ * SPRS_HIP_INDEX_OVERFLOW when nnz(L) does not fit m's declared index width.  n = 0 and n = 1 are accepted (factor is not). */
+typedef struct sprs_hip_ldl_sym sprs_hip_ldl_sym;
+typedef struct sprs_hip_ldl_num sprs_hip_ldl_num;
+int32_t sprs_hip_ldl_symbolic(const sprs_hip_csmat *m, const sprs_hip_perm *perm, int32_t check_symmetry, sprs_hip_ldl_sym **out,
+                              void *stream);
+/* problem_size (lib.rs:288), nnz (lib.rs:294) and — stats may be NULL — four counters of the call that made the handle: launches
+ * of the elimination-tree pass, all launches (a sort or a scan counts as one), host read-backs, 0 */
+int32_t sprs_hip_ldl_symbolic_info(const sprs_hip_ldl_sym *s, uint64_t *n, uint64_t *nnz, uint64_t *stats /* 4 */);
+/* l_colptr to a host array of n + 1 uint64_t */
+int32_t sprs_hip_ldl_symbolic_colptr(const sprs_hip_ldl_sym *s, uint64_t *colptr);
+/* the elimination tree to a host array of n uint64_t: parents[i], UINT64_MAX for a root (etree.rs: None) */
+int32_t sprs_hip_ldl_symbolic_parents(const sprs_hip_ldl_sym *s, uint64_t *parents);
+/* the permutation the analysis was made with: a NEW handle (the Identity variant when none was given) */
+int32_t sprs_hip_ldl_symbolic_perm(const sprs_hip_ldl_sym *s, sprs_hip_perm **out);
+int32_t sprs_hip_ldl_symbolic_free(sprs_hip_ldl_sym *s);
+/* LdlSymbolic::factor (lib.rs:300-323): a numeric handle that shares s's analysis and keeps it alive (s may be freed, or
+ * factored again).  m: square, of s's dimension (SPRS_HIP_DIM_MISMATCH) and index type (SPRS_HIP_STORAGE_MISMATCH), with the
+ * pattern that was analysed (a stored entry outside it: SPRS_HIP_HIP_ERROR, nothing is written out of range).
+ *   n < 2        SPRS_HIP_INVALID_ARG  "assertion failed: n > 1 (DStack::with_capacity, sprs/src/stack.rs:39)" (lib.rs:313)
+ *   d[k] == 0    SPRS_HIP_SINGULAR_MATRIX "Singular matrix at index k (diagonal element is a numeric 0)" (lib.rs:585-590) with the
+ *                smallest such k; info (may be NULL) then holds singular_index = k, singular_reason = 1, as after
+ *                sprs_hip_trisolve_f64; no handle is returned
+ * Nothing else is checked, as in the reference.  A polling loop that times out is SPRS_HIP_HIP_ERROR, never a hang. */
+int32_t sprs_hip_ldl_factor_f64(const sprs_hip_ldl_sym *s, const sprs_hip_csmat *m, sprs_hip_ldl_num **out,
+                                sprs_hip_trisolve_info *info, void *stream);
+/* LdlNumeric::update (lib.rs:364-381): the same with new values into the handle's arrays; after an error its factors are
+ * unspecified */
+int32_t sprs_hip_ldl_update_f64(sprs_hip_ldl_num *f, const sprs_hip_csmat *m, sprs_hip_trisolve_info *info, void *stream);
+/* LdlNumeric::solve (lib.rs:388-410): x = P^-1 ltsolve(diag_solve(lsolve(P b))) for DEVICE arrays of n doubles (x may be b) */
+int32_t sprs_hip_ldl_solve_f64(sprs_hip_ldl_num *f, const double *b_dev, double *x_dev, uint64_t n, void *stream);
+/* LdlNumeric::d (lib.rs:413): the n pivots into a DEVICE array.  Asynchronous on `stream`. */
+int32_t sprs_hip_ldl_d(const sprs_hip_ldl_num *f, double *d_dev, uint64_t n, void *stream);
+/* LdlNumeric::l (lib.rs:418-429): a NEW owning CSC handle, n x n, strictly lower, no diagonal stored; indptr and indices both in
+ * the index type of the matrix that was analysed */
+int32_t sprs_hip_ldl_l(const sprs_hip_ldl_num *f, sprs_hip_csmat **out, void *stream);
+int32_t sprs_hip_ldl_numeric_free(sprs_hip_ldl_num *f);
+/* ldl_lsolve (lib.rs:597-609) and ldl_ltsolve (lib.rs:613-626), in place on the n doubles of x_dev, for a CSC handle that is
+ * STRICTLY lower triangular with an implied unit diagonal (what sprs_hip_ldl_l returns; entries on or above the diagonal are not
+ * read).  lsolve: columns 0 .. n-1 scatter, so x[r] receives its products by ascending column; ltsolve: columns n-1 .. 0, each
+ * subtracting in stored order.  SPRS_HIP_STORAGE_MISMATCH for a CSR handle, SPRS_HIP_DIM_MISMATCH as sprs_hip_trisolve_f64. */
+int32_t sprs_hip_ldl_lsolve_f64(sprs_hip_csmat *l, double *x_dev, uint64_t n, void *stream);
+int32_t sprs_hip_ldl_ltsolve_f64(sprs_hip_csmat *l, double *x_dev, uint64_t n, void *stream);
+/* linalg::diag_solve (linalg.rs:17-29): x[i] /= d[i] on DEVICE arrays.  Asynchronous on `stream`. */
+int32_t sprs_hip_diag_solve_f64(const double *d_dev, double *x_dev, uint64_t n, void *stream);
+
 /* ---- construction (sprs/src/sparse/kronecker.rs, construct.rs) -----------------------------------------------------------
  * New owning handles assembled on the device; indptr, indices and value bits are the reference's.  All operands of one call
  * must declare the same index and indptr widths (the reference's one I / Iptr): SPRS_HIP_STORAGE_MISMATCH otherwise.  The
@@ -723,6 +780,8 @@ int32_t sprs_hip_triplets_to_cs(uint64_t rows, uint64_t cols, uint64_t n, const 
  * name = "gauss_seidel_blocks": workgroups of the Gauss-Seidel sweep kernel (0 = default: one per CU), "gauss_seidel_naps";
  * name = "ordering_narrow_cap": Cuthill-McKee: widest frontier (vertices, default and maximum 1024) the one-workgroup kernel
  *                          keeps in LDS; wider levels run as a grid; 0: every level does; "ordering_key_bits" (INTEGRATION.md);
+ * name = "ldl_lds_cap":    LDL^T numeric pass: longest row of L (entries, default and maximum 1024) whose work vector stays in
+ *                          LDS; longer rows use a slice of a device array.  Same bits either way;
  * name = "spgemm_*", "spmm_long_row", "spmm_stream", "pool", "pool_max_bytes": INTEGRATION.md, "Options".
  * The whole table (name, default, range) is SPRS_HIP_OPTIONS in sprs_amd/csrc/common.hpp.  Developer switches — timing
  * experiments with WRONG results (spgemm_debug, spmv_xmask, spmv_band_debug) and the profiling printout spgemm_prof — exist

@@ -582,6 +582,145 @@ inline bool is_symmetric(const DeviceCsMat &mat, void *stream = nullptr) {
 }
 }  // namespace ordering
 
+// Twin of the sprs-ldl crate (sprs-ldl/src/lib.rs): P A P^T = L D L^T on the device, f64.  l_colptr, the elimination tree,
+// l_indices and every bit of l_data, d and the solutions are the reference's.  Its panics and its Err(SingularMatrix) arrive as
+// exceptions with its text (SPRS_HIP_SINGULAR_MATRIX: SingularMatrix::index holds the pivot).
+namespace ldl {
+enum class FillInReduction { NoReduction, ReverseCuthillMcKee, CAMDSuiteSparse };
+
+struct SingularMatrix : Error {                      // LinalgError::SingularMatrix (lib.rs:585-590)
+    uint64_t index;
+    SingularMatrix(const std::string &m, uint64_t k) : Error(SPRS_HIP_SINGULAR_MATRIX, m), index(k) {}
+};
+
+class LdlNumeric {                                   // lib.rs:102-111, 326-442
+public:
+    explicit LdlNumeric(sprs_hip_ldl_num *h, uint64_t n, uint64_t nnz) : h_(h), n_(n), nnz_(nnz) {}
+    LdlNumeric(LdlNumeric &&o) noexcept : h_(o.h_), n_(o.n_), nnz_(o.nnz_) { o.h_ = nullptr; }
+    LdlNumeric(const LdlNumeric &) = delete;
+    LdlNumeric &operator=(const LdlNumeric &) = delete;
+    ~LdlNumeric() {
+        if (h_) sprs_hip_ldl_numeric_free(h_);
+    }
+    // update (lib.rs:364-381): new values on the pattern that was analysed
+    void update(const DeviceCsMat &mat, void *stream = nullptr) {
+        sprs_hip_trisolve_info info{};
+        const int32_t st = sprs_hip_ldl_update_f64(h_, mat.handle(), &info, stream);
+        if (st == SPRS_HIP_SINGULAR_MATRIX) throw SingularMatrix(sprs_hip_last_error(), info.singular_index);
+        check(st);
+    }
+    // solve (lib.rs:388-410)
+    DeviceVec solve(const DeviceVec &rhs, void *stream = nullptr) const {
+        DeviceVec x(rhs.dim());
+        check(sprs_hip_ldl_solve_f64(h_, rhs.ptr(), x.ptr(), rhs.dim(), stream));
+        return x;
+    }
+    DeviceVec d(void *stream = nullptr) const {      // lib.rs:413
+        DeviceVec out(n_);
+        check(sprs_hip_ldl_d(h_, out.ptr(), n_, stream));
+        check(sprs_hip_synchronize(stream));
+        return out;
+    }
+    DeviceCsMat l(void *stream = nullptr) const {    // lib.rs:418-429: CSC, no diagonal stored
+        sprs_hip_csmat *c = nullptr;
+        check(sprs_hip_ldl_l(h_, &c, stream));
+        return DeviceCsMat(c);
+    }
+    uint64_t problem_size() const { return n_; }     // lib.rs:433
+    uint64_t nnz() const { return nnz_; }            // lib.rs:439
+
+private:
+    sprs_hip_ldl_num *h_ = nullptr;
+    uint64_t n_ = 0, nnz_ = 0;
+};
+
+class LdlSymbolic {                                  // lib.rs:94-100, 228-324
+public:
+    // new_perm (lib.rs:252-284); perm = nullptr is the identity.  LdlSymbolic::new is (mat, nullptr, true)
+    explicit LdlSymbolic(const DeviceCsMat &mat, const DevicePerm *perm = nullptr, bool check_symmetry = true, void *stream = nullptr) {
+        check(sprs_hip_ldl_symbolic(mat.handle(), perm ? perm->handle() : nullptr, check_symmetry ? 1 : 0, &h_, stream));
+        check(sprs_hip_ldl_symbolic_info(h_, &n_, &nnz_, stats_));
+    }
+    LdlSymbolic(LdlSymbolic &&o) noexcept : h_(o.h_), n_(o.n_), nnz_(o.nnz_) {
+        o.h_ = nullptr;
+        for (int k = 0; k < 4; ++k) stats_[k] = o.stats_[k];
+    }
+    LdlSymbolic(const LdlSymbolic &) = delete;
+    LdlSymbolic &operator=(const LdlSymbolic &) = delete;
+    ~LdlSymbolic() {
+        if (h_) sprs_hip_ldl_symbolic_free(h_);
+    }
+    uint64_t problem_size() const { return n_; }     // lib.rs:288
+    uint64_t nnz() const { return nnz_; }            // lib.rs:294
+    const uint64_t *stats() const { return stats_; } // launches of the etree pass, all launches, host read-backs, 0
+    std::vector<uint64_t> colptr() const {
+        std::vector<uint64_t> out(n_ + 1);
+        check(sprs_hip_ldl_symbolic_colptr(h_, out.data()));
+        return out;
+    }
+    std::vector<uint64_t> parents() const {          // UINT64_MAX for a root
+        std::vector<uint64_t> out(n_ ? n_ : 1);
+        check(sprs_hip_ldl_symbolic_parents(h_, out.data()));
+        out.resize(n_);
+        return out;
+    }
+    DevicePerm perm() const {
+        sprs_hip_perm *p = nullptr;
+        check(sprs_hip_ldl_symbolic_perm(h_, &p));
+        return DevicePerm(p);
+    }
+    // factor (lib.rs:300-323).  The reference consumes self; here the handle stays usable.
+    LdlNumeric factor(const DeviceCsMat &mat, void *stream = nullptr) const {
+        sprs_hip_ldl_num *f = nullptr;
+        sprs_hip_trisolve_info info{};
+        const int32_t st = sprs_hip_ldl_factor_f64(h_, mat.handle(), &f, &info, stream);
+        if (st == SPRS_HIP_SINGULAR_MATRIX) throw SingularMatrix(sprs_hip_last_error(), info.singular_index);
+        check(st);
+        return LdlNumeric(f, n_, nnz_);
+    }
+
+private:
+    sprs_hip_ldl_sym *h_ = nullptr;
+    uint64_t n_ = 0, nnz_ = 0, stats_[4] = {0, 0, 0, 0};
+};
+
+// The builder (lib.rs:74-226).  Defaults: symmetry checked, reverse Cuthill-McKee; check_perm is kept for the signature and,
+// as in the reference's native path, never read.
+class Ldl {
+public:
+    Ldl check_symmetry(bool check) const { return Ldl(check, perm_, fill_); }
+    Ldl check_perm(bool check) const { return Ldl(sym_, check, fill_); }
+    Ldl fill_in_reduction(FillInReduction method) const { return Ldl(sym_, perm_, method); }
+    Ldl() = default;
+    LdlSymbolic symbolic(const DeviceCsMat &mat, void *stream = nullptr) const {       // lib.rs:139-170
+        if (fill_ == FillInReduction::NoReduction) return LdlSymbolic(mat, nullptr, sym_, stream);
+        if (fill_ == FillInReduction::CAMDSuiteSparse)
+            throw Error(SPRS_HIP_INVALID_ARG, "Unavailable without the `sprs_suitesparse_camd` feature");
+        const ordering::Ordering o = ordering::reverse_cuthill_mckee(mat, stream);
+        return LdlSymbolic(mat, &o.perm, sym_, stream);
+    }
+    LdlNumeric numeric(const DeviceCsMat &mat, void *stream = nullptr) const { return symbolic(mat, stream).factor(mat, stream); }   // lib.rs:190-201
+
+private:
+    Ldl(bool sym, bool perm, FillInReduction fill) : sym_(sym), perm_(perm), fill_(fill) {}
+    bool sym_ = true, perm_ = true;
+    FillInReduction fill_ = FillInReduction::ReverseCuthillMcKee;
+};
+
+// ldl_lsolve (lib.rs:597-609), ldl_ltsolve (lib.rs:613-626): in place, l a strictly lower CSC matrix with an implied unit diagonal
+inline void ldl_lsolve(const DeviceCsMat &l, DeviceVec &x, void *stream = nullptr) {
+    check(sprs_hip_ldl_lsolve_f64(const_cast<sprs_hip_csmat *>(l.handle()), x.ptr(), x.dim(), stream));
+}
+inline void ldl_ltsolve(const DeviceCsMat &l, DeviceVec &x, void *stream = nullptr) {
+    check(sprs_hip_ldl_ltsolve_f64(const_cast<sprs_hip_csmat *>(l.handle()), x.ptr(), x.dim(), stream));
+}
+// linalg::diag_solve (sprs/src/sparse/linalg.rs:17-29): x[i] /= d[i]
+inline void diag_solve(const DeviceVec &d, DeviceVec &x, void *stream = nullptr) {
+    if (d.dim() != x.dim()) throw Error(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    check(sprs_hip_diag_solve_f64(d.ptr(), x.ptr(), x.dim(), stream));
+}
+}  // namespace ldl
+
 // sprs::kronecker_product (kronecker.rs:50-99) and sprs::sparse::construct (construct.rs:10-160) on device handles.  The
 // reference's panics arrive as exceptions with its text; kronecker_product refuses by shape (SPRS_HIP_INDEX_OVERFLOW) what
 // the reference refuses by stored index.

@@ -58,6 +58,16 @@ pub struct sprs_hip_ordering {
     _private: [u8; 0],
 }
 
+#[repr(C)]
+pub struct sprs_hip_ldl_sym {
+    _private: [u8; 0],
+}
+
+#[repr(C)]
+pub struct sprs_hip_ldl_num {
+    _private: [u8; 0],
+}
+
 /// counters of BiCGSTAB::solve (include/sprs_hip.h)
 #[repr(C)]
 #[derive(Debug, Clone, Copy, Default)]
@@ -253,6 +263,26 @@ extern "C" {
     pub fn sprs_hip_ordering_perm(o: *const sprs_hip_ordering, out: *mut *mut sprs_hip_perm) -> i32;
     pub fn sprs_hip_ordering_parts(o: *const sprs_hip_ordering, parts: *mut u64) -> i32;
     pub fn sprs_hip_ordering_free(o: *mut sprs_hip_ordering) -> i32;
+    pub fn sprs_hip_ldl_symbolic(
+        m: *const sprs_hip_csmat, perm: *const sprs_hip_perm, check_symmetry: i32, out: *mut *mut sprs_hip_ldl_sym, stream: *mut c_void,
+    ) -> i32;
+    pub fn sprs_hip_ldl_symbolic_info(s: *const sprs_hip_ldl_sym, n: *mut u64, nnz: *mut u64, stats: *mut u64) -> i32;
+    pub fn sprs_hip_ldl_symbolic_colptr(s: *const sprs_hip_ldl_sym, colptr: *mut u64) -> i32;
+    pub fn sprs_hip_ldl_symbolic_parents(s: *const sprs_hip_ldl_sym, parents: *mut u64) -> i32;
+    pub fn sprs_hip_ldl_symbolic_perm(s: *const sprs_hip_ldl_sym, out: *mut *mut sprs_hip_perm) -> i32;
+    pub fn sprs_hip_ldl_symbolic_free(s: *mut sprs_hip_ldl_sym) -> i32;
+    pub fn sprs_hip_ldl_factor_f64(
+        s: *const sprs_hip_ldl_sym, m: *const sprs_hip_csmat, out: *mut *mut sprs_hip_ldl_num, info: *mut sprs_hip_trisolve_info,
+        stream: *mut c_void,
+    ) -> i32;
+    pub fn sprs_hip_ldl_update_f64(f: *mut sprs_hip_ldl_num, m: *const sprs_hip_csmat, info: *mut sprs_hip_trisolve_info, stream: *mut c_void) -> i32;
+    pub fn sprs_hip_ldl_solve_f64(f: *mut sprs_hip_ldl_num, b_dev: *const f64, x_dev: *mut f64, n: u64, stream: *mut c_void) -> i32;
+    pub fn sprs_hip_ldl_d(f: *const sprs_hip_ldl_num, d_dev: *mut f64, n: u64, stream: *mut c_void) -> i32;
+    pub fn sprs_hip_ldl_l(f: *const sprs_hip_ldl_num, out: *mut *mut sprs_hip_csmat, stream: *mut c_void) -> i32;
+    pub fn sprs_hip_ldl_numeric_free(f: *mut sprs_hip_ldl_num) -> i32;
+    pub fn sprs_hip_ldl_lsolve_f64(l: *mut sprs_hip_csmat, x_dev: *mut f64, n: u64, stream: *mut c_void) -> i32;
+    pub fn sprs_hip_ldl_ltsolve_f64(l: *mut sprs_hip_csmat, x_dev: *mut f64, n: u64, stream: *mut c_void) -> i32;
+    pub fn sprs_hip_diag_solve_f64(d_dev: *const f64, x_dev: *mut f64, n: u64, stream: *mut c_void) -> i32;
     pub fn sprs_hip_csmat_kronecker_f64(
         a: *const sprs_hip_csmat, b: *const sprs_hip_csmat, out: *mut *mut sprs_hip_csmat, stream: *mut c_void,
     ) -> i32;

@@ -956,6 +956,240 @@ pub mod ordering {
     }
 }
 
+/// Twin of the `sprs-ldl` crate (sprs-ldl/src/lib.rs) for device operands: `Ldl`, `LdlSymbolic`, `LdlNumeric`, `ldl_lsolve`,
+/// `ldl_ltsolve` and `diag_solve` under the reference's names, f64.  l_colptr, the elimination tree, l_indices and every bit of
+/// l_data, d and the solutions are the reference's.  Its panics arrive as panics with its text, `Err(SingularMatrix)` as `Err`.
+pub mod ldl {
+    use super::{check, sys, DeviceCsMat, DevicePerm, DeviceVec};
+    use sprs::errors::{LinalgError, SingularMatrixInfo};
+    pub use sprs::{FillInReduction, PermutationCheck, SymmetryCheck};
+
+    fn singular(info: &sys::sprs_hip_trisolve_info) -> LinalgError {
+        LinalgError::SingularMatrix(SingularMatrixInfo { index: info.singular_index as usize, reason: "diagonal element is a numeric 0" })
+    }
+
+    /// `LdlSymbolic` (lib.rs:94-100, 228-324)
+    pub struct LdlSymbolic {
+        h: *mut sys::sprs_hip_ldl_sym,
+        n: usize,
+        nnz: usize,
+    }
+
+    /// `LdlNumeric` (lib.rs:102-111, 326-442)
+    pub struct LdlNumeric {
+        h: *mut sys::sprs_hip_ldl_num,
+        n: usize,
+        nnz: usize,
+    }
+
+    unsafe impl Send for LdlSymbolic {}
+    unsafe impl Send for LdlNumeric {}
+
+    impl LdlSymbolic {
+        /// `LdlSymbolic::new` (lib.rs:234-241)
+        pub fn new(mat: &DeviceCsMat) -> Self {
+            Self::new_perm(mat, None, SymmetryCheck::CheckSymmetry)
+        }
+
+        /// `LdlSymbolic::new_perm` (lib.rs:252-284); `None` is the identity.
+        pub fn new_perm(mat: &DeviceCsMat, perm: Option<&DevicePerm>, check_symmetry: SymmetryCheck) -> Self {
+            let mut h = std::ptr::null_mut();
+            let p = perm.map_or(std::ptr::null(), |p| p.h as *const sys::sprs_hip_perm);
+            let chk = matches!(check_symmetry, SymmetryCheck::CheckSymmetry) as i32;
+            unsafe { check(sys::sprs_hip_ldl_symbolic(mat.h, p, chk, &mut h, std::ptr::null_mut())) };
+            let (mut n, mut nnz) = (0u64, 0u64);
+            unsafe { check(sys::sprs_hip_ldl_symbolic_info(h, &mut n, &mut nnz, std::ptr::null_mut())) };
+            Self { h, n: n as usize, nnz: nnz as usize }
+        }
+
+        /// lib.rs:288
+        pub fn problem_size(&self) -> usize {
+            self.n
+        }
+
+        /// lib.rs:294
+        pub fn nnz(&self) -> usize {
+            self.nnz
+        }
+
+        /// l_colptr
+        pub fn colptr(&self) -> Vec<usize> {
+            let mut out = vec![0u64; self.n + 1];
+            unsafe { check(sys::sprs_hip_ldl_symbolic_colptr(self.h, out.as_mut_ptr())) };
+            out.into_iter().map(|v| v as usize).collect()
+        }
+
+        /// the elimination tree, `None` for a root (etree.rs)
+        pub fn parents(&self) -> Vec<Option<usize>> {
+            let mut out = vec![0u64; self.n.max(1)];
+            unsafe { check(sys::sprs_hip_ldl_symbolic_parents(self.h, out.as_mut_ptr())) };
+            out.truncate(self.n);
+            out.into_iter().map(|v| if v == u64::MAX { None } else { Some(v as usize) }).collect()
+        }
+
+        pub fn perm(&self) -> DevicePerm {
+            let mut p: *mut sys::sprs_hip_perm = std::ptr::null_mut();
+            unsafe { check(sys::sprs_hip_ldl_symbolic_perm(self.h, &mut p)) };
+            DevicePerm { h: p }
+        }
+
+        /// `LdlSymbolic::factor` (lib.rs:300-323)
+        pub fn factor(self, mat: &DeviceCsMat) -> Result<LdlNumeric, LinalgError> {
+            let mut f = std::ptr::null_mut();
+            let mut info = sys::sprs_hip_trisolve_info::default();
+            let st = unsafe { sys::sprs_hip_ldl_factor_f64(self.h, mat.h, &mut f, &mut info, std::ptr::null_mut()) };
+            if st == sys::SPRS_HIP_SINGULAR_MATRIX {
+                return Err(singular(&info));
+            }
+            check(st);
+            Ok(LdlNumeric { h: f, n: self.n, nnz: self.nnz })
+        }
+    }
+
+    impl Drop for LdlSymbolic {
+        fn drop(&mut self) {
+            unsafe { sys::sprs_hip_ldl_symbolic_free(self.h) };
+        }
+    }
+
+    impl LdlNumeric {
+        /// `LdlNumeric::new` (lib.rs:332-338)
+        pub fn new(mat: &DeviceCsMat) -> Result<Self, LinalgError> {
+            LdlSymbolic::new(mat).factor(mat)
+        }
+
+        /// `LdlNumeric::new_perm` (lib.rs:349-359)
+        pub fn new_perm(mat: &DeviceCsMat, perm: Option<&DevicePerm>, check_symmetry: SymmetryCheck) -> Result<Self, LinalgError> {
+            LdlSymbolic::new_perm(mat, perm, check_symmetry).factor(mat)
+        }
+
+        /// `LdlNumeric::update` (lib.rs:364-381)
+        pub fn update(&mut self, mat: &DeviceCsMat) -> Result<(), LinalgError> {
+            let mut info = sys::sprs_hip_trisolve_info::default();
+            let st = unsafe { sys::sprs_hip_ldl_update_f64(self.h, mat.h, &mut info, std::ptr::null_mut()) };
+            if st == sys::SPRS_HIP_SINGULAR_MATRIX {
+                return Err(singular(&info));
+            }
+            check(st);
+            Ok(())
+        }
+
+        /// `LdlNumeric::solve` (lib.rs:388-410)
+        pub fn solve(&self, rhs: &DeviceVec) -> DeviceVec {
+            let x = DeviceVec::zeros(rhs.len);
+            unsafe { check(sys::sprs_hip_ldl_solve_f64(self.h, rhs.ptr as *const f64, x.ptr, rhs.len as u64, std::ptr::null_mut())) };
+            x
+        }
+
+        /// lib.rs:413
+        pub fn d(&self) -> DeviceVec {
+            let out = DeviceVec::zeros(self.n);
+            unsafe {
+                check(sys::sprs_hip_ldl_d(self.h, out.ptr, self.n as u64, std::ptr::null_mut()));
+                check(sys::sprs_hip_synchronize(std::ptr::null_mut()));
+            }
+            out
+        }
+
+        /// lib.rs:418-429: CSC, no diagonal stored
+        pub fn l(&self) -> DeviceCsMat {
+            let mut h: *mut sys::sprs_hip_csmat = std::ptr::null_mut();
+            unsafe { check(sys::sprs_hip_ldl_l(self.h, &mut h, std::ptr::null_mut())) };
+            DeviceCsMat { h }
+        }
+
+        /// lib.rs:433
+        pub fn problem_size(&self) -> usize {
+            self.n
+        }
+
+        /// lib.rs:439
+        pub fn nnz(&self) -> usize {
+            self.nnz
+        }
+    }
+
+    impl Drop for LdlNumeric {
+        fn drop(&mut self) {
+            unsafe { sys::sprs_hip_ldl_numeric_free(self.h) };
+        }
+    }
+
+    /// The builder (lib.rs:74-226); `check_perm` is kept and, as in the reference's native path, never read.
+    #[derive(Copy, Clone, Debug)]
+    pub struct Ldl {
+        check_symmetry: SymmetryCheck,
+        check_perm: PermutationCheck,
+        fill_red_method: FillInReduction,
+    }
+
+    impl Default for Ldl {
+        fn default() -> Self {
+            Self {
+                check_symmetry: SymmetryCheck::CheckSymmetry,
+                fill_red_method: FillInReduction::ReverseCuthillMcKee,
+                check_perm: PermutationCheck::CheckPerm,
+            }
+        }
+    }
+
+    impl Ldl {
+        pub fn new() -> Self {
+            Self::default()
+        }
+
+        pub fn check_symmetry(self, check: SymmetryCheck) -> Self {
+            Self { check_symmetry: check, ..self }
+        }
+
+        pub fn check_perm(self, check: PermutationCheck) -> Self {
+            Self { check_perm: check, ..self }
+        }
+
+        pub fn fill_in_reduction(self, method: FillInReduction) -> Self {
+            Self { fill_red_method: method, ..self }
+        }
+
+        /// lib.rs:139-162: `None` stands for `PermOwnedI::identity`
+        pub fn perm(&self, mat: &DeviceCsMat) -> Option<DevicePerm> {
+            match self.fill_red_method {
+                FillInReduction::NoReduction => None,
+                FillInReduction::ReverseCuthillMcKee => Some(super::ordering::reverse_cuthill_mckee(mat).perm),
+                FillInReduction::CAMDSuiteSparse => panic!("Unavailable without the `sprs_suitesparse_camd` feature"),
+                _ => unreachable!("Unhandled method, report a bug at https://github.com/vbarrielle/sprs/issues/199"),
+            }
+        }
+
+        /// lib.rs:164-170
+        pub fn symbolic(self, mat: &DeviceCsMat) -> LdlSymbolic {
+            let _ = self.check_perm;
+            let perm = self.perm(mat);
+            LdlSymbolic::new_perm(mat, perm.as_ref(), self.check_symmetry)
+        }
+
+        /// lib.rs:190-201
+        pub fn numeric(self, mat: &DeviceCsMat) -> Result<LdlNumeric, LinalgError> {
+            self.symbolic(mat).factor(mat)
+        }
+    }
+
+    /// `ldl_lsolve` (lib.rs:597-609), in place: `l` a strictly lower CSC matrix with an implied unit diagonal.
+    pub fn ldl_lsolve(l: &DeviceCsMat, x: &mut DeviceVec) {
+        unsafe { check(sys::sprs_hip_ldl_lsolve_f64(l.h, x.ptr, x.len as u64, std::ptr::null_mut())) };
+    }
+
+    /// `ldl_ltsolve` (lib.rs:613-626)
+    pub fn ldl_ltsolve(l: &DeviceCsMat, x: &mut DeviceVec) {
+        unsafe { check(sys::sprs_hip_ldl_ltsolve_f64(l.h, x.ptr, x.len as u64, std::ptr::null_mut())) };
+    }
+
+    /// `linalg::diag_solve` (sprs/src/sparse/linalg.rs:17-29): `x[i] /= diag[i]`
+    pub fn diag_solve(diag: &DeviceVec, x: &mut DeviceVec) {
+        assert_eq!(diag.len, x.len);
+        unsafe { check(sys::sprs_hip_diag_solve_f64(diag.ptr as *const f64, x.ptr, x.len as u64, std::ptr::null_mut())) };
+    }
+}
+
 /// Twins of `sprs::kronecker_product` (kronecker.rs:50-99) and of `sprs::sparse::construct` (construct.rs:10-160) on device
 /// handles: same names, same argument order, the reference's panic texts.  One departure: `kronecker_product` panics by SHAPE
 /// (inner(a) * inner(b) - 1 or nnz(a) * nnz(b) beyond the index types) where the reference panics on a stored index.

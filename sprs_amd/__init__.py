@@ -2,17 +2,18 @@
 
 Product code: libsprs_hip.so (sprs_amd/csrc, hand-written HIP behind the C ABI
 of include/sprs_hip.h) and this thin host mirror of the reference interface
-(`prod`, `smmp`, `binop`, `permutation`, `construct`, `ordering`, DeviceCsMat/DeviceVec with `*`).  Importing fails loudly when
+(`prod`, `smmp`, `binop`, `permutation`, `construct`, `ordering`, `ldl`, DeviceCsMat/DeviceVec with `*`).  Importing fails loudly when
 the shared library is absent; nothing here computes on the CPU.
 """
 from . import _ffi
 from ._ffi import CSC, CSR, SprsHipError
 from .device import DeviceCsMat, DeviceCsVec, DeviceVec
-from . import prod, smmp, linalg, binop, permutation, construct, to_dense, ordering
+from . import prod, smmp, linalg, binop, permutation, construct, to_dense, ordering, ldl
 from .construct import bmat, hstack, kronecker_product, same_storage_fast_stack, vstack
 from .permutation import DevicePerm
 from .ordering import Ordering, cuthill_mckee_custom, is_symmetric, reverse_cuthill_mckee
-from .linalg import lsolve_csc_dense_rhs, lsolve_csr_dense_rhs, usolve_csc_dense_rhs, usolve_csr_dense_rhs
+from .ldl import FillInReduction, Ldl, LdlNumeric, LdlSymbolic, PermutationCheck, SymmetryCheck, ldl_lsolve, ldl_ltsolve
+from .linalg import diag_solve, lsolve_csc_dense_rhs, lsolve_csr_dense_rhs, usolve_csc_dense_rhs, usolve_csr_dense_rhs
 
 
 def device_count():

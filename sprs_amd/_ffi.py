@@ -125,7 +125,22 @@ SIGNATURES = {
     "sprs_hip_ordering_perm": (i32, [vp, P(vp)]),
     "sprs_hip_ordering_parts": (i32, [vp, vp]),
     "sprs_hip_ordering_free": (i32, [vp]),
-    "sprs_hip_csmat_kronecker_f64": (i32, [vp, vp, P(vp), vp]),
+    "sprs_hip_ldl_symbolic": (i32, [vp, vp, i32, P(vp), vp]),
+    "sprs_hip_ldl_symbolic_info": (i32, [vp, P(u64), P(u64), P(u64)]),
+    "sprs_hip_ldl_symbolic_colptr": (i32, [vp, vp]),
+    "sprs_hip_ldl_symbolic_parents": (i32, [vp, vp]),
+    "sprs_hip_ldl_symbolic_perm": (i32, [vp, P(vp)]),
+    "sprs_hip_ldl_symbolic_free": (i32, [vp]),
+    "sprs_hip_ldl_factor_f64": (i32, [vp, vp, P(vp), vp, vp]),
+    "sprs_hip_ldl_update_f64": (i32, [vp, vp, vp, vp]),
+    "sprs_hip_ldl_solve_f64": (i32, [vp, vp, vp, u64, vp]),
+    "sprs_hip_ldl_d": (i32, [vp, vp, u64, vp]),
+    "sprs_hip_ldl_l": (i32, [vp, P(vp), vp]),
+    "sprs_hip_ldl_numeric_free": (i32, [vp]),
+    "sprs_hip_ldl_lsolve_f64": (i32, [vp, vp, u64, vp]),
+    "sprs_hip_ldl_ltsolve_f64": (i32, [vp, vp, u64, vp]),
+    "sprs_hip_diag_solve_f64": (i32, [vp, vp, u64, vp]),
+    "sprs_hip_csmat_kronecker_f64":(i32, [vp, vp, P(vp), vp]),
     "sprs_hip_csmat_same_storage_fast_stack": (i32, [P(vp), u64, P(vp), vp]),
     "sprs_hip_csmat_vstack": (i32, [P(vp), u64, P(vp), vp]),
     "sprs_hip_csmat_hstack": (i32, [P(vp), u64, P(vp), vp]),

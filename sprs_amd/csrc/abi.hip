@@ -1474,6 +1474,178 @@ int32_t sprs_hip_ordering_free(sprs_hip_ordering *o) {
 
 }  // extern "C"
 
+// ---- LDL^T (sprs-ldl/src/lib.rs, sprs/src/sparse/linalg.rs:17-29); kernels in ldl.hpp --------------------------------------------
+
+// the matrix a factor / update call takes against the analysis it is factored with
+static int32_t ldl_matrix_ok(const LdlSym &s, const sprs_hip_csmat *m) {
+    if (m->rows != m->cols) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "matrix should be square");      // lib.rs:262
+    if (m->rows != s.n) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");                 // assert!(diag.len() == mat.outer_dims()), lib.rs:521
+    if (m->idx_bytes != s.idx_bytes || m->user_idx_bytes() != (s.decl_idx_bytes ? s.decl_idx_bytes : s.idx_bytes))
+        SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "the matrix must have the index type of the one that was analysed");
+    // DStack::with_capacity(n) in LdlSymbolic::factor (lib.rs:313)
+    if (s.n < 2) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "assertion failed: n > 1 (DStack::with_capacity, sprs/src/stack.rs:39)");
+    return SPRS_HIP_OK;
+}
+
+extern "C" {
+
+int32_t sprs_hip_ldl_symbolic(const sprs_hip_csmat *m, const sprs_hip_perm *perm, int32_t check_symmetry, sprs_hip_ldl_sym **out, void *stream) {
+    clear_error();
+    if (!m || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    if (m->rows != m->cols) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "matrix should be square");      // lib.rs:262
+    if (perm && perm->dim != m->rows) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    SPRS_TRY(perm_width_ok(m, perm));
+    if (m->rows >= (1ull << 31)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "LDL: 2^31 rows or more are not supported");
+    std::unique_ptr<sprs_hip_ldl_sym> h(make_ldl_symbolic());
+    if (check_symmetry) {                            // lib.rs:458-465
+        int32_t sym = 0;
+        SPRS_TRY(csmat_is_symmetric(m, &sym, (hipStream_t)stream));
+        ++h->s->stats[2];
+        if (!sym) SPRS_FAIL(SPRS_HIP_BAD_STRUCTURE, "Matrix is not symmetric");
+    }
+    SPRS_TRY(ldl_symbolic(m, perm, *h->s, (hipStream_t)stream));
+    if (h->s->lnz > width_max(m->user_idx_bytes()))  // prev += l_nz[k] in I (lib.rs:493)
+        SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "Index type is not large enough to hold %llu", (unsigned long long)h->s->lnz);
+    *out = h.release();
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_ldl_symbolic_info(const sprs_hip_ldl_sym *s, uint64_t *n, uint64_t *nnz, uint64_t *stats) {
+    clear_error();
+    if (!s) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if (n) *n = s->s->n;
+    if (nnz) *nnz = s->s->lnz;
+    if (stats)
+        for (int k = 0; k < 4; ++k) stats[k] = s->s->stats[k];
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_ldl_symbolic_colptr(const sprs_hip_ldl_sym *s, uint64_t *colptr) {
+    clear_error();
+    if (!s || !colptr) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    SPRS_TRY_HIP(copy_to_host(colptr, s->s->colptr, (s->s->n + 1) * 8, nullptr));
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_ldl_symbolic_parents(const sprs_hip_ldl_sym *s, uint64_t *parents) {
+    clear_error();
+    if (!s || (s->s->n && !parents)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    std::vector<uint32_t> p32(s->s->n);
+    if (s->s->n) SPRS_TRY_HIP(copy_to_host(p32.data(), s->s->parents, s->s->n * sizeof(uint32_t), nullptr));
+    for (uint64_t i = 0; i < s->s->n; ++i) parents[i] = p32[i] == 0xFFFFFFFFu ? UINT64_MAX : (uint64_t)p32[i];
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_ldl_symbolic_perm(const sprs_hip_ldl_sym *s, sprs_hip_perm **out) {
+    clear_error();
+    if (!s || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    const sprs_hip_perm *p = s->s->perm.get();
+    if (p->identity) {
+        *out = identity_perm(p->dim, p->user_idx_bytes());
+        return SPRS_HIP_OK;
+    }
+    OwnedPerm q;
+    SPRS_TRY(make_perm(q, p->dim, p->idx_bytes, p->user_idx_bytes()));
+    if (p->dim) {
+        const uint64_t bytes = p->dim * (uint64_t)p->idx_bytes;
+        hipError_t e = hipMemcpyAsync(q->perm, p->perm, bytes, hipMemcpyDeviceToDevice, nullptr);
+        if (e == hipSuccess) e = hipMemcpyAsync(q->perm_inv, p->perm_inv, bytes, hipMemcpyDeviceToDevice, nullptr);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        if (e != hipSuccess) return fail_hip(e, "ldl_symbolic_perm");
+    }
+    *out = q.release();
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_ldl_symbolic_free(sprs_hip_ldl_sym *s) {
+    clear_error();
+    delete s;
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_ldl_factor_f64(const sprs_hip_ldl_sym *s, const sprs_hip_csmat *m, sprs_hip_ldl_num **out, sprs_hip_trisolve_info *info,
+                                void *stream) {
+    clear_error();
+    if (!s || !m || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    if (info) *info = sprs_hip_trisolve_info{0, UINT64_MAX, 0};
+    SPRS_TRY(ldl_matrix_ok(*s->s, m));
+    std::unique_ptr<sprs_hip_ldl_num> f(make_ldl_numeric(s));
+    SPRS_TRY(ldl_factor_f64(*f->s, m, f.get(), info, (hipStream_t)stream));
+    *out = f.release();
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_ldl_update_f64(sprs_hip_ldl_num *f, const sprs_hip_csmat *m, sprs_hip_trisolve_info *info, void *stream) {
+    clear_error();
+    if (!f || !m) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    if (info) *info = sprs_hip_trisolve_info{0, UINT64_MAX, 0};
+    SPRS_TRY(ldl_matrix_ok(*f->s, m));
+    return ldl_factor_f64(*f->s, m, f, info, (hipStream_t)stream);
+}
+
+int32_t sprs_hip_ldl_solve_f64(sprs_hip_ldl_num *f, const double *b_dev, double *x_dev, uint64_t n, void *stream) {
+    clear_error();
+    if (!f) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if (n != f->s->n) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    if (n && (!b_dev || !x_dev)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL vector");
+    return ldl_solve_f64(f, b_dev, x_dev, (hipStream_t)stream);
+}
+
+int32_t sprs_hip_ldl_d(const sprs_hip_ldl_num *f, double *d_dev, uint64_t n, void *stream) {
+    clear_error();
+    if (!f) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if (n != f->s->n) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    if (n && !d_dev) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL vector");
+    if (n) SPRS_TRY_HIP(hipMemcpyAsync(d_dev, f->d.p, n * sizeof(double), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_ldl_l(const sprs_hip_ldl_num *f, sprs_hip_csmat **out, void *stream) {
+    clear_error();
+    if (!f || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    OwnedCsmat res;
+    SPRS_TRY(ldl_export_l(f, res, (hipStream_t)stream));
+    *out = res.release();
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_ldl_numeric_free(sprs_hip_ldl_num *f) {
+    clear_error();
+    delete f;
+    return SPRS_HIP_OK;
+}
+
+static int32_t ldl_tri_entry(sprs_hip_csmat *l, bool transposed, double *x_dev, uint64_t n, void *stream) {
+    clear_error();
+    if (!l) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if (l->storage != SPRS_HIP_CSC) SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "Storage mismatch");
+    if (l->rows != l->cols) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Non square matrix passed to solver");
+    if (l->cols != n) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    if (n && !x_dev) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL vector");
+    if (n >= (1ull << 32)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "triangular solve: 2^32 rows or more are not supported");
+    if (n == 0) return SPRS_HIP_OK;
+    std::lock_guard<std::recursive_mutex> lock(l->mu);
+    sprs_hip_csmat *csr = nullptr;
+    if (!transposed) SPRS_TRY(csr_form(l, &csr));
+    return ldl_tri_f64(l, csr, transposed, x_dev, (hipStream_t)stream);
+}
+
+int32_t sprs_hip_ldl_lsolve_f64(sprs_hip_csmat *l, double *x_dev, uint64_t n, void *stream) { return ldl_tri_entry(l, false, x_dev, n, stream); }
+
+int32_t sprs_hip_ldl_ltsolve_f64(sprs_hip_csmat *l, double *x_dev, uint64_t n, void *stream) { return ldl_tri_entry(l, true, x_dev, n, stream); }
+
+int32_t sprs_hip_diag_solve_f64(const double *d_dev, double *x_dev, uint64_t n, void *stream) {
+    clear_error();
+    if (n && (!d_dev || !x_dev)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL vector");
+    return diag_solve_f64(d_dev, x_dev, n, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
 // ---- construction (kronecker.rs, construct.rs); kernels in construct.hpp --------------------------------------------------------
 
 // the one I / Iptr of the reference's signatures

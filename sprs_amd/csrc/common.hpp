@@ -113,6 +113,7 @@ constexpr bool DEVTOOLS = false;
     X(dense_tile, 2048, 2048, 2048, 0)  /* dense elements (from_dense) / stored entries (assign_to_dense, the sparse-with-dense binops) per workgroup of the dense <-> sparse kernels (dense.hpp): fixed, published so that tests can place tile edges */ \
     X(ordering_narrow_cap, 1024, 0, 1024, 0) /* Cuthill-McKee (ordering.hpp): a frontier of at most this many vertices (and at most 4096 stored entries) is expanded, sorted and committed in LDS by the one-workgroup kernel, which goes on to the next level or component without returning to the host; wider levels run as a grid; 0: every level runs as a grid.  Published so that tests can put the seam at 8 vertices */ \
     X(ordering_key_bits, 64, 1, 64, 0)  /* Cuthill-McKee, wide levels: the key (owner, degree, id) goes through ONE radix sort when it fits this many bits, else through two stable ones (by id, then by owner and degree); 64 = whenever it fits a word.  Published so that tests can take the second route */ \
+    X(ldl_lds_cap, 1024, 1, 1024, 0)    /* LDL^T numeric kernel (ldl.hpp): a row of L with at most this many entries keeps its work vector y in LDS, a longer one in its slice of a device array.  Published so that tests can run both paths at small n */ \
     X(pool, 1, 0, 1, 0)                 /* keep released result blocks (>= 1 MiB) for the next result instead of hipFree */        \
     X(pool_max_bytes, 128ll << 30, 0, INT64_MAX, 0) /* cap on the bytes the pool may hold */
 
@@ -334,6 +335,40 @@ struct sprs_hip_ordering {
 };
 
 // Device twin of CsMatBase (sprs/src/sparse.rs:94-122).
+struct sprs_hip_csmat;
+namespace sprs_hip {
+// What LdlSymbolic holds (sprs-ldl/src/lib.rs:94-100) plus the structure of L that the reference only writes during the numeric
+// pass: shared by the symbolic handle and by every numeric handle made from it (ldl.hpp).
+struct LdlSym {
+    uint64_t n = 0, lnz = 0;
+    int device = 0;
+
+
+    int32_t idx_bytes = 8, iptr_bytes = 8, decl_idx_bytes = 0;
+    std::unique_ptr<sprs_hip_perm> perm;           // the Identity variant or perm and perm_inv, in the matrix's index width
+    uint32_t *parents = nullptr;                   // n: elimination tree, 0xFFFFFFFF for a root
+    uint64_t *colptr = nullptr;                    // n + 1: l_colptr
+    uint32_t *l_indices = nullptr;                 // lnz: rows of L by column, ascending (the reference's l_indices)
+    uint32_t *col_of_slot = nullptr;               // lnz: the column of every slot of the arrays above
+    uint64_t *rowptr = nullptr;                    // n + 1: L by rows ...
+    uint32_t *row_cols = nullptr;                  // lnz: ... columns ascending ...
+    uint64_t *row_slot = nullptr;                  // lnz: ... and the column-form slot of every row entry
+    uint64_t *walk_slot = nullptr;                 // lnz: per row, the column-form slots in the order the reference's pattern stack is walked
+    uint32_t *walk_pos = nullptr;                  // lnz: the position inside its row (ascending columns) of every walk entry
+    std::vector<DevBuf> blocks;                    // the blocks behind the arrays above
+    std::mutex mu;                                 // guards the two level plans
+    GsPlan lower, upper;                           // level orders of L by rows (lsolve) and of L^T (ltsolve): built at the first solve
+    uint64_t stats[4] = {0, 0, 0, 0};              // launches of the etree pass, all launches (a sort or a scan counts as one), host read-backs, 0
+};
+}  // namespace sprs_hip
+struct sprs_hip_ldl_sym {
+    std::shared_ptr<sprs_hip::LdlSym> s;
+};
+struct sprs_hip_ldl_num {
+    std::shared_ptr<sprs_hip::LdlSym> s;           // the numeric handle keeps the analysis alive
+    sprs_hip::DevBuf l_data, d, row_vals;          // lnz values by column (l_data), n pivots, lnz values by row (for lsolve)
+};
+
 struct sprs_hip_csmat {
     int32_t storage = SPRS_HIP_CSR;
     uint64_t rows = 0, cols = 0, nnz = 0;
@@ -490,6 +525,14 @@ int32_t gauss_seidel_f64(sprs_hip_csmat *a, double *x, const double *rhs, uint64
                          sprs_hip_gauss_seidel_info *info, hipStream_t stream);
 // trisolve.hpp (compiled in gauss_seidel.hip): csr = the CSR form of the caller's handle, csc = that handle is CSC
 int32_t trisolve_f64(sprs_hip_csmat *csr, bool upper, bool csc, double *x, uint64_t n, sprs_hip_trisolve_info *info, hipStream_t stream);
+// ldl.hpp (compiled in gauss_seidel.hip): twins of sprs-ldl/src/lib.rs; p = null for the identity.  Complete on `stream` at return
+int32_t ldl_symbolic(const sprs_hip_csmat *m, const sprs_hip_perm *p, LdlSym &s, hipStream_t stream);
+int32_t ldl_factor_f64(LdlSym &s, const sprs_hip_csmat *m, sprs_hip_ldl_num *num, sprs_hip_trisolve_info *info, hipStream_t stream);
+int32_t ldl_export_l(const sprs_hip_ldl_num *num, OwnedCsmat &out, hipStream_t stream);
+int32_t ldl_solve_f64(sprs_hip_ldl_num *num, const double *b, double *x, hipStream_t stream);
+// ldl_lsolve (transposed = false) / ldl_ltsolve (true) on the arrays of a CSC handle (csr = its CSR form, for lsolve)
+int32_t ldl_tri_f64(sprs_hip_csmat *l, sprs_hip_csmat *csr, bool transposed, double *x, hipStream_t stream);
+int32_t diag_solve_f64(const double *d, double *x, uint64_t n, hipStream_t stream);
 int32_t slice_outer(const sprs_hip_csmat *m, uint64_t start, uint64_t end, OwnedCsmat &out);
 // csvec.hpp (compiled in spmv.hip)
 int32_t csvec_check_device(const sprs_hip_csvec *v, hipStream_t stream);
@@ -508,6 +551,8 @@ sprs_hip_csmat *view_csmat(int32_t storage, uint64_t rows, uint64_t cols, uint64
 sprs_hip_csvec *view_csvec(uint64_t dim, uint64_t nnz, const void *indices, int32_t idx_bytes, const double *data, int device);
 sprs_hip_perm *identity_perm(uint64_t dim, int32_t idx_bytes);
 sprs_hip_ordering *make_ordering();                 // empty: csmat_cuthill_mckee fills it
+sprs_hip_ldl_sym *make_ldl_symbolic();         // with a fresh, empty LdlSym: ldl_symbolic fills it
+sprs_hip_ldl_num *make_ldl_numeric(const sprs_hip_ldl_sym *sym);   // shares sym's analysis; arrays empty
 // a view of m's arrays with m's declared widths and device; transpose: transpose_view (csmat.rs:982-991) — free, flips the tag
 sprs_hip_csmat *view_csmat(const sprs_hip_csmat *m, bool transpose, sprs_hip_csmat *into = nullptr);
 // an owned matrix of m's storage, shape and widths whose indptr, indices and (with_data) values are copies of m's, enqueued

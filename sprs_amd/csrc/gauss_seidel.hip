@@ -800,6 +800,10 @@ int32_t gs_impl(sprs_hip_csmat *a, double *x, const double *rhs, uint64_t n, uin
 // trisolve.hpp, compiled here: they share the level plan and the device helpers above
 #include "trisolve.hpp"
 
+// LDL^T factorization (sprs-ldl): the etree pass, the numeric kernel and the unit-diagonal solves share the hand-off, the level
+// plans and tri_solve_kernel
+#include "ldl.hpp"
+
 int32_t gauss_seidel_f64(sprs_hip_csmat *a, double *x, const double *rhs, uint64_t n, uint64_t max_iter, double eps,
                          sprs_hip_gauss_seidel_info *info, hipStream_t stream) {
     if (n >= (1ull << 32)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "Gauss-Seidel: 2^32 rows or more are not supported");

@@ -196,6 +196,18 @@ sprs_hip_perm *identity_perm(uint64_t dim, int32_t idx_bytes) {
 
 sprs_hip_ordering *make_ordering() { return new sprs_hip_ordering(); }
 
+sprs_hip_ldl_sym *make_ldl_symbolic() {
+    auto *h = new sprs_hip_ldl_sym();
+    h->s = std::make_shared<LdlSym>();
+    return h;
+}
+
+sprs_hip_ldl_num *make_ldl_numeric(const sprs_hip_ldl_sym *sym) {
+    auto *h = new sprs_hip_ldl_num();
+    h->s = sym->s;
+    return h;
+}
+
 // ---- device copy ------------------------------------------------------------------------------------
 int32_t copy_csmat(const sprs_hip_csmat *m, bool with_data, OwnedCsmat &out, hipStream_t stream) {
     OwnedCsmat res;

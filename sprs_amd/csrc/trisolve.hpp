@@ -35,7 +35,9 @@ namespace {
 
 constexpr unsigned int TS_SINGULAR = 4u;                      // status bit beside GS_NO_DIAG / GS_TIMEOUT
 
-template <typename IDX, typename PTR, bool UPPER, bool BACKWARD>
+// UNIT: the diagonal is 1 and not stored (the factor L of ldl.hpp: ldl_lsolve / ldl_ltsolve, sprs-ldl/src/lib.rs:595-626); a row
+// is then its chain of subtractions, never divided and never singular.
+template <typename IDX, typename PTR, bool UPPER, bool BACKWARD, bool UNIT = false>
 __global__ __launch_bounds__(GS_BLOCK) void tri_solve_kernel(const PTR *__restrict__ indptr, const IDX *__restrict__ indices,
                                                              const double *__restrict__ data, const uint32_t *__restrict__ order,
                                                              double *x, unsigned long long *work, uint64_t n,
@@ -117,9 +119,9 @@ __global__ __launch_bounds__(GS_BLOCK) void tri_solve_kernel(const PTR *__restri
                     loaded = false;
                     moved = true;
                     if (last || p == end) {
-                        const double xr = acc / diag;           // trisolve.rs:70, 134, 193, 259
+                        const double xr = UNIT ? acc : acc / diag;   // trisolve.rs:70, 134, 193, 259
                         unsigned long long out = (unsigned long long)__double_as_longlong(xr);
-                        if (!has_diag || diag == 0.0) {
+                        if (!UNIT && (!has_diag || diag == 0.0)) {
                             const unsigned long long word = ((unsigned long long)row << 1) | (has_diag ? 0ull : (unsigned long long)structural);
                             if (UPPER) atomicMax(singular, word);
                             else atomicMin(singular, word);
@@ -140,15 +142,11 @@ __global__ __launch_bounds__(GS_BLOCK) void tri_solve_kernel(const PTR *__restri
     }
 }
 
+// one solve over arrays in CSR form, rows taken in `order`: the launch and the read-back of the status words into hw
+// ([0] chunks drawn, [1] status, [2..3] the singular word)
 template <typename IDX, typename PTR>
-int32_t trisolve_impl(sprs_hip_csmat *a, bool upper, bool csc, double *x, uint64_t n, sprs_hip_trisolve_info *info, hipStream_t stream) {
-    // held from the look-up of the row order to the end of the (blocking) solve, the way gs_impl holds it
-    std::lock_guard<std::recursive_mutex> lock(a->mu);
-    GsPlan &pl = upper ? a->tri_upper : a->gs;                 // lower: exactly the Gauss-Seidel order
-    if (!pl.built) SPRS_TRY(upper ? (gs_plan_build<IDX, PTR, true>(a, pl)) : (gs_plan_build<IDX, PTR, false>(a, pl)));
-    if (info) info->levels = pl.nlevels;
-
-    unsigned int hw[4] = {0, 0, 0, 0};                         // [0] chunks drawn, [1] status, [2..3] the singular word
+int32_t tri_run(const void *indptr, const void *indices, const double *data, const uint32_t *order, bool upper, bool csc, bool unit,
+                double *x, uint64_t n, unsigned int *hw, hipStream_t stream) {
     DevBuf work, words;
     StreamDrain drain{stream};
     SPRS_TRY_HIP(work.alloc(n * sizeof(double)));
@@ -166,15 +164,30 @@ int32_t trisolve_impl(sprs_hip_csmat *a, bool upper, bool csc, double *x, uint64
     uint64_t grid = (uint64_t)(ncu > 0 ? ncu : 1);
     if (grid > need) grid = need;
     auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(GS_BLOCK), 0, stream, (const PTR *)a->indptr, (const IDX *)a->indices,
-                           (const double *)a->data, (const uint32_t *)pl.order, x, (unsigned long long *)work.p, n, w, w + 1,
-                           (unsigned long long *)(w + 2), csc ? 1u : 0u);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(GS_BLOCK), 0, stream, (const PTR *)indptr, (const IDX *)indices, data, order, x,
+                           (unsigned long long *)work.p, n, w, w + 1, (unsigned long long *)(w + 2), csc ? 1u : 0u);
     };
-    if (!upper) launch(tri_solve_kernel<IDX, PTR, false, false>);
+    if (unit) {
+        if (!upper) launch(tri_solve_kernel<IDX, PTR, false, false, true>);
+        else launch(tri_solve_kernel<IDX, PTR, true, false, true>);
+    } else if (!upper) launch(tri_solve_kernel<IDX, PTR, false, false>);
     else if (csc) launch(tri_solve_kernel<IDX, PTR, true, true>);
     else launch(tri_solve_kernel<IDX, PTR, true, false>);
     SPRS_TRY_HIP(hipGetLastError());
-    SPRS_TRY_HIP(copy_to_host(hw, words.p, sizeof(hw), stream));
+    SPRS_TRY_HIP(copy_to_host(hw, words.p, 4 * sizeof(unsigned int), stream));
+    return SPRS_HIP_OK;
+}
+
+template <typename IDX, typename PTR>
+int32_t trisolve_impl(sprs_hip_csmat *a, bool upper, bool csc, double *x, uint64_t n, sprs_hip_trisolve_info *info, hipStream_t stream) {
+    // held from the look-up of the row order to the end of the (blocking) solve, the way gs_impl holds it
+    std::lock_guard<std::recursive_mutex> lock(a->mu);
+    GsPlan &pl = upper ? a->tri_upper : a->gs;                 // lower: exactly the Gauss-Seidel order
+    if (!pl.built) SPRS_TRY(upper ? (gs_plan_build<IDX, PTR, true>(a, pl)) : (gs_plan_build<IDX, PTR, false>(a, pl)));
+    if (info) info->levels = pl.nlevels;
+
+    unsigned int hw[4] = {0, 0, 0, 0};
+    SPRS_TRY((tri_run<IDX, PTR>(a->indptr, a->indices, a->data, pl.order, upper, csc, false, x, n, hw, stream)));
     if ((uint64_t)hw[0] * 64u < n)
         SPRS_FAIL(SPRS_HIP_HIP_ERROR, "triangular solve: only %llu of %llu rows were solved", (unsigned long long)hw[0] * 64ull, (unsigned long long)n);
     if (hw[1] & GS_TIMEOUT)

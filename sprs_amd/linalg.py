@@ -156,3 +156,11 @@ def usolve_csc_dense_rhs(mat, rhs, stream=None):
     """usolve_csc_dense_rhs(upper_tri_mat, rhs) (trisolve.rs:161-210): every unknown receives its subtractions by DESCENDING
     column, so the bits differ from usolve_csr_dense_rhs on the same matrix, as they do in the reference."""
     return _trisolve(mat, rhs, _ffi.CSC, _ffi.UPPER, stream)
+
+
+def diag_solve(diag, x, stream=None):
+    """linalg::diag_solve (sprs/src/sparse/linalg.rs:17-29): x[i] /= diag[i], in place on the DeviceVec x."""
+    if diag.n != x.n:                               # assert_eq!(diag.len(), x.len())
+        raise _ffi.SprsHipError(_ffi.DIM_MISMATCH, "Dimension mismatch")
+    check(lib.sprs_hip_diag_solve_f64(C.c_void_p(diag.ptr), C.c_void_p(x.ptr), x.n, C.c_void_p(int(getattr(stream, "cuda_stream", stream)) if stream else 0)))
+    return x
