@@ -537,6 +537,43 @@ int32_t sprs_hip_csmat_transform_paq(const sprs_hip_csmat *m, const sprs_hip_per
  * copy when p.is_identity() — the elementwise test, so a stored permutation equal to 0..dim counts.  Otherwise as above. */
 int32_t sprs_hip_csmat_transform_papt(const sprs_hip_csmat *m, const sprs_hip_perm *p, sprs_hip_csmat **out, void *stream);
 
+/* ---- structure checks and unsorted input (sprs/src/sparse.rs:300-358, csmat.rs:311-401, vec.rs:536-557) ---------------------
+ * For arrays that were assembled on the device (sprs_hip_csmat_wrap_device, sprs_hip_csvec_wrap_device, `validate = 0` uploads):
+ * the check and the sort run there, nothing but the verdict travels to the host.  All four block until the answer (and the
+ * result) is complete on `stream` and return SPRS_HIP_OK or SPRS_HIP_BAD_STRUCTURE with the reference's text in
+ * sprs_hip_last_error().  `info` may be NULL. */
+typedef struct sprs_hip_structure_info {
+    int32_t kind;      /* StructureErrorKind (errors.rs): 0 ok, 1 Unsorted, 2 SizeMismatch, 3 OutOfRange */
+    int32_t reserved;
+    uint64_t outer;    /* the first offending outer slice; ~0 for a finding about the dimensions or the indptr; 0 for a vector */
+} sprs_hip_structure_info;
+/* utils::check_compressed_structure in the reference's order:
+ *   1. the dimensions against the declared index widths: "Index type not large enough for this matrix", "Iptr type not large
+ *      enough for this matrix" (OutOfRange);
+ *   2. the indptr, in a pass of its own: "Unsorted indptr" (Unsorted), "An indptr value is larger than allowed" (OutOfRange),
+ *      "Indices length and inpdtr's nnz do not match" (SizeMismatch); an indptr that does not start at 0 is SPRS_HIP_INVALID_ARG
+ *      (device handles are zero based).  `indices` is not read unless this pass found nothing;
+ *   3. the outer slices: "Indices are not sorted" (Unsorted: an index <= its predecessor), "Indice is larger than inner
+ *      dimension" (OutOfRange: the last index of a slice >= inner).  The lowest offending slice is reported; Unsorted wins
+ *      inside one slice.
+ * Index arrays are read as unsigned at the handle's width: a negative value of a signed array is a large index (OutOfRange).  The
+ * reference would report such a value ("Indices value out of range of usize") ahead of any Unsorted slice; this check reports in
+ * slice order. */
+int32_t sprs_hip_csmat_check_structure(const sprs_hip_csmat *m, sprs_hip_structure_info *info, void *stream);
+/* CsVec::try_new's invariants (vec.rs:440-491): "Index size is too small" (OutOfRange), "Unsorted indices" (Unsorted), "indices
+ * larger than vector size" (SizeMismatch, as in the reference). */
+int32_t sprs_hip_csvec_check_structure(const sprs_hip_csvec *v, sprs_hip_structure_info *info, void *stream);
+/* CsMat::new_from_unsorted / new_from_unsorted_csc: a NEW owning handle in m's storage and index widths whose outer slices are
+ * sorted by inner index, validated as above.  m is only read (the reference sorts in place because it takes ownership).  Values
+ * travel as 64-bit words.  Slices that are already sorted are copied; a valid m costs the check and a copy.  The indptr pass
+ * (2.) runs first, where the reference would index out of bounds and panic (csmat.rs:337-340).  Two equal indices in a slice are
+ * Unsorted; a slice that holds both a duplicate and an index >= inner is Unsorted, as in the reference.  On any finding *out
+ * stays NULL and `info` names the kind and the first offending slice.  An inner dimension above 2^40 is not supported. */
+int32_t sprs_hip_csmat_from_unsorted(const sprs_hip_csmat *m, sprs_hip_csmat **out, sprs_hip_structure_info *info, void *stream);
+/* CsVec::new_from_unsorted: check, sort only on Unsorted, check again ("Unsorted indices" for a duplicate, "indices larger than
+ * vector size" for a last index >= dim). */
+int32_t sprs_hip_csvec_from_unsorted(const sprs_hip_csvec *v, sprs_hip_csvec **out, sprs_hip_structure_info *info, void *stream);
+
 /* ---- orderings (sprs/src/sparse/linalg/ordering.rs, symmetric.rs, csmat.rs:1188-1216) --------------------------------------
  * Everything here walks the OUTER dimension as the reference does: a CSC handle is read as the CSR arrays of its transpose.
  * `stream` comes last: the kernels run there, host results are complete on return.

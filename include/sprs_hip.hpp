@@ -34,6 +34,19 @@ inline void check(int32_t status) {
     if (status != SPRS_HIP_OK) throw Error(status, sprs_hip_last_error());
 }
 
+// A finding of the structure checks (StructureError, errors.rs): the reference's text, its kind (0 ok, 1 Unsorted,
+// 2 SizeMismatch, 3 OutOfRange) and the first offending outer slice (~0 for the dimensions or the indptr, 0 for a vector)
+struct StructureError : Error {
+    int32_t kind;
+    uint64_t outer;
+    StructureError(int32_t s, const std::string &m, const sprs_hip_structure_info &i) : Error(s, m), kind(i.kind), outer(i.outer) {}
+};
+
+inline void check_structure_status(int32_t status, const sprs_hip_structure_info &info) {
+    if (status == SPRS_HIP_BAD_STRUCTURE) throw StructureError(status, sprs_hip_last_error(), info);
+    check(status);
+}
+
 // Dense f64 vector in HBM (what `&[f64]` / `Vec<f64>` / `Array1<f64>` are on the host,
 // sprs/src/dense_vector.rs:10-29).
 class DeviceVec {
@@ -86,6 +99,36 @@ public:
     DeviceCsMat &operator=(const DeviceCsMat &) = delete;
     ~DeviceCsMat() {
         if (h_) sprs_hip_csmat_free(h_);
+    }
+
+    // CsMat::new_from_unsorted / new_from_unsorted_csc (csmat.rs:374-401): uploaded as they are, sorted and validated on the
+    // device; throws StructureError
+    template <typename I, typename Iptr>
+    static DeviceCsMat new_from_unsorted(uint64_t rows, uint64_t cols, const std::vector<Iptr> &indptr, const std::vector<I> &indices,
+                                         const std::vector<double> &data, int32_t storage = SPRS_HIP_CSR, void *stream = nullptr) {
+        // (the upload sizes its copies by the indptr)
+        if (indptr.size() != (storage == SPRS_HIP_CSR ? rows : cols) + 1) throw Error(SPRS_HIP_BAD_STRUCTURE, "Indptr length does not match dimension");
+        if (indices.size() != data.size()) throw Error(SPRS_HIP_BAD_STRUCTURE, "data and indices have different sizes");
+        if ((uint64_t)indptr.back() - (uint64_t)indptr.front() != indices.size())
+            throw Error(SPRS_HIP_BAD_STRUCTURE, "Indices length and inpdtr's nnz do not match");
+        return DeviceCsMat(storage, rows, cols, indptr, indices, data, false).sort_indices(stream);
+    }
+    template <typename I, typename Iptr>
+    static DeviceCsMat new_from_unsorted_csc(uint64_t rows, uint64_t cols, const std::vector<Iptr> &indptr, const std::vector<I> &indices,
+                                             const std::vector<double> &data, void *stream = nullptr) {
+        return new_from_unsorted(rows, cols, indptr, indices, data, SPRS_HIP_CSC, stream);
+    }
+    // utils::check_compressed_structure (sparse.rs:300-358) on the device arrays; throws StructureError
+    void check_structure(void *stream = nullptr) const {
+        sprs_hip_structure_info info{};
+        check_structure_status(sprs_hip_csmat_check_structure(h_, &info, stream), info);
+    }
+    // a new matrix whose outer slices are sorted by inner index, validated; this one is only read
+    DeviceCsMat sort_indices(void *stream = nullptr) const {
+        sprs_hip_structure_info info{};
+        sprs_hip_csmat *c = nullptr;
+        check_structure_status(sprs_hip_csmat_from_unsorted(h_, &c, &info, stream), info);
+        return DeviceCsMat(c);
     }
 
     static DeviceCsMat eye(uint64_t dim) {   // csmat.rs:416-426
@@ -343,6 +386,23 @@ public:
     DeviceCsVec &operator=(const DeviceCsVec &) = delete;
     ~DeviceCsVec() {
         if (h_) sprs_hip_csvec_free(h_);
+    }
+
+    // CsVec::new_from_unsorted (vec.rs:536-557): check, sort only on Unsorted, check again — on the device
+    template <typename I>
+    static DeviceCsVec new_from_unsorted(uint64_t dim, const std::vector<I> &indices, const std::vector<double> &data, void *stream = nullptr) {
+        return DeviceCsVec(dim, indices, data, false).sort_indices(stream);
+    }
+    // the invariants of CsVec::try_new (vec.rs:440-491) on the device arrays; throws StructureError
+    void check_structure(void *stream = nullptr) const {
+        sprs_hip_structure_info info{};
+        check_structure_status(sprs_hip_csvec_check_structure(h_, &info, stream), info);
+    }
+    DeviceCsVec sort_indices(void *stream = nullptr) const {
+        sprs_hip_structure_info info{};
+        sprs_hip_csvec *c = nullptr;
+        check_structure_status(sprs_hip_csvec_from_unsorted(h_, &c, &info, stream), info);
+        return DeviceCsVec(c);
     }
 
     uint64_t dim() const { return info().dim; }      // vec.rs:681

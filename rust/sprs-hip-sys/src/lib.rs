@@ -100,6 +100,16 @@ pub struct sprs_hip_trisolve_info {
     pub singular_reason: i32,
 }
 
+/// result of the structure checks and of new_from_unsorted (include/sprs_hip.h): kind = StructureErrorKind (0 ok, 1 Unsorted,
+/// 2 SizeMismatch, 3 OutOfRange), outer = the first offending outer slice (u64::MAX for the dimensions or the indptr)
+#[repr(C)]
+#[derive(Debug, Clone, Copy, Default)]
+pub struct sprs_hip_structure_info {
+    pub kind: i32,
+    pub reserved: i32,
+    pub outer: u64,
+}
+
 extern "C" {
     pub fn sprs_hip_last_error() -> *const c_char;
     pub fn sprs_hip_last_hip_code() -> i32;
@@ -252,6 +262,14 @@ extern "C" {
     ) -> i32;
     pub fn sprs_hip_csmat_transform_papt(
         m: *const sprs_hip_csmat, p: *const sprs_hip_perm, out: *mut *mut sprs_hip_csmat, stream: *mut c_void,
+    ) -> i32;
+    pub fn sprs_hip_csmat_check_structure(m: *const sprs_hip_csmat, info: *mut sprs_hip_structure_info, stream: *mut c_void) -> i32;
+    pub fn sprs_hip_csvec_check_structure(v: *const sprs_hip_csvec, info: *mut sprs_hip_structure_info, stream: *mut c_void) -> i32;
+    pub fn sprs_hip_csmat_from_unsorted(
+        m: *const sprs_hip_csmat, out: *mut *mut sprs_hip_csmat, info: *mut sprs_hip_structure_info, stream: *mut c_void,
+    ) -> i32;
+    pub fn sprs_hip_csvec_from_unsorted(
+        v: *const sprs_hip_csvec, out: *mut *mut sprs_hip_csvec, info: *mut sprs_hip_structure_info, stream: *mut c_void,
     ) -> i32;
     pub fn sprs_hip_csmat_is_symmetric(m: *const sprs_hip_csmat, flag: *mut i32, stream: *mut c_void) -> i32;
     pub fn sprs_hip_csmat_degrees(m: *const sprs_hip_csmat, out_dev: *mut u64, stream: *mut c_void) -> i32;

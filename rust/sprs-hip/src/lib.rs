@@ -895,6 +895,112 @@ impl DeviceCsMat {
     }
 }
 
+/// The finding of a structure check as the reference's error: the kind from the info struct, the text (one of the reference's
+/// own `&'static str`s) from `sprs_hip_last_error()`.  Any other failure panics like every other call here.
+fn structure_result(status: i32, info: &sys::sprs_hip_structure_info) -> Result<(), sprs::errors::StructureError> {
+    use sprs::errors::StructureError;
+    if status != sys::SPRS_HIP_BAD_STRUCTURE {
+        check(status);
+        return Ok(());
+    }
+    const TEXTS: [&str; 10] = [
+        "Index type not large enough for this matrix",
+        "Iptr type not large enough for this matrix",
+        "Unsorted indptr",
+        "An indptr value is larger than allowed",
+        "Indices length and inpdtr's nnz do not match",
+        "Indices are not sorted",
+        "Indice is larger than inner dimension",
+        "Index size is too small",
+        "Unsorted indices",
+        "indices larger than vector size",
+    ];
+    let msg = unsafe { CStr::from_ptr(sys::sprs_hip_last_error()) }.to_string_lossy().into_owned();
+    let text = TEXTS.iter().copied().find(|t| *t == msg).unwrap_or("invalid structure");
+    Err(match info.kind {
+        1 => StructureError::Unsorted(text),
+        2 => StructureError::SizeMismatch(text),
+        _ => StructureError::OutOfRange(text),
+    })
+}
+
+/// Structure checks and unsorted input on the device (include/sprs_hip.h, "structure checks and unsorted input").
+impl DeviceCsMat {
+    fn upload_unchecked<I: SpIndex, Iptr: SpIndex>(storage: i32, shape: (usize, usize), indptr: &[Iptr], indices: &[I], data: &[f64]) -> Self {
+        let outer = if storage == sys::SPRS_HIP_CSR { shape.0 } else { shape.1 };
+        assert_eq!(indptr.len(), outer + 1, "Indptr length does not match dimension");
+        assert_eq!(indices.len(), data.len(), "data and indices have different sizes");
+        // (the upload sizes its copies by the indptr)
+        assert_eq!(indptr[outer].index() - indptr[0].index(), indices.len(), "Indices length and inpdtr's nnz do not match");
+        let mut h = std::ptr::null_mut();
+        unsafe {
+            check(sys::sprs_hip_csmat_upload(
+                &mut h, storage, shape.0 as u64, shape.1 as u64, indptr.as_ptr() as *const c_void, std::mem::size_of::<Iptr>() as i32,
+                indices.as_ptr() as *const c_void, std::mem::size_of::<I>() as i32, data.as_ptr(), 0,
+            ));
+        }
+        Self { h }
+    }
+
+    /// `CsMat::new_from_unsorted` (csmat.rs:374-384): the arrays are uploaded as they are, sorted and validated on the device.
+    pub fn new_from_unsorted<I: SpIndex, Iptr: SpIndex>(
+        shape: (usize, usize), indptr: &[Iptr], indices: &[I], data: &[f64],
+    ) -> Result<Self, sprs::errors::StructureError> {
+        Self::upload_unchecked(sys::SPRS_HIP_CSR, shape, indptr, indices, data).sort_indices()
+    }
+
+    /// `CsMat::new_from_unsorted_csc` (csmat.rs:391-401).
+    pub fn new_from_unsorted_csc<I: SpIndex, Iptr: SpIndex>(
+        shape: (usize, usize), indptr: &[Iptr], indices: &[I], data: &[f64],
+    ) -> Result<Self, sprs::errors::StructureError> {
+        Self::upload_unchecked(sys::SPRS_HIP_CSC, shape, indptr, indices, data).sort_indices()
+    }
+
+    /// `utils::check_compressed_structure` (sparse.rs:300-358) on the device arrays.
+    pub fn check_compressed_structure(&self) -> Result<(), sprs::errors::StructureError> {
+        let mut info = sys::sprs_hip_structure_info::default();
+        let status = unsafe { sys::sprs_hip_csmat_check_structure(self.h, &mut info, std::ptr::null_mut()) };
+        structure_result(status, &info)
+    }
+
+    /// A new matrix whose outer slices are sorted by inner index, validated; `self` is only read.
+    pub fn sort_indices(&self) -> Result<DeviceCsMat, sprs::errors::StructureError> {
+        let mut info = sys::sprs_hip_structure_info::default();
+        let mut h = std::ptr::null_mut();
+        let status = unsafe { sys::sprs_hip_csmat_from_unsorted(self.h, &mut h, &mut info, std::ptr::null_mut()) };
+        structure_result(status, &info).map(|_| DeviceCsMat { h })
+    }
+}
+
+impl DeviceCsVec {
+    /// `CsVec::new_from_unsorted` (vec.rs:536-557): check, sort only on Unsorted, check again — on the device.
+    pub fn new_from_unsorted<I: SpIndex>(n: usize, indices: &[I], data: &[f64]) -> Result<Self, sprs::errors::StructureError> {
+        assert_eq!(indices.len(), data.len(), "indices and data do not have compatible lengths");
+        let mut h = std::ptr::null_mut();
+        unsafe {
+            check(sys::sprs_hip_csvec_upload(
+                &mut h, n as u64, indices.len() as u64, indices.as_ptr() as *const c_void, std::mem::size_of::<I>() as i32, data.as_ptr(), 0,
+            ));
+        }
+        (Self { h }).sort_indices()
+    }
+
+    /// The invariants of `CsVec::try_new` (vec.rs:440-491) on the device arrays.
+    pub fn check_structure(&self) -> Result<(), sprs::errors::StructureError> {
+        let mut info = sys::sprs_hip_structure_info::default();
+        let status = unsafe { sys::sprs_hip_csvec_check_structure(self.h, &mut info, std::ptr::null_mut()) };
+        structure_result(status, &info)
+    }
+
+    /// A new sorted, validated vector; `self` is only read.
+    pub fn sort_indices(&self) -> Result<DeviceCsVec, sprs::errors::StructureError> {
+        let mut info = sys::sprs_hip_structure_info::default();
+        let mut h = std::ptr::null_mut();
+        let status = unsafe { sys::sprs_hip_csvec_from_unsorted(self.h, &mut h, &mut info, std::ptr::null_mut()) };
+        structure_result(status, &info).map(|_| DeviceCsVec { h })
+    }
+}
+
 /// Twin of `sprs::sparse::linalg::ordering` (linalg/ordering.rs) and of `sprs::sparse::symmetric::is_symmetric` for device
 /// operands: the matrix stays in HBM and the permutation arrives there, ready for `permutation::transform_mat_papt`.  The result is
 /// the reference's with ties between vertices of equal degree broken by vertex id (the stable outcome of its

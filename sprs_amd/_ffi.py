@@ -21,6 +21,8 @@ ROW_MAJOR, COL_MAJOR = 0, 1
 ROUTE_RCCL, ROUTE_PEER = 0, 1
 BINOP_ADD, BINOP_SUB, BINOP_MUL = 0, 1, 2
 START_NEXT, START_MINIMUM_DEGREE, START_PSEUDO_PERIPHERAL = 0, 1, 2
+KIND_OK, KIND_UNSORTED, KIND_SIZE_MISMATCH, KIND_OUT_OF_RANGE = 0, 1, 2, 3     # StructureErrorKind (errors.rs)
+NO_OUTER = (1 << 64) - 1       # StructureInfo.outer of a finding about the dimensions or the indptr
 
 STATUS_NAMES = {
     OK: "OK", DIM_MISMATCH: "DIM_MISMATCH", STORAGE_MISMATCH: "STORAGE_MISMATCH",
@@ -117,6 +119,10 @@ SIGNATURES = {
     "sprs_hip_perm_mul_vec_f64": (i32, [vp, vp, vp, u64, vp]),
     "sprs_hip_csmat_transform_paq": (i32, [vp, vp, vp, P(vp), vp]),
     "sprs_hip_csmat_transform_papt": (i32, [vp, vp, P(vp), vp]),
+    "sprs_hip_csmat_check_structure": (i32, [vp, vp, vp]),
+    "sprs_hip_csvec_check_structure": (i32, [vp, vp, vp]),
+    "sprs_hip_csmat_from_unsorted": (i32, [vp, P(vp), vp, vp]),
+    "sprs_hip_csvec_from_unsorted": (i32, [vp, P(vp), vp, vp]),
     "sprs_hip_csmat_is_symmetric": (i32, [vp, P(i32), vp]),
     "sprs_hip_csmat_degrees": (i32, [vp, vp, vp]),
     "sprs_hip_csmat_max_outer_nnz": (i32, [vp, P(u64), vp]),
@@ -160,9 +166,11 @@ class SprsHipError(RuntimeError):
     violations is the reference's own panic text ("Dimension mismatch",
     "Storage mismatch", "Index type is not large enough to hold ...")."""
 
-    def __init__(self, status, message, hip_code=0):
+    def __init__(self, status, message, hip_code=0, kind=None, outer=None):
         self.status = status
         self.hip_code = hip_code
+        self.kind = kind       # structure checks: the StructureErrorKind (KIND_*) ...
+        self.outer = outer     # ... and the first offending outer slice (NO_OUTER: the dimensions or the indptr)
         super().__init__("%s: %s" % (STATUS_NAMES.get(status, status), message))
 
 
@@ -197,6 +205,18 @@ for _name, (_res, _args) in SIGNATURES.items():
     _f = getattr(lib, _name)   # AttributeError here == the .so does not match the header
     _f.restype = _res
     _f.argtypes = _args
+
+
+class StructureInfo(C.Structure):
+    """sprs_hip_structure_info"""
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("outer", C.c_uint64)]
+
+
+def check_structure_status(status, info):
+    """check() for the four structure entry points: the error carries the info struct's kind and outer slice"""
+    if status != OK:
+        raise SprsHipError(status, lib.sprs_hip_last_error().decode("utf-8", "replace"), lib.sprs_hip_last_hip_code(),
+                           kind=info.kind, outer=info.outer)
 
 
 def check(status):

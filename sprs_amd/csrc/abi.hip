@@ -1384,6 +1384,53 @@ int32_t sprs_hip_csmat_transform_papt(const sprs_hip_csmat *m, const sprs_hip_pe
 
 }  // extern "C"
 
+// ---- structure checks and unsorted input (sparse.rs:300-358, csmat.rs:311-401, vec.rs:536-557); kernels in structure.hpp -----
+
+extern "C" {
+
+int32_t sprs_hip_csmat_check_structure(const sprs_hip_csmat *m, sprs_hip_structure_info *info, void *stream) {
+    clear_error();
+    if (info) *info = sprs_hip_structure_info{0, 0, 0};
+    if (!m) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    return csmat_check_structure(m, info, (hipStream_t)stream);
+}
+
+int32_t sprs_hip_csvec_check_structure(const sprs_hip_csvec *v, sprs_hip_structure_info *info, void *stream) {
+    clear_error();
+    if (info) *info = sprs_hip_structure_info{0, 0, 0};
+    if (!v) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if (v->dim > width_max(v->user_idx_bytes())) {      // I::from(n) (vec.rs:445-451)
+        if (info) info->kind = 3;
+        SPRS_FAIL(SPRS_HIP_BAD_STRUCTURE, "Index size is too small");
+    }
+    return csvec_check_device(v, (hipStream_t)stream, info);
+}
+
+int32_t sprs_hip_csmat_from_unsorted(const sprs_hip_csmat *m, sprs_hip_csmat **out, sprs_hip_structure_info *info, void *stream) {
+    clear_error();
+    if (info) *info = sprs_hip_structure_info{0, 0, 0};
+    if (!m || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    OwnedCsmat res;
+    SPRS_TRY(csmat_from_unsorted(m, res, info, (hipStream_t)stream));
+    return finish_result(res, m, out);
+}
+
+int32_t sprs_hip_csvec_from_unsorted(const sprs_hip_csvec *v, sprs_hip_csvec **out, sprs_hip_structure_info *info, void *stream) {
+    clear_error();
+    if (info) *info = sprs_hip_structure_info{0, 0, 0};
+    if (!v || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    if (v->dim > width_max(v->user_idx_bytes())) {
+        if (info) info->kind = 3;
+        SPRS_FAIL(SPRS_HIP_BAD_STRUCTURE, "Index size is too small");
+    }
+    OwnedCsvec res;
+    return finish_csvec(csvec_from_unsorted(v, res, info, (hipStream_t)stream), res, out);
+}
+
+}  // extern "C"
+
 // ---- orderings (linalg/ordering.rs, symmetric.rs, csmat.rs:1188-1216); kernels in ordering.hpp ----------------------------------
 
 extern "C" {

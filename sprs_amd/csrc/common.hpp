@@ -496,6 +496,11 @@ int32_t csmat_permute(const sprs_hip_csmat *m, const void *o, const void *g, Own
 int32_t perm_build_inverse(sprs_hip_perm *p, bool validate, hipStream_t stream);
 int32_t perm_is_identity(const sprs_hip_perm *p, int32_t *flag, hipStream_t stream);
 int32_t perm_mul_vec_f64(const sprs_hip_perm *p, const double *x, double *y, hipStream_t stream);
+// structure.hpp (compiled in convert.hip): check_compressed_structure and new_from_unsorted on handles; `info` may be null;
+// the answer (and the result) is complete on `stream` at return
+int32_t csmat_check_structure(const sprs_hip_csmat *m, sprs_hip_structure_info *info, hipStream_t stream);
+int32_t csmat_from_unsorted(const sprs_hip_csmat *m, OwnedCsmat &out, sprs_hip_structure_info *info, hipStream_t stream);
+int32_t csvec_from_unsorted(const sprs_hip_csvec *v, OwnedCsvec &out, sprs_hip_structure_info *info, hipStream_t stream);
 // ordering.hpp (compiled in convert.hip): everything walks the outer dimension; host results are complete on `stream` at return
 int32_t csmat_is_symmetric(const sprs_hip_csmat *m, int32_t *flag, hipStream_t stream);
 int32_t csmat_degrees(const sprs_hip_csmat *m, uint64_t *out_dev, hipStream_t stream);   // ordered on `stream`
@@ -535,7 +540,8 @@ int32_t ldl_tri_f64(sprs_hip_csmat *l, sprs_hip_csmat *csr, bool transposed, dou
 int32_t diag_solve_f64(const double *d, double *x, uint64_t n, hipStream_t stream);
 int32_t slice_outer(const sprs_hip_csmat *m, uint64_t start, uint64_t end, OwnedCsmat &out);
 // csvec.hpp (compiled in spmv.hip)
-int32_t csvec_check_device(const sprs_hip_csvec *v, hipStream_t stream);
+// the invariants of CsVec::try_new on the device; `info` (may be null): the kind of the finding (a vector is its one slice, 0)
+int32_t csvec_check_device(const sprs_hip_csvec *v, hipStream_t stream, sprs_hip_structure_info *info = nullptr);
 int32_t csvec_scatter(const sprs_hip_csvec *v, double *out, hipStream_t stream);
 int32_t csvec_masked_dot(const sprs_hip_csmat *m, const sprs_hip_csvec *v, bool drop_zero, int32_t idx_bytes, int32_t decl_bytes,
                          OwnedCsvec &out, hipStream_t stream);

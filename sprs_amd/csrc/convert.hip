@@ -296,6 +296,7 @@ int32_t slice_outer(const sprs_hip_csmat *m, uint64_t start, uint64_t end, Owned
 
 #include "binop.hpp"   // sparse +, -, elementwise * and scale
 #include "perm.hpp"    // permutations: PermOwned, P * x, permute_rows / permute_cols, P A P^T, P A Q
+#include "structure.hpp"   // check_compressed_structure and new_from_unsorted on handles
 #include "construct.hpp"   // kronecker_product, same_storage_fast_stack, vstack, hstack, bmat
 #include "dense.hpp"   // csr_from_dense / csc_from_dense, assign_to_dense / to_dense, the sparse-with-dense binops
 #include "ordering.hpp"   // is_symmetric, degrees, max_outer_nnz, Cuthill-McKee orderings

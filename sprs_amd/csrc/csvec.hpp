@@ -241,7 +241,8 @@ static int32_t csvec_scratch(sprs_hip_csmat *m, uint64_t n) {
     return SPRS_HIP_OK;
 }
 
-int32_t csvec_check_device(const sprs_hip_csvec *v, hipStream_t s) {
+int32_t csvec_check_device(const sprs_hip_csvec *v, hipStream_t s, sprs_hip_structure_info *info) {
+    if (info) *info = sprs_hip_structure_info{0, 0, 0};
     if (v->nnz == 0) return SPRS_HIP_OK;
     DevBuf bad;
     SPRS_TRY_HIP(bad.alloc(16));
@@ -257,8 +258,14 @@ int32_t csvec_check_device(const sprs_hip_csvec *v, hipStream_t s) {
     }
     if (e == hipSuccess) e = copy_to_host(host, bad.p, 16, s);
     if (e != hipSuccess) return fail_hip(e, "csvec_check");
-    if (host[0] != ~0ull) SPRS_FAIL(SPRS_HIP_BAD_STRUCTURE, "Unsorted indices");
-    if (host[1]) SPRS_FAIL(SPRS_HIP_BAD_STRUCTURE, "indices larger than vector size");
+    if (host[0] != ~0ull) {                         // StructureError::Unsorted (vec.rs:472-478)
+        if (info) info->kind = 1;
+        SPRS_FAIL(SPRS_HIP_BAD_STRUCTURE, "Unsorted indices");
+    }
+    if (host[1]) {                                  // StructureError::SizeMismatch (vec.rs:479-489)
+        if (info) info->kind = 2;
+        SPRS_FAIL(SPRS_HIP_BAD_STRUCTURE, "indices larger than vector size");
+    }
     return SPRS_HIP_OK;
 }
 

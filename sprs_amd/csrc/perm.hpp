@@ -26,6 +26,8 @@
 //                                 start'[row] + i - first[hub]
 //     Keys are unique inside a slice (a validated handle has no duplicates and g is a bijection), so no sort has to be stable.
 //  4. P * x is a gather; the inverse, the validation and is_identity are one small kernel each.
+//  5. structure.hpp (new_from_unsorted) runs the same row passes and sorts with o = g = identity and a row mask `pick`: only the
+//     masked rows are counted, listed and sorted — keyed on their own indices — and every other row is copied.
 // An unvalidated handle or permutation (unsorted, duplicated or out-of-range values) gives an unspecified result but never an
 // access outside the arrays: a source row >= outer counts as empty, slice bounds are clamped to nnz, an inner index >= inner
 // is not looked up in g, and every store is tested against nnz.
@@ -58,6 +60,11 @@ __device__ __forceinline__ int length_class(uint64_t len) {
     return len == 0 ? -1 : len <= 16 ? 0 : len <= 32 ? 1 : len <= 64 ? 2 : len <= (uint64_t)PM_WAVE_CAP ? 3 : len <= (uint64_t)PM_CAP ? 4 : 5;
 }
 
+// the class of row r when only the rows with pick[r] != 0 are sorted (structure.hpp; a null `pick` = every row)
+__device__ __forceinline__ int picked_class(const uint8_t *pick, uint64_t r, uint64_t len) {
+    return pick && !pick[r] ? -1 : length_class(len);
+}
+
 // the source slice of result slice r: [s, s + len) inside [0, nnz), empty when o[r] is no slice of the matrix
 template <typename P, typename I>
 __device__ __forceinline__ uint64_t source_slice(const P *ip, const I *o, uint64_t r, uint64_t outer, uint64_t nnz, uint64_t *len) {
@@ -81,8 +88,8 @@ __device__ __forceinline__ uint64_t relabel(const I *g, uint64_t j, uint64_t inn
 // five counts with ONE atomic each: an atomic per wave on the same five words took ~5 ms of the 17 ms of P A P^T on the 4096^2
 // Laplacian (16.8 M rows).
 template <typename P, typename I>
-__global__ void __launch_bounds__(PM_BLOCK) perm_len_kernel(const P *ip, const I *o, uint64_t outer, uint64_t nnz, uint64_t *lens,
-                                                            unsigned long long *counts) {
+__global__ void __launch_bounds__(PM_BLOCK) perm_len_kernel(const P *ip, const I *o, const uint8_t *pick, uint64_t outer, uint64_t nnz,
+                                                            uint64_t *lens, unsigned long long *counts) {
     __shared__ uint32_t s_cnt[PM_CLASSES];
     if (threadIdx.x < PM_CLASSES) s_cnt[threadIdx.x] = 0;
     __syncthreads();
@@ -94,7 +101,7 @@ __global__ void __launch_bounds__(PM_BLOCK) perm_len_kernel(const P *ip, const I
         uint64_t len;
         (void)source_slice(ip, o, r, outer, nnz, &len);
         lens[r] = len;
-        const int cls = length_class(len);
+        const int cls = picked_class(pick, r, len);
 #pragma unroll
         for (int c = 0; c < PM_CLASSES; ++c) mine[c] += cls == c ? 1u : 0u;
     }
@@ -115,8 +122,8 @@ __global__ void __launch_bounds__(PM_BLOCK) perm_indptr_kernel(const uint64_t *o
 
 // 3. list[base[c] ..] = the rows of class c (in no particular order: every row knows its place in the result).  A workgroup
 // counts the rows of its PM_CHUNK by class, reserves its five ranges with one atomic each and fills them.
-__global__ void __launch_bounds__(PM_BLOCK) perm_list_kernel(const uint64_t *offs, uint64_t outer, const unsigned long long *counts,
-                                                             unsigned long long *cursor, uint64_t *list) {
+__global__ void __launch_bounds__(PM_BLOCK) perm_list_kernel(const uint64_t *offs, const uint8_t *pick, uint64_t outer,
+                                                             const unsigned long long *counts, unsigned long long *cursor, uint64_t *list) {
     __shared__ uint32_t s_cnt[PM_CLASSES], s_cur[PM_CLASSES];
     __shared__ uint64_t s_base[PM_CLASSES];
     const uint32_t lane = threadIdx.x & 63;
@@ -127,7 +134,7 @@ __global__ void __launch_bounds__(PM_BLOCK) perm_list_kernel(const uint64_t *off
     for (int it = 0; it < PM_CHUNK / PM_BLOCK; ++it) {
         const uint64_t r = r0 + (uint64_t)it * PM_BLOCK + threadIdx.x;
         if (r >= outer) break;
-        const int cls = length_class(offs[r + 1] - offs[r]);
+        const int cls = picked_class(pick, r, offs[r + 1] - offs[r]);
 #pragma unroll
         for (int c = 0; c < PM_CLASSES; ++c) mine[c] += cls == c ? 1u : 0u;
     }
@@ -145,7 +152,7 @@ __global__ void __launch_bounds__(PM_BLOCK) perm_list_kernel(const uint64_t *off
         const uint64_t rw = r0 + (uint64_t)it * PM_BLOCK + (threadIdx.x & ~63u);      // the wave's first row: the waves loop alike
         if (rw >= outer) break;
         const uint64_t r = rw + lane;
-        const int cls = r < outer ? length_class(offs[r + 1] - offs[r]) : -1;
+        const int cls = r < outer ? picked_class(pick, r, offs[r + 1] - offs[r]) : -1;
         for (int c = 0; c < PM_CLASSES; ++c) {
             const uint64_t mask = __ballot(cls == c);
             uint32_t first = 0;
@@ -407,8 +414,10 @@ inline int bits_for(uint64_t n) {                   // bits needed for values < 
     return b;
 }
 
+// `pick` (structure.hpp, with o = g = null): only the rows with pick[r] != 0 go through the sorts, keyed on their own indices;
+// every other row is copied as it is
 template <typename P, typename I>
-int32_t run(const sprs_hip_csmat *m, const void *o_, const void *g_, sprs_hip_csmat *res, hipStream_t st) {
+int32_t run(const sprs_hip_csmat *m, const void *o_, const void *g_, const uint8_t *pick, sprs_hip_csmat *res, hipStream_t st) {
     const uint64_t outer = m->outer(), inner = m->inner(), nnz = m->nnz;
     const P *ip = (const P *)m->indptr;
     const I *ix = (const I *)m->indices, *o = (const I *)o_, *g = (const I *)g_;
@@ -421,9 +430,9 @@ int32_t run(const sprs_hip_csmat *m, const void *o_, const void *g_, sprs_hip_cs
     SPRS_TRY_HIP(tmp.alloc_for(st, (2 * outer + 1 + 2 * PM_CLASSES) * 8));
     uint64_t *lens = tmp.u64(), *offs = lens + outer;
     unsigned long long *counts = (unsigned long long *)(offs + outer + 1), *cursor = counts + PM_CLASSES;
-    const bool sorting = g != nullptr && nnz != 0;
+    const bool sorting = (g != nullptr || pick != nullptr) && nnz != 0;
     SPRS_TRY_HIP(hipMemsetAsync(counts, 0, 2 * PM_CLASSES * 8, st));
-    hipLaunchKernelGGL((perm_len_kernel<P, I>), dim3(chunks_for(outer)), dim3(PM_BLOCK), 0, st, ip, o, outer, nnz, lens,
+    hipLaunchKernelGGL((perm_len_kernel<P, I>), dim3(chunks_for(outer)), dim3(PM_BLOCK), 0, st, ip, o, pick, outer, nnz, lens,
                        sorting ? counts : (unsigned long long *)nullptr);
     SPRS_TRY_HIP(hipGetLastError());
     SPRS_TRY(exclusive_scan_u64(lens, offs, outer, st));
@@ -444,9 +453,13 @@ int32_t run(const sprs_hip_csmat *m, const void *o_, const void *g_, sprs_hip_cs
         return SPRS_HIP_OK;
     }
     if (inner > (1ull << PM_HUB_SHIFT)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "permutation: an inner dimension above 2^40 is not supported");
+    if (pick) {                                     // the rows that no sort rewrites
+        SPRS_TRY_HIP(hipMemcpyAsync(ix_out, ix, nnz * sizeof(I), hipMemcpyDeviceToDevice, st));
+        SPRS_TRY_HIP(hipMemcpyAsync(v_out, val, nnz * 8, hipMemcpyDeviceToDevice, st));
+    }
     SPRS_TRY_HIP(listb.alloc_for(st, outer * 8));
     uint64_t *list = listb.u64();
-    hipLaunchKernelGGL(perm_list_kernel, dim3(chunks_for(outer)), dim3(PM_BLOCK), 0, st, (const uint64_t *)offs, outer,
+    hipLaunchKernelGGL(perm_list_kernel, dim3(chunks_for(outer)), dim3(PM_BLOCK), 0, st, (const uint64_t *)offs, pick, outer,
                        (const unsigned long long *)counts, cursor, list);
     SPRS_TRY_HIP(hipGetLastError());
     uint64_t cnt[PM_CLASSES];
@@ -518,7 +531,7 @@ int32_t csmat_permute(const sprs_hip_csmat *m, const void *o, const void *g, Own
     } else {
         SPRS_TRY(make_csmat(res, m->storage, m->rows, m->cols, m->nnz, m->iptr_bytes, m->idx_bytes));
         SPRS_TRY(dispatch_widths(m->idx_bytes, m->iptr_bytes, [&](auto i, auto p) {
-            return pm::run<typename decltype(p)::type, typename decltype(i)::type>(m, o, g, res.get(), st);
+            return pm::run<typename decltype(p)::type, typename decltype(i)::type>(m, o, g, nullptr, res.get(), st);
         }));
     }
     out = std::move(res);

@@ -100,8 +100,34 @@ class DeviceCsMat:
         return cls(h.value)
 
     @classmethod
-    def wrap_torch(cls, shape, indptr_t, indices_t, data_t, storage=CSR):
-        """Borrow torch CUDA tensors as the three CSR arrays (no copy)."""
+    def new_from_unsorted(cls, shape, indptr, indices, data, storage=CSR, stream=None):
+        """CsMat::new_from_unsorted (csmat.rs:374-384): host arrays whose outer slices need not be sorted; they are uploaded as
+        they are and sorted and validated on the device."""
+        indptr, indices = np.ascontiguousarray(indptr), np.ascontiguousarray(indices)
+        if indptr.size != (shape[0] if storage == CSR else shape[1]) + 1:
+            raise _ffi.SprsHipError(_ffi.BAD_STRUCTURE, "Indptr length does not match dimension",
+                                    kind=_ffi.KIND_SIZE_MISMATCH, outer=_ffi.NO_OUTER)
+        if int(indptr[-1]) - int(indptr[0]) != indices.size:    # (the upload sizes its copies by the indptr)
+            raise _ffi.SprsHipError(_ffi.BAD_STRUCTURE, "Indices length and inpdtr's nnz do not match",
+                                    kind=_ffi.KIND_SIZE_MISMATCH, outer=_ffi.NO_OUTER)
+        return cls.from_host(shape, indptr, indices, data, storage=storage, validate=False).sort_indices(stream)
+
+    @classmethod
+    def new_from_unsorted_csc(cls, shape, indptr, indices, data, stream=None):
+        """CsMat::new_from_unsorted_csc (csmat.rs:391-401)."""
+        return cls.new_from_unsorted(shape, indptr, indices, data, storage=CSC, stream=stream)
+
+    @classmethod
+    def wrap_torch(cls, shape, indptr_t, indices_t, data_t, storage=CSR, validate=False):
+        """Borrow torch CUDA tensors as the three CSR arrays (no copy).  validate: run check_structure on the device before
+        returning (CsMat::new instead of new_trusted)."""
+        m = cls._wrap_torch(shape, indptr_t, indices_t, data_t, storage)
+        if validate:
+            m.check_structure()
+        return m
+
+    @classmethod
+    def _wrap_torch(cls, shape, indptr_t, indices_t, data_t, storage):
         h = C.c_void_p()
         check(lib.sprs_hip_csmat_wrap_device(
             C.byref(h), storage, shape[0], shape[1], indices_t.numel(),
@@ -177,6 +203,20 @@ class DeviceCsMat:
         """slice_outer (slicing.rs:65-89) + to_proper, materialised on the device."""
         h = C.c_void_p()
         check(lib.sprs_hip_csmat_slice_outer(self._h, start, end, C.byref(h)))
+        return DeviceCsMat(h.value)
+
+    def check_structure(self, stream=None):
+        """utils::check_compressed_structure (sparse.rs:300-358) on the device arrays.  Raises SprsHipError (BAD_STRUCTURE, the
+        reference's text) carrying `.kind` (_ffi.KIND_*) and `.outer`, the first offending outer slice."""
+        info = _ffi.StructureInfo()
+        _ffi.check_structure_status(lib.sprs_hip_csmat_check_structure(self._h, C.byref(info), _stream_arg(stream)), info)
+        return self
+
+    def sort_indices(self, stream=None):
+        """A new handle whose outer slices are sorted by inner index, validated (sprs_hip_csmat_from_unsorted); this one is only
+        read.  Errors as check_structure."""
+        h, info = C.c_void_p(), _ffi.StructureInfo()
+        _ffi.check_structure_status(lib.sprs_hip_csmat_from_unsorted(self._h, C.byref(h), C.byref(info), _stream_arg(stream)), info)
         return DeviceCsMat(h.value)
 
     def refresh(self):
@@ -307,15 +347,37 @@ class DeviceCsVec:
         return cls(h.value)
 
     @classmethod
-    def borrow(cls, dim, indices_t, data_t):
-        """Borrow two contiguous torch CUDA tensors (int32 / int64 indices, float64 data) without a copy (new_trusted)."""
+    def new_from_unsorted(cls, dim, indices, data, stream=None):
+        """CsVec::new_from_unsorted (vec.rs:536-557): uploaded as it is, checked, sorted when unsorted and checked again on the
+        device."""
+        return cls.from_host(dim, indices, data, validate=False).sort_indices(stream)
+
+    def check_structure(self, stream=None):
+        """The invariants of CsVec::try_new (vec.rs:440-491) on the device arrays; raises SprsHipError carrying `.kind`."""
+        info = _ffi.StructureInfo()
+        _ffi.check_structure_status(lib.sprs_hip_csvec_check_structure(self._h, C.byref(info), _stream_arg(stream)), info)
+        return self
+
+    def sort_indices(self, stream=None):
+        """A new sorted, validated vector (sprs_hip_csvec_from_unsorted); this one is only read."""
+        h, info = C.c_void_p(), _ffi.StructureInfo()
+        _ffi.check_structure_status(lib.sprs_hip_csvec_from_unsorted(self._h, C.byref(h), C.byref(info), _stream_arg(stream)), info)
+        return DeviceCsVec(h.value)
+
+    @classmethod
+    def borrow(cls, dim, indices_t, data_t, validate=False):
+        """Borrow two contiguous torch CUDA tensors (int32 / int64 indices, float64 data) without a copy (new_trusted, or
+        CsVec::new with validate: the check runs on the device)."""
         assert indices_t.is_cuda and data_t.is_cuda and indices_t.is_contiguous() and data_t.is_contiguous()
         assert data_t.element_size() == 8 and indices_t.numel() == data_t.numel()
         h = C.c_void_p()
         check(lib.sprs_hip_csvec_wrap_device(C.byref(h), int(dim), indices_t.numel(),
                                              C.c_void_p(indices_t.data_ptr() if indices_t.numel() else 0),
                                              indices_t.element_size(), C.c_void_p(data_t.data_ptr() if data_t.numel() else 0)))
-        return cls(h.value, keep=(indices_t, data_t))
+        v = cls(h.value, keep=(indices_t, data_t))
+        if validate:
+            v.check_structure()
+        return v
 
     def _info(self):
         d, n, ib = C.c_uint64(), C.c_uint64(), C.c_int32()
