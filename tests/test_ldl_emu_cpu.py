@@ -29,3 +29,13 @@ def test_ldl_under_wave_orders(emu_lib, order):
                         "-p", "no:cacheprovider"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
     assert " passed" in r.stdout and "skipped" in r.stdout, r.stdout[-1000:]    # the grid / torch cases skip there
+
+
+@pytest.mark.parametrize("order", ["default", "reverse", "rotate"])
+def test_ldl_seams_under_wave_orders(emu_lib, order):
+    """tests/test_ldl_seams_gpu.py on the emulator's 4 CUs: 67 rows for 32 waves, so waves take a second and a third row"""
+    env = dict(os.environ, SPRS_HIP_LIBRARY=emu_lib, HIPEMU_WAVE_ORDER=order)
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_ldl_seams_gpu.py"), "-x", "-q", "-m", "gpu",
+                        "-p", "no:cacheprovider"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
+    assert " passed" in r.stdout and "skipped" in r.stdout and "failed" not in r.stdout, r.stdout[-1000:]   # the device-size cases skip there
