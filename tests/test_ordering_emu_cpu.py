@@ -29,3 +29,14 @@ def test_orderings_under_wave_orders(emu_lib, order):
                         "-p", "no:cacheprovider"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
     assert " passed" in r.stdout and "skipped" in r.stdout, r.stdout[-1000:]    # the large / torch cases skip there
+
+
+@pytest.mark.parametrize("order", ["default", "reverse", "rotate"])
+def test_ordering_seams_under_wave_orders(emu_lib, order):
+    """tests/test_ordering_seams_gpu.py: the narrow kernel's LDS limits, the budget seam and the tile seams of degrees and
+    is_symmetric.  The route witnesses are counted by host code, so they hold here as on the device."""
+    env = dict(os.environ, SPRS_HIP_LIBRARY=emu_lib, HIPEMU_WAVE_ORDER=order)
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_ordering_seams_gpu.py"), "-x", "-q", "-m", "gpu",
+                        "-p", "no:cacheprovider"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
+    assert " passed" in r.stdout and "1 skipped" in r.stdout and "failed" not in r.stdout, r.stdout[-1000:]   # the third launch of the budget skips there
