@@ -674,6 +674,43 @@ int32_t sprs_hip_ldl_ltsolve_f64(sprs_hip_csmat *l, double *x_dev, uint64_t n, v
 /* linalg::diag_solve (linalg.rs:17-29): x[i] /= d[i] on DEVICE arrays.  Asynchronous on `stream`. */
 int32_t sprs_hip_diag_solve_f64(const double *d_dev, double *x_dev, uint64_t n, void *stream);
 
+/* ---- sparse-rhs triangular solve (sprs/src/sparse/linalg/trisolve.rs:286-358) ---------------------------------------------- */
+
+/* reach = unknowns of the solution's pattern; reach_levels = breadth-first levels of the search that found them;
+ * reach_launches = launches of its frontier kernels, each followed by one read-back of its state (the one-workgroup kernel
+ * runs up to `sptrisolve_budget` narrow levels per launch, a wide level is a launch of its own); solve_levels = levels of the
+ * handle's lower level plan, from which the solve order is drawn (an upper bound on the chain inside the reach).
+ * singular_index / singular_reason as in sprs_hip_trisolve_info. */
+typedef struct sprs_hip_sptrisolve_info {
+    uint64_t reach, reach_levels, reach_launches, solve_levels;
+    uint64_t singular_index;    /* UINT64_MAX */
+    int32_t singular_reason;    /* 0 / 1 numeric / 2 structural */
+} sprs_hip_sptrisolve_info;
+
+/* Twin of lsolve_csc_sparse_rhs (sprs/src/sparse/linalg/trisolve.rs:286-358): L x = rhs with a sparse rhs, at a cost that
+ * follows the REACH of rhs — every column a search over the columns of L gets to from a stored index of rhs (stored zeros
+ * are roots too; every stored entry of a column is followed, the diagonal and entries above it included) — instead of n.
+ * *out = a NEW owning CsVec handle: dimension n, L's declared index width, the reach in ASCENDING order with every index of
+ * it stored (numeric zeros kept), x there.  Differences from the reference, all three deliberate:
+ *   (a) the reference leaves the pattern as an unsorted stack beside a dense workspace and processes its columns in the
+ *       reverse post-order of its depth-first search; here unknown r receives its products by ascending column (each
+ *       product rounded, then each subtraction, then one division).  Exact arithmetic gives identical bits; general values
+ *       can differ in the last bits where a row receives two or more products;
+ *   (b) a fill-in unknown (in the reach, not stored in rhs) starts from +0.0, not from the previous contents of a workspace;
+ *   (c) of several singular columns in the reach the SMALLEST index is reported (the reference: the first in its search
+ *       order), "a structural 0" for a diagonal that is not stored, "a numeric 0" for a stored 0.0 or -0.0 (NaN is not
+ *       zero).  A singular column outside the reach is not an error, and an inf or NaN stored under a column outside the
+ *       reach never reaches x.
+ * l must be a CSC handle (a transpose view of a CSR matrix is one) with sorted columns; the solve runs on its cached CSR
+ * form, whose level plan and scratch are kept in the handle: after the first solve, a solve makes no pass over n or
+ * nnz(L).
+ * SPRS_HIP_INVALID_ARG for a NULL handle, vector or out, a CSR handle ("Storage mismatch") or n >= 2^32;
+ * SPRS_HIP_DIM_MISMATCH unless L is square and rhs.dim == n; SPRS_HIP_INDEX_OVERFLOW when n does not fit L's declared
+ * index width; SPRS_HIP_SINGULAR_MATRIX ("Singular matrix at index i (reason)") with *out == NULL; n == 0 or an rhs without
+ * stored entries give an empty vector.  Blocks until done; runs its work on `stream`. */
+int32_t sprs_hip_lsolve_csc_sparse_rhs_f64(sprs_hip_csmat *l, const sprs_hip_csvec *rhs, sprs_hip_csvec **out,
+                                           sprs_hip_sptrisolve_info *info, void *stream);
+
 /* ---- construction (sprs/src/sparse/kronecker.rs, construct.rs) -----------------------------------------------------------
  * New owning handles assembled on the device; indptr, indices and value bits are the reference's.  All operands of one call
  * must declare the same index and indptr widths (the reference's one I / Iptr): SPRS_HIP_STORAGE_MISMATCH otherwise.  The
@@ -819,6 +856,8 @@ int32_t sprs_hip_triplets_to_cs(uint64_t rows, uint64_t cols, uint64_t n, const 
  *                          keeps in LDS; wider levels run as a grid; 0: every level does; "ordering_key_bits" (INTEGRATION.md);
  * name = "ldl_lds_cap":    LDL^T numeric pass: longest row of L (entries, default and maximum 1024) whose work vector stays in
  *                          LDS; longer rows use a slice of a device array.  Same bits either way;
+ * name = "sptrisolve_budget": sparse-rhs triangular solve: narrow levels of the reach per launch of its one-workgroup kernel
+ *                          (default 4096, 1 ... 2^20); same result whatever the value;
  * name = "spgemm_*", "spmm_long_row", "spmm_stream", "pool", "pool_max_bytes": INTEGRATION.md, "Options".
  * The whole table (name, default, range) is SPRS_HIP_OPTIONS in sprs_amd/csrc/common.hpp.  Developer switches — timing
  * experiments with WRONG results (spgemm_debug, spmv_xmask, spmv_band_debug) and the profiling printout spgemm_prof — exist

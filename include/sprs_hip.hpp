@@ -997,6 +997,20 @@ inline TriSolveResult usolve_csc_dense_rhs(const DeviceCsMat &upper_tri_mat, Dev
 inline TriSolveResult usolve_csr_dense_rhs(const DeviceCsMat &upper_tri_mat, DeviceVec &rhs) {   // trisolve.rs:219-262
     return detail::trisolve(upper_tri_mat, rhs, true, SPRS_HIP_UPPER);
 }
+// lsolve_csc_sparse_rhs (trisolve.rs:286-358) with a device-resident sparse rhs.  The reference leaves an unsorted stack and
+// a dense workspace; here the solution is a new DeviceCsVec over the reach of rhs in ascending order (numeric zeros kept).
+// Products go into an unknown by ascending column (identical bits wherever the arithmetic is exact), fill-in starts from
+// +0.0, the smallest singular index of the reach is thrown as SingularMatrix; `info` (optional) receives the device-side counts.
+inline DeviceCsVec lsolve_csc_sparse_rhs(const DeviceCsMat &lower_tri_mat, const DeviceCsVec &rhs, sprs_hip_sptrisolve_info *info = nullptr) {
+    if (lower_tri_mat.is_csr()) throw Error(SPRS_HIP_STORAGE_MISMATCH, "Storage mismatch");
+    sprs_hip_sptrisolve_info local{};
+    sprs_hip_csvec *x = nullptr;
+    const int32_t status = sprs_hip_lsolve_csc_sparse_rhs_f64(const_cast<sprs_hip_csmat *>(lower_tri_mat.handle()), rhs.handle(), &x, &local, nullptr);
+    if (info) *info = local;
+    if (status == SPRS_HIP_SINGULAR_MATRIX) throw SingularMatrix(sprs_hip_last_error(), local.singular_index, local.singular_reason);
+    check(status);
+    return DeviceCsVec(x);
+}
 }  // namespace linalg
 
 // Result blocks released by ~DeviceCsMat stay in the library's pool for the next result (sprs_hip.h);

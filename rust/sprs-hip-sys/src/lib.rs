@@ -100,6 +100,19 @@ pub struct sprs_hip_trisolve_info {
     pub singular_reason: i32,
 }
 
+/// result of sprs_hip_lsolve_csc_sparse_rhs_f64 (include/sprs_hip.h; trisolve.rs:286-358): the size of the reach, the levels
+/// and launches of the search that found it, the levels of the handle's lower level plan; the singular report as above
+#[repr(C)]
+#[derive(Debug, Clone, Copy, Default)]
+pub struct sprs_hip_sptrisolve_info {
+    pub reach: u64,
+    pub reach_levels: u64,
+    pub reach_launches: u64,
+    pub solve_levels: u64,
+    pub singular_index: u64,
+    pub singular_reason: i32,
+}
+
 /// result of the structure checks and of new_from_unsorted (include/sprs_hip.h): kind = StructureErrorKind (0 ok, 1 Unsorted,
 /// 2 SizeMismatch, 3 OutOfRange), outer = the first offending outer slice (u64::MAX for the dimensions or the indptr)
 #[repr(C)]
@@ -131,6 +144,8 @@ extern "C" {
                                      eps: f64, info: *mut sprs_hip_gauss_seidel_info, stream: *mut c_void) -> i32;
     pub fn sprs_hip_trisolve_f64(a: *mut sprs_hip_csmat, uplo: i32, x_dev: *mut f64, n: u64,
                                  info: *mut sprs_hip_trisolve_info, stream: *mut c_void) -> i32;
+    pub fn sprs_hip_lsolve_csc_sparse_rhs_f64(l: *mut sprs_hip_csmat, rhs: *const sprs_hip_csvec, out: *mut *mut sprs_hip_csvec,
+                                              info: *mut sprs_hip_sptrisolve_info, stream: *mut c_void) -> i32;
     pub fn sprs_hip_csmat_upload(
         out: *mut *mut sprs_hip_csmat, storage: i32, rows: u64, cols: u64,
         indptr: *const c_void, iptr_bytes: i32, indices: *const c_void, idx_bytes: i32,

@@ -440,6 +440,29 @@ pub mod linalg {
     pub fn usolve_csr_dense_rhs(upper_tri_mat: &DeviceCsMat, rhs: &mut DeviceVec) -> Result<(), sprs::errors::LinalgError> {
         trisolve(upper_tri_mat, rhs, true, sys::SPRS_HIP_UPPER, "diagonal element is a numeric 0")
     }
+
+    /// Twin of `lsolve_csc_sparse_rhs` (trisolve.rs:286-358) with a device-resident sparse `rhs`.  The reference leaves the
+    /// pattern as an unsorted stack beside a dense workspace; here the solution comes back as a new `DeviceCsVec` whose
+    /// pattern is the reach of `rhs` in ascending order (numeric zeros kept).  Unknown r receives its products by ascending
+    /// column (identical bits wherever the arithmetic is exact), a fill-in unknown starts from +0.0, and of several
+    /// singular columns in the reach the smallest index is reported; a singular column outside the reach is not an error.
+    pub fn lsolve_csc_sparse_rhs(lower_tri_mat: &DeviceCsMat, rhs: &DeviceCsVec) -> Result<DeviceCsVec, sprs::errors::LinalgError> {
+        let (rows, cols, _, _, _, st) = lower_tri_mat.info();
+        assert!(st == sys::SPRS_HIP_CSC, "Storage mismatch");                      // trisolve.rs:301
+        assert_eq!(cols, rows, "Non square matrix passed to solver");
+        assert_eq!(rows, rhs.dim(), "Dimension mismatch");
+        let mut info = sys::sprs_hip_sptrisolve_info::default();
+        let mut h: *mut sys::sprs_hip_csvec = std::ptr::null_mut();
+        let status = unsafe { sys::sprs_hip_lsolve_csc_sparse_rhs_f64(lower_tri_mat.h, rhs.h, &mut h, &mut info, std::ptr::null_mut()) };
+        if status == sys::SPRS_HIP_SINGULAR_MATRIX {
+            return Err(sprs::errors::LinalgError::SingularMatrix(sprs::errors::SingularMatrixInfo {
+                index: info.singular_index as usize,
+                reason: if info.singular_reason == 2 { "diagonal element is a structural 0" } else { "diagonal element is a numeric 0" },
+            }));
+        }
+        check(status);
+        Ok(DeviceCsVec { h })
+    }
 }
 
 /// Result blocks released by `Drop for DeviceCsMat` stay pooled inside the library; this returns them to

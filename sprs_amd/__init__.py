@@ -13,7 +13,8 @@ from .construct import bmat, hstack, kronecker_product, same_storage_fast_stack,
 from .permutation import DevicePerm
 from .ordering import Ordering, cuthill_mckee_custom, is_symmetric, reverse_cuthill_mckee
 from .ldl import FillInReduction, Ldl, LdlNumeric, LdlSymbolic, PermutationCheck, SymmetryCheck, ldl_lsolve, ldl_ltsolve
-from .linalg import diag_solve, lsolve_csc_dense_rhs, lsolve_csr_dense_rhs, usolve_csc_dense_rhs, usolve_csr_dense_rhs
+from .linalg import (diag_solve, lsolve_csc_dense_rhs, lsolve_csc_sparse_rhs, lsolve_csr_dense_rhs, usolve_csc_dense_rhs,
+                     usolve_csr_dense_rhs)
 
 
 def device_count():

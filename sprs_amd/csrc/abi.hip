@@ -728,6 +728,35 @@ int32_t sprs_hip_trisolve_f64(sprs_hip_csmat *a, int32_t uplo, double *x_dev, ui
     return trisolve_f64(csr, uplo == SPRS_HIP_UPPER, a->storage == SPRS_HIP_CSC, x_dev, n, info, (hipStream_t)stream);
 }
 
+// lsolve_csc_sparse_rhs (trisolve.rs:286-358): the reach over l's own columns, the solve on its CSR form (where the level plan
+// and the scratch live).  l->mu is held for the whole (blocking) call, like above.
+int32_t sprs_hip_lsolve_csc_sparse_rhs_f64(sprs_hip_csmat *l, const sprs_hip_csvec *rhs, sprs_hip_csvec **out, sprs_hip_sptrisolve_info *info,
+                                           void *stream) {
+    clear_error();
+    if (!out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    if (!l || !rhs) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if (l->storage != SPRS_HIP_CSC) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "Storage mismatch");       // trisolve.rs:301
+    if (l->rows != l->cols) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Non square matrix passed to solver");
+    const uint64_t n = l->rows;
+    if (rhs->dim != n) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    if (n >= (1ull << 32)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "triangular solve: 2^32 rows or more are not supported");
+    if (info) *info = sprs_hip_sptrisolve_info{0, 0, 0, 0, UINT64_MAX, 0};
+    // the result carries l's index type: its dimension must be representable there (I::from(n), vec.rs:446-451)
+    if (n > width_max(l->user_idx_bytes())) SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "Index size is too small");
+    OwnedCsvec res;
+    if (n == 0 || rhs->nnz == 0) {
+        SPRS_TRY(make_csvec(res, n, 0, l->idx_bytes, l->user_idx_bytes()));
+    } else {
+        std::lock_guard<std::recursive_mutex> lock(l->mu);
+        sprs_hip_csmat *csr = nullptr;
+        SPRS_TRY(csr_form(l, &csr));
+        SPRS_TRY(sptrisolve_f64(l, csr, rhs, res, info, (hipStream_t)stream));
+    }
+    *out = res.release();
+    return SPRS_HIP_OK;
+}
+
 static int32_t vec_args_ok(const double *x_dev, uint64_t x_len, double *y_dev, uint64_t y_len) {
     if ((x_len && !x_dev) || (y_len && !y_dev)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL vector");
     if (x_len && y_len && x_dev < y_dev + y_len && y_dev < x_dev + x_len)

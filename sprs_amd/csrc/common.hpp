@@ -113,7 +113,8 @@ constexpr bool DEVTOOLS = false;
     X(dense_tile, 2048, 2048, 2048, 0)  /* dense elements (from_dense) / stored entries (assign_to_dense, the sparse-with-dense binops) per workgroup of the dense <-> sparse kernels (dense.hpp): fixed, published so that tests can place tile edges */ \
     X(ordering_narrow_cap, 1024, 0, 1024, 0) /* Cuthill-McKee (ordering.hpp): a frontier of at most this many vertices (and at most 4096 stored entries) is expanded, sorted and committed in LDS by the one-workgroup kernel, which goes on to the next level or component without returning to the host; wider levels run as a grid; 0: every level runs as a grid.  Published so that tests can put the seam at 8 vertices */ \
     X(ordering_key_bits, 64, 1, 64, 0)  /* Cuthill-McKee, wide levels: the key (owner, degree, id) goes through ONE radix sort when it fits this many bits, else through two stable ones (by id, then by owner and degree); 64 = whenever it fits a word.  Published so that tests can take the second route */ \
-    X(ldl_lds_cap, 1024, 1, 1024, 0)    /* LDL^T numeric kernel (ldl.hpp): a row of L with at most this many entries keeps its work vector y in LDS, a longer one in its slice of a device array.  Published so that tests can run both paths at small n */ \
+    X(sptrisolve_budget, 4096, 1, 1ll << 20, 0) /* sparse-rhs triangular solve (sptrisolve.hpp): levels of the reach the one-workgroup kernel runs per launch before it hands the state back to the host; a reach of depth d costs ceil(d / budget) launches and read-backs while its frontiers stay narrow (at most 1024 vertices and 4096 stored entries).  Published so that tests can cross it with a short chain */ \
+    X(ldl_lds_cap, 1024, 1, 1024, 0)   /* LDL^T numeric kernel (ldl.hpp): a row of L with at most this many entries keeps its work vector y in LDS, a longer one in its slice of a device array.  Published so that tests can run both paths at small n */ \
     X(pool, 1, 0, 1, 0)                 /* keep released result blocks (>= 1 MiB) for the next result instead of hipFree */        \
     X(pool_max_bytes, 128ll << 30, 0, INT64_MAX, 0) /* cap on the bytes the pool may hold */
 
@@ -287,6 +288,25 @@ struct GsPlan {
     uint64_t no_diag_row = UINT64_MAX; // first row without a stored diagonal entry (the reference's diag.unwrap() panics there)
     uint64_t chain_tried = 0;          // stride the band schedule was last checked for (0: never) ...
     bool chain_ok = false;             // ... and whether every dependency fits it (gs_band_check_kernel)
+    uint32_t *pos = nullptr;           // device, rows entries: pos[order[q]] = q, made by the first sparse-rhs solve (sptrisolve.hpp)
+    DevBuf pos_block;                  // the block behind pos
+};
+
+// ---- sparse-rhs triangular solve: per-handle scratch (sptrisolve.hpp) ------------------------------
+// Lives on the CSR form of the handle, beside the lower level plan.  `clean`: the bitmap is all zero, every granule of the work
+// vector reads "absent" and b is +0.0 everywhere — what a solve finds and, by touching only its pattern, leaves behind.  Any
+// error in between leaves clean = false and the next solve clears all of it.
+struct SpTriScratch {
+    uint32_t *bits = nullptr;          // device, ceil(n / 32): the visited bitmap of the reach
+    uint32_t *queue = nullptr;         // device, n: the reach in discovery order, then the solve order
+    unsigned long long *work = nullptr;   // device, n: the hand-off granules of tri_solve_kernel
+    double *b = nullptr;               // device, n: the right-hand side scattered, the solution on return
+    uint64_t *keys = nullptr;          // device, 4 n: (index, index) and (position in the level order, index), the two sorts
+    uint64_t *words = nullptr;         // device: the state of the reach, the status words of the solve
+    uint64_t *lens = nullptr;          // device, 2 n + 1: column lengths of a wide frontier and their scan (made by the first wide level)
+    uint64_t n = 0;
+    bool clean = false;
+    std::vector<DevBuf> blocks;        // the blocks behind the arrays above
 };
 
 // ---- sparse-vector products: per-handle temporaries (csvec.hpp) ------------------------------------
@@ -393,6 +413,7 @@ struct sprs_hip_csmat {
     sprs_hip::GsPlan gs;                 // rows by the levels of the stored c < row: Gauss-Seidel and the lower triangular solves
     sprs_hip::GsPlan tri_upper;          // the mirror (stored c > row, levels rising from the last row): the upper triangular solves (trisolve.hpp)
     sprs_hip::CsvecScratch cv;           // temporaries of the sparse-vector products that run on this handle (csvec.hpp)
+    sprs_hip::SpTriScratch sp;           // scratch of the sparse-rhs triangular solve (sptrisolve.hpp): on the CSR form, beside gs
     sprs_hip_csmat *t_view = nullptr;    // transpose view (of the CSC form) kept for dense . sparse products (sprs_hip_dense_dot_csmat_f64): its SpMM / SpMV plans live as long as the values do; dropped with as_other
     sprs_hip_csmat *as_other = nullptr;  // the handle in the OTHER storage order (to_other_storage, csmat.rs:1405-1426): made by the first product that needs it (a CSC operand of a dense product / SpMV runs on its CSR form), dropped by refresh / free
 
@@ -530,6 +551,10 @@ int32_t gauss_seidel_f64(sprs_hip_csmat *a, double *x, const double *rhs, uint64
                          sprs_hip_gauss_seidel_info *info, hipStream_t stream);
 // trisolve.hpp (compiled in gauss_seidel.hip): csr = the CSR form of the caller's handle, csc = that handle is CSC
 int32_t trisolve_f64(sprs_hip_csmat *csr, bool upper, bool csc, double *x, uint64_t n, sprs_hip_trisolve_info *info, hipStream_t stream);
+// sptrisolve.hpp (compiled in gauss_seidel.hip): lsolve_csc_sparse_rhs; l = the caller's CSC handle (its columns are the graph
+// of the reach), csr = its CSR form (plan, scratch, the rows the solve walks).  Complete on `stream` at return
+int32_t sptrisolve_f64(sprs_hip_csmat *l, sprs_hip_csmat *csr, const sprs_hip_csvec *rhs, OwnedCsvec &out, sprs_hip_sptrisolve_info *info,
+                       hipStream_t stream);
 // ldl.hpp (compiled in gauss_seidel.hip): twins of sprs-ldl/src/lib.rs; p = null for the identity.  Complete on `stream` at return
 int32_t ldl_symbolic(const sprs_hip_csmat *m, const sprs_hip_perm *p, LdlSym &s, hipStream_t stream);
 int32_t ldl_factor_f64(LdlSym &s, const sprs_hip_csmat *m, sprs_hip_ldl_num *num, sprs_hip_trisolve_info *info, hipStream_t stream);

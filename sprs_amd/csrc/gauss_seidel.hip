@@ -800,6 +800,10 @@ int32_t gs_impl(sprs_hip_csmat *a, double *x, const double *rhs, uint64_t n, uin
 // trisolve.hpp, compiled here: they share the level plan and the device helpers above
 #include "trisolve.hpp"
 
+// the lower solve with a sparse right-hand side (lsolve_csc_sparse_rhs): a reach over the columns, then tri_solve_kernel over the
+// level order restricted to it
+#include "sptrisolve.hpp"
+
 // LDL^T factorization (sprs-ldl): the etree pass, the numeric kernel and the unit-diagonal solves share the hand-off, the level
 // plans and tri_solve_kernel
 #include "ldl.hpp"

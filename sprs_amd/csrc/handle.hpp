@@ -230,6 +230,7 @@ void invalidate_caches(sprs_hip_csmat *m) {
     m->gs = GsPlan();
     m->tri_upper = GsPlan();
     m->cv = CsvecScratch();
+    m->sp = SpTriScratch();
     delete m->t_view;
     m->t_view = nullptr;
     delete m->as_other;
@@ -241,6 +242,6 @@ void invalidate_caches(sprs_hip_csmat *m) {
 sprs_hip_csmat::~sprs_hip_csmat() {
     // a kernel launched through a cached copy (as_other, t_view) or a plan copy may still be reading it: a handle that holds
     // any of them waits for the device before they go (refresh does the same; a bare handle frees at once)
-    if (t_view || as_other || plan.built || cv.bits) (void)hipDeviceSynchronize();
+    if (t_view || as_other || plan.built || cv.bits || sp.bits) (void)hipDeviceSynchronize();
     sprs_hip::invalidate_caches(this);
 }

@@ -34,10 +34,15 @@
 namespace {
 
 constexpr unsigned int TS_SINGULAR = 4u;                      // status bit beside GS_NO_DIAG / GS_TIMEOUT
+constexpr unsigned long long TS_ABSENT = ~0ull - 1ull;       // SPARSE: "this unknown is not part of the solve" (a second NaN no arithmetic yields)
 
 // UNIT: the diagonal is 1 and not stored (the factor L of ldl.hpp: ldl_lsolve / ldl_ltsolve, sprs-ldl/src/lib.rs:595-626); a row
 // is then its chain of subtractions, never divided and never singular.
-template <typename IDX, typename PTR, bool UPPER, bool BACKWARD, bool UNIT = false>
+// SPARSE: `order` holds a SUBSET of the unknowns (the reach of a sparse right-hand side, sptrisolve.hpp) and the work vector
+// tells three states apart: GS_PENDING (in the subset, not solved yet), a value, and TS_ABSENT (not in the subset: the unknown
+// is exactly zero).  An absent operand counts as arrived and its product is SKIPPED — not multiplied by 0.0, which would turn
+// a stored inf or NaN of that column into a NaN.  Off, the kernel compiles to what it was.
+template <typename IDX, typename PTR, bool UPPER, bool BACKWARD, bool UNIT = false, bool SPARSE = false>
 __global__ __launch_bounds__(GS_BLOCK) void tri_solve_kernel(const PTR *__restrict__ indptr, const IDX *__restrict__ indices,
                                                              const double *__restrict__ data, const uint32_t *__restrict__ order,
                                                              double *x, unsigned long long *work, uint64_t n,
@@ -62,7 +67,7 @@ __global__ __launch_bounds__(GS_BLOCK) void tri_solve_kernel(const PTR *__restri
         bool has_diag = false, last = false;
         uint32_t col[GS_B];
         double val[GS_B], xv[GS_B];
-        uint32_t nb = 0, pend = 0, spins = 0;
+        uint32_t nb = 0, pend = 0, spins = 0, absent = 0;
         bool loaded = false, more = true;
         while (more) {
             bool moved = false;
@@ -84,6 +89,7 @@ __global__ __launch_bounds__(GS_BLOCK) void tri_solve_kernel(const PTR *__restri
                         if ((uint32_t)u < nb) touch |= col[u];
                     GS_TOUCH(touch);
                     pend = 0;
+                    absent = 0;
 #pragma unroll
                     for (int u = 0; u < GS_B; ++u)
                         if ((uint32_t)u < nb && (UPPER ? col[u] > row : col[u] < row)) pend |= 1u << u;
@@ -99,6 +105,7 @@ __global__ __launch_bounds__(GS_BLOCK) void tri_solve_kernel(const PTR *__restri
                 for (int u = 0; u < GS_B; ++u)
                     if (((pend >> u) & 1u) && bits[u] != GS_PENDING) {
                         xv[u] = __longlong_as_double((long long)bits[u]);
+                        if (SPARSE && bits[u] == TS_ABSENT) absent |= 1u << u;
                         pend &= ~(1u << u);
                         moved = true;
                     }
@@ -110,7 +117,7 @@ __global__ __launch_bounds__(GS_BLOCK) void tri_solve_kernel(const PTR *__restri
                             if (c == row) {
                                 diag = val[u];
                                 has_diag = true;
-                            } else if (UPPER ? c > row : c < row) {
+                            } else if ((UPPER ? c > row : c < row) && !(SPARSE && ((absent >> u) & 1u))) {
                                 const double prod = val[u] * xv[u];
                                 acc = acc - prod;
                             }
@@ -130,7 +137,7 @@ __global__ __launch_bounds__(GS_BLOCK) void tri_solve_kernel(const PTR *__restri
                         } else {
                             x[row] = xr;
                         }
-                        if (out == GS_PENDING) out = GS_QNAN;   // (a NaN payload handed through from b: still a NaN, but not "pending")
+                        if (out == GS_PENDING || (SPARSE && out == TS_ABSENT)) out = GS_QNAN;   // (a NaN payload handed through from b: still a NaN, but not "pending")
                         __hip_atomic_store(work + row, out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         done = true;
                     }

@@ -2,7 +2,8 @@
 sprs::linalg::bicgstab (sprs/src/sparse/linalg/bicgstab.rs) behind `sprs_hip_bicgstab_f64` (every vector resident
 in HBM: two SpMVs, four fused element-wise kernels and three dot launches per iteration) and the Gauss-Seidel
 solver of the heat example (sprs/examples/heat.rs:103-139) behind `sprs_hip_gauss_seidel_f64`; and of the four dense-rhs
-triangular solves of sprs::linalg::trisolve (sprs/src/sparse/linalg/trisolve.rs) behind `sprs_hip_trisolve_f64`."""
+triangular solves of sprs::linalg::trisolve (sprs/src/sparse/linalg/trisolve.rs) behind `sprs_hip_trisolve_f64`, and of its
+sparse-rhs solve behind `sprs_hip_lsolve_csc_sparse_rhs_f64`."""
 import ctypes as C
 
 from . import _ffi
@@ -156,6 +157,33 @@ def usolve_csc_dense_rhs(mat, rhs, stream=None):
     """usolve_csc_dense_rhs(upper_tri_mat, rhs) (trisolve.rs:161-210): every unknown receives its subtractions by DESCENDING
     column, so the bits differ from usolve_csr_dense_rhs on the same matrix, as they do in the reference."""
     return _trisolve(mat, rhs, _ffi.CSC, _ffi.UPPER, stream)
+
+
+class _SpTriInfo(C.Structure):
+    _fields_ = [("reach", C.c_uint64), ("reach_levels", C.c_uint64), ("reach_launches", C.c_uint64), ("solve_levels", C.c_uint64),
+                ("singular_index", C.c_uint64), ("singular_reason", C.c_int32)]
+
+
+def lsolve_csc_sparse_rhs(mat, rhs, stream=None):
+    """lsolve_csc_sparse_rhs(lower_tri_mat, rhs, ..) (trisolve.rs:286-358): mat a square CSC DeviceCsMat, rhs a DeviceCsVec.
+    Returns the solution as a new DeviceCsVec whose pattern is the reach of rhs in ascending order (numeric zeros kept), where
+    the reference leaves an unsorted stack and a dense workspace; `.reach`, `.reach_levels`, `.reach_launches` and
+    `.solve_levels` of the result are device-side information.  Fill-in unknowns start from +0.0.  Raises SprsHipError:
+    INVALID_ARG for a CSR matrix ("Storage mismatch"), DIM_MISMATCH, and SINGULAR_MATRIX (with `.index`, the smallest singular
+    index of the reach, and `.reason`) — a singular column outside the reach is not an error."""
+    from .device import DeviceCsVec
+    info, h = _SpTriInfo(), C.c_void_p()
+    status = lib.sprs_hip_lsolve_csc_sparse_rhs_f64(mat._h, rhs._h, C.byref(h), C.byref(info), C.c_void_p(int(stream) if stream else 0))
+    if status == _ffi.SINGULAR_MATRIX:              # Err(LinalgError::SingularMatrix(SingularMatrixInfo { index, reason }))
+        err = _ffi.SprsHipError(status, lib.sprs_hip_last_error().decode("utf-8", "replace"))
+        err.index = int(info.singular_index)
+        err.reason = _SINGULAR_REASONS[int(info.singular_reason)]
+        raise err
+    check(status)
+    out = DeviceCsVec(h.value)
+    out.reach, out.reach_levels = int(info.reach), int(info.reach_levels)
+    out.reach_launches, out.solve_levels = int(info.reach_launches), int(info.solve_levels)
+    return out
 
 
 def diag_solve(diag, x, stream=None):
