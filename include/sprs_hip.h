@@ -783,6 +783,64 @@ int32_t sprs_hip_csmat_binop_dense_f64(const sprs_hip_csmat *lhs, const double *
 int32_t sprs_hip_csmat_add_dense_f64(const sprs_hip_csmat *lhs, const double *rhs_dev, uint64_t rows, uint64_t cols, int32_t layout,
                                      uint64_t ld, double *out_dev, void *stream);
 
+/* ---- reductions and extraction: the small questions asked of a vector or matrix that already sits on the device ----------------
+ * THE ORDERED SUM.  Every scalar below is the reference's left-to-right chain (dot_acc from Acc::zero(), vec.rs:856-880; the
+ * others through Iterator::sum) of unfused terms, bit for bit at every size: a grid forms the terms in entry order, ONE wave adds
+ * them in that order.  No float atomics: the same bits from run to run.  The serial chain's rate bounds these calls on very long
+ * vectors; that is the price of the reference's bits.  The one documented difference: every chain starts from +0.0 (dot_acc does
+ * too; the neutral element of Iterator::sum for f64 has not been the same in every Rust toolchain), so the SIGN of a zero
+ * result of dot_dense and of the norms may differ from a given build of the reference.
+ * All of them run on `stream`; an entry that returns a scalar or a new handle blocks until the result is complete there.
+ * Temporaries are sized by nnz or by the number of queries, never by dim. */
+
+/* CsVec::dot with a sparse rhs (vec.rs:828-881) and prod::csvec_dot_by_binary_search (prod.rs:14-70), one device function: each
+ * entry of the vector with fewer entries (v on equal counts, prod.rs:25) binary-searches the other's indices; the products
+ * v[i] * w[i] of the matched indices are added by ascending index — matched zeros and NaNs like any other term.  The index widths
+ * may differ (the reference compares usize).  SPRS_HIP_DIM_MISMATCH "Dimension mismatch" unless v.dim == w.dim (vec.rs:855).  The
+ * search stays inside [0, nnz) whatever a borrowed, unchecked vector holds. */
+int32_t sprs_hip_csvec_dot_f64(const sprs_hip_csvec *v, const sprs_hip_csvec *w, double *out_host, void *stream);
+/* CsVec::dot_dense and dot with a dense rhs (vec.rs:857-860, 894-904): the chain over data[i] * x[indices[i]] in storage order.
+ * x_len must equal v.dim (SPRS_HIP_DIM_MISMATCH).  An index >= x_len of a borrowed vector contributes no term and is never read. */
+int32_t sprs_hip_csvec_dot_dense_f64(const sprs_hip_csvec *v, const double *x_dev, uint64_t x_len, double *out_host, void *stream);
+/* squared_l2_norm (vec.rs:907-913: terms x * x), l2_norm (916-922: its sqrt, taken on the HOST from the scalar that came back —
+ * the reference's libm, the reference's bits), l1_norm (925-930: terms |x|) and norm(p) (939-958), kind = SPRS_HIP_NORM_P:
+ *   p = +inf  fold(-inf, max) of |x|: 0.0 for an empty vector, -inf for one of NaNs only (f64::max ignores NaN);
+ *   p = -inf  fold(+inf, min) of |x|: 0.0 for an empty vector;
+ *   p = 0     the count of entries with !(|x| == 0), NaN counted, as a double;
+ *   else      the chain over pow(|x|, p) formed on the device, then pow(sum, 1 / p) on the host.  The device's pow is not the
+ *             host's: this is the one result that is close to, not bit-equal with, the reference (DESIGN.md has the measure).
+ * The first three are order-free (exact) and run as an ordinary parallel reduction.  p is ignored for the other kinds. */
+#define SPRS_HIP_NORM_SQUARED_L2 0
+#define SPRS_HIP_NORM_L2 1
+#define SPRS_HIP_NORM_L1 2
+#define SPRS_HIP_NORM_P 3
+int32_t sprs_hip_csvec_norm_f64(const sprs_hip_csvec *v, int32_t kind, double p, double *out_host, void *stream);
+/* unit_normalize (vec.rs:1051-1061): the squared norm by the chain; when it is > 0 every value is divided by its sqrt (taken on
+ * the host; a plain IEEE divide on the device).  Handles are immutable snapshots, so — like sprs_hip_csmat_scale_f64 — this
+ * returns a NEW owning vector with the same indices, width and dim and leaves v alone; a zero vector comes back as a copy. */
+int32_t sprs_hip_csvec_unit_normalize_f64(const sprs_hip_csvec *v, sprs_hip_csvec **out, void *stream);
+/* nnz_index / get (vec.rs:787-805), batched: for the nq indices q_dev[q] (device, uint64_t) pos_dev[q] = the position in the stored
+ * arrays or UINT64_MAX (None) and, when val_dev is not NULL, val_dev[q] = the stored value or 0.0.  An index >= dim is None.
+ * nq = 0 and nnz = 0 launch no kernel.  Asynchronous on `stream`. */
+int32_t sprs_hip_csvec_nnz_index(const sprs_hip_csvec *v, uint64_t nq, const uint64_t *q_dev, uint64_t *pos_dev, double *val_dev,
+                                 void *stream);
+/* outer_view (csmat.rs:1219-1231): zero-copy, as transpose_view is — a BORROWING vector over indices + indptr[i] and
+ * data + indptr[i], of dim = the inner dimension and m's index widths (device and declared); the two indptr values are read back
+ * on `stream`.  i >= outer dims: SPRS_HIP_OK with *out = NULL (the reference's None).  The view is valid until m is freed. */
+int32_t sprs_hip_csmat_outer_view(const sprs_hip_csmat *m, uint64_t i, sprs_hip_csvec **out, void *stream);
+/* diag (csmat.rs:1234-1256): NEW owning vector of dim min(rows, cols) in m's index width; entry i is stored iff (i, i) is —
+ * structural: an explicit 0.0 on the diagonal is kept.  The same for CSR and CSC. */
+int32_t sprs_hip_csmat_diag_f64(const sprs_hip_csmat *m, sprs_hip_csvec **out, void *stream);
+/* nnz_index / get (csmat.rs:1312-1351), batched: for the nq pairs (rows_dev[q], cols_dev[q]) (device, uint64_t) pos_dev[q] = the
+ * global position in indices / data or UINT64_MAX (None), val_dev (may be NULL) as above.  For a CSC handle (outer, inner) =
+ * (col, row).  An outer index >= outer dims or an inner index that is not stored is None, not an error.  Asynchronous on `stream`. */
+int32_t sprs_hip_csmat_nnz_index(const sprs_hip_csmat *m, uint64_t nq, const uint64_t *rows_dev, const uint64_t *cols_dev,
+                                 uint64_t *pos_dev, double *val_dev, void *stream);
+/* to_inner_onehot (csmat.rs:1017-1056): NEW owning matrix of m's shape, storage and index types with a proper indptr: outer slice
+ * o is populated iff it has a non-NaN entry; its one index is the inner index of the maximum — the LAST of equal maxima
+ * (Iterator::max_by; -0.0 == +0.0), NaNs skipped, +-inf taking part — and its value 1.0. */
+int32_t sprs_hip_csmat_to_inner_onehot_f64(const sprs_hip_csmat *m, sprs_hip_csmat **out, void *stream);
+
 /* ---- row-sharded SpMV over the GPUs of one node (one process per GPU, RCCL over xGMI) ----
  * The reference has no distributed code; the shard is its slice_outer (slicing.rs:65-89) with a rebased indptr
  * (indptr.rs:206-214): rank g owns rows [row_starts[g], row_starts[g+1]) and a full replica of x; one exchange, an

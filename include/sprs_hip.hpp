@@ -424,6 +424,42 @@ public:
         return out;
     }
 
+    // Reductions (vec.rs:787-958, 1051-1061; prod.rs:14-70): every sum is the reference's left-to-right chain from +0.0, bit for
+    // bit; the one documented difference is the sign of a zero result of dot_dense and of the norms (sprs_hip.h).
+    double dot(const DeviceCsVec &rhs, void *stream = nullptr) const {          // vec.rs:828-881; throws "Dimension mismatch"
+        double out = 0.0;
+        check(sprs_hip_csvec_dot_f64(h_, rhs.h_, &out, stream));
+        return out;
+    }
+    double dot(const DeviceVec &rhs, void *stream = nullptr) const { return dot_dense(rhs, stream); }
+    double dot_dense(const DeviceVec &rhs, void *stream = nullptr) const {      // vec.rs:894-904
+        double out = 0.0;
+        check(sprs_hip_csvec_dot_dense_f64(h_, rhs.ptr(), rhs.dim(), &out, stream));
+        return out;
+    }
+    double squared_l2_norm(void *stream = nullptr) const { return norm_kind(SPRS_HIP_NORM_SQUARED_L2, 0.0, stream); }   // vec.rs:907-913
+    double l2_norm(void *stream = nullptr) const { return norm_kind(SPRS_HIP_NORM_L2, 0.0, stream); }                   // vec.rs:916-922
+    double l1_norm(void *stream = nullptr) const { return norm_kind(SPRS_HIP_NORM_L1, 0.0, stream); }                   // vec.rs:925-930
+    double norm(double p, void *stream = nullptr) const { return norm_kind(SPRS_HIP_NORM_P, p, stream); }               // vec.rs:939-958
+    // unit_normalize (vec.rs:1051-1061) as a NEW vector: handles are immutable snapshots; a zero vector comes back as a copy
+    DeviceCsVec unit_normalize(void *stream = nullptr) const {
+        sprs_hip_csvec *c = nullptr;
+        check(sprs_hip_csvec_unit_normalize_f64(h_, &c, stream));
+        return DeviceCsVec(c);
+    }
+    // nnz_index / get (vec.rs:787-805), batched: pos[q] = the position in the stored arrays or UINT64_MAX, val[q] = the value or 0.0
+    void nnz_index(const std::vector<uint64_t> &indices, std::vector<uint64_t> &pos, std::vector<double> &val, void *stream = nullptr) const {
+        const uint64_t nq = indices.size();
+        DeviceVec q(nq ? nq : 1), p(nq ? nq : 1), v(nq ? nq : 1);
+        if (nq) check(sprs_hip_memcpy_h2d(q.ptr(), indices.data(), nq * 8));
+        check(sprs_hip_csvec_nnz_index(h_, nq, reinterpret_cast<const uint64_t *>(q.ptr()), reinterpret_cast<uint64_t *>(p.ptr()), v.ptr(), stream));
+        check(sprs_hip_synchronize(stream));
+        pos.resize(nq);
+        val.resize(nq);
+        if (nq) check(sprs_hip_memcpy_d2h(pos.data(), p.ptr(), nq * 8));
+        if (nq) check(sprs_hip_memcpy_d2h(val.data(), v.ptr(), nq * 8));
+    }
+
 private:
     struct Info {
         uint64_t dim, nnz;
@@ -434,8 +470,57 @@ private:
         check(sprs_hip_csvec_info(h_, &i.dim, &i.nnz, &i.idx_bytes));
         return i;
     }
+    double norm_kind(int32_t kind, double p, void *stream) const {
+        double out = 0.0;
+        check(sprs_hip_csvec_norm_f64(h_, kind, p, &out, stream));
+        return out;
+    }
     sprs_hip_csvec *h_ = nullptr;
 };
+
+namespace prod {
+// prod::csvec_dot_by_binary_search (prod.rs:14-70): on the device the same function as CsVec::dot
+inline double csvec_dot_by_binary_search(const DeviceCsVec &vec1, const DeviceCsVec &vec2, void *stream = nullptr) { return vec1.dot(vec2, stream); }
+}  // namespace prod
+
+// Extraction (csmat.rs:1017-1056, 1219-1256, 1312-1351).
+// outer_view (csmat.rs:1219-1231): zero-copy — the vector BORROWS m's arrays and must not outlive m; `found` = false (and an
+// empty handle that must not be used) when i >= outer dims, the reference's None
+inline DeviceCsVec outer_view(const DeviceCsMat &m, uint64_t i, bool *found, void *stream = nullptr) {
+    sprs_hip_csvec *c = nullptr;
+    check(sprs_hip_csmat_outer_view(m.handle(), i, &c, stream));
+    if (found) *found = c != nullptr;
+    return DeviceCsVec(c);
+}
+// diag (csmat.rs:1234-1256): structural, an explicit 0.0 on the diagonal is kept
+inline DeviceCsVec diag(const DeviceCsMat &m, void *stream = nullptr) {
+    sprs_hip_csvec *c = nullptr;
+    check(sprs_hip_csmat_diag_f64(m.handle(), &c, stream));
+    return DeviceCsVec(c);
+}
+// nnz_index / get (csmat.rs:1312-1351), batched over (row, col) pairs: pos[q] = the global position or UINT64_MAX, val[q] = the
+// value or 0.0
+inline void nnz_index(const DeviceCsMat &m, const std::vector<uint64_t> &rows, const std::vector<uint64_t> &cols, std::vector<uint64_t> &pos,
+                      std::vector<double> &val, void *stream = nullptr) {
+    if (rows.size() != cols.size()) throw Error(SPRS_HIP_INVALID_ARG, "rows and cols differ in length");
+    const uint64_t nq = rows.size();
+    DeviceVec r(nq ? nq : 1), c(nq ? nq : 1), p(nq ? nq : 1), v(nq ? nq : 1);
+    if (nq) check(sprs_hip_memcpy_h2d(r.ptr(), rows.data(), nq * 8));
+    if (nq) check(sprs_hip_memcpy_h2d(c.ptr(), cols.data(), nq * 8));
+    check(sprs_hip_csmat_nnz_index(m.handle(), nq, reinterpret_cast<const uint64_t *>(r.ptr()), reinterpret_cast<const uint64_t *>(c.ptr()),
+                                   reinterpret_cast<uint64_t *>(p.ptr()), v.ptr(), stream));
+    check(sprs_hip_synchronize(stream));
+    pos.resize(nq);
+    val.resize(nq);
+    if (nq) check(sprs_hip_memcpy_d2h(pos.data(), p.ptr(), nq * 8));
+    if (nq) check(sprs_hip_memcpy_d2h(val.data(), v.ptr(), nq * 8));
+}
+// to_inner_onehot (csmat.rs:1017-1056): the LAST of equal maxima, NaNs skipped
+inline DeviceCsMat to_inner_onehot(const DeviceCsMat &m, void *stream = nullptr) {
+    sprs_hip_csmat *c = nullptr;
+    check(sprs_hip_csmat_to_inner_onehot_f64(m.handle(), &c, stream));
+    return DeviceCsMat(c);
+}
 
 // `&CsMat * &CsVec` (vec.rs:1104-1131): csr_mul_csvec for CSR, structural for CSC; `&CsVec * &CsMat` (vec.rs:1084-1102)
 inline DeviceCsVec operator*(const DeviceCsMat &a, const DeviceCsVec &v) {

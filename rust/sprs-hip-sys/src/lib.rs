@@ -24,6 +24,10 @@ pub const SPRS_HIP_ROUTE_PEER: i32 = 1;
 pub const SPRS_HIP_BINOP_ADD: i32 = 0;
 pub const SPRS_HIP_BINOP_SUB: i32 = 1;
 pub const SPRS_HIP_BINOP_MUL: i32 = 2;
+pub const SPRS_HIP_NORM_SQUARED_L2: i32 = 0;
+pub const SPRS_HIP_NORM_L2: i32 = 1;
+pub const SPRS_HIP_NORM_L1: i32 = 2;
+pub const SPRS_HIP_NORM_P: i32 = 3;
 pub const SPRS_HIP_START_NEXT: i32 = 0;
 pub const SPRS_HIP_START_MINIMUM_DEGREE: i32 = 1;
 pub const SPRS_HIP_START_PSEUDO_PERIPHERAL: i32 = 2;
@@ -259,6 +263,20 @@ extern "C" {
     pub fn sprs_hip_csvec_binop_f64(
         lhs: *const sprs_hip_csvec, rhs: *const sprs_hip_csvec, op: i32, out: *mut *mut sprs_hip_csvec, stream: *mut c_void,
     ) -> i32;
+    pub fn sprs_hip_csvec_dot_f64(v: *const sprs_hip_csvec, w: *const sprs_hip_csvec, out_host: *mut f64, stream: *mut c_void) -> i32;
+    pub fn sprs_hip_csvec_dot_dense_f64(v: *const sprs_hip_csvec, x_dev: *const f64, x_len: u64, out_host: *mut f64, stream: *mut c_void) -> i32;
+    pub fn sprs_hip_csvec_norm_f64(v: *const sprs_hip_csvec, kind: i32, p: f64, out_host: *mut f64, stream: *mut c_void) -> i32;
+    pub fn sprs_hip_csvec_unit_normalize_f64(v: *const sprs_hip_csvec, out: *mut *mut sprs_hip_csvec, stream: *mut c_void) -> i32;
+    pub fn sprs_hip_csvec_nnz_index(
+        v: *const sprs_hip_csvec, nq: u64, q_dev: *const u64, pos_dev: *mut u64, val_dev: *mut f64, stream: *mut c_void,
+    ) -> i32;
+    pub fn sprs_hip_csmat_outer_view(m: *const sprs_hip_csmat, i: u64, out: *mut *mut sprs_hip_csvec, stream: *mut c_void) -> i32;
+    pub fn sprs_hip_csmat_diag_f64(m: *const sprs_hip_csmat, out: *mut *mut sprs_hip_csvec, stream: *mut c_void) -> i32;
+    pub fn sprs_hip_csmat_nnz_index(
+        m: *const sprs_hip_csmat, nq: u64, rows_dev: *const u64, cols_dev: *const u64, pos_dev: *mut u64, val_dev: *mut f64,
+        stream: *mut c_void,
+    ) -> i32;
+    pub fn sprs_hip_csmat_to_inner_onehot_f64(m: *const sprs_hip_csmat, out: *mut *mut sprs_hip_csmat, stream: *mut c_void) -> i32;
     pub fn sprs_hip_perm_upload(out: *mut *mut sprs_hip_perm, dim: u64, perm: *const c_void, idx_bytes: i32, validate: i32) -> i32;
     pub fn sprs_hip_perm_from_device(
         out: *mut *mut sprs_hip_perm, dim: u64, dev_perm: *const c_void, idx_bytes: i32, validate: i32, stream: *mut c_void,

@@ -193,6 +193,10 @@ impl DeviceMat {
 
 pub mod prod {
     use super::*;
+    /// Twin of `sprs::prod::csvec_dot_by_binary_search` (prod.rs:14-70): on the device the same function as `CsVec::dot`.
+    pub fn csvec_dot_by_binary_search(vec1: &DeviceCsVec, vec2: &DeviceCsVec) -> f64 {
+        vec1.dot(vec2)
+    }
     /// Twin of `sprs::prod::mul_acc_mat_vec_csr` (prod.rs:103-127): `res_vec += mat * in_vec`.
     pub fn mul_acc_mat_vec_csr(mat: &DeviceCsMat, in_vec: &DeviceVec, res_vec: &mut DeviceVec) {
         unsafe {
@@ -579,6 +583,170 @@ impl DeviceCsVec {
 impl Drop for DeviceCsVec {
     fn drop(&mut self) {
         unsafe { sys::sprs_hip_csvec_free(self.h) };
+    }
+}
+
+/// Reductions (vec.rs:787-958, 1051-1061; prod.rs:14-70).  Every sum is the reference's left-to-right chain from +0.0, bit for
+/// bit; the one documented difference is the sign of a zero result of `dot_dense` and of the norms (include/sprs_hip.h).
+impl DeviceCsVec {
+    /// `CsVec::dot` with a sparse rhs (vec.rs:828-881); panics with "Dimension mismatch" like the reference's assert.
+    pub fn dot(&self, rhs: &DeviceCsVec) -> f64 {
+        let mut out = 0.0f64;
+        unsafe { check(sys::sprs_hip_csvec_dot_f64(self.h, rhs.h, &mut out, std::ptr::null_mut())) };
+        out
+    }
+
+    /// `CsVec::dot_dense` (vec.rs:894-904).
+    pub fn dot_dense(&self, rhs: &DeviceVec) -> f64 {
+        let mut out = 0.0f64;
+        unsafe { check(sys::sprs_hip_csvec_dot_dense_f64(self.h, rhs.ptr, rhs.len as u64, &mut out, std::ptr::null_mut())) };
+        out
+    }
+
+    fn norm_kind(&self, kind: i32, p: f64) -> f64 {
+        let mut out = 0.0f64;
+        unsafe { check(sys::sprs_hip_csvec_norm_f64(self.h, kind, p, &mut out, std::ptr::null_mut())) };
+        out
+    }
+
+    /// vec.rs:907-913.
+    pub fn squared_l2_norm(&self) -> f64 {
+        self.norm_kind(sys::SPRS_HIP_NORM_SQUARED_L2, 0.0)
+    }
+
+    /// vec.rs:916-922: the square root is taken on the host.
+    pub fn l2_norm(&self) -> f64 {
+        self.norm_kind(sys::SPRS_HIP_NORM_L2, 0.0)
+    }
+
+    /// vec.rs:925-930.
+    pub fn l1_norm(&self) -> f64 {
+        self.norm_kind(sys::SPRS_HIP_NORM_L1, 0.0)
+    }
+
+    /// vec.rs:939-958, with its branches for p = +-inf and p = 0.
+    pub fn norm(&self, p: f64) -> f64 {
+        self.norm_kind(sys::SPRS_HIP_NORM_P, p)
+    }
+
+    /// `unit_normalize` (vec.rs:1051-1061) as a NEW vector: handles are immutable snapshots; a zero vector comes back as a copy.
+    pub fn unit_normalize(&self) -> DeviceCsVec {
+        let mut h: *mut sys::sprs_hip_csvec = std::ptr::null_mut();
+        unsafe { check(sys::sprs_hip_csvec_unit_normalize_f64(self.h, &mut h, std::ptr::null_mut())) };
+        DeviceCsVec { h }
+    }
+
+    /// `nnz_index` / `get` (vec.rs:787-805), batched: per index the position in the stored arrays and the value, `None` where
+    /// nothing is stored.
+    pub fn get_many(&self, indices: &[usize]) -> Vec<Option<(usize, f64)>> {
+        let q: Vec<u64> = indices.iter().map(|&i| i as u64).collect();
+        let (pos, val) = lookup(q.len(), &[&q], |ptrs, pos, val| unsafe {
+            sys::sprs_hip_csvec_nnz_index(self.h, q.len() as u64, ptrs[0], pos, val, std::ptr::null_mut())
+        });
+        pos.iter().zip(val).map(|(&p, v)| if p == u64::MAX { None } else { Some((p as usize, v)) }).collect()
+    }
+
+    /// vec.rs:800-805.
+    pub fn nnz_index(&self, index: usize) -> Option<usize> {
+        self.get_many(&[index])[0].map(|(p, _)| p)
+    }
+
+    /// vec.rs:787-792.
+    pub fn get(&self, index: usize) -> Option<f64> {
+        self.get_many(&[index])[0].map(|(_, v)| v)
+    }
+}
+
+/// uploads the query arrays, runs `call(queries, pos, val)` and downloads the positions and values
+fn lookup<F: FnOnce(&[*const u64], *mut u64, *mut f64) -> i32>(nq: usize, queries: &[&Vec<u64>], call: F) -> (Vec<u64>, Vec<f64>) {
+    let bytes = (nq.max(1) * 8) as u64;
+    let mut bufs: Vec<*mut c_void> = Vec::new();
+    for _ in 0..queries.len() + 2 {
+        let mut p: *mut c_void = std::ptr::null_mut();
+        unsafe { check(sys::sprs_hip_malloc(&mut p, bytes)) };
+        bufs.push(p);
+    }
+    for (k, q) in queries.iter().enumerate() {
+        unsafe { check(sys::sprs_hip_memcpy_h2d(bufs[k], q.as_ptr() as *const c_void, (nq * 8) as u64)) };
+    }
+    let ptrs: Vec<*const u64> = bufs[..queries.len()].iter().map(|&p| p as *const u64).collect();
+    let (pb, vb) = (bufs[queries.len()], bufs[queries.len() + 1]);
+    let status = call(&ptrs, pb as *mut u64, vb as *mut f64);
+    let (mut pos, mut val) = (vec![0u64; nq], vec![0.0f64; nq]);
+    if status == sys::SPRS_HIP_OK {
+        unsafe {
+            check(sys::sprs_hip_synchronize(std::ptr::null_mut()));
+            check(sys::sprs_hip_memcpy_d2h(pos.as_mut_ptr() as *mut c_void, pb, (nq * 8) as u64));
+            check(sys::sprs_hip_memcpy_d2h(val.as_mut_ptr() as *mut c_void, vb, (nq * 8) as u64));
+        }
+    }
+    for p in bufs {
+        unsafe { sys::sprs_hip_free(p) };
+    }
+    check(status);
+    (pos, val)
+}
+
+/// A `DeviceCsVec` that borrows the arrays of a matrix (`DeviceCsMat::outer_view`): it cannot outlive the matrix.
+pub struct DeviceCsVecView<'a> {
+    v: DeviceCsVec,
+    _m: std::marker::PhantomData<&'a DeviceCsMat>,
+}
+
+impl<'a> std::ops::Deref for DeviceCsVecView<'a> {
+    type Target = DeviceCsVec;
+    fn deref(&self) -> &DeviceCsVec {
+        &self.v
+    }
+}
+
+/// Extraction (csmat.rs:1017-1056, 1219-1256, 1312-1351).
+impl DeviceCsMat {
+    /// `outer_view` (csmat.rs:1219-1231): zero-copy; `None` when `i >= outer_dims()`.
+    pub fn outer_view(&self, i: usize) -> Option<DeviceCsVecView<'_>> {
+        let mut h: *mut sys::sprs_hip_csvec = std::ptr::null_mut();
+        unsafe { check(sys::sprs_hip_csmat_outer_view(self.h, i as u64, &mut h, std::ptr::null_mut())) };
+        if h.is_null() {
+            None
+        } else {
+            Some(DeviceCsVecView { v: DeviceCsVec { h }, _m: std::marker::PhantomData })
+        }
+    }
+
+    /// `diag` (csmat.rs:1234-1256): structural, an explicit 0.0 on the diagonal is kept.
+    pub fn diag(&self) -> DeviceCsVec {
+        let mut h: *mut sys::sprs_hip_csvec = std::ptr::null_mut();
+        unsafe { check(sys::sprs_hip_csmat_diag_f64(self.h, &mut h, std::ptr::null_mut())) };
+        DeviceCsVec { h }
+    }
+
+    /// `nnz_index` / `get` (csmat.rs:1312-1351), batched over (row, col) pairs: the global position and the value, `None`
+    /// where nothing is stored (out-of-range rows and cols included).
+    pub fn get_many(&self, rows: &[usize], cols: &[usize]) -> Vec<Option<(usize, f64)>> {
+        assert_eq!(rows.len(), cols.len());
+        let r: Vec<u64> = rows.iter().map(|&i| i as u64).collect();
+        let c: Vec<u64> = cols.iter().map(|&i| i as u64).collect();
+        let (pos, val) = lookup(r.len(), &[&r, &c], |ptrs, pos, val| unsafe {
+            sys::sprs_hip_csmat_nnz_index(self.h, r.len() as u64, ptrs[0], ptrs[1], pos, val, std::ptr::null_mut())
+        });
+        pos.iter().zip(val).map(|(&p, v)| if p == u64::MAX { None } else { Some((p as usize, v)) }).collect()
+    }
+
+    /// csmat.rs:1312-1330.
+    pub fn nnz_index(&self, row: usize, col: usize) -> Option<usize> {
+        self.get_many(&[row], &[col])[0].map(|(p, _)| p)
+    }
+
+    /// csmat.rs `get`.
+    pub fn get(&self, row: usize, col: usize) -> Option<f64> {
+        self.get_many(&[row], &[col])[0].map(|(_, v)| v)
+    }
+
+    /// `to_inner_onehot` (csmat.rs:1017-1056): the LAST of equal maxima, NaNs skipped.
+    pub fn to_inner_onehot(&self) -> DeviceCsMat {
+        let mut h: *mut sys::sprs_hip_csmat = std::ptr::null_mut();
+        unsafe { check(sys::sprs_hip_csmat_to_inner_onehot_f64(self.h, &mut h, std::ptr::null_mut())) };
+        DeviceCsMat { h }
     }
 }
 

@@ -20,6 +20,8 @@ LOWER, UPPER = 0, 1
 ROW_MAJOR, COL_MAJOR = 0, 1
 ROUTE_RCCL, ROUTE_PEER = 0, 1
 BINOP_ADD, BINOP_SUB, BINOP_MUL = 0, 1, 2
+NORM_SQUARED_L2, NORM_L2, NORM_L1, NORM_P = 0, 1, 2, 3
+NONE = (1 << 64) - 1           # a position of the batched nnz_index: nothing is stored there (the reference's None)
 START_NEXT, START_MINIMUM_DEGREE, START_PSEUDO_PERIPHERAL = 0, 1, 2
 KIND_OK, KIND_UNSORTED, KIND_SIZE_MISMATCH, KIND_OUT_OF_RANGE = 0, 1, 2, 3     # StructureErrorKind (errors.rs)
 NO_OUTER = (1 << 64) - 1       # StructureInfo.outer of a finding about the dimensions or the indptr
@@ -108,6 +110,15 @@ SIGNATURES = {
     "sprs_hip_csmat_sub_csmat_f64": (i32, [vp, vp, P(vp), vp]),
     "sprs_hip_csmat_scale_f64": (i32, [vp, C.c_double, P(vp), vp]),
     "sprs_hip_csvec_binop_f64": (i32, [vp, vp, i32, P(vp), vp]),
+    "sprs_hip_csvec_dot_f64": (i32, [vp, vp, P(C.c_double), vp]),
+    "sprs_hip_csvec_dot_dense_f64": (i32, [vp, vp, u64, P(C.c_double), vp]),
+    "sprs_hip_csvec_norm_f64": (i32, [vp, i32, C.c_double, P(C.c_double), vp]),
+    "sprs_hip_csvec_unit_normalize_f64": (i32, [vp, P(vp), vp]),
+    "sprs_hip_csvec_nnz_index": (i32, [vp, u64, vp, vp, vp, vp]),
+    "sprs_hip_csmat_outer_view": (i32, [vp, u64, P(vp), vp]),
+    "sprs_hip_csmat_diag_f64": (i32, [vp, P(vp), vp]),
+    "sprs_hip_csmat_nnz_index": (i32, [vp, u64, vp, vp, vp, vp, vp]),
+    "sprs_hip_csmat_to_inner_onehot_f64": (i32, [vp, P(vp), vp]),
     "sprs_hip_perm_upload": (i32, [P(vp), u64, vp, i32, i32]),
     "sprs_hip_perm_from_device": (i32, [P(vp), u64, vp, i32, i32, vp]),
     "sprs_hip_perm_identity": (i32, [P(vp), u64, i32]),

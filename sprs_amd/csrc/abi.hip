@@ -4,6 +4,7 @@
 // here inside their owners and are released to the caller's raw pointer in the extern "C" function.  Kernels live in the other
 // translation units.
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstring>
 #include <vector>
@@ -1212,6 +1213,114 @@ int32_t sprs_hip_csvec_binop_f64(const sprs_hip_csvec *lhs, const sprs_hip_csvec
         SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "operands must share the index type (binop.rs:442-446)");
     OwnedCsvec res;
     return finish_csvec(csvec_binop_f64(lhs, rhs, op, ldim, res, (hipStream_t)stream), res, out);
+}
+
+}  // extern "C"
+
+// ---- reductions and extraction (vec.rs:787-958, 1051-1061; prod.rs:14-70; csmat.rs:1017-1056, 1219-1256, 1312-1351);
+// kernels in csvec_reduce.hpp and extract.hpp ------------------------------------------------------------------------------------
+
+extern "C" {
+
+int32_t sprs_hip_csvec_dot_f64(const sprs_hip_csvec *v, const sprs_hip_csvec *w, double *out_host, void *stream) {
+    clear_error();
+    if (!v || !w || !out_host) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    if (v->dim != w->dim) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");     // vec.rs:855
+    return csvec_dot_f64(v, w, out_host, (hipStream_t)stream);
+}
+
+int32_t sprs_hip_csvec_dot_dense_f64(const sprs_hip_csvec *v, const double *x_dev, uint64_t x_len, double *out_host, void *stream) {
+    clear_error();
+    if (!v || !out_host) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    if (x_len != v->dim) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");      // vec.rs:855, 900
+    if (x_len && !x_dev) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL vector");
+    return csvec_dot_dense_f64(v, x_dev, x_len, out_host, (hipStream_t)stream);
+}
+
+int32_t sprs_hip_csvec_norm_f64(const sprs_hip_csvec *v, int32_t kind, double p, double *out_host, void *stream) {
+    clear_error();
+    if (!v || !out_host) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    hipStream_t st = (hipStream_t)stream;
+    double sum = 0.0;
+    switch (kind) {
+    case SPRS_HIP_NORM_SQUARED_L2:
+        return csvec_sum_f64(v, 0, 0.0, out_host, st);
+    case SPRS_HIP_NORM_L2:
+        SPRS_TRY(csvec_sum_f64(v, 0, 0.0, &sum, st));
+        *out_host = std::sqrt(sum);
+        return SPRS_HIP_OK;
+    case SPRS_HIP_NORM_L1:
+        return csvec_sum_f64(v, 1, 0.0, out_host, st);
+    case SPRS_HIP_NORM_P:
+        break;
+    default:
+        SPRS_FAIL(SPRS_HIP_INVALID_ARG, "kind must be SPRS_HIP_NORM_SQUARED_L2, SPRS_HIP_NORM_L2, SPRS_HIP_NORM_L1 or SPRS_HIP_NORM_P");
+    }
+    // norm(p), vec.rs:939-958
+    if (std::isinf(p) || p == 0.0) {
+        if (std::isinf(p) && v->nnz == 0) {
+            *out_host = 0.0;
+            return SPRS_HIP_OK;
+        }
+        double ext[3];
+        SPRS_TRY(csvec_extrema_f64(v, ext, st));
+        *out_host = p == 0.0 ? ext[2] : p > 0.0 ? ext[0] : ext[1];
+        return SPRS_HIP_OK;
+    }
+    SPRS_TRY(csvec_sum_f64(v, 2, p, &sum, st));
+    *out_host = std::pow(sum, 1.0 / p);                          // powf(p.powi(-1))
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_csvec_unit_normalize_f64(const sprs_hip_csvec *v, sprs_hip_csvec **out, void *stream) {
+    clear_error();
+    if (!v || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    double norm_sq = 0.0;
+    SPRS_TRY(csvec_sum_f64(v, 0, 0.0, &norm_sq, (hipStream_t)stream));
+    OwnedCsvec res;
+    return finish_csvec(csvec_divided_f64(v, norm_sq > 0.0 ? std::sqrt(norm_sq) : 0.0, res, (hipStream_t)stream), res, out);
+}
+
+int32_t sprs_hip_csvec_nnz_index(const sprs_hip_csvec *v, uint64_t nq, const uint64_t *q_dev, uint64_t *pos_dev, double *val_dev,
+                                 void *stream) {
+    clear_error();
+    if (!v) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if (nq && (!q_dev || !pos_dev)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL query / position array with nq > 0");
+    return csvec_lookup(v, nq, q_dev, pos_dev, val_dev, (hipStream_t)stream);
+}
+
+int32_t sprs_hip_csmat_outer_view(const sprs_hip_csmat *m, uint64_t i, sprs_hip_csvec **out, void *stream) {
+    clear_error();
+    if (!m || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    if (i >= m->outer()) return SPRS_HIP_OK;                     // None (csmat.rs:1220-1222)
+    return csmat_outer_view(m, i, out, (hipStream_t)stream);
+}
+
+int32_t sprs_hip_csmat_diag_f64(const sprs_hip_csmat *m, sprs_hip_csvec **out, void *stream) {
+    clear_error();
+    if (!m || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    OwnedCsvec res;
+    return finish_csvec(csmat_diag_f64(m, res, (hipStream_t)stream), res, out);
+}
+
+int32_t sprs_hip_csmat_nnz_index(const sprs_hip_csmat *m, uint64_t nq, const uint64_t *rows_dev, const uint64_t *cols_dev, uint64_t *pos_dev,
+                                 double *val_dev, void *stream) {
+    clear_error();
+    if (!m) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if (nq && (!rows_dev || !cols_dev || !pos_dev)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL query / position array with nq > 0");
+    return csmat_lookup(m, nq, rows_dev, cols_dev, pos_dev, val_dev, (hipStream_t)stream);
+}
+
+int32_t sprs_hip_csmat_to_inner_onehot_f64(const sprs_hip_csmat *m, sprs_hip_csmat **out, void *stream) {
+    clear_error();
+    if (!m || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    OwnedCsmat res;
+    SPRS_TRY(csmat_onehot_f64(m, res, (hipStream_t)stream));
+    return finish_result(res, m, out);
 }
 
 }  // extern "C"

@@ -570,6 +570,22 @@ int32_t csvec_check_device(const sprs_hip_csvec *v, hipStream_t stream, sprs_hip
 int32_t csvec_scatter(const sprs_hip_csvec *v, double *out, hipStream_t stream);
 int32_t csvec_masked_dot(const sprs_hip_csmat *m, const sprs_hip_csvec *v, bool drop_zero, int32_t idx_bytes, int32_t decl_bytes,
                          OwnedCsvec &out, hipStream_t stream);
+// csvec_reduce.hpp (compiled in spmv.hip): every scalar is the reference's left-to-right chain from +0.0 and is complete on
+// `stream` at return; csvec_sum_f64: term 0 = x * x, 1 = |x|, 2 = pow(|x|, p); csvec_extrema_f64: out[0..2] = max |x| from -inf,
+// min |x| from +inf, the count of !(|x| == 0); csvec_lookup is ordered on `stream`
+int32_t csvec_dot_f64(const sprs_hip_csvec *v, const sprs_hip_csvec *w, double *out, hipStream_t stream);
+int32_t csvec_dot_dense_f64(const sprs_hip_csvec *v, const double *x, uint64_t x_len, double *out, hipStream_t stream);
+int32_t csvec_sum_f64(const sprs_hip_csvec *v, int32_t term, double p, double *out, hipStream_t stream);
+int32_t csvec_extrema_f64(const sprs_hip_csvec *v, double *out, hipStream_t stream);
+int32_t csvec_divided_f64(const sprs_hip_csvec *v, double norm, OwnedCsvec &out, hipStream_t stream);
+int32_t csvec_lookup(const sprs_hip_csvec *v, uint64_t nq, const uint64_t *qs, uint64_t *pos, double *val, hipStream_t stream);
+// extract.hpp (compiled in convert.hip): outer_view (i < outer, a borrowing vector), diag, the batched nnz_index / get (ordered on
+// `stream`) and to_inner_onehot; results are complete on `stream` at return
+int32_t csmat_outer_view(const sprs_hip_csmat *m, uint64_t i, sprs_hip_csvec **out, hipStream_t stream);
+int32_t csmat_diag_f64(const sprs_hip_csmat *m, OwnedCsvec &out, hipStream_t stream);
+int32_t csmat_lookup(const sprs_hip_csmat *m, uint64_t nq, const uint64_t *rows, const uint64_t *cols, uint64_t *pos, double *val,
+                     hipStream_t stream);
+int32_t csmat_onehot_f64(const sprs_hip_csmat *m, OwnedCsmat &out, hipStream_t stream);
 // handle.hpp: the one place that makes handles
 // an owned matrix / vector / permutation with uninitialised arrays of the given sizes on the current device
 int32_t make_csmat(OwnedCsmat &out, int32_t storage, uint64_t rows, uint64_t cols, uint64_t nnz, int32_t iptr_bytes, int32_t idx_bytes);

@@ -300,3 +300,4 @@ int32_t slice_outer(const sprs_hip_csmat *m, uint64_t start, uint64_t end, Owned
 #include "construct.hpp"   // kronecker_product, same_storage_fast_stack, vstack, hstack, bmat
 #include "dense.hpp"   // csr_from_dense / csc_from_dense, assign_to_dense / to_dense, the sparse-with-dense binops
 #include "ordering.hpp"   // is_symmetric, degrees, max_outer_nnz, Cuthill-McKee orderings
+#include "extract.hpp"   // outer_view, diag, batched nnz_index / get, to_inner_onehot

@@ -26,34 +26,15 @@
 #pragma once
 
 #include "common.hpp"
+#include "csvec_shared.hpp"   // CV_BLOCK, rl_u64 / rl_f64 / span_mask, csvec_emit_kernel (step 4), blocks_for
 
 namespace sprs_hip {
 namespace cv {
 
-constexpr int CV_BLOCK = 256;                 // 4 waves, each its own group of 64 outer slices
 constexpr int CV_WAVES = CV_BLOCK / 64;
 constexpr int CV_UNROLL = 4;                  // chunks of 64 entries whose loads are in flight together (short slices)
 constexpr int CV_UNROLL_LONG = 16;            // the same for a slice walked by the whole wave: its walk is a chain of round trips
 constexpr uint64_t CV_LONG = 128;             // slices with more entries are walked by the whole wave
-
-__device__ __forceinline__ uint64_t rl_u64(uint64_t v, int lane) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, lane);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), lane);
-    return ((uint64_t)hi << 32) | lo;
-}
-
-__device__ __forceinline__ double rl_f64(double v, int lane) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-    return __hiloint2double(hi, lo);
-}
-
-// bits [a, b) of a 64-bit mask, 0 <= a <= b <= 64
-__device__ __forceinline__ uint64_t span_mask(uint64_t a, uint64_t b) {
-    if (a >= b) return 0;
-    const uint64_t upto = b >= 64 ? ~0ull : ((1ull << b) - 1ull);
-    return upto & ~((1ull << a) - 1ull);
-}
 
 // 1. the look-up table: bit k of `bits` and vals[k] = v[k] for every stored k (indices below n: checked at upload; the
 // test here keeps a borrowed, unchecked vector from writing outside the table)
@@ -175,26 +156,6 @@ __global__ void __launch_bounds__(CV_BLOCK) csvec_dot_kernel(const P *ip, const 
     }
 }
 
-// 4. kept slices -> the result's sorted (indices, data).  An index above `limit` (the declared width's maximum) is not
-// written: it raises *overflow instead (I::from_usize would panic, vec.rs append)
-template <typename OI>
-__global__ void __launch_bounds__(CV_BLOCK) csvec_emit_kernel(const uint64_t *masks, const uint64_t *offs, const double *sums,
-                                                              uint64_t nouter, uint64_t limit, OI *oidx, double *oval,
-                                                              uint32_t *overflow) {
-    const uint64_t o = (uint64_t)blockIdx.x * CV_BLOCK + threadIdx.x;
-    if (o >= nouter) return;
-    const uint64_t m = masks[o >> 6];
-    const int b = (int)(o & 63);
-    if (!((m >> b) & 1ull)) return;
-    const uint64_t pos = offs[o >> 6] + (uint64_t)__popcll(m & ((1ull << b) - 1ull));
-    if (o > limit) {
-        atomicOr(overflow, 1u);
-        return;
-    }
-    oidx[pos] = (OI)o;
-    oval[pos] = sums[o];
-}
-
 // CsVec::scatter / to_dense (vec.rs:621, 965): out[idx[i]] = data[i] on a zeroed out
 template <typename VI>
 __global__ void __launch_bounds__(CV_BLOCK) csvec_scatter_kernel(const VI *vidx, const double *vdata, uint64_t nnz, uint64_t n,
@@ -215,8 +176,6 @@ __global__ void __launch_bounds__(CV_BLOCK) csvec_check_kernel(const VI *vidx, u
     if (i + 1 < nnz && (uint64_t)vidx[i + 1] <= k) atomicMin((unsigned long long *)&bad[0], (unsigned long long)i);
     if (i + 1 == nnz && k >= dim) bad[1] = 1;
 }
-
-inline unsigned blocks_for(uint64_t items) { return (unsigned)((items + CV_BLOCK - 1) / CV_BLOCK); }
 
 }  // namespace cv
 

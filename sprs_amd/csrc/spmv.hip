@@ -827,3 +827,5 @@ int32_t spmv_f64(sprs_hip_csmat *a, const double *x, double *y, bool accumulate,
 // sparse-vector products (masked ordered dot): kernels and launchers live in csvec.hpp, compiled here so that the library and
 // its emulator build (tests/emu, a fixed list of translation units) both carry them
 #include "csvec.hpp"
+// sparse-vector reductions (the ordered sum), unit_normalize and the batched look-ups
+#include "csvec_reduce.hpp"

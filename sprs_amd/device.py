@@ -267,6 +267,60 @@ class DeviceCsMat:
         check(lib.sprs_hip_csmat_max_outer_nnz(self._h, C.byref(v), _stream_arg(stream)))
         return v.value
 
+    # -- extraction ---------------------------------------------------------------
+    def outer_view(self, i, stream=None):
+        """csmat.rs:1219-1231: the i-th outer slice as a DeviceCsVec that BORROWS this matrix's arrays (zero-copy; it keeps the
+        matrix alive), or None when i >= outer dims."""
+        h = C.c_void_p()
+        check(lib.sprs_hip_csmat_outer_view(self._h, int(i), C.byref(h), _stream_arg(stream)))
+        return DeviceCsVec(h.value, keep=self) if h.value else None
+
+    def diag(self, stream=None):
+        """csmat.rs:1234-1256: the stored diagonal entries (an explicit 0.0 included) as a new DeviceCsVec of dim min(rows, cols)."""
+        h = C.c_void_p()
+        check(lib.sprs_hip_csmat_diag_f64(self._h, C.byref(h), _stream_arg(stream)))
+        return DeviceCsVec(h.value)
+
+    def _lookup(self, rows, cols, stream):
+        scalar = np.ndim(rows) == 0 and np.ndim(cols) == 0
+        r, c = np.broadcast_arrays(np.atleast_1d(np.asarray(rows, dtype=np.uint64)), np.atleast_1d(np.asarray(cols, dtype=np.uint64)))
+        nq = r.size
+        rb, cb, pb, vb = _u64_to_device(r), _u64_to_device(c), DeviceVec(max(nq, 1)), DeviceVec(max(nq, 1))
+        check(lib.sprs_hip_csmat_nnz_index(self._h, nq, C.c_void_p(rb.ptr), C.c_void_p(cb.ptr), C.c_void_p(pb.ptr), C.c_void_p(vb.ptr),
+                                           _stream_arg(stream)))
+        pos, val = _lookup_results(pb, vb, nq, stream)
+        return scalar, pos, val
+
+    def nnz_index(self, rows, cols, stream=None):
+        """csmat.rs:1312-1330, batched: the position in indices / data of every (row, col), _ffi.NONE where nothing is stored
+        (out-of-range rows and cols included).  Ints give an int or None, arrays a uint64 array."""
+        scalar, pos, _ = self._lookup(rows, cols, stream)
+        if scalar:
+            return None if int(pos[0]) == _ffi.NONE else int(pos[0])
+        return pos
+
+    def nnz_index_outer_inner(self, outer, inner, stream=None):
+        """csmat.rs:1332-1351: the same by (outer, inner)."""
+        return self.nnz_index(outer, inner, stream) if self.is_csr() else self.nnz_index(inner, outer, stream)
+
+    def get(self, rows, cols, stream=None):
+        """csmat.rs get: the stored value of every (row, col); an int pair gives a float or None, arrays give (values, found)
+        with 0.0 where nothing is stored."""
+        scalar, pos, val = self._lookup(rows, cols, stream)
+        if scalar:
+            return None if int(pos[0]) == _ffi.NONE else float(val[0])
+        return val, pos != np.uint64(_ffi.NONE)
+
+    def get_outer_inner(self, outer, inner, stream=None):
+        """csmat.rs get_outer_inner."""
+        return self.get(outer, inner, stream) if self.is_csr() else self.get(inner, outer, stream)
+
+    def to_inner_onehot(self, stream=None):
+        """csmat.rs:1017-1056: per outer slice the last maximal non-NaN entry, with value 1.0, as a new matrix."""
+        h = C.c_void_p()
+        check(lib.sprs_hip_csmat_to_inner_onehot_f64(self._h, C.byref(h), _stream_arg(stream)))
+        return DeviceCsMat(h.value)
+
     # -- operators: `&A * &x`, `&A * &B` ---------------------------------------
     def __mul__(self, rhs):
         from . import prod
@@ -322,6 +376,25 @@ def _stream_arg(stream):
     if stream is None:
         return None
     return C.c_void_p(int(getattr(stream, "cuda_stream", stream)))
+
+
+def _u64_to_device(arr):
+    """a host array as uint64 words in a DeviceVec (complete when this returns)"""
+    arr = np.ascontiguousarray(arr, dtype=np.uint64)
+    buf = DeviceVec(max(arr.size, 1))
+    if arr.size:
+        check(lib.sprs_hip_memcpy_h2d(C.c_void_p(buf.ptr), _vp(arr), arr.size * 8))
+    return buf
+
+
+def _lookup_results(pos_buf, val_buf, nq, stream):
+    """(pos, val) host arrays of a batched nnz_index / get once `stream` has finished them"""
+    check(lib.sprs_hip_synchronize(_stream_arg(stream)))
+    pos, val = np.empty(nq, dtype=np.uint64), np.empty(nq, dtype=np.float64)
+    if nq:
+        check(lib.sprs_hip_memcpy_d2h(_vp(pos), C.c_void_p(pos_buf.ptr), nq * 8))
+        check(lib.sprs_hip_memcpy_d2h(_vp(val), C.c_void_p(val_buf.ptr), nq * 8))
+    return pos, val
 
 
 class DeviceCsVec:
@@ -405,6 +478,68 @@ class DeviceCsVec:
     def to_dense(self, stream=None):
         """CsVec::to_dense (vec.rs:621) as a DeviceVec."""
         return self.scatter(DeviceVec(self.dim()), stream)
+
+    # -- reductions: every sum is the reference's left-to-right chain, bit for bit ---------------------------------
+    def dot(self, rhs, stream=None):
+        """CsVec::dot (vec.rs:828-881) with a DeviceCsVec, a DeviceVec or a contiguous float64 torch CUDA tensor."""
+        out = C.c_double()
+        if isinstance(rhs, DeviceCsVec):
+            check(lib.sprs_hip_csvec_dot_f64(self._h, rhs._h, C.byref(out), _stream_arg(stream)))
+            return out.value
+        return self.dot_dense(rhs, stream)
+
+    def dot_dense(self, rhs, stream=None):
+        """CsVec::dot_dense (vec.rs:894-904)."""
+        if not isinstance(rhs, DeviceVec):
+            rhs = DeviceVec.borrow(rhs)
+        out = C.c_double()
+        check(lib.sprs_hip_csvec_dot_dense_f64(self._h, C.c_void_p(rhs.ptr), rhs.n, C.byref(out), _stream_arg(stream)))
+        return out.value
+
+    def _norm(self, kind, p, stream):
+        out = C.c_double()
+        check(lib.sprs_hip_csvec_norm_f64(self._h, kind, float(p), C.byref(out), _stream_arg(stream)))
+        return out.value
+
+    def squared_l2_norm(self, stream=None):    # vec.rs:907-913
+        return self._norm(_ffi.NORM_SQUARED_L2, 0.0, stream)
+
+    def l2_norm(self, stream=None):            # vec.rs:916-922
+        return self._norm(_ffi.NORM_L2, 0.0, stream)
+
+    def l1_norm(self, stream=None):            # vec.rs:925-930
+        return self._norm(_ffi.NORM_L1, 0.0, stream)
+
+    def norm(self, p, stream=None):            # vec.rs:939-958
+        return self._norm(_ffi.NORM_P, p, stream)
+
+    def unit_normalize(self, stream=None):
+        """unit_normalize (vec.rs:1051-1061) as a NEW vector: handles are immutable snapshots, this one is only read."""
+        h = C.c_void_p()
+        check(lib.sprs_hip_csvec_unit_normalize_f64(self._h, C.byref(h), _stream_arg(stream)))
+        return DeviceCsVec(h.value)
+
+    def _lookup(self, index, stream):
+        q = np.atleast_1d(np.asarray(index, dtype=np.uint64))
+        nq = q.size
+        qb, pb, vb = _u64_to_device(q), DeviceVec(max(nq, 1)), DeviceVec(max(nq, 1))
+        check(lib.sprs_hip_csvec_nnz_index(self._h, nq, C.c_void_p(qb.ptr), C.c_void_p(pb.ptr), C.c_void_p(vb.ptr), _stream_arg(stream)))
+        return _lookup_results(pb, vb, nq, stream)
+
+    def nnz_index(self, index, stream=None):
+        """vec.rs:800-805, batched: the position of every index in the stored arrays, _ffi.NONE where it is not stored.  An int
+        gives an int or None, an array a uint64 array."""
+        pos, _ = self._lookup(index, stream)
+        if np.ndim(index) == 0:
+            return None if int(pos[0]) == _ffi.NONE else int(pos[0])
+        return pos
+
+    def get(self, index, stream=None):
+        """vec.rs:787-792: an int gives the stored value or None; an array gives (values, found), 0.0 where nothing is stored."""
+        pos, val = self._lookup(index, stream)
+        if np.ndim(index) == 0:
+            return None if int(pos[0]) == _ffi.NONE else float(val[0])
+        return val, pos != np.uint64(_ffi.NONE)
 
     def __mul__(self, rhs):
         from . import prod

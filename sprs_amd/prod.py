@@ -202,3 +202,9 @@ def csvec_mul_csmat(vec, mat, stream=None):
     h = C.c_void_p()
     check(lib.sprs_hip_csvec_mul_csmat_f64(vec._h, mat._h, C.byref(h), _stream_ptr(stream)))
     return DeviceCsVec(h.value)
+
+
+def csvec_dot_by_binary_search(vec1, vec2, stream=None):
+    """prod::csvec_dot_by_binary_search (prod.rs:14-70): the entries of the shorter vector looked up in the other by binary search,
+    the matched products added by ascending index — on the device the same function as CsVec::dot (sprs_hip_csvec_dot_f64)."""
+    return vec1.dot(vec2, stream)

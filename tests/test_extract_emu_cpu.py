@@ -1,0 +1,31 @@
+"""Kernel LOGIC of the matrix extraction on the CPU: tests/test_extract_gpu.py against the emulator build of the same sources
+(tests/emu), with the waves of a workgroup scheduled in three orders.  The diagonal search, the look-ups, the lane-per-slice and
+whole-wave paths of onehot_pick_kernel, the scan and both emit kernels run as shipped; speed and the real memory model are the job
+of the -m gpu run."""
+import os
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EMU = os.path.join(ROOT, "tests", "emu")
+CLANG = "/opt/rocm/lib/llvm/bin/clang++"
+
+
+@pytest.fixture(scope="module")
+def emu_lib():
+    if not os.path.exists(CLANG):
+        pytest.skip("no host clang++ of the ROCm toolchain here")
+    r = subprocess.run(["make", "-C", EMU, "-j8"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    return os.path.join(EMU, "libsprs_hip_emu.so")
+
+
+@pytest.mark.parametrize("order", ["default", "reverse", "rotate"])
+def test_extraction_under_wave_orders(emu_lib, order):
+    env = dict(os.environ, SPRS_HIP_LIBRARY=emu_lib, HIPEMU_WAVE_ORDER=order)
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_extract_gpu.py"), "-x", "-q", "-m", "gpu",
+                        "-p", "no:cacheprovider"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
+    assert " passed" in r.stdout and "failed" not in r.stdout and "skipped" not in r.stdout, r.stdout[-1000:]
