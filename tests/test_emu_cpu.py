@@ -79,6 +79,20 @@ def test_gauss_seidel_sweep_in_the_emulator(emu_lib, order):
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
 
 
+@pytest.mark.parametrize("order", ["default", "reverse", "rotate"])
+def test_gauss_seidel_band_seams_in_the_emulator(emu_lib, order):
+    """the band schedule (eight waves that pass a turn through an LDS word, operands out of the LDS ring, from a wait two turns
+    ahead and from a poll at the use), its check kernel and the sweep's launch options on the systems of
+    tests/test_gauss_seidel_seams_gpu.py with at most 1200 rows (under a minute), with the waves of a workgroup scheduled in three
+    orders: which wave the emulator runs first must not matter.  The emulator runs one workgroup after the other, so every case
+    of several bands has ONE workgroup draw them all; the cases that need more bands than CUs or a torch stream skip themselves."""
+    env = dict(os.environ, SPRS_HIP_LIBRARY=emu_lib, HIPEMU_WAVE_ORDER=order)
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gauss_seidel_seams_gpu.py"), "-x", "-q", "-m", "gpu",
+                        "-p", "no:cacheprovider"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
+    assert " passed" in r.stdout and " failed" not in r.stdout
+
+
 def test_spmm_stream_kernel_in_the_emulator(emu_lib):
     """the entry-stream SpMM kernel (tiles of 256 entries, rows by marks + max-scan, runs per lane group, fix-up of the rows that
     cross tiles) at its seams, and the reference's golden dense products, on the CPU; and the exact-arithmetic seam cases of all
