@@ -927,6 +927,76 @@ int32_t sprs_hip_triplets_to_cs(uint64_t rows, uint64_t cols, uint64_t n, const 
 int32_t sprs_hip_set_option(const char *name, int64_t value);
 int32_t sprs_hip_get_option(const char *name, int64_t *value);
 
+/* ---- single precision: CsMat<f32>, its SpMV and BiCGSTAB -------------------------------------------------------------
+ * The reference is generic over its scalar N and instantiates its solver for f64 and f32 (bicgstab.rs:304-305); its MulAcc
+ * products (mul_acc.rs:17-31) are scalar-generic.  An f32 matrix lives behind a handle type OF ITS OWN: no entry that reads
+ * the `double` values of a sprs_hip_csmat can be handed one.  Built for f32: the container, SpMV in both storages, BiCGSTAB,
+ * and the value casts to and from the f64 handle, through which every other operation of the library stays reachable without
+ * leaving the device.  Index widths: 4 or 8 bytes for indptr and indices, in all four pairs, on the host as on the device;
+ * 2-byte host arrays are NOT accepted for f32 handles (SPRS_HIP_INVALID_ARG). */
+
+typedef struct sprs_hip_csmat_f32 sprs_hip_csmat_f32;
+
+/* The contracts of their f64 namesakes (sprs_hip_csmat_upload ... sprs_hip_csmat_free above) with float values: the same
+ * structure validation, the same SPRS_HIP_BAD_STRUCTURE / SPRS_HIP_DIM_MISMATCH statuses and texts, a possibly non-zero-based
+ * host indptr rebased on the way in, wrapped device buffers 16-byte aligned and not owned. */
+int32_t sprs_hip_csmat_f32_upload(sprs_hip_csmat_f32 **out, int32_t storage, uint64_t rows, uint64_t cols,
+                                  const void *indptr, int32_t iptr_bytes, const void *indices,
+                                  int32_t idx_bytes, const float *data, int32_t validate);
+int32_t sprs_hip_csmat_f32_wrap_device(sprs_hip_csmat_f32 **out, int32_t storage, uint64_t rows,
+                                       uint64_t cols, uint64_t nnz, const void *dev_indptr,
+                                       int32_t iptr_bytes, const void *dev_indices, int32_t idx_bytes,
+                                       const float *dev_data);
+int32_t sprs_hip_csmat_f32_info(const sprs_hip_csmat_f32 *m, uint64_t *rows, uint64_t *cols, uint64_t *nnz,
+                                int32_t *iptr_bytes, int32_t *idx_bytes, int32_t *storage);
+int32_t sprs_hip_csmat_f32_device_ptrs(const sprs_hip_csmat_f32 *m, const void **indptr,
+                                       const void **indices, const float **data);
+int32_t sprs_hip_csmat_f32_download(const sprs_hip_csmat_f32 *m, void *indptr, void *indices, float *data);
+int32_t sprs_hip_csmat_f32_transpose_view(const sprs_hip_csmat_f32 *m, sprs_hip_csmat_f32 **out);
+/* drops the SpMV plan and the cached CSR form of a CSC handle after the wrapped arrays were modified in place */
+int32_t sprs_hip_csmat_f32_refresh(sprs_hip_csmat_f32 *m);
+/* Builds the SpMV plan now: the tile index over the handle's arrays and the carry array of `stream` (a CSC handle: of its CSR
+ * form, made and cached here).  An f32 SpMV has ONE plan (no re-laid-out copies), so preparing changes no bits; it is what
+ * lets an SpMV run on a stream that is being captured into a hipGraph: there the plan and THAT stream's carry array must
+ * exist already (the build allocates and synchronises), else SPRS_HIP_INVALID_ARG. */
+int32_t sprs_hip_csmat_f32_prepare(sprs_hip_csmat_f32 *m, void *stream);
+int32_t sprs_hip_csmat_f32_free(sprs_hip_csmat_f32 *m);
+/* Twin of to_other_storage (csmat.rs:1405-1426) for N = f32: every output row strictly increasing, the values travel with
+ * their index (bit for bit).  Complete at return. */
+int32_t sprs_hip_csmat_f32_to_other_storage(const sprs_hip_csmat_f32 *m, sprs_hip_csmat_f32 **out);
+/* CsMat::map (csmat.rs:1289-1305) with |&v| v as f32 / |&v| v as f64: the structure is copied, the values converted by a plain
+ * cast — narrowing rounds to nearest even, overflow becomes +-inf, NaN stays NaN; widening is exact.  The result carries the
+ * operand's DEVICE index widths (an f64 matrix uploaded from 2-byte host arrays gives 4-byte ones).  Complete at return. */
+int32_t sprs_hip_csmat_f32_from_f64(const sprs_hip_csmat *m, sprs_hip_csmat_f32 **out, void *stream);
+int32_t sprs_hip_csmat_f32_to_f64(const sprs_hip_csmat_f32 *m, sprs_hip_csmat **out, void *stream);
+
+/* Twin of prod::mul_acc_mat_vec_csr (prod.rs:103-127; accumulate != 0) and of `&A * &x` on a zeroed result (accumulate == 0)
+ * for N = f32.  x_dev / y_dev: x_len / y_len floats.  SPRS_HIP_DIM_MISMATCH unless A.cols == x_len && A.rows == y_len, then
+ * SPRS_HIP_STORAGE_MISMATCH unless A is CSR.  Asynchronous on `stream`.  Every product is rounded to f32, then added in f32.
+ * A row (or the part of a row inside one 2048- / 4096-entry tile of the nnz axis) of fewer than 64 entries is summed left to
+ * right from 0.0f — the reference's chain, bit for bit, when the row lies inside one tile; a longer one by a wave (tree); a
+ * row that spans tiles adds its parts in tile order.  Deterministic run to run.  Empty rows: the accumulate form leaves
+ * y[r] untouched, the other writes +0.0f.  Runs on the nnz-tile plan only (option spmv_tile applies; the banded and
+ * XCD-sliced plans of the f64 SpMV do not exist for f32). */
+int32_t sprs_hip_spmv_f32(const sprs_hip_csmat_f32 *a, const float *x_dev, uint64_t x_len,
+                          float *y_dev, uint64_t y_len, int32_t accumulate, void *stream);
+/* the CSC accumulate form (prod.rs:74-99) and the either-storage operator `&A * &x`: a CSC handle multiplies through its CSR
+ * form, converted once and cached in the handle (dropped by _refresh / _free) */
+int32_t sprs_hip_mul_acc_mat_vec_csc_f32(const sprs_hip_csmat_f32 *a, const float *x_dev, uint64_t x_len, float *y_dev,
+                                         uint64_t y_len, void *stream);
+int32_t sprs_hip_csmat_mul_vec_f32(const sprs_hip_csmat_f32 *a, const float *x_dev, uint64_t x_len, float *y_dev,
+                                   uint64_t y_len, void *stream);
+
+/* Twin of BiCGSTAB::<f32>::solve (bicgstab.rs:148-171, instantiated at :305): sprs_hip_bicgstab_f64 with every vector, dot
+ * product and host scalar (alpha, omega, beta, rho, err; sqrt) in f32, in the reference's expression order.  x0_dev, b_dev,
+ * x_dev: n floats.  tol and soft_restart_threshold are f32 values that TRAVEL AS double (every f32 is exactly a double) and
+ * are narrowed by a plain cast on entry.  Serial dots for n <= 2048 — with the SpMV's short-row chain the reference's own
+ * test_bicgstab_f32 system reproduces bit for bit — the fixed two-level tree above.  info->err / info->rho hold the f32
+ * values widened exactly. */
+int32_t sprs_hip_bicgstab_f32(sprs_hip_csmat_f32 *a, const float *x0_dev, const float *b_dev, uint64_t n,
+                              double tol, uint64_t max_iter, double soft_restart_threshold, float *x_dev,
+                              sprs_hip_bicgstab_info *info, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1106,4 +1106,146 @@ inline uint64_t pool_trim() {
     return freed;
 }
 
+// ---- single precision: CsMatI<f32, I, Iptr>, `&A * &x` and BiCGSTAB::<f32> ------------------------------------------------
+// Distinct classes over a distinct handle type: an f64 entry cannot be handed f32 buffers, and the compiler rejects a product
+// of mixed precision.  Every other operation is reached through to_f64() / to_f32(), on the device.
+class DeviceVecF32 {
+public:
+    explicit DeviceVecF32(uint64_t n) : n_(n) {
+        check(sprs_hip_malloc(&p_, n * 4));
+        check(sprs_hip_memset(p_, 0, n * 4, nullptr));
+    }
+    explicit DeviceVecF32(const std::vector<float> &v) : n_(v.size()) {
+        check(sprs_hip_malloc(&p_, n_ * 4));
+        check(sprs_hip_memcpy_h2d(p_, v.data(), n_ * 4));
+    }
+    DeviceVecF32(DeviceVecF32 &&o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr; }
+    DeviceVecF32(const DeviceVecF32 &) = delete;
+    DeviceVecF32 &operator=(const DeviceVecF32 &) = delete;
+    ~DeviceVecF32() {
+        if (p_) sprs_hip_free(p_);
+    }
+    uint64_t dim() const { return n_; }
+    float *ptr() { return static_cast<float *>(p_); }
+    const float *ptr() const { return static_cast<const float *>(p_); }
+    std::vector<float> to_host() const {
+        std::vector<float> out(n_);
+        check(sprs_hip_synchronize(nullptr));
+        check(sprs_hip_memcpy_d2h(out.data(), p_, n_ * 4));
+        return out;
+    }
+
+private:
+    void *p_ = nullptr;
+    uint64_t n_ = 0;
+};
+
+class DeviceCsMatF32 {
+public:
+    // CsMat::new / new_csc (validate = true) or new_trusted (validate = false); I and Iptr of 4 or 8 bytes
+    template <typename I, typename Iptr>
+    DeviceCsMatF32(int32_t storage, uint64_t rows, uint64_t cols, const std::vector<Iptr> &indptr, const std::vector<I> &indices,
+                   const std::vector<float> &data, bool validate = true) {
+        static_assert(std::is_integral<I>::value && std::is_integral<Iptr>::value, "SpIndex types");
+        static_assert(sizeof(I) == 4 || sizeof(I) == 8, "I must be 4 or 8 bytes");
+        static_assert(sizeof(Iptr) == 4 || sizeof(Iptr) == 8, "Iptr must be 4 or 8 bytes");
+        check(sprs_hip_csmat_f32_upload(&h_, storage, rows, cols, indptr.data(), (int32_t)sizeof(Iptr), indices.data(), (int32_t)sizeof(I),
+                                        data.data(), validate ? 1 : 0));
+    }
+    explicit DeviceCsMatF32(sprs_hip_csmat_f32 *h) : h_(h) {}
+    // CsMat::map(|&v| v as f32) (csmat.rs:1289-1305)
+    explicit DeviceCsMatF32(const DeviceCsMat &m, void *stream = nullptr) { check(sprs_hip_csmat_f32_from_f64(m.handle(), &h_, stream)); }
+    DeviceCsMatF32(DeviceCsMatF32 &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    DeviceCsMatF32(const DeviceCsMatF32 &) = delete;
+    DeviceCsMatF32 &operator=(const DeviceCsMatF32 &) = delete;
+    ~DeviceCsMatF32() {
+        if (h_) sprs_hip_csmat_f32_free(h_);
+    }
+    uint64_t rows() const { return info().rows; }
+    uint64_t cols() const { return info().cols; }
+    uint64_t nnz() const { return info().nnz; }
+    bool is_csr() const { return info().storage == SPRS_HIP_CSR; }
+    const sprs_hip_csmat_f32 *handle() const { return h_; }
+    void prepare(void *stream = nullptr) { check(sprs_hip_csmat_f32_prepare(h_, stream)); }
+    void refresh() { check(sprs_hip_csmat_f32_refresh(h_)); }
+    DeviceCsMatF32 transpose_view() const {          // shares this matrix's buffers: must not outlive it
+        sprs_hip_csmat_f32 *t = nullptr;
+        check(sprs_hip_csmat_f32_transpose_view(h_, &t));
+        return DeviceCsMatF32(t);
+    }
+    DeviceCsMatF32 to_other_storage() const {        // csmat.rs:1405-1426
+        sprs_hip_csmat_f32 *t = nullptr;
+        check(sprs_hip_csmat_f32_to_other_storage(h_, &t));
+        return DeviceCsMatF32(t);
+    }
+    DeviceCsMat to_f64(void *stream = nullptr) const {   // CsMat::map(|&v| v as f64): exact
+        sprs_hip_csmat *t = nullptr;
+        check(sprs_hip_csmat_f32_to_f64(h_, &t, stream));
+        return DeviceCsMat(t);
+    }
+    // into_raw_storage for 8-byte handles
+    void to_host(std::vector<uint64_t> &indptr, std::vector<uint64_t> &indices, std::vector<float> &data) const {
+        const Info i = info();
+        if (i.iptr_bytes != 8 || i.idx_bytes != 8) throw Error(SPRS_HIP_INVALID_ARG, "to_host: 64-bit handles only");
+        indptr.resize((i.storage == SPRS_HIP_CSR ? i.rows : i.cols) + 1);
+        indices.resize(i.nnz);
+        data.resize(i.nnz);
+        check(sprs_hip_csmat_f32_download(h_, indptr.data(), indices.data(), data.data()));
+    }
+
+private:
+    struct Info {
+        uint64_t rows, cols, nnz;
+        int32_t iptr_bytes, idx_bytes, storage;
+    };
+    Info info() const {
+        Info i{};
+        check(sprs_hip_csmat_f32_info(h_, &i.rows, &i.cols, &i.nnz, &i.iptr_bytes, &i.idx_bytes, &i.storage));
+        return i;
+    }
+    sprs_hip_csmat_f32 *h_ = nullptr;
+};
+
+namespace prod {
+inline void mul_acc_mat_vec_csr(const DeviceCsMatF32 &mat, const DeviceVecF32 &in_vec, DeviceVecF32 &res_vec, void *stream = nullptr) {
+    check(sprs_hip_spmv_f32(mat.handle(), in_vec.ptr(), in_vec.dim(), res_vec.ptr(), res_vec.dim(), 1, stream));
+}
+inline void mul_acc_mat_vec_csc(const DeviceCsMatF32 &mat, const DeviceVecF32 &in_vec, DeviceVecF32 &res_vec, void *stream = nullptr) {
+    check(sprs_hip_mul_acc_mat_vec_csc_f32(mat.handle(), in_vec.ptr(), in_vec.dim(), res_vec.ptr(), res_vec.dim(), stream));
+}
+}  // namespace prod
+
+inline DeviceVecF32 operator*(const DeviceCsMatF32 &a, const DeviceVecF32 &x) {      // CSR or CSC
+    DeviceVecF32 y(a.rows());
+    check(sprs_hip_csmat_mul_vec_f32(a.handle(), x.ptr(), x.dim(), y.ptr(), y.dim(), nullptr));
+    return y;
+}
+
+namespace linalg {
+// BiCGSTAB::<f32>::solve (bicgstab.rs:148-171, :305)
+class BiCGSTABF32 {
+public:
+    static BiCGSTABF32 solve(const DeviceCsMatF32 &a, const DeviceVecF32 &x0, const DeviceVecF32 &b, float tol, uint64_t max_iter,
+                             float soft_restart_threshold = 0.1f) {
+        if (x0.dim() != b.dim()) throw Error(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+        BiCGSTABF32 s(x0.dim());
+        check(sprs_hip_bicgstab_f32(const_cast<sprs_hip_csmat_f32 *>(a.handle()), x0.ptr(), b.ptr(), x0.dim(), (double)tol, max_iter,
+                                    (double)soft_restart_threshold, s.x_.ptr(), &s.info_, nullptr));
+        return s;
+    }
+    bool converged() const { return info_.converged != 0; }
+    uint64_t iteration_count() const { return info_.iteration_count; }
+    uint64_t soft_restart_count() const { return info_.soft_restart_count; }
+    uint64_t hard_restart_count() const { return info_.hard_restart_count; }
+    float err() const { return (float)info_.err; }
+    float rho() const { return (float)info_.rho; }
+    const DeviceVecF32 &x() const { return x_; }
+
+private:
+    explicit BiCGSTABF32(uint64_t n) : x_(n) {}
+    DeviceVecF32 x_;
+    sprs_hip_bicgstab_info info_{};
+};
+}  // namespace linalg
+
 }  // namespace sprs_hip

@@ -47,6 +47,12 @@ pub struct sprs_hip_csmat {
     _private: [u8; 0],
 }
 
+/// `CsMat<f32>`: a handle type of its own, so that no `f64` entry can be handed `f32` buffers.
+#[repr(C)]
+pub struct sprs_hip_csmat_f32 {
+    _private: [u8; 0],
+}
+
 #[repr(C)]
 pub struct sprs_hip_csvec {
     _private: [u8; 0],
@@ -365,6 +371,43 @@ extern "C" {
     pub fn sprs_hip_triplets_to_cs(
         rows: u64, cols: u64, n: u64, row_inds_dev: *const c_void, col_inds_dev: *const c_void, in_idx_bytes: i32,
         data_dev: *const f64, storage: i32, out_idx_bytes: i32, out_iptr_bytes: i32, out: *mut *mut sprs_hip_csmat,
+    ) -> i32;
+    // single precision: the f32 container, SpMV in both storages, BiCGSTAB, the casts to and from the f64 handle
+    pub fn sprs_hip_csmat_f32_upload(
+        out: *mut *mut sprs_hip_csmat_f32, storage: i32, rows: u64, cols: u64, indptr: *const c_void, iptr_bytes: i32,
+        indices: *const c_void, idx_bytes: i32, data: *const f32, validate: i32,
+    ) -> i32;
+    pub fn sprs_hip_csmat_f32_wrap_device(
+        out: *mut *mut sprs_hip_csmat_f32, storage: i32, rows: u64, cols: u64, nnz: u64, dev_indptr: *const c_void, iptr_bytes: i32,
+        dev_indices: *const c_void, idx_bytes: i32, dev_data: *const f32,
+    ) -> i32;
+    pub fn sprs_hip_csmat_f32_info(
+        m: *const sprs_hip_csmat_f32, rows: *mut u64, cols: *mut u64, nnz: *mut u64, iptr_bytes: *mut i32, idx_bytes: *mut i32,
+        storage: *mut i32,
+    ) -> i32;
+    pub fn sprs_hip_csmat_f32_device_ptrs(
+        m: *const sprs_hip_csmat_f32, indptr: *mut *const c_void, indices: *mut *const c_void, data: *mut *const f32,
+    ) -> i32;
+    pub fn sprs_hip_csmat_f32_download(m: *const sprs_hip_csmat_f32, indptr: *mut c_void, indices: *mut c_void, data: *mut f32) -> i32;
+    pub fn sprs_hip_csmat_f32_transpose_view(m: *const sprs_hip_csmat_f32, out: *mut *mut sprs_hip_csmat_f32) -> i32;
+    pub fn sprs_hip_csmat_f32_refresh(m: *mut sprs_hip_csmat_f32) -> i32;
+    pub fn sprs_hip_csmat_f32_prepare(m: *mut sprs_hip_csmat_f32, stream: *mut c_void) -> i32;
+    pub fn sprs_hip_csmat_f32_free(m: *mut sprs_hip_csmat_f32) -> i32;
+    pub fn sprs_hip_csmat_f32_to_other_storage(m: *const sprs_hip_csmat_f32, out: *mut *mut sprs_hip_csmat_f32) -> i32;
+    pub fn sprs_hip_csmat_f32_from_f64(m: *const sprs_hip_csmat, out: *mut *mut sprs_hip_csmat_f32, stream: *mut c_void) -> i32;
+    pub fn sprs_hip_csmat_f32_to_f64(m: *const sprs_hip_csmat_f32, out: *mut *mut sprs_hip_csmat, stream: *mut c_void) -> i32;
+    pub fn sprs_hip_spmv_f32(
+        a: *const sprs_hip_csmat_f32, x_dev: *const f32, x_len: u64, y_dev: *mut f32, y_len: u64, accumulate: i32, stream: *mut c_void,
+    ) -> i32;
+    pub fn sprs_hip_mul_acc_mat_vec_csc_f32(
+        a: *const sprs_hip_csmat_f32, x_dev: *const f32, x_len: u64, y_dev: *mut f32, y_len: u64, stream: *mut c_void,
+    ) -> i32;
+    pub fn sprs_hip_csmat_mul_vec_f32(
+        a: *const sprs_hip_csmat_f32, x_dev: *const f32, x_len: u64, y_dev: *mut f32, y_len: u64, stream: *mut c_void,
+    ) -> i32;
+    pub fn sprs_hip_bicgstab_f32(
+        a: *mut sprs_hip_csmat_f32, x0_dev: *const f32, b_dev: *const f32, n: u64, tol: f64, max_iter: u64, soft_restart_threshold: f64,
+        x_dev: *mut f32, info: *mut sprs_hip_bicgstab_info, stream: *mut c_void,
     ) -> i32;
     pub fn sprs_hip_set_option(name: *const c_char, value: i64) -> i32;
     pub fn sprs_hip_get_option(name: *const c_char, value: *mut i64) -> i32;

@@ -1544,3 +1544,163 @@ pub mod construct {
         DeviceCsMat { h }
     }
 }
+
+/// Single precision: `CsMat<f32>` on the device, `&A * &x` and `BiCGSTAB::<f32>` — what the reference instantiates for f32 on
+/// the product path (bicgstab.rs:304-305; MulAcc, mul_acc.rs:17-31).  Types of their own over a handle type of its own: the
+/// compiler rejects a product of mixed precision.  Every other operation is reached through `to_f64` / `from_f64`, on the device.
+pub mod single {
+    use super::*;
+
+    /// A dense f32 vector in HBM.
+    pub struct DeviceVecF32 {
+        ptr: *mut f32,
+        len: usize,
+    }
+
+    impl DeviceVecF32 {
+        pub fn zeros(len: usize) -> Self {
+            let mut p: *mut c_void = std::ptr::null_mut();
+            unsafe {
+                check(sys::sprs_hip_malloc(&mut p, (len * 4) as u64));
+                check(sys::sprs_hip_memset(p, 0, (len * 4) as u64, std::ptr::null_mut()));
+            }
+            Self { ptr: p as *mut f32, len }
+        }
+        pub fn from_slice(x: &[f32]) -> Self {
+            let v = Self::zeros(x.len());
+            unsafe { check(sys::sprs_hip_memcpy_h2d(v.ptr as *mut c_void, x.as_ptr() as *const c_void, (x.len() * 4) as u64)) };
+            v
+        }
+        pub fn to_vec(&self) -> Vec<f32> {
+            let mut out = vec![0.0f32; self.len];
+            unsafe {
+                check(sys::sprs_hip_synchronize(std::ptr::null_mut()));
+                check(sys::sprs_hip_memcpy_d2h(out.as_mut_ptr() as *mut c_void, self.ptr as *const c_void, (self.len * 4) as u64));
+            }
+            out
+        }
+        pub fn dim(&self) -> usize {
+            self.len
+        }
+    }
+
+    impl Drop for DeviceVecF32 {
+        fn drop(&mut self) {
+            unsafe { sys::sprs_hip_free(self.ptr as *mut c_void) };
+        }
+    }
+
+    /// Device twin of `CsMatI<f32, I, Iptr>` with 4- or 8-byte index types.
+    pub struct DeviceCsMatF32 {
+        h: *mut sys::sprs_hip_csmat_f32,
+    }
+
+    unsafe impl Send for DeviceCsMatF32 {}
+
+    impl DeviceCsMatF32 {
+        /// Upload of host arrays (`CsMat::new` / `new_csc` when `validate`); `I` and `Iptr` must be 4 or 8 bytes wide.
+        pub fn from_raw<I: Copy, Iptr: Copy>(csr: bool, rows: usize, cols: usize, indptr: &[Iptr], indices: &[I], data: &[f32],
+                                             validate: bool) -> Self {
+            let mut h: *mut sys::sprs_hip_csmat_f32 = std::ptr::null_mut();
+            unsafe {
+                check(sys::sprs_hip_csmat_f32_upload(&mut h, if csr { sys::SPRS_HIP_CSR } else { sys::SPRS_HIP_CSC }, rows as u64,
+                                                     cols as u64, indptr.as_ptr() as *const c_void, std::mem::size_of::<Iptr>() as i32,
+                                                     indices.as_ptr() as *const c_void, std::mem::size_of::<I>() as i32, data.as_ptr(),
+                                                     validate as i32));
+            }
+            Self { h }
+        }
+        /// `CsMat::map(|&v| v as f32)` (csmat.rs:1289-1305)
+        pub fn from_f64(m: &DeviceCsMat) -> Self {
+            let mut h: *mut sys::sprs_hip_csmat_f32 = std::ptr::null_mut();
+            unsafe { check(sys::sprs_hip_csmat_f32_from_f64(m.h, &mut h, std::ptr::null_mut())) };
+            Self { h }
+        }
+        /// `CsMat::map(|&v| v as f64)`: exact
+        pub fn to_f64(&self) -> DeviceCsMat {
+            let mut h: *mut sys::sprs_hip_csmat = std::ptr::null_mut();
+            unsafe { check(sys::sprs_hip_csmat_f32_to_f64(self.h, &mut h, std::ptr::null_mut())) };
+            DeviceCsMat { h }
+        }
+        fn info(&self) -> (u64, u64, u64, i32, i32, i32) {
+            let (mut r, mut c, mut n, mut pb, mut ib, mut st) = (0u64, 0u64, 0u64, 0i32, 0i32, 0i32);
+            unsafe { check(sys::sprs_hip_csmat_f32_info(self.h, &mut r, &mut c, &mut n, &mut pb, &mut ib, &mut st)) };
+            (r, c, n, pb, ib, st)
+        }
+        pub fn rows(&self) -> usize { self.info().0 as usize }
+        pub fn cols(&self) -> usize { self.info().1 as usize }
+        pub fn nnz(&self) -> usize { self.info().2 as usize }
+        pub fn is_csr(&self) -> bool { self.info().5 == sys::SPRS_HIP_CSR }
+        /// csmat.rs:1405-1426
+        pub fn to_other_storage(&self) -> Self {
+            let mut h: *mut sys::sprs_hip_csmat_f32 = std::ptr::null_mut();
+            unsafe { check(sys::sprs_hip_csmat_f32_to_other_storage(self.h, &mut h)) };
+            Self { h }
+        }
+        pub fn prepare(&mut self) {
+            unsafe { check(sys::sprs_hip_csmat_f32_prepare(self.h, std::ptr::null_mut())) };
+        }
+        pub fn refresh(&mut self) {
+            unsafe { check(sys::sprs_hip_csmat_f32_refresh(self.h)) };
+        }
+        /// `&A * &x` for either storage
+        pub fn mul_vec(&self, x: &DeviceVecF32) -> DeviceVecF32 {
+            let y = DeviceVecF32::zeros(self.rows());
+            unsafe { check(sys::sprs_hip_csmat_mul_vec_f32(self.h, x.ptr, x.len as u64, y.ptr, y.len as u64, std::ptr::null_mut())) };
+            y
+        }
+        /// values to the host (8-byte handles: the arrays as u64)
+        pub fn data_to_vec(&self) -> Vec<f32> {
+            let mut out = vec![0.0f32; self.nnz()];
+            unsafe { check(sys::sprs_hip_csmat_f32_download(self.h, std::ptr::null_mut(), std::ptr::null_mut(), out.as_mut_ptr())) };
+            out
+        }
+    }
+
+    impl Drop for DeviceCsMatF32 {
+        fn drop(&mut self) {
+            unsafe { sys::sprs_hip_csmat_f32_free(self.h) };
+        }
+    }
+
+    /// prod::mul_acc_mat_vec_csr (prod.rs:103-127) for N = f32
+    pub fn mul_acc_mat_vec_csr(mat: &DeviceCsMatF32, in_vec: &DeviceVecF32, res_vec: &mut DeviceVecF32) {
+        unsafe {
+            check(sys::sprs_hip_spmv_f32(mat.h, in_vec.ptr, in_vec.len as u64, res_vec.ptr, res_vec.len as u64, 1, std::ptr::null_mut()))
+        };
+    }
+
+    /// prod::mul_acc_mat_vec_csc (prod.rs:74-99) for N = f32
+    pub fn mul_acc_mat_vec_csc(mat: &DeviceCsMatF32, in_vec: &DeviceVecF32, res_vec: &mut DeviceVecF32) {
+        unsafe {
+            check(sys::sprs_hip_mul_acc_mat_vec_csc_f32(mat.h, in_vec.ptr, in_vec.len as u64, res_vec.ptr, res_vec.len as u64,
+                                                        std::ptr::null_mut()))
+        };
+    }
+
+    /// `BiCGSTAB::<f32>::solve` (bicgstab.rs:148-171): `Ok(solver)` / `Err(solver)` like the reference.
+    pub struct BiCGSTAB {
+        x: DeviceVecF32,
+        info: sys::sprs_hip_bicgstab_info,
+    }
+    impl BiCGSTAB {
+        pub fn solve(a: &DeviceCsMatF32, x0: &DeviceVecF32, b: &DeviceVecF32, tol: f32, max_iter: usize)
+            -> Result<Box<BiCGSTAB>, Box<BiCGSTAB>> {
+            assert_eq!(x0.len, b.len, "Dimension mismatch");
+            let x = DeviceVecF32::zeros(x0.len);
+            let mut info = sys::sprs_hip_bicgstab_info::default();
+            unsafe {
+                check(sys::sprs_hip_bicgstab_f32(a.h, x0.ptr, b.ptr, x0.len as u64, tol as f64, max_iter as u64, 0.1f32 as f64, x.ptr,
+                                                 &mut info, std::ptr::null_mut()));
+            }
+            let s = Box::new(BiCGSTAB { x, info });
+            if s.info.converged != 0 { Ok(s) } else { Err(s) }
+        }
+        pub fn iteration_count(&self) -> usize { self.info.iteration_count as usize }
+        pub fn soft_restart_count(&self) -> usize { self.info.soft_restart_count as usize }
+        pub fn hard_restart_count(&self) -> usize { self.info.hard_restart_count as usize }
+        pub fn err(&self) -> f32 { self.info.err as f32 }
+        pub fn rho(&self) -> f32 { self.info.rho as f32 }
+        pub fn x(&self) -> &DeviceVecF32 { &self.x }
+    }
+}

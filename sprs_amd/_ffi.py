@@ -168,6 +168,22 @@ SIGNATURES = {
     "sprs_hip_csmat_to_dense_f64": (i32, [vp, vp, u64, u64, i32, u64, vp]),
     "sprs_hip_csmat_binop_dense_f64": (i32, [vp, vp, u64, u64, i32, u64, i32, C.c_double, C.c_double, vp, u64, vp]),
     "sprs_hip_csmat_add_dense_f64": (i32, [vp, vp, u64, u64, i32, u64, vp, vp]),
+    "sprs_hip_csmat_f32_upload": (i32, [P(vp), i32, u64, u64, vp, i32, vp, i32, vp, i32]),
+    "sprs_hip_csmat_f32_wrap_device": (i32, [P(vp), i32, u64, u64, u64, vp, i32, vp, i32, vp]),
+    "sprs_hip_csmat_f32_info": (i32, [vp, P(u64), P(u64), P(u64), P(i32), P(i32), P(i32)]),
+    "sprs_hip_csmat_f32_device_ptrs": (i32, [vp, P(vp), P(vp), P(vp)]),
+    "sprs_hip_csmat_f32_download": (i32, [vp, vp, vp, vp]),
+    "sprs_hip_csmat_f32_transpose_view": (i32, [vp, P(vp)]),
+    "sprs_hip_csmat_f32_refresh": (i32, [vp]),
+    "sprs_hip_csmat_f32_prepare": (i32, [vp, vp]),
+    "sprs_hip_csmat_f32_free": (i32, [vp]),
+    "sprs_hip_csmat_f32_to_other_storage": (i32, [vp, P(vp)]),
+    "sprs_hip_csmat_f32_from_f64": (i32, [vp, P(vp), vp]),
+    "sprs_hip_csmat_f32_to_f64": (i32, [vp, P(vp), vp]),
+    "sprs_hip_spmv_f32": (i32, [vp, vp, u64, vp, u64, i32, vp]),
+    "sprs_hip_mul_acc_mat_vec_csc_f32": (i32, [vp, vp, u64, vp, u64, vp]),
+    "sprs_hip_csmat_mul_vec_f32": (i32, [vp, vp, u64, vp, u64, vp]),
+    "sprs_hip_bicgstab_f32": (i32, [vp, vp, vp, u64, C.c_double, u64, C.c_double, vp, vp, vp]),
     "sprs_hip_set_option": (i32, [C.c_char_p, i64]),
     "sprs_hip_get_option": (i32, [C.c_char_p, P(i64)]),
 }

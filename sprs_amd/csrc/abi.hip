@@ -2137,6 +2137,258 @@ int32_t sprs_hip_csmat_add_dense_f64(const sprs_hip_csmat *lhs, const double *rh
 
 }  // extern "C"
 
+// ---- single precision: the f32 container, its SpMV entries and BiCGSTAB (kernels: spmv_f32.hpp, bicgstab.hip) ---------------
+// CsMat::new / new_csc on host arrays for N = f32: csmat_upload above without the 2-byte widths
+static int32_t csmat_f32_upload(OwnedCsmatF32 &out, int32_t storage, uint64_t rows, uint64_t cols, const void *indptr, int32_t iptr_bytes,
+                                const void *indices, int32_t idx_bytes, const float *data, int32_t validate) {
+    if (storage != SPRS_HIP_CSR && storage != SPRS_HIP_CSC) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "bad storage tag %d", storage);
+    if (!widths_ok(iptr_bytes, idx_bytes))
+        SPRS_FAIL(SPRS_HIP_INVALID_ARG, "index widths of an f32 matrix must be 4 or 8 bytes (2-byte host arrays are not supported for f32 handles)");
+    const uint64_t outer = storage == SPRS_HIP_CSR ? rows : cols;
+    const uint64_t inner = storage == SPRS_HIP_CSR ? cols : rows;
+    const uint64_t first = host_index_at(indptr, iptr_bytes, 0), last = host_index_at(indptr, iptr_bytes, outer);
+    if (last < first) SPRS_FAIL(SPRS_HIP_BAD_STRUCTURE, "Unsorted indptr");
+    const uint64_t nnz = last - first;
+    if (nnz && (!indices || !data)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL indices/data with nnz > 0");
+    if (validate) {
+        SPRS_TRY(dispatch_widths(idx_bytes, iptr_bytes, [&](auto i, auto p) {
+            return check_structure(inner, outer, (const typename decltype(p)::type *)indptr, (const typename decltype(i)::type *)indices);
+        }));
+    }
+    OwnedCsmatF32 m;
+    SPRS_TRY(make_csmat_f32(m, storage, rows, cols, nnz, iptr_bytes, idx_bytes));
+    hipError_t e = hipSuccess;
+    if (first == 0) {
+        e = copy_to_device(m->indptr, indptr, (outer + 1) * (uint64_t)iptr_bytes, nullptr);
+    } else {
+        // to_proper (sprs/src/sparse/indptr.rs:206-214): rebase on the way in
+        std::vector<uint8_t> tmp((outer + 1) * (size_t)iptr_bytes);
+        for (uint64_t i = 0; i <= outer; ++i) {
+            const uint64_t v = host_index_at(indptr, iptr_bytes, i) - first;
+            if (iptr_bytes == 8) ((uint64_t *)tmp.data())[i] = v;
+            else ((uint32_t *)tmp.data())[i] = (uint32_t)v;
+        }
+        e = copy_to_device(m->indptr, tmp.data(), tmp.size(), nullptr);
+    }
+    if (e == hipSuccess && nnz) e = copy_to_device(m->indices, indices, nnz * (uint64_t)idx_bytes, nullptr);
+    if (e == hipSuccess && nnz) e = copy_to_device(m->data, data, nnz * sizeof(float), nullptr);
+    if (e != hipSuccess) return fail_hip(e, "csmat_f32_upload");
+    out = std::move(m);
+    return SPRS_HIP_OK;
+}
+
+// the CSR form of an f32 handle: itself, or its to_other_storage() copy, made once and kept in the handle (as csr_form above)
+static int32_t csr_form_f32(const sprs_hip_csmat_f32 *m, sprs_hip_csmat_f32 **out) {
+    auto *mm = const_cast<sprs_hip_csmat_f32 *>(m);
+    if (m->storage == SPRS_HIP_CSR) {
+        *out = mm;
+        return SPRS_HIP_OK;
+    }
+    std::lock_guard<std::recursive_mutex> lock(mm->mu);
+    if (!mm->as_other) {
+        OwnedCsmatF32 other;
+        SPRS_TRY(csmat_f32_to_other_storage(m, other));
+        mm->as_other = other.release();
+        mm->as_other->prepared = mm->prepared;
+    }
+    *out = mm->as_other;
+    return SPRS_HIP_OK;
+}
+
+static int32_t vec_args_ok_f32(const float *x_dev, uint64_t x_len, float *y_dev, uint64_t y_len) {
+    if ((x_len && !x_dev) || (y_len && !y_dev)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL vector");
+    if (x_len && y_len && x_dev < y_dev + y_len && y_dev < x_dev + x_len)
+        SPRS_FAIL(SPRS_HIP_INVALID_ARG, "the result vector overlaps the input vector");
+    return SPRS_HIP_OK;
+}
+
+extern "C" {
+
+int32_t sprs_hip_csmat_f32_upload(sprs_hip_csmat_f32 **out, int32_t storage, uint64_t rows, uint64_t cols, const void *indptr,
+                                  int32_t iptr_bytes, const void *indices, int32_t idx_bytes, const float *data, int32_t validate) {
+    clear_error();
+    if (!out || !indptr) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    OwnedCsmatF32 m;
+    SPRS_TRY(csmat_f32_upload(m, storage, rows, cols, indptr, iptr_bytes, indices, idx_bytes, data, validate));
+    *out = m.release();
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_csmat_f32_wrap_device(sprs_hip_csmat_f32 **out, int32_t storage, uint64_t rows, uint64_t cols, uint64_t nnz,
+                                       const void *dev_indptr, int32_t iptr_bytes, const void *dev_indices, int32_t idx_bytes,
+                                       const float *dev_data) {
+    clear_error();
+    if (!out || !dev_indptr) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    if (storage != SPRS_HIP_CSR && storage != SPRS_HIP_CSC) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "bad storage tag %d", storage);
+    if (!widths_ok(iptr_bytes, idx_bytes)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "index widths must be 4 or 8 bytes");
+    if (nnz && (!dev_indices || !dev_data)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL indices/data with nnz > 0");
+    if (((uintptr_t)dev_indptr | (uintptr_t)dev_indices | (uintptr_t)dev_data) & 15)
+        SPRS_FAIL(SPRS_HIP_INVALID_ARG, "device buffers must be 16-byte aligned");
+    int device = 0;
+    const hipError_t e = hipGetDevice(&device);
+    if (e != hipSuccess) return fail_hip(e, "hipGetDevice");
+    *out = view_csmat_f32(storage, rows, cols, nnz, dev_indptr, iptr_bytes, dev_indices, idx_bytes, dev_data, device);
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_csmat_f32_info(const sprs_hip_csmat_f32 *m, uint64_t *rows, uint64_t *cols, uint64_t *nnz, int32_t *iptr_bytes,
+                                int32_t *idx_bytes, int32_t *storage) {
+    clear_error();
+    if (!m) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if (rows) *rows = m->rows;
+    if (cols) *cols = m->cols;
+    if (nnz) *nnz = m->nnz;
+    if (iptr_bytes) *iptr_bytes = m->iptr_bytes;
+    if (idx_bytes) *idx_bytes = m->idx_bytes;
+    if (storage) *storage = m->storage;
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_csmat_f32_device_ptrs(const sprs_hip_csmat_f32 *m, const void **indptr, const void **indices, const float **data) {
+    clear_error();
+    if (!m) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if (indptr) *indptr = m->indptr;
+    if (indices) *indices = m->indices;
+    if (data) *data = m->data;
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_csmat_f32_download(const sprs_hip_csmat_f32 *m, void *indptr, void *indices, float *data) {
+    clear_error();
+    if (!m) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if (indptr) SPRS_TRY_HIP(copy_to_host(indptr, m->indptr, (m->outer() + 1) * (uint64_t)m->iptr_bytes, nullptr));
+    if (indices && m->nnz) SPRS_TRY_HIP(copy_to_host(indices, m->indices, m->nnz * (uint64_t)m->idx_bytes, nullptr));
+    if (data && m->nnz) SPRS_TRY_HIP(copy_to_host(data, m->data, m->nnz * sizeof(float), nullptr));
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_csmat_f32_transpose_view(const sprs_hip_csmat_f32 *m, sprs_hip_csmat_f32 **out) {
+    clear_error();
+    if (!m || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = view_csmat_f32(m, true);
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_csmat_f32_refresh(sprs_hip_csmat_f32 *m) {
+    clear_error();
+    if (!m) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    SPRS_TRY_HIP(hipDeviceSynchronize());     // nothing in flight may still read the plan or the CSR copy
+    std::lock_guard<std::recursive_mutex> lock(m->mu);
+    invalidate_caches(m);
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_csmat_f32_prepare(sprs_hip_csmat_f32 *m, void *stream) {
+    clear_error();
+    if (!m) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    {
+        std::lock_guard<std::recursive_mutex> lock(m->mu);
+        m->prepared = true;
+    }
+    sprs_hip_csmat_f32 *csr = nullptr;
+    SPRS_TRY(csr_form_f32(m, &csr));
+    return spmv_f32_prepare(csr, (hipStream_t)stream);
+}
+
+int32_t sprs_hip_csmat_f32_free(sprs_hip_csmat_f32 *m) {
+    clear_error();
+    delete m;
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_csmat_f32_to_other_storage(const sprs_hip_csmat_f32 *m, sprs_hip_csmat_f32 **out) {
+    clear_error();
+    if (!m || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    // the index-type check of the reference (csmat.rs:1794-1797)
+    if (m->rows > width_max(m->idx_bytes))
+        SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "Index type is not large enough to hold the number of rows requested (required %llu)",
+                  (unsigned long long)m->rows);
+    OwnedCsmatF32 res;
+    SPRS_TRY(csmat_f32_to_other_storage(m, res));
+    *out = res.release();
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_csmat_f32_from_f64(const sprs_hip_csmat *m, sprs_hip_csmat_f32 **out, void *stream) {
+    clear_error();
+    if (!m || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    OwnedCsmatF32 res;
+    SPRS_TRY(csmat_f32_from_f64(m, res, (hipStream_t)stream));
+    SPRS_TRY_HIP(hipStreamSynchronize((hipStream_t)stream));
+    *out = res.release();
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_csmat_f32_to_f64(const sprs_hip_csmat_f32 *m, sprs_hip_csmat **out, void *stream) {
+    clear_error();
+    if (!m || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    OwnedCsmat res;
+    SPRS_TRY(csmat_f32_to_f64(m, res, (hipStream_t)stream));
+    SPRS_TRY_HIP(hipStreamSynchronize((hipStream_t)stream));
+    *out = res.release();
+    return SPRS_HIP_OK;
+}
+
+int32_t sprs_hip_spmv_f32(const sprs_hip_csmat_f32 *a, const float *x_dev, uint64_t x_len, float *y_dev, uint64_t y_len,
+                          int32_t accumulate, void *stream) {
+    clear_error();
+    if (!a) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    // prod.rs:114-118: dimension check first, then storage
+    if (a->cols != x_len || a->rows != y_len) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    if (a->storage != SPRS_HIP_CSR) SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "Storage mismatch");
+    SPRS_TRY(vec_args_ok_f32(x_dev, x_len, y_dev, y_len));
+    return spmv_f32(const_cast<sprs_hip_csmat_f32 *>(a), x_dev, y_dev, accumulate != 0, (hipStream_t)stream);
+}
+
+int32_t sprs_hip_mul_acc_mat_vec_csc_f32(const sprs_hip_csmat_f32 *a, const float *x_dev, uint64_t x_len, float *y_dev, uint64_t y_len,
+                                         void *stream) {
+    clear_error();
+    if (!a) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    // prod.rs:88-92: dimensions first, then storage
+    if (a->cols != x_len || a->rows != y_len) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    if (a->storage != SPRS_HIP_CSC) SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "Storage mismatch");
+    SPRS_TRY(vec_args_ok_f32(x_dev, x_len, y_dev, y_len));
+    sprs_hip_csmat_f32 *csr = nullptr;
+    SPRS_TRY(csr_form_f32(a, &csr));
+    return spmv_f32(csr, x_dev, y_dev, true, (hipStream_t)stream);
+}
+
+int32_t sprs_hip_csmat_mul_vec_f32(const sprs_hip_csmat_f32 *a, const float *x_dev, uint64_t x_len, float *y_dev, uint64_t y_len,
+                                   void *stream) {
+    clear_error();
+    if (!a) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if (a->cols != x_len || a->rows != y_len) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    SPRS_TRY(vec_args_ok_f32(x_dev, x_len, y_dev, y_len));
+    sprs_hip_csmat_f32 *csr = nullptr;
+    SPRS_TRY(csr_form_f32(a, &csr));
+    return spmv_f32(csr, x_dev, y_dev, false, (hipStream_t)stream);
+}
+
+int32_t sprs_hip_bicgstab_f32(sprs_hip_csmat_f32 *a, const float *x0_dev, const float *b_dev, uint64_t n, double tol, uint64_t max_iter,
+                              double soft_restart_threshold, float *x_dev, sprs_hip_bicgstab_info *info, void *stream) {
+    clear_error();
+    if (!a) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if (a->rows != a->cols || a->rows != n) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    if (n && (!x0_dev || !b_dev || !x_dev)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL vector");
+    if (x_dev == x0_dev || x_dev == b_dev) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "x_dev may not alias x0_dev / b_dev");
+    const float tol32 = (float)tol, thr32 = (float)soft_restart_threshold;   // f32 values that travelled as doubles
+    if (n == 0) {
+        // as sprs_hip_bicgstab_f64 with empty vectors: every norm is sqrt(0) = 0
+        const bool passes = max_iter > 0 && 0.0f < tol32;
+        const uint64_t it = passes ? 1 : max_iter;
+        if (info) *info = sprs_hip_bicgstab_info{it, 0, passes ? 1ull : 0ull, 0.0, 0.0, passes ? 1 : 0};
+        return SPRS_HIP_OK;
+    }
+    return bicgstab_f32(a, x0_dev, b_dev, n, tol32, max_iter, thr32, x_dev, info, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
 // the pool and the handle constructors live in handle.hpp, compiled here so that the library and its emulator build (tests/emu,
 // a fixed list of translation units) both carry them
 #include "handle.hpp"

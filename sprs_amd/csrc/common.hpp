@@ -422,6 +422,41 @@ struct sprs_hip_csmat {
     ~sprs_hip_csmat();         // handle.hpp: waits for the device when cached copies are held, drops them, then the blocks
 };
 
+// ---- single precision (spmv_f32.hpp) ----------------------------------------------------------------
+namespace sprs_hip {
+// The f32 SpMV runs on the plain nnz-tile plan only: the tile index over the handle's own arrays and one carry array per stream.
+struct SpmvPlanF32 {
+    bool built = false;
+    uint32_t tile = 0;                 // nnz per tile: 2048 or 4096
+    int64_t opt_tile = 0;              // value of option spmv_tile the plan was built with
+    uint64_t ntiles = 0;
+    uint64_t *tile_row = nullptr;      // device, ntiles + 1: first row starting at/after tile c
+    std::vector<DevBuf> blocks;        // the block behind tile_row
+    std::unordered_map<void *, DevBuf> carry;   // per stream: ntiles floats
+};
+}  // namespace sprs_hip
+
+// Device twin of CsMatBase for N = f32.  A type of its own, not a flag of sprs_hip_csmat: no entry that reads `double *data`
+// can be handed one (include/sprs_hip.h).  Index arrays are 4 or 8 bytes wide, on the host as on the device.
+struct sprs_hip_csmat_f32 {
+    int32_t storage = SPRS_HIP_CSR;
+    uint64_t rows = 0, cols = 0, nnz = 0;
+    int32_t iptr_bytes = 8, idx_bytes = 8;
+    void *indptr = nullptr;    // device, outer+1 entries, zero based
+    void *indices = nullptr;   // device, nnz entries
+    float *data = nullptr;     // device, nnz entries
+    bool prepared = false;     // sprs_hip_csmat_f32_prepare was called (kept across refresh: the CSR copy of a CSC handle is prepared with it)
+    sprs_hip::PoolBlock own_data, own_indices, own_indptr;    // the blocks behind the arrays when the handle owns them (released indptr first)
+    int device = 0;
+    std::recursive_mutex mu;   // guards plan / as_other, like sprs_hip_csmat::mu
+    sprs_hip::SpmvPlanF32 plan;
+    sprs_hip_csmat_f32 *as_other = nullptr;   // the handle in the other storage order: a CSC operand multiplies through its CSR form; dropped by refresh / free
+
+    uint64_t outer() const { return storage == SPRS_HIP_CSR ? rows : cols; }
+    uint64_t inner() const { return storage == SPRS_HIP_CSR ? cols : rows; }
+    ~sprs_hip_csmat_f32();     // handle.hpp
+};
+
 namespace sprs_hip {
 
 // Host copies run on the stream of the work around them and are complete when these return: a read-back sees every kernel
@@ -468,6 +503,7 @@ auto dispatch_host_width(int32_t bytes, F &&f) {
 using OwnedCsmat = std::unique_ptr<sprs_hip_csmat>;
 using OwnedCsvec = std::unique_ptr<sprs_hip_csvec>;
 using OwnedPerm = std::unique_ptr<sprs_hip_perm>;
+using OwnedCsmatF32 = std::unique_ptr<sprs_hip_csmat_f32>;
 
 // spmv_band.hip
 int32_t band_build(sprs_hip_csmat *a, hipStream_t stream, OwnedBandPlan &out);   // out stays empty when the plan does not apply
@@ -546,6 +582,8 @@ int32_t csmat_binop_dense_f64(const sprs_hip_csmat *lhs, const double *rhs, int3
 // bicgstab.hip
 int32_t bicgstab_f64(sprs_hip_csmat *a, const double *x0, const double *b, uint64_t n, double tol, uint64_t max_iter,
                      double soft_restart_threshold, double *x, sprs_hip_bicgstab_info *info, hipStream_t stream);
+int32_t bicgstab_f32(sprs_hip_csmat_f32 *a, const float *x0, const float *b, uint64_t n, float tol, uint64_t max_iter,
+                     float soft_restart_threshold, float *x, sprs_hip_bicgstab_info *info, hipStream_t stream);
 // gauss_seidel.hip
 int32_t gauss_seidel_f64(sprs_hip_csmat *a, double *x, const double *rhs, uint64_t n, uint64_t max_iter, double eps,
                          sprs_hip_gauss_seidel_info *info, hipStream_t stream);
@@ -607,6 +645,20 @@ sprs_hip_csmat *view_csmat(const sprs_hip_csmat *m, bool transpose, sprs_hip_csm
 int32_t copy_csmat(const sprs_hip_csmat *m, bool with_data, OwnedCsmat &out, hipStream_t stream);
 // everything a handle derives from its arrays (plans, row orders, the copy in the other storage order, the transpose view)
 void invalidate_caches(sprs_hip_csmat *m);
+// single precision (handle.hpp): an owned f32 matrix with uninitialised arrays, the two views, and an owned f32 matrix that takes
+// over the indptr and indices blocks of an owned f64 one (which is left without them) beside a fresh block of nnz floats
+int32_t make_csmat_f32(OwnedCsmatF32 &out, int32_t storage, uint64_t rows, uint64_t cols, uint64_t nnz, int32_t iptr_bytes, int32_t idx_bytes);
+sprs_hip_csmat_f32 *view_csmat_f32(int32_t storage, uint64_t rows, uint64_t cols, uint64_t nnz, const void *indptr, int32_t iptr_bytes,
+                                   const void *indices, int32_t idx_bytes, const float *data, int device);
+sprs_hip_csmat_f32 *view_csmat_f32(const sprs_hip_csmat_f32 *m, bool transpose);
+int32_t adopt_structure_f32(sprs_hip_csmat *from, OwnedCsmatF32 &out);
+void invalidate_caches(sprs_hip_csmat_f32 *m);
+// spmv_f32.hpp (compiled in spmv.hip)
+int32_t spmv_f32_prepare(sprs_hip_csmat_f32 *a, hipStream_t stream);   // the tile index and `stream`'s carry array, now
+int32_t spmv_f32(sprs_hip_csmat_f32 *a, const float *x, float *y, bool accumulate, hipStream_t stream);
+int32_t csmat_f32_to_other_storage(const sprs_hip_csmat_f32 *m, OwnedCsmatF32 &out);             // complete at return
+int32_t csmat_f32_from_f64(const sprs_hip_csmat *m, OwnedCsmatF32 &out, hipStream_t stream);     // ordered on `stream`
+int32_t csmat_f32_to_f64(const sprs_hip_csmat_f32 *m, OwnedCsmat &out, hipStream_t stream);      // ordered on `stream`
 // abi.hip
 // a result inherits the declared index widths of its operand; INDEX_OVERFLOW where a value would not fit them
 int32_t inherit_declared_widths(sprs_hip_csmat *result, const sprs_hip_csmat *from);

@@ -148,6 +148,43 @@ int32_t make_perm(OwnedPerm &out, uint64_t dim, int32_t idx_bytes, int32_t decl_
     return SPRS_HIP_OK;
 }
 
+int32_t make_csmat_f32(OwnedCsmatF32 &out, int32_t storage, uint64_t rows, uint64_t cols, uint64_t nnz, int32_t iptr_bytes, int32_t idx_bytes) {
+    OwnedCsmatF32 m(new sprs_hip_csmat_f32());
+    m->storage = storage;
+    m->rows = rows;
+    m->cols = cols;
+    m->nnz = nnz;
+    m->iptr_bytes = iptr_bytes;
+    m->idx_bytes = idx_bytes;
+    SPRS_TRY(take_blocks(&m->device, {{&m->own_indptr, (m->outer() + 1) * (uint64_t)iptr_bytes}, {&m->own_indices, nnz * (uint64_t)idx_bytes},
+                                      {&m->own_data, nnz * sizeof(float)}}, "alloc_csmat_f32"));
+    m->indptr = m->own_indptr.p;
+    m->indices = m->own_indices.p;
+    m->data = (float *)m->own_data.p;
+    out = std::move(m);
+    return SPRS_HIP_OK;
+}
+
+// the structure of `from` (an owned f64 matrix: a conversion result) moves into a new f32 handle; its values get a fresh block
+int32_t adopt_structure_f32(sprs_hip_csmat *from, OwnedCsmatF32 &out) {
+    OwnedCsmatF32 m(new sprs_hip_csmat_f32());
+    m->storage = from->storage;
+    m->rows = from->rows;
+    m->cols = from->cols;
+    m->nnz = from->nnz;
+    m->iptr_bytes = from->iptr_bytes;
+    m->idx_bytes = from->idx_bytes;
+    SPRS_TRY(take_blocks(&m->device, {{&m->own_data, from->nnz * sizeof(float)}}, "alloc_csmat_f32"));
+    m->own_indptr = std::move(from->own_indptr);
+    m->own_indices = std::move(from->own_indices);
+    from->indptr = from->indices = nullptr;
+    m->indptr = m->own_indptr.p;
+    m->indices = m->own_indices.p;
+    m->data = (float *)m->own_data.p;
+    out = std::move(m);
+    return SPRS_HIP_OK;
+}
+
 // ---- views: the array pointers set, the owners empty ----------------------------------------------------
 sprs_hip_csmat *view_csmat(int32_t storage, uint64_t rows, uint64_t cols, uint64_t nnz, const void *indptr, int32_t iptr_bytes,
                            const void *indices, int32_t idx_bytes, const double *data, int device, sprs_hip_csmat *into) {
@@ -172,6 +209,28 @@ sprs_hip_csmat *view_csmat(const sprs_hip_csmat *m, bool transpose, sprs_hip_csm
     t->decl_iptr_bytes = m->decl_iptr_bytes;
     t->decl_idx_bytes = m->decl_idx_bytes;
     return t;
+}
+
+sprs_hip_csmat_f32 *view_csmat_f32(int32_t storage, uint64_t rows, uint64_t cols, uint64_t nnz, const void *indptr, int32_t iptr_bytes,
+                                   const void *indices, int32_t idx_bytes, const float *data, int device) {
+    auto *t = new sprs_hip_csmat_f32();
+    t->storage = storage;
+    t->rows = rows;
+    t->cols = cols;
+    t->nnz = nnz;
+    t->iptr_bytes = iptr_bytes;
+    t->idx_bytes = idx_bytes;
+    t->indptr = const_cast<void *>(indptr);
+    t->indices = const_cast<void *>(indices);
+    t->data = const_cast<float *>(data);
+    t->device = device;
+    return t;
+}
+
+sprs_hip_csmat_f32 *view_csmat_f32(const sprs_hip_csmat_f32 *m, bool transpose) {
+    const int32_t other = m->storage == SPRS_HIP_CSR ? SPRS_HIP_CSC : SPRS_HIP_CSR;
+    return view_csmat_f32(transpose ? other : m->storage, transpose ? m->cols : m->rows, transpose ? m->rows : m->cols, m->nnz, m->indptr,
+                          m->iptr_bytes, m->indices, m->idx_bytes, m->data, m->device);
 }
 
 sprs_hip_csvec *view_csvec(uint64_t dim, uint64_t nnz, const void *indices, int32_t idx_bytes, const double *data, int device) {
@@ -237,7 +296,19 @@ void invalidate_caches(sprs_hip_csmat *m) {
     m->as_other = nullptr;
 }
 
+void invalidate_caches(sprs_hip_csmat_f32 *m) {
+    m->plan = SpmvPlanF32();
+    delete m->as_other;
+    m->as_other = nullptr;
+}
+
 }  // namespace sprs_hip
+
+sprs_hip_csmat_f32::~sprs_hip_csmat_f32() {
+    // as for the f64 handle: a kernel in flight may still read the tile index, a carry array or the CSR copy
+    if (as_other || plan.built) (void)hipDeviceSynchronize();
+    sprs_hip::invalidate_caches(this);
+}
 
 sprs_hip_csmat::~sprs_hip_csmat() {
     // a kernel launched through a cached copy (as_other, t_view) or a plan copy may still be reading it: a handle that holds

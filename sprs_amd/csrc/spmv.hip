@@ -829,3 +829,5 @@ int32_t spmv_f64(sprs_hip_csmat *a, const double *x, double *y, bool accumulate,
 #include "csvec.hpp"
 // sparse-vector reductions (the ordered sum), unit_normalize and the batched look-ups
 #include "csvec_reduce.hpp"
+// single precision: the f32 tile kernel and its plan, to_other_storage and the value casts of f32 handles
+#include "spmv_f32.hpp"

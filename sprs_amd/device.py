@@ -69,6 +69,62 @@ class DeviceVec:
             self.ptr = 0
 
 
+class DeviceVecF32:
+    """A dense f32 vector in HBM: the operand and result type of the single-precision products (DeviceCsMatF32).  Not a
+    DeviceVec: an entry that reads n doubles must never be handed n floats."""
+
+    def __init__(self, n, ptr=None, owner=None):
+        self.n = int(n)
+        self._owner = owner
+        if ptr is None:
+            p = C.c_void_p()
+            check(lib.sprs_hip_malloc(C.byref(p), self.n * 4))
+            self.ptr = p.value
+            self._owned = True
+        else:
+            self.ptr = int(ptr)
+            self._owned = False
+
+    @classmethod
+    def from_host(cls, arr):
+        """casts to float32 (numpy's astype: round to nearest even)"""
+        arr = np.ascontiguousarray(arr, dtype=np.float32)
+        v = cls(arr.size)
+        check(lib.sprs_hip_memcpy_h2d(C.c_void_p(v.ptr), _vp(arr), arr.size * 4))
+        return v
+
+    @classmethod
+    def zeros(cls, n):
+        v = cls(n)
+        check(lib.sprs_hip_memset(C.c_void_p(v.ptr), 0, v.n * 4, None))
+        return v
+
+    @classmethod
+    def borrow(cls, tensor):
+        """Borrow a contiguous float32 torch CUDA tensor (no copy); TypeError for any other element type."""
+        if tensor.element_size() != 4 or not tensor.is_floating_point():
+            raise TypeError("float32 elements expected")
+        assert tensor.is_cuda and tensor.is_contiguous()
+        return cls(tensor.numel(), ptr=tensor.data_ptr(), owner=tensor)
+
+    def to_host(self):
+        out = np.empty(self.n, dtype=np.float32)
+        check(lib.sprs_hip_synchronize(None))
+        check(lib.sprs_hip_memcpy_d2h(_vp(out), C.c_void_p(self.ptr), self.n * 4))
+        return out
+
+    def dim(self):
+        return self.n
+
+    def __len__(self):
+        return self.n
+
+    def __del__(self):
+        if getattr(self, "_owned", False) and self.ptr:
+            lib.sprs_hip_free(C.c_void_p(self.ptr))
+            self.ptr = 0
+
+
 class DeviceCsMat:
     """A CSR/CSC matrix whose indptr / indices / data live in HBM behind a
     `sprs_hip_csmat*` handle."""
@@ -248,6 +304,13 @@ class DeviceCsMat:
         check(lib.sprs_hip_csmat_to_other_storage(self._h, C.byref(h)))
         return DeviceCsMat(h.value)
 
+    def to_f32(self, stream=None):
+        """CsMat::map(|&v| v as f32) (csmat.rs:1289-1305) as a DeviceCsMatF32: the structure copied, the values rounded to
+        nearest even (overflow gives inf, NaN stays NaN)."""
+        h = C.c_void_p()
+        check(lib.sprs_hip_csmat_f32_from_f64(self._h, C.byref(h), _stream_arg(stream)))
+        return DeviceCsMatF32(h.value)
+
     def degrees(self, stream=None, out=None):
         """csmat.rs:1205-1216: per outer index the stored entries off the diagonal, as a host uint64 array.  `out`: a
         DeviceVec of outer-dimension words that receives the counts instead (they stay on the device; returns out)."""
@@ -324,6 +387,8 @@ class DeviceCsMat:
     # -- operators: `&A * &x`, `&A * &B` ---------------------------------------
     def __mul__(self, rhs):
         from . import prod
+        if isinstance(rhs, DeviceVecF32):
+            raise TypeError("an f64 matrix times an f32 vector: convert one operand (DeviceCsMat.to_f32)")
         if isinstance(rhs, DeviceCsVec):
             return prod.csmat_mul_csvec(self, rhs)        # vec.rs:1104-1131
         if isinstance(rhs, DeviceVec):
@@ -369,6 +434,124 @@ class DeviceCsMat:
         h = getattr(self, "_h", None)
         if h is not None and h.value:
             lib.sprs_hip_csmat_free(h)
+            self._h = C.c_void_p(0)
+
+
+class DeviceCsMatF32:
+    """A CSR/CSC matrix of f32 values in HBM behind a `sprs_hip_csmat_f32*` handle: CsMat<f32>.  Built for it: the container,
+    `&A * &x` and the two mul_acc forms with DeviceVecF32 (prod.py), BiCGSTAB (linalg.py); `to_f64()` reaches every other
+    operation.  Index arrays are 4 or 8 bytes wide (no 2-byte ones)."""
+
+    def __init__(self, handle, keep=None):
+        self._h = C.c_void_p(handle)
+        self._keep = keep   # objects the handle borrows from
+
+    @classmethod
+    def from_host(cls, shape, indptr, indices, data, storage=CSR, validate=True):
+        """CsMat::new / new_csc when validate, new_trusted otherwise; data is cast to float32."""
+        indptr = np.ascontiguousarray(indptr)
+        indices = np.ascontiguousarray(indices)
+        data = np.ascontiguousarray(data, dtype=np.float32)
+        if indptr.dtype.kind not in "iu" or indices.dtype.kind not in "iu":
+            raise TypeError("integer index arrays expected")
+        if indices.size != data.size:
+            raise _ffi.SprsHipError(_ffi.BAD_STRUCTURE, "indices and data lengths differ")
+        outer = shape[0] if storage == CSR else shape[1]
+        if indptr.size != outer + 1:
+            raise _ffi.SprsHipError(_ffi.BAD_STRUCTURE, "Indptr length does not match dimension")
+        if validate and int(indptr[-1]) - int(indptr[0]) != indices.size:
+            raise _ffi.SprsHipError(_ffi.BAD_STRUCTURE, "Indices length and inpdtr's nnz do not match")
+        h = C.c_void_p()
+        check(lib.sprs_hip_csmat_f32_upload(C.byref(h), storage, shape[0], shape[1], _vp(indptr), indptr.dtype.itemsize,
+                                            _vp(indices), indices.dtype.itemsize, _vp(data), 1 if validate else 0))
+        return cls(h.value)
+
+    @classmethod
+    def wrap_torch(cls, shape, indptr_t, indices_t, data_t, storage=CSR):
+        """Borrow torch CUDA tensors (int32 / int64 index arrays, float32 data) as the three arrays (no copy)."""
+        if data_t.element_size() != 4 or not data_t.is_floating_point():
+            raise TypeError("float32 data expected")
+        h = C.c_void_p()
+        check(lib.sprs_hip_csmat_f32_wrap_device(
+            C.byref(h), storage, shape[0], shape[1], indices_t.numel(),
+            C.c_void_p(indptr_t.data_ptr()), indptr_t.element_size(),
+            C.c_void_p(indices_t.data_ptr() if indices_t.numel() else 0), indices_t.element_size(),
+            C.c_void_p(data_t.data_ptr() if data_t.numel() else 0)))
+        return cls(h.value, keep=(indptr_t, indices_t, data_t))
+
+    def _info(self):
+        r, c, n = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        pb, ib, st = C.c_int32(), C.c_int32(), C.c_int32()
+        check(lib.sprs_hip_csmat_f32_info(self._h, C.byref(r), C.byref(c), C.byref(n), C.byref(pb), C.byref(ib), C.byref(st)))
+        return r.value, c.value, n.value, pb.value, ib.value, st.value
+
+    def rows(self): return self._info()[0]
+    def cols(self): return self._info()[1]
+    def shape(self): return self._info()[:2]
+    def nnz(self): return self._info()[2]
+    def storage(self): return self._info()[5]
+    def is_csr(self): return self.storage() == CSR
+    def is_csc(self): return self.storage() == CSC
+    def index_bytes(self): return self._info()[4]
+    def indptr_bytes(self): return self._info()[3]
+
+    def device_ptrs(self):
+        """-> (indptr, indices, data) device addresses (into_raw_storage), still owned by the handle"""
+        a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(lib.sprs_hip_csmat_f32_device_ptrs(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def to_host(self):
+        """-> (shape, indptr, indices, data) numpy arrays, data float32"""
+        r, c, n, pb, ib, st = self._info()
+        outer = r if st == CSR else c
+        indptr = np.empty(outer + 1, dtype=_DT[pb])
+        indices = np.empty(n, dtype=_DT[ib])
+        data = np.empty(n, dtype=np.float32)
+        check(lib.sprs_hip_csmat_f32_download(self._h, _vp(indptr), _vp(indices), _vp(data)))
+        return (r, c), indptr, indices, data
+
+    def transpose_view(self):
+        """csmat.rs:982-991: free, shares buffers."""
+        h = C.c_void_p()
+        check(lib.sprs_hip_csmat_f32_transpose_view(self._h, C.byref(h)))
+        return DeviceCsMatF32(h.value, keep=self)
+
+    def to_other_storage(self):
+        """csmat.rs:1405-1426."""
+        h = C.c_void_p()
+        check(lib.sprs_hip_csmat_f32_to_other_storage(self._h, C.byref(h)))
+        return DeviceCsMatF32(h.value)
+
+    def to_f64(self, stream=None):
+        """CsMat::map(|&v| v as f64): exact."""
+        h = C.c_void_p()
+        check(lib.sprs_hip_csmat_f32_to_f64(self._h, C.byref(h), _stream_arg(stream)))
+        return DeviceCsMat(h.value)
+
+    def prepare(self, stream=None):
+        """Build the SpMV plan (and `stream`'s carry array) now: needed before an SpMV on a capturing stream."""
+        check(lib.sprs_hip_csmat_f32_prepare(self._h, _stream_arg(stream)))
+        return self
+
+    def refresh(self):
+        """Drop the cached plan and CSR form after the wrapped device arrays were modified in place."""
+        check(lib.sprs_hip_csmat_f32_refresh(self._h))
+
+    def __mul__(self, rhs):
+        from . import prod
+        if isinstance(rhs, DeviceVecF32):
+            return prod.csmat_mul_vec(self, rhs)
+        if isinstance(rhs, DeviceVec):
+            raise TypeError("an f32 matrix times an f64 vector: convert one operand (DeviceCsMatF32.to_f64)")
+        return NotImplemented
+
+    __matmul__ = __mul__
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            lib.sprs_hip_csmat_f32_free(h)
             self._h = C.c_void_p(0)
 
 

@@ -28,10 +28,23 @@ class BiCGSTAB:
     @classmethod
     def solve(cls, a, x0, b, tol, max_iter, soft_restart_threshold=0.1, stream=None):
         """BiCGSTAB::solve(a, x0, b, tol, max_iter) (bicgstab.rs:148-171).  a: square DeviceCsMat (CSR or
-        CSC), x0 / b: DeviceVec.  Dimension mismatch raises like the reference's panics."""
+        CSC), x0 / b: DeviceVec.  Dimension mismatch raises like the reference's panics.  A DeviceCsMatF32 with DeviceVecF32
+        vectors runs BiCGSTAB::<f32> (sprs_hip_bicgstab_f32): tol and the threshold are rounded to f32 first."""
+        from .device import DeviceCsMatF32, DeviceVecF32
         n = x0.n
         if b.n != n:
             raise _ffi.SprsHipError(_ffi.DIM_MISMATCH, "Dimension mismatch")
+        f32 = isinstance(a, DeviceCsMatF32)
+        if isinstance(x0, DeviceVecF32) != f32 or isinstance(b, DeviceVecF32) != f32:
+            raise TypeError("matrix and vectors must have the same precision")
+        if f32:
+            import numpy as np
+            x = DeviceVecF32(n)
+            info = _Info()
+            check(lib.sprs_hip_bicgstab_f32(a._h, C.c_void_p(x0.ptr), C.c_void_p(b.ptr), n, float(np.float32(tol)), int(max_iter),
+                                            float(np.float32(soft_restart_threshold)), C.c_void_p(x.ptr), C.byref(info),
+                                            C.c_void_p(int(stream) if stream else 0)))
+            return cls(a, x, b, info, soft_restart_threshold)
         x = DeviceVec(n)
         info = _Info()
         check(lib.sprs_hip_bicgstab_f64(a._h, C.c_void_p(x0.ptr), C.c_void_p(b.ptr), n, float(tol), int(max_iter),

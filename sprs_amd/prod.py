@@ -14,8 +14,23 @@ def _stream_ptr(stream):
     return C.c_void_p(int(getattr(stream, "cuda_stream", stream)))
 
 
+def _is_f32(mat, *vecs):
+    """True for a DeviceCsMatF32 with DeviceVecF32 operands, False for the f64 classes; a mix raises TypeError (the reference's
+    N is one type per call: the entries of one precision must never read the buffers of the other)"""
+    from .device import DeviceCsMatF32, DeviceVecF32
+    f32 = isinstance(mat, DeviceCsMatF32)
+    for v in vecs:
+        if isinstance(v, DeviceVecF32) != f32:
+            raise TypeError("matrix and vectors must have the same precision: %s with %s" % (type(mat).__name__, type(v).__name__))
+    return f32
+
+
 def mul_acc_mat_vec_csr(mat, in_vec, res_vec, stream=None):
-    """prod::mul_acc_mat_vec_csr (prod.rs:103-127): res_vec += mat * in_vec."""
+    """prod::mul_acc_mat_vec_csr (prod.rs:103-127): res_vec += mat * in_vec.  A DeviceCsMatF32 with DeviceVecF32 operands runs
+    the f32 entry."""
+    if _is_f32(mat, in_vec, res_vec):
+        check(lib.sprs_hip_spmv_f32(mat._h, C.c_void_p(in_vec.ptr), in_vec.n, C.c_void_p(res_vec.ptr), res_vec.n, 1, _stream_ptr(stream)))
+        return
     check(lib.sprs_hip_spmv_f64(mat._h, C.c_void_p(in_vec.ptr), in_vec.n, C.c_void_p(res_vec.ptr),
                                 res_vec.n, 1, _stream_ptr(stream)))
 
@@ -23,7 +38,11 @@ def mul_acc_mat_vec_csr(mat, in_vec, res_vec, stream=None):
 def mul_acc_mat_vec_csc(mat, in_vec, res_vec, stream=None):
     """prod::mul_acc_mat_vec_csc (prod.rs:74-99): res_vec += mat * in_vec for a CSC matrix (sprs_hip_mul_acc_mat_vec_csc_f64:
     the matrix is converted once to CSR on the device, the copy is cached in the HANDLE, the CSR kernel runs — every result
-    element still receives its products by ascending column)."""
+    element still receives its products by ascending column).  A DeviceCsMatF32 with DeviceVecF32 operands runs the f32 entry."""
+    if _is_f32(mat, in_vec, res_vec):
+        check(lib.sprs_hip_mul_acc_mat_vec_csc_f32(mat._h, C.c_void_p(in_vec.ptr), in_vec.n, C.c_void_p(res_vec.ptr), res_vec.n,
+                                                   _stream_ptr(stream)))
+        return
     check(lib.sprs_hip_mul_acc_mat_vec_csc_f64(mat._h, C.c_void_p(in_vec.ptr), in_vec.n, C.c_void_p(res_vec.ptr), res_vec.n,
                                                _stream_ptr(stream)))
 
@@ -165,6 +184,12 @@ def dense_dot_csmat(lhs, mat, stream=None):
 def csmat_mul_vec(mat, vec, out=None, stream=None):
     """`&CsMat * &Array1` (csmat.rs:2119-2160): fresh zero result; CSR goes through csr_mulacc_dense_colmaj with one column,
     CSC through csc_mulacc_dense_colmaj (csmat.rs:2140-2156) — dispatched below the C ABI (sprs_hip_csmat_mul_vec_f64)."""
+    if _is_f32(mat, vec, *([] if out is None else [out])):
+        from .device import DeviceVecF32
+        if out is None:
+            out = DeviceVecF32(mat.rows())
+        check(lib.sprs_hip_csmat_mul_vec_f32(mat._h, C.c_void_p(vec.ptr), vec.n, C.c_void_p(out.ptr), out.n, _stream_ptr(stream)))
+        return out
     if out is None:
         out = DeviceVec(mat.rows())
     check(lib.sprs_hip_csmat_mul_vec_f64(mat._h, C.c_void_p(vec.ptr), vec.n, C.c_void_p(out.ptr), out.n, _stream_ptr(stream)))
