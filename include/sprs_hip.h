@@ -997,6 +997,54 @@ int32_t sprs_hip_bicgstab_f32(sprs_hip_csmat_f32 *a, const float *x0_dev, const 
                               double tol, uint64_t max_iter, double soft_restart_threshold, float *x_dev,
                               sprs_hip_bicgstab_info *info, void *stream);
 
+/* ---- f32 SpMM: the dense products of an f32 matrix ----------------------------------------------------------------------
+ * The reference's dense kernels are generic over the scalar (prod.rs:189-298 over MulAcc, mul_acc.rs:17-31; dispatch at
+ * csmat.rs:1989-2117).  The four entries below are the f32 twins of sprs_hip_spmm_rowmaj_f64, sprs_hip_csmat_mulacc_dense_f64,
+ * sprs_hip_csmat_mul_dense_f64 and sprs_hip_dense_dot_csmat_f64: the same argument order, checks, statuses and texts, with
+ * `float *` operands (leading dimensions in ELEMENTS).  Every product is rounded to f32 and added in f32, multiply and add
+ * unfused; no atomics, the same bits from call to call.  The summation order is the entry-stream kernel's (runs of
+ * consecutive entries in entry order, joined in run and tile order) — not the reference's single chain, unless option
+ * spmm_long_row = L > 0 asks for that chain for rows of <= L entries.  Options spmm_stream, spmm_long_row and spmm_relayout
+ * act as documented for f64; option spmm_f32_pair picks the lane form of the f32 stream kernel: paired lanes (two adjacent
+ * columns per lane, one 8-byte gather) are ELIGIBLE where the rhs the kernel reads has unit column stride, an even row pitch
+ * and an 8-byte aligned base — always so for the re-laid-out copy — and scalar lanes run elsewhere; 1 (default) takes the
+ * paired form where it is eligible and was measured faster (column groups of 32 / 64, matrices of >= 8 entries per row), 2
+ * wherever it is eligible, 0 never. */
+
+/* Twin of prod::csr_mulacc_dense_rowmaj (prod.rs:189-214) for N = f32: out[i, :] += A[i, c] * rhs[c, :] (accumulate != 0) or
+ * the same on a zeroed `out`.  rhs_dev: rhs_rows x k floats, row-major, leading dimension ld_rhs (>= k); out_dev: out_rows x k,
+ * leading dimension ld_out.  SPRS_HIP_DIM_MISMATCH unless A.cols == rhs_rows && A.rows == out_rows, then
+ * SPRS_HIP_STORAGE_MISMATCH unless A is CSR (prod.rs:199-202).  Asynchronous on `stream`; deterministic. */
+int32_t sprs_hip_spmm_rowmaj_f32(const sprs_hip_csmat_f32 *a, const float *rhs_dev, uint64_t rhs_rows,
+                                 uint64_t k, uint64_t ld_rhs, float *out_dev, uint64_t out_rows,
+                                 uint64_t ld_out, int32_t accumulate, void *stream);
+
+/* The four dense kernels of prod.rs in one entry for N = f32: csr_mulacc_dense_rowmaj / _colmaj (prod.rs:189-214, 274-298) and
+ * csc_mulacc_dense_rowmaj / _colmaj (prod.rs:219-270).  lhs in either storage (CSC through the cached CSR form), rhs
+ * (rhs_rows x k) and out (out_rows x k) each in the layout its tag names with leading dimension ld in floats (row-major: >= k,
+ * column-major: >= rows).  Column-major x column-major with k < 8 runs column by column through sprs_hip_spmv_f32's kernel.
+ * SPRS_HIP_DIM_MISMATCH unless lhs.cols == rhs_rows && lhs.rows == out_rows (prod.rs:199-201, 228-230, 257-259, 284-289);
+ * SPRS_HIP_INVALID_ARG for a bad layout tag, a leading dimension smaller than the extent it strides over, a NULL matrix, or an
+ * `out` that shares an element with `rhs` (two views of one buffer with the same layout and pitch whose lines fall into each
+ * other's gaps are accepted). */
+int32_t sprs_hip_csmat_mulacc_dense_f32(const sprs_hip_csmat_f32 *lhs, const float *rhs_dev, uint64_t rhs_rows, uint64_t k,
+                                        int32_t rhs_layout, uint64_t ld_rhs, float *out_dev, uint64_t out_rows,
+                                        int32_t out_layout, uint64_t ld_out, int32_t accumulate, void *stream);
+
+/* Twin of `&CsMat * &Array2` / `CsMat::dot(&Array2)` (csmat.rs:1989-2048, 2119-2137) for N = f32.  out_dev: lhs.rows x k floats,
+ * contiguous; written in the layout the reference allocates — row-major for k >= 8 (csmat.rs:2002-2016), column-major (`.f()`,
+ * csmat.rs:2017-2045) below — which *out_layout reports. */
+int32_t sprs_hip_csmat_mul_dense_f32(const sprs_hip_csmat_f32 *lhs, const float *rhs_dev, uint64_t rhs_rows, uint64_t k,
+                                     int32_t rhs_layout, uint64_t ld_rhs, float *out_dev, int32_t *out_layout, void *stream);
+
+/* Twin of `Array2::dot(&CsMat)` (csmat.rs:2050-2117) for N = f32: lhs (lhs_rows x lhs_cols, dense) . rhs (sparse) as
+ * (rhs^T lhs^T)^T with the reference's free transposes.  out_dev: lhs_rows x rhs.cols floats, contiguous, in the layout
+ * *out_layout reports.  A CSR rhs is converted once to CSC (cached in the handle); the transpose view and its plans stay in the
+ * rhs handle until _refresh / _free. */
+int32_t sprs_hip_dense_dot_csmat_f32(const float *lhs_dev, uint64_t lhs_rows, uint64_t lhs_cols, int32_t lhs_layout,
+                                     uint64_t ld_lhs, const sprs_hip_csmat_f32 *rhs, float *out_dev, int32_t *out_layout,
+                                     void *stream);
+
 #ifdef __cplusplus
 }
 #endif

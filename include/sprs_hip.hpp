@@ -1221,6 +1221,70 @@ inline DeviceVecF32 operator*(const DeviceCsMatF32 &a, const DeviceVecF32 &x) { 
     return y;
 }
 
+// Dense f32 matrix in HBM: DeviceMat for N = f32, the operand and result type of the dense products of a DeviceCsMatF32.  A
+// type of its own: no overload below takes operands of two precisions.
+class DeviceMatF32 {
+public:
+    DeviceMatF32(uint64_t rows, uint64_t cols, bool col_major = false) : buf_(rows * cols), rows_(rows), cols_(cols), col_major_(col_major) {}
+    // elements in memory order of the chosen layout
+    DeviceMatF32(uint64_t rows, uint64_t cols, const std::vector<float> &elems, bool col_major = false)
+        : buf_(elems), rows_(rows), cols_(cols), col_major_(col_major) {
+        if (elems.size() != rows * cols) throw Error(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    }
+    uint64_t rows() const { return rows_; }
+    uint64_t cols() const { return cols_; }
+    bool is_standard_layout() const { return !col_major_; }
+    int32_t layout() const { return col_major_ ? SPRS_HIP_COL_MAJOR : SPRS_HIP_ROW_MAJOR; }
+    uint64_t ld() const { return col_major_ ? rows_ : cols_; }
+    float *ptr() { return buf_.ptr(); }
+    const float *ptr() const { return buf_.ptr(); }
+    void set_layout(int32_t layout) { col_major_ = layout == SPRS_HIP_COL_MAJOR; }
+    float at(const std::vector<float> &host, uint64_t i, uint64_t j) const { return col_major_ ? host[j * rows_ + i] : host[i * cols_ + j]; }
+    std::vector<float> to_host() const { return buf_.to_host(); }       // memory order
+
+private:
+    DeviceVecF32 buf_;
+    uint64_t rows_, cols_;
+    bool col_major_;
+};
+
+namespace prod {
+namespace detail {
+inline void mulacc_dense(const DeviceCsMatF32 &lhs, bool want_csr, const DeviceMatF32 &rhs, DeviceMatF32 &out, void *stream) {
+    if (rhs.cols() != out.cols()) throw Error(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");       // prod.rs:201, 230, 259, 287
+    if (lhs.is_csr() != want_csr) {                                                                // prod.rs:202, 231, 258, 288 (after the dimensions)
+        if (lhs.cols() != rhs.rows() || lhs.rows() != out.rows()) throw Error(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+        throw Error(SPRS_HIP_STORAGE_MISMATCH, "Storage mismatch");
+    }
+    check(sprs_hip_csmat_mulacc_dense_f32(lhs.handle(), rhs.ptr(), rhs.rows(), rhs.cols(), rhs.layout(), rhs.ld(), out.ptr(),
+                                          out.rows(), out.layout(), out.ld(), 1, stream));
+}
+}  // namespace detail
+// prod::csr_mulacc_dense_rowmaj / _colmaj (prod.rs:189-214, 274-298), csc_mulacc_dense_rowmaj / _colmaj (prod.rs:219-270) for N = f32
+inline void csr_mulacc_dense_rowmaj(const DeviceCsMatF32 &lhs, const DeviceMatF32 &rhs, DeviceMatF32 &out, void *stream = nullptr) { detail::mulacc_dense(lhs, true, rhs, out, stream); }
+inline void csr_mulacc_dense_colmaj(const DeviceCsMatF32 &lhs, const DeviceMatF32 &rhs, DeviceMatF32 &out, void *stream = nullptr) { detail::mulacc_dense(lhs, true, rhs, out, stream); }
+inline void csc_mulacc_dense_rowmaj(const DeviceCsMatF32 &lhs, const DeviceMatF32 &rhs, DeviceMatF32 &out, void *stream = nullptr) { detail::mulacc_dense(lhs, false, rhs, out, stream); }
+inline void csc_mulacc_dense_colmaj(const DeviceCsMatF32 &lhs, const DeviceMatF32 &rhs, DeviceMatF32 &out, void *stream = nullptr) { detail::mulacc_dense(lhs, false, rhs, out, stream); }
+}  // namespace prod
+
+// `&A * &M` for N = f32 (csmat.rs:1989-2048): standard layout from 8 columns on, `.f()` layout below
+inline DeviceMatF32 operator*(const DeviceCsMatF32 &a, const DeviceMatF32 &m) {
+    DeviceMatF32 out(a.rows(), m.cols());
+    int32_t lay = SPRS_HIP_ROW_MAJOR;
+    check(sprs_hip_csmat_mul_dense_f32(a.handle(), m.ptr(), m.rows(), m.cols(), m.layout(), m.ld(), out.ptr(), &lay, nullptr));
+    out.set_layout(lay);
+    return out;
+}
+
+// `Array2::dot(&CsMat)` for N = f32 (csmat.rs:2050-2117): dense . sparse
+inline DeviceMatF32 dot(const DeviceMatF32 &lhs, const DeviceCsMatF32 &rhs) {
+    DeviceMatF32 out(lhs.rows(), rhs.cols());
+    int32_t lay = SPRS_HIP_ROW_MAJOR;
+    check(sprs_hip_dense_dot_csmat_f32(lhs.ptr(), lhs.rows(), lhs.cols(), lhs.layout(), lhs.ld(), rhs.handle(), out.ptr(), &lay, nullptr));
+    out.set_layout(lay);
+    return out;
+}
+
 namespace linalg {
 // BiCGSTAB::<f32>::solve (bicgstab.rs:148-171, :305)
 class BiCGSTABF32 {

@@ -409,6 +409,22 @@ extern "C" {
         a: *mut sprs_hip_csmat_f32, x0_dev: *const f32, b_dev: *const f32, n: u64, tol: f64, max_iter: u64, soft_restart_threshold: f64,
         x_dev: *mut f32, info: *mut sprs_hip_bicgstab_info, stream: *mut c_void,
     ) -> i32;
+    pub fn sprs_hip_spmm_rowmaj_f32(
+        a: *const sprs_hip_csmat_f32, rhs_dev: *const f32, rhs_rows: u64, k: u64, ld_rhs: u64,
+        out_dev: *mut f32, out_rows: u64, ld_out: u64, accumulate: i32, stream: *mut c_void,
+    ) -> i32;
+    pub fn sprs_hip_csmat_mulacc_dense_f32(
+        lhs: *const sprs_hip_csmat_f32, rhs_dev: *const f32, rhs_rows: u64, k: u64, rhs_layout: i32, ld_rhs: u64,
+        out_dev: *mut f32, out_rows: u64, out_layout: i32, ld_out: u64, accumulate: i32, stream: *mut c_void,
+    ) -> i32;
+    pub fn sprs_hip_csmat_mul_dense_f32(
+        lhs: *const sprs_hip_csmat_f32, rhs_dev: *const f32, rhs_rows: u64, k: u64, rhs_layout: i32, ld_rhs: u64,
+        out_dev: *mut f32, out_layout: *mut i32, stream: *mut c_void,
+    ) -> i32;
+    pub fn sprs_hip_dense_dot_csmat_f32(
+        lhs_dev: *const f32, lhs_rows: u64, lhs_cols: u64, lhs_layout: i32, ld_lhs: u64, rhs: *const sprs_hip_csmat_f32,
+        out_dev: *mut f32, out_layout: *mut i32, stream: *mut c_void,
+    ) -> i32;
     pub fn sprs_hip_set_option(name: *const c_char, value: i64) -> i32;
     pub fn sprs_hip_get_option(name: *const c_char, value: *mut i64) -> i32;
 }

@@ -1545,7 +1545,8 @@ pub mod construct {
     }
 }
 
-/// Single precision: `CsMat<f32>` on the device, `&A * &x` and `BiCGSTAB::<f32>` — what the reference instantiates for f32 on
+/// Single precision: `CsMat<f32>` on the device, `&A * &x`, the dense products (`&A * &M`, `M.dot(&A)`, the four `mulacc_dense`
+/// functions) and `BiCGSTAB::<f32>` — what the reference instantiates for f32 on
 /// the product path (bicgstab.rs:304-305; MulAcc, mul_acc.rs:17-31).  Types of their own over a handle type of its own: the
 /// compiler rejects a product of mixed precision.  Every other operation is reached through `to_f64` / `from_f64`, on the device.
 pub mod single {
@@ -1676,6 +1677,87 @@ pub mod single {
             check(sys::sprs_hip_mul_acc_mat_vec_csc_f32(mat.h, in_vec.ptr, in_vec.len as u64, res_vec.ptr, res_vec.len as u64,
                                                         std::ptr::null_mut()))
         };
+    }
+
+    /// A dense f32 matrix in HBM with ndarray's two contiguous layouts: `DeviceMat` for N = f32.
+    pub struct DeviceMatF32 {
+        buf: DeviceVecF32,
+        rows: usize,
+        cols: usize,
+        col_major: bool,
+    }
+
+    impl DeviceMatF32 {
+        pub fn zeros(shape: (usize, usize)) -> Self {
+            DeviceMatF32 { buf: DeviceVecF32::zeros(shape.0 * shape.1), rows: shape.0, cols: shape.1, col_major: false }
+        }
+        /// `Array::zeros(shape.f())`
+        pub fn zeros_f(shape: (usize, usize)) -> Self {
+            DeviceMatF32 { buf: DeviceVecF32::zeros(shape.0 * shape.1), rows: shape.0, cols: shape.1, col_major: true }
+        }
+        /// from an ndarray in standard layout (`as_slice()` order)
+        pub fn from_rows(shape: (usize, usize), row_major: &[f32]) -> Self {
+            assert_eq!(shape.0 * shape.1, row_major.len(), "Dimension mismatch");
+            DeviceMatF32 { buf: DeviceVecF32::from_slice(row_major), rows: shape.0, cols: shape.1, col_major: false }
+        }
+        pub fn shape(&self) -> (usize, usize) { (self.rows, self.cols) }
+        pub fn is_standard_layout(&self) -> bool { !self.col_major }
+        /// the elements in memory order (row-major, or column-major when `!is_standard_layout()`)
+        pub fn to_vec(&self) -> Vec<f32> { self.buf.to_vec() }
+        fn layout(&self) -> i32 { if self.col_major { sys::SPRS_HIP_COL_MAJOR } else { sys::SPRS_HIP_ROW_MAJOR } }
+        fn ld(&self) -> u64 { (if self.col_major { self.rows } else { self.cols }) as u64 }
+        /// `Array2::dot(&CsMat)` (csmat.rs:2050-2117) for N = f32: dense . sparse
+        pub fn dot(&self, rhs: &DeviceCsMatF32) -> DeviceMatF32 {
+            let mut out = DeviceMatF32::zeros((self.rows, rhs.cols()));
+            let mut lay = 0i32;
+            unsafe {
+                check(sys::sprs_hip_dense_dot_csmat_f32(self.buf.ptr, self.rows as u64, self.cols as u64, self.layout(), self.ld(), rhs.h,
+                                                        out.buf.ptr, &mut lay, std::ptr::null_mut()));
+            }
+            out.col_major = lay == sys::SPRS_HIP_COL_MAJOR;
+            out
+        }
+    }
+
+    /// `&A * &M` for N = f32 (csmat.rs:1989-2048): standard layout for >= 8 columns, `.f()` layout below.
+    impl<'a, 'b> std::ops::Mul<&'b DeviceMatF32> for &'a DeviceCsMatF32 {
+        type Output = DeviceMatF32;
+        fn mul(self, rhs: &'b DeviceMatF32) -> DeviceMatF32 {
+            let mut out = DeviceMatF32::zeros((self.rows(), rhs.cols));
+            let mut lay = 0i32;
+            unsafe {
+                check(sys::sprs_hip_csmat_mul_dense_f32(self.h, rhs.buf.ptr, rhs.rows as u64, rhs.cols as u64, rhs.layout(), rhs.ld(),
+                                                        out.buf.ptr, &mut lay, std::ptr::null_mut()));
+            }
+            out.col_major = lay == sys::SPRS_HIP_COL_MAJOR;
+            out
+        }
+    }
+
+    fn mulacc_dense(lhs: &DeviceCsMatF32, rhs: &DeviceMatF32, out: &mut DeviceMatF32) {
+        assert_eq!(rhs.cols, out.cols, "Dimension mismatch");                       // prod.rs:201
+        unsafe {
+            check(sys::sprs_hip_csmat_mulacc_dense_f32(lhs.h, rhs.buf.ptr, rhs.rows as u64, rhs.cols as u64, rhs.layout(), rhs.ld(),
+                                                       out.buf.ptr, out.rows as u64, out.layout(), out.ld(), 1, std::ptr::null_mut()));
+        }
+    }
+    /// Twins of `csr_mulacc_dense_rowmaj` / `_colmaj` (prod.rs:189-214, 274-298) and `csc_mulacc_dense_rowmaj` / `_colmaj`
+    /// (prod.rs:219-270) for N = f32: `out += lhs * rhs`.
+    pub fn csr_mulacc_dense_rowmaj(lhs: &DeviceCsMatF32, rhs: &DeviceMatF32, out: &mut DeviceMatF32) {
+        assert!(lhs.is_csr(), "Storage mismatch");
+        mulacc_dense(lhs, rhs, out)
+    }
+    pub fn csr_mulacc_dense_colmaj(lhs: &DeviceCsMatF32, rhs: &DeviceMatF32, out: &mut DeviceMatF32) {
+        assert!(lhs.is_csr(), "Storage mismatch");
+        mulacc_dense(lhs, rhs, out)
+    }
+    pub fn csc_mulacc_dense_rowmaj(lhs: &DeviceCsMatF32, rhs: &DeviceMatF32, out: &mut DeviceMatF32) {
+        assert!(!lhs.is_csr(), "Storage mismatch");
+        mulacc_dense(lhs, rhs, out)
+    }
+    pub fn csc_mulacc_dense_colmaj(lhs: &DeviceCsMatF32, rhs: &DeviceMatF32, out: &mut DeviceMatF32) {
+        assert!(!lhs.is_csr(), "Storage mismatch");
+        mulacc_dense(lhs, rhs, out)
     }
 
     /// `BiCGSTAB::<f32>::solve` (bicgstab.rs:148-171): `Ok(solver)` / `Err(solver)` like the reference.

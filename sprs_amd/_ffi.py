@@ -184,6 +184,10 @@ SIGNATURES = {
     "sprs_hip_mul_acc_mat_vec_csc_f32": (i32, [vp, vp, u64, vp, u64, vp]),
     "sprs_hip_csmat_mul_vec_f32": (i32, [vp, vp, u64, vp, u64, vp]),
     "sprs_hip_bicgstab_f32": (i32, [vp, vp, vp, u64, C.c_double, u64, C.c_double, vp, vp, vp]),
+    "sprs_hip_spmm_rowmaj_f32": (i32, [vp, vp, u64, u64, u64, vp, u64, u64, i32, vp]),
+    "sprs_hip_csmat_mulacc_dense_f32": (i32, [vp, vp, u64, u64, i32, u64, vp, u64, i32, u64, i32, vp]),
+    "sprs_hip_csmat_mul_dense_f32": (i32, [vp, vp, u64, u64, i32, u64, vp, P(i32), vp]),
+    "sprs_hip_dense_dot_csmat_f32": (i32, [vp, u64, u64, i32, u64, vp, vp, P(i32), vp]),
     "sprs_hip_set_option": (i32, [C.c_char_p, i64]),
     "sprs_hip_get_option": (i32, [C.c_char_p, P(i64)]),
 }

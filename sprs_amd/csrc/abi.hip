@@ -2387,6 +2387,100 @@ int32_t sprs_hip_bicgstab_f32(sprs_hip_csmat_f32 *a, const float *x0_dev, const 
     return bicgstab_f32(a, x0_dev, b_dev, n, tol32, max_iter, thr32, x_dev, info, (hipStream_t)stream);
 }
 
+// ---- f32 SpMM: the four dense products of an f32 handle (kernels: spmm_f32.hpp, spmm.hip) ----
+int32_t sprs_hip_spmm_rowmaj_f32(const sprs_hip_csmat_f32 *a, const float *rhs_dev, uint64_t rhs_rows, uint64_t k, uint64_t ld_rhs,
+                                 float *out_dev, uint64_t out_rows, uint64_t ld_out, int32_t accumulate, void *stream) {
+    clear_error();
+    if (!a) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    // prod.rs:199-202: three dimension asserts, then storage
+    if (a->cols != rhs_rows || a->rows != out_rows) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    if (a->storage != SPRS_HIP_CSR) SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "Storage mismatch");
+    if (ld_rhs < k || ld_out < k) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "leading dimension smaller than the column count");
+    if (k && ((rhs_rows && !rhs_dev) || (out_rows && !out_dev))) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL matrix");
+    return spmm_strided_f32(const_cast<sprs_hip_csmat_f32 *>(a), rhs_dev, k, ld_rhs, 1, out_dev, ld_out, 1, accumulate != 0, (hipStream_t)stream);
+}
+
+int32_t sprs_hip_csmat_mulacc_dense_f32(const sprs_hip_csmat_f32 *lhs, const float *rhs_dev, uint64_t rhs_rows, uint64_t k,
+                                        int32_t rhs_layout, uint64_t ld_rhs, float *out_dev, uint64_t out_rows,
+                                        int32_t out_layout, uint64_t ld_out, int32_t accumulate, void *stream) {
+    clear_error();
+    if (!lhs) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if ((rhs_layout != SPRS_HIP_ROW_MAJOR && rhs_layout != SPRS_HIP_COL_MAJOR) || (out_layout != SPRS_HIP_ROW_MAJOR && out_layout != SPRS_HIP_COL_MAJOR))
+        SPRS_FAIL(SPRS_HIP_INVALID_ARG, "bad layout tag");
+    // prod.rs:199-201, 228-230, 257-259, 284-289: the dimension asserts of the four dense kernels
+    if (lhs->cols != rhs_rows || lhs->rows != out_rows) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    if (ld_rhs < (rhs_layout == SPRS_HIP_ROW_MAJOR ? k : rhs_rows) || ld_out < (out_layout == SPRS_HIP_ROW_MAJOR ? k : out_rows))
+        SPRS_FAIL(SPRS_HIP_INVALID_ARG, "leading dimension smaller than the extent it strides over");
+    if (k && ((rhs_rows && !rhs_dev) || (out_rows && !out_dev))) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL matrix");
+    if (k && rhs_rows && out_rows) {   // the two operands must not share an ELEMENT: the rule of sprs_hip_csmat_mulacc_dense_f64, in floats
+        const uint64_t span_r = (rhs_layout == SPRS_HIP_ROW_MAJOR ? rhs_rows - 1 : k - 1) * ld_rhs + (rhs_layout == SPRS_HIP_ROW_MAJOR ? k : rhs_rows);
+        const uint64_t span_o = (out_layout == SPRS_HIP_ROW_MAJOR ? out_rows - 1 : k - 1) * ld_out + (out_layout == SPRS_HIP_ROW_MAJOR ? k : out_rows);
+        if (rhs_dev < out_dev + span_o && out_dev < rhs_dev + span_r) {
+            bool disjoint = false;
+            if (rhs_layout == out_layout && ld_rhs == ld_out) {
+                const uint64_t w_r = rhs_layout == SPRS_HIP_ROW_MAJOR ? k : rhs_rows, w_o = out_layout == SPRS_HIP_ROW_MAJOR ? k : out_rows;
+                const uint64_t d = rhs_dev <= out_dev ? (uint64_t)(out_dev - rhs_dev) % ld_rhs : (ld_rhs - (uint64_t)(rhs_dev - out_dev) % ld_rhs) % ld_rhs;
+                disjoint = d >= w_r && d + w_o <= ld_rhs;   // inside one pitch: rhs lines occupy [0, w_r), out lines [d, d + w_o)
+            }
+            if (!disjoint) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "the result matrix overlaps the right-hand side");
+        }
+    }
+    sprs_hip_csmat_f32 *csr = nullptr;
+    SPRS_TRY(csr_form_f32(lhs, &csr));
+    hipStream_t st = (hipStream_t)stream;
+    if (rhs_layout == SPRS_HIP_COL_MAJOR && out_layout == SPRS_HIP_COL_MAJOR && k < 8) {
+        // csr_mulacc_dense_colmaj's shape (fewer than 8 columns, csmat.rs:2017-2045): column by column through the SpMV
+        for (uint64_t j = 0; j < k; ++j) SPRS_TRY(spmv_f32(csr, rhs_dev + j * ld_rhs, out_dev + j * ld_out, accumulate != 0, st));
+        return SPRS_HIP_OK;
+    }
+    const uint64_t rs_r = rhs_layout == SPRS_HIP_ROW_MAJOR ? ld_rhs : 1, cs_r = rhs_layout == SPRS_HIP_ROW_MAJOR ? 1 : ld_rhs;
+    const uint64_t rs_o = out_layout == SPRS_HIP_ROW_MAJOR ? ld_out : 1, cs_o = out_layout == SPRS_HIP_ROW_MAJOR ? 1 : ld_out;
+    return spmm_strided_f32(csr, rhs_dev, k, rs_r, cs_r, out_dev, rs_o, cs_o, accumulate != 0, st);
+}
+
+int32_t sprs_hip_csmat_mul_dense_f32(const sprs_hip_csmat_f32 *lhs, const float *rhs_dev, uint64_t rhs_rows, uint64_t k,
+                                     int32_t rhs_layout, uint64_t ld_rhs, float *out_dev, int32_t *out_layout, void *stream) {
+    clear_error();
+    if (!lhs || !out_layout) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    // csmat.rs:2002-2045: Array::zeros((rows, cols)) for >= 8 columns, Array::zeros((rows, cols).f()) below — in both storages
+    const int32_t lay = k >= 8 ? SPRS_HIP_ROW_MAJOR : SPRS_HIP_COL_MAJOR;
+    *out_layout = lay;
+    return sprs_hip_csmat_mulacc_dense_f32(lhs, rhs_dev, rhs_rows, k, rhs_layout, ld_rhs, out_dev, lhs->rows, lay,
+                                           lay == SPRS_HIP_ROW_MAJOR ? k : lhs->rows, 0, stream);
+}
+
+int32_t sprs_hip_dense_dot_csmat_f32(const float *lhs_dev, uint64_t lhs_rows, uint64_t lhs_cols, int32_t lhs_layout, uint64_t ld_lhs,
+                                     const sprs_hip_csmat_f32 *rhs, float *out_dev, int32_t *out_layout, void *stream) {
+    clear_error();
+    if (!rhs || !out_layout) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    if (lhs_layout != SPRS_HIP_ROW_MAJOR && lhs_layout != SPRS_HIP_COL_MAJOR) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "bad layout tag");
+    // csmat.rs:2064-2117: (rhs^T * lhs^T)^T with free transposes.  The CSR form of rhs^T is the transpose view of a CSC rhs, or
+    // of the (cached) CSC copy of a CSR rhs; the view stays in the rhs handle under its lock, like t_view of the f64 handle
+    sprs_hip_csmat_f32 *owner = const_cast<sprs_hip_csmat_f32 *>(rhs);
+    std::lock_guard<std::recursive_mutex> lock(owner->mu);
+    if (!owner->t_view) {
+        const sprs_hip_csmat_f32 *src = rhs;
+        if (rhs->storage == SPRS_HIP_CSR) {
+            if (!owner->as_other) {
+                OwnedCsmatF32 other;
+                SPRS_TRY(csmat_f32_to_other_storage(rhs, other));
+                owner->as_other = other.release();
+                owner->as_other->prepared = owner->prepared;
+            }
+            src = owner->as_other;
+        }
+        owner->t_view = view_csmat_f32(src, true);
+    }
+    int32_t lay_t = 0;
+    // lhs^T: lhs_cols x lhs_rows, the other layout over the same memory
+    const int32_t st = sprs_hip_csmat_mul_dense_f32(owner->t_view, lhs_dev, lhs_cols, lhs_rows,
+                                                    lhs_layout == SPRS_HIP_ROW_MAJOR ? SPRS_HIP_COL_MAJOR : SPRS_HIP_ROW_MAJOR, ld_lhs, out_dev,
+                                                    &lay_t, stream);
+    if (st != SPRS_HIP_OK) return st;
+    *out_layout = lay_t == SPRS_HIP_ROW_MAJOR ? SPRS_HIP_COL_MAJOR : SPRS_HIP_ROW_MAJOR;     // reversed_axes()
+    return SPRS_HIP_OK;
+}
+
 }  // extern "C"
 
 // the pool and the handle constructors live in handle.hpp, compiled here so that the library and its emulator build (tests/emu,

@@ -94,6 +94,7 @@ constexpr bool DEVTOOLS = false;
     X(spgemm_mid, 65536, 0, 1ll << 31, 0) /* rows of <= 64 k's and at most this many products run one wave per row (0: none) */   \
     X(spgemm_ordered, 1, 0, 1, 0)       /* 1: products are added in the reference's order (values bit-identical to sprs'); 0: the waves of a large-row workgroup add as they arrive (LDS atomics: same products, rounding-level differences, not reproducible run to run; ~20 % faster kernel) */ \
     X(spmm_relayout, 0, 0, 2, 0)        /* SpMM stream kernel: gather from a copy of the rhs whose rows are scattered by a multiplicative hash inside blocks of 4096 rows (hub columns sit at 0, 2^k, 2^j + 2^k: their rhs rows would share a few L2 / fabric channels): 0 auto (a rhs of >= 256 MiB per column block under >= 24 entries per column whose row pitch is a power of two or leaves rows of < 16 columns across lines, or one that is not row-major), 1 on, 2 off */ \
+    X(spmm_f32_pair, 1, 0, 2, 0)        /* f32 SpMM stream kernel, paired lanes (a lane owns two adjacent columns, one 8-byte gather; needs a rhs with unit column stride, an even row pitch and an 8-byte aligned base, scalar lanes elsewhere): 1 auto = where eligible AND measured faster (column groups of 32 / 64, at least 8 entries per row); 2 wherever eligible; 0 scalar lanes always.  Same results up to the summation order */ \
     X(spmm_debug, 0, 0, 7, 1)           /* developer A/B of the stream kernel (right results): 1 plain instead of non-temporal entry loads, 2 plain result stores, 4 non-temporal rhs gathers */ \
     X(spgemm_debug, 0, 0, 15, 1)        /* TIMING EXPERIMENTS ONLY (wrong results): 1 no ordering of the adds, 2 no index emission, 4 no value stores and 8 no adds (wave-per-row kernel) */ \
     X(spgemm_occupancy, 3, 2, 3, 0)     /* workgroups per CU the large-row numeric kernel is compiled for: 3 (80 VGPRs) or 2 (128) */ \
@@ -450,6 +451,8 @@ struct sprs_hip_csmat_f32 {
     int device = 0;
     std::recursive_mutex mu;   // guards plan / as_other, like sprs_hip_csmat::mu
     sprs_hip::SpmvPlanF32 plan;
+    sprs_hip::SpmmPlan mm;     // the SpMM plan (spmm.hip): value-agnostic, the same struct as the f64 handle's
+    sprs_hip_csmat_f32 *t_view = nullptr;     // transpose view (of the CSC form) kept for dense . sparse products (sprs_hip_dense_dot_csmat_f32), like sprs_hip_csmat::t_view
     sprs_hip_csmat_f32 *as_other = nullptr;   // the handle in the other storage order: a CSC operand multiplies through its CSR form; dropped by refresh / free
 
     uint64_t outer() const { return storage == SPRS_HIP_CSR ? rows : cols; }
@@ -526,6 +529,8 @@ int32_t spmm_rowmaj_f64(sprs_hip_csmat *a, const double *rhs, uint64_t k, uint64
                         uint64_t ld_out, bool accumulate, hipStream_t stream);
 int32_t spmm_strided_f64(sprs_hip_csmat *a, const double *rhs, uint64_t k, uint64_t rs_rhs, uint64_t cs_rhs, double *out,
                          uint64_t rs_out, uint64_t cs_out, bool accumulate, hipStream_t stream);
+int32_t spmm_strided_f32(sprs_hip_csmat_f32 *a, const float *rhs, uint64_t k, uint64_t rs_rhs, uint64_t cs_rhs, float *out,
+                         uint64_t rs_out, uint64_t cs_out, bool accumulate, hipStream_t stream);   // kernels: spmm_f32.hpp
 // dist.hip
 int32_t dist_unique_id(void *id128);
 int32_t dist_create(sprs_hip_dist **out, const void *unique_id128, int32_t world, int32_t rank, uint64_t rows, uint64_t cols,

@@ -298,6 +298,9 @@ void invalidate_caches(sprs_hip_csmat *m) {
 
 void invalidate_caches(sprs_hip_csmat_f32 *m) {
     m->plan = SpmvPlanF32();
+    m->mm = SpmmPlan();
+    delete m->t_view;
+    m->t_view = nullptr;
     delete m->as_other;
     m->as_other = nullptr;
 }
@@ -306,7 +309,7 @@ void invalidate_caches(sprs_hip_csmat_f32 *m) {
 
 sprs_hip_csmat_f32::~sprs_hip_csmat_f32() {
     // as for the f64 handle: a kernel in flight may still read the tile index, a carry array or the CSR copy
-    if (as_other || plan.built) (void)hipDeviceSynchronize();
+    if (t_view || as_other || plan.built || mm.built) (void)hipDeviceSynchronize();
     sprs_hip::invalidate_caches(this);
 }
 

@@ -21,6 +21,8 @@
 //    into one accumulator per column — the reference's own order, bit for bit, the accumulate form included.  Measured
 //    3.4x slower than the chunks (41 ms at k = 16, profiles/r03f), hence opt-in for callers that need the reference's bits.
 // Unfused multiply-add (-ffp-contract=off) like MulAcc (mul_acc.rs:28-30).
+// An f32 handle (sprs_hip_csmat_f32) runs the same three decompositions: the plan pieces and the host code below serve both
+// handle types, the row-walking kernels are templates on the scalar, the f32 entry stream lives in spmm_f32.hpp.
 #include "common.hpp"
 #include "scan.hpp"
 
@@ -56,12 +58,13 @@ __global__ void fill_chunks_kernel(const uint64_t *__restrict__ first_chunk, con
     if (n > 1) multi_rows[multi_pos[r]] = r;
 }
 
-// rows of at most LONG_ROW entries: one group of KP lanes per row at a time (see the header)
-template <typename IDX, typename PTR, int KP, bool ACC>
+// rows of at most LONG_ROW entries: one group of KP lanes per row at a time (see the header).  This kernel, the chunk kernel and
+// the combine pass are templates on the scalar T (double, or float for an f32 handle: spmm_f32.hpp holds the f32 entry stream)
+template <typename T, typename IDX, typename PTR, int KP, bool ACC>
 __global__ __launch_bounds__(MM_BLOCK) void spmm_rows_kernel(const PTR *__restrict__ indptr, const IDX *__restrict__ indices,
-                                                             const double *__restrict__ data, uint64_t rows,
-                                                             const double *__restrict__ rhs, uint64_t ld_rhs, uint64_t cs_rhs, uint32_t k,
-                                                             double *__restrict__ out, uint64_t ld_out, uint64_t cs_out, uint64_t long_row) {
+                                                             const T *__restrict__ data, uint64_t rows,
+                                                             const T *__restrict__ rhs, uint64_t ld_rhs, uint64_t cs_rhs, uint32_t k,
+                                                             T *__restrict__ out, uint64_t ld_out, uint64_t cs_out, uint64_t long_row) {
     constexpr int EB = KP <= 16 ? 32 / KP : 1;           // entries a lane loads per turn
     constexpr int NB = EB * KP;                          // entries of a turn (32, or KP)
     constexpr int UN = NB < 32 ? NB : 32;                // rhs rows in flight per group
@@ -71,7 +74,7 @@ __global__ __launch_bounds__(MM_BLOCK) void spmm_rows_kernel(const PTR *__restri
     uint64_t r = ((uint64_t)blockIdx.x * MM_BLOCK + threadIdx.x) / KP;
     bool active = r < rows, mine = false;
     uint64_t cur = 0, end = 0, ncur = 0, nend = 0;
-    double acc = 0.0;
+    T acc = T(0);
     if (active) {
         cur = (uint64_t)indptr[r];
         end = (uint64_t)indptr[r + 1];
@@ -87,30 +90,30 @@ __global__ __launch_bounds__(MM_BLOCK) void spmm_rows_kernel(const PTR *__restri
     while (__ballot(active) != 0ull) {
         const uint32_t nb = active ? (uint32_t)(end - cur < (uint64_t)NB ? end - cur : (uint64_t)NB) : 0u;
         uint64_t col[EB];
-        double val[EB];
+        T val[EB];
 #pragma unroll
         for (int e = 0; e < EB; ++e) {
             const uint32_t t = (uint32_t)e * KP + j;
             const bool ok = t < nb;
             col[e] = ok ? (uint64_t)indices[cur + t] : 0ull;
-            val[e] = ok ? data[cur + t] : 0.0;
+            val[e] = ok ? data[cur + t] : T(0);
         }
 #pragma unroll
         for (int t0 = 0; t0 < NB; t0 += UN) {
             if (__ballot((uint32_t)t0 < nb) == 0ull) break;            // wave-uniform
-            double x[UN];
+            T x[UN];
 #pragma unroll
             for (int u = 0; u < UN; ++u) {
                 const int t = t0 + u;
                 // (an entry past the end reads rhs row 0 and is not added: no branch in the load sequence)
                 const uint64_t c = __shfl(col[t / KP], t % KP, KP);
-                x[u] = col_ok ? rhs[c * ld_rhs + j * cs_rhs] : 0.0;
+                x[u] = col_ok ? rhs[c * ld_rhs + j * cs_rhs] : T(0);
             }
 #pragma unroll
             for (int u = 0; u < UN; ++u) {
                 const int t = t0 + u;
-                const double v = __shfl(val[t / KP], t % KP, KP);
-                const double sum = acc + v * x[u];
+                const T v = __shfl(val[t / KP], t % KP, KP);
+                const T sum = acc + v * x[u];
                 acc = (uint32_t)t < nb ? sum : acc;
             }
         }
@@ -121,7 +124,7 @@ __global__ __launch_bounds__(MM_BLOCK) void spmm_rows_kernel(const PTR *__restri
             active = r < rows;
             cur = ncur;
             end = nend;
-            acc = 0.0;
+            acc = T(0);
             if (active) {
                 mine = end - cur <= long_row;
                 if (!mine) cur = end;
@@ -136,15 +139,15 @@ __global__ __launch_bounds__(MM_BLOCK) void spmm_rows_kernel(const PTR *__restri
     }
 }
 
-template <typename IDX, typename PTR, int KP, bool ACC>
+template <typename T, typename IDX, typename PTR, int KP, bool ACC>
 __global__ __launch_bounds__(MM_BLOCK) void spmm_chunk_kernel(const PTR *__restrict__ indptr,
                                                               const IDX *__restrict__ indices,
-                                                              const double *__restrict__ data,
+                                                              const T *__restrict__ data,
                                                               const uint64_t *__restrict__ chunk_row,
                                                               const uint64_t *__restrict__ first_chunk,
-                                                              uint64_t nchunks, const double *__restrict__ rhs,
-                                                              uint64_t ld_rhs, uint64_t cs_rhs, uint32_t k, double *__restrict__ out,
-                                                              uint64_t ld_out, uint64_t cs_out, double *__restrict__ partial) {
+                                                              uint64_t nchunks, const T *__restrict__ rhs,
+                                                              uint64_t ld_rhs, uint64_t cs_rhs, uint32_t k, T *__restrict__ out,
+                                                              uint64_t ld_out, uint64_t cs_out, T *__restrict__ partial) {
     constexpr int G = WAVE / KP;                       // entries processed concurrently by one wave
     const uint32_t lane = threadIdx.x & (WAVE - 1);
     const uint32_t j = lane % KP, g = lane / KP;
@@ -156,22 +159,22 @@ __global__ __launch_bounds__(MM_BLOCK) void spmm_chunk_kernel(const PTR *__restr
         const uint64_t rs = (uint64_t)indptr[r], re = (uint64_t)indptr[r + 1];
         const uint64_t s = rs + (c - f) * CHUNK;
         const uint64_t e = (s + CHUNK < re) ? s + CHUNK : re;
-        double acc = 0.0;
+        T acc = T(0);
         if (j < k) {
             for (uint64_t p = s + g; p < e; p += 4 * G) {              // four rhs rows in flight; added in the order g, g + G, ...
                 uint64_t col[4];
-                double a[4], x[4];
+                T a[4], x[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const bool ok = p + (uint64_t)u * G < e;
                     col[u] = ok ? (uint64_t)indices[p + (uint64_t)u * G] : 0ull;
-                    a[u] = ok ? data[p + (uint64_t)u * G] : 0.0;
+                    a[u] = ok ? data[p + (uint64_t)u * G] : T(0);
                 }
 #pragma unroll
                 for (int u = 0; u < 4; ++u) x[u] = rhs[col[u] * ld_rhs + j * cs_rhs];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
-                    const double sum = acc + a[u] * x[u];
+                    const T sum = acc + a[u] * x[u];
                     acc = p + (uint64_t)u * G < e ? sum : acc;
                 }
             }
@@ -180,7 +183,7 @@ __global__ __launch_bounds__(MM_BLOCK) void spmm_chunk_kernel(const PTR *__restr
         for (int o = KP; o < WAVE; o <<= 1) acc += __shfl_xor(acc, o, WAVE);
         if (g == 0 && j < k) {
             if (nc == 1) {
-                double *dst = out + r * ld_out + j * cs_out;
+                T *dst = out + r * ld_out + j * cs_out;
                 if constexpr (ACC) *dst = *dst + acc;
                 else *dst = acc;
             } else {
@@ -191,18 +194,18 @@ __global__ __launch_bounds__(MM_BLOCK) void spmm_chunk_kernel(const PTR *__restr
 }
 
 // rows longer than one chunk: add the chunk partials in chunk order
-template <bool ACC>
+template <typename T, bool ACC>
 __global__ void spmm_combine_kernel(const uint64_t *__restrict__ multi_rows, uint64_t n_multi,
-                                    const uint64_t *__restrict__ first_chunk, const double *__restrict__ partial,
-                                    uint32_t k, double *__restrict__ out, uint64_t ld_out, uint64_t cs_out) {
+                                    const uint64_t *__restrict__ first_chunk, const T *__restrict__ partial,
+                                    uint32_t k, T *__restrict__ out, uint64_t ld_out, uint64_t cs_out) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_multi * k) return;
     const uint64_t r = multi_rows[t / k];
     const uint32_t j = (uint32_t)(t % k);
     const uint64_t f = first_chunk[r], n = first_chunk[r + 1] - f;
-    double s = 0.0;
+    T s = T(0);
     for (uint64_t c = 0; c < n; ++c) s += partial[(f + c) * (uint64_t)k + j];
-    double *dst = out + r * ld_out + j * cs_out;
+    T *dst = out + r * ld_out + j * cs_out;
     if constexpr (ACC) *dst = *dst + s;
     else *dst = s;
 }
@@ -480,8 +483,25 @@ __global__ __launch_bounds__(MM_BLOCK) void spmm_stream_fixup_kernel(const PTR *
     }
 }
 
-template <typename PTR>
-int32_t build_spmm_plan(sprs_hip_csmat *a, bool stream_mode, hipStream_t stream) {
+}  // namespace
+
+}  // namespace sprs_hip
+
+// single precision: the f32 entry-stream kernels (both lane forms), their fix-up and re-layout copy
+#include "spmm_f32.hpp"
+
+namespace sprs_hip {
+
+namespace {
+
+// The host code below serves both handle types: H = sprs_hip_csmat (T = double) or sprs_hip_csmat_f32 (T = float).  The plan
+// pieces are value-agnostic; the row-walking kernels are templates on T; the entry stream is spmm_stream_kernel for double and
+// spmm_stream_f32_kernel for float.
+template <typename H>
+using scalar_of = std::remove_pointer_t<decltype(H::data)>;
+
+template <typename PTR, typename H>
+int32_t build_spmm_plan(H *a, bool stream_mode, hipStream_t stream) {
     SpmmPlan &pl = a->mm;
     pl = SpmmPlan();
     pl.long_row = options().spmm_long_row >= 0 ? (uint64_t)options().spmm_long_row : LONG_ROW;
@@ -520,8 +540,8 @@ int32_t build_spmm_plan(sprs_hip_csmat *a, bool stream_mode, hipStream_t stream)
 }
 
 // rows of at most long_row entries (the empty ones among them): the lane-group kernel
-template <typename IDX, typename PTR, int KP>
-int32_t launch_short_rows(sprs_hip_csmat *a, const double *rhs, uint64_t ld_rhs, uint64_t cs_rhs, uint32_t k, double *out, uint64_t ld_out,
+template <typename IDX, typename PTR, int KP, typename H, typename T>
+int32_t launch_short_rows(H *a, const T *rhs, uint64_t ld_rhs, uint64_t cs_rhs, uint32_t k, T *out, uint64_t ld_out,
                           uint64_t cs_out, bool acc, uint64_t long_row, hipStream_t stream) {
     // groups of KP lanes, group-stride; enough workgroups to fill the chip eight deep
     constexpr uint64_t groups_per_block = MM_BLOCK / KP;
@@ -529,10 +549,10 @@ int32_t launch_short_rows(sprs_hip_csmat *a, const double *rhs, uint64_t ld_rhs,
     if (blocks > 256 * 8) blocks = 256 * 8;
     const dim3 grid((unsigned)blocks), block(MM_BLOCK);
     if (acc)
-        hipLaunchKernelGGL((spmm_rows_kernel<IDX, PTR, KP, true>), grid, block, 0, stream, (const PTR *)a->indptr,
+        hipLaunchKernelGGL((spmm_rows_kernel<T, IDX, PTR, KP, true>), grid, block, 0, stream, (const PTR *)a->indptr,
                            (const IDX *)a->indices, a->data, a->rows, rhs, ld_rhs, cs_rhs, k, out, ld_out, cs_out, long_row);
     else
-        hipLaunchKernelGGL((spmm_rows_kernel<IDX, PTR, KP, false>), grid, block, 0, stream, (const PTR *)a->indptr,
+        hipLaunchKernelGGL((spmm_rows_kernel<T, IDX, PTR, KP, false>), grid, block, 0, stream, (const PTR *)a->indptr,
                            (const IDX *)a->indices, a->data, a->rows, rhs, ld_rhs, cs_rhs, k, out, ld_out, cs_out, long_row);
     SPRS_TRY_HIP(hipGetLastError());
     return SPRS_HIP_OK;
@@ -572,9 +592,16 @@ int32_t launch_stream(sprs_hip_csmat *a, const double *rhs, uint64_t ld_rhs, uin
     return SPRS_HIP_OK;
 }
 
+// (an f32 handle: the kernels of spmm_f32.hpp)
 template <typename IDX, typename PTR, int KP>
-int32_t launch_block(sprs_hip_csmat *a, const double *rhs, uint64_t ld_rhs, uint64_t cs_rhs, uint32_t k, double *out, uint64_t ld_out,
-                     uint64_t cs_out, bool acc, double *partial, hipStream_t stream) {
+int32_t launch_stream(sprs_hip_csmat_f32 *a, const float *rhs, uint64_t ld_rhs, uint64_t cs_rhs, uint32_t k, float *out, uint64_t ld_out,
+                      uint64_t cs_out, bool acc, float *carry, float *relaid, hipStream_t stream) {
+    return launch_stream_f32<IDX, PTR, KP>(a, rhs, ld_rhs, cs_rhs, k, out, ld_out, cs_out, acc, carry, relaid, stream);
+}
+
+template <typename IDX, typename PTR, int KP, typename H, typename T>
+int32_t launch_block(H *a, const T *rhs, uint64_t ld_rhs, uint64_t cs_rhs, uint32_t k, T *out, uint64_t ld_out,
+                     uint64_t cs_out, bool acc, T *partial, hipStream_t stream) {
     const SpmmPlan &pl = a->mm;
     SPRS_TRY((launch_short_rows<IDX, PTR, KP>(a, rhs, ld_rhs, cs_rhs, k, out, ld_out, cs_out, acc, pl.long_row, stream)));
     if (!pl.nchunks) return SPRS_HIP_OK;
@@ -582,11 +609,11 @@ int32_t launch_block(sprs_hip_csmat *a, const double *rhs, uint64_t ld_rhs, uint
     if (blocks > 256 * 64) blocks = 256 * 64;
     const dim3 grid((unsigned)blocks), block(MM_BLOCK);
     if (acc)
-        hipLaunchKernelGGL((spmm_chunk_kernel<IDX, PTR, KP, true>), grid, block, 0, stream, (const PTR *)a->indptr,
+        hipLaunchKernelGGL((spmm_chunk_kernel<T, IDX, PTR, KP, true>), grid, block, 0, stream, (const PTR *)a->indptr,
                            (const IDX *)a->indices, a->data, pl.chunk_row, pl.first_chunk, pl.nchunks, rhs, ld_rhs, cs_rhs, k,
                            out, ld_out, cs_out, partial);
     else
-        hipLaunchKernelGGL((spmm_chunk_kernel<IDX, PTR, KP, false>), grid, block, 0, stream, (const PTR *)a->indptr,
+        hipLaunchKernelGGL((spmm_chunk_kernel<T, IDX, PTR, KP, false>), grid, block, 0, stream, (const PTR *)a->indptr,
                            (const IDX *)a->indices, a->data, pl.chunk_row, pl.first_chunk, pl.nchunks, rhs, ld_rhs, cs_rhs, k,
                            out, ld_out, cs_out, partial);
     SPRS_TRY_HIP(hipGetLastError());
@@ -594,20 +621,21 @@ int32_t launch_block(sprs_hip_csmat *a, const double *rhs, uint64_t ld_rhs, uint
         const uint64_t th = pl.n_multi * k;
         const dim3 g2((unsigned)((th + 255) / 256)), b2(256);
         if (acc)
-            hipLaunchKernelGGL(spmm_combine_kernel<true>, g2, b2, 0, stream, pl.multi_rows, pl.n_multi, pl.first_chunk,
+            hipLaunchKernelGGL((spmm_combine_kernel<T, true>), g2, b2, 0, stream, pl.multi_rows, pl.n_multi, pl.first_chunk,
                                partial, k, out, ld_out, cs_out);
         else
-            hipLaunchKernelGGL(spmm_combine_kernel<false>, g2, b2, 0, stream, pl.multi_rows, pl.n_multi, pl.first_chunk,
+            hipLaunchKernelGGL((spmm_combine_kernel<T, false>), g2, b2, 0, stream, pl.multi_rows, pl.n_multi, pl.first_chunk,
                                partial, k, out, ld_out, cs_out);
         SPRS_TRY_HIP(hipGetLastError());
     }
     return SPRS_HIP_OK;
 }
 
-template <typename IDX, typename PTR>
-int32_t spmm_impl(sprs_hip_csmat *a, const double *rhs, uint64_t k, uint64_t ld_rhs, uint64_t cs_rhs, double *out, uint64_t ld_out,
+template <typename IDX, typename PTR, typename H, typename T>
+int32_t spmm_impl(H *a, const T *rhs, uint64_t k, uint64_t ld_rhs, uint64_t cs_rhs, T *out, uint64_t ld_out,
                   uint64_t cs_out, bool acc, hipStream_t stream) {
-    double *partial = nullptr, *relaid = nullptr;
+    static_assert(std::is_same_v<T, scalar_of<H>>, "the operands have the handle's scalar");
+    T *partial = nullptr, *relaid = nullptr;
     std::lock_guard<std::recursive_mutex> lock(a->mu);   // held until the kernels that read the plan are launched
     const uint64_t want_long = options().spmm_long_row >= 0 ? (uint64_t)options().spmm_long_row : LONG_ROW;
     // the entry stream keeps 32-bit column ids in LDS; the lane-group mode (reference bits for short rows) has its own kernels
@@ -617,20 +645,20 @@ int32_t spmm_impl(sprs_hip_csmat *a, const double *rhs, uint64_t k, uint64_t ld_
     // column — with many more rows than entries that is a cliff.  The result is cleared in one piece instead and
     // the accumulate kernels run on it: +0.0 + products, the same bits as starting from zero.
     if (!acc && stream_mode && a->rows > 4 * a->nnz + 4096 && k && (cs_out == 1 || ld_out == 1)) {
-        if (cs_out == 1 && ld_out == k) SPRS_TRY_HIP(hipMemsetAsync(out, 0, a->rows * k * sizeof(double), stream));
-        else if (ld_out == 1 && cs_out == a->rows) SPRS_TRY_HIP(hipMemsetAsync(out, 0, a->rows * k * sizeof(double), stream));
-        else if (cs_out == 1) SPRS_TRY_HIP(hipMemset2DAsync(out, ld_out * sizeof(double), 0, k * sizeof(double), a->rows, stream));
-        else SPRS_TRY_HIP(hipMemset2DAsync(out, cs_out * sizeof(double), 0, a->rows * sizeof(double), k, stream));
+        if (cs_out == 1 && ld_out == k) SPRS_TRY_HIP(hipMemsetAsync(out, 0, a->rows * k * sizeof(T), stream));
+        else if (ld_out == 1 && cs_out == a->rows) SPRS_TRY_HIP(hipMemsetAsync(out, 0, a->rows * k * sizeof(T), stream));
+        else if (cs_out == 1) SPRS_TRY_HIP(hipMemset2DAsync(out, ld_out * sizeof(T), 0, k * sizeof(T), a->rows, stream));
+        else SPRS_TRY_HIP(hipMemset2DAsync(out, cs_out * sizeof(T), 0, a->rows * sizeof(T), k, stream));
         acc = true;
     }
     {
-        if (!a->mm.built || a->mm.long_row != want_long || a->mm.stream != stream_mode) SPRS_TRY(build_spmm_plan<PTR>(a, stream_mode, stream));
+        if (!a->mm.built || a->mm.long_row != want_long || a->mm.stream != stream_mode) SPRS_TRY((build_spmm_plan<PTR, H>(a, stream_mode, stream)));
         SpmmPlan &pl = a->mm;
         const uint64_t kb = k < 64 ? k : 64;
-        const uint64_t need = (stream_mode ? 2 * pl.ntiles : pl.n_multi ? pl.nchunks : 0) * kb * sizeof(double);
+        const uint64_t need = (stream_mode ? 2 * pl.ntiles : pl.n_multi ? pl.nchunks : 0) * kb * sizeof(T);
         DevBuf &slot = pl.partial[(void *)stream];
         SPRS_TRY_HIP(slot.reserve(need));
-        partial = slot.as<double>();
+        partial = slot.template as<T>();
         // the re-laid-out copy of the rhs (option spmm_relayout; auto: a rhs that is not row-major — a column of it is a separate
         // line per entry — or one of 256 MiB and more per column block with 24 and more gathers per row to pay for the copy:
         // R-MAT 4M x 32 2.55 -> 2.20 ms at k = 16, 1M x 16 0.32 -> 0.38 ms, profiles/r11zc)
@@ -638,17 +666,18 @@ int32_t spmm_impl(sprs_hip_csmat *a, const double *rhs, uint64_t k, uint64_t ld_
         // bytes — k = 24, 48 — spreads the hub rows by itself: 10.7 ms in place against 15.5 ms at k = 32, and the copy only costs
         // there, profiles/r12b), or rows of fewer than 16 columns that straddle lines (k = 12: 96-byte rows; the copy's pitch is 128)
         const int64_t rl = options().spmm_relayout;
-        const bool big = a->cols * kb * sizeof(double) >= (256ull << 20) && a->nnz >= 24 * a->cols;
-        const bool pitch = (ld_rhs & (ld_rhs - 1)) == 0 || (kb < 16 && (ld_rhs * sizeof(double)) % 128 != 0);
+        const bool big = a->cols * kb * sizeof(T) >= (256ull << 20) && a->nnz >= 24 * a->cols;
+        // (rows shorter than a line: fewer than 16 doubles, fewer than 32 floats)
+        const bool pitch = (ld_rhs & (ld_rhs - 1)) == 0 || (kb * sizeof(T) < 128 && (ld_rhs * sizeof(T)) % 128 != 0);
         const bool want = stream_mode && (rl == 1 || (rl == 0 && (cs_rhs != 1 || (big && pitch))));
         if (want) {
             const uint64_t rows_pad = (a->cols + RL_MASK) & ~(uint64_t)RL_MASK;
             const uint64_t kp = kb <= 8 ? 8 : kb <= 16 ? 16 : kb <= 32 ? 32 : 64;
-            const uint64_t bytes = rows_pad * kp * sizeof(double);
+            const uint64_t bytes = rows_pad * kp * sizeof(T);
             DevBuf &rs = pl.relaid[(void *)stream];
             // (no room for a second copy of the rhs: the kernel gathers from the caller's, as with spmm_relayout = 2)
             if (rs.reserve(bytes) != hipSuccess) (void)hipGetLastError();
-            relaid = rs.as<double>();
+            relaid = rs.template as<T>();
         }
     }
     if (a->nnz == 0) {
@@ -656,18 +685,18 @@ int32_t spmm_impl(sprs_hip_csmat *a, const double *rhs, uint64_t k, uint64_t ld_
         if (!acc) {
             // (one row or one column is contiguous whatever the other stride says: the column-major 1 x k result of the operator
             // form has cs_out == rows == 1 and ld_out == 1, which is no pitch for rows of k doubles)
-            if (cs_out == 1 && (ld_out == k || a->rows == 1)) SPRS_TRY_HIP(hipMemsetAsync(out, 0, a->rows * k * sizeof(double), stream));
-            else if (ld_out == 1 && (cs_out == a->rows || k == 1)) SPRS_TRY_HIP(hipMemsetAsync(out, 0, a->rows * k * sizeof(double), stream));
-            else if (cs_out == 1) SPRS_TRY_HIP(hipMemset2DAsync(out, ld_out * sizeof(double), 0, k * sizeof(double), a->rows, stream));
-            else SPRS_TRY_HIP(hipMemset2DAsync(out, cs_out * sizeof(double), 0, a->rows * sizeof(double), k, stream));   // column-major: k columns of `rows` doubles
+            if (cs_out == 1 && (ld_out == k || a->rows == 1)) SPRS_TRY_HIP(hipMemsetAsync(out, 0, a->rows * k * sizeof(T), stream));
+            else if (ld_out == 1 && (cs_out == a->rows || k == 1)) SPRS_TRY_HIP(hipMemsetAsync(out, 0, a->rows * k * sizeof(T), stream));
+            else if (cs_out == 1) SPRS_TRY_HIP(hipMemset2DAsync(out, ld_out * sizeof(T), 0, k * sizeof(T), a->rows, stream));
+            else SPRS_TRY_HIP(hipMemset2DAsync(out, cs_out * sizeof(T), 0, a->rows * sizeof(T), k, stream));   // column-major: k columns of `rows` doubles
         }
         return SPRS_HIP_OK;
     }
     // every row is written by exactly one kernel (an empty row as zeros): no memset of `out`
     for (uint64_t j0 = 0; j0 < k; j0 += 64) {          // column blocks of 64
         const uint32_t kb = (uint32_t)(k - j0 < 64 ? k - j0 : 64);
-        const double *r = rhs + j0 * cs_rhs;
-        double *o = out + j0 * cs_out;
+        const T *r = rhs + j0 * cs_rhs;
+        T *o = out + j0 * cs_out;
         int32_t st;
         if (stream_mode) {
             if (kb <= 8) st = launch_stream<IDX, PTR, 8>(a, r, ld_rhs, cs_rhs, kb, o, ld_out, cs_out, acc, partial, relaid, stream);
@@ -689,6 +718,15 @@ int32_t spmm_impl(sprs_hip_csmat *a, const double *rhs, uint64_t k, uint64_t ld_
 // operands have cs = 1, column-major ones rs = 1.  One kernel family serves the four layout pairs `&CsMat * &Array2` can meet
 // (csmat.rs:1989-2048: the result is row-major for >= 8 columns, column-major below, whatever the rhs is).
 int32_t spmm_strided_f64(sprs_hip_csmat *a, const double *rhs, uint64_t k, uint64_t rs_rhs, uint64_t cs_rhs, double *out,
+                         uint64_t rs_out, uint64_t cs_out, bool accumulate, hipStream_t stream) {
+    if (a->rows == 0 || k == 0) return SPRS_HIP_OK;
+    return dispatch_widths(a->idx_bytes, a->iptr_bytes, [&](auto i, auto p) {
+        return spmm_impl<typename decltype(i)::type, typename decltype(p)::type>(a, rhs, k, rs_rhs, cs_rhs, out, rs_out, cs_out, accumulate, stream);
+    });
+}
+
+// the same for an f32 handle and float operands
+int32_t spmm_strided_f32(sprs_hip_csmat_f32 *a, const float *rhs, uint64_t k, uint64_t rs_rhs, uint64_t cs_rhs, float *out,
                          uint64_t rs_out, uint64_t cs_out, bool accumulate, hipStream_t stream) {
     if (a->rows == 0 || k == 0) return SPRS_HIP_OK;
     return dispatch_widths(a->idx_bytes, a->iptr_bytes, [&](auto i, auto p) {

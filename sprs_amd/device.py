@@ -397,6 +397,8 @@ class DeviceCsMat:
             return prod.csmat_mul_csmat(self, rhs)        # csmat.rs:1866-1949
         if isinstance(rhs, prod.DeviceMat):
             return prod.csmat_mul_dense(self, rhs)        # csmat.rs:1989-2048
+        if isinstance(rhs, prod.DeviceMatF32):
+            raise TypeError("an f64 matrix times an f32 dense matrix: convert one operand (DeviceCsMat.to_f32)")
         if isinstance(rhs, (float, np.floating)):
             from . import binop
             return binop.scale(self, rhs)                 # binop.rs:132-163
@@ -439,7 +441,8 @@ class DeviceCsMat:
 
 class DeviceCsMatF32:
     """A CSR/CSC matrix of f32 values in HBM behind a `sprs_hip_csmat_f32*` handle: CsMat<f32>.  Built for it: the container,
-    `&A * &x` and the two mul_acc forms with DeviceVecF32 (prod.py), BiCGSTAB (linalg.py); `to_f64()` reaches every other
+    `&A * &x` and the two mul_acc forms with DeviceVecF32, `&A * &B` and the four mulacc_dense forms with prod.DeviceMatF32,
+    prod.dense_dot_csmat (prod.py), BiCGSTAB (linalg.py); `to_f64()` reaches every other
     operation.  Index arrays are 4 or 8 bytes wide (no 2-byte ones)."""
 
     def __init__(self, handle, keep=None):
@@ -544,6 +547,10 @@ class DeviceCsMatF32:
             return prod.csmat_mul_vec(self, rhs)
         if isinstance(rhs, DeviceVec):
             raise TypeError("an f32 matrix times an f64 vector: convert one operand (DeviceCsMatF32.to_f64)")
+        if isinstance(rhs, prod.DeviceMatF32):
+            return prod.csmat_mul_dense(self, rhs)        # csmat.rs:1989-2048
+        if isinstance(rhs, prod.DeviceMat):
+            raise TypeError("an f32 matrix times an f64 dense matrix: convert one operand (DeviceCsMatF32.to_f64)")
         return NotImplemented
 
     __matmul__ = __mul__

@@ -47,9 +47,14 @@ def mul_acc_mat_vec_csc(mat, in_vec, res_vec, stream=None):
                                                _stream_ptr(stream)))
 
 
-class DeviceMat:
-    """Dense f64 matrix in HBM in one of ndarray's two contiguous layouts: `Array2` in standard (row-major) order, or
-    `Array::zeros(shape.f())` (column-major) — what `&CsMat * &Array2` returns for fewer than 8 columns (csmat.rs:2017-2024)."""
+class _DenseMat:
+    """What DeviceMat and DeviceMatF32 share: a dense matrix in HBM in one of ndarray's two contiguous layouts.  The two are
+    SIBLINGS, not parent and child: an isinstance test for one never admits the other."""
+    _np_dtype = None
+
+    @staticmethod
+    def _vec_type():
+        raise NotImplementedError
 
     def __init__(self, rows, cols, vec=None, col_major=False, ld=None):
         """ld: the leading dimension in elements (None: contiguous) — the lines of the matrix are ld apart in `vec`, which then
@@ -58,24 +63,26 @@ class DeviceMat:
         self._ld = None if ld is None else int(ld)
         lines = self.cols if self.col_major else self.rows
         want = self.rows * self.cols if self._ld is None else lines * self._ld
-        self.vec = vec if vec is not None else DeviceVec.zeros(want)
+        self.vec = vec if vec is not None else self._vec_type().zeros(want)
+        if not isinstance(self.vec, self._vec_type()):
+            raise TypeError("%s holds a %s, not a %s" % (type(self).__name__, self._vec_type().__name__, type(self.vec).__name__))
         assert self.vec.n == want
 
     @classmethod
     def from_host(cls, arr, col_major=False, ld=None, fill=0.0):
         """ld: pad every line to ld elements; the padding holds `fill` (a float, or an array of lines x (ld - width))"""
         import numpy as np
-        arr = np.asarray(arr, dtype=np.float64)
+        arr = np.asarray(arr, dtype=cls._np_dtype)
         if ld is not None:
             lines = arr.T if col_major else arr
             if int(ld) < lines.shape[1]:
                 raise _ffi.SprsHipError(_ffi.INVALID_ARG, "leading dimension smaller than the extent it strides over")
-            buf = np.empty((lines.shape[0], int(ld)), dtype=np.float64)
+            buf = np.empty((lines.shape[0], int(ld)), dtype=cls._np_dtype)
             buf[:, lines.shape[1]:] = fill
             buf[:, :lines.shape[1]] = lines
-            return cls(arr.shape[0], arr.shape[1], DeviceVec.from_host(buf.reshape(-1)), col_major, ld)
+            return cls(arr.shape[0], arr.shape[1], cls._vec_type().from_host(buf.reshape(-1)), col_major, ld)
         flat = np.asfortranarray(arr).reshape(-1, order="F") if col_major else np.ascontiguousarray(arr).reshape(-1)
-        return cls(arr.shape[0], arr.shape[1], DeviceVec.from_host(np.ascontiguousarray(flat)), col_major)
+        return cls(arr.shape[0], arr.shape[1], cls._vec_type().from_host(np.ascontiguousarray(flat)), col_major)
 
     def to_host(self):
         flat = self.vec.to_host()
@@ -96,16 +103,50 @@ class DeviceMat:
         return self.rows if self.col_major else self.cols
 
 
+class DeviceMat(_DenseMat):
+    """Dense f64 matrix in HBM in one of ndarray's two contiguous layouts: `Array2` in standard (row-major) order, or
+    `Array::zeros(shape.f())` (column-major) — what `&CsMat * &Array2` returns for fewer than 8 columns (csmat.rs:2017-2024)."""
+    _np_dtype = "float64"
+
+    @staticmethod
+    def _vec_type():
+        return DeviceVec
+
+
+class DeviceMatF32(_DenseMat):
+    """Dense f32 matrix in HBM over a DeviceVecF32: the operand and result type of the dense products of a DeviceCsMatF32.
+    Constructor, from_host (casts to float32), to_host, layout, ld, padding and fill as DeviceMat."""
+    _np_dtype = "float32"
+
+    @staticmethod
+    def _vec_type():
+        from .device import DeviceVecF32
+        return DeviceVecF32
+
+
+def _is_f32_dense(mat, *dense):
+    """True for a DeviceCsMatF32 with DeviceMatF32 operands, False for the f64 classes; any mix raises TypeError before the
+    library is called (as _is_f32 for the vectors)"""
+    from .device import DeviceCsMatF32
+    f32 = isinstance(mat, DeviceCsMatF32)
+    for d in dense:
+        if isinstance(d, DeviceMatF32) != f32:
+            raise TypeError("matrix and dense operands must have the same precision: %s with %s" % (type(mat).__name__, type(d).__name__))
+    return f32
+
+
 def _dims(lhs, rhs, out):
     """the three dimension asserts of the four dense kernels come FIRST, the storage assert last (prod.rs:199-202, 228-231,
     256-259, 284-288): with both wrong every mirror reports the dimensions"""
+    _is_f32_dense(lhs, rhs, out)       # a mix of precisions is a TypeError, whatever the shapes are
     if rhs.cols != out.cols or lhs.cols() != rhs.rows or lhs.rows() != out.rows:
         raise _ffi.SprsHipError(_ffi.DIM_MISMATCH, "Dimension mismatch")
 
 
 def _mulacc_dense(lhs, rhs, out, stream):
-    check(lib.sprs_hip_csmat_mulacc_dense_f64(lhs._h, C.c_void_p(rhs.vec.ptr), rhs.rows, rhs.cols, rhs.layout, rhs.ld,
-                                              C.c_void_p(out.vec.ptr), out.rows, out.layout, out.ld, 1, _stream_ptr(stream)))
+    entry = lib.sprs_hip_csmat_mulacc_dense_f32 if _is_f32_dense(lhs, rhs, out) else lib.sprs_hip_csmat_mulacc_dense_f64
+    check(entry(lhs._h, C.c_void_p(rhs.vec.ptr), rhs.rows, rhs.cols, rhs.layout, rhs.ld,
+                C.c_void_p(out.vec.ptr), out.rows, out.layout, out.ld, 1, _stream_ptr(stream)))
 
 
 def _storage(lhs, want_csr):
@@ -163,20 +204,24 @@ def csmat_mul_dense(mat, rhs, stream=None):
     """`&CsMat * &Array2` (csmat.rs:1989-2048), ONE call below the C ABI (sprs_hip_csmat_mul_dense_f64): the four arms
     (CSR | CSC) x (>= 8 columns | fewer); the result comes back row-major for >= 8 columns and column-major (`.f()`) below,
     like the reference's."""
-    out = DeviceMat(mat.rows(), rhs.cols, DeviceVec(mat.rows() * rhs.cols))
+    f32 = _is_f32_dense(mat, rhs)
+    out = type(rhs)(mat.rows(), rhs.cols, rhs._vec_type()(mat.rows() * rhs.cols))
     lay = C.c_int32(0)
-    check(lib.sprs_hip_csmat_mul_dense_f64(mat._h, C.c_void_p(rhs.vec.ptr), rhs.rows, rhs.cols, rhs.layout, rhs.ld,
-                                           C.c_void_p(out.vec.ptr), C.byref(lay), _stream_ptr(stream)))
+    entry = lib.sprs_hip_csmat_mul_dense_f32 if f32 else lib.sprs_hip_csmat_mul_dense_f64
+    check(entry(mat._h, C.c_void_p(rhs.vec.ptr), rhs.rows, rhs.cols, rhs.layout, rhs.ld,
+                C.c_void_p(out.vec.ptr), C.byref(lay), _stream_ptr(stream)))
     out.col_major = lay.value == _ffi.COL_MAJOR
     return out
 
 
 def dense_dot_csmat(lhs, mat, stream=None):
     """`Array2::dot(&CsMat)` (csmat.rs:2050-2117): dense . sparse through the transposes of the reference, below the C ABI."""
-    out = DeviceMat(lhs.rows, mat.cols(), DeviceVec(lhs.rows * mat.cols()))
+    f32 = _is_f32_dense(mat, lhs)
+    out = type(lhs)(lhs.rows, mat.cols(), lhs._vec_type()(lhs.rows * mat.cols()))
     lay = C.c_int32(0)
-    check(lib.sprs_hip_dense_dot_csmat_f64(C.c_void_p(lhs.vec.ptr), lhs.rows, lhs.cols, lhs.layout, lhs.ld, mat._h,
-                                           C.c_void_p(out.vec.ptr), C.byref(lay), _stream_ptr(stream)))
+    entry = lib.sprs_hip_dense_dot_csmat_f32 if f32 else lib.sprs_hip_dense_dot_csmat_f64
+    check(entry(C.c_void_p(lhs.vec.ptr), lhs.rows, lhs.cols, lhs.layout, lhs.ld, mat._h,
+                C.c_void_p(out.vec.ptr), C.byref(lay), _stream_ptr(stream)))
     out.col_major = lay.value == _ffi.COL_MAJOR
     return out
 
