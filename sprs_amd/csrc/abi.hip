@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "common.hpp"
@@ -146,11 +147,31 @@ static int32_t finish_result(OwnedCsmat &res, const sprs_hip_csmat *from, sprs_h
     return SPRS_HIP_OK;
 }
 
-// CsMat::new / new_csc on host arrays (the checks of sprs_hip_csmat_upload that follow its argument checks)
-static int32_t csmat_upload(OwnedCsmat &out, int32_t storage, uint64_t rows, uint64_t cols, const void *indptr, int32_t iptr_bytes,
-                            const void *indices, int32_t idx_bytes, const double *data, int32_t validate) {
+// ---- what the f64 and the f32 matrix entries share -------------------------------------------------------------------------------
+// Every entry that exists for both precisions has ONE body below: a template on the handle type H (sprs_hip_csmat or
+// sprs_hip_csmat_f32), with the scalar T taken from it.  The extern "C" functions forward to it, so a check, its text and its
+// place in the order of checks (the reference's assert order) are the same for both.  Where the two differ, the difference
+// is a branch or an overload here.
+template <typename H>
+using Value = typename H::value_type;
+template <typename H>
+constexpr bool IS_F32 = std::is_same<H, sprs_hip_csmat_f32>::value;
+
+// the f64 handle counts its multiplies (the copy plans are built at the second one); the f32 handle has no such policy
+static void copy_spmv_calls(sprs_hip_csmat *to, const sprs_hip_csmat *from) { to->spmv_calls = from->spmv_calls; }
+static void copy_spmv_calls(sprs_hip_csmat_f32 *, const sprs_hip_csmat_f32 *) {}
+
+// CsMat::new / new_csc on host arrays (the checks of the upload entries that follow their argument checks)
+template <typename H>
+static int32_t csmat_upload(Owned<H> &out, int32_t storage, uint64_t rows, uint64_t cols, const void *indptr, int32_t iptr_bytes,
+                            const void *indices, int32_t idx_bytes, const Value<H> *data, int32_t validate) {
     if (storage != SPRS_HIP_CSR && storage != SPRS_HIP_CSC) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "bad storage tag %d", storage);
-    if (!host_widths_ok(iptr_bytes, idx_bytes)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "index widths must be 2, 4 or 8 bytes");
+    if (IS_F32<H>) {               // an f32 matrix takes 4- and 8-byte host arrays only: nothing below is narrow for it
+        if (!widths_ok(iptr_bytes, idx_bytes))
+            SPRS_FAIL(SPRS_HIP_INVALID_ARG, "index widths of an f32 matrix must be 4 or 8 bytes (2-byte host arrays are not supported for f32 handles)");
+    } else if (!host_widths_ok(iptr_bytes, idx_bytes)) {
+        SPRS_FAIL(SPRS_HIP_INVALID_ARG, "index widths must be 2, 4 or 8 bytes");
+    }
     const uint64_t outer = storage == SPRS_HIP_CSR ? rows : cols;
     const uint64_t inner = storage == SPRS_HIP_CSR ? cols : rows;
     const uint64_t first = host_index_at(indptr, iptr_bytes, 0), last = host_index_at(indptr, iptr_bytes, outer);
@@ -170,7 +191,7 @@ static int32_t csmat_upload(OwnedCsmat &out, int32_t storage, uint64_t rows, uin
             return check_structure(inner, outer, (const typename decltype(p)::type *)ip.p, (const typename decltype(i)::type *)ix.p);
         }));
     }
-    OwnedCsmat m;
+    Owned<H> m;
     SPRS_TRY(make_csmat(m, storage, rows, cols, nnz, ip.bytes, ix.bytes));
     hipError_t e = hipSuccess;
     if (first == 0) {
@@ -186,14 +207,316 @@ static int32_t csmat_upload(OwnedCsmat &out, int32_t storage, uint64_t rows, uin
         e = copy_to_device(m->indptr, tmp.data(), tmp.size(), nullptr);
     }
     if (e == hipSuccess) e = ix.upload(m->indices, nnz);
-    if (e == hipSuccess && nnz) e = copy_to_device(m->data, data, nnz * sizeof(double), nullptr);
-    if (e != hipSuccess) return fail_hip(e, "csmat_upload");
+    if (e == hipSuccess && nnz) e = copy_to_device(m->data, data, nnz * sizeof(Value<H>), nullptr);
+    if (e != hipSuccess) return fail_hip(e, IS_F32<H> ? "csmat_f32_upload" : "csmat_upload");
     if (narrow) {
         m->decl_iptr_bytes = iptr_bytes;
         m->decl_idx_bytes = idx_bytes;
     }
     out = std::move(m);
     return SPRS_HIP_OK;
+}
+
+template <typename H>
+static int32_t entry_upload(H **out, int32_t storage, uint64_t rows, uint64_t cols, const void *indptr, int32_t iptr_bytes, const void *indices,
+                            int32_t idx_bytes, const Value<H> *data, int32_t validate) {
+    clear_error();
+    if (!out || !indptr) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    Owned<H> m;
+    SPRS_TRY(csmat_upload(m, storage, rows, cols, indptr, iptr_bytes, indices, idx_bytes, data, validate));
+    *out = m.release();
+    return SPRS_HIP_OK;
+}
+
+template <typename H>
+static int32_t entry_wrap_device(H **out, int32_t storage, uint64_t rows, uint64_t cols, uint64_t nnz, const void *dev_indptr, int32_t iptr_bytes,
+                                 const void *dev_indices, int32_t idx_bytes, const Value<H> *dev_data) {
+    clear_error();
+    if (!out || !dev_indptr) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    if (storage != SPRS_HIP_CSR && storage != SPRS_HIP_CSC) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "bad storage tag %d", storage);
+    if (!widths_ok(iptr_bytes, idx_bytes)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "index widths must be 4 or 8 bytes");
+    if (nnz && (!dev_indices || !dev_data)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL indices/data with nnz > 0");
+    if (((uintptr_t)dev_indptr | (uintptr_t)dev_indices | (uintptr_t)dev_data) & 15)
+        SPRS_FAIL(SPRS_HIP_INVALID_ARG, "device buffers must be 16-byte aligned");
+    int device = 0;
+    const hipError_t e = hipGetDevice(&device);
+    if (e != hipSuccess) return fail_hip(e, "hipGetDevice");
+    *out = view_csmat(storage, rows, cols, nnz, dev_indptr, iptr_bytes, dev_indices, idx_bytes, dev_data, device);
+    return SPRS_HIP_OK;
+}
+
+template <typename H>
+static int32_t entry_info(const H *m, uint64_t *rows, uint64_t *cols, uint64_t *nnz, int32_t *iptr_bytes, int32_t *idx_bytes, int32_t *storage) {
+    clear_error();
+    if (!m) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if (rows) *rows = m->rows;
+    if (cols) *cols = m->cols;
+    if (nnz) *nnz = m->nnz;
+    if (iptr_bytes) *iptr_bytes = m->user_iptr_bytes();       // the widths the caller declared (2-byte arrays live widened on the device)
+    if (idx_bytes) *idx_bytes = m->user_idx_bytes();
+    if (storage) *storage = m->storage;
+    return SPRS_HIP_OK;
+}
+
+template <typename H>
+static int32_t entry_device_ptrs(const H *m, const void **indptr, const void **indices, const Value<H> **data) {
+    clear_error();
+    if (!m) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if (indptr) *indptr = m->indptr;
+    if (indices) *indices = m->indices;
+    if (data) *data = m->data;
+    return SPRS_HIP_OK;
+}
+
+template <typename H>
+static int32_t entry_download(const H *m, void *indptr, void *indices, Value<H> *data) {
+    clear_error();
+    if (!m) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if (indptr) SPRS_TRY(download_indices(indptr, m->indptr, m->outer() + 1, m->iptr_bytes, m->user_iptr_bytes()));
+    if (indices && m->nnz) SPRS_TRY(download_indices(indices, m->indices, m->nnz, m->idx_bytes, m->user_idx_bytes()));
+    if (data && m->nnz) SPRS_TRY_HIP(copy_to_host(data, m->data, m->nnz * sizeof(Value<H>), nullptr));
+    return SPRS_HIP_OK;
+}
+
+template <typename H>
+static int32_t entry_refresh(H *m) {
+    clear_error();
+    if (!m) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    SPRS_TRY_HIP(hipDeviceSynchronize());     // nothing in flight may still read the plan copies or the CSR copy
+    std::lock_guard<std::recursive_mutex> lock(m->mu);
+    invalidate_caches(m);
+    return SPRS_HIP_OK;
+}
+
+template <typename H>
+static int32_t entry_transpose_view(const H *m, H **out) {
+    clear_error();
+    if (!m || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = view_csmat(m, true);
+    return SPRS_HIP_OK;
+}
+
+template <typename H>
+static int32_t entry_free(H *m) {
+    clear_error();
+    delete m;
+    return SPRS_HIP_OK;
+}
+
+// ---- products with dense operands: the storage dispatch of the reference below the ABI -----------------------------------------
+// The CSR form of a handle: itself, or — for a CSC handle — its to_other_storage() copy (csmat.rs:1405-1426), made once and kept
+// IN THE HANDLE (as_other): every later product of the same CSC matrix reuses it, from any host language.  The reference walks a
+// CSC matrix column by column and scatters (prod.rs:74-99, 219-270): every result element receives its products by ascending
+// column index, which is the order of the CSR kernels on the converted matrix.
+template <typename H>
+static int32_t other_form(const H *m, H **out) {
+    auto *mm = const_cast<H *>(m);
+    std::lock_guard<std::recursive_mutex> lock(mm->mu);
+    if (!mm->as_other) {
+        Owned<H> other;
+        SPRS_TRY(to_other_storage(m, other));
+        mm->as_other = other.release();
+        // the plan policy (prepare flag, multiplies so far) is the OWNER's: a copy rebuilt after a refresh keeps it
+        mm->as_other->prepared = mm->prepared;
+        copy_spmv_calls(mm->as_other, mm);
+    }
+    *out = mm->as_other;
+    return SPRS_HIP_OK;
+}
+template <typename H>
+static int32_t csr_form(const H *m, H **out) {
+    if (m->storage == SPRS_HIP_CSR) {
+        *out = const_cast<H *>(m);
+        return SPRS_HIP_OK;
+    }
+    return other_form(m, out);
+}
+
+template <typename H>
+static int32_t entry_prepare(H *m, void *stream) {
+    clear_error();
+    if (!m) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    H *csr = nullptr;
+    {
+        std::lock_guard<std::recursive_mutex> lock(m->mu);
+        m->prepared = true;                    // kept on the handle the caller holds: survives a refresh of a CSC handle's CSR copy
+    }
+    SPRS_TRY(csr_form(m, &csr));               // a CSC handle multiplies through its CSR copy: that is the handle to prepare
+    return spmv_prepare(csr, (hipStream_t)stream);
+}
+
+template <typename T>
+static int32_t vec_args_ok(const T *x_dev, uint64_t x_len, T *y_dev, uint64_t y_len) {
+    if ((x_len && !x_dev) || (y_len && !y_dev)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL vector");
+    // &mut res_vec cannot alias &in_vec in the reference; here the kernels read x while they write y
+    if (x_len && y_len && x_dev < y_dev + y_len && y_dev < x_dev + x_len)
+        SPRS_FAIL(SPRS_HIP_INVALID_ARG, "the result vector overlaps the input vector");
+    return SPRS_HIP_OK;
+}
+
+template <typename H>
+static int32_t entry_spmv(const H *a, const Value<H> *x_dev, uint64_t x_len, Value<H> *y_dev, uint64_t y_len, int32_t accumulate, void *stream) {
+    clear_error();
+    if (!a) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    // prod.rs:114-118: dimension check first, then storage
+    if (a->cols != x_len || a->rows != y_len) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    if (a->storage != SPRS_HIP_CSR) SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "Storage mismatch");
+    SPRS_TRY(vec_args_ok(x_dev, x_len, y_dev, y_len));
+    return spmv(const_cast<H *>(a), x_dev, y_dev, accumulate != 0, (hipStream_t)stream);
+}
+
+// a multiply of either storage through the CSR form; a CSC owner takes the multiply count of its CSR copy back
+template <typename H>
+static int32_t spmv_csr_form(const H *a, const Value<H> *x_dev, Value<H> *y_dev, bool accumulate, void *stream) {
+    H *csr = nullptr;
+    SPRS_TRY(csr_form(a, &csr));
+    const int32_t st = spmv(csr, x_dev, y_dev, accumulate, (hipStream_t)stream);
+    if (csr != a) copy_spmv_calls(const_cast<H *>(a), csr);
+    return st;
+}
+
+template <typename H>
+static int32_t entry_mul_acc_mat_vec_csc(const H *a, const Value<H> *x_dev, uint64_t x_len, Value<H> *y_dev, uint64_t y_len, void *stream) {
+    clear_error();
+    if (!a) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    // prod.rs:88-92: dimensions first, then storage
+    if (a->cols != x_len || a->rows != y_len) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    if (a->storage != SPRS_HIP_CSC) SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "Storage mismatch");
+    SPRS_TRY(vec_args_ok(x_dev, x_len, y_dev, y_len));
+    return spmv_csr_form(a, x_dev, y_dev, true, stream);
+}
+
+template <typename H>
+static int32_t entry_csmat_mul_vec(const H *a, const Value<H> *x_dev, uint64_t x_len, Value<H> *y_dev, uint64_t y_len, void *stream) {
+    clear_error();
+    if (!a) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    // csmat.rs:2119-2160 -> csr_/csc_mulacc_dense_colmaj with one column (prod.rs:284-289 / 257-259: "Dimension mismatch")
+    if (a->cols != x_len || a->rows != y_len) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    SPRS_TRY(vec_args_ok(x_dev, x_len, y_dev, y_len));
+    return spmv_csr_form(a, x_dev, y_dev, false, stream);
+}
+
+template <typename H>
+static int32_t entry_spmm_rowmaj(const H *a, const Value<H> *rhs_dev, uint64_t rhs_rows, uint64_t k, uint64_t ld_rhs, Value<H> *out_dev,
+                                 uint64_t out_rows, uint64_t ld_out, int32_t accumulate, void *stream) {
+    clear_error();
+    if (!a) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    // prod.rs:199-202: three dimension asserts, then storage
+    if (a->cols != rhs_rows || a->rows != out_rows) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    if (a->storage != SPRS_HIP_CSR) SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "Storage mismatch");
+    if (ld_rhs < k || ld_out < k) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "leading dimension smaller than the column count");
+    if (k && ((rhs_rows && !rhs_dev) || (out_rows && !out_dev))) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL matrix");
+    return spmm_strided(const_cast<H *>(a), rhs_dev, k, ld_rhs, 1, out_dev, ld_out, 1, accumulate != 0, (hipStream_t)stream);
+}
+
+template <typename H>
+static int32_t entry_mulacc_dense(const H *lhs, const Value<H> *rhs_dev, uint64_t rhs_rows, uint64_t k, int32_t rhs_layout, uint64_t ld_rhs,
+                                  Value<H> *out_dev, uint64_t out_rows, int32_t out_layout, uint64_t ld_out, int32_t accumulate, void *stream) {
+    clear_error();
+    if (!lhs) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if ((rhs_layout != SPRS_HIP_ROW_MAJOR && rhs_layout != SPRS_HIP_COL_MAJOR) || (out_layout != SPRS_HIP_ROW_MAJOR && out_layout != SPRS_HIP_COL_MAJOR))
+        SPRS_FAIL(SPRS_HIP_INVALID_ARG, "bad layout tag");
+    // prod.rs:199-201, 228-230, 257-259, 284-289: the three dimension asserts of the four dense kernels (the column counts of rhs
+    // and out are one argument here)
+    if (lhs->cols != rhs_rows || lhs->rows != out_rows) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    if (ld_rhs < (rhs_layout == SPRS_HIP_ROW_MAJOR ? k : rhs_rows) || ld_out < (out_layout == SPRS_HIP_ROW_MAJOR ? k : out_rows))
+        SPRS_FAIL(SPRS_HIP_INVALID_ARG, "leading dimension smaller than the extent it strides over");
+    if (k && ((rhs_rows && !rhs_dev) || (out_rows && !out_dev))) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL matrix");
+    if (k && rhs_rows && out_rows) {   // the two operands must not share an ELEMENT (as vec_args_ok for the vectors)
+        const uint64_t span_r = (rhs_layout == SPRS_HIP_ROW_MAJOR ? rhs_rows - 1 : k - 1) * ld_rhs + (rhs_layout == SPRS_HIP_ROW_MAJOR ? k : rhs_rows);
+        const uint64_t span_o = (out_layout == SPRS_HIP_ROW_MAJOR ? out_rows - 1 : k - 1) * ld_out + (out_layout == SPRS_HIP_ROW_MAJOR ? k : out_rows);
+        if (rhs_dev < out_dev + span_o && out_dev < rhs_dev + span_r) {
+            // the strided spans meet.  Two views of ONE buffer with the same layout and pitch — rhs = buf[:, 0:k], out = buf[:, k:2k],
+            // or the same as column blocks; ndarray views the reference accepts — are still element-disjoint when the lines of one
+            // fall into the gaps of the other: the offset between them, modulo the pitch, leaves both line extents apart.
+            bool disjoint = false;
+            if (rhs_layout == out_layout && ld_rhs == ld_out) {
+                const uint64_t w_r = rhs_layout == SPRS_HIP_ROW_MAJOR ? k : rhs_rows, w_o = out_layout == SPRS_HIP_ROW_MAJOR ? k : out_rows;
+                const uint64_t d = rhs_dev <= out_dev ? (uint64_t)(out_dev - rhs_dev) % ld_rhs : (ld_rhs - (uint64_t)(rhs_dev - out_dev) % ld_rhs) % ld_rhs;
+                // inside one pitch: rhs lines occupy [0, w_r), out lines [d, d + w_o)
+                disjoint = d >= w_r && d + w_o <= ld_rhs;
+            }
+            if (!disjoint) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "the result matrix overlaps the right-hand side");
+        }
+    }
+    H *csr = nullptr;
+    SPRS_TRY(csr_form(lhs, &csr));
+    hipStream_t st = (hipStream_t)stream;
+    if (rhs_layout == SPRS_HIP_COL_MAJOR && out_layout == SPRS_HIP_COL_MAJOR && k < 8) {
+        // the shape `&CsMat * &Array2` gives csr_mulacc_dense_colmaj (fewer than 8 columns, csmat.rs:2002-2016): column by column
+        // through the SpMV — a column of a column-major rhs is a separate line per entry, so the SpMM kernel would issue k gathers
+        // per entry where it issues one for a row-major rhs (k x 5.5 ms against k x 1.04 ms of the banded f64 SpMV)
+        for (uint64_t j = 0; j < k; ++j) SPRS_TRY(spmv(csr, rhs_dev + j * ld_rhs, out_dev + j * ld_out, accumulate != 0, st));
+        return SPRS_HIP_OK;
+    }
+    const uint64_t rs_r = rhs_layout == SPRS_HIP_ROW_MAJOR ? ld_rhs : 1, cs_r = rhs_layout == SPRS_HIP_ROW_MAJOR ? 1 : ld_rhs;
+    const uint64_t rs_o = out_layout == SPRS_HIP_ROW_MAJOR ? ld_out : 1, cs_o = out_layout == SPRS_HIP_ROW_MAJOR ? 1 : ld_out;
+    return spmm_strided(csr, rhs_dev, k, rs_r, cs_r, out_dev, rs_o, cs_o, accumulate != 0, st);
+}
+
+template <typename H>
+static int32_t entry_mul_dense(const H *lhs, const Value<H> *rhs_dev, uint64_t rhs_rows, uint64_t k, int32_t rhs_layout, uint64_t ld_rhs,
+                               Value<H> *out_dev, int32_t *out_layout, void *stream) {
+    clear_error();
+    if (!lhs || !out_layout) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    // csmat.rs:2002-2045: Array::zeros((rows, cols)) for >= 8 columns, Array::zeros((rows, cols).f()) below — in both storages
+    const int32_t lay = k >= 8 ? SPRS_HIP_ROW_MAJOR : SPRS_HIP_COL_MAJOR;
+    *out_layout = lay;
+    return entry_mulacc_dense(lhs, rhs_dev, rhs_rows, k, rhs_layout, ld_rhs, out_dev, lhs->rows, lay, lay == SPRS_HIP_ROW_MAJOR ? k : lhs->rows, 0,
+                              stream);
+}
+
+template <typename H>
+static int32_t entry_dense_dot(const Value<H> *lhs_dev, uint64_t lhs_rows, uint64_t lhs_cols, int32_t lhs_layout, uint64_t ld_lhs, const H *rhs,
+                               Value<H> *out_dev, int32_t *out_layout, void *stream) {
+    clear_error();
+    if (!rhs || !out_layout) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    if (lhs_layout != SPRS_HIP_ROW_MAJOR && lhs_layout != SPRS_HIP_COL_MAJOR) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "bad layout tag");
+    // csmat.rs:2064-2117: (rhs^T * lhs^T)^T with free transposes — rhs.transpose_view(), lhs.t(), res.reversed_axes()
+    // the CSR form of rhs^T: the transpose view of a CSC rhs, or of the (cached) CSC copy of a CSR rhs — either way a view.
+    // The view stays in the rhs handle (beside as_other): its tile / band plans are built once, not per call.
+    // The owner's lock is held until the product's kernels are launched: a concurrent refresh / numeric SpGEMM on rhs frees the
+    // view in invalidate_caches (behind a device synchronise), and must not do so between the look-up and the launches.
+    H *owner = const_cast<H *>(rhs);
+    std::lock_guard<std::recursive_mutex> lock(owner->mu);
+    if (!owner->t_view) {
+        H *src = owner;
+        if (rhs->storage == SPRS_HIP_CSR) SPRS_TRY(other_form(rhs, &src));
+        owner->t_view = view_csmat(src, true);
+    }
+    int32_t lay_t = 0;
+    // lhs^T: lhs_cols x lhs_rows, the other layout over the same memory
+    const int32_t st = entry_mul_dense(owner->t_view, lhs_dev, lhs_cols, lhs_rows, lhs_layout == SPRS_HIP_ROW_MAJOR ? SPRS_HIP_COL_MAJOR : SPRS_HIP_ROW_MAJOR,
+                                       ld_lhs, out_dev, &lay_t, stream);
+    if (st != SPRS_HIP_OK) return st;
+    *out_layout = lay_t == SPRS_HIP_ROW_MAJOR ? SPRS_HIP_COL_MAJOR : SPRS_HIP_ROW_MAJOR;     // reversed_axes()
+    return SPRS_HIP_OK;
+}
+
+// tol and the threshold travel as doubles for both precisions; the solve, and the empty case below, compare in T
+template <typename H>
+static int32_t entry_bicgstab(H *a, const Value<H> *x0_dev, const Value<H> *b_dev, uint64_t n, double tol, uint64_t max_iter,
+                              double soft_restart_threshold, Value<H> *x_dev, sprs_hip_bicgstab_info *info, void *stream) {
+    using T = Value<H>;
+    clear_error();
+    if (!a) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if (a->rows != a->cols || a->rows != n) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    if (n && (!x0_dev || !b_dev || !x_dev)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL vector");
+    if (x_dev == x0_dev || x_dev == b_dev) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "x_dev may not alias x0_dev / b_dev");
+    const T tol_t = (T)tol, threshold_t = (T)soft_restart_threshold;
+    if (n == 0) {
+        // what solve() does with empty vectors (bicgstab.rs:158-172): every norm is sqrt(0) = 0.  Without an iteration the loop
+        // falls through to Err; otherwise the first step's err = 0 passes any tol > 0, the hard restart confirms it: Ok after
+        // one iteration and one hard restart.  With tol <= 0 (or NaN) nothing passes and the iterations run out: Err.
+        // (|rho| / err^2 = 0 / 0 is below no threshold: no soft restart.)
+        const bool passes = max_iter > 0 && T(0) < tol_t;
+        const uint64_t it = passes ? 1 : max_iter;
+        if (info) *info = sprs_hip_bicgstab_info{it, 0, passes ? 1ull : 0ull, 0.0, 0.0, passes ? 1 : 0};
+        return SPRS_HIP_OK;
+    }
+    return bicgstab(a, x0_dev, b_dev, n, tol_t, max_iter, threshold_t, x_dev, info, (hipStream_t)stream);
 }
 
 extern "C" {
@@ -276,64 +599,28 @@ int32_t sprs_hip_synchronize(void *stream) {
 int32_t sprs_hip_csmat_upload(sprs_hip_csmat **out, int32_t storage, uint64_t rows, uint64_t cols,
                               const void *indptr, int32_t iptr_bytes, const void *indices,
                               int32_t idx_bytes, const double *data, int32_t validate) {
-    clear_error();
-    if (!out || !indptr) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
-    *out = nullptr;
-    OwnedCsmat m;
-    SPRS_TRY(csmat_upload(m, storage, rows, cols, indptr, iptr_bytes, indices, idx_bytes, data, validate));
-    *out = m.release();
-    return SPRS_HIP_OK;
+    return entry_upload(out, storage, rows, cols, indptr, iptr_bytes, indices, idx_bytes, data, validate);
 }
 
 int32_t sprs_hip_csmat_wrap_device(sprs_hip_csmat **out, int32_t storage, uint64_t rows,
                                    uint64_t cols, uint64_t nnz, const void *dev_indptr,
                                    int32_t iptr_bytes, const void *dev_indices, int32_t idx_bytes,
                                    const double *dev_data) {
-    clear_error();
-    if (!out || !dev_indptr) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
-    *out = nullptr;
-    if (storage != SPRS_HIP_CSR && storage != SPRS_HIP_CSC) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "bad storage tag %d", storage);
-    if (!widths_ok(iptr_bytes, idx_bytes)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "index widths must be 4 or 8 bytes");
-    if (nnz && (!dev_indices || !dev_data)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL indices/data with nnz > 0");
-    if (((uintptr_t)dev_indptr | (uintptr_t)dev_indices | (uintptr_t)dev_data) & 15)
-        SPRS_FAIL(SPRS_HIP_INVALID_ARG, "device buffers must be 16-byte aligned");
-    int device = 0;
-    const hipError_t e = hipGetDevice(&device);
-    if (e != hipSuccess) return fail_hip(e, "hipGetDevice");
-    *out = view_csmat(storage, rows, cols, nnz, dev_indptr, iptr_bytes, dev_indices, idx_bytes, dev_data, device);
-    return SPRS_HIP_OK;
+    return entry_wrap_device(out, storage, rows, cols, nnz, dev_indptr, iptr_bytes, dev_indices, idx_bytes, dev_data);
 }
 
 int32_t sprs_hip_csmat_info(const sprs_hip_csmat *m, uint64_t *rows, uint64_t *cols, uint64_t *nnz,
                             int32_t *iptr_bytes, int32_t *idx_bytes, int32_t *storage) {
-    clear_error();
-    if (!m) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
-    if (rows) *rows = m->rows;
-    if (cols) *cols = m->cols;
-    if (nnz) *nnz = m->nnz;
-    if (iptr_bytes) *iptr_bytes = m->user_iptr_bytes();       // the widths the caller declared (2-byte arrays live widened on the device)
-    if (idx_bytes) *idx_bytes = m->user_idx_bytes();
-    if (storage) *storage = m->storage;
-    return SPRS_HIP_OK;
+    return entry_info(m, rows, cols, nnz, iptr_bytes, idx_bytes, storage);
 }
 
 int32_t sprs_hip_csmat_device_ptrs(const sprs_hip_csmat *m, const void **indptr,
                                    const void **indices, const double **data) {
-    clear_error();
-    if (!m) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
-    if (indptr) *indptr = m->indptr;
-    if (indices) *indices = m->indices;
-    if (data) *data = m->data;
-    return SPRS_HIP_OK;
+    return entry_device_ptrs(m, indptr, indices, data);
 }
 
 int32_t sprs_hip_csmat_download(const sprs_hip_csmat *m, void *indptr, void *indices, double *data) {
-    clear_error();
-    if (!m) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
-    if (indptr) SPRS_TRY(download_indices(indptr, m->indptr, m->outer() + 1, m->iptr_bytes, m->user_iptr_bytes()));
-    if (indices && m->nnz) SPRS_TRY(download_indices(indices, m->indices, m->nnz, m->idx_bytes, m->user_idx_bytes()));
-    if (data && m->nnz) SPRS_TRY_HIP(copy_to_host(data, m->data, m->nnz * sizeof(double), nullptr));
-    return SPRS_HIP_OK;
+    return entry_download(m, indptr, indices, data);
 }
 
 int32_t sprs_hip_csmat_download_outer(const sprs_hip_csmat *m, uint64_t start, uint64_t end,
@@ -364,12 +651,7 @@ int32_t sprs_hip_csmat_download_outer(const sprs_hip_csmat *m, uint64_t start, u
 }
 
 int32_t sprs_hip_csmat_refresh(sprs_hip_csmat *m) {
-    clear_error();
-    if (!m) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
-    SPRS_TRY_HIP(hipDeviceSynchronize());     // nothing in flight may still read the plan copies
-    std::lock_guard<std::recursive_mutex> lock(m->mu);
-    invalidate_caches(m);
-    return SPRS_HIP_OK;
+    return entry_refresh(m);
 }
 
 int32_t sprs_hip_csmat_spmv_plan_info(const sprs_hip_csmat *m, int32_t *kind, uint64_t *plan_bytes) {
@@ -399,30 +681,16 @@ int32_t sprs_hip_csmat_spmv_plan_info(const sprs_hip_csmat *m, int32_t *kind, ui
 }
 
 int32_t sprs_hip_csmat_transpose_view(const sprs_hip_csmat *m, sprs_hip_csmat **out) {
-    clear_error();
-    if (!m || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
-    *out = view_csmat(m, true);
-    return SPRS_HIP_OK;
+    return entry_transpose_view(m, out);
 }
 
 int32_t sprs_hip_csmat_free(sprs_hip_csmat *m) {
-    clear_error();
-    delete m;
-    return SPRS_HIP_OK;
+    return entry_free(m);
 }
 
 int32_t sprs_hip_spmv_f64(const sprs_hip_csmat *a, const double *x_dev, uint64_t x_len,
                           double *y_dev, uint64_t y_len, int32_t accumulate, void *stream) {
-    clear_error();
-    if (!a) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
-    // prod.rs:114-118: dimension check first, then storage
-    if (a->cols != x_len || a->rows != y_len) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
-    if (a->storage != SPRS_HIP_CSR) SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "Storage mismatch");
-    if ((x_len && !x_dev) || (y_len && !y_dev)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL vector");
-    // &mut res_vec cannot alias &in_vec in the reference; here the kernels read x while they write y
-    if (x_len && y_len && x_dev < y_dev + y_len && y_dev < x_dev + x_len)
-        SPRS_FAIL(SPRS_HIP_INVALID_ARG, "the result vector overlaps the input vector");
-    return spmv_f64(const_cast<sprs_hip_csmat *>(a), x_dev, y_dev, accumulate != 0, (hipStream_t)stream);
+    return entry_spmv(a, x_dev, x_len, y_dev, y_len, accumulate, stream);
 }
 
 int32_t sprs_hip_spmv_f64_host(uint64_t rows, uint64_t cols, const void *indptr,
@@ -450,15 +718,7 @@ int32_t sprs_hip_spmv_f64_host(uint64_t rows, uint64_t cols, const void *indptr,
 int32_t sprs_hip_spmm_rowmaj_f64(const sprs_hip_csmat *a, const double *rhs_dev, uint64_t rhs_rows, uint64_t k,
                                  uint64_t ld_rhs, double *out_dev, uint64_t out_rows, uint64_t ld_out,
                                  int32_t accumulate, void *stream) {
-    clear_error();
-    if (!a) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
-    // prod.rs:199-202: three dimension asserts, then storage
-    if (a->cols != rhs_rows || a->rows != out_rows) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
-    if (a->storage != SPRS_HIP_CSR) SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "Storage mismatch");
-    if (ld_rhs < k || ld_out < k) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "leading dimension smaller than the column count");
-    if (k && ((rhs_rows && !rhs_dev) || (out_rows && !out_dev))) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL matrix");
-    return spmm_rowmaj_f64(const_cast<sprs_hip_csmat *>(a), rhs_dev, k, ld_rhs, out_dev, ld_out, accumulate != 0,
-                           (hipStream_t)stream);
+    return entry_spmm_rowmaj(a, rhs_dev, rhs_rows, k, ld_rhs, out_dev, out_rows, ld_out, accumulate, stream);
 }
 
 static int32_t spgemm_contract(const sprs_hip_csmat *a, const sprs_hip_csmat *b) {
@@ -553,22 +813,7 @@ int32_t sprs_hip_spgemm_plan_free(sprs_hip_spgemm_plan *plan) {
 int32_t sprs_hip_bicgstab_f64(sprs_hip_csmat *a, const double *x0_dev, const double *b_dev, uint64_t n, double tol,
                               uint64_t max_iter, double soft_restart_threshold, double *x_dev,
                               sprs_hip_bicgstab_info *info, void *stream) {
-    clear_error();
-    if (!a) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
-    if (a->rows != a->cols || a->rows != n) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
-    if (n && (!x0_dev || !b_dev || !x_dev)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL vector");
-    if (x_dev == x0_dev || x_dev == b_dev) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "x_dev may not alias x0_dev / b_dev");
-    if (n == 0) {
-        // what solve() does with empty vectors (bicgstab.rs:158-172): every norm is sqrt(0) = 0.  Without an iteration the loop
-        // falls through to Err; otherwise the first step's err = 0 passes any tol > 0, the hard restart confirms it: Ok after
-        // one iteration and one hard restart.  With tol <= 0 (or NaN) nothing passes and the iterations run out: Err.
-        // (|rho| / err^2 = 0 / 0 is below no threshold: no soft restart.)
-        const bool passes = max_iter > 0 && 0.0 < tol;
-        const uint64_t it = passes ? 1 : max_iter;
-        if (info) *info = sprs_hip_bicgstab_info{it, 0, passes ? 1ull : 0ull, 0.0, 0.0, passes ? 1 : 0};
-        return SPRS_HIP_OK;
-    }
-    return bicgstab_f64(a, x0_dev, b_dev, n, tol, max_iter, soft_restart_threshold, x_dev, info, (hipStream_t)stream);
+    return entry_bicgstab(a, x0_dev, b_dev, n, tol, max_iter, soft_restart_threshold, x_dev, info, stream);
 }
 
 int32_t sprs_hip_gauss_seidel_f64(sprs_hip_csmat *a, double *x_dev, const double *rhs_dev, uint64_t n, uint64_t max_iter,
@@ -670,43 +915,8 @@ int32_t sprs_hip_dist_spmv_f64(sprs_hip_dist *d, const double *x_dev, uint64_t x
     return dist_spmv(d, x_dev, y_dev, (hipStream_t)stream);
 }
 
-// ---- products with dense operands: the storage dispatch of the reference below the ABI -----------------------------------------
-// The CSR form of a handle: itself, or — for a CSC handle — its to_other_storage() copy (csmat.rs:1405-1426), made once and kept
-// IN THE HANDLE (as_other): every later product of the same CSC matrix reuses it, from any host language.  The reference walks a
-// CSC matrix column by column and scatters (prod.rs:74-99, 219-270): every result element receives its products by ascending
-// column index, which is the order of the CSR kernels on the converted matrix.
-static int32_t other_form(const sprs_hip_csmat *m, sprs_hip_csmat **out) {
-    auto *mm = const_cast<sprs_hip_csmat *>(m);
-    std::lock_guard<std::recursive_mutex> lock(mm->mu);
-    if (!mm->as_other) {
-        OwnedCsmat other;
-        SPRS_TRY(to_other_storage(m, other));
-        mm->as_other = other.release();
-        // the plan policy (prepare flag, multiplies so far) is the OWNER's: a copy rebuilt after a refresh keeps it
-        mm->as_other->prepared = mm->prepared;
-        mm->as_other->spmv_calls = mm->spmv_calls;
-    }
-    *out = mm->as_other;
-    return SPRS_HIP_OK;
-}
-static int32_t csr_form(const sprs_hip_csmat *m, sprs_hip_csmat **out) {
-    if (m->storage == SPRS_HIP_CSR) {
-        *out = const_cast<sprs_hip_csmat *>(m);
-        return SPRS_HIP_OK;
-    }
-    return other_form(m, out);
-}
-
 int32_t sprs_hip_csmat_prepare(sprs_hip_csmat *m, void *stream) {
-    clear_error();
-    if (!m) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
-    sprs_hip_csmat *csr = nullptr;
-    {
-        std::lock_guard<std::recursive_mutex> lock(m->mu);
-        m->prepared = true;                    // kept on the handle the caller holds: survives a refresh of a CSC handle's CSR copy
-    }
-    SPRS_TRY(csr_form(m, &csr));               // a CSC handle multiplies through its CSR copy: that is the handle to prepare
-    return spmv_prepare(csr, (hipStream_t)stream);
+    return entry_prepare(m, stream);
 }
 
 // The four dense-rhs solves of sprs::linalg::trisolve behind one entry: the handle's storage selects the CSR or CSC function, uplo
@@ -758,125 +968,30 @@ int32_t sprs_hip_lsolve_csc_sparse_rhs_f64(sprs_hip_csmat *l, const sprs_hip_csv
     return SPRS_HIP_OK;
 }
 
-static int32_t vec_args_ok(const double *x_dev, uint64_t x_len, double *y_dev, uint64_t y_len) {
-    if ((x_len && !x_dev) || (y_len && !y_dev)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL vector");
-    if (x_len && y_len && x_dev < y_dev + y_len && y_dev < x_dev + x_len)
-        SPRS_FAIL(SPRS_HIP_INVALID_ARG, "the result vector overlaps the input vector");
-    return SPRS_HIP_OK;
-}
-
 int32_t sprs_hip_mul_acc_mat_vec_csc_f64(const sprs_hip_csmat *a, const double *x_dev, uint64_t x_len, double *y_dev,
                                          uint64_t y_len, void *stream) {
-    clear_error();
-    if (!a) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
-    // prod.rs:88-92: dimensions first, then storage
-    if (a->cols != x_len || a->rows != y_len) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
-    if (a->storage != SPRS_HIP_CSC) SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "Storage mismatch");
-    SPRS_TRY(vec_args_ok(x_dev, x_len, y_dev, y_len));
-    sprs_hip_csmat *csr = nullptr;
-    SPRS_TRY(csr_form(a, &csr));
-    const int32_t st = spmv_f64(csr, x_dev, y_dev, true, (hipStream_t)stream);
-    if (csr != a) const_cast<sprs_hip_csmat *>(a)->spmv_calls = csr->spmv_calls;
-    return st;
+    return entry_mul_acc_mat_vec_csc(a, x_dev, x_len, y_dev, y_len, stream);
 }
 
 int32_t sprs_hip_csmat_mul_vec_f64(const sprs_hip_csmat *a, const double *x_dev, uint64_t x_len, double *y_dev, uint64_t y_len,
                                    void *stream) {
-    clear_error();
-    if (!a) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
-    // csmat.rs:2119-2160 -> csr_/csc_mulacc_dense_colmaj with one column (prod.rs:284-289 / 257-259: "Dimension mismatch")
-    if (a->cols != x_len || a->rows != y_len) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
-    SPRS_TRY(vec_args_ok(x_dev, x_len, y_dev, y_len));
-    sprs_hip_csmat *csr = nullptr;
-    SPRS_TRY(csr_form(a, &csr));
-    const int32_t st = spmv_f64(csr, x_dev, y_dev, false, (hipStream_t)stream);
-    if (csr != a) const_cast<sprs_hip_csmat *>(a)->spmv_calls = csr->spmv_calls;
-    return st;
+    return entry_csmat_mul_vec(a, x_dev, x_len, y_dev, y_len, stream);
 }
 
 int32_t sprs_hip_csmat_mulacc_dense_f64(const sprs_hip_csmat *lhs, const double *rhs_dev, uint64_t rhs_rows, uint64_t k,
                                         int32_t rhs_layout, uint64_t ld_rhs, double *out_dev, uint64_t out_rows,
                                         int32_t out_layout, uint64_t ld_out, int32_t accumulate, void *stream) {
-    clear_error();
-    if (!lhs) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
-    if ((rhs_layout != SPRS_HIP_ROW_MAJOR && rhs_layout != SPRS_HIP_COL_MAJOR) || (out_layout != SPRS_HIP_ROW_MAJOR && out_layout != SPRS_HIP_COL_MAJOR))
-        SPRS_FAIL(SPRS_HIP_INVALID_ARG, "bad layout tag");
-    // prod.rs:199-201, 228-230, 257-259, 284-289: the three dimension asserts of the four dense kernels (the column counts of rhs
-    // and out are one argument here)
-    if (lhs->cols != rhs_rows || lhs->rows != out_rows) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
-    if (ld_rhs < (rhs_layout == SPRS_HIP_ROW_MAJOR ? k : rhs_rows) || ld_out < (out_layout == SPRS_HIP_ROW_MAJOR ? k : out_rows))
-        SPRS_FAIL(SPRS_HIP_INVALID_ARG, "leading dimension smaller than the extent it strides over");
-    if (k && ((rhs_rows && !rhs_dev) || (out_rows && !out_dev))) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL matrix");
-    if (k && rhs_rows && out_rows) {   // the two operands must not share an ELEMENT (as vec_args_ok for the vectors)
-        const uint64_t span_r = (rhs_layout == SPRS_HIP_ROW_MAJOR ? rhs_rows - 1 : k - 1) * ld_rhs + (rhs_layout == SPRS_HIP_ROW_MAJOR ? k : rhs_rows);
-        const uint64_t span_o = (out_layout == SPRS_HIP_ROW_MAJOR ? out_rows - 1 : k - 1) * ld_out + (out_layout == SPRS_HIP_ROW_MAJOR ? k : out_rows);
-        if (rhs_dev < out_dev + span_o && out_dev < rhs_dev + span_r) {
-            // the strided spans meet.  Two views of ONE buffer with the same layout and pitch — rhs = buf[:, 0:k], out = buf[:, k:2k],
-            // or the same as column blocks; ndarray views the reference accepts — are still element-disjoint when the lines of one
-            // fall into the gaps of the other: the offset between them, modulo the pitch, leaves both line extents apart.
-            bool disjoint = false;
-            if (rhs_layout == out_layout && ld_rhs == ld_out) {
-                const uint64_t w_r = rhs_layout == SPRS_HIP_ROW_MAJOR ? k : rhs_rows, w_o = out_layout == SPRS_HIP_ROW_MAJOR ? k : out_rows;
-                const uint64_t d = rhs_dev <= out_dev ? (uint64_t)(out_dev - rhs_dev) % ld_rhs : (ld_rhs - (uint64_t)(rhs_dev - out_dev) % ld_rhs) % ld_rhs;
-                // inside one pitch: rhs lines occupy [0, w_r), out lines [d, d + w_o)
-                disjoint = d >= w_r && d + w_o <= ld_rhs;
-            }
-            if (!disjoint) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "the result matrix overlaps the right-hand side");
-        }
-    }
-    sprs_hip_csmat *csr = nullptr;
-    SPRS_TRY(csr_form(lhs, &csr));
-    hipStream_t st = (hipStream_t)stream;
-    if (rhs_layout == SPRS_HIP_COL_MAJOR && out_layout == SPRS_HIP_COL_MAJOR && k < 8) {
-        // the shape `&CsMat * &Array2` gives csr_mulacc_dense_colmaj (fewer than 8 columns, csmat.rs:2002-2016): column by column
-        // through the SpMV — a column of a column-major rhs is a separate line per entry, so the SpMM kernel would issue k gathers
-        // per entry where it issues one for a row-major rhs (k x 5.5 ms against k x 1.04 ms of the banded SpMV)
-        for (uint64_t j = 0; j < k; ++j) SPRS_TRY(spmv_f64(csr, rhs_dev + j * ld_rhs, out_dev + j * ld_out, accumulate != 0, st));
-        return SPRS_HIP_OK;
-    }
-    const uint64_t rs_r = rhs_layout == SPRS_HIP_ROW_MAJOR ? ld_rhs : 1, cs_r = rhs_layout == SPRS_HIP_ROW_MAJOR ? 1 : ld_rhs;
-    const uint64_t rs_o = out_layout == SPRS_HIP_ROW_MAJOR ? ld_out : 1, cs_o = out_layout == SPRS_HIP_ROW_MAJOR ? 1 : ld_out;
-    return spmm_strided_f64(csr, rhs_dev, k, rs_r, cs_r, out_dev, rs_o, cs_o, accumulate != 0, st);
+    return entry_mulacc_dense(lhs, rhs_dev, rhs_rows, k, rhs_layout, ld_rhs, out_dev, out_rows, out_layout, ld_out, accumulate, stream);
 }
 
 int32_t sprs_hip_csmat_mul_dense_f64(const sprs_hip_csmat *lhs, const double *rhs_dev, uint64_t rhs_rows, uint64_t k,
                                      int32_t rhs_layout, uint64_t ld_rhs, double *out_dev, int32_t *out_layout, void *stream) {
-    clear_error();
-    if (!lhs || !out_layout) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
-    // csmat.rs:2002-2045: Array::zeros((rows, cols)) for >= 8 columns, Array::zeros((rows, cols).f()) below — in both storages
-    const int32_t lay = k >= 8 ? SPRS_HIP_ROW_MAJOR : SPRS_HIP_COL_MAJOR;
-    *out_layout = lay;
-    return sprs_hip_csmat_mulacc_dense_f64(lhs, rhs_dev, rhs_rows, k, rhs_layout, ld_rhs, out_dev, lhs->rows, lay,
-                                           lay == SPRS_HIP_ROW_MAJOR ? k : lhs->rows, 0, stream);
+    return entry_mul_dense(lhs, rhs_dev, rhs_rows, k, rhs_layout, ld_rhs, out_dev, out_layout, stream);
 }
 
 int32_t sprs_hip_dense_dot_csmat_f64(const double *lhs_dev, uint64_t lhs_rows, uint64_t lhs_cols, int32_t lhs_layout, uint64_t ld_lhs,
                                      const sprs_hip_csmat *rhs, double *out_dev, int32_t *out_layout, void *stream) {
-    clear_error();
-    if (!rhs || !out_layout) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
-    if (lhs_layout != SPRS_HIP_ROW_MAJOR && lhs_layout != SPRS_HIP_COL_MAJOR) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "bad layout tag");
-    // csmat.rs:2064-2117: (rhs^T * lhs^T)^T with free transposes — rhs.transpose_view(), lhs.t(), res.reversed_axes()
-    // the CSR form of rhs^T: the transpose view of a CSC rhs, or of the (cached) CSC copy of a CSR rhs — either way a view
-    const sprs_hip_csmat *src = rhs;
-    if (rhs->storage == SPRS_HIP_CSR) {
-        sprs_hip_csmat *csc = nullptr;
-        SPRS_TRY(other_form(rhs, &csc));
-        src = csc;
-    }
-    // the view stays in the rhs handle (beside as_other): its tile / band plans are built once, not per call
-    // The owner's lock is held until the product's kernels are launched: a concurrent refresh / numeric SpGEMM on rhs frees the
-    // view in invalidate_caches (behind a device synchronise), and must not do so between the look-up and the launches.
-    sprs_hip_csmat *owner = const_cast<sprs_hip_csmat *>(rhs);
-    std::lock_guard<std::recursive_mutex> lock(owner->mu);
-    if (!owner->t_view) owner->t_view = view_csmat(src, true);
-    sprs_hip_csmat *rt = owner->t_view;
-    int32_t lay_t = 0;
-    // lhs^T: lhs_cols x lhs_rows, the other layout over the same memory
-    const int32_t st = sprs_hip_csmat_mul_dense_f64(rt, lhs_dev, lhs_cols, lhs_rows, lhs_layout == SPRS_HIP_ROW_MAJOR ? SPRS_HIP_COL_MAJOR : SPRS_HIP_ROW_MAJOR,
-                                                    ld_lhs, out_dev, &lay_t, stream);
-    if (st != SPRS_HIP_OK) return st;
-    *out_layout = lay_t == SPRS_HIP_ROW_MAJOR ? SPRS_HIP_COL_MAJOR : SPRS_HIP_ROW_MAJOR;     // reversed_axes()
-    return SPRS_HIP_OK;
+    return entry_dense_dot(lhs_dev, lhs_rows, lhs_cols, lhs_layout, ld_lhs, rhs, out_dev, out_layout, stream);
 }
 
 int32_t sprs_hip_dist_comm_count(const sprs_hip_dist *d, int32_t *ranks) {
@@ -2137,165 +2252,47 @@ int32_t sprs_hip_csmat_add_dense_f64(const sprs_hip_csmat *lhs, const double *rh
 
 }  // extern "C"
 
-// ---- single precision: the f32 container, its SpMV entries and BiCGSTAB (kernels: spmv_f32.hpp, bicgstab.hip) ---------------
-// CsMat::new / new_csc on host arrays for N = f32: csmat_upload above without the 2-byte widths
-static int32_t csmat_f32_upload(OwnedCsmatF32 &out, int32_t storage, uint64_t rows, uint64_t cols, const void *indptr, int32_t iptr_bytes,
-                                const void *indices, int32_t idx_bytes, const float *data, int32_t validate) {
-    if (storage != SPRS_HIP_CSR && storage != SPRS_HIP_CSC) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "bad storage tag %d", storage);
-    if (!widths_ok(iptr_bytes, idx_bytes))
-        SPRS_FAIL(SPRS_HIP_INVALID_ARG, "index widths of an f32 matrix must be 4 or 8 bytes (2-byte host arrays are not supported for f32 handles)");
-    const uint64_t outer = storage == SPRS_HIP_CSR ? rows : cols;
-    const uint64_t inner = storage == SPRS_HIP_CSR ? cols : rows;
-    const uint64_t first = host_index_at(indptr, iptr_bytes, 0), last = host_index_at(indptr, iptr_bytes, outer);
-    if (last < first) SPRS_FAIL(SPRS_HIP_BAD_STRUCTURE, "Unsorted indptr");
-    const uint64_t nnz = last - first;
-    if (nnz && (!indices || !data)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL indices/data with nnz > 0");
-    if (validate) {
-        SPRS_TRY(dispatch_widths(idx_bytes, iptr_bytes, [&](auto i, auto p) {
-            return check_structure(inner, outer, (const typename decltype(p)::type *)indptr, (const typename decltype(i)::type *)indices);
-        }));
-    }
-    OwnedCsmatF32 m;
-    SPRS_TRY(make_csmat_f32(m, storage, rows, cols, nnz, iptr_bytes, idx_bytes));
-    hipError_t e = hipSuccess;
-    if (first == 0) {
-        e = copy_to_device(m->indptr, indptr, (outer + 1) * (uint64_t)iptr_bytes, nullptr);
-    } else {
-        // to_proper (sprs/src/sparse/indptr.rs:206-214): rebase on the way in
-        std::vector<uint8_t> tmp((outer + 1) * (size_t)iptr_bytes);
-        for (uint64_t i = 0; i <= outer; ++i) {
-            const uint64_t v = host_index_at(indptr, iptr_bytes, i) - first;
-            if (iptr_bytes == 8) ((uint64_t *)tmp.data())[i] = v;
-            else ((uint32_t *)tmp.data())[i] = (uint32_t)v;
-        }
-        e = copy_to_device(m->indptr, tmp.data(), tmp.size(), nullptr);
-    }
-    if (e == hipSuccess && nnz) e = copy_to_device(m->indices, indices, nnz * (uint64_t)idx_bytes, nullptr);
-    if (e == hipSuccess && nnz) e = copy_to_device(m->data, data, nnz * sizeof(float), nullptr);
-    if (e != hipSuccess) return fail_hip(e, "csmat_f32_upload");
-    out = std::move(m);
-    return SPRS_HIP_OK;
-}
-
-// the CSR form of an f32 handle: itself, or its to_other_storage() copy, made once and kept in the handle (as csr_form above)
-static int32_t csr_form_f32(const sprs_hip_csmat_f32 *m, sprs_hip_csmat_f32 **out) {
-    auto *mm = const_cast<sprs_hip_csmat_f32 *>(m);
-    if (m->storage == SPRS_HIP_CSR) {
-        *out = mm;
-        return SPRS_HIP_OK;
-    }
-    std::lock_guard<std::recursive_mutex> lock(mm->mu);
-    if (!mm->as_other) {
-        OwnedCsmatF32 other;
-        SPRS_TRY(csmat_f32_to_other_storage(m, other));
-        mm->as_other = other.release();
-        mm->as_other->prepared = mm->prepared;
-    }
-    *out = mm->as_other;
-    return SPRS_HIP_OK;
-}
-
-static int32_t vec_args_ok_f32(const float *x_dev, uint64_t x_len, float *y_dev, uint64_t y_len) {
-    if ((x_len && !x_dev) || (y_len && !y_dev)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL vector");
-    if (x_len && y_len && x_dev < y_dev + y_len && y_dev < x_dev + x_len)
-        SPRS_FAIL(SPRS_HIP_INVALID_ARG, "the result vector overlaps the input vector");
-    return SPRS_HIP_OK;
-}
-
+// ---- single precision: the f32 twins forward to the same bodies as the f64 entries (kernels: spmv_f32.hpp, spmm_f32.hpp, bicgstab.hip) ----
 extern "C" {
 
 int32_t sprs_hip_csmat_f32_upload(sprs_hip_csmat_f32 **out, int32_t storage, uint64_t rows, uint64_t cols, const void *indptr,
                                   int32_t iptr_bytes, const void *indices, int32_t idx_bytes, const float *data, int32_t validate) {
-    clear_error();
-    if (!out || !indptr) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
-    *out = nullptr;
-    OwnedCsmatF32 m;
-    SPRS_TRY(csmat_f32_upload(m, storage, rows, cols, indptr, iptr_bytes, indices, idx_bytes, data, validate));
-    *out = m.release();
-    return SPRS_HIP_OK;
+    return entry_upload(out, storage, rows, cols, indptr, iptr_bytes, indices, idx_bytes, data, validate);
 }
 
 int32_t sprs_hip_csmat_f32_wrap_device(sprs_hip_csmat_f32 **out, int32_t storage, uint64_t rows, uint64_t cols, uint64_t nnz,
                                        const void *dev_indptr, int32_t iptr_bytes, const void *dev_indices, int32_t idx_bytes,
                                        const float *dev_data) {
-    clear_error();
-    if (!out || !dev_indptr) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
-    *out = nullptr;
-    if (storage != SPRS_HIP_CSR && storage != SPRS_HIP_CSC) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "bad storage tag %d", storage);
-    if (!widths_ok(iptr_bytes, idx_bytes)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "index widths must be 4 or 8 bytes");
-    if (nnz && (!dev_indices || !dev_data)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL indices/data with nnz > 0");
-    if (((uintptr_t)dev_indptr | (uintptr_t)dev_indices | (uintptr_t)dev_data) & 15)
-        SPRS_FAIL(SPRS_HIP_INVALID_ARG, "device buffers must be 16-byte aligned");
-    int device = 0;
-    const hipError_t e = hipGetDevice(&device);
-    if (e != hipSuccess) return fail_hip(e, "hipGetDevice");
-    *out = view_csmat_f32(storage, rows, cols, nnz, dev_indptr, iptr_bytes, dev_indices, idx_bytes, dev_data, device);
-    return SPRS_HIP_OK;
+    return entry_wrap_device(out, storage, rows, cols, nnz, dev_indptr, iptr_bytes, dev_indices, idx_bytes, dev_data);
 }
 
 int32_t sprs_hip_csmat_f32_info(const sprs_hip_csmat_f32 *m, uint64_t *rows, uint64_t *cols, uint64_t *nnz, int32_t *iptr_bytes,
                                 int32_t *idx_bytes, int32_t *storage) {
-    clear_error();
-    if (!m) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
-    if (rows) *rows = m->rows;
-    if (cols) *cols = m->cols;
-    if (nnz) *nnz = m->nnz;
-    if (iptr_bytes) *iptr_bytes = m->iptr_bytes;
-    if (idx_bytes) *idx_bytes = m->idx_bytes;
-    if (storage) *storage = m->storage;
-    return SPRS_HIP_OK;
+    return entry_info(m, rows, cols, nnz, iptr_bytes, idx_bytes, storage);
 }
 
 int32_t sprs_hip_csmat_f32_device_ptrs(const sprs_hip_csmat_f32 *m, const void **indptr, const void **indices, const float **data) {
-    clear_error();
-    if (!m) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
-    if (indptr) *indptr = m->indptr;
-    if (indices) *indices = m->indices;
-    if (data) *data = m->data;
-    return SPRS_HIP_OK;
+    return entry_device_ptrs(m, indptr, indices, data);
 }
 
 int32_t sprs_hip_csmat_f32_download(const sprs_hip_csmat_f32 *m, void *indptr, void *indices, float *data) {
-    clear_error();
-    if (!m) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
-    if (indptr) SPRS_TRY_HIP(copy_to_host(indptr, m->indptr, (m->outer() + 1) * (uint64_t)m->iptr_bytes, nullptr));
-    if (indices && m->nnz) SPRS_TRY_HIP(copy_to_host(indices, m->indices, m->nnz * (uint64_t)m->idx_bytes, nullptr));
-    if (data && m->nnz) SPRS_TRY_HIP(copy_to_host(data, m->data, m->nnz * sizeof(float), nullptr));
-    return SPRS_HIP_OK;
+    return entry_download(m, indptr, indices, data);
 }
 
 int32_t sprs_hip_csmat_f32_transpose_view(const sprs_hip_csmat_f32 *m, sprs_hip_csmat_f32 **out) {
-    clear_error();
-    if (!m || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
-    *out = view_csmat_f32(m, true);
-    return SPRS_HIP_OK;
+    return entry_transpose_view(m, out);
 }
 
 int32_t sprs_hip_csmat_f32_refresh(sprs_hip_csmat_f32 *m) {
-    clear_error();
-    if (!m) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
-    SPRS_TRY_HIP(hipDeviceSynchronize());     // nothing in flight may still read the plan or the CSR copy
-    std::lock_guard<std::recursive_mutex> lock(m->mu);
-    invalidate_caches(m);
-    return SPRS_HIP_OK;
+    return entry_refresh(m);
 }
 
 int32_t sprs_hip_csmat_f32_prepare(sprs_hip_csmat_f32 *m, void *stream) {
-    clear_error();
-    if (!m) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
-    {
-        std::lock_guard<std::recursive_mutex> lock(m->mu);
-        m->prepared = true;
-    }
-    sprs_hip_csmat_f32 *csr = nullptr;
-    SPRS_TRY(csr_form_f32(m, &csr));
-    return spmv_f32_prepare(csr, (hipStream_t)stream);
+    return entry_prepare(m, stream);
 }
 
 int32_t sprs_hip_csmat_f32_free(sprs_hip_csmat_f32 *m) {
-    clear_error();
-    delete m;
-    return SPRS_HIP_OK;
+    return entry_free(m);
 }
 
 int32_t sprs_hip_csmat_f32_to_other_storage(const sprs_hip_csmat_f32 *m, sprs_hip_csmat_f32 **out) {
@@ -2336,149 +2333,43 @@ int32_t sprs_hip_csmat_f32_to_f64(const sprs_hip_csmat_f32 *m, sprs_hip_csmat **
 
 int32_t sprs_hip_spmv_f32(const sprs_hip_csmat_f32 *a, const float *x_dev, uint64_t x_len, float *y_dev, uint64_t y_len,
                           int32_t accumulate, void *stream) {
-    clear_error();
-    if (!a) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
-    // prod.rs:114-118: dimension check first, then storage
-    if (a->cols != x_len || a->rows != y_len) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
-    if (a->storage != SPRS_HIP_CSR) SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "Storage mismatch");
-    SPRS_TRY(vec_args_ok_f32(x_dev, x_len, y_dev, y_len));
-    return spmv_f32(const_cast<sprs_hip_csmat_f32 *>(a), x_dev, y_dev, accumulate != 0, (hipStream_t)stream);
+    return entry_spmv(a, x_dev, x_len, y_dev, y_len, accumulate, stream);
 }
 
 int32_t sprs_hip_mul_acc_mat_vec_csc_f32(const sprs_hip_csmat_f32 *a, const float *x_dev, uint64_t x_len, float *y_dev, uint64_t y_len,
                                          void *stream) {
-    clear_error();
-    if (!a) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
-    // prod.rs:88-92: dimensions first, then storage
-    if (a->cols != x_len || a->rows != y_len) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
-    if (a->storage != SPRS_HIP_CSC) SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "Storage mismatch");
-    SPRS_TRY(vec_args_ok_f32(x_dev, x_len, y_dev, y_len));
-    sprs_hip_csmat_f32 *csr = nullptr;
-    SPRS_TRY(csr_form_f32(a, &csr));
-    return spmv_f32(csr, x_dev, y_dev, true, (hipStream_t)stream);
+    return entry_mul_acc_mat_vec_csc(a, x_dev, x_len, y_dev, y_len, stream);
 }
 
 int32_t sprs_hip_csmat_mul_vec_f32(const sprs_hip_csmat_f32 *a, const float *x_dev, uint64_t x_len, float *y_dev, uint64_t y_len,
                                    void *stream) {
-    clear_error();
-    if (!a) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
-    if (a->cols != x_len || a->rows != y_len) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
-    SPRS_TRY(vec_args_ok_f32(x_dev, x_len, y_dev, y_len));
-    sprs_hip_csmat_f32 *csr = nullptr;
-    SPRS_TRY(csr_form_f32(a, &csr));
-    return spmv_f32(csr, x_dev, y_dev, false, (hipStream_t)stream);
+    return entry_csmat_mul_vec(a, x_dev, x_len, y_dev, y_len, stream);
 }
 
 int32_t sprs_hip_bicgstab_f32(sprs_hip_csmat_f32 *a, const float *x0_dev, const float *b_dev, uint64_t n, double tol, uint64_t max_iter,
                               double soft_restart_threshold, float *x_dev, sprs_hip_bicgstab_info *info, void *stream) {
-    clear_error();
-    if (!a) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
-    if (a->rows != a->cols || a->rows != n) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
-    if (n && (!x0_dev || !b_dev || !x_dev)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL vector");
-    if (x_dev == x0_dev || x_dev == b_dev) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "x_dev may not alias x0_dev / b_dev");
-    const float tol32 = (float)tol, thr32 = (float)soft_restart_threshold;   // f32 values that travelled as doubles
-    if (n == 0) {
-        // as sprs_hip_bicgstab_f64 with empty vectors: every norm is sqrt(0) = 0
-        const bool passes = max_iter > 0 && 0.0f < tol32;
-        const uint64_t it = passes ? 1 : max_iter;
-        if (info) *info = sprs_hip_bicgstab_info{it, 0, passes ? 1ull : 0ull, 0.0, 0.0, passes ? 1 : 0};
-        return SPRS_HIP_OK;
-    }
-    return bicgstab_f32(a, x0_dev, b_dev, n, tol32, max_iter, thr32, x_dev, info, (hipStream_t)stream);
+    return entry_bicgstab(a, x0_dev, b_dev, n, tol, max_iter, soft_restart_threshold, x_dev, info, stream);
 }
 
-// ---- f32 SpMM: the four dense products of an f32 handle (kernels: spmm_f32.hpp, spmm.hip) ----
 int32_t sprs_hip_spmm_rowmaj_f32(const sprs_hip_csmat_f32 *a, const float *rhs_dev, uint64_t rhs_rows, uint64_t k, uint64_t ld_rhs,
                                  float *out_dev, uint64_t out_rows, uint64_t ld_out, int32_t accumulate, void *stream) {
-    clear_error();
-    if (!a) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
-    // prod.rs:199-202: three dimension asserts, then storage
-    if (a->cols != rhs_rows || a->rows != out_rows) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
-    if (a->storage != SPRS_HIP_CSR) SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "Storage mismatch");
-    if (ld_rhs < k || ld_out < k) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "leading dimension smaller than the column count");
-    if (k && ((rhs_rows && !rhs_dev) || (out_rows && !out_dev))) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL matrix");
-    return spmm_strided_f32(const_cast<sprs_hip_csmat_f32 *>(a), rhs_dev, k, ld_rhs, 1, out_dev, ld_out, 1, accumulate != 0, (hipStream_t)stream);
+    return entry_spmm_rowmaj(a, rhs_dev, rhs_rows, k, ld_rhs, out_dev, out_rows, ld_out, accumulate, stream);
 }
 
 int32_t sprs_hip_csmat_mulacc_dense_f32(const sprs_hip_csmat_f32 *lhs, const float *rhs_dev, uint64_t rhs_rows, uint64_t k,
                                         int32_t rhs_layout, uint64_t ld_rhs, float *out_dev, uint64_t out_rows,
                                         int32_t out_layout, uint64_t ld_out, int32_t accumulate, void *stream) {
-    clear_error();
-    if (!lhs) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
-    if ((rhs_layout != SPRS_HIP_ROW_MAJOR && rhs_layout != SPRS_HIP_COL_MAJOR) || (out_layout != SPRS_HIP_ROW_MAJOR && out_layout != SPRS_HIP_COL_MAJOR))
-        SPRS_FAIL(SPRS_HIP_INVALID_ARG, "bad layout tag");
-    // prod.rs:199-201, 228-230, 257-259, 284-289: the dimension asserts of the four dense kernels
-    if (lhs->cols != rhs_rows || lhs->rows != out_rows) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
-    if (ld_rhs < (rhs_layout == SPRS_HIP_ROW_MAJOR ? k : rhs_rows) || ld_out < (out_layout == SPRS_HIP_ROW_MAJOR ? k : out_rows))
-        SPRS_FAIL(SPRS_HIP_INVALID_ARG, "leading dimension smaller than the extent it strides over");
-    if (k && ((rhs_rows && !rhs_dev) || (out_rows && !out_dev))) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL matrix");
-    if (k && rhs_rows && out_rows) {   // the two operands must not share an ELEMENT: the rule of sprs_hip_csmat_mulacc_dense_f64, in floats
-        const uint64_t span_r = (rhs_layout == SPRS_HIP_ROW_MAJOR ? rhs_rows - 1 : k - 1) * ld_rhs + (rhs_layout == SPRS_HIP_ROW_MAJOR ? k : rhs_rows);
-        const uint64_t span_o = (out_layout == SPRS_HIP_ROW_MAJOR ? out_rows - 1 : k - 1) * ld_out + (out_layout == SPRS_HIP_ROW_MAJOR ? k : out_rows);
-        if (rhs_dev < out_dev + span_o && out_dev < rhs_dev + span_r) {
-            bool disjoint = false;
-            if (rhs_layout == out_layout && ld_rhs == ld_out) {
-                const uint64_t w_r = rhs_layout == SPRS_HIP_ROW_MAJOR ? k : rhs_rows, w_o = out_layout == SPRS_HIP_ROW_MAJOR ? k : out_rows;
-                const uint64_t d = rhs_dev <= out_dev ? (uint64_t)(out_dev - rhs_dev) % ld_rhs : (ld_rhs - (uint64_t)(rhs_dev - out_dev) % ld_rhs) % ld_rhs;
-                disjoint = d >= w_r && d + w_o <= ld_rhs;   // inside one pitch: rhs lines occupy [0, w_r), out lines [d, d + w_o)
-            }
-            if (!disjoint) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "the result matrix overlaps the right-hand side");
-        }
-    }
-    sprs_hip_csmat_f32 *csr = nullptr;
-    SPRS_TRY(csr_form_f32(lhs, &csr));
-    hipStream_t st = (hipStream_t)stream;
-    if (rhs_layout == SPRS_HIP_COL_MAJOR && out_layout == SPRS_HIP_COL_MAJOR && k < 8) {
-        // csr_mulacc_dense_colmaj's shape (fewer than 8 columns, csmat.rs:2017-2045): column by column through the SpMV
-        for (uint64_t j = 0; j < k; ++j) SPRS_TRY(spmv_f32(csr, rhs_dev + j * ld_rhs, out_dev + j * ld_out, accumulate != 0, st));
-        return SPRS_HIP_OK;
-    }
-    const uint64_t rs_r = rhs_layout == SPRS_HIP_ROW_MAJOR ? ld_rhs : 1, cs_r = rhs_layout == SPRS_HIP_ROW_MAJOR ? 1 : ld_rhs;
-    const uint64_t rs_o = out_layout == SPRS_HIP_ROW_MAJOR ? ld_out : 1, cs_o = out_layout == SPRS_HIP_ROW_MAJOR ? 1 : ld_out;
-    return spmm_strided_f32(csr, rhs_dev, k, rs_r, cs_r, out_dev, rs_o, cs_o, accumulate != 0, st);
+    return entry_mulacc_dense(lhs, rhs_dev, rhs_rows, k, rhs_layout, ld_rhs, out_dev, out_rows, out_layout, ld_out, accumulate, stream);
 }
 
 int32_t sprs_hip_csmat_mul_dense_f32(const sprs_hip_csmat_f32 *lhs, const float *rhs_dev, uint64_t rhs_rows, uint64_t k,
                                      int32_t rhs_layout, uint64_t ld_rhs, float *out_dev, int32_t *out_layout, void *stream) {
-    clear_error();
-    if (!lhs || !out_layout) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
-    // csmat.rs:2002-2045: Array::zeros((rows, cols)) for >= 8 columns, Array::zeros((rows, cols).f()) below — in both storages
-    const int32_t lay = k >= 8 ? SPRS_HIP_ROW_MAJOR : SPRS_HIP_COL_MAJOR;
-    *out_layout = lay;
-    return sprs_hip_csmat_mulacc_dense_f32(lhs, rhs_dev, rhs_rows, k, rhs_layout, ld_rhs, out_dev, lhs->rows, lay,
-                                           lay == SPRS_HIP_ROW_MAJOR ? k : lhs->rows, 0, stream);
+    return entry_mul_dense(lhs, rhs_dev, rhs_rows, k, rhs_layout, ld_rhs, out_dev, out_layout, stream);
 }
 
 int32_t sprs_hip_dense_dot_csmat_f32(const float *lhs_dev, uint64_t lhs_rows, uint64_t lhs_cols, int32_t lhs_layout, uint64_t ld_lhs,
                                      const sprs_hip_csmat_f32 *rhs, float *out_dev, int32_t *out_layout, void *stream) {
-    clear_error();
-    if (!rhs || !out_layout) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
-    if (lhs_layout != SPRS_HIP_ROW_MAJOR && lhs_layout != SPRS_HIP_COL_MAJOR) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "bad layout tag");
-    // csmat.rs:2064-2117: (rhs^T * lhs^T)^T with free transposes.  The CSR form of rhs^T is the transpose view of a CSC rhs, or
-    // of the (cached) CSC copy of a CSR rhs; the view stays in the rhs handle under its lock, like t_view of the f64 handle
-    sprs_hip_csmat_f32 *owner = const_cast<sprs_hip_csmat_f32 *>(rhs);
-    std::lock_guard<std::recursive_mutex> lock(owner->mu);
-    if (!owner->t_view) {
-        const sprs_hip_csmat_f32 *src = rhs;
-        if (rhs->storage == SPRS_HIP_CSR) {
-            if (!owner->as_other) {
-                OwnedCsmatF32 other;
-                SPRS_TRY(csmat_f32_to_other_storage(rhs, other));
-                owner->as_other = other.release();
-                owner->as_other->prepared = owner->prepared;
-            }
-            src = owner->as_other;
-        }
-        owner->t_view = view_csmat_f32(src, true);
-    }
-    int32_t lay_t = 0;
-    // lhs^T: lhs_cols x lhs_rows, the other layout over the same memory
-    const int32_t st = sprs_hip_csmat_mul_dense_f32(owner->t_view, lhs_dev, lhs_cols, lhs_rows,
-                                                    lhs_layout == SPRS_HIP_ROW_MAJOR ? SPRS_HIP_COL_MAJOR : SPRS_HIP_ROW_MAJOR, ld_lhs, out_dev,
-                                                    &lay_t, stream);
-    if (st != SPRS_HIP_OK) return st;
-    *out_layout = lay_t == SPRS_HIP_ROW_MAJOR ? SPRS_HIP_COL_MAJOR : SPRS_HIP_ROW_MAJOR;     // reversed_axes()
-    return SPRS_HIP_OK;
+    return entry_dense_dot(lhs_dev, lhs_rows, lhs_cols, lhs_layout, ld_lhs, rhs, out_dev, out_layout, stream);
 }
 
 }  // extern "C"

@@ -187,12 +187,6 @@ __global__ void resid_kernel(const T *__restrict__ b, const T *__restrict__ v, u
     r[i] = b[i] - v[i];
 }
 
-// the two scalars the reference instantiates (bicgstab.rs:304-305): the handle type, its SpMV and its to_other_storage
-inline int32_t spmv_of(sprs_hip_csmat *a, const double *x, double *y, hipStream_t stream) { return spmv_f64(a, x, y, false, stream); }
-inline int32_t spmv_of(sprs_hip_csmat_f32 *a, const float *x, float *y, hipStream_t stream) { return spmv_f32(a, x, y, false, stream); }
-inline int32_t other_storage_of(const sprs_hip_csmat *m, OwnedCsmat &out) { return to_other_storage(m, out); }
-inline int32_t other_storage_of(const sprs_hip_csmat_f32 *m, OwnedCsmatF32 &out) { return csmat_f32_to_other_storage(m, out); }
-
 // Every host scalar (alpha, omega, beta, rho, err) is computed in T, in the reference's expression order; sqrt in T.
 template <typename T, typename MAT>
 int32_t bicgstab_impl(MAT *a_in, const T *x0, const T *b, uint64_t n, T tol, uint64_t max_iter, T soft_restart_threshold, T *x,
@@ -201,7 +195,7 @@ int32_t bicgstab_impl(MAT *a_in, const T *x0, const T *b, uint64_t n, T tol, uin
     MAT *a = a_in;
     std::unique_ptr<MAT> converted;
     if (a_in->storage != SPRS_HIP_CSR) {
-        SPRS_TRY(other_storage_of(a_in, converted));
+        SPRS_TRY(to_other_storage(a_in, converted));
         a = converted.get();
     }
 
@@ -233,7 +227,7 @@ int32_t bicgstab_impl(MAT *a_in, const T *x0, const T *b, uint64_t n, T tol, uin
     T d0 = T(0), d1 = T(0);
 
     // ---- new() ---------------------------------------------------------------------------------
-    SPRS_TRY(spmv_of(a, x0, v, stream));
+    SPRS_TRY(spmv(a, x0, v, false, stream));
     hipLaunchKernelGGL(init_kernel<T>, eg, eb, 0, stream, b, v, x0, n, r, rhat, p, x);
     SPRS_TRY_HIP(hipGetLastError());
     SPRS_TRY(dots(r, r, none, none, d0, d1));
@@ -245,12 +239,12 @@ int32_t bicgstab_impl(MAT *a_in, const T *x0, const T *b, uint64_t n, T tol, uin
     for (uint64_t k = 0; k < max_iter && !converged; ++k) {
         // ---- step() ----------------------------------------------------------------------------
         ++it;
-        SPRS_TRY(spmv_of(a, p, v, stream));
+        SPRS_TRY(spmv(a, p, v, false, stream));
         SPRS_TRY(dots(rhat, v, none, none, d0, d1));
         const T alpha = rho / d0;
         hipLaunchKernelGGL(hs_kernel<T>, eg, eb, 0, stream, x, p, r, v, alpha, n, h, s);
         SPRS_TRY_HIP(hipGetLastError());
-        SPRS_TRY(spmv_of(a, s, t, stream));
+        SPRS_TRY(spmv(a, s, t, false, stream));
         SPRS_TRY(dots(t, s, t, t, d0, d1));
         const T omega = d0 / d1;
         hipLaunchKernelGGL(xr_kernel<T>, eg, eb, 0, stream, h, s, t, omega, n, x, r);
@@ -271,7 +265,7 @@ int32_t bicgstab_impl(MAT *a_in, const T *x0, const T *b, uint64_t n, T tol, uin
         // ---- solve(): check the TRUE error before claiming convergence ---------------------------
         if (err < tol) {
             ++hard;
-            SPRS_TRY(spmv_of(a, x, v, stream));
+            SPRS_TRY(spmv(a, x, v, false, stream));
             hipLaunchKernelGGL(resid_kernel<T>, eg, eb, 0, stream, b, v, n, r);
             SPRS_TRY_HIP(hipGetLastError());
             SPRS_TRY(dots(r, r, none, none, d0, d1));

@@ -390,36 +390,47 @@ struct sprs_hip_ldl_num {
     sprs_hip::DevBuf l_data, d, row_vals;          // lnz values by column (l_data), n pivots, lnz values by row (for lsolve)
 };
 
-struct sprs_hip_csmat {
+namespace sprs_hip {
+// What the f64 and the f32 matrix handle share: the structure, the values as T, the owned blocks, the lock, the SpMM plan and the
+// cached derived handles.  The public structs below derive from it (Self = the deriving struct) and add only their own plans.
+// The owned blocks are members of this base, so they go after everything a deriving struct holds.
+template <typename T, typename Self>
+struct CsmatCore {
+    using value_type = T;
     int32_t storage = SPRS_HIP_CSR;
     uint64_t rows = 0, cols = 0, nnz = 0;
     int32_t iptr_bytes = 8, idx_bytes = 8;       // widths of the device arrays (4 or 8)
     // widths the CALLER declared (2, 4 or 8): sprs' SpIndex covers u16 / i16 too (indexing.rs:124-130).  2-byte arrays are
     // widened to 4 bytes on upload and narrowed on download; every value a result could hold is checked against the
-    // declared width where the reference's I::from_usize / Iptr::from_usize would panic.  0 = same as the device width.
+    // declared width where the reference's I::from_usize / Iptr::from_usize would panic.  0 = same as the device width
+    // (always so for an f32 handle: its host arrays are 4 or 8 bytes wide).
     int32_t decl_iptr_bytes = 0, decl_idx_bytes = 0;
     int32_t user_iptr_bytes() const { return decl_iptr_bytes ? decl_iptr_bytes : iptr_bytes; }
     int32_t user_idx_bytes() const { return decl_idx_bytes ? decl_idx_bytes : idx_bytes; }
     void *indptr = nullptr;    // device, outer+1 entries, zero based
     void *indices = nullptr;   // device, nnz entries
-    double *data = nullptr;    // device, nnz entries
-    uint64_t spmv_calls = 0;   // multiplies so far: the re-laid-out plan copies (banded / XCD-sliced) are built at the SECOND one (or by sprs_hip_csmat_prepare)
-    bool prepared = false;     // sprs_hip_csmat_prepare was called: the copy plans may be built at once
-    bool one_shot = false;     // the handle multiplies once (sprs_hip_spmv_f64_host): plain plan, no copies of the matrix
-    sprs_hip::PoolBlock own_data, own_indices, own_indptr;    // the blocks behind the arrays when the handle owns them (released indptr first)
+    T *data = nullptr;         // device, nnz entries
+    bool prepared = false;     // the prepare entry was called: the copy plans may be built at once (kept across refresh: the CSR copy of a CSC handle is prepared with it)
+    PoolBlock own_data, own_indices, own_indptr;    // the blocks behind the arrays when the handle owns them (released indptr first)
     int device = 0;
-    std::recursive_mutex mu;   // guards plan / mm: held from the look-up (or rebuild) of a plan until the kernels that read it are launched
+    std::recursive_mutex mu;   // guards the plans and as_other / t_view: held from the look-up (or rebuild) of a plan until the kernels that read it are launched
+    SpmmPlan mm;               // the SpMM plan (spmm.hip): value-agnostic
+    Self *t_view = nullptr;    // transpose view (of the CSC form) kept for dense . sparse products (sprs_hip_dense_dot_csmat_*): its SpMM / SpMV plans live as long as the values do; dropped with as_other
+    Self *as_other = nullptr;  // the handle in the OTHER storage order (to_other_storage, csmat.rs:1405-1426): made by the first product that needs it (a CSC operand of a dense product / SpMV runs on its CSR form), dropped by refresh / free
+
+    uint64_t outer() const { return storage == SPRS_HIP_CSR ? rows : cols; }
+    uint64_t inner() const { return storage == SPRS_HIP_CSR ? cols : rows; }
+};
+}  // namespace sprs_hip
+
+struct sprs_hip_csmat : sprs_hip::CsmatCore<double, sprs_hip_csmat> {
+    uint64_t spmv_calls = 0;   // multiplies so far: the re-laid-out plan copies (banded / XCD-sliced) are built at the SECOND one (or by sprs_hip_csmat_prepare)
+    bool one_shot = false;     // the handle multiplies once (sprs_hip_spmv_f64_host): plain plan, no copies of the matrix
     sprs_hip::SpmvPlan plan;
-    sprs_hip::SpmmPlan mm;
     sprs_hip::GsPlan gs;                 // rows by the levels of the stored c < row: Gauss-Seidel and the lower triangular solves
     sprs_hip::GsPlan tri_upper;          // the mirror (stored c > row, levels rising from the last row): the upper triangular solves (trisolve.hpp)
     sprs_hip::CsvecScratch cv;           // temporaries of the sparse-vector products that run on this handle (csvec.hpp)
     sprs_hip::SpTriScratch sp;           // scratch of the sparse-rhs triangular solve (sptrisolve.hpp): on the CSR form, beside gs
-    sprs_hip_csmat *t_view = nullptr;    // transpose view (of the CSC form) kept for dense . sparse products (sprs_hip_dense_dot_csmat_f64): its SpMM / SpMV plans live as long as the values do; dropped with as_other
-    sprs_hip_csmat *as_other = nullptr;  // the handle in the OTHER storage order (to_other_storage, csmat.rs:1405-1426): made by the first product that needs it (a CSC operand of a dense product / SpMV runs on its CSR form), dropped by refresh / free
-
-    uint64_t outer() const { return storage == SPRS_HIP_CSR ? rows : cols; }
-    uint64_t inner() const { return storage == SPRS_HIP_CSR ? cols : rows; }
     ~sprs_hip_csmat();         // handle.hpp: waits for the device when cached copies are held, drops them, then the blocks
 };
 
@@ -439,24 +450,8 @@ struct SpmvPlanF32 {
 
 // Device twin of CsMatBase for N = f32.  A type of its own, not a flag of sprs_hip_csmat: no entry that reads `double *data`
 // can be handed one (include/sprs_hip.h).  Index arrays are 4 or 8 bytes wide, on the host as on the device.
-struct sprs_hip_csmat_f32 {
-    int32_t storage = SPRS_HIP_CSR;
-    uint64_t rows = 0, cols = 0, nnz = 0;
-    int32_t iptr_bytes = 8, idx_bytes = 8;
-    void *indptr = nullptr;    // device, outer+1 entries, zero based
-    void *indices = nullptr;   // device, nnz entries
-    float *data = nullptr;     // device, nnz entries
-    bool prepared = false;     // sprs_hip_csmat_f32_prepare was called (kept across refresh: the CSR copy of a CSC handle is prepared with it)
-    sprs_hip::PoolBlock own_data, own_indices, own_indptr;    // the blocks behind the arrays when the handle owns them (released indptr first)
-    int device = 0;
-    std::recursive_mutex mu;   // guards plan / as_other, like sprs_hip_csmat::mu
+struct sprs_hip_csmat_f32 : sprs_hip::CsmatCore<float, sprs_hip_csmat_f32> {
     sprs_hip::SpmvPlanF32 plan;
-    sprs_hip::SpmmPlan mm;     // the SpMM plan (spmm.hip): value-agnostic, the same struct as the f64 handle's
-    sprs_hip_csmat_f32 *t_view = nullptr;     // transpose view (of the CSC form) kept for dense . sparse products (sprs_hip_dense_dot_csmat_f32), like sprs_hip_csmat::t_view
-    sprs_hip_csmat_f32 *as_other = nullptr;   // the handle in the other storage order: a CSC operand multiplies through its CSR form; dropped by refresh / free
-
-    uint64_t outer() const { return storage == SPRS_HIP_CSR ? rows : cols; }
-    uint64_t inner() const { return storage == SPRS_HIP_CSR ? cols : rows; }
     ~sprs_hip_csmat_f32();     // handle.hpp
 };
 
@@ -503,10 +498,12 @@ auto dispatch_host_width(int32_t bytes, F &&f) {
 // A handle and its owner: results travel as these below the ABI and are released to a raw pointer only in the extern "C"
 // function; a temporary (a converted operand, a slice) goes with the scope that made it.  `delete` is the whole release and
 // leaves the thread's error state alone.
-using OwnedCsmat = std::unique_ptr<sprs_hip_csmat>;
-using OwnedCsvec = std::unique_ptr<sprs_hip_csvec>;
-using OwnedPerm = std::unique_ptr<sprs_hip_perm>;
-using OwnedCsmatF32 = std::unique_ptr<sprs_hip_csmat_f32>;
+template <typename H>
+using Owned = std::unique_ptr<H>;
+using OwnedCsmat = Owned<sprs_hip_csmat>;
+using OwnedCsvec = Owned<sprs_hip_csvec>;
+using OwnedPerm = Owned<sprs_hip_perm>;
+using OwnedCsmatF32 = Owned<sprs_hip_csmat_f32>;
 
 // spmv_band.hip
 int32_t band_build(sprs_hip_csmat *a, hipStream_t stream, OwnedBandPlan &out);   // out stays empty when the plan does not apply
@@ -525,8 +522,6 @@ int32_t spgemm_plan_numeric(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, c
 uint64_t spgemm_plan_nnz(const sprs_hip_spgemm_plan *pl);
 void spgemm_plan_free(sprs_hip_spgemm_plan *pl);
 // spmm.hip
-int32_t spmm_rowmaj_f64(sprs_hip_csmat *a, const double *rhs, uint64_t k, uint64_t ld_rhs, double *out,
-                        uint64_t ld_out, bool accumulate, hipStream_t stream);
 int32_t spmm_strided_f64(sprs_hip_csmat *a, const double *rhs, uint64_t k, uint64_t rs_rhs, uint64_t cs_rhs, double *out,
                          uint64_t rs_out, uint64_t cs_out, bool accumulate, hipStream_t stream);
 int32_t spmm_strided_f32(sprs_hip_csmat_f32 *a, const float *rhs, uint64_t k, uint64_t rs_rhs, uint64_t cs_rhs, float *out,
@@ -650,12 +645,12 @@ sprs_hip_csmat *view_csmat(const sprs_hip_csmat *m, bool transpose, sprs_hip_csm
 int32_t copy_csmat(const sprs_hip_csmat *m, bool with_data, OwnedCsmat &out, hipStream_t stream);
 // everything a handle derives from its arrays (plans, row orders, the copy in the other storage order, the transpose view)
 void invalidate_caches(sprs_hip_csmat *m);
-// single precision (handle.hpp): an owned f32 matrix with uninitialised arrays, the two views, and an owned f32 matrix that takes
-// over the indptr and indices blocks of an owned f64 one (which is left without them) beside a fresh block of nnz floats
-int32_t make_csmat_f32(OwnedCsmatF32 &out, int32_t storage, uint64_t rows, uint64_t cols, uint64_t nnz, int32_t iptr_bytes, int32_t idx_bytes);
-sprs_hip_csmat_f32 *view_csmat_f32(int32_t storage, uint64_t rows, uint64_t cols, uint64_t nnz, const void *indptr, int32_t iptr_bytes,
-                                   const void *indices, int32_t idx_bytes, const float *data, int device);
-sprs_hip_csmat_f32 *view_csmat_f32(const sprs_hip_csmat_f32 *m, bool transpose);
+// single precision (handle.hpp): the same constructors for the f32 handle, and an owned f32 matrix that takes over the indptr
+// and indices blocks of an owned f64 one (which is left without them) beside a fresh block of nnz floats
+int32_t make_csmat(OwnedCsmatF32 &out, int32_t storage, uint64_t rows, uint64_t cols, uint64_t nnz, int32_t iptr_bytes, int32_t idx_bytes);
+sprs_hip_csmat_f32 *view_csmat(int32_t storage, uint64_t rows, uint64_t cols, uint64_t nnz, const void *indptr, int32_t iptr_bytes,
+                               const void *indices, int32_t idx_bytes, const float *data, int device, sprs_hip_csmat_f32 *into = nullptr);
+sprs_hip_csmat_f32 *view_csmat(const sprs_hip_csmat_f32 *m, bool transpose, sprs_hip_csmat_f32 *into = nullptr);
 int32_t adopt_structure_f32(sprs_hip_csmat *from, OwnedCsmatF32 &out);
 void invalidate_caches(sprs_hip_csmat_f32 *m);
 // spmv_f32.hpp (compiled in spmv.hip)
@@ -664,6 +659,27 @@ int32_t spmv_f32(sprs_hip_csmat_f32 *a, const float *x, float *y, bool accumulat
 int32_t csmat_f32_to_other_storage(const sprs_hip_csmat_f32 *m, OwnedCsmatF32 &out);             // complete at return
 int32_t csmat_f32_from_f64(const sprs_hip_csmat *m, OwnedCsmatF32 &out, hipStream_t stream);     // ordered on `stream`
 int32_t csmat_f32_to_f64(const sprs_hip_csmat_f32 *m, OwnedCsmat &out, hipStream_t stream);      // ordered on `stream`
+// one name per operation for code that is generic over the handle type (abi.hip, bicgstab.hip)
+inline int32_t spmv(sprs_hip_csmat *a, const double *x, double *y, bool accumulate, hipStream_t stream) { return spmv_f64(a, x, y, accumulate, stream); }
+inline int32_t spmv(sprs_hip_csmat_f32 *a, const float *x, float *y, bool accumulate, hipStream_t stream) { return spmv_f32(a, x, y, accumulate, stream); }
+inline int32_t spmv_prepare(sprs_hip_csmat_f32 *a, hipStream_t stream) { return spmv_f32_prepare(a, stream); }
+inline int32_t to_other_storage(const sprs_hip_csmat_f32 *m, OwnedCsmatF32 &out) { return csmat_f32_to_other_storage(m, out); }
+inline int32_t spmm_strided(sprs_hip_csmat *a, const double *rhs, uint64_t k, uint64_t rs_rhs, uint64_t cs_rhs, double *out, uint64_t rs_out,
+                            uint64_t cs_out, bool accumulate, hipStream_t stream) {
+    return spmm_strided_f64(a, rhs, k, rs_rhs, cs_rhs, out, rs_out, cs_out, accumulate, stream);
+}
+inline int32_t spmm_strided(sprs_hip_csmat_f32 *a, const float *rhs, uint64_t k, uint64_t rs_rhs, uint64_t cs_rhs, float *out, uint64_t rs_out,
+                            uint64_t cs_out, bool accumulate, hipStream_t stream) {
+    return spmm_strided_f32(a, rhs, k, rs_rhs, cs_rhs, out, rs_out, cs_out, accumulate, stream);
+}
+inline int32_t bicgstab(sprs_hip_csmat *a, const double *x0, const double *b, uint64_t n, double tol, uint64_t max_iter, double threshold, double *x,
+                        sprs_hip_bicgstab_info *info, hipStream_t stream) {
+    return bicgstab_f64(a, x0, b, n, tol, max_iter, threshold, x, info, stream);
+}
+inline int32_t bicgstab(sprs_hip_csmat_f32 *a, const float *x0, const float *b, uint64_t n, float tol, uint64_t max_iter, float threshold, float *x,
+                        sprs_hip_bicgstab_info *info, hipStream_t stream) {
+    return bicgstab_f32(a, x0, b, n, tol, max_iter, threshold, x, info, stream);
+}
 // abi.hip
 // a result inherits the declared index widths of its operand; INDEX_OVERFLOW where a value would not fit them
 int32_t inherit_declared_widths(sprs_hip_csmat *result, const sprs_hip_csmat *from);

@@ -1,5 +1,7 @@
 // The handles of libsprs_hip.so and the memory behind them: the pool of result blocks, the one constructor per kind of handle
 // (owned, view, device copy) and what `delete` does to a matrix.  No other file says `new sprs_hip_...`.
+// The f64 and the f32 matrix handle share their fields (CsmatCore, common.hpp), so each kind of matrix constructor is one
+// template on the handle type H; make_csmat / view_csmat are overloads that forward to it.
 // Host code only.  Included by abi.hip (one translation unit of the library and of the emulator build, tests/emu).
 #pragma once
 #include <map>
@@ -106,21 +108,35 @@ static int32_t take_blocks(int *device, std::initializer_list<std::pair<PoolBloc
     return e == hipSuccess ? (int32_t)SPRS_HIP_OK : fail_hip(e, what);
 }
 
-int32_t make_csmat(OwnedCsmat &out, int32_t storage, uint64_t rows, uint64_t cols, uint64_t nnz, int32_t iptr_bytes, int32_t idx_bytes) {
-    OwnedCsmat m(new sprs_hip_csmat());
+template <typename H>
+static void set_shape(H *m, int32_t storage, uint64_t rows, uint64_t cols, uint64_t nnz, int32_t iptr_bytes, int32_t idx_bytes) {
     m->storage = storage;
     m->rows = rows;
     m->cols = cols;
     m->nnz = nnz;
     m->iptr_bytes = iptr_bytes;
     m->idx_bytes = idx_bytes;
+}
+
+template <typename H>
+static int32_t make_matrix(Owned<H> &out, int32_t storage, uint64_t rows, uint64_t cols, uint64_t nnz, int32_t iptr_bytes, int32_t idx_bytes,
+                           const char *what) {
+    using T = typename H::value_type;
+    Owned<H> m(new H());
+    set_shape(m.get(), storage, rows, cols, nnz, iptr_bytes, idx_bytes);
     SPRS_TRY(take_blocks(&m->device, {{&m->own_indptr, (m->outer() + 1) * (uint64_t)iptr_bytes}, {&m->own_indices, nnz * (uint64_t)idx_bytes},
-                                      {&m->own_data, nnz * sizeof(double)}}, "alloc_csmat"));
+                                      {&m->own_data, nnz * sizeof(T)}}, what));
     m->indptr = m->own_indptr.p;
     m->indices = m->own_indices.p;
-    m->data = (double *)m->own_data.p;
+    m->data = (T *)m->own_data.p;
     out = std::move(m);
     return SPRS_HIP_OK;
+}
+int32_t make_csmat(OwnedCsmat &out, int32_t storage, uint64_t rows, uint64_t cols, uint64_t nnz, int32_t iptr_bytes, int32_t idx_bytes) {
+    return make_matrix(out, storage, rows, cols, nnz, iptr_bytes, idx_bytes, "alloc_csmat");
+}
+int32_t make_csmat(OwnedCsmatF32 &out, int32_t storage, uint64_t rows, uint64_t cols, uint64_t nnz, int32_t iptr_bytes, int32_t idx_bytes) {
+    return make_matrix(out, storage, rows, cols, nnz, iptr_bytes, idx_bytes, "alloc_csmat_f32");
 }
 
 int32_t make_csvec(OwnedCsvec &out, uint64_t dim, uint64_t nnz, int32_t idx_bytes, int32_t decl_idx_bytes) {
@@ -148,32 +164,10 @@ int32_t make_perm(OwnedPerm &out, uint64_t dim, int32_t idx_bytes, int32_t decl_
     return SPRS_HIP_OK;
 }
 
-int32_t make_csmat_f32(OwnedCsmatF32 &out, int32_t storage, uint64_t rows, uint64_t cols, uint64_t nnz, int32_t iptr_bytes, int32_t idx_bytes) {
-    OwnedCsmatF32 m(new sprs_hip_csmat_f32());
-    m->storage = storage;
-    m->rows = rows;
-    m->cols = cols;
-    m->nnz = nnz;
-    m->iptr_bytes = iptr_bytes;
-    m->idx_bytes = idx_bytes;
-    SPRS_TRY(take_blocks(&m->device, {{&m->own_indptr, (m->outer() + 1) * (uint64_t)iptr_bytes}, {&m->own_indices, nnz * (uint64_t)idx_bytes},
-                                      {&m->own_data, nnz * sizeof(float)}}, "alloc_csmat_f32"));
-    m->indptr = m->own_indptr.p;
-    m->indices = m->own_indices.p;
-    m->data = (float *)m->own_data.p;
-    out = std::move(m);
-    return SPRS_HIP_OK;
-}
-
 // the structure of `from` (an owned f64 matrix: a conversion result) moves into a new f32 handle; its values get a fresh block
 int32_t adopt_structure_f32(sprs_hip_csmat *from, OwnedCsmatF32 &out) {
     OwnedCsmatF32 m(new sprs_hip_csmat_f32());
-    m->storage = from->storage;
-    m->rows = from->rows;
-    m->cols = from->cols;
-    m->nnz = from->nnz;
-    m->iptr_bytes = from->iptr_bytes;
-    m->idx_bytes = from->idx_bytes;
+    set_shape(m.get(), from->storage, from->rows, from->cols, from->nnz, from->iptr_bytes, from->idx_bytes);
     SPRS_TRY(take_blocks(&m->device, {{&m->own_data, from->nnz * sizeof(float)}}, "alloc_csmat_f32"));
     m->own_indptr = std::move(from->own_indptr);
     m->own_indices = std::move(from->own_indices);
@@ -186,52 +180,38 @@ int32_t adopt_structure_f32(sprs_hip_csmat *from, OwnedCsmatF32 &out) {
 }
 
 // ---- views: the array pointers set, the owners empty ----------------------------------------------------
-sprs_hip_csmat *view_csmat(int32_t storage, uint64_t rows, uint64_t cols, uint64_t nnz, const void *indptr, int32_t iptr_bytes,
-                           const void *indices, int32_t idx_bytes, const double *data, int device, sprs_hip_csmat *into) {
-    sprs_hip_csmat *t = into ? into : new sprs_hip_csmat();
-    t->storage = storage;
-    t->rows = rows;
-    t->cols = cols;
-    t->nnz = nnz;
-    t->iptr_bytes = iptr_bytes;
-    t->idx_bytes = idx_bytes;
+template <typename H>
+static H *view_arrays(int32_t storage, uint64_t rows, uint64_t cols, uint64_t nnz, const void *indptr, int32_t iptr_bytes, const void *indices,
+                      int32_t idx_bytes, const typename H::value_type *data, int device, H *into) {
+    H *t = into ? into : new H();
+    set_shape(t, storage, rows, cols, nnz, iptr_bytes, idx_bytes);
     t->indptr = const_cast<void *>(indptr);
     t->indices = const_cast<void *>(indices);
-    t->data = const_cast<double *>(data);
+    t->data = const_cast<typename H::value_type *>(data);
     t->device = device;
     return t;
 }
 
-sprs_hip_csmat *view_csmat(const sprs_hip_csmat *m, bool transpose, sprs_hip_csmat *into) {
+template <typename H>
+static H *view_handle(const H *m, bool transpose, H *into) {
     const int32_t other = m->storage == SPRS_HIP_CSR ? SPRS_HIP_CSC : SPRS_HIP_CSR;
-    sprs_hip_csmat *t = view_csmat(transpose ? other : m->storage, transpose ? m->cols : m->rows, transpose ? m->rows : m->cols, m->nnz, m->indptr,
-                                   m->iptr_bytes, m->indices, m->idx_bytes, m->data, m->device, into);
+    H *t = view_arrays(transpose ? other : m->storage, transpose ? m->cols : m->rows, transpose ? m->rows : m->cols, m->nnz, m->indptr, m->iptr_bytes,
+                       m->indices, m->idx_bytes, m->data, m->device, into);
     t->decl_iptr_bytes = m->decl_iptr_bytes;
     t->decl_idx_bytes = m->decl_idx_bytes;
     return t;
 }
 
-sprs_hip_csmat_f32 *view_csmat_f32(int32_t storage, uint64_t rows, uint64_t cols, uint64_t nnz, const void *indptr, int32_t iptr_bytes,
-                                   const void *indices, int32_t idx_bytes, const float *data, int device) {
-    auto *t = new sprs_hip_csmat_f32();
-    t->storage = storage;
-    t->rows = rows;
-    t->cols = cols;
-    t->nnz = nnz;
-    t->iptr_bytes = iptr_bytes;
-    t->idx_bytes = idx_bytes;
-    t->indptr = const_cast<void *>(indptr);
-    t->indices = const_cast<void *>(indices);
-    t->data = const_cast<float *>(data);
-    t->device = device;
-    return t;
+sprs_hip_csmat *view_csmat(int32_t storage, uint64_t rows, uint64_t cols, uint64_t nnz, const void *indptr, int32_t iptr_bytes,
+                           const void *indices, int32_t idx_bytes, const double *data, int device, sprs_hip_csmat *into) {
+    return view_arrays(storage, rows, cols, nnz, indptr, iptr_bytes, indices, idx_bytes, data, device, into);
 }
-
-sprs_hip_csmat_f32 *view_csmat_f32(const sprs_hip_csmat_f32 *m, bool transpose) {
-    const int32_t other = m->storage == SPRS_HIP_CSR ? SPRS_HIP_CSC : SPRS_HIP_CSR;
-    return view_csmat_f32(transpose ? other : m->storage, transpose ? m->cols : m->rows, transpose ? m->rows : m->cols, m->nnz, m->indptr,
-                          m->iptr_bytes, m->indices, m->idx_bytes, m->data, m->device);
+sprs_hip_csmat_f32 *view_csmat(int32_t storage, uint64_t rows, uint64_t cols, uint64_t nnz, const void *indptr, int32_t iptr_bytes,
+                               const void *indices, int32_t idx_bytes, const float *data, int device, sprs_hip_csmat_f32 *into) {
+    return view_arrays(storage, rows, cols, nnz, indptr, iptr_bytes, indices, idx_bytes, data, device, into);
 }
+sprs_hip_csmat *view_csmat(const sprs_hip_csmat *m, bool transpose, sprs_hip_csmat *into) { return view_handle(m, transpose, into); }
+sprs_hip_csmat_f32 *view_csmat(const sprs_hip_csmat_f32 *m, bool transpose, sprs_hip_csmat_f32 *into) { return view_handle(m, transpose, into); }
 
 sprs_hip_csvec *view_csvec(uint64_t dim, uint64_t nnz, const void *indices, int32_t idx_bytes, const double *data, int device) {
     auto *v = new sprs_hip_csvec();
@@ -283,26 +263,27 @@ int32_t copy_csmat(const sprs_hip_csmat *m, bool with_data, OwnedCsmat &out, hip
 // storage order and the transpose view kept for dense . sparse products.  Called whenever the values (or the arrays) change:
 // refresh, delete and BOTH numeric SpGEMM entries, which rewrite C's values in place (a stale CSC copy of C
 // would otherwise serve later products).
-void invalidate_caches(sprs_hip_csmat *m) {
-    m->plan = SpmvPlan();
+template <typename H>
+static void drop_shared_caches(H *m) {
     m->mm = SpmmPlan();
-    m->gs = GsPlan();
-    m->tri_upper = GsPlan();
-    m->cv = CsvecScratch();
-    m->sp = SpTriScratch();
     delete m->t_view;
     m->t_view = nullptr;
     delete m->as_other;
     m->as_other = nullptr;
 }
 
+void invalidate_caches(sprs_hip_csmat *m) {
+    m->plan = SpmvPlan();
+    m->gs = GsPlan();
+    m->tri_upper = GsPlan();
+    m->cv = CsvecScratch();
+    m->sp = SpTriScratch();
+    drop_shared_caches(m);
+}
+
 void invalidate_caches(sprs_hip_csmat_f32 *m) {
     m->plan = SpmvPlanF32();
-    m->mm = SpmmPlan();
-    delete m->t_view;
-    m->t_view = nullptr;
-    delete m->as_other;
-    m->as_other = nullptr;
+    drop_shared_caches(m);
 }
 
 }  // namespace sprs_hip

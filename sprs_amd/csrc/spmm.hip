@@ -734,9 +734,4 @@ int32_t spmm_strided_f32(sprs_hip_csmat_f32 *a, const float *rhs, uint64_t k, ui
     });
 }
 
-int32_t spmm_rowmaj_f64(sprs_hip_csmat *a, const double *rhs, uint64_t k, uint64_t ld_rhs, double *out,
-                        uint64_t ld_out, bool accumulate, hipStream_t stream) {
-    return spmm_strided_f64(a, rhs, k, ld_rhs, 1, out, ld_out, 1, accumulate, stream);
-}
-
 }  // namespace sprs_hip

@@ -224,7 +224,7 @@ inline dim3 entry_grid(uint64_t n) { return dim3((unsigned)((n + ENTRY_TILE - 1)
 int32_t csmat_f32_from_f64(const sprs_hip_csmat *m, OwnedCsmatF32 &out, hipStream_t stream) {
     if (m->nnz > 0x7fffffffull * ENTRY_TILE) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "too many entries for one launch");
     OwnedCsmatF32 res;
-    SPRS_TRY(make_csmat_f32(res, m->storage, m->rows, m->cols, m->nnz, m->iptr_bytes, m->idx_bytes));
+    SPRS_TRY(make_csmat(res, m->storage, m->rows, m->cols, m->nnz, m->iptr_bytes, m->idx_bytes));
     SPRS_TRY_HIP(hipMemcpyAsync(res->indptr, m->indptr, (m->outer() + 1) * (uint64_t)m->iptr_bytes, hipMemcpyDeviceToDevice, stream));
     if (m->nnz) {
         SPRS_TRY_HIP(hipMemcpyAsync(res->indices, m->indices, m->nnz * (uint64_t)m->idx_bytes, hipMemcpyDeviceToDevice, stream));

@@ -16,16 +16,18 @@ def _vp(a):
     return C.c_void_p(a.ctypes.data) if a.size else C.c_void_p(0)
 
 
-class DeviceVec:
-    """A dense f64 vector in HBM.  Either owns its buffer or borrows one
-    (e.g. a torch tensor's `data_ptr()`), like a `&mut [f64]` would."""
+class _DeviceVecBase:
+    """What DeviceVec and DeviceVecF32 share: a dense vector in HBM of the subclass's element type.  The two are SIBLINGS: an
+    isinstance test for one never admits the other, so no entry that reads n doubles is handed n floats."""
+    _dtype = None          # numpy element type
+    _itemsize = 0
 
     def __init__(self, n, ptr=None, owner=None):
         self.n = int(n)
         self._owner = owner
         if ptr is None:
             p = C.c_void_p()
-            check(lib.sprs_hip_malloc(C.byref(p), self.n * 8))
+            check(lib.sprs_hip_malloc(C.byref(p), self.n * self._itemsize))
             self.ptr = p.value
             self._owned = True
         else:
@@ -34,27 +36,22 @@ class DeviceVec:
 
     @classmethod
     def from_host(cls, arr):
-        arr = np.ascontiguousarray(arr, dtype=np.float64)
+        """casts to the element type (numpy's astype: round to nearest even)"""
+        arr = np.ascontiguousarray(arr, dtype=cls._dtype)
         v = cls(arr.size)
-        check(lib.sprs_hip_memcpy_h2d(C.c_void_p(v.ptr), _vp(arr), arr.size * 8))
+        check(lib.sprs_hip_memcpy_h2d(C.c_void_p(v.ptr), _vp(arr), arr.size * cls._itemsize))
         return v
 
     @classmethod
     def zeros(cls, n):
         v = cls(n)
-        check(lib.sprs_hip_memset(C.c_void_p(v.ptr), 0, v.n * 8, None))
+        check(lib.sprs_hip_memset(C.c_void_p(v.ptr), 0, v.n * cls._itemsize, None))
         return v
 
-    @classmethod
-    def borrow(cls, tensor):
-        """Borrow a contiguous float64 torch CUDA tensor (no copy)."""
-        assert tensor.is_cuda and tensor.is_contiguous() and tensor.element_size() == 8
-        return cls(tensor.numel(), ptr=tensor.data_ptr(), owner=tensor)
-
     def to_host(self):
-        out = np.empty(self.n, dtype=np.float64)
+        out = np.empty(self.n, dtype=self._dtype)
         check(lib.sprs_hip_synchronize(None))
-        check(lib.sprs_hip_memcpy_d2h(_vp(out), C.c_void_p(self.ptr), self.n * 8))
+        check(lib.sprs_hip_memcpy_d2h(_vp(out), C.c_void_p(self.ptr), self.n * self._itemsize))
         return out
 
     def dim(self):   # DenseVector::dim, dense_vector.rs:14
@@ -69,35 +66,22 @@ class DeviceVec:
             self.ptr = 0
 
 
-class DeviceVecF32:
+class DeviceVec(_DeviceVecBase):
+    """A dense f64 vector in HBM.  Either owns its buffer or borrows one
+    (e.g. a torch tensor's `data_ptr()`), like a `&mut [f64]` would."""
+    _dtype, _itemsize = np.float64, 8
+
+    @classmethod
+    def borrow(cls, tensor):
+        """Borrow a contiguous float64 torch CUDA tensor (no copy)."""
+        assert tensor.is_cuda and tensor.is_contiguous() and tensor.element_size() == 8
+        return cls(tensor.numel(), ptr=tensor.data_ptr(), owner=tensor)
+
+
+class DeviceVecF32(_DeviceVecBase):
     """A dense f32 vector in HBM: the operand and result type of the single-precision products (DeviceCsMatF32).  Not a
     DeviceVec: an entry that reads n doubles must never be handed n floats."""
-
-    def __init__(self, n, ptr=None, owner=None):
-        self.n = int(n)
-        self._owner = owner
-        if ptr is None:
-            p = C.c_void_p()
-            check(lib.sprs_hip_malloc(C.byref(p), self.n * 4))
-            self.ptr = p.value
-            self._owned = True
-        else:
-            self.ptr = int(ptr)
-            self._owned = False
-
-    @classmethod
-    def from_host(cls, arr):
-        """casts to float32 (numpy's astype: round to nearest even)"""
-        arr = np.ascontiguousarray(arr, dtype=np.float32)
-        v = cls(arr.size)
-        check(lib.sprs_hip_memcpy_h2d(C.c_void_p(v.ptr), _vp(arr), arr.size * 4))
-        return v
-
-    @classmethod
-    def zeros(cls, n):
-        v = cls(n)
-        check(lib.sprs_hip_memset(C.c_void_p(v.ptr), 0, v.n * 4, None))
-        return v
+    _dtype, _itemsize = np.float32, 4
 
     @classmethod
     def borrow(cls, tensor):
@@ -107,39 +91,33 @@ class DeviceVecF32:
         assert tensor.is_cuda and tensor.is_contiguous()
         return cls(tensor.numel(), ptr=tensor.data_ptr(), owner=tensor)
 
-    def to_host(self):
-        out = np.empty(self.n, dtype=np.float32)
-        check(lib.sprs_hip_synchronize(None))
-        check(lib.sprs_hip_memcpy_d2h(_vp(out), C.c_void_p(self.ptr), self.n * 4))
-        return out
 
-    def dim(self):
-        return self.n
+class _DeviceCsMatBase:
+    """The container part DeviceCsMat and DeviceCsMatF32 share: a CSR/CSC matrix whose indptr / indices / data live in HBM
+    behind a handle of the subclass's type.  The two are SIBLINGS (see _DeviceVecBase).  Every entry is looked up by the
+    class: _c("info") is sprs_hip_csmat_info or sprs_hip_csmat_f32_info, _op("spmv") sprs_hip_spmv_f64 or sprs_hip_spmv_f32."""
+    _dtype = None          # numpy type of the values
+    _vec_type = None       # the dense vector class of the same precision
+    _container, _suffix = None, None
 
-    def __len__(self):
-        return self.n
+    @classmethod
+    def _c(cls, name):
+        return getattr(lib, cls._container + name)
 
-    def __del__(self):
-        if getattr(self, "_owned", False) and self.ptr:
-            lib.sprs_hip_free(C.c_void_p(self.ptr))
-            self.ptr = 0
-
-
-class DeviceCsMat:
-    """A CSR/CSC matrix whose indptr / indices / data live in HBM behind a
-    `sprs_hip_csmat*` handle."""
+    @classmethod
+    def _op(cls, name):
+        return getattr(lib, "sprs_hip_%s_%s" % (name, cls._suffix))
 
     def __init__(self, handle, keep=None):
         self._h = C.c_void_p(handle)
         self._keep = keep   # objects the handle borrows from
 
-    # -- constructors -------------------------------------------------------
     @classmethod
     def from_host(cls, shape, indptr, indices, data, storage=CSR, validate=True):
-        """CsMat::new / new_csc when validate (csmat.rs:146-166), new_trusted otherwise."""
+        """CsMat::new / new_csc when validate (csmat.rs:146-166), new_trusted otherwise; data is cast to the class's type."""
         indptr = np.ascontiguousarray(indptr)
         indices = np.ascontiguousarray(indices)
-        data = np.ascontiguousarray(data, dtype=np.float64)
+        data = np.ascontiguousarray(data, dtype=cls._dtype)
         if indptr.dtype.kind not in "iu" or indices.dtype.kind not in "iu":
             raise TypeError("integer index arrays expected")
         if indices.size != data.size:
@@ -150,11 +128,89 @@ class DeviceCsMat:
         if validate and int(indptr[-1]) - int(indptr[0]) != indices.size:
             raise _ffi.SprsHipError(_ffi.BAD_STRUCTURE, "Indices length and inpdtr's nnz do not match")
         h = C.c_void_p()
-        check(lib.sprs_hip_csmat_upload(C.byref(h), storage, shape[0], shape[1], _vp(indptr),
-                                        indptr.dtype.itemsize, _vp(indices), indices.dtype.itemsize,
-                                        _vp(data), 1 if validate else 0))
+        check(cls._c("upload")(C.byref(h), storage, shape[0], shape[1], _vp(indptr), indptr.dtype.itemsize, _vp(indices),
+                               indices.dtype.itemsize, _vp(data), 1 if validate else 0))
         return cls(h.value)
 
+    @classmethod
+    def _wrap_torch(cls, shape, indptr_t, indices_t, data_t, storage):
+        h = C.c_void_p()
+        check(cls._c("wrap_device")(
+            C.byref(h), storage, shape[0], shape[1], indices_t.numel(),
+            C.c_void_p(indptr_t.data_ptr()), indptr_t.element_size(),
+            C.c_void_p(indices_t.data_ptr() if indices_t.numel() else 0), indices_t.element_size(),
+            C.c_void_p(data_t.data_ptr() if data_t.numel() else 0)))
+        return cls(h.value, keep=(indptr_t, indices_t, data_t))
+
+    # -- accessors ------------------------------------------------------------
+    def _info(self):
+        r, c, n = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        pb, ib, st = C.c_int32(), C.c_int32(), C.c_int32()
+        check(self._c("info")(self._h, C.byref(r), C.byref(c), C.byref(n), C.byref(pb), C.byref(ib), C.byref(st)))
+        return r.value, c.value, n.value, pb.value, ib.value, st.value
+
+    def rows(self): return self._info()[0]
+    def cols(self): return self._info()[1]
+    def shape(self): return self._info()[:2]
+    def nnz(self): return self._info()[2]
+    def storage(self): return self._info()[5]
+    def is_csr(self): return self.storage() == CSR
+    def is_csc(self): return self.storage() == CSC
+    def index_bytes(self): return self._info()[4]
+    def indptr_bytes(self): return self._info()[3]
+
+    def device_ptrs(self):
+        """-> (indptr, indices, data) device addresses (into_raw_storage), still owned by the handle"""
+        a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(self._c("device_ptrs")(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def to_host(self):
+        """-> (shape, indptr, indices, data) numpy arrays (into_raw_storage, csmat.rs:946-954)."""
+        r, c, n, pb, ib, st = self._info()
+        outer = r if st == CSR else c
+        indptr = np.empty(outer + 1, dtype=_DT[pb])
+        indices = np.empty(n, dtype=_DT[ib])
+        data = np.empty(n, dtype=self._dtype)
+        check(self._c("download")(self._h, _vp(indptr), _vp(indices), _vp(data)))
+        return (r, c), indptr, indices, data
+
+    def refresh(self):
+        """Drop the cached multiply plans and the CSR form after the wrapped device arrays were modified in place."""
+        check(self._c("refresh")(self._h))
+
+    def prepare(self, stream=None):
+        """Build the full SpMV plan (and `stream`'s scratch) now.  f64: without it the re-laid-out copy plans come with the
+        SECOND multiply of the handle — the first one runs on the plain tile index.  f32: needed before an SpMV on a capturing
+        stream."""
+        check(self._c("prepare")(self._h, _stream_arg(stream)))
+        return self
+
+    def transpose_view(self):
+        """csmat.rs:982-991: free, shares buffers."""
+        h = C.c_void_p()
+        check(self._c("transpose_view")(self._h, C.byref(h)))
+        return type(self)(h.value, keep=self)
+
+    def to_other_storage(self):
+        """csmat.rs:1405-1426."""
+        h = C.c_void_p()
+        check(self._c("to_other_storage")(self._h, C.byref(h)))
+        return type(self)(h.value)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            self._c("free")(h)
+            self._h = C.c_void_p(0)
+
+
+class DeviceCsMat(_DeviceCsMatBase):
+    """A CSR/CSC matrix whose indptr / indices / data live in HBM behind a
+    `sprs_hip_csmat*` handle."""
+    _dtype, _container, _suffix = np.float64, "sprs_hip_csmat_", "f64"
+
+    # -- constructors -------------------------------------------------------
     @classmethod
     def new_from_unsorted(cls, shape, indptr, indices, data, storage=CSR, stream=None):
         """CsMat::new_from_unsorted (csmat.rs:374-384): host arrays whose outer slices need not be sorted; they are uploaded as
@@ -183,16 +239,6 @@ class DeviceCsMat:
         return m
 
     @classmethod
-    def _wrap_torch(cls, shape, indptr_t, indices_t, data_t, storage):
-        h = C.c_void_p()
-        check(lib.sprs_hip_csmat_wrap_device(
-            C.byref(h), storage, shape[0], shape[1], indices_t.numel(),
-            C.c_void_p(indptr_t.data_ptr()), indptr_t.element_size(),
-            C.c_void_p(indices_t.data_ptr() if indices_t.numel() else 0), indices_t.element_size(),
-            C.c_void_p(data_t.data_ptr() if data_t.numel() else 0)))
-        return cls(h.value, keep=(indptr_t, indices_t, data_t))
-
-    @classmethod
     def eye(cls, dim, idx_dtype=np.uint64, ptr_dtype=np.uint64):
         """CsMatI::eye (csmat.rs:416-426)."""
         return cls.from_host((dim, dim), np.arange(dim + 1, dtype=ptr_dtype),
@@ -214,34 +260,6 @@ class DeviceCsMat:
         """CsMat::to_dense (csmat.rs:1127-1134) as a prod.DeviceMat in standard layout (or into `out`)."""
         from . import to_dense
         return to_dense.to_dense(self, out, stream)
-
-    # -- accessors ------------------------------------------------------------
-    def _info(self):
-        r, c, n = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        pb, ib, st = C.c_int32(), C.c_int32(), C.c_int32()
-        check(lib.sprs_hip_csmat_info(self._h, C.byref(r), C.byref(c), C.byref(n), C.byref(pb),
-                                      C.byref(ib), C.byref(st)))
-        return r.value, c.value, n.value, pb.value, ib.value, st.value
-
-    def rows(self): return self._info()[0]
-    def cols(self): return self._info()[1]
-    def shape(self): return self._info()[:2]
-    def nnz(self): return self._info()[2]
-    def storage(self): return self._info()[5]
-    def is_csr(self): return self.storage() == CSR
-    def is_csc(self): return self.storage() == CSC
-    def index_bytes(self): return self._info()[4]
-    def indptr_bytes(self): return self._info()[3]
-
-    def to_host(self):
-        """-> (shape, indptr, indices, data) numpy arrays (into_raw_storage, csmat.rs:946-954)."""
-        r, c, n, pb, ib, st = self._info()
-        outer = r if st == CSR else c
-        indptr = np.empty(outer + 1, dtype=_DT[pb])
-        indices = np.empty(n, dtype=_DT[ib])
-        data = np.empty(n, dtype=np.float64)
-        check(lib.sprs_hip_csmat_download(self._h, _vp(indptr), _vp(indices), _vp(data)))
-        return (r, c), indptr, indices, data
 
     def slice_outer_to_host(self, start, end):
         """Rows [start, end) as a host view: indptr NOT rebased (slicing.rs:65-89)."""
@@ -275,34 +293,11 @@ class DeviceCsMat:
         _ffi.check_structure_status(lib.sprs_hip_csmat_from_unsorted(self._h, C.byref(h), C.byref(info), _stream_arg(stream)), info)
         return DeviceCsMat(h.value)
 
-    def refresh(self):
-        """Drop the cached multiply plans after the wrapped device arrays were modified in place."""
-        check(lib.sprs_hip_csmat_refresh(self._h))
-
-    def prepare(self, stream=None):
-        """Build the full SpMV plan now (sprs_hip_csmat_prepare): without it the re-laid-out copy plans come with the SECOND
-        multiply of the handle — the first one runs on the plain tile index."""
-        sp = C.c_void_p(stream.cuda_stream) if stream is not None and hasattr(stream, "cuda_stream") else C.c_void_p(stream or 0)
-        check(lib.sprs_hip_csmat_prepare(self._h, sp))
-        return self
-
     def spmv_plan_info(self):
         """-> (kind, plan_bytes): 0 none yet, 1 nnz tiles, 2 XCD-sliced copy, 3 banded copy (hot columns from LDS)."""
         kind, nbytes = C.c_int32(), C.c_uint64()
         check(lib.sprs_hip_csmat_spmv_plan_info(self._h, C.byref(kind), C.byref(nbytes)))
         return kind.value, nbytes.value
-
-    def transpose_view(self):
-        """csmat.rs:982-991: free, shares buffers."""
-        h = C.c_void_p()
-        check(lib.sprs_hip_csmat_transpose_view(self._h, C.byref(h)))
-        return DeviceCsMat(h.value, keep=self)
-
-    def to_other_storage(self):
-        """csmat.rs:1405-1426."""
-        h = C.c_void_p()
-        check(lib.sprs_hip_csmat_to_other_storage(self._h, C.byref(h)))
-        return DeviceCsMat(h.value)
 
     def to_f32(self, stream=None):
         """CsMat::map(|&v| v as f32) (csmat.rs:1289-1305) as a DeviceCsMatF32: the structure copied, the values rounded to
@@ -432,114 +427,25 @@ class DeviceCsMat:
             return binop.sub_mat(self, rhs)               # binop.rs:99-111
         return NotImplemented
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            lib.sprs_hip_csmat_free(h)
-            self._h = C.c_void_p(0)
-
-
-class DeviceCsMatF32:
+class DeviceCsMatF32(_DeviceCsMatBase):
     """A CSR/CSC matrix of f32 values in HBM behind a `sprs_hip_csmat_f32*` handle: CsMat<f32>.  Built for it: the container,
     `&A * &x` and the two mul_acc forms with DeviceVecF32, `&A * &B` and the four mulacc_dense forms with prod.DeviceMatF32,
     prod.dense_dot_csmat (prod.py), BiCGSTAB (linalg.py); `to_f64()` reaches every other
     operation.  Index arrays are 4 or 8 bytes wide (no 2-byte ones)."""
-
-    def __init__(self, handle, keep=None):
-        self._h = C.c_void_p(handle)
-        self._keep = keep   # objects the handle borrows from
-
-    @classmethod
-    def from_host(cls, shape, indptr, indices, data, storage=CSR, validate=True):
-        """CsMat::new / new_csc when validate, new_trusted otherwise; data is cast to float32."""
-        indptr = np.ascontiguousarray(indptr)
-        indices = np.ascontiguousarray(indices)
-        data = np.ascontiguousarray(data, dtype=np.float32)
-        if indptr.dtype.kind not in "iu" or indices.dtype.kind not in "iu":
-            raise TypeError("integer index arrays expected")
-        if indices.size != data.size:
-            raise _ffi.SprsHipError(_ffi.BAD_STRUCTURE, "indices and data lengths differ")
-        outer = shape[0] if storage == CSR else shape[1]
-        if indptr.size != outer + 1:
-            raise _ffi.SprsHipError(_ffi.BAD_STRUCTURE, "Indptr length does not match dimension")
-        if validate and int(indptr[-1]) - int(indptr[0]) != indices.size:
-            raise _ffi.SprsHipError(_ffi.BAD_STRUCTURE, "Indices length and inpdtr's nnz do not match")
-        h = C.c_void_p()
-        check(lib.sprs_hip_csmat_f32_upload(C.byref(h), storage, shape[0], shape[1], _vp(indptr), indptr.dtype.itemsize,
-                                            _vp(indices), indices.dtype.itemsize, _vp(data), 1 if validate else 0))
-        return cls(h.value)
+    _dtype, _container, _suffix = np.float32, "sprs_hip_csmat_f32_", "f32"
 
     @classmethod
     def wrap_torch(cls, shape, indptr_t, indices_t, data_t, storage=CSR):
         """Borrow torch CUDA tensors (int32 / int64 index arrays, float32 data) as the three arrays (no copy)."""
         if data_t.element_size() != 4 or not data_t.is_floating_point():
             raise TypeError("float32 data expected")
-        h = C.c_void_p()
-        check(lib.sprs_hip_csmat_f32_wrap_device(
-            C.byref(h), storage, shape[0], shape[1], indices_t.numel(),
-            C.c_void_p(indptr_t.data_ptr()), indptr_t.element_size(),
-            C.c_void_p(indices_t.data_ptr() if indices_t.numel() else 0), indices_t.element_size(),
-            C.c_void_p(data_t.data_ptr() if data_t.numel() else 0)))
-        return cls(h.value, keep=(indptr_t, indices_t, data_t))
-
-    def _info(self):
-        r, c, n = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        pb, ib, st = C.c_int32(), C.c_int32(), C.c_int32()
-        check(lib.sprs_hip_csmat_f32_info(self._h, C.byref(r), C.byref(c), C.byref(n), C.byref(pb), C.byref(ib), C.byref(st)))
-        return r.value, c.value, n.value, pb.value, ib.value, st.value
-
-    def rows(self): return self._info()[0]
-    def cols(self): return self._info()[1]
-    def shape(self): return self._info()[:2]
-    def nnz(self): return self._info()[2]
-    def storage(self): return self._info()[5]
-    def is_csr(self): return self.storage() == CSR
-    def is_csc(self): return self.storage() == CSC
-    def index_bytes(self): return self._info()[4]
-    def indptr_bytes(self): return self._info()[3]
-
-    def device_ptrs(self):
-        """-> (indptr, indices, data) device addresses (into_raw_storage), still owned by the handle"""
-        a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        check(lib.sprs_hip_csmat_f32_device_ptrs(self._h, C.byref(a), C.byref(b), C.byref(c)))
-        return a.value, b.value, c.value
-
-    def to_host(self):
-        """-> (shape, indptr, indices, data) numpy arrays, data float32"""
-        r, c, n, pb, ib, st = self._info()
-        outer = r if st == CSR else c
-        indptr = np.empty(outer + 1, dtype=_DT[pb])
-        indices = np.empty(n, dtype=_DT[ib])
-        data = np.empty(n, dtype=np.float32)
-        check(lib.sprs_hip_csmat_f32_download(self._h, _vp(indptr), _vp(indices), _vp(data)))
-        return (r, c), indptr, indices, data
-
-    def transpose_view(self):
-        """csmat.rs:982-991: free, shares buffers."""
-        h = C.c_void_p()
-        check(lib.sprs_hip_csmat_f32_transpose_view(self._h, C.byref(h)))
-        return DeviceCsMatF32(h.value, keep=self)
-
-    def to_other_storage(self):
-        """csmat.rs:1405-1426."""
-        h = C.c_void_p()
-        check(lib.sprs_hip_csmat_f32_to_other_storage(self._h, C.byref(h)))
-        return DeviceCsMatF32(h.value)
+        return cls._wrap_torch(shape, indptr_t, indices_t, data_t, storage)
 
     def to_f64(self, stream=None):
         """CsMat::map(|&v| v as f64): exact."""
         h = C.c_void_p()
         check(lib.sprs_hip_csmat_f32_to_f64(self._h, C.byref(h), _stream_arg(stream)))
         return DeviceCsMat(h.value)
-
-    def prepare(self, stream=None):
-        """Build the SpMV plan (and `stream`'s carry array) now: needed before an SpMV on a capturing stream."""
-        check(lib.sprs_hip_csmat_f32_prepare(self._h, _stream_arg(stream)))
-        return self
-
-    def refresh(self):
-        """Drop the cached plan and CSR form after the wrapped device arrays were modified in place."""
-        check(lib.sprs_hip_csmat_f32_refresh(self._h))
 
     def __mul__(self, rhs):
         from . import prod
@@ -555,11 +461,8 @@ class DeviceCsMatF32:
 
     __matmul__ = __mul__
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            lib.sprs_hip_csmat_f32_free(h)
-            self._h = C.c_void_p(0)
+
+DeviceCsMat._vec_type, DeviceCsMatF32._vec_type = DeviceVec, DeviceVecF32
 
 
 def _stream_arg(stream):

@@ -37,19 +37,12 @@ class BiCGSTAB:
         f32 = isinstance(a, DeviceCsMatF32)
         if isinstance(x0, DeviceVecF32) != f32 or isinstance(b, DeviceVecF32) != f32:
             raise TypeError("matrix and vectors must have the same precision")
-        if f32:
-            import numpy as np
-            x = DeviceVecF32(n)
-            info = _Info()
-            check(lib.sprs_hip_bicgstab_f32(a._h, C.c_void_p(x0.ptr), C.c_void_p(b.ptr), n, float(np.float32(tol)), int(max_iter),
-                                            float(np.float32(soft_restart_threshold)), C.c_void_p(x.ptr), C.byref(info),
-                                            C.c_void_p(int(stream) if stream else 0)))
-            return cls(a, x, b, info, soft_restart_threshold)
-        x = DeviceVec(n)
+        x = a._vec_type(n)
         info = _Info()
-        check(lib.sprs_hip_bicgstab_f64(a._h, C.c_void_p(x0.ptr), C.c_void_p(b.ptr), n, float(tol), int(max_iter),
-                                        float(soft_restart_threshold), C.c_void_p(x.ptr), C.byref(info),
-                                        C.c_void_p(int(stream) if stream else 0)))
+        # tol and the threshold travel as doubles: rounded to the matrix's precision first (the identity for f64)
+        check(a._op("bicgstab")(a._h, C.c_void_p(x0.ptr), C.c_void_p(b.ptr), n, float(a._dtype(tol)), int(max_iter),
+                                float(a._dtype(soft_restart_threshold)), C.c_void_p(x.ptr), C.byref(info),
+                                C.c_void_p(int(stream) if stream else 0)))
         return cls(a, x, b, info, soft_restart_threshold)
 
     @property

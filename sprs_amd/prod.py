@@ -28,23 +28,16 @@ def _is_f32(mat, *vecs):
 def mul_acc_mat_vec_csr(mat, in_vec, res_vec, stream=None):
     """prod::mul_acc_mat_vec_csr (prod.rs:103-127): res_vec += mat * in_vec.  A DeviceCsMatF32 with DeviceVecF32 operands runs
     the f32 entry."""
-    if _is_f32(mat, in_vec, res_vec):
-        check(lib.sprs_hip_spmv_f32(mat._h, C.c_void_p(in_vec.ptr), in_vec.n, C.c_void_p(res_vec.ptr), res_vec.n, 1, _stream_ptr(stream)))
-        return
-    check(lib.sprs_hip_spmv_f64(mat._h, C.c_void_p(in_vec.ptr), in_vec.n, C.c_void_p(res_vec.ptr),
-                                res_vec.n, 1, _stream_ptr(stream)))
+    _is_f32(mat, in_vec, res_vec)
+    check(mat._op("spmv")(mat._h, C.c_void_p(in_vec.ptr), in_vec.n, C.c_void_p(res_vec.ptr), res_vec.n, 1, _stream_ptr(stream)))
 
 
 def mul_acc_mat_vec_csc(mat, in_vec, res_vec, stream=None):
     """prod::mul_acc_mat_vec_csc (prod.rs:74-99): res_vec += mat * in_vec for a CSC matrix (sprs_hip_mul_acc_mat_vec_csc_f64:
     the matrix is converted once to CSR on the device, the copy is cached in the HANDLE, the CSR kernel runs — every result
     element still receives its products by ascending column).  A DeviceCsMatF32 with DeviceVecF32 operands runs the f32 entry."""
-    if _is_f32(mat, in_vec, res_vec):
-        check(lib.sprs_hip_mul_acc_mat_vec_csc_f32(mat._h, C.c_void_p(in_vec.ptr), in_vec.n, C.c_void_p(res_vec.ptr), res_vec.n,
-                                                   _stream_ptr(stream)))
-        return
-    check(lib.sprs_hip_mul_acc_mat_vec_csc_f64(mat._h, C.c_void_p(in_vec.ptr), in_vec.n, C.c_void_p(res_vec.ptr), res_vec.n,
-                                               _stream_ptr(stream)))
+    _is_f32(mat, in_vec, res_vec)
+    check(mat._op("mul_acc_mat_vec_csc")(mat._h, C.c_void_p(in_vec.ptr), in_vec.n, C.c_void_p(res_vec.ptr), res_vec.n, _stream_ptr(stream)))
 
 
 class _DenseMat:
@@ -144,9 +137,9 @@ def _dims(lhs, rhs, out):
 
 
 def _mulacc_dense(lhs, rhs, out, stream):
-    entry = lib.sprs_hip_csmat_mulacc_dense_f32 if _is_f32_dense(lhs, rhs, out) else lib.sprs_hip_csmat_mulacc_dense_f64
-    check(entry(lhs._h, C.c_void_p(rhs.vec.ptr), rhs.rows, rhs.cols, rhs.layout, rhs.ld,
-                C.c_void_p(out.vec.ptr), out.rows, out.layout, out.ld, 1, _stream_ptr(stream)))
+    _is_f32_dense(lhs, rhs, out)
+    check(lhs._op("csmat_mulacc_dense")(lhs._h, C.c_void_p(rhs.vec.ptr), rhs.rows, rhs.cols, rhs.layout, rhs.ld,
+                                        C.c_void_p(out.vec.ptr), out.rows, out.layout, out.ld, 1, _stream_ptr(stream)))
 
 
 def _storage(lhs, want_csr):
@@ -204,24 +197,22 @@ def csmat_mul_dense(mat, rhs, stream=None):
     """`&CsMat * &Array2` (csmat.rs:1989-2048), ONE call below the C ABI (sprs_hip_csmat_mul_dense_f64): the four arms
     (CSR | CSC) x (>= 8 columns | fewer); the result comes back row-major for >= 8 columns and column-major (`.f()`) below,
     like the reference's."""
-    f32 = _is_f32_dense(mat, rhs)
+    _is_f32_dense(mat, rhs)
     out = type(rhs)(mat.rows(), rhs.cols, rhs._vec_type()(mat.rows() * rhs.cols))
     lay = C.c_int32(0)
-    entry = lib.sprs_hip_csmat_mul_dense_f32 if f32 else lib.sprs_hip_csmat_mul_dense_f64
-    check(entry(mat._h, C.c_void_p(rhs.vec.ptr), rhs.rows, rhs.cols, rhs.layout, rhs.ld,
-                C.c_void_p(out.vec.ptr), C.byref(lay), _stream_ptr(stream)))
+    check(mat._op("csmat_mul_dense")(mat._h, C.c_void_p(rhs.vec.ptr), rhs.rows, rhs.cols, rhs.layout, rhs.ld,
+                                     C.c_void_p(out.vec.ptr), C.byref(lay), _stream_ptr(stream)))
     out.col_major = lay.value == _ffi.COL_MAJOR
     return out
 
 
 def dense_dot_csmat(lhs, mat, stream=None):
     """`Array2::dot(&CsMat)` (csmat.rs:2050-2117): dense . sparse through the transposes of the reference, below the C ABI."""
-    f32 = _is_f32_dense(mat, lhs)
+    _is_f32_dense(mat, lhs)
     out = type(lhs)(lhs.rows, mat.cols(), lhs._vec_type()(lhs.rows * mat.cols()))
     lay = C.c_int32(0)
-    entry = lib.sprs_hip_dense_dot_csmat_f32 if f32 else lib.sprs_hip_dense_dot_csmat_f64
-    check(entry(C.c_void_p(lhs.vec.ptr), lhs.rows, lhs.cols, lhs.layout, lhs.ld, mat._h,
-                C.c_void_p(out.vec.ptr), C.byref(lay), _stream_ptr(stream)))
+    check(mat._op("dense_dot_csmat")(C.c_void_p(lhs.vec.ptr), lhs.rows, lhs.cols, lhs.layout, lhs.ld, mat._h,
+                                     C.c_void_p(out.vec.ptr), C.byref(lay), _stream_ptr(stream)))
     out.col_major = lay.value == _ffi.COL_MAJOR
     return out
 
@@ -229,15 +220,10 @@ def dense_dot_csmat(lhs, mat, stream=None):
 def csmat_mul_vec(mat, vec, out=None, stream=None):
     """`&CsMat * &Array1` (csmat.rs:2119-2160): fresh zero result; CSR goes through csr_mulacc_dense_colmaj with one column,
     CSC through csc_mulacc_dense_colmaj (csmat.rs:2140-2156) — dispatched below the C ABI (sprs_hip_csmat_mul_vec_f64)."""
-    if _is_f32(mat, vec, *([] if out is None else [out])):
-        from .device import DeviceVecF32
-        if out is None:
-            out = DeviceVecF32(mat.rows())
-        check(lib.sprs_hip_csmat_mul_vec_f32(mat._h, C.c_void_p(vec.ptr), vec.n, C.c_void_p(out.ptr), out.n, _stream_ptr(stream)))
-        return out
+    _is_f32(mat, vec, *([] if out is None else [out]))
     if out is None:
-        out = DeviceVec(mat.rows())
-    check(lib.sprs_hip_csmat_mul_vec_f64(mat._h, C.c_void_p(vec.ptr), vec.n, C.c_void_p(out.ptr), out.n, _stream_ptr(stream)))
+        out = mat._vec_type(mat.rows())
+    check(mat._op("csmat_mul_vec")(mat._h, C.c_void_p(vec.ptr), vec.n, C.c_void_p(out.ptr), out.n, _stream_ptr(stream)))
     return out
 
 
