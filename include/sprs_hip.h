@@ -920,6 +920,8 @@ int32_t sprs_hip_triplets_to_cs(uint64_t rows, uint64_t cols, uint64_t n, const 
  * The whole table (name, default, range) is SPRS_HIP_OPTIONS in sprs_amd/csrc/common.hpp.  Developer switches — timing
  * experiments with WRONG results (spgemm_debug, spmv_xmask, spmv_band_debug) and the profiling printout spgemm_prof — exist
  * only in libraries built with -DSPRS_HIP_DEVTOOLS; this one rejects them.  get_option("devtools") tells which build it is.
+ * get_option("spgemm_f32_lds_add") (read-only) reports the library's probe of the f32 LDS add on the current device: bit 0 the
+ * lanes of one add instruction that hit one address are applied in ascending lane order, bit 1 f32 subnormals are kept.
  * Process-wide.  Unknown names / bad values return SPRS_HIP_INVALID_ARG. */
 /* Contract: every option has a closed range (the table in sprs_amd/csrc/common.hpp); a value outside it — including a value
  * other than 0 / 1 for an on / off switch — and an unknown or retired name return SPRS_HIP_INVALID_ARG and change nothing
@@ -1044,6 +1046,37 @@ int32_t sprs_hip_csmat_mul_dense_f32(const sprs_hip_csmat_f32 *lhs, const float 
 int32_t sprs_hip_dense_dot_csmat_f32(const float *lhs_dev, uint64_t lhs_rows, uint64_t lhs_cols, int32_t lhs_layout,
                                      uint64_t ld_lhs, const sprs_hip_csmat_f32 *rhs, float *out_dev, int32_t *out_layout,
                                      void *stream);
+
+/* ---- f32 SpGEMM: CsMat<f32> times CsMat<f32> ----------------------------------------------------------------------------
+ * smmp::mul_csr_csr is generic over the scalar (smmp.rs:196-416).  The eight entries below are the f32 twins of
+ * sprs_hip_spgemm_f64, sprs_hip_spgemm_symbolic / _numeric, the five plan entries that read a matrix, and
+ * sprs_hip_csmat_mul_csmat: the same argument order, checks, statuses and texts, on sprs_hip_csmat_f32 handles.
+ * Structure: indptr and indices equal the reference's (every reachable column, structural zeros kept, rows sorted).
+ * Values: every C(i,j) starts at +0.0f; each product a*b is rounded to f32 and added, unfused, one at a time in ascending
+ * position of k in A's row — the reference's f32 chain, bit for bit (an f64 product rounded once at the end is NOT that).
+ * Subnormals are kept.  Deterministic; option spgemm_ordered = 0 frees the order of the adds in the large-row kernel exactly
+ * as for f64.  The value walks read one 8-byte {column, float} record of B per product (f64: 16 bytes).
+ * A sprs_hip_spgemm_plan holds STRUCTURE only (task lists, counts, offsets, the column-bucket table of B; the records of B are
+ * packed per call): sprs_hip_spgemm_plan_nnz and _plan_free serve both precisions, and a plan made by either _plan_create
+ * serves handles of the OTHER precision wrapped over the same indptr / indices device arrays (the plan matches operands by
+ * shape, index widths and those two pointers per operand).  Mixing precisions in one call is impossible by type. */
+int32_t sprs_hip_spgemm_f32(const sprs_hip_csmat_f32 *a, const sprs_hip_csmat_f32 *b, sprs_hip_csmat_f32 **c);
+/* structure only: an f32 matrix whose values are 0.0f */
+int32_t sprs_hip_spgemm_symbolic_f32(const sprs_hip_csmat_f32 *a, const sprs_hip_csmat_f32 *b,
+                                     sprs_hip_csmat_f32 **c_structure);
+int32_t sprs_hip_spgemm_numeric_f32(const sprs_hip_csmat_f32 *a, const sprs_hip_csmat_f32 *b, sprs_hip_csmat_f32 *c);
+int32_t sprs_hip_spgemm_plan_create_f32(const sprs_hip_csmat_f32 *a, const sprs_hip_csmat_f32 *b,
+                                        sprs_hip_spgemm_plan **plan);
+int32_t sprs_hip_spgemm_plan_structure_f32(sprs_hip_spgemm_plan *plan, const sprs_hip_csmat_f32 *a,
+                                           const sprs_hip_csmat_f32 *b, sprs_hip_csmat_f32 **c_structure);
+int32_t sprs_hip_spgemm_plan_product_f32(sprs_hip_spgemm_plan *plan, const sprs_hip_csmat_f32 *a,
+                                         const sprs_hip_csmat_f32 *b, sprs_hip_csmat_f32 **c);
+int32_t sprs_hip_spgemm_plan_numeric_f32(sprs_hip_spgemm_plan *plan, const sprs_hip_csmat_f32 *a,
+                                         const sprs_hip_csmat_f32 *b, sprs_hip_csmat_f32 *c);
+/* `&lhs * &rhs` in any pair of storages (csmat.rs:1895-1949) through sprs_hip_csmat_f32_to_other_storage and the free
+ * transpose views; the result has the storage of the lhs */
+int32_t sprs_hip_csmat_mul_csmat_f32(const sprs_hip_csmat_f32 *lhs, const sprs_hip_csmat_f32 *rhs,
+                                     sprs_hip_csmat_f32 **out);
 
 #ifdef __cplusplus
 }

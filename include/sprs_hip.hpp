@@ -1285,6 +1285,80 @@ inline DeviceMatF32 dot(const DeviceMatF32 &lhs, const DeviceCsMatF32 &rhs) {
     return out;
 }
 
+// `&A * &B` for N = f32 (csmat.rs:1866-1949) in any pair of storages; the result has the storage of the lhs.  Every product and
+// every partial sum is rounded to f32, in the reference's order.  No overload takes one f64 and one f32 matrix.
+inline DeviceCsMatF32 operator*(const DeviceCsMatF32 &a, const DeviceCsMatF32 &b) {
+    sprs_hip_csmat_f32 *c = nullptr;
+    check(sprs_hip_csmat_mul_csmat_f32(a.handle(), b.handle(), &c));
+    return DeviceCsMatF32(c);
+}
+
+namespace smmp {
+// smmp::mul_csr_csr / symbolic / numeric (smmp.rs:196-416, 81-131, 151-189) for N = f32
+inline DeviceCsMatF32 mul_csr_csr(const DeviceCsMatF32 &lhs, const DeviceCsMatF32 &rhs) {
+    sprs_hip_csmat_f32 *c = nullptr;
+    check(sprs_hip_spgemm_f32(lhs.handle(), rhs.handle(), &c));
+    return DeviceCsMatF32(c);
+}
+inline DeviceCsMatF32 symbolic(const DeviceCsMatF32 &lhs, const DeviceCsMatF32 &rhs) {
+    sprs_hip_csmat_f32 *c = nullptr;
+    check(sprs_hip_spgemm_symbolic_f32(lhs.handle(), rhs.handle(), &c));
+    return DeviceCsMatF32(c);
+}
+inline void numeric(const DeviceCsMatF32 &lhs, const DeviceCsMatF32 &rhs, DeviceCsMatF32 &c) {
+    check(sprs_hip_spgemm_numeric_f32(lhs.handle(), rhs.handle(), const_cast<sprs_hip_csmat_f32 *>(c.handle())));
+}
+
+// The symbolic phase of a product, kept (sprs_hip_spgemm_plan_*): structure() / product() / numeric() launch the value kernels
+// only.  The plan holds structure alone, so ONE plan serves f64 and f32 operands over the same indptr / indices device arrays:
+// every method is overloaded on the operand type.  The operands must keep their structure while the plan lives.
+class SpgemmPlan {
+public:
+    SpgemmPlan(const DeviceCsMat &a, const DeviceCsMat &b) { check(sprs_hip_spgemm_plan_create(a.handle(), b.handle(), &p_)); }
+    SpgemmPlan(const DeviceCsMatF32 &a, const DeviceCsMatF32 &b) { check(sprs_hip_spgemm_plan_create_f32(a.handle(), b.handle(), &p_)); }
+    SpgemmPlan(SpgemmPlan &&o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    SpgemmPlan(const SpgemmPlan &) = delete;
+    SpgemmPlan &operator=(const SpgemmPlan &) = delete;
+    ~SpgemmPlan() {
+        if (p_) sprs_hip_spgemm_plan_free(p_);
+    }
+    uint64_t nnz() const {
+        uint64_t n = 0;
+        check(sprs_hip_spgemm_plan_nnz(p_, &n));
+        return n;
+    }
+    DeviceCsMat structure(const DeviceCsMat &a, const DeviceCsMat &b) {
+        sprs_hip_csmat *c = nullptr;
+        check(sprs_hip_spgemm_plan_structure(p_, a.handle(), b.handle(), &c));
+        return DeviceCsMat(c);
+    }
+    DeviceCsMatF32 structure(const DeviceCsMatF32 &a, const DeviceCsMatF32 &b) {
+        sprs_hip_csmat_f32 *c = nullptr;
+        check(sprs_hip_spgemm_plan_structure_f32(p_, a.handle(), b.handle(), &c));
+        return DeviceCsMatF32(c);
+    }
+    DeviceCsMat product(const DeviceCsMat &a, const DeviceCsMat &b) {
+        sprs_hip_csmat *c = nullptr;
+        check(sprs_hip_spgemm_plan_product(p_, a.handle(), b.handle(), &c));
+        return DeviceCsMat(c);
+    }
+    DeviceCsMatF32 product(const DeviceCsMatF32 &a, const DeviceCsMatF32 &b) {
+        sprs_hip_csmat_f32 *c = nullptr;
+        check(sprs_hip_spgemm_plan_product_f32(p_, a.handle(), b.handle(), &c));
+        return DeviceCsMatF32(c);
+    }
+    void numeric(const DeviceCsMat &a, const DeviceCsMat &b, DeviceCsMat &c) {
+        check(sprs_hip_spgemm_plan_numeric(p_, a.handle(), b.handle(), const_cast<sprs_hip_csmat *>(c.handle())));
+    }
+    void numeric(const DeviceCsMatF32 &a, const DeviceCsMatF32 &b, DeviceCsMatF32 &c) {
+        check(sprs_hip_spgemm_plan_numeric_f32(p_, a.handle(), b.handle(), const_cast<sprs_hip_csmat_f32 *>(c.handle())));
+    }
+
+private:
+    sprs_hip_spgemm_plan *p_ = nullptr;
+};
+}  // namespace smmp
+
 namespace linalg {
 // BiCGSTAB::<f32>::solve (bicgstab.rs:148-171, :305)
 class BiCGSTABF32 {

@@ -425,6 +425,20 @@ extern "C" {
         lhs_dev: *const f32, lhs_rows: u64, lhs_cols: u64, lhs_layout: i32, ld_lhs: u64, rhs: *const sprs_hip_csmat_f32,
         out_dev: *mut f32, out_layout: *mut i32, stream: *mut c_void,
     ) -> i32;
+    pub fn sprs_hip_spgemm_f32(a: *const sprs_hip_csmat_f32, b: *const sprs_hip_csmat_f32, c: *mut *mut sprs_hip_csmat_f32) -> i32;
+    pub fn sprs_hip_spgemm_symbolic_f32(a: *const sprs_hip_csmat_f32, b: *const sprs_hip_csmat_f32, c_structure: *mut *mut sprs_hip_csmat_f32) -> i32;
+    pub fn sprs_hip_spgemm_numeric_f32(a: *const sprs_hip_csmat_f32, b: *const sprs_hip_csmat_f32, c: *mut sprs_hip_csmat_f32) -> i32;
+    pub fn sprs_hip_spgemm_plan_create_f32(a: *const sprs_hip_csmat_f32, b: *const sprs_hip_csmat_f32, plan: *mut *mut sprs_hip_spgemm_plan) -> i32;
+    pub fn sprs_hip_spgemm_plan_structure_f32(
+        plan: *mut sprs_hip_spgemm_plan, a: *const sprs_hip_csmat_f32, b: *const sprs_hip_csmat_f32, c_structure: *mut *mut sprs_hip_csmat_f32,
+    ) -> i32;
+    pub fn sprs_hip_spgemm_plan_product_f32(
+        plan: *mut sprs_hip_spgemm_plan, a: *const sprs_hip_csmat_f32, b: *const sprs_hip_csmat_f32, c: *mut *mut sprs_hip_csmat_f32,
+    ) -> i32;
+    pub fn sprs_hip_spgemm_plan_numeric_f32(
+        plan: *mut sprs_hip_spgemm_plan, a: *const sprs_hip_csmat_f32, b: *const sprs_hip_csmat_f32, c: *mut sprs_hip_csmat_f32,
+    ) -> i32;
+    pub fn sprs_hip_csmat_mul_csmat_f32(lhs: *const sprs_hip_csmat_f32, rhs: *const sprs_hip_csmat_f32, out: *mut *mut sprs_hip_csmat_f32) -> i32;
     pub fn sprs_hip_set_option(name: *const c_char, value: i64) -> i32;
     pub fn sprs_hip_get_option(name: *const c_char, value: *mut i64) -> i32;
 }

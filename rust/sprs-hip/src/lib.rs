@@ -1760,6 +1760,74 @@ pub mod single {
         mulacc_dense(lhs, rhs, out)
     }
 
+    /// `&A * &B` for N = f32 (csmat.rs:1866-1888 -> csmat_mul_csmat -> smmp::mul_csr_csr) in any pair of storages: every product
+    /// and every partial sum rounded to f32, in the reference's order.
+    impl<'a, 'b> std::ops::Mul<&'b DeviceCsMatF32> for &'a DeviceCsMatF32 {
+        type Output = DeviceCsMatF32;
+        fn mul(self, rhs: &'b DeviceCsMatF32) -> DeviceCsMatF32 {
+            let mut h: *mut sys::sprs_hip_csmat_f32 = std::ptr::null_mut();
+            unsafe { check(sys::sprs_hip_csmat_mul_csmat_f32(self.h, rhs.h, &mut h)) };
+            DeviceCsMatF32 { h }
+        }
+    }
+
+    /// `sprs::smmp` for N = f32
+    pub mod smmp {
+        use super::*;
+        /// Twin of `smmp::mul_csr_csr` (smmp.rs:196-416)
+        pub fn mul_csr_csr(lhs: &DeviceCsMatF32, rhs: &DeviceCsMatF32) -> DeviceCsMatF32 {
+            let mut h: *mut sys::sprs_hip_csmat_f32 = std::ptr::null_mut();
+            unsafe { check(sys::sprs_hip_spgemm_f32(lhs.h, rhs.h, &mut h)) };
+            DeviceCsMatF32 { h }
+        }
+        /// Twin of `smmp::symbolic` (smmp.rs:81-131): the structure of `lhs * rhs`, values 0.0f32
+        pub fn symbolic(lhs: &DeviceCsMatF32, rhs: &DeviceCsMatF32) -> DeviceCsMatF32 {
+            let mut h: *mut sys::sprs_hip_csmat_f32 = std::ptr::null_mut();
+            unsafe { check(sys::sprs_hip_spgemm_symbolic_f32(lhs.h, rhs.h, &mut h)) };
+            DeviceCsMatF32 { h }
+        }
+        /// Twin of `smmp::numeric` (smmp.rs:151-189): the values of `lhs * rhs` into `c`, which must have the product's structure
+        pub fn numeric(lhs: &DeviceCsMatF32, rhs: &DeviceCsMatF32, c: &mut DeviceCsMatF32) {
+            unsafe { check(sys::sprs_hip_spgemm_numeric_f32(lhs.h, rhs.h, c.h)) };
+        }
+
+        /// The symbolic phase of `lhs * rhs`, kept: `structure`, `product` and `numeric` run the value kernels only.  The plan
+        /// holds structure alone; it is released when dropped.
+        pub struct SpgemmPlan {
+            p: *mut sys::sprs_hip_spgemm_plan,
+        }
+        impl SpgemmPlan {
+            pub fn new(lhs: &DeviceCsMatF32, rhs: &DeviceCsMatF32) -> Self {
+                let mut p: *mut sys::sprs_hip_spgemm_plan = std::ptr::null_mut();
+                unsafe { check(sys::sprs_hip_spgemm_plan_create_f32(lhs.h, rhs.h, &mut p)) };
+                SpgemmPlan { p }
+            }
+            pub fn nnz(&self) -> usize {
+                let mut n = 0u64;
+                unsafe { check(sys::sprs_hip_spgemm_plan_nnz(self.p, &mut n)) };
+                n as usize
+            }
+            pub fn structure(&mut self, lhs: &DeviceCsMatF32, rhs: &DeviceCsMatF32) -> DeviceCsMatF32 {
+                let mut h: *mut sys::sprs_hip_csmat_f32 = std::ptr::null_mut();
+                unsafe { check(sys::sprs_hip_spgemm_plan_structure_f32(self.p, lhs.h, rhs.h, &mut h)) };
+                DeviceCsMatF32 { h }
+            }
+            pub fn product(&mut self, lhs: &DeviceCsMatF32, rhs: &DeviceCsMatF32) -> DeviceCsMatF32 {
+                let mut h: *mut sys::sprs_hip_csmat_f32 = std::ptr::null_mut();
+                unsafe { check(sys::sprs_hip_spgemm_plan_product_f32(self.p, lhs.h, rhs.h, &mut h)) };
+                DeviceCsMatF32 { h }
+            }
+            pub fn numeric(&mut self, lhs: &DeviceCsMatF32, rhs: &DeviceCsMatF32, c: &mut DeviceCsMatF32) {
+                unsafe { check(sys::sprs_hip_spgemm_plan_numeric_f32(self.p, lhs.h, rhs.h, c.h)) };
+            }
+        }
+        impl Drop for SpgemmPlan {
+            fn drop(&mut self) {
+                unsafe { sys::sprs_hip_spgemm_plan_free(self.p) };
+            }
+        }
+    }
+
     /// `BiCGSTAB::<f32>::solve` (bicgstab.rs:148-171): `Ok(solver)` / `Err(solver)` like the reference.
     pub struct BiCGSTAB {
         x: DeviceVecF32,

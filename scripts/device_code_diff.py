@@ -2,7 +2,9 @@
 """Is the device code of two source trees the same, kernel by kernel?  A refactor of the host side must not move it.
 Every translation unit of sprs_amd/csrc is compiled for the device only (the Makefile's flags + --cuda-device-only -S;
 spgemm.hip also with -DSPRS_HIP_DEVTOOLS), the assembly is split per function symbol, and symbol sets, bodies and the
-.amdhsa_* resource lines are compared.  Emission order may differ (local labels carry the function's number): nothing else.
+.amdhsa_* resource lines are compared.  Emission order may differ (local labels carry the function's number), tree B may hold
+functions A does not have, and a template parameter that is `double` for the f64 code may have been added (see canonical()):
+nothing else.
 usage: device_code_diff.py <tree A> <tree B> [work dir]      exit status 1 when anything differs"""
 import os
 import re
@@ -41,6 +43,29 @@ def split(text):
     return bodies, resources
 
 
+import shutil
+
+CXXFILT = shutil.which("llvm-cxxfilt") or shutil.which("c++filt")
+
+
+def canonical(text):
+    """Kernel templates may gain a defaulted or trailing scalar parameter (the SpGEMM kernels: `typename T`, double for the f64
+    code) without their f64 bodies moving; the mangled names change all the same.  Every mangled symbol of the text is replaced
+    by its demangled form with that parameter dropped where it is `double`: CsrView<I, P, double> -> CsrView<I, P> and a last
+    template argument `, double>` of a function template.  Symbols instantiated for another scalar keep their own names and show up
+    as added functions."""
+    syms = sorted(set(re.findall(r"\b_Z[A-Za-z0-9_$.]+", text)), key=len, reverse=True)
+    if not syms:
+        return text
+    dem = subprocess.run([CXXFILT], input="\n".join(syms), capture_output=True, text=True, check=True).stdout.splitlines()
+    names = {}
+    for m, d in zip(syms, dem):
+        d = re.sub(r"(CsrView<[^<>]*?), double>", r"\1>", d)
+        d = re.sub(r", double>\(", ">(", d)
+        names[m] = re.sub(r"[^A-Za-z0-9_]", "_", d)
+    return re.sub(r"\b_Z[A-Za-z0-9_$.]+", lambda m: names[m.group(0)], text)
+
+
 def main():
     a, b = sys.argv[1], sys.argv[2]
     work = sys.argv[3] if len(sys.argv) > 3 else tempfile.mkdtemp()
@@ -49,12 +74,15 @@ def main():
     asm_a, asm_b = assembly(a, os.path.join(work, "a")), assembly(b, os.path.join(work, "b"))
     same = True
     for u in asm_a:
-        (ba, ra), (bb, rb) = split(asm_a[u]), split(asm_b[u])
-        bad = sorted(set(ba) ^ set(bb)) + sorted(set(ra) ^ set(rb)) + [k for k in ba if k in bb and ba[k] != bb[k]] + \
+        (ba, ra), (bb, rb) = split(canonical(asm_a[u])), split(canonical(asm_b[u]))
+        # functions only tree B has (new instantiations) are reported, not counted as a difference: everything A has must be in B, unchanged
+        added = sorted(set(bb) - set(ba))
+        bad = sorted(set(ba) - set(bb)) + sorted(set(ra) - set(rb)) + [k for k in ba if k in bb and ba[k] != bb[k]] + \
             [k for k in ra if k in rb and ra[k] != rb[k]]
         same &= not bad
-        print("%-14s functions %4d / %4d   kernels %4d / %4d   %s" % (u, len(ba), len(bb), len(ra), len(rb),
-                                                                     "identical" if not bad else "DIFFERENT: " + ", ".join(bad[:4])))
+        print("%-14s functions %4d / %4d   kernels %4d / %4d   %s%s" % (u, len(ba), len(bb), len(ra), len(rb),
+                                                                       "identical" if not bad else "DIFFERENT: " + ", ".join(bad[:4]),
+                                                                       "   (+%d functions only in B)" % len(added) if added else ""))
     sys.exit(0 if same else 1)
 
 

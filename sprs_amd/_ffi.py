@@ -188,6 +188,14 @@ SIGNATURES = {
     "sprs_hip_csmat_mulacc_dense_f32": (i32, [vp, vp, u64, u64, i32, u64, vp, u64, i32, u64, i32, vp]),
     "sprs_hip_csmat_mul_dense_f32": (i32, [vp, vp, u64, u64, i32, u64, vp, P(i32), vp]),
     "sprs_hip_dense_dot_csmat_f32": (i32, [vp, u64, u64, i32, u64, vp, vp, P(i32), vp]),
+    "sprs_hip_spgemm_f32": (i32, [vp, vp, P(vp)]),
+    "sprs_hip_spgemm_symbolic_f32": (i32, [vp, vp, P(vp)]),
+    "sprs_hip_spgemm_numeric_f32": (i32, [vp, vp, vp]),
+    "sprs_hip_spgemm_plan_create_f32": (i32, [vp, vp, P(vp)]),
+    "sprs_hip_spgemm_plan_structure_f32": (i32, [vp, vp, vp, P(vp)]),
+    "sprs_hip_spgemm_plan_product_f32": (i32, [vp, vp, vp, P(vp)]),
+    "sprs_hip_spgemm_plan_numeric_f32": (i32, [vp, vp, vp, vp]),
+    "sprs_hip_csmat_mul_csmat_f32": (i32, [vp, vp, P(vp)]),
     "sprs_hip_set_option": (i32, [C.c_char_p, i64]),
     "sprs_hip_get_option": (i32, [C.c_char_p, P(i64)]),
 }

@@ -721,7 +721,11 @@ int32_t sprs_hip_spmm_rowmaj_f64(const sprs_hip_csmat *a, const double *rhs_dev,
     return entry_spmm_rowmaj(a, rhs_dev, rhs_rows, k, ld_rhs, out_dev, out_rows, ld_out, accumulate, stream);
 }
 
-static int32_t spgemm_contract(const sprs_hip_csmat *a, const sprs_hip_csmat *b) {
+}  // extern "C"
+
+// ---- SpGEMM: one body per entry for both handle types ----------------------------------------------------------------------
+template <typename H>
+static int32_t spgemm_contract(const H *a, const H *b) {
     if (a->cols != b->rows) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");   // smmp.rs:207
     if (a->storage != SPRS_HIP_CSR || b->storage != SPRS_HIP_CSR) SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "Storage mismatch");
     if (a->user_iptr_bytes() != b->user_iptr_bytes() || a->user_idx_bytes() != b->user_idx_bytes())
@@ -731,7 +735,8 @@ static int32_t spgemm_contract(const sprs_hip_csmat *a, const sprs_hip_csmat *b)
 
 // C as the target of a numeric phase: the asserts of numeric() on its shape (smmp.rs:161-166); then, under C's lock (which
 // the caller holds until the kernels are launched), everything derived from its values goes
-static int32_t numeric_target(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat *c) {
+template <typename H>
+static int32_t numeric_target(const H *a, const H *b, H *c) {
     if (c->rows != a->rows || c->cols != b->cols) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
     if (c->storage != SPRS_HIP_CSR) SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "Storage mismatch");
     if (c->user_iptr_bytes() != a->user_iptr_bytes() || c->user_idx_bytes() != a->user_idx_bytes())
@@ -741,17 +746,38 @@ static int32_t numeric_target(const sprs_hip_csmat *a, const sprs_hip_csmat *b, 
     return SPRS_HIP_OK;
 }
 
-int32_t sprs_hip_spgemm_symbolic(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat **c) {
+// the ABI boundary of a product for either handle type: the f64 result takes its operand's declared widths (and their overflow
+// checks); an f32 handle declares none (its arrays are 4 or 8 bytes wide on the host as on the device)
+static int32_t finish_product(OwnedCsmat &res, const sprs_hip_csmat *from, sprs_hip_csmat **out) { return finish_result(res, from, out); }
+static int32_t finish_product(OwnedCsmatF32 &res, const sprs_hip_csmat_f32 *, sprs_hip_csmat_f32 **out) {
+    *out = res.release();
+    return SPRS_HIP_OK;
+}
+
+template <typename H>
+static int32_t entry_spgemm(const H *a, const H *b, H **c) {
     clear_error();
     if (!a || !b || !c) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
     *c = nullptr;
     SPRS_TRY(spgemm_contract(a, b));
-    OwnedCsmat res;
-    SPRS_TRY(spgemm_symbolic(a, b, res));
-    return finish_result(res, a, c);
+    Owned<H> res;
+    SPRS_TRY(spgemm_product(a, b, res));
+    return finish_product(res, a, c);
 }
 
-int32_t sprs_hip_spgemm_numeric(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat *c) {
+template <typename H>
+static int32_t entry_spgemm_symbolic(const H *a, const H *b, H **c) {
+    clear_error();
+    if (!a || !b || !c) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *c = nullptr;
+    SPRS_TRY(spgemm_contract(a, b));
+    Owned<H> res;
+    SPRS_TRY(spgemm_symbolic(a, b, res));
+    return finish_product(res, a, c);
+}
+
+template <typename H>
+static int32_t entry_spgemm_numeric(const H *a, const H *b, H *c) {
     clear_error();
     if (!a || !b || !c) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
     SPRS_TRY(spgemm_contract(a, b));
@@ -760,12 +786,89 @@ int32_t sprs_hip_spgemm_numeric(const sprs_hip_csmat *a, const sprs_hip_csmat *b
     return spgemm_numeric(a, b, c);
 }
 
-int32_t sprs_hip_spgemm_plan_create(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_spgemm_plan **plan) {
+template <typename H>
+static int32_t entry_spgemm_plan_create(const H *a, const H *b, sprs_hip_spgemm_plan **plan) {
     clear_error();
     if (!a || !b || !plan) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
     *plan = nullptr;
     SPRS_TRY(spgemm_contract(a, b));
     return spgemm_plan_create(a, b, plan);
+}
+
+template <typename H>
+static int32_t entry_spgemm_plan_structure(sprs_hip_spgemm_plan *plan, const H *a, const H *b, H **c, bool with_values) {
+    clear_error();
+    if (!plan || !a || !b || !c) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *c = nullptr;
+    Owned<H> res;
+    SPRS_TRY(spgemm_plan_structure(plan, a, b, res, with_values));
+    return finish_product(res, a, c);
+}
+
+template <typename H>
+static int32_t entry_spgemm_plan_numeric(sprs_hip_spgemm_plan *plan, const H *a, const H *b, H *c) {
+    clear_error();
+    if (!plan || !a || !b || !c) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    SPRS_TRY(numeric_target(a, b, c));
+    return spgemm_plan_numeric(plan, a, b, c);
+}
+
+// to_other_storage with the index-type check of the reference on the DECLARED widths (csmat.rs:1794-1797)
+static int32_t convert_checked(const sprs_hip_csmat *m, OwnedCsmat &out) {
+    if (m->rows > width_max(m->user_idx_bytes()))
+        SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "Index type is not large enough to hold the number of rows requested (required %llu)",
+                  (unsigned long long)m->rows);
+    SPRS_TRY(to_other_storage(m, out));
+    return inherit_declared_widths(out.get(), m);
+}
+static int32_t convert_checked(const sprs_hip_csmat_f32 *m, OwnedCsmatF32 &out) {
+    if (m->rows > width_max(m->idx_bytes))
+        SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "Index type is not large enough to hold the number of rows requested (required %llu)",
+                  (unsigned long long)m->rows);
+    return to_other_storage(m, out);
+}
+
+// `&lhs * &rhs` for two sparse matrices: csmat_mul_csmat (csmat.rs:1895-1949) — the storage dispatch around
+// smmp::mul_csr_csr; the result has the storage of the lhs.
+template <typename H>
+static int32_t entry_csmat_mul_csmat(const H *lhs, const H *rhs, H **out) {
+    clear_error();
+    if (!lhs || !rhs || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    if (lhs->cols != rhs->rows) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    if (lhs->user_iptr_bytes() != rhs->user_iptr_bytes() || lhs->user_idx_bytes() != rhs->user_idx_bytes())
+        SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "operands must share index types (smmp.rs:196-199)");
+    const bool l_csr = lhs->storage == SPRS_HIP_CSR, r_csr = rhs->storage == SPRS_HIP_CSR;
+    Owned<H> conv, c;                                             // rhs.to_other_storage() where the storages call for it; the product
+    if (l_csr) {                                                  // (CSR, CSR) and (CSR, CSC)
+        if (!r_csr) SPRS_TRY(convert_checked(rhs, conv));
+        SPRS_TRY(spgemm_product(lhs, r_csr ? rhs : conv.get(), c));
+        return finish_product(c, lhs, out);
+    }
+    // lhs is CSC: (rhs^T * lhs^T)^T on the transpose views (csmat.rs:982-991), which are CSR; transpose_into flips the result back
+    if (r_csr) SPRS_TRY(convert_checked(rhs, conv));              // (CSC, CSR): rhs.to_other_storage() first
+    H rt, lt;                                                     // stack views: their destructors find no plan and no block to release
+    view_csmat(r_csr ? conv.get() : rhs, true, &rt);
+    view_csmat(lhs, true, &lt);
+    SPRS_TRY(spgemm_product(&rt, &lt, c));
+    c->storage = SPRS_HIP_CSC;                                    // transpose_into: same buffers, other tag
+    std::swap(c->rows, c->cols);
+    return finish_product(c, lhs, out);
+}
+
+extern "C" {
+
+int32_t sprs_hip_spgemm_symbolic(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat **c) {
+    return entry_spgemm_symbolic(a, b, c);
+}
+
+int32_t sprs_hip_spgemm_numeric(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat *c) {
+    return entry_spgemm_numeric(a, b, c);
+}
+
+int32_t sprs_hip_spgemm_plan_create(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_spgemm_plan **plan) {
+    return entry_spgemm_plan_create(a, b, plan);
 }
 
 int32_t sprs_hip_spgemm_plan_nnz(const sprs_hip_spgemm_plan *plan, uint64_t *nnz) {
@@ -777,31 +880,17 @@ int32_t sprs_hip_spgemm_plan_nnz(const sprs_hip_spgemm_plan *plan, uint64_t *nnz
 
 int32_t sprs_hip_spgemm_plan_structure(sprs_hip_spgemm_plan *plan, const sprs_hip_csmat *a, const sprs_hip_csmat *b,
                                        sprs_hip_csmat **c_structure) {
-    clear_error();
-    if (!plan || !a || !b || !c_structure) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
-    *c_structure = nullptr;
-    OwnedCsmat res;
-    SPRS_TRY(spgemm_plan_structure(plan, a, b, res, false));
-    return finish_result(res, a, c_structure);
+    return entry_spgemm_plan_structure(plan, a, b, c_structure, false);
 }
 
 int32_t sprs_hip_spgemm_plan_product(sprs_hip_spgemm_plan *plan, const sprs_hip_csmat *a, const sprs_hip_csmat *b,
                                      sprs_hip_csmat **c) {
-    clear_error();
-    if (!plan || !a || !b || !c) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
-    *c = nullptr;
-    OwnedCsmat res;
-    SPRS_TRY(spgemm_plan_structure(plan, a, b, res, true));
-    return finish_result(res, a, c);
+    return entry_spgemm_plan_structure(plan, a, b, c, true);
 }
 
 int32_t sprs_hip_spgemm_plan_numeric(sprs_hip_spgemm_plan *plan, const sprs_hip_csmat *a, const sprs_hip_csmat *b,
                                      sprs_hip_csmat *c) {
-    clear_error();
-    if (!plan || !a || !b || !c) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
-    std::lock_guard<std::recursive_mutex> lock(c->mu);
-    SPRS_TRY(numeric_target(a, b, c));
-    return spgemm_plan_numeric(plan, a, b, c);
+    return entry_spgemm_plan_numeric(plan, a, b, c);
 }
 
 int32_t sprs_hip_spgemm_plan_free(sprs_hip_spgemm_plan *plan) {
@@ -828,22 +917,7 @@ int32_t sprs_hip_gauss_seidel_f64(sprs_hip_csmat *a, double *x_dev, const double
 }
 
 int32_t sprs_hip_spgemm_f64(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat **c) {
-    clear_error();
-    if (!a || !b || !c) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
-    *c = nullptr;
-    SPRS_TRY(spgemm_contract(a, b));
-    OwnedCsmat res;
-    SPRS_TRY(spgemm_f64(a, b, res));
-    return finish_result(res, a, c);
-}
-
-// to_other_storage with the index-type check of the reference on the DECLARED widths (csmat.rs:1794-1797)
-static int32_t convert_checked(const sprs_hip_csmat *m, OwnedCsmat &out) {
-    if (m->rows > width_max(m->user_idx_bytes()))
-        SPRS_FAIL(SPRS_HIP_INDEX_OVERFLOW, "Index type is not large enough to hold the number of rows requested (required %llu)",
-                  (unsigned long long)m->rows);
-    SPRS_TRY(to_other_storage(m, out));
-    return inherit_declared_widths(out.get(), m);
+    return entry_spgemm(a, b, c);
 }
 
 int32_t sprs_hip_csmat_to_other_storage(const sprs_hip_csmat *m, sprs_hip_csmat **out) {
@@ -856,31 +930,8 @@ int32_t sprs_hip_csmat_to_other_storage(const sprs_hip_csmat *m, sprs_hip_csmat 
     return SPRS_HIP_OK;
 }
 
-// `&lhs * &rhs` for two sparse matrices: csmat_mul_csmat (csmat.rs:1895-1949) — the storage dispatch around
-// smmp::mul_csr_csr; the result has the storage of the lhs.
 int32_t sprs_hip_csmat_mul_csmat(const sprs_hip_csmat *lhs, const sprs_hip_csmat *rhs, sprs_hip_csmat **out) {
-    clear_error();
-    if (!lhs || !rhs || !out) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
-    *out = nullptr;
-    if (lhs->cols != rhs->rows) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
-    if (lhs->user_iptr_bytes() != rhs->user_iptr_bytes() || lhs->user_idx_bytes() != rhs->user_idx_bytes())
-        SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "operands must share index types (smmp.rs:196-199)");
-    const bool l_csr = lhs->storage == SPRS_HIP_CSR, r_csr = rhs->storage == SPRS_HIP_CSR;
-    OwnedCsmat conv, c;                                           // rhs.to_other_storage() where the storages call for it; the product
-    if (l_csr) {                                                  // (CSR, CSR) and (CSR, CSC)
-        if (!r_csr) SPRS_TRY(convert_checked(rhs, conv));
-        SPRS_TRY(spgemm_f64(lhs, r_csr ? rhs : conv.get(), c));
-        return finish_result(c, lhs, out);
-    }
-    // lhs is CSC: (rhs^T * lhs^T)^T on the transpose views (csmat.rs:982-991), which are CSR; transpose_into flips the result back
-    if (r_csr) SPRS_TRY(convert_checked(rhs, conv));              // (CSC, CSR): rhs.to_other_storage() first
-    sprs_hip_csmat rt, lt;                                        // stack views: their destructors find no plan and no block to release
-    view_csmat(r_csr ? conv.get() : rhs, true, &rt);
-    view_csmat(lhs, true, &lt);
-    SPRS_TRY(spgemm_f64(&rt, &lt, c));
-    c->storage = SPRS_HIP_CSC;                                    // transpose_into: same buffers, other tag
-    std::swap(c->rows, c->cols);
-    return finish_result(c, lhs, out);
+    return entry_csmat_mul_csmat(lhs, rhs, out);
 }
 
 int32_t sprs_hip_csmat_slice_outer(const sprs_hip_csmat *m, uint64_t start, uint64_t end, sprs_hip_csmat **out) {
@@ -1092,6 +1143,10 @@ int32_t sprs_hip_get_option(const char *name, int64_t *value) {
     if (!name || !value) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL argument");
     if (!strcmp(name, "pool_cached_bytes")) {
         *value = (int64_t)pool_cached_bytes();
+        return SPRS_HIP_OK;
+    }
+    if (!strcmp(name, "spgemm_f32_lds_add")) {  // read-only: the verdict of the f32 probe of the LDS add on the current device (spgemm.hip)
+        *value = spgemm_f32_lds_add_verdict();
         return SPRS_HIP_OK;
     }
     if (!strcmp(name, "devtools")) {           // 1 when the library was built with SPRS_HIP_DEVTOOLS
@@ -2365,6 +2420,41 @@ int32_t sprs_hip_csmat_mulacc_dense_f32(const sprs_hip_csmat_f32 *lhs, const flo
 int32_t sprs_hip_csmat_mul_dense_f32(const sprs_hip_csmat_f32 *lhs, const float *rhs_dev, uint64_t rhs_rows, uint64_t k,
                                      int32_t rhs_layout, uint64_t ld_rhs, float *out_dev, int32_t *out_layout, void *stream) {
     return entry_mul_dense(lhs, rhs_dev, rhs_rows, k, rhs_layout, ld_rhs, out_dev, out_layout, stream);
+}
+
+int32_t sprs_hip_spgemm_f32(const sprs_hip_csmat_f32 *a, const sprs_hip_csmat_f32 *b, sprs_hip_csmat_f32 **c) {
+    return entry_spgemm(a, b, c);
+}
+
+int32_t sprs_hip_spgemm_symbolic_f32(const sprs_hip_csmat_f32 *a, const sprs_hip_csmat_f32 *b, sprs_hip_csmat_f32 **c) {
+    return entry_spgemm_symbolic(a, b, c);
+}
+
+int32_t sprs_hip_spgemm_numeric_f32(const sprs_hip_csmat_f32 *a, const sprs_hip_csmat_f32 *b, sprs_hip_csmat_f32 *c) {
+    return entry_spgemm_numeric(a, b, c);
+}
+
+int32_t sprs_hip_spgemm_plan_create_f32(const sprs_hip_csmat_f32 *a, const sprs_hip_csmat_f32 *b, sprs_hip_spgemm_plan **plan) {
+    return entry_spgemm_plan_create(a, b, plan);
+}
+
+int32_t sprs_hip_spgemm_plan_structure_f32(sprs_hip_spgemm_plan *plan, const sprs_hip_csmat_f32 *a, const sprs_hip_csmat_f32 *b,
+                                           sprs_hip_csmat_f32 **c_structure) {
+    return entry_spgemm_plan_structure(plan, a, b, c_structure, false);
+}
+
+int32_t sprs_hip_spgemm_plan_product_f32(sprs_hip_spgemm_plan *plan, const sprs_hip_csmat_f32 *a, const sprs_hip_csmat_f32 *b,
+                                         sprs_hip_csmat_f32 **c) {
+    return entry_spgemm_plan_structure(plan, a, b, c, true);
+}
+
+int32_t sprs_hip_spgemm_plan_numeric_f32(sprs_hip_spgemm_plan *plan, const sprs_hip_csmat_f32 *a, const sprs_hip_csmat_f32 *b,
+                                         sprs_hip_csmat_f32 *c) {
+    return entry_spgemm_plan_numeric(plan, a, b, c);
+}
+
+int32_t sprs_hip_csmat_mul_csmat_f32(const sprs_hip_csmat_f32 *lhs, const sprs_hip_csmat_f32 *rhs, sprs_hip_csmat_f32 **out) {
+    return entry_csmat_mul_csmat(lhs, rhs, out);
 }
 
 int32_t sprs_hip_dense_dot_csmat_f32(const float *lhs_dev, uint64_t lhs_rows, uint64_t lhs_cols, int32_t lhs_layout, uint64_t ld_lhs,

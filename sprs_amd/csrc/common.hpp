@@ -519,6 +519,8 @@ int32_t spgemm_numeric(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hi
 int32_t spgemm_plan_create(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_spgemm_plan **out);
 int32_t spgemm_plan_structure(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, const sprs_hip_csmat *b, OwnedCsmat &out, bool with_values);
 int32_t spgemm_plan_numeric(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat *c);
+// A plan holds structure only (task lists, counts, offsets, the bucket table of B): one made from f64 operands serves f32
+// handles over the same indptr / indices arrays and the reverse; the {column, value} records of B are packed per call.
 uint64_t spgemm_plan_nnz(const sprs_hip_spgemm_plan *pl);
 void spgemm_plan_free(sprs_hip_spgemm_plan *pl);
 // spmm.hip
@@ -664,6 +666,16 @@ inline int32_t spmv(sprs_hip_csmat *a, const double *x, double *y, bool accumula
 inline int32_t spmv(sprs_hip_csmat_f32 *a, const float *x, float *y, bool accumulate, hipStream_t stream) { return spmv_f32(a, x, y, accumulate, stream); }
 inline int32_t spmv_prepare(sprs_hip_csmat_f32 *a, hipStream_t stream) { return spmv_f32_prepare(a, stream); }
 inline int32_t to_other_storage(const sprs_hip_csmat_f32 *m, OwnedCsmatF32 &out) { return csmat_f32_to_other_storage(m, out); }
+// spgemm.hip: the f32 products (rounded to f32 after every multiply and every add, in the reference's order)
+int32_t spgemm_f32(const sprs_hip_csmat_f32 *a, const sprs_hip_csmat_f32 *b, OwnedCsmatF32 &c);
+int32_t spgemm_symbolic(const sprs_hip_csmat_f32 *a, const sprs_hip_csmat_f32 *b, OwnedCsmatF32 &c);
+int32_t spgemm_numeric(const sprs_hip_csmat_f32 *a, const sprs_hip_csmat_f32 *b, sprs_hip_csmat_f32 *c);
+int32_t spgemm_plan_create(const sprs_hip_csmat_f32 *a, const sprs_hip_csmat_f32 *b, sprs_hip_spgemm_plan **out);
+int32_t spgemm_plan_structure(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat_f32 *a, const sprs_hip_csmat_f32 *b, OwnedCsmatF32 &out, bool with_values);
+int32_t spgemm_plan_numeric(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat_f32 *a, const sprs_hip_csmat_f32 *b, sprs_hip_csmat_f32 *c);
+int64_t spgemm_f32_lds_add_verdict();      // bit 0: lane order holds for the f32 LDS add, bit 1: it keeps subnormals (probed once per device)
+inline int32_t spgemm_product(const sprs_hip_csmat *a, const sprs_hip_csmat *b, OwnedCsmat &c) { return spgemm_f64(a, b, c); }
+inline int32_t spgemm_product(const sprs_hip_csmat_f32 *a, const sprs_hip_csmat_f32 *b, OwnedCsmatF32 &c) { return spgemm_f32(a, b, c); }
 inline int32_t spmm_strided(sprs_hip_csmat *a, const double *rhs, uint64_t k, uint64_t rs_rhs, uint64_t cs_rhs, double *out, uint64_t rs_out,
                             uint64_t cs_out, bool accumulate, hipStream_t stream) {
     return spmm_strided_f64(a, rhs, k, rs_rhs, cs_rhs, out, rs_out, cs_out, accumulate, stream);

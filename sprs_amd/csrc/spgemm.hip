@@ -29,6 +29,10 @@
 // History of what was measured (profiles/): per-row windows + LDS accumulators 1.96 s -> 0.50 s on
 // config 5; bucket table, LDS staging, prefetch -> 0.454 s (waves owning column ranges, one k at a time); entry-parallel
 // expansion with order tags -> 0.22 s (round 1); row tasks, LDS-ordered adds, wave-per-row kernel -> 0.112 s (round 2).
+// Two scalars: the counting kernels and the plan read structure only and exist once; the four numeric kernel families carry a
+// trailing `typename T` (double, float).  The f32 value walks gather 8-byte {column, float} records of B, the adds are
+// ds_add_f32 under a probe of their own (lds_add_f32_probe); the f64 instantiations are instruction for instruction what they
+// were before the parameter (scripts/device_code_diff.py).  DESIGN.md 4.18.
 // Developer builds (make DEVTOOLS=1): option spgemm_prof prints per-class / per-phase timings of the numeric kernels; the
 // release library compiles the timers and the printout out.
 #include "common.hpp"
@@ -36,6 +40,7 @@
 #include "scan.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <type_traits>
 #include <cstring>
 #include <vector>
@@ -85,11 +90,16 @@ __device__ __forceinline__ uint64_t lower_bound_col(const IDX *__restrict__ idx,
     return lo;
 }
 
-template <typename IDX, typename PTR>
+template <typename T>
+struct BRecOf;
+
+// T = the scalar of the operands (double or float).  The counting kernels (NUMERIC = false) read no values and exist for
+// T = double only: a plan is built through views whose data pointer is never followed.
+template <typename IDX, typename PTR, typename T = double>
 struct CsrView {
     const PTR *indptr;
     const IDX *indices;
-    const double *data;
+    const T *data;
     // optional column-bucket table of the right operand: bucket[k * nb + b] = number of entries of
     // row k with column < b * 2048.  Turns "where does row k enter column window [lo,hi)" — two
     // binary searches, ~20 dependent loads per (row, window) — into two independent loads.
@@ -100,7 +110,7 @@ struct CsrView {
     // half the bytes of a usize index — and one 16-byte record {column, value} per entry for the value walks — one load
     // and ONE cache line per short run instead of two.  Null in views that do not come from a plan.
     const uint32_t *col32;
-    const struct BRec *pack;
+    const typename BRecOf<T>::type *pack;
 };
 
 struct alignas(16) BRec {
@@ -108,13 +118,28 @@ struct alignas(16) BRec {
     double val;
 };
 
+// the f32 record: the same information in 8 bytes — half the bytes the value walks pull through the fabric
+struct alignas(8) BRecF32 {
+    uint32_t col;
+    float val;
+};
+
+template <>
+struct BRecOf<double> {
+    using type = BRec;
+};
+template <>
+struct BRecOf<float> {
+    using type = BRecF32;
+};
+
 constexpr int BUCKET_LOG2 = 11;   // 2048 columns = one superblock of the LDS bitmap: pass and window bounds are free
 
 // sub-range [s,e) of row k (given its [s,e) = whole row) inside columns [lo, hi).  With the bucket
 // table a bound that is a multiple of 2048 costs one load (callers round hi UP past the last
 // column instead of clamping it); any other bound adds a binary search inside its bucket.
-template <typename IDX, typename PTR>
-__device__ __forceinline__ void row_window(const CsrView<IDX, PTR> &B, uint64_t k, uint64_t lo, uint64_t hi,
+template <typename IDX, typename PTR, typename T>
+__device__ __forceinline__ void row_window(const CsrView<IDX, PTR, T> &B, uint64_t k, uint64_t lo, uint64_t hi,
                                            uint64_t &s, uint64_t &e) {
     if (B.bucket) {
         const uint32_t *t = B.bucket + k * B.nb;
@@ -193,6 +218,18 @@ __global__ __launch_bounds__(256) void pack_entries_kernel(const IDX *__restrict
         BRec r;
         r.col = (uint32_t)indices[p];
         r.pad = 0;
+        r.val = data[p];
+        pack[p] = r;
+    }
+}
+
+template <typename IDX>
+__global__ __launch_bounds__(256) void pack_entries_f32_kernel(const IDX *__restrict__ indices, const float *__restrict__ data, uint64_t nnz,
+                                                               BRecF32 *__restrict__ pack) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p < nnz; p += stride) {
+        BRecF32 r;
+        r.col = (uint32_t)indices[p];
         r.val = data[p];
         pack[p] = r;
     }
@@ -509,24 +546,24 @@ __device__ __forceinline__ uint64_t task_of_block(uint64_t bid, uint64_t n, uint
 // ---------------------------------------------------------------------------
 // small rows: one wave per task, LDS hash table
 // ---------------------------------------------------------------------------
-template <typename IDX, typename PTR, bool NUMERIC, int TAB>
-__global__ __launch_bounds__(SM_BLOCK) void small_rows_kernel(CsrView<IDX, PTR> A, CsrView<IDX, PTR> B,
+template <typename IDX, typename PTR, bool NUMERIC, int TAB, typename T>
+__global__ __launch_bounds__(SM_BLOCK) void small_rows_kernel(CsrView<IDX, PTR, T> A, CsrView<IDX, PTR, T> B,
                                                               const uint64_t *__restrict__ small_list,
                                                               uint64_t n_small, const uint64_t *__restrict__ task_row,
                                                               const uint64_t *__restrict__ ub,
                                                               uint64_t *__restrict__ count,        // symbolic: out
                                                               const uint64_t *__restrict__ off,    // numeric: in
-                                                              IDX *__restrict__ c_indices, double *__restrict__ c_data,
+                                                              IDX *__restrict__ c_indices, T *__restrict__ c_data,
                                                               uint32_t bin_shift, uint32_t flags) {
     __shared__ uint32_t keys_s[SM_WAVES][TAB];
-    __shared__ double vals_s[NUMERIC ? SM_WAVES : 1][NUMERIC ? TAB : 1];
+    __shared__ T vals_s[NUMERIC ? SM_WAVES : 1][NUMERIC ? TAB : 1];
     __shared__ uint32_t tag_s[NUMERIC ? SM_WAVES : 1][WAVE];   // order tags of the entry-parallel path
     __shared__ uint32_t bin_s[NUMERIC ? SM_WAVES : 1][NUMERIC ? SM_NBIN : 1];      // rank pass: keys per column bin, then the bins' ends
     __shared__ uint32_t skey_s[NUMERIC ? SM_WAVES : 1][NUMERIC ? TAB / 2 : 1];     // rank pass: the keys grouped by bin
     const bool lane_order = (flags & 1u) != 0;                 // one ds_add_f64 per wave instruction: see add_lanes()
     const uint32_t lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
     uint32_t *keys = keys_s[wave];
-    double *vals = vals_s[NUMERIC ? wave : 0];
+    T *vals = vals_s[NUMERIC ? wave : 0];
     const uint64_t w0 = (uint64_t)blockIdx.x * SM_WAVES + wave;
     const uint64_t nw = (uint64_t)gridDim.x * SM_WAVES;
     for (uint64_t q = w0; q < n_small; q += nw) {
@@ -548,7 +585,7 @@ __global__ __launch_bounds__(SM_BLOCK) void small_rows_kernel(CsrView<IDX, PTR> 
             // and chains one memory round trip per k: 5-pt Laplacian squared, 51 ms of 71.)
             const bool has = as + lane < ae;
             const uint64_t k = has ? (uint64_t)A.indices[as + lane] : 0;
-            const double av = has ? A.data[as + lane] : 0.0;
+            const T av = NUMERIC && has ? A.data[as + lane] : T(0);     // (the counting form follows no value pointer)
             const uint64_t bs = has ? (uint64_t)B.indptr[k] : 0;
             const uint32_t len = has ? (uint32_t)((uint64_t)B.indptr[k + 1] - bs) : 0u;
             uint32_t inc = len;                               // inclusive prefix of the lengths over the lanes
@@ -571,10 +608,10 @@ __global__ __launch_bounds__(SM_BLOCK) void small_rows_kernel(CsrView<IDX, PTR> 
                 own &= WAVE - 1;
                 const uint32_t inc_o = __shfl(inc, (int)own, WAVE), len_o = __shfl(len, (int)own, WAVE);
                 const uint64_t bs_o = __shfl(bs, (int)own, WAVE);
-                const double av_o = __shfl(av, (int)own, WAVE);
+                const T av_o = __shfl(av, (int)own, WAVE);
                 const uint64_t pos = valid ? bs_o + (uint64_t)(t - (inc_o - len_o)) : 0ull;   // (a lane without an entry loads entry 0 and drops it:
                 const uint32_t c = (uint32_t)B.indices[pos];                                   //  a load under a per-lane condition ends in its own wait)
-                double pr = 0.0;
+                T pr = T(0);
                 if constexpr (NUMERIC) pr = av_o * B.data[pos];
                 uint32_t h = hash_slot(c, lg);
                 if (valid) {
@@ -582,7 +619,7 @@ __global__ __launch_bounds__(SM_BLOCK) void small_rows_kernel(CsrView<IDX, PTR> 
                         const uint32_t old = atomicCAS(&keys[h], EMPTY, c);
                         if (old == EMPTY) {
                             ++fresh;
-                            if constexpr (NUMERIC) vals[h] = 0.0;       // tmp starts at N::zero()
+                            if constexpr (NUMERIC) vals[h] = T(0);      // tmp starts at N::zero()
                             break;
                         }
                         if (old == c) break;
@@ -618,22 +655,22 @@ __global__ __launch_bounds__(SM_BLOCK) void small_rows_kernel(CsrView<IDX, PTR> 
             const uint64_t p = p0 + lane;
             const bool valid = p < ae;
             const uint64_t k = valid ? (uint64_t)A.indices[p] : 0;
-            const double av = valid ? A.data[p] : 0.0;
+            const T av = NUMERIC && valid ? A.data[p] : T(0);
             const uint64_t bs = valid ? (uint64_t)B.indptr[k] : 0, be = valid ? (uint64_t)B.indptr[k + 1] : 0;
             const int nb = (ae - p0 < (uint64_t)WAVE) ? (int)(ae - p0) : WAVE;
             for (int j = 0; j < nb; ++j) {            // k ascending: the reference's order (smmp.rs:174-181)
                 const uint64_t bsj = __shfl(bs, j, WAVE), bej = __shfl(be, j, WAVE);
-                const double avj = __shfl(av, j, WAVE);
+                const T avj = __shfl(av, j, WAVE);
                 for (uint64_t b = bsj + lane; b < bej; b += WAVE) {
                     const uint32_t c = (uint32_t)B.indices[b];
-                    double pr = 0.0;
+                    T pr = T(0);
                     if constexpr (NUMERIC) pr = avj * B.data[b];
                     uint32_t h = hash_slot(c, lg);
                     for (;;) {
                         const uint32_t old = atomicCAS(&keys[h], EMPTY, c);
                         if (old == EMPTY) {
                             ++fresh;
-                            if constexpr (NUMERIC) vals[h] = 0.0 + pr;     // tmp starts at N::zero()
+                            if constexpr (NUMERIC) vals[h] = T(0) + pr;     // tmp starts at N::zero()
                             break;
                         }
                         if (old == c) {
@@ -718,11 +755,11 @@ __global__ __launch_bounds__(SM_BLOCK) void small_rows_kernel(CsrView<IDX, PTR> 
 // else to do meanwhile, so the chain is a software pipeline over the wave's rows: while the entries of row i are in flight
 // the extents of row i + 1, the bounds of row i + 2 and the record of row i + 3 are requested — one round trip per row.
 // ---------------------------------------------------------------------------
-template <typename IDX, typename PTR, bool NUMERIC, int G, typename KEY>
-__global__ __launch_bounds__(256) void micro_rows_kernel(CsrView<IDX, PTR> A, CsrView<IDX, PTR> B, const uint64_t *__restrict__ ext,
+template <typename IDX, typename PTR, bool NUMERIC, int G, typename KEY, typename T>
+__global__ __launch_bounds__(256) void micro_rows_kernel(CsrView<IDX, PTR, T> A, CsrView<IDX, PTR, T> B, const uint64_t *__restrict__ ext,
                                                          const MicroRec *__restrict__ list, uint64_t n, uint64_t *__restrict__ count,
                                                          const uint64_t *__restrict__ off, IDX *__restrict__ c_indices,
-                                                         double *__restrict__ c_data) {
+                                                         T *__restrict__ c_data) {
     constexpr int R = WAVE / G, LOG2G = G == 16 ? 4 : G == 32 ? 5 : 6;
     constexpr KEY NO_KEY = ~(KEY)0;                                      // a lane without a product: the end of the order
     const uint32_t lane = threadIdx.x & (WAVE - 1), g = lane / G, gl = lane % G;
@@ -744,13 +781,13 @@ __global__ __launch_bounds__(256) void micro_rows_kernel(CsrView<IDX, PTR> A, Cs
         bd.t = rc.t;
         return bd;
     };
-    struct Ext { uint64_t e; double av; uint64_t o, t; uint32_t nk; };
+    struct Ext { uint64_t e; T av; uint64_t o, t; uint32_t nk; };
     auto load_ext = [&](const Bounds &bd, uint64_t qq0) {
         Ext x;
         x.nk = qq0 + g < n ? (uint32_t)(bd.ae - bd.as) : 0u;            // <= G by the row's class
         const uint64_t at = bd.as + (gl < x.nk ? gl : 0u);
         x.e = ext[at];
-        x.av = NUMERIC ? A.data[at] : 0.0;
+        x.av = NUMERIC ? A.data[at] : T(0);
         x.o = bd.o;
         x.t = bd.t;
         return x;
@@ -787,9 +824,9 @@ __global__ __launch_bounds__(256) void micro_rows_kernel(CsrView<IDX, PTR> A, Cs
         const uint64_t base_o = __shfl(bs - (uint64_t)(inc - len), (int)own, G);
         const uint64_t pos = valid ? base_o + gl : 0ull;                 // (a lane without a product loads entry 0 and drops it)
         uint32_t c;
-        double pr = 0.0;
+        T pr = T(0);
         if constexpr (NUMERIC) {
-            const double av_o = __shfl(xc.av, (int)own, G);
+            const T av_o = __shfl(xc.av, (int)own, G);
             // ({column, value} records of B — one 64-byte gather per k instead of 16 + 32 — take 35 us off the three value kernels
             // of the 2.5 M-row benchmark product and cost 57 us to build: profiles/r16r)
             c = B.col32[pos];
@@ -807,14 +844,14 @@ __global__ __launch_bounds__(256) void micro_rows_kernel(CsrView<IDX, PTR> A, Cs
         if constexpr (!NUMERIC) {
             if (row_ok && gl == 0) count[xc.t] = (uint64_t)__popcll(mine);
         } else {
-            const double v = __shfl(pr, (int)ps, G);
+            const T v = __shfl(pr, (int)ps, G);
             const uint32_t rank = (uint32_t)__popcll(mine & ((1ull << gl) - 1ull));
-            double acc = 0.0 + v;                                        // tmp starts at N::zero() (smmp.rs:166-170)
+            T acc = T(0) + v;                                          // tmp starts at N::zero() (smmp.rs:166-170)
             if (__ballot(sk != NO_KEY && !head) != 0ull) {               // some column of the wave's rows has more than one product (wave-uniform)
                 bool alive = head;
                 for (int t = 1; t < G; ++t) {                            // (every lane takes part in every exchange; the exit is wave-uniform)
                     const uint32_t cn = __shfl_down(cs, (unsigned)t, G);
-                    const double vn = __shfl_down(v, (unsigned)t, G);
+                    const T vn = __shfl_down(v, (unsigned)t, G);
                     alive = alive && gl + (uint32_t)t < (uint32_t)G && cn == cs;
                     if (__ballot(alive) == 0ull) break;
                     if (alive) acc += vn;
@@ -867,8 +904,8 @@ __global__ __launch_bounds__(256) void micro_rows_kernel(CsrView<IDX, PTR> A, Cs
 // position of the first entry of row k with column >= v; the row's entries are [row0, ..), those before `lo` are known
 // to be < v and those from `hi` on >= v.  With the bucket table a bound that is a multiple of 2048 costs one load
 // (callers round an upper bound UP past the last column instead of clamping it).
-template <typename IDX, typename PTR>
-__device__ __forceinline__ uint64_t first_ge(const CsrView<IDX, PTR> &B, uint64_t k, uint64_t row0, uint64_t lo, uint64_t hi,
+template <typename IDX, typename PTR, typename T>
+__device__ __forceinline__ uint64_t first_ge(const CsrView<IDX, PTR, T> &B, uint64_t k, uint64_t row0, uint64_t lo, uint64_t hi,
                                              uint64_t v) {
     if (B.bucket) {
         const uint32_t *t = B.bucket + k * B.nb;
@@ -884,8 +921,8 @@ __device__ __forceinline__ uint64_t first_ge(const CsrView<IDX, PTR> &B, uint64_
 // Only the k's that HAVE entries in the range are kept (most do not, in a narrow window): the walks then cross exactly
 // one boundary per k instead of idling through runs of empty k's.  One scan carries both the count of kept k's (high
 // word) and the prefix of the lengths (low word).  kP[kept] = total, sentinels behind it for the search.
-template <int K_CAP>
-__device__ __forceinline__ uint32_t stage_compact(uint32_t len, uint64_t s, double av, uint64_t *kS, uint32_t *kP, double *kA,
+template <int K_CAP, typename T>
+__device__ __forceinline__ uint32_t stage_compact(uint32_t len, uint64_t s, T av, uint64_t *kS, uint32_t *kP, T *kA,
                                                   uint64_t *wt) {
     const uint32_t tid = threadIdx.x;
     uint64_t tot;
@@ -904,14 +941,14 @@ __device__ __forceinline__ uint32_t stage_compact(uint32_t len, uint64_t s, doub
 }
 
 // general form: the group's k's, their rows of B and the bounds are loaded here (rows with more than K_CAP k's)
-template <int K_CAP, typename IDX, typename PTR>
-__device__ __forceinline__ uint32_t stage_k_group(const CsrView<IDX, PTR> &A, const CsrView<IDX, PTR> &B,
+template <int K_CAP, typename IDX, typename PTR, typename T>
+__device__ __forceinline__ uint32_t stage_k_group(const CsrView<IDX, PTR, T> &A, const CsrView<IDX, PTR, T> &B,
                                                   uint64_t kc, uint32_t n, uint64_t wlo, uint64_t whi, bool whole_row,
-                                                  uint64_t *kS, uint32_t *kP, double *kA, uint64_t *wt) {
+                                                  uint64_t *kS, uint32_t *kP, T *kA, uint64_t *wt) {
     const uint32_t tid = threadIdx.x;
     uint32_t len = 0;                      // < 2^32: a window holds at most 2^19 columns of a row
     uint64_t s = 0;
-    double av = 0.0;
+    T av = T(0);
     if (tid < n) {
         const uint64_t k = (uint64_t)A.indices[kc + tid];
         uint64_t e = (uint64_t)B.indptr[k + 1];
@@ -959,28 +996,29 @@ __device__ __forceinline__ uint32_t batch_u(uint32_t gtot) {
 }
 
 // the entries of one batch as a wave holds them: lane l, instruction u = position (b U + u) 64 + l
+template <typename T>
 struct Batch {
     uint32_t cc[LG_U];        // column - first column of the window
     uint32_t own[LG_U];       // staged k the entry belongs to (ascending with the position)
-    double pr[LG_U];          // a_ik * b_kj
+    T pr[LG_U];               // a_ik * b_kj
     bool val[LG_U];
 };
 
-template <int K_CAP, bool VALUES>
-__device__ __forceinline__ void batch_load(Batch &bt, const uint32_t *__restrict__ b_col32, const BRec *__restrict__ b_pack,
+template <int K_CAP, bool VALUES, typename T>
+__device__ __forceinline__ void batch_load(Batch<T> &bt, const uint32_t *__restrict__ b_col32, const typename BRecOf<T>::type *__restrict__ b_pack,
                                            uint64_t wlo, uint32_t gtot, uint32_t U, uint32_t b, const uint64_t *kS,
-                                           const uint32_t *kP, const double *kA) {
+                                           const uint32_t *kP, const T *kA) {
     const uint32_t t0 = b * (64 * U) + (threadIdx.x & (WAVE - 1));
     FlatWalk wk;
     uint64_t pos[LG_U];
-    double av[LG_U];
+    T av[LG_U];
 #pragma unroll
     for (int u = 0; u < LG_U; ++u) {
         const uint32_t t = t0 + 64u * u;
         bt.val[u] = (uint32_t)u < U && t < gtot;
         pos[u] = 0;                            // a lane without an entry loads entry 0 and drops it: see the loads below
         bt.own[u] = 0;
-        av[u] = 0.0;
+        av[u] = T(0);
         if (bt.val[u]) {
             wk.seek<K_CAP>(kS, kP, t);
             pos[u] = wk.base + t;
@@ -991,12 +1029,12 @@ __device__ __forceinline__ void batch_load(Batch &bt, const uint32_t *__restrict
     // All loads of the batch are independent and UNCONDITIONAL (a load under a per-lane condition is compiled as a branch
     // whose arm waits for that one load: four memory round trips per batch instead of one — the ISA of rounds 1 to 3).
     uint32_t col[LG_U];
-    double bv[LG_U];
+    T bv[LG_U];
 #pragma unroll
     for (int u = 0; u < LG_U; ++u) {
-        bv[u] = 0.0;
-        if constexpr (VALUES) {                // one 16-byte record per entry
-            const BRec rec = b_pack[pos[u]];
+        bv[u] = T(0);
+        if constexpr (VALUES) {                // one record per entry: 16 bytes (f64) or 8 (f32)
+            const typename BRecOf<T>::type rec = b_pack[pos[u]];
             col[u] = rec.col;
             bv[u] = rec.val;
         } else {
@@ -1010,7 +1048,8 @@ __device__ __forceinline__ void batch_load(Batch &bt, const uint32_t *__restrict
     }
 }
 
-__device__ __forceinline__ void batch_bits(const Batch &bt, uint32_t *bm32) {
+template <typename T>
+__device__ __forceinline__ void batch_bits(const Batch<T> &bt, uint32_t *bm32) {
 #pragma unroll
     for (int u = 0; u < LG_U; ++u)
         if (bt.val[u]) atomicOr(&bm32[bt.cc[u] >> 5], 1u << (bt.cc[u] & 31));   // little endian: bit c & 63 of word c >> 6
@@ -1023,7 +1062,7 @@ __device__ __forceinline__ void walk_bits(const uint32_t *__restrict__ b_col32, 
     const uint32_t U = batch_u(gtot);
     const uint32_t nbatch = (gtot + 64 * U - 1) / (64 * U);
     for (uint32_t b = wave; b < nbatch; b += LG_WAVES) {
-        Batch bt;
+        Batch<double> bt;
         batch_load<K_CAP, false>(bt, b_col32, (const BRec *)nullptr, wlo, gtot, U, b, kS, kP, (const double *)nullptr);
         batch_bits(bt, bm32);
     }
@@ -1038,6 +1077,8 @@ __device__ __forceinline__ uint32_t lds_load_u32(const uint32_t *p) { return *(c
 __device__ __forceinline__ void lds_store_u32(uint32_t *p, uint32_t v) { *(volatile uint32_t *)p = v; }
 __device__ __forceinline__ double lds_load_f64(const double *p) { return *(const volatile double *)p; }
 __device__ __forceinline__ void lds_store_f64(double *p, double v) { *(volatile double *)p = v; }
+__device__ __forceinline__ float lds_load_f32(const float *p) { return *(const volatile float *)p; }
+__device__ __forceinline__ void lds_store_f32(float *p, float v) { *(volatile float *)p = v; }
 #else
 typedef __attribute__((address_space(3))) volatile uint32_t lds_vu32;
 typedef __attribute__((address_space(3))) volatile double lds_vf64;
@@ -1045,7 +1086,12 @@ __device__ __forceinline__ uint32_t lds_load_u32(const uint32_t *p) { return *(c
 __device__ __forceinline__ void lds_store_u32(uint32_t *p, uint32_t v) { *(lds_vu32 *)p = v; }
 __device__ __forceinline__ double lds_load_f64(const double *p) { return *(const lds_vf64 *)p; }
 __device__ __forceinline__ void lds_store_f64(double *p, double v) { *(lds_vf64 *)p = v; }
+typedef __attribute__((address_space(3))) volatile float lds_vf32;
+__device__ __forceinline__ float lds_load_f32(const float *p) { return *(const lds_vf32 *)p; }
+__device__ __forceinline__ void lds_store_f32(float *p, float v) { *(lds_vf32 *)p = v; }
 #endif
+__device__ __forceinline__ void lds_add_rw(double *p, double v) { lds_store_f64(p, lds_load_f64(p) + v); }   // read, add, write
+__device__ __forceinline__ void lds_add_rw(float *p, float v) { lds_store_f32(p, lds_load_f32(p) + v); }
 
 __device__ __forceinline__ void token_wait(uint32_t *token, uint32_t turn) {
     if (turn == 0xFFFFFFFFu) return;       // option spgemm_ordered = 0: no ordering of the waves' adds
@@ -1063,7 +1109,8 @@ __device__ __forceinline__ void token_pass(uint32_t *token, uint32_t next) {
 
 // the products of one wave instruction (64 consecutive positions, owners ascending with the lane): one add instruction
 // per k-run, runs in ascending order
-__device__ __forceinline__ void add_runs(bool val, uint32_t own, uint32_t slot, double pr, double *acc, bool lds_atomic) {
+template <typename T>
+__device__ __forceinline__ void add_runs(bool val, uint32_t own, uint32_t slot, T pr, T *acc, bool lds_atomic) {
     unsigned long long todo = __ballot(val);
     while (todo) {
         const int first = __ffsll((long long)todo) - 1;
@@ -1071,9 +1118,9 @@ __device__ __forceinline__ void add_runs(bool val, uint32_t own, uint32_t slot, 
         const bool mine = val && own == oo;
         if (mine) {
             if (lds_atomic) {
-                atomicAdd(&acc[slot], pr);               // ds_add_f64, no return value
+                atomicAdd(&acc[slot], pr);               // ds_add_f64 / ds_add_f32, no return value
             } else {
-                lds_store_f64(acc + slot, lds_load_f64(acc + slot) + pr);   // A/B switch: read, add, write (same order)
+                lds_add_rw(acc + slot, pr);              // A/B switch: read, add, write (same order)
             }
         }
         todo &= ~__ballot(mine);
@@ -1106,32 +1153,34 @@ __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v) { return grou
 // lane order (measured on gfx950: scripts/probes/lds_add_order.hip, 2.2e7 sums of which 2.2e6 order-sensitive, every one equal
 // to the ascending-lane sum; the library repeats a short form of that probe once per device, lds_lane_order_ok(), and falls
 // back to one instruction per k-run when it does not hold).
-__device__ __forceinline__ void add_lanes(bool val, uint32_t own, uint32_t slot, double pr, double *acc, bool lane_order) {
+template <typename T>
+__device__ __forceinline__ void add_lanes(bool val, uint32_t own, uint32_t slot, T pr, T *acc, bool lane_order, bool lds_atomic = true) {
     if (lane_order) {
 #ifdef SPRS_HIP_EMU
         wave_sync_lds();      // the CPU emulator runs a lane until its next collective: without this a lane would issue the adds of
                               // several wave instructions before its neighbours issue their first (the hardware is instruction-major)
 #endif
-        if (val) atomicAdd(&acc[slot], pr);                      // ds_add_f64, no return value
+        if (val) atomicAdd(&acc[slot], pr);                      // ds_add_f64 / ds_add_f32, no return value
     } else {
-        add_runs(val, own, slot, pr, acc, true);
+        add_runs(val, own, slot, pr, acc, lds_atomic);
     }
 }
 
 // what a position of the expansion needs from its k: where the k's sub-range starts (as the offset that turns a flat
 // position into an entry of B) and a_ik — one 16-byte LDS read
+template <typename T>
 struct alignas(16) KRec {
     uint64_t base;
-    double a;
+    T a;
 };
 
-template <typename IDX, typename PTR, bool NUMERIC, int MID_WL, int MID_KEEP>
-__global__ __launch_bounds__(MID_BLOCK, !NUMERIC ? 4 : MID_KEEP >= 8 ? 3 : 5) void mid_rows_kernel(CsrView<IDX, PTR> A, CsrView<IDX, PTR> B, uint64_t b_cols,
+template <typename IDX, typename PTR, bool NUMERIC, int MID_WL, int MID_KEEP, typename T>
+__global__ __launch_bounds__(MID_BLOCK, !NUMERIC ? 4 : MID_KEEP >= 8 ? 3 : 5) void mid_rows_kernel(CsrView<IDX, PTR, T> A, CsrView<IDX, PTR, T> B, uint64_t b_cols,
                                                              const uint64_t *__restrict__ mid_list, uint64_t n_mid,
                                                              const uint64_t *__restrict__ task_row,
                                                              uint64_t *__restrict__ count,        // symbolic: out
                                                              const uint64_t *__restrict__ off,    // numeric: in
-                                                             IDX *__restrict__ c_indices, double *__restrict__ c_data,
+                                                             IDX *__restrict__ c_indices, T *__restrict__ c_data,
                                                              unsigned long long *__restrict__ prof,
                                                              const uint64_t *__restrict__ ub_dbg,
                                                              unsigned int *__restrict__ next_row, uint32_t flags) {
@@ -1157,21 +1206,22 @@ __global__ __launch_bounds__(MID_BLOCK, !NUMERIC ? 4 : MID_KEEP >= 8 ? 3 : 5) vo
     static_assert(MID_WL >= 13 && MID_WL <= 16, "window of the wave-per-row kernel");   // (the owner | column pairs are packed 16 + 16 bits)
     __shared__ unsigned long long bm_s[MID_WAVES][MID_WORDS];
     __shared__ uint16_t sub_s[NUMERIC ? MID_WAVES : 1][NUMERIC ? MID_WORDS : 4];
-    __shared__ double acc_s[NUMERIC ? MID_WAVES : 1][NUMERIC ? MID_ACC : 1];
-    __shared__ KRec krec_s[MID_WAVES][MID_K];
+    __shared__ T acc_s[NUMERIC ? MID_WAVES : 1][NUMERIC ? MID_ACC : 1];
+    __shared__ KRec<T> krec_s[MID_WAVES][MID_K];
     __shared__ uint16_t stage_s[NUMERIC ? MID_WAVES : 1][NUMERIC ? MID_ACC : 1];      // columns (offsets in the segment) of one pass, by rank
     __shared__ uint32_t mark_s[MID_WAVES][MID_KEEP * WAVE / 4];      // one-byte marks: which k starts at a position of the current chunk
     const uint32_t lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
     unsigned long long *bm = bm_s[wave];
     uint32_t *bm32 = (uint32_t *)bm;
     uint16_t *sub = sub_s[NUMERIC ? wave : 0];
-    double *acc = acc_s[NUMERIC ? wave : 0];
-    KRec *krec = krec_s[wave];
+    T *acc = acc_s[NUMERIC ? wave : 0];
+    KRec<T> *krec = krec_s[wave];
     uint16_t *stage = stage_s[NUMERIC ? wave : 0];
     uint32_t *mark32 = mark_s[wave];
     uint8_t *mark8 = (uint8_t *)mark32;
     const bool values = NUMERIC && c_data != nullptr;
     const bool lane_order = (flags & 1u) != 0;
+    const bool add_atomic = !(std::is_same<T, float>::value && (flags & 2u));   // f32 on a device whose LDS add fails the probe's subnormal sums: read, add, write per k-run
     const bool dbg_no_emit = DEVTOOLS && (flags & 8u), dbg_no_flush = DEVTOOLS && (flags & 16u), dbg_no_add = DEVTOOLS && (flags & 32u);   // timing experiments (option spgemm_debug & 2 / 4 / 8): WRONG results
     uint64_t nwin = (b_cols + (1ull << MID_WL) - 1) >> MID_WL;
     if (nwin == 0) nwin = 1;
@@ -1204,7 +1254,7 @@ __global__ __launch_bounds__(MID_BLOCK, !NUMERIC ? 4 : MID_KEEP >= 8 ? 3 : 5) vo
         const uint64_t rk = (uint64_t)A.indices[as + (has ? lane : 0u)];
         const uint64_t rs = (uint64_t)B.indptr[rk];
         const uint32_t re = (uint32_t)((uint64_t)B.indptr[rk + 1] - rs);
-        double rav = 0.0;
+        T rav = T(0);
         if (values) rav = A.data[as + (has ? lane : 0u)];
         const uint32_t *__restrict__ bt = B.bucket + rk * B.nb;
         auto edge = [&](uint64_t col) -> uint32_t {          // first entry of my row with column >= col (col a multiple of 2048)
@@ -1226,14 +1276,14 @@ __global__ __launch_bounds__(MID_BLOCK, !NUMERIC ? 4 : MID_KEEP >= 8 ? 3 : 5) vo
             } else {
                 for (uint32_t i0 = 0; i0 < re; i0 += 4 * WAVE) {
                     uint32_t col[4];
-                    double bv[4];
+                    T bv[4];
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
                         const uint32_t i = i0 + (uint32_t)(u * WAVE) + lane;
                         const uint64_t at = rs + (i < re ? i : 0u);       // (unconditional loads: see load_chunk_n)
-                        bv[u] = 0.0;
+                        bv[u] = T(0);
                         if (values) {                                     // wave-uniform
-                            const BRec rec = B.pack[at];
+                            const typename BRecOf<T>::type rec = B.pack[at];
                             col[u] = rec.col;
                             bv[u] = rec.val;
                         } else {
@@ -1245,7 +1295,7 @@ __global__ __launch_bounds__(MID_BLOCK, !NUMERIC ? 4 : MID_KEEP >= 8 ? 3 : 5) vo
                         const uint32_t i = i0 + (uint32_t)(u * WAVE) + lane;
                         if (i < re) {
                             if (c_indices) c_indices[out + i] = (IDX)col[u];
-                            if (values) c_data[out + i] = 0.0 + rav * bv[u];
+                            if (values) c_data[out + i] = T(0) + rav * bv[u];
                         }
                     }
                 }
@@ -1283,7 +1333,7 @@ __global__ __launch_bounds__(MID_BLOCK, !NUMERIC ? 4 : MID_KEEP >= 8 ? 3 : 5) vo
             if (total == 0) continue;                                 // wave-uniform
             const uint32_t excl = inc - len;                          // flat position of my k's first entry
             {
-                KRec rec;
+                KRec<T> rec;
                 rec.base = rs + ws - excl;                            // flat position p of my k lives at entry base + p of B
                 rec.a = rav;
                 krec[lane] = rec;
@@ -1292,7 +1342,7 @@ __global__ __launch_bounds__(MID_BLOCK, !NUMERIC ? 4 : MID_KEEP >= 8 ? 3 : 5) vo
             const uint32_t nb = (total + WAVE - 1) / WAVE;
             const bool keep = values && nb <= (uint32_t)MID_KEEP;     // wave-uniform
             uint32_t kco[MID_KEEP];                                   // column offset (< 2^16) | owner << 16; 0xFFFFFFFF: no entry
-            double kpr[MID_KEEP];
+            T kpr[MID_KEEP];
             uint32_t carry = 0;                                       // owner + 1 of the position before the chunk (wave-uniform)
             // One CHUNK = MID_KEEP wave instructions = 256 consecutive positions of the expansion (k ascending, columns ascending
             // inside a k: the reference's order).  Owners: every k that starts inside the chunk leaves its number at its first
@@ -1326,12 +1376,12 @@ __global__ __launch_bounds__(MID_BLOCK, !NUMERIC ? 4 : MID_KEEP >= 8 ? 3 : 5) vo
                     pos[b] = ok[b] ? at : 0ull;
                 }
                 uint32_t col[NB];
-                double bv[NB];
+                T bv[NB];
 #pragma unroll
                 for (int b = 0; b < NB; ++b) {
-                    bv[b] = 0.0;
-                    if constexpr (WITH_VALUE) {                       // one 16-byte record per entry
-                        const BRec rec = B.pack[pos[b]];
+                    bv[b] = T(0);
+                    if constexpr (WITH_VALUE) {                       // one record per entry: 16 bytes (f64) or 8 (f32)
+                        const typename BRecOf<T>::type rec = B.pack[pos[b]];
                         col[b] = rec.col;
                         bv[b] = rec.val;
                     } else {
@@ -1341,7 +1391,7 @@ __global__ __launch_bounds__(MID_BLOCK, !NUMERIC ? 4 : MID_KEEP >= 8 ? 3 : 5) vo
 #pragma unroll
                 for (int b = 0; b < NB; ++b) {
                     kco[b] = ok[b] ? (col[b] - (uint32_t)wlo) | (own[b] << 16) : 0xFFFFFFFFu;
-                    kpr[b] = 0.0;
+                    kpr[b] = T(0);
                     if constexpr (WITH_VALUE) kpr[b] = krec[own[b]].a * bv[b];
                 }
             };
@@ -1394,7 +1444,7 @@ __global__ __launch_bounds__(MID_BLOCK, !NUMERIC ? 4 : MID_KEEP >= 8 ? 3 : 5) vo
                 // 8-byte places per instruction — the kernel wrote 34 GB for 18 GB of C and ran 19 % slower: profiles/r10i.)
                 for (uint32_t p0 = 0; (values || c_indices) && p0 < wtot; p0 += MID_ACC) {
                     const uint32_t n_out = wtot - p0 < (uint32_t)MID_ACC ? wtot - p0 : (uint32_t)MID_ACC;
-                    for (uint32_t i = lane; values && i < n_out; i += WAVE) acc[i] = 0.0;   // tmp starts at N::zero()
+                    for (uint32_t i = lane; values && i < n_out; i += WAVE) acc[i] = T(0);   // tmp starts at N::zero()
                     wave_sync_lds();
                     auto slot_of = [&](uint32_t cc) -> uint32_t {
                         const uint32_t word = cc >> 6;
@@ -1407,7 +1457,7 @@ __global__ __launch_bounds__(MID_BLOCK, !NUMERIC ? 4 : MID_KEEP >= 8 ? 3 : 5) vo
                                 const bool kv = kco[b] != 0xFFFFFFFFu;
                                 const uint32_t slot = kv ? slot_of(kco[b] & 0xFFFFu) : 0xFFFFFFFFu;
                                 if (kv && slot < n_out && c_indices) stage[slot] = (uint16_t)(kco[b] & 0xFFFFu);
-                                if (values && !dbg_no_add) add_lanes(kv && slot < n_out, kco[b] >> 16, slot, kpr[b], acc, lane_order);
+                                if (values && !dbg_no_add) add_lanes(kv && slot < n_out, kco[b] >> 16, slot, kpr[b], acc, lane_order, add_atomic);
                             }
                         }
                     };
@@ -1461,8 +1511,9 @@ __global__ __launch_bounds__(MID_BLOCK, !NUMERIC ? 4 : MID_KEEP >= 8 ? 3 : 5) vo
 // NTOK tokens instead of one: the accumulators are split by the low bits of their rank into NTOK independent sets (the
 // order only matters inside one accumulator), each with its own token chain — wave v + 1 adds into set 0 while wave v is
 // still busy with set 1: the hand-overs (a completed ds_add, a token write, the next wave's poll) overlap NTOK deep.
-__device__ __forceinline__ void batch_add(const Batch &bt, uint32_t U, const unsigned long long *bm, const uint16_t *sub,
-                                          const uint32_t *super, uint32_t base_rank, double *acc, uint32_t *token, uint32_t turn,
+template <typename T>
+__device__ __forceinline__ void batch_add(const Batch<T> &bt, uint32_t U, const unsigned long long *bm, const uint16_t *sub,
+                                          const uint32_t *super, uint32_t base_rank, T *acc, uint32_t *token, uint32_t turn,
                                           uint32_t lds_atomic, uint32_t ntok) {
     uint32_t slot[LG_U];
 #pragma unroll
@@ -1489,17 +1540,17 @@ __device__ __forceinline__ void batch_add(const Batch &bt, uint32_t U, const uns
 }
 
 // value walk of one staged group restricted to a pass; returns the number of batches (the token advances by it)
-template <int K_CAP>
-__device__ __forceinline__ uint32_t walk_values(const BRec *__restrict__ b_pack, uint64_t wlo,
-                                                uint32_t gtot, const uint64_t *kS, const uint32_t *kP, const double *kA,
+template <int K_CAP, typename T>
+__device__ __forceinline__ uint32_t walk_values(const typename BRecOf<T>::type *__restrict__ b_pack, uint64_t wlo,
+                                                uint32_t gtot, const uint64_t *kS, const uint32_t *kP, const T *kA,
                                                 const unsigned long long *bm, const uint16_t *sub, const uint32_t *super,
-                                                uint32_t base_rank, double *acc, uint32_t *token, uint32_t tok_base,
+                                                uint32_t base_rank, T *acc, uint32_t *token, uint32_t tok_base,
                                                 uint32_t lds_atomic, uint32_t ntok) {
     const uint32_t wave = threadIdx.x / WAVE;
     const uint32_t U = batch_u(gtot);
     const uint32_t nbatch = (gtot + 64 * U - 1) / (64 * U);
     for (uint32_t b = wave; b < nbatch; b += LG_WAVES) {
-        Batch bt;
+        Batch<T> bt;
         batch_load<K_CAP, true>(bt, (const uint32_t *)nullptr, b_pack, wlo, gtot, U, b, kS, kP, kA);
         batch_add(bt, U, bm, sub, super, base_rank, acc, token, tok_base == 0xFFFFFFFFu ? tok_base : tok_base + b, lds_atomic, ntok);
     }
@@ -1508,8 +1559,8 @@ __device__ __forceinline__ uint32_t walk_values(const BRec *__restrict__ b_pack,
 
 // OCC = waves per SIMD the register allocation aims at: 6 = three workgroups per CU (what the LDS of the 2^16 / 2^17
 // layouts allows; 80 VGPRs, a few spills), 4 = two per CU with 128 VGPRs (option spgemm_occupancy, A/B)
-template <int WL, typename IDX, typename PTR, bool NUMERIC, int OCC>
-__global__ __launch_bounds__(LG_BLOCK, OCC) void large_rows_kernel(CsrView<IDX, PTR> A, CsrView<IDX, PTR> B, uint64_t b_cols,
+template <int WL, typename IDX, typename PTR, bool NUMERIC, int OCC, typename T>
+__global__ __launch_bounds__(LG_BLOCK, OCC) void large_rows_kernel(CsrView<IDX, PTR, T> A, CsrView<IDX, PTR, T> B, uint64_t b_cols,
                                                               const uint64_t *__restrict__ large_list,
                                                               const uint64_t *__restrict__ task_row,
                                                               const uint64_t *__restrict__ first_task,
@@ -1517,7 +1568,7 @@ __global__ __launch_bounds__(LG_BLOCK, OCC) void large_rows_kernel(CsrView<IDX, 
                                                               const uint8_t *__restrict__ wlog,
                                                               uint64_t *__restrict__ count,       // symbolic: out
                                                               const uint64_t *__restrict__ off,   // numeric: in
-                                                              IDX *__restrict__ c_indices, double *__restrict__ c_data,
+                                                              IDX *__restrict__ c_indices, T *__restrict__ c_data,
                                                               uint32_t xcd_chunk, uint32_t flags,
                                                               unsigned long long *__restrict__ prof,
                                                               const uint64_t *__restrict__ ub_dbg,
@@ -1542,10 +1593,10 @@ __global__ __launch_bounds__(LG_BLOCK, OCC) void large_rows_kernel(CsrView<IDX, 
     __shared__ unsigned long long bm[WORDS];                 // the window's structure: one bit per column
     __shared__ uint16_t sub[NUMERIC ? WORDS : 1];            // outputs before a word inside its superblock
     __shared__ uint32_t super[NUMERIC ? NSUPER + 1 : 1];     // outputs before each 2048-column superblock
-    __shared__ double acc[NUMERIC ? ACC_CAP : 1];            // accumulators of the current pass
+    __shared__ T acc[NUMERIC ? ACC_CAP : 1];            // accumulators of the current pass
     __shared__ uint64_t kS[K_CAP];
     __shared__ uint32_t kP[K_CAP + 1];
-    __shared__ double kA[NUMERIC ? K_CAP : 1];
+    __shared__ T kA[NUMERIC ? K_CAP : 1];
     __shared__ uint64_t wt[16];
     __shared__ uint32_t token[4];
     const uint32_t tid = threadIdx.x;
@@ -1577,7 +1628,7 @@ __global__ __launch_bounds__(LG_BLOCK, OCC) void large_rows_kernel(CsrView<IDX, 
     // a row whose k's fit one staged group: thread j keeps k_j, the bounds of B's row k_j and a_ik for the whole task
     const bool mine_k = one_group && tid < (uint32_t)(ae - as) && w_begin < w_end;
     uint64_t rk = 0, rs = 0, re = 0, cur = 0, nxt_e = 0;
-    double rav = 0.0;
+    T rav = T(0);
     if (mine_k) {
         rk = (uint64_t)A.indices[as + tid];
         rs = (uint64_t)B.indptr[rk];
@@ -1612,7 +1663,7 @@ __global__ __launch_bounds__(LG_BLOCK, OCC) void large_rows_kernel(CsrView<IDX, 
             // below uses kS / kP / kA as they are left here), a row of several groups decides by the count of set bits
             for (int i = tid; i < words; i += LG_BLOCK) bm[i] = gbm[(wlo >> 6) + (uint64_t)i];
             if (one_group) {
-                k_total = stage_compact<K_CAP>(mine_k ? (uint32_t)(we - ws) : 0u, ws, rav, kS, kP, values ? kA : (double *)nullptr, wt);
+                k_total = stage_compact<K_CAP>(mine_k ? (uint32_t)(we - ws) : 0u, ws, rav, kS, kP, values ? kA : (T *)nullptr, wt);
                 any = k_total != 0;
             } else {
                 any = true;
@@ -1621,8 +1672,8 @@ __global__ __launch_bounds__(LG_BLOCK, OCC) void large_rows_kernel(CsrView<IDX, 
         for (uint64_t kc = as; kc < ae; kc += K_CAP) {
             const uint32_t n = (ae - kc < (uint64_t)K_CAP) ? (uint32_t)(ae - kc) : (uint32_t)K_CAP;
             const uint32_t gtot =
-                one_group ? stage_compact<K_CAP>(mine_k ? (uint32_t)(we - ws) : 0u, ws, rav, kS, kP, values ? kA : (double *)nullptr, wt)
-                          : stage_k_group<K_CAP>(A, B, kc, n, wlo, whi, nwin == 1, kS, kP, values ? kA : (double *)nullptr, wt);
+                one_group ? stage_compact<K_CAP>(mine_k ? (uint32_t)(we - ws) : 0u, ws, rav, kS, kP, values ? kA : (T *)nullptr, wt)
+                          : stage_k_group<K_CAP>(A, B, kc, n, wlo, whi, nwin == 1, kS, kP, values ? kA : (T *)nullptr, wt);
             k_total = gtot;
             any |= gtot != 0;
             walk_bits<K_CAP>(B.col32, wlo, gtot, kS, kP, (uint32_t *)bm);
@@ -1679,7 +1730,7 @@ __global__ __launch_bounds__(LG_BLOCK, OCC) void large_rows_kernel(CsrView<IDX, 
             // with the stores left out the kernel ran 17 % faster: profiles/r10i.)
             if (c_indices && !no_emit) {                            // (null: C already has its structure)
                 uint32_t *stage = (uint32_t *)acc;
-                constexpr uint32_t STAGE_CAP = 2u * ACC_CAP;
+                constexpr uint32_t STAGE_CAP = (uint32_t)(sizeof(T) / sizeof(uint32_t)) * ACC_CAP;    // what the accumulators' bytes hold
                 for (uint32_t base = 0; base < wtot; base += STAGE_CAP) {      // block-uniform
                     const uint32_t lim = wtot - base < STAGE_CAP ? wtot - base : STAGE_CAP;
 #pragma unroll 1
@@ -1724,7 +1775,7 @@ __global__ __launch_bounds__(LG_BLOCK, OCC) void large_rows_kernel(CsrView<IDX, 
                 const uint32_t base_rank = super[pb];
                 const uint32_t pass_out = super[pe] - base_rank;
                 if (pass_out) {                                  // block-uniform
-                    for (uint32_t i = tid; i < pass_out; i += LG_BLOCK) acc[i] = 0.0;   // tmp starts at N::zero()
+                    for (uint32_t i = tid; i < pass_out; i += LG_BLOCK) acc[i] = T(0);   // tmp starts at N::zero()
                     const bool single = pb == 0 && pe == (uint32_t)nsb;
                     const uint64_t plo = wlo + (uint64_t)pb * (SUPER_WORDS * 64);
                     const uint64_t phi = wlo + (uint64_t)pe * (SUPER_WORDS * 64);
@@ -1740,7 +1791,7 @@ __global__ __launch_bounds__(LG_BLOCK, OCC) void large_rows_kernel(CsrView<IDX, 
                             gtot = stage_k_group<K_CAP>(A, B, kc, n, single ? wlo : plo, single ? whi : phi, single && nwin == 1,
                                                         kS, kP, kA, wt);
                         }
-                        const uint32_t nb_ = walk_values<K_CAP>(B.pack, wlo, gtot, kS, kP, kA, bm, sub, super, base_rank, acc,
+                        const uint32_t nb_ = walk_values<K_CAP, T>(B.pack, wlo, gtot, kS, kP, kA, bm, sub, super, base_rank, acc,
                                                                 token, no_order ? 0xFFFFFFFFu : tok_base, lds_atomic, ntok);
                         tok_base += nb_;
                     }
@@ -1821,9 +1872,16 @@ namespace sprs_hip {
 
 namespace {
 
-template <typename IDX, typename PTR>
-CsrView<IDX, PTR> view_of(const sprs_hip_csmat *m) {
-    return CsrView<IDX, PTR>{(const PTR *)m->indptr, (const IDX *)m->indices, m->data, nullptr, 0, nullptr, nullptr};
+// the view the numeric kernels take: the handle's structure and its values (H = sprs_hip_csmat or sprs_hip_csmat_f32)
+template <typename IDX, typename PTR, typename H>
+CsrView<IDX, PTR, typename H::value_type> view_of(const H *m) {
+    return CsrView<IDX, PTR, typename H::value_type>{(const PTR *)m->indptr, (const IDX *)m->indices, m->data, nullptr, 0, nullptr, nullptr};
+}
+
+// the view the counting kernels take: structure only (they follow neither `data` nor `pack`), the same type for both handle types
+template <typename IDX, typename PTR, typename H>
+CsrView<IDX, PTR> structure_view_of(const H *m) {
+    return CsrView<IDX, PTR>{(const PTR *)m->indptr, (const IDX *)m->indices, nullptr, nullptr, 0, nullptr, nullptr};
 }
 
 // Option spgemm_overlap = 1: the wave kernels (hash rows, wave-per-row rows) run on a second stream beside the workgroup
@@ -1933,19 +1991,107 @@ bool lds_lane_order_ok() {
     return ok;
 }
 
+// ---- the same probe for the f32 LDS add, plus sums among f32 subnormals -----------------------------------------------
+// Nothing was known about the f32 form of the add (ds_add_f32).  Two separate questions, two verdicts, cached per device:
+//   * order: the lanes of ONE instruction that hit one address are applied in ascending lane order (trials as above, f32);
+//   * subnormal: operands and results that are f32 subnormals are kept (the reference runs on a CPU that keeps them; an LDS
+//     add that flushed them to zero would change bits).  These trials add integer multiples of 2^-149 whose sums stay
+//     below 2^-126 or just cross it: exact in any order, so a failure here says nothing but "flushed".
+// order fails -> one add per k-run (as option spgemm_lane_order = 2); subnormal fails -> read, add, write (as option
+// spgemm_lds_atomic = 0) in every f32 kernel.  All three forms give the same bits.
+__global__ __launch_bounds__(WAVE) void lane_order_probe_f32_kernel(const float *__restrict__ v, const uint32_t *__restrict__ slot,
+                                                                    float *__restrict__ out) {
+    __shared__ float acc[8];
+    const uint32_t lane = threadIdx.x;
+    if (lane < 8) acc[lane] = 0.0f;
+    wave_sync_lds();
+    atomicAdd(&acc[slot[blockIdx.x * WAVE + lane]], v[blockIdx.x * WAVE + lane]);
+    wave_sync_lds();
+    if (lane < 8) out[blockIdx.x * 8 + lane] = acc[lane];
+}
+
+struct LdsAddF32 {
+    bool order = false, subnormal = false;
+};
+
+LdsAddF32 lds_add_f32_probe() {
+    static std::mutex mu;
+    static std::unordered_map<int, LdsAddF32> per_device;
+    std::lock_guard<std::mutex> lock(mu);
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return LdsAddF32();
+    auto it = per_device.find(dev);
+    if (it != per_device.end()) return it->second;
+    constexpr int ORDER_TRIALS = 256, SUB_TRIALS = 64, TRIALS = ORDER_TRIALS + SUB_TRIALS;
+    std::vector<float> v(TRIALS * WAVE), got(TRIALS * 8, -1.0f);
+    std::vector<float> ref(TRIALS * 8, 0.0f);
+    std::vector<uint32_t> slot(TRIALS * WAVE);
+    uint64_t s = 0x13198A2E03707344ull;
+    auto next = [&]() {
+        uint64_t z = (s += 0x9E3779B97F4A7C15ull);
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        return z ^ (z >> 31);
+    };
+    static const int NSLOT[4] = {1, 2, 3, 8};
+    const float tiny = std::ldexp(1.0f, -149);            // the smallest f32 subnormal
+    for (int t = 0; t < TRIALS; ++t)
+        for (int l = 0; l < WAVE; ++l) {
+            const uint64_t h = next();
+            float x;
+            if (t < ORDER_TRIALS) {
+                const float m = 0.5f + (float)(h >> 40) * (1.0f / 16777216.0f);
+                x = std::ldexp((h & 1) ? -m : m, (int)(next() % 25) - 12);         // magnitudes over 2^-12 .. 2^12: the order shows in the last bits
+            } else {
+                // up to 2^17 times 2^-149, either sign: the operands are subnormal, the partial sums subnormal or just past 2^-126
+                // (at most 64 * 2^17 = 2^23 times 2^-149: every sum is exact, in any order)
+                const float m = (float)(1 + (h >> 47));
+                x = ((h & 1) ? -m : m) * tiny;
+            }
+            v[t * WAVE + l] = x;
+            slot[t * WAVE + l] = (uint32_t)(next() % (uint64_t)NSLOT[t & 3]);
+            ref[t * 8 + slot[t * WAVE + l]] = ref[t * 8 + slot[t * WAVE + l]] + x;    // ascending lane order, one rounding per add
+        }
+    LdsAddF32 res;
+    DevBuf dv, ds, dout;
+    if (dv.alloc_pooled(v.size() * 4) == hipSuccess && ds.alloc_pooled(slot.size() * 4) == hipSuccess && dout.alloc_pooled(got.size() * 4) == hipSuccess &&
+        copy_to_device(dv.p, v.data(), v.size() * 4, nullptr) == hipSuccess &&
+        copy_to_device(ds.p, slot.data(), slot.size() * 4, nullptr) == hipSuccess) {
+        hipLaunchKernelGGL(lane_order_probe_f32_kernel, dim3(TRIALS), dim3(WAVE), 0, nullptr, dv.as<float>(), ds.as<uint32_t>(), dout.as<float>());
+        if (hipGetLastError() == hipSuccess && copy_to_host(got.data(), dout.p, got.size() * 4, nullptr) == hipSuccess) {
+            const std::vector<float> &want = ref;
+            res.order = memcmp(got.data(), want.data(), (size_t)ORDER_TRIALS * 8 * 4) == 0;
+            res.subnormal = memcmp(got.data() + ORDER_TRIALS * 8, want.data() + ORDER_TRIALS * 8, (size_t)SUB_TRIALS * 8 * 4) == 0;
+        }
+    }
+    (void)hipGetLastError();
+    per_device[dev] = res;
+    return res;
+}
+
 // what the wave kernels are told about the adds (bit 0: one ds_add_f64 per wave instruction)
 uint32_t add_flags() { return options().spgemm_lane_order != 2 && lds_lane_order_ok() ? 1u : 0u; }
+// the f32 kernels: bit 0 as above, by the f32 probe; bit 1: the LDS add does not keep f32 subnormals -> read, add, write
+uint32_t add_flags_f32() {
+    const LdsAddF32 p = lds_add_f32_probe();
+    return (options().spgemm_lane_order != 2 && p.order && p.subnormal ? 1u : 0u) | (p.subnormal ? 0u : 2u);
+}
+template <typename T>
+uint32_t add_flags_of() {
+    if constexpr (std::is_same<T, float>::value) return add_flags_f32();
+    else return add_flags();
+}
 
 // ---- the launches of one phase ------------------------------------------------------------------------------------
 // Counting (plan_build, NUMERIC = false) and numeric (plan_run, NUMERIC = true) launch the same kernel families over the plan's task
 // lists.  PhaseArgs holds what differs between them; a launch_* picks its instantiation from the plan and the options.
-template <typename IDX, typename PTR>
+template <typename IDX, typename PTR, typename T = double>
 struct PhaseArgs {
-    CsrView<IDX, PTR> A, B;                // (numeric: B with its {column, value} records)
+    CsrView<IDX, PTR, T> A, B;             // (numeric: B with its {column, value} records)
     const uint64_t *off = nullptr;         // offsets of the tasks' outputs (numeric)
     const uint64_t *ub = nullptr;          // products per row for the workgroup and wave-per-row kernels (numeric; the hash kernels always read the plan's)
     IDX *c_indices = nullptr;              // (null: not written)
-    double *c_values = nullptr;
+    T *c_values = nullptr;
     uint32_t large_flags = 0, hash_flags = 0, bin_shift = 0, mid_flags = 0;
     unsigned long long *large_prof = nullptr, *mid_prof = nullptr;      // developer build, option spgemm_prof
     uint32_t counter_slot = 0;             // the word of pl->counters the wave-per-row kernel draws its rows from
@@ -1975,11 +2121,11 @@ dim3 mid_grid(uint64_t n_tasks) {
 }
 
 // ONE launch for all large tasks, in the LDS layout of the window width (option spgemm_winlog)
-template <bool NUMERIC, typename IDX, typename PTR>
-int32_t launch_large(const sprs_hip_spgemm_plan *pl, const PhaseArgs<IDX, PTR> &ph, hipStream_t stream) {
+template <bool NUMERIC, typename IDX, typename PTR, typename T>
+int32_t launch_large(const sprs_hip_spgemm_plan *pl, const PhaseArgs<IDX, PTR, T> &ph, hipStream_t stream) {
     if (!pl->n_large) return SPRS_HIP_OK;
     auto go = [&](auto wl, auto occ) {
-        hipLaunchKernelGGL((large_rows_kernel<decltype(wl)::value, IDX, PTR, NUMERIC, decltype(occ)::value>), dim3((unsigned)pl->n_large),
+        hipLaunchKernelGGL((large_rows_kernel<decltype(wl)::value, IDX, PTR, NUMERIC, decltype(occ)::value, T>), dim3((unsigned)pl->n_large),
                            dim3(LG_BLOCK), 0, stream, ph.A, ph.B, pl->b_cols, pl->large_list.u64(), pl->task_row.u64(), pl->first_task.u64(),
                            pl->ntasks.u64(), pl->wlog.as<uint8_t>(), pl->count.u64(), ph.off, ph.c_indices, ph.c_values, pl->xcd_chunk,
                            ph.large_flags, ph.large_prof, ph.ub, pl->large_slot.u64(),
@@ -2006,12 +2152,12 @@ int32_t launch_large(const sprs_hip_spgemm_plan *pl, const PhaseArgs<IDX, PTR> &
 }
 
 // the micro rows: class list 0 / 1 / 2 on groups of 16 / 32 / 64 lanes
-template <bool NUMERIC, typename IDX, typename PTR>
-int32_t launch_micro(const sprs_hip_spgemm_plan *pl, const PhaseArgs<IDX, PTR> &ph, hipStream_t stream) {
+template <bool NUMERIC, typename IDX, typename PTR, typename T>
+int32_t launch_micro(const sprs_hip_spgemm_plan *pl, const PhaseArgs<IDX, PTR, T> &ph, hipStream_t stream) {
     auto go = [&](int m, auto group, auto key) -> int32_t {
         constexpr int G = decltype(group)::value;
         if (!pl->n_micro[m]) return SPRS_HIP_OK;
-        hipLaunchKernelGGL((micro_rows_kernel<IDX, PTR, NUMERIC, G, typename decltype(key)::type>), micro_grid(pl->n_micro[m], WAVE / G),
+        hipLaunchKernelGGL((micro_rows_kernel<IDX, PTR, NUMERIC, G, typename decltype(key)::type, T>), micro_grid(pl->n_micro[m], WAVE / G),
                            dim3(256), 0, stream, ph.A, ph.B, pl->ent_ext.u64(), pl->micro_list[m].as<MicroRec>(), pl->n_micro[m],
                            pl->count.u64(), ph.off, ph.c_indices, ph.c_values);
         SPRS_TRY_HIP(hipGetLastError());
@@ -2026,23 +2172,23 @@ int32_t launch_micro(const sprs_hip_spgemm_plan *pl, const PhaseArgs<IDX, PTR> &
 }
 
 // the hash rows of one list: tiny (TAB = TINY_TAB) or small (SMALL_TAB)
-template <bool NUMERIC, int TAB, typename IDX, typename PTR>
-int32_t launch_hash(const sprs_hip_spgemm_plan *pl, const PhaseArgs<IDX, PTR> &ph, const DevBuf &list, uint64_t n, hipStream_t stream) {
+template <bool NUMERIC, int TAB, typename IDX, typename PTR, typename T>
+int32_t launch_hash(const sprs_hip_spgemm_plan *pl, const PhaseArgs<IDX, PTR, T> &ph, const DevBuf &list, uint64_t n, hipStream_t stream) {
     if (!n) return SPRS_HIP_OK;
-    hipLaunchKernelGGL((small_rows_kernel<IDX, PTR, NUMERIC, TAB>), small_grid(n), dim3(SM_BLOCK), 0, stream, ph.A, ph.B, list.u64(), n,
+    hipLaunchKernelGGL((small_rows_kernel<IDX, PTR, NUMERIC, TAB, T>), small_grid(n), dim3(SM_BLOCK), 0, stream, ph.A, ph.B, list.u64(), n,
                        pl->task_row.u64(), pl->ub.u64(), pl->count.u64(), ph.off, ph.c_indices, ph.c_values, ph.bin_shift, ph.hash_flags);
     SPRS_TRY_HIP(hipGetLastError());
     return SPRS_HIP_OK;
 }
 
 // the wave-per-row rows (the counting kernel has no accumulators: windows of up to 2^16 columns, four times fewer prologues per row)
-template <bool NUMERIC, typename IDX, typename PTR>
-int32_t launch_mid(const sprs_hip_spgemm_plan *pl, const PhaseArgs<IDX, PTR> &ph, hipStream_t stream) {
+template <bool NUMERIC, typename IDX, typename PTR, typename T>
+int32_t launch_mid(const sprs_hip_spgemm_plan *pl, const PhaseArgs<IDX, PTR, T> &ph, hipStream_t stream) {
     if (!pl->n_mid) return SPRS_HIP_OK;
     unsigned int *counter = pl->counters.as<unsigned int>() + ph.counter_slot;
     SPRS_TRY_HIP(hipMemsetAsync(counter, 0, NUMERIC ? 4 : COUNTER_BYTES, stream));
     auto go = [&](auto wl, auto keep) {
-        hipLaunchKernelGGL((mid_rows_kernel<IDX, PTR, NUMERIC, decltype(wl)::value, decltype(keep)::value>), mid_grid(pl->n_mid),
+        hipLaunchKernelGGL((mid_rows_kernel<IDX, PTR, NUMERIC, decltype(wl)::value, decltype(keep)::value, T>), mid_grid(pl->n_mid),
                            dim3(MID_BLOCK), 0, stream, ph.A, ph.B, pl->b_cols, pl->mid_list.u64(), pl->n_mid, pl->task_row.u64(),
                            pl->count.u64(), ph.off, ph.c_indices, ph.c_values, ph.mid_prof, ph.ub, counter, ph.mid_flags);
     };
@@ -2061,8 +2207,8 @@ int32_t launch_mid(const sprs_hip_spgemm_plan *pl, const PhaseArgs<IDX, PTR> &ph
 
 // All launches of one phase: the large rows first on the main stream (the long tasks start at once), the wave kernels beside
 // them on the second stream (option spgemm_overlap), joined before this returns.
-template <bool NUMERIC, typename IDX, typename PTR>
-int32_t launch_phase(const sprs_hip_spgemm_plan *pl, const PhaseArgs<IDX, PTR> &ph, hipStream_t stream) {
+template <bool NUMERIC, typename IDX, typename PTR, typename T>
+int32_t launch_phase(const sprs_hip_spgemm_plan *pl, const PhaseArgs<IDX, PTR, T> &ph, hipStream_t stream) {
     AuxFork aux(stream);
     SPRS_TRY(launch_large<NUMERIC>(pl, ph, stream));
     SPRS_TRY(launch_micro<NUMERIC>(pl, ph, aux.wave));
@@ -2074,8 +2220,10 @@ int32_t launch_phase(const sprs_hip_spgemm_plan *pl, const PhaseArgs<IDX, PTR> &
 }
 
 // ---- symbolic phase: counts, offsets, task lists ---------------------------------------------------------
-template <typename IDX, typename PTR>
-int32_t plan_build(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_spgemm_plan *pl) {
+// H = the handle type of the operands: only the structure fields they share (CsmatCore) are read, so the plan is the same
+// for an f64 and an f32 pair over the same index arrays
+template <typename IDX, typename PTR, typename H>
+int32_t plan_build(const H *a, const H *b, sprs_hip_spgemm_plan *pl) {
     hipStream_t stream = nullptr;
     const uint64_t rows = a->rows, b_cols = b->cols;
     pl->idx_bytes = (int32_t)sizeof(IDX);
@@ -2092,7 +2240,7 @@ int32_t plan_build(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_sp
     pl->winlog = options().spgemm_winlog;
     pl->midwin = options().spgemm_midwin;
     pl->xcd_chunk = options().spgemm_xcd_chunk < 0 ? 0xFFFFFFFFu : (uint32_t)options().spgemm_xcd_chunk;
-    CsrView<IDX, PTR> A = view_of<IDX, PTR>(a), B = view_of<IDX, PTR>(b);
+    CsrView<IDX, PTR> A = structure_view_of<IDX, PTR>(a), B = structure_view_of<IDX, PTR>(b);
     // column-bucket table of B (4 bytes per 2048 columns per row; config 5: 1.96 GB): bounded — up to 4 GiB outright
     // (1.4 % of the device), beyond that only within a small multiple of B's own size and never above 8 GiB (a
     // 10M x 10M operand would ask for 195 GB) — and skipped when pointless (every row of B has at most one entry);
@@ -2231,7 +2379,7 @@ int32_t plan_build(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_sp
 
 // ---- option spgemm_prof (developer build): what the numeric kernels' timers say ----------------------------------
 // 100 MHz ticks per large task, by block (= position in the launch order)
-void print_large_prof(const sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, const DevBuf &prof, hipStream_t stream) {
+void print_large_prof(const sprs_hip_spgemm_plan *pl, const void *a_indptr, const DevBuf &prof, hipStream_t stream) {
     const uint64_t n_large = pl->n_large;
     unsigned long long phs[40];
     (void)copy_to_host(phs, (char *)prof.p + n_large * 8, 320, stream);
@@ -2246,7 +2394,7 @@ void print_large_prof(const sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, c
     (void)copy_to_host(ubv.data(), pl->ub.p, pl->rows * 8, stream);
     (void)copy_to_host(ntk.data(), pl->ntasks.p, pl->rows * 8, stream);
     std::vector<uint64_t> a_ip(pl->rows + 1);
-    if (pl->iptr_bytes == 8) (void)copy_to_host(a_ip.data(), a->indptr, (pl->rows + 1) * 8, stream);
+    if (pl->iptr_bytes == 8) (void)copy_to_host(a_ip.data(), a_indptr, (pl->rows + 1) * 8, stream);
     double sum = 0;
     unsigned long long mx = 0;
     // classes by products per task: < 2^13, < 2^15, < 2^17, < 2^19, rest
@@ -2292,24 +2440,30 @@ void print_mid_prof(const sprs_hip_spgemm_plan *pl, const DevBuf &mprof, hipStre
 }
 
 // ---- numeric phase: indices (optional) and values into a matrix of the product's structure -------------------------
-template <typename IDX, typename PTR>
-int32_t plan_run(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat *c, bool values,
+template <typename IDX, typename PTR, typename H>
+int32_t plan_run(sprs_hip_spgemm_plan *pl, const H *a, const H *b, H *c, bool values,
                  bool indices) {
+    using T = typename H::value_type;
+    using Rec = typename BRecOf<T>::type;
     hipStream_t stream = nullptr;
-    CsrView<IDX, PTR> A = view_of<IDX, PTR>(a), B = view_of<IDX, PTR>(b);
+    CsrView<IDX, PTR, T> A = view_of<IDX, PTR>(a), B = view_of<IDX, PTR>(b);
     B.bucket = pl->nb ? pl->bucket.as<uint32_t>() : nullptr;
     B.nb = pl->nb;
     B.col32 = sizeof(IDX) == 4 ? (const uint32_t *)b->indices : pl->bcol32.as<uint32_t>();
     if (values && (pl->n_mid || pl->n_large)) {
-        // {column, value} records of B for the value walks; rebuilt per call: the values of b may have changed since the plan was made
-        SPRS_TRY_HIP(pl->bpack.alloc_pooled((b->nnz ? b->nnz : 1) * sizeof(BRec)));
+        // {column, value} records of B for the value walks; rebuilt per call, in the caller's record type (16 bytes for f64, 8 for
+        // f32): the values of b may have changed since the plan was made, and so may the precision of the handles it serves
+        SPRS_TRY_HIP(pl->bpack.alloc_pooled((b->nnz ? b->nnz : 1) * sizeof(Rec)));
         if (b->nnz) {
-            hipLaunchKernelGGL((pack_entries_kernel<IDX>), dim3(2048), dim3(256), 0, stream, B.indices, B.data, b->nnz, pl->bpack.as<BRec>());
+            if constexpr (std::is_same<T, float>::value)
+                hipLaunchKernelGGL((pack_entries_f32_kernel<IDX>), dim3(2048), dim3(256), 0, stream, B.indices, B.data, b->nnz, pl->bpack.as<Rec>());
+            else
+                hipLaunchKernelGGL((pack_entries_kernel<IDX>), dim3(2048), dim3(256), 0, stream, B.indices, B.data, b->nnz, pl->bpack.as<Rec>());
             SPRS_TRY_HIP(hipGetLastError());
         }
-        B.pack = pl->bpack.as<BRec>();
+        B.pack = pl->bpack.as<Rec>();
     }
-    PhaseArgs<IDX, PTR> ph{A, B};
+    PhaseArgs<IDX, PTR, T> ph{A, B};
     ph.off = pl->off.u64();
     ph.ub = pl->ub.u64();
     ph.c_indices = indices ? (IDX *)c->indices : nullptr;
@@ -2317,15 +2471,17 @@ int32_t plan_run(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, const sprs_h
     // large rows, bit 2: the adds of a workgroup's waves are NOT put in the reference's order (option spgemm_ordered = 0: every C(i,j) still
     // is the sum of the same products, added by LDS atomics in whatever order the waves arrive — rounding-level differences,
     // not reproducible run to run; structure unaffected).  Needs the atomic form of the add.
-    const bool unordered = options().spgemm_ordered == 0, atomic = options().spgemm_lds_atomic || unordered;
+    // (f32 on a device whose LDS add drops subnormals — add_flags_f32, bit 1 — orders its adds by read, add, write)
+    const uint32_t wave_flags = add_flags_of<T>();
+    const bool unordered = options().spgemm_ordered == 0, atomic = (options().spgemm_lds_atomic && !(wave_flags & 2u)) || unordered;
     if (pl->n_large)
         ph.large_flags = (atomic ? 1u : 0u) | (unordered ? 4u : 0u) | ((uint32_t)(options().spgemm_debug & 3) << 2) |
                          ((options().spgemm_tokens >= 4 ? 2u : options().spgemm_tokens >= 2 ? 1u : 0u) << 4) |
-                         (atomic && add_flags() ? 64u : 0u);
+                         (atomic && (wave_flags & 1u) ? 64u : 0u);
     // bins of the hash kernels' rank pass: the column space cut into SM_NBIN equal power-of-two ranges
     while (ph.bin_shift < 32 && ((pl->b_cols - (pl->b_cols ? 1 : 0)) >> ph.bin_shift) >= (uint64_t)SM_NBIN) ++ph.bin_shift;
-    ph.hash_flags = add_flags();
-    if (pl->n_mid) ph.mid_flags = add_flags() | (DEVTOOLS ? (uint32_t)options().spgemm_debug << 2 : 0u);
+    ph.hash_flags = wave_flags & 1u;
+    if (pl->n_mid) ph.mid_flags = wave_flags | (DEVTOOLS ? (uint32_t)options().spgemm_debug << 2 : 0u);
     ph.counter_slot = NUMERIC_COUNTER;
     DevBuf prof, mprof;
     if (DEVTOOLS && options().spgemm_prof) {
@@ -2344,13 +2500,13 @@ int32_t plan_run(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, const sprs_h
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e != hipSuccess) return fail_hip(e, "spgemm numeric");
-    if (DEVTOOLS && prof.p) print_large_prof(pl, a, prof, stream);
+    if (DEVTOOLS && prof.p) print_large_prof(pl, a->indptr, prof, stream);
     if (DEVTOOLS && mprof.p) print_mid_prof(pl, mprof, stream);
     return SPRS_HIP_OK;
 }
 
-template <typename PTR>
-int32_t plan_indptr(sprs_hip_spgemm_plan *pl, sprs_hip_csmat *c, bool compare) {
+template <typename PTR, typename H>
+int32_t plan_indptr(sprs_hip_spgemm_plan *pl, H *c, bool compare) {
     hipStream_t stream = nullptr;
     const dim3 g((unsigned)((pl->rows + 256) / 256)), b(256);
     if (!compare) {
@@ -2370,21 +2526,28 @@ int32_t plan_indptr(sprs_hip_spgemm_plan *pl, sprs_hip_csmat *c, bool compare) {
     return SPRS_HIP_OK;
 }
 
-int32_t plan_indptr(sprs_hip_spgemm_plan *pl, sprs_hip_csmat *c, bool compare) {
+template <typename H>
+int32_t plan_indptr(sprs_hip_spgemm_plan *pl, H *c, bool compare) {
     return dispatch_width(pl->iptr_bytes, [&](auto p) { return plan_indptr<typename decltype(p)::type>(pl, c, compare); });
 }
 
-int32_t plan_run(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat *c, bool values, bool indices) {
+// The float instantiations of the numeric kernels take the indptr type as `const PTR` (the kernels only read through it), which
+// sets their symbols apart from the f64 ones by more than the trailing scalar: tools that select the f64 kernels by a prefix of
+// their names (tests/test_isa_cpu.py pins the 16-byte-record load bursts of those) keep selecting exactly them.
+template <typename H>
+int32_t plan_run(sprs_hip_spgemm_plan *pl, const H *a, const H *b, H *c, bool values, bool indices) {
     return dispatch_widths(pl->idx_bytes, pl->iptr_bytes, [&](auto i, auto p) {
-        return plan_run<typename decltype(i)::type, typename decltype(p)::type>(pl, a, b, c, values, indices);
+        using P = typename decltype(p)::type;
+        using PTR = std::conditional_t<std::is_same<typename H::value_type, float>::value, const P, P>;
+        return plan_run<typename decltype(i)::type, PTR>(pl, a, b, c, values, indices);
     });
 }
 
 using OwnedPlan = std::unique_ptr<sprs_hip_spgemm_plan, decltype(&spgemm_plan_free)>;
 
-}  // namespace
-
-int32_t spgemm_plan_create(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_spgemm_plan **out) {
+// ---- one body per entry for both handle types (H = sprs_hip_csmat or sprs_hip_csmat_f32) -------------------------------------
+template <typename H>
+int32_t plan_create_t(const H *a, const H *b, sprs_hip_spgemm_plan **out) {
     if (b->cols > 0xFFFFFFFEull) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "SpGEMM: more than 2^32-2 columns is not supported");
     OwnedPlan pl(new sprs_hip_spgemm_plan(), spgemm_plan_free);
     SPRS_TRY(dispatch_widths(a->idx_bytes, a->iptr_bytes, [&](auto i, auto p) {
@@ -2394,9 +2557,10 @@ int32_t spgemm_plan_create(const sprs_hip_csmat *a, const sprs_hip_csmat *b, spr
     return SPRS_HIP_OK;
 }
 
-void spgemm_plan_free(sprs_hip_spgemm_plan *pl) { delete pl; }
-
-static int32_t plan_matches(const sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, const sprs_hip_csmat *b) {
+// A plan holds no values and no record of the precision it was made from: it matches operands of either handle type over the
+// same structure arrays (bpack is re-packed per call in the caller's record type).
+template <typename H>
+int32_t plan_matches(const sprs_hip_spgemm_plan *pl, const H *a, const H *b) {
     if (pl->rows != a->rows || pl->inner != a->cols || pl->b_cols != b->cols || pl->nnz_a != a->nnz || pl->nnz_b != b->nnz ||
         pl->idx_bytes != a->idx_bytes || pl->iptr_bytes != a->iptr_bytes || pl->a_indptr != a->indptr || pl->a_indices != a->indices ||
         pl->b_indptr != b->indptr || pl->b_indices != b->indices)
@@ -2405,13 +2569,14 @@ static int32_t plan_matches(const sprs_hip_spgemm_plan *pl, const sprs_hip_csmat
 }
 
 // structure of the product as a new matrix (values zero): what smmp::symbolic returns
-int32_t spgemm_plan_structure(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, const sprs_hip_csmat *b, OwnedCsmat &out,
-                              bool with_values) {
+template <typename H>
+int32_t plan_structure_t(sprs_hip_spgemm_plan *pl, const H *a, const H *b, Owned<H> &out, bool with_values) {
     SPRS_TRY(plan_matches(pl, a, b));
-    OwnedCsmat c;
+    Owned<H> c;
     SPRS_TRY(make_csmat(c, SPRS_HIP_CSR, pl->rows, pl->b_cols, pl->c_nnz, pl->iptr_bytes, pl->idx_bytes));
     SPRS_TRY(plan_indptr(pl, c.get(), false));
-    const hipError_t e = with_values ? hipSuccess : hipMemsetAsync(c->data, 0, (pl->c_nnz ? pl->c_nnz : 1) * sizeof(double), nullptr);
+    const hipError_t e =
+        with_values ? hipSuccess : hipMemsetAsync(c->data, 0, (pl->c_nnz ? pl->c_nnz : 1) * sizeof(typename H::value_type), nullptr);
     if (e != hipSuccess) return fail_hip(e, "spgemm structure");
     SPRS_TRY(plan_run(pl, a, b, c.get(), with_values, true));
     out = std::move(c);
@@ -2420,7 +2585,8 @@ int32_t spgemm_plan_structure(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a,
 
 // values into a matrix that already has the product's structure (smmp::numeric, smmp.rs:151-189): shape, nnz and indptr
 // are checked; the indices of c are neither read nor written
-int32_t spgemm_plan_numeric(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat *c) {
+template <typename H>
+int32_t plan_numeric_t(sprs_hip_spgemm_plan *pl, const H *a, const H *b, H *c) {
     SPRS_TRY(plan_matches(pl, a, b));
     if (c->nnz != pl->c_nnz)
         SPRS_FAIL(SPRS_HIP_BAD_STRUCTURE, "numeric: C holds %llu entries, the product has %llu", (unsigned long long)c->nnz,
@@ -2429,29 +2595,67 @@ int32_t spgemm_plan_numeric(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, c
     return plan_run(pl, a, b, c, true, false);
 }
 
-uint64_t spgemm_plan_nnz(const sprs_hip_spgemm_plan *pl) { return pl->c_nnz; }
-
 // a product that keeps no plan: f(plan) runs on one that lives for this call
-template <typename F>
-static int32_t with_temporary_plan(const sprs_hip_csmat *a, const sprs_hip_csmat *b, F &&f) {
+template <typename H, typename F>
+int32_t with_temporary_plan(const H *a, const H *b, F &&f) {
     sprs_hip_spgemm_plan *pl = nullptr;
-    SPRS_TRY(spgemm_plan_create(a, b, &pl));
+    SPRS_TRY(plan_create_t(a, b, &pl));
     OwnedPlan own(pl, spgemm_plan_free);
     return f(pl);
 }
 
-int32_t spgemm_f64(const sprs_hip_csmat *a, const sprs_hip_csmat *b, OwnedCsmat &c) {
-    return with_temporary_plan(a, b, [&](sprs_hip_spgemm_plan *pl) { return spgemm_plan_structure(pl, a, b, c, true); });
+template <typename H>
+int32_t product_t(const H *a, const H *b, Owned<H> &c) {
+    return with_temporary_plan(a, b, [&](sprs_hip_spgemm_plan *pl) { return plan_structure_t(pl, a, b, c, true); });
 }
 
 // smmp::symbolic (smmp.rs:81-131): structure only; the values of the result are zero
-int32_t spgemm_symbolic(const sprs_hip_csmat *a, const sprs_hip_csmat *b, OwnedCsmat &c) {
-    return with_temporary_plan(a, b, [&](sprs_hip_spgemm_plan *pl) { return spgemm_plan_structure(pl, a, b, c, false); });
+template <typename H>
+int32_t symbolic_t(const H *a, const H *b, Owned<H> &c) {
+    return with_temporary_plan(a, b, [&](sprs_hip_spgemm_plan *pl) { return plan_structure_t(pl, a, b, c, false); });
 }
 
 // smmp::numeric (smmp.rs:151-189) without a kept plan: the symbolic phase is redone to check c and to cut the work
-int32_t spgemm_numeric(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat *c) {
-    return with_temporary_plan(a, b, [&](sprs_hip_spgemm_plan *pl) { return spgemm_plan_numeric(pl, a, b, c); });
+template <typename H>
+int32_t numeric_t(const H *a, const H *b, H *c) {
+    return with_temporary_plan(a, b, [&](sprs_hip_spgemm_plan *pl) { return plan_numeric_t(pl, a, b, c); });
 }
+
+}  // namespace
+
+// what the f32 probe of the LDS add found on the current device (run now if it has not been): bit 0 same-address lanes of one
+// instruction are applied in ascending lane order, bit 1 f32 subnormals are kept; 3 = the f32 kernels use one LDS add per wave
+// instruction.  Read through sprs_hip_get_option("spgemm_f32_lds_add").
+int64_t spgemm_f32_lds_add_verdict() {
+    const LdsAddF32 p = lds_add_f32_probe();
+    return (p.order ? 1 : 0) | (p.subnormal ? 2 : 0);
+}
+
+void spgemm_plan_free(sprs_hip_spgemm_plan *pl) { delete pl; }
+uint64_t spgemm_plan_nnz(const sprs_hip_spgemm_plan *pl) { return pl->c_nnz; }
+
+int32_t spgemm_plan_create(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_spgemm_plan **out) { return plan_create_t(a, b, out); }
+int32_t spgemm_plan_structure(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, const sprs_hip_csmat *b, OwnedCsmat &out, bool with_values) {
+    return plan_structure_t(pl, a, b, out, with_values);
+}
+int32_t spgemm_plan_numeric(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat *c) {
+    return plan_numeric_t(pl, a, b, c);
+}
+int32_t spgemm_f64(const sprs_hip_csmat *a, const sprs_hip_csmat *b, OwnedCsmat &c) { return product_t(a, b, c); }
+int32_t spgemm_symbolic(const sprs_hip_csmat *a, const sprs_hip_csmat *b, OwnedCsmat &c) { return symbolic_t(a, b, c); }
+int32_t spgemm_numeric(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat *c) { return numeric_t(a, b, c); }
+
+// the f32 twins: the same bodies on sprs_hip_csmat_f32 (numeric kernels instantiated for float, 8-byte records of B)
+int32_t spgemm_plan_create(const sprs_hip_csmat_f32 *a, const sprs_hip_csmat_f32 *b, sprs_hip_spgemm_plan **out) { return plan_create_t(a, b, out); }
+int32_t spgemm_plan_structure(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat_f32 *a, const sprs_hip_csmat_f32 *b, OwnedCsmatF32 &out,
+                              bool with_values) {
+    return plan_structure_t(pl, a, b, out, with_values);
+}
+int32_t spgemm_plan_numeric(sprs_hip_spgemm_plan *pl, const sprs_hip_csmat_f32 *a, const sprs_hip_csmat_f32 *b, sprs_hip_csmat_f32 *c) {
+    return plan_numeric_t(pl, a, b, c);
+}
+int32_t spgemm_f32(const sprs_hip_csmat_f32 *a, const sprs_hip_csmat_f32 *b, OwnedCsmatF32 &c) { return product_t(a, b, c); }
+int32_t spgemm_symbolic(const sprs_hip_csmat_f32 *a, const sprs_hip_csmat_f32 *b, OwnedCsmatF32 &c) { return symbolic_t(a, b, c); }
+int32_t spgemm_numeric(const sprs_hip_csmat_f32 *a, const sprs_hip_csmat_f32 *b, sprs_hip_csmat_f32 *c) { return numeric_t(a, b, c); }
 
 }  // namespace sprs_hip

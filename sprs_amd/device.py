@@ -390,6 +390,8 @@ class DeviceCsMat(_DeviceCsMatBase):
             return prod.csmat_mul_vec(self, rhs)          # csmat.rs:2119-2160
         if isinstance(rhs, DeviceCsMat):
             return prod.csmat_mul_csmat(self, rhs)        # csmat.rs:1866-1949
+        if isinstance(rhs, DeviceCsMatF32):
+            raise TypeError("an f64 matrix times an f32 matrix: convert one operand (DeviceCsMat.to_f32 / DeviceCsMatF32.to_f64)")
         if isinstance(rhs, prod.DeviceMat):
             return prod.csmat_mul_dense(self, rhs)        # csmat.rs:1989-2048
         if isinstance(rhs, prod.DeviceMatF32):
@@ -430,7 +432,8 @@ class DeviceCsMat(_DeviceCsMatBase):
 class DeviceCsMatF32(_DeviceCsMatBase):
     """A CSR/CSC matrix of f32 values in HBM behind a `sprs_hip_csmat_f32*` handle: CsMat<f32>.  Built for it: the container,
     `&A * &x` and the two mul_acc forms with DeviceVecF32, `&A * &B` and the four mulacc_dense forms with prod.DeviceMatF32,
-    prod.dense_dot_csmat (prod.py), BiCGSTAB (linalg.py); `to_f64()` reaches every other
+    prod.dense_dot_csmat (prod.py), `&A * &B` with another DeviceCsMatF32 and the smmp functions (smmp.py), BiCGSTAB
+    (linalg.py); `to_f64()` reaches every other
     operation.  Index arrays are 4 or 8 bytes wide (no 2-byte ones)."""
     _dtype, _container, _suffix = np.float32, "sprs_hip_csmat_f32_", "f32"
 
@@ -457,6 +460,10 @@ class DeviceCsMatF32(_DeviceCsMatBase):
             return prod.csmat_mul_dense(self, rhs)        # csmat.rs:1989-2048
         if isinstance(rhs, prod.DeviceMat):
             raise TypeError("an f32 matrix times an f64 dense matrix: convert one operand (DeviceCsMatF32.to_f64)")
+        if isinstance(rhs, DeviceCsMatF32):
+            return prod.csmat_mul_csmat(self, rhs)        # csmat.rs:1866-1949, N = f32
+        if isinstance(rhs, DeviceCsMat):
+            raise TypeError("an f32 matrix times an f64 matrix: convert one operand (DeviceCsMatF32.to_f64 / DeviceCsMat.to_f32)")
         return NotImplemented
 
     __matmul__ = __mul__

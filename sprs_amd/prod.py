@@ -229,11 +229,13 @@ def csmat_mul_vec(mat, vec, out=None, stream=None):
 
 def csmat_mul_csmat(lhs, rhs):
     """csmat_mul_csmat (csmat.rs:1895-1949): storage dispatch around smmp::mul_csr_csr, done below the C ABI
-    (sprs_hip_csmat_mul_csmat); the result has the lhs' storage order."""
-    from .device import DeviceCsMat
+    (sprs_hip_csmat_mul_csmat / _f32); the result has the lhs' storage order and the operands' class.  TypeError when the
+    operands differ in precision."""
+    from .smmp import _same_precision
+    cls = _same_precision(lhs, rhs)
     h = C.c_void_p()
-    check(lib.sprs_hip_csmat_mul_csmat(lhs._h, rhs._h, C.byref(h)))
-    return DeviceCsMat(h.value)
+    check(getattr(lib, "sprs_hip_csmat_mul_csmat" + ("_f32" if cls._suffix == "f32" else ""))(lhs._h, rhs._h, C.byref(h)))
+    return cls(h.value)
 
 
 def csr_mul_csvec(mat, vec, stream=None):
