@@ -904,7 +904,8 @@ int32_t sprs_hip_triplets_to_cs(uint64_t rows, uint64_t cols, uint64_t n, const 
  * name = "spmv_band*":     the banded plan (hot columns from LDS): spmv_band 0 auto / 1 on / 2 off, spmv_band_hot (slices, default
  *                          128), spmv_band_tile (labels per slice: 16384 or 8192), spmv_band_split (row length from which a row
  *                          is cut into pieces, default 24), spmv_band_rounds, spmv_band_hot_run, spmv_band_cold_tiles,
- *                          spmv_band_overlap, spmv_band_split_permute, spmv_band_phases, spmv_band_hot_cut;
+ *                          spmv_band_overlap, spmv_band_split_permute, spmv_band_phases, spmv_band_hot_cut, spmv_band_pack (2: the hot
+ *                          slices keep 10 bytes per entry instead of the lossless 8.5-byte records);
  * name = "spgemm_ordered":  1 (default): SpGEMM adds the products of an entry in the reference's order (values bit-identical
  *                          to sprs', deterministic); 0: unordered atomic adds in the large-row kernel (same products, rounding-
  *                          level differences, not reproducible run to run; since round 4 no faster: the order costs nothing

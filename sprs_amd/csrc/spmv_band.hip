@@ -331,6 +331,112 @@ __global__ void bp_tile_rows_kernel(const TileRowJob *__restrict__ jobs) {
     jb.tile_row[c] = lo;
 }
 
+// ---- packed hot slices (spmv_band_kernels.hpp, "PACKED hot slices") ---------------------------------------------------
+struct PackJob {                 // one hot slice
+    uint64_t ent0, nnz;          // in the raw hot arrays
+    uint64_t rec0;               // its first record in the packed array; a raw slice: its first tile in the plan's raw arrays
+    const uint32_t *tile_row;    // ntiles + 1
+    TileWord *tile_word;         // ntiles + 1
+    uint32_t tile0;              // number of its first tile among all hot tiles
+    uint32_t ntiles, packed, pad;
+};
+constexpr uint32_t KEYS_BAD = 0x80000000u;     // bp_tile_keys_kernel: the tile's values use more than two keys
+
+__device__ __forceinline__ uint32_t pack_key(double v) { return (uint32_t)__double2hiint(v) >> 20; }
+
+// One wave per hot tile: the smallest key of its values, the smallest key different from it, and whether every value has one
+// of the two -> keys[tile] = key0 | key1 << 12 (| KEYS_BAD).  The padding behind a slice's last entry has no say.
+__global__ __launch_bounds__(256) void bp_tile_keys_kernel(const PackJob *__restrict__ jobs, const double *__restrict__ vals_hot,
+                                                           uint32_t *__restrict__ keys) {
+    const PackJob jb = jobs[blockIdx.y];
+    const uint32_t lane = threadIdx.x & (WAVE - 1);
+    const uint32_t c = blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE;
+    if (c >= jb.ntiles) return;                                          // wave-uniform
+    const uint64_t base = (uint64_t)c * WT;
+    const uint32_t cnt = jb.nnz - base < (uint64_t)WT ? (uint32_t)(jb.nnz - base) : (uint32_t)WT;
+    uint32_t k[EPL];
+#pragma unroll
+    for (int p = 0; p < WPASS; ++p) {
+        const dbl2 v = *(const dbl2 *)(vals_hot + jb.ent0 + base + p * (WAVE * 2) + lane * 2);
+        k[2 * p] = pack_key(v[0]);
+        k[2 * p + 1] = pack_key(v[1]);
+    }
+    auto wave_min = [&](uint32_t v) {
+        for (int d = 1; d < WAVE; d <<= 1) {
+            const uint32_t o = (uint32_t)__shfl_xor((int)v, d, WAVE);
+            v = o < v ? o : v;
+        }
+        return v;
+    };
+    constexpr uint32_t NONE = 0xFFFFu;
+    uint32_t a = NONE;
+#pragma unroll
+    for (int q = 0; q < EPL; ++q)
+        if (lane * EPL + q < cnt && k[q] < a) a = k[q];
+    const uint32_t key0 = wave_min(a);
+    uint32_t b = NONE;
+#pragma unroll
+    for (int q = 0; q < EPL; ++q)
+        if (lane * EPL + q < cnt && k[q] != key0 && k[q] < b) b = k[q];
+    uint32_t key1 = wave_min(b);
+    if (key1 == NONE) key1 = key0;
+    bool ok = true;
+#pragma unroll
+    for (int q = 0; q < EPL; ++q)
+        if (lane * EPL + q < cnt && k[q] != key0 && k[q] != key1) ok = false;
+    const bool all_ok = __ballot(!ok) == 0ull;
+    if (lane == 0) keys[jb.tile0 + c] = key0 | (key1 << 12) | (all_ok ? 0u : KEYS_BAD);
+}
+
+// the tile words of every hot slice: first row of the tile, and the keys of a packed slice's tile
+__global__ __launch_bounds__(256) void bp_tile_words_kernel(const PackJob *__restrict__ jobs, const uint32_t *__restrict__ keys) {
+    const PackJob jb = jobs[blockIdx.y];
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c > jb.ntiles) return;
+    jb.tile_word[c] = TileWord{jb.tile_row[c], jb.packed && c < jb.ntiles ? keys[jb.tile0 + c] & 0xFFFFFFu : 0u};
+}
+
+// One lane per (tile, lane of the hot kernel) of the packed slices: its eight raw entries -> its part of the tile's record.
+__global__ __launch_bounds__(256) void bp_pack_kernel(const PackJob *__restrict__ jobs, const double *__restrict__ vals_hot,
+                                                      const uint16_t *__restrict__ cid_hot, const uint32_t *__restrict__ keys,
+                                                      unsigned char *__restrict__ packed) {
+    const PackJob jb = jobs[blockIdx.y];
+    const uint32_t lane = threadIdx.x & (WAVE - 1);
+    const uint32_t c = blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE;
+    if (!jb.packed || c >= jb.ntiles) return;
+    const uint64_t base = (uint64_t)c * WT;
+    const uint32_t cnt = jb.nnz - base < (uint64_t)WT ? (uint32_t)(jb.nnz - base) : (uint32_t)WT;
+    const uint32_t key0 = keys[jb.tile0 + c] & 0xFFFu;
+    uint32_t lo[EPL], hi[EPL];
+#pragma unroll
+    for (int p = 0; p < WPASS; ++p) {
+        const dbl2 v = *(const dbl2 *)(vals_hot + jb.ent0 + base + p * (WAVE * 2) + lane * 2);
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            lo[2 * p + e] = (uint32_t)__double2loint(v[e]);
+            hi[2 * p + e] = (uint32_t)__double2hiint(v[e]);
+        }
+    }
+    u32x4 ids = *(const u32x4 *)(cid_hot + jb.ent0 + base + lane * EPL);
+    uint32_t m[5] = {0u, 0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int q = 0; q < EPL; ++q) {
+        const bool live = lane * EPL + q < cnt;                          // the padding: key0, zero mantissa, id 0 (as the raw arrays hold it)
+        if (live && (hi[q] >> 20) != key0) ids[q / 2] |= KEY_SEL << (16 * (q & 1));
+        const uint32_t f = live ? hi[q] & 0xFFFFFu : 0u;
+        if (!live) lo[q] = 0u;
+        const int bit = 20 * q, i = bit >> 5, s = bit & 31;
+        m[i] |= f << s;
+        if (s + 20 > 32) m[i + 1] |= f >> (32 - s);
+    }
+    unsigned char *rec = packed + (jb.rec0 + c) * (uint64_t)PK_TILE_BYTES;
+    *(u32x4 *)(rec + lane * 16) = u32x4{lo[0], lo[1], lo[2], lo[3]};
+    *(u32x4 *)(rec + WAVE * 16 + lane * 16) = u32x4{lo[4], lo[5], lo[6], lo[7]};
+    *(u32x4 *)(rec + PK_MH + lane * 16) = u32x4{m[0], m[1], m[2], m[3]};
+    *(uint32_t *)(rec + PK_MH4 + lane * 4) = m[4];
+    *(u32x4 *)(rec + PK_ID + lane * 16) = ids;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -368,8 +474,11 @@ struct BandPlan {
     uint32_t *inv_hot = nullptr;                   // inverse of the labelling for the labels of REFERENCED columns: inv_hot[l] = column
     uint32_t nref = 0;                             // referenced columns = labels in use ([nref, cols) are the columns nobody references)
     uint32_t hot_labels = 0;                       // nh << xt_log2, at most cols_pad
-    double *vals_hot = nullptr, *vals_cold = nullptr;
+    double *vals_hot = nullptr, *vals_cold = nullptr;  // vals_hot / cid_hot: the raw hot arrays; null when every hot slice is packed
     uint16_t *cid_hot = nullptr;
+    unsigned char *packed_hot = nullptr;           // the records of the packed hot slices
+    TileWord *hot_tw = nullptr;                    // tile words of the hot slices (both forms)
+    uint32_t hot_wgs_packed = 0;                   // the hot workgroups [0, hot_wgs_packed) walk packed slices, the rest raw ones
     uint32_t *cid_cold = nullptr;
     uint32_t *rowidx_all = nullptr, *tile_row_all = nullptr;
     Seg *segs = nullptr;                           // hot segments (workgroup by workgroup), then one segment per cold piece, the short piece
@@ -601,8 +710,12 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, OwnedBandPlan &out) 
 
     // ---- arrays of the plan ----------------------------------------------------------------------
     const uint64_t hot_entries = hot_tiles * WT;
-    SPRS_TRY_HIP(alloc_block(bp->blocks, bp->vals_hot, (hot_entries + WT) * 8));
-    SPRS_TRY_HIP(alloc_block(bp->blocks, bp->cid_hot, (hot_entries + WT) * 2));
+    // (the raw hot arrays join the plan's blocks at the end, unless every slice is packed)
+    DevBuf vals_hot_blk, cid_hot_blk;
+    SPRS_TRY_HIP(vals_hot_blk.alloc((hot_entries + WT) * 8));
+    SPRS_TRY_HIP(cid_hot_blk.alloc((hot_entries + WT) * 2));
+    bp->vals_hot = vals_hot_blk.as<double>();
+    bp->cid_hot = cid_hot_blk.as<uint16_t>();
     SPRS_TRY_HIP(hipMemsetAsync(bp->vals_hot, 0, (hot_entries + WT) * 8, stream));
     SPRS_TRY_HIP(hipMemsetAsync(bp->cid_hot, 0, (hot_entries + WT) * 2, stream));
     SPRS_TRY_HIP(alloc_block(bp->blocks, bp->vals_cold, (cold_ent + WT) * 8));
@@ -615,7 +728,7 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, OwnedBandPlan &out) 
     SPRS_TRY_HIP(ptr_all.alloc((ptr_off + n_short_rows + 2) * 4));
     SPRS_TRY_HIP(alloc_block(bp->blocks, bp->rowidx_all, (row_off + n_short_rows + 1) * 4));
     SPRS_TRY_HIP(alloc_block(bp->blocks, bp->tile_row_all, (tile_off + 1) * 4));
-    bp->bytes = (hot_entries + WT) * 10 + (cold_ent + WT) * 12 + (row_off + n_short_rows + tile_off) * 4 + cols * 4 + n_long * 4 +
+    bp->bytes = (cold_ent + WT) * 12 + (row_off + n_short_rows + tile_off) * 4 + cols * 4 + n_long * 4 +
                 ((uint64_t)bp->nref + 4) * 4;
     // short piece: its entries go straight into place (piece 0 of the cold arrays), its row lists are copied
     hipLaunchKernelGGL((bp_fill_short_kernel<IDX, PTR>), dim3((unsigned)((rows + 256) / 256)), dim3(256), 0, stream, ip, ix,
@@ -666,6 +779,52 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, OwnedBandPlan &out) 
     hipLaunchKernelGGL(bp_tile_rows_kernel, dim3((max_tiles + 256) / 256, NP + 1), dim3(256), 0, stream,
                        (const TileRowJob *)jobs_d.p);
     SPRS_TRY_HIP(hipGetLastError());
+
+    // ---- packed hot slices: which slices can be, and the tile words of all of them ------------------------------------------
+    // (option spmv_band_pack: 0 / 1 on, 2 off.  Big plans are bound by the stream of bytes; the small ones — instructions and latency,
+    // DESIGN 4.1 — measured no slower packed: R-MAT 1M 0.0668 against 0.0687 ms warm, 0.0749 against 0.0765 ms cold, profiles/r29a)
+    std::vector<PackJob> pjobs(nh);
+    DevBuf pjobs_d, keys_d;
+    uint64_t packed_tiles = 0, raw_tiles = 0;
+    uint32_t max_hot_tiles = 0;
+    if (hot_tiles) {
+        SPRS_TRY_HIP(alloc_block(bp->blocks, bp->hot_tw, (tile_row_off[nh] + 1) * sizeof(TileWord)));
+        for (uint32_t k = 0; k < nh; ++k) {
+            const BandPiece &d = bp->host_pieces[k];
+            pjobs[k] = PackJob{d.ent0, d.nnz, 0ull, bp->tile_row_all + tile_row_off[k], bp->hot_tw + tile_row_off[k], (uint32_t)(d.ent0 / WT), d.ntiles, 0u, 0u};
+            max_hot_tiles = std::max(max_hot_tiles, d.ntiles);
+        }
+        SPRS_TRY_HIP(pjobs_d.alloc(pjobs.size() * sizeof(PackJob)));
+        SPRS_TRY_HIP(keys_d.alloc((hot_tiles + 1) * 4));
+        const bool want_pack = o.spmv_band_pack != 2;
+        if (want_pack) {
+            SPRS_TRY_HIP(hipMemcpyAsync(pjobs_d.p, pjobs.data(), pjobs.size() * sizeof(PackJob), hipMemcpyHostToDevice, stream));
+            hipLaunchKernelGGL(bp_tile_keys_kernel, dim3((max_hot_tiles + 3) / 4, (uint32_t)nh), dim3(256), 0, stream, (const PackJob *)pjobs_d.p,
+                               (const double *)bp->vals_hot, (uint32_t *)keys_d.p);
+            SPRS_TRY_HIP(hipGetLastError());
+            std::vector<uint32_t> keys(hot_tiles);                     // the verdicts: the one read-back of the packing
+            SPRS_TRY_HIP(copy_to_host(keys.data(), keys_d.p, keys.size() * 4, stream));
+            for (uint32_t k = 0; k < nh; ++k) {
+                PackJob &jb = pjobs[k];
+                bool ok = jb.ntiles != 0;
+                for (uint32_t c = 0; ok && c < jb.ntiles; ++c) ok = !(keys[jb.tile0 + c] & KEYS_BAD);
+                if (!ok) continue;
+                jb.packed = 1u;
+                jb.rec0 = packed_tiles;
+                packed_tiles += jb.ntiles;
+            }
+        }
+        for (PackJob &jb : pjobs) {                                    // the raw slices close ranks in the arrays the plan keeps
+            if (jb.packed) continue;
+            jb.rec0 = raw_tiles;
+            raw_tiles += jb.ntiles;
+        }
+        SPRS_TRY_HIP(hipMemcpyAsync(pjobs_d.p, pjobs.data(), pjobs.size() * sizeof(PackJob), hipMemcpyHostToDevice, stream));
+        hipLaunchKernelGGL(bp_tile_words_kernel, dim3((max_hot_tiles + 256) / 256, (uint32_t)nh), dim3(256), 0, stream, (const PackJob *)pjobs_d.p,
+                           (const uint32_t *)keys_d.p);
+        SPRS_TRY_HIP(hipGetLastError());
+        bp->bytes += tile_row_off[nh] * sizeof(TileWord);
+    }
 
     // ---- who walks what: hot segments (equal shares of the hot tiles per workgroup), cold segments, launch groups ------------
     std::vector<Seg> segs;
@@ -763,14 +922,29 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, OwnedBandPlan &out) 
         for (uint32_t i = 0; i < nhs; ++i) {
             const Seg &sg = segs[i];
             const BandPiece &d = bp->host_pieces[sg.piece];
-            hs[i] = HotSeg{d.ent0, d.nnz, d.tile_row, bp->pair_off[sg.piece], d.x0, sg.tile0, sg.ntiles, sg.range0, sg.run, 0u, 0u, 0u};
+            const PackJob &jb = pjobs[sg.piece];
+            hs[i] = HotSeg{jb.rec0 * WT, d.nnz, jb.tile_word, bp->pair_off[sg.piece], d.x0, sg.tile0, sg.ntiles, sg.range0, sg.run, 0u, 0u, 0u};
         }
-        std::vector<HotSeg> wf(bp->hot_wgs);
+        // The packed slices and the raw ones are two launches of the hot kernel (two instantiations): the workgroups of the packed
+        // slices' segments come first in wg_first, then those of the raw slices'.  Segments and ranges are the same whatever is
+        // packed — they fix the order of the additions —, so a share that runs from a slice of one form into one of the other
+        // is walked by one workgroup of either launch (only in a plan that holds both forms).
+        std::vector<HotSeg> wf, wf_raw;
         for (uint32_t b = 0; b < bp->hot_wgs; ++b) {
-            wf[b] = hs[wg_seg[b]];
-            wf[b].pad0 = wg_seg[b];
-            wf[b].pad1 = wg_seg[b + 1];
+            for (uint32_t s = wg_seg[b]; s < wg_seg[b + 1];) {
+                const uint32_t form = pjobs[segs[s].piece].packed;
+                uint32_t e = s + 1;
+                while (e < wg_seg[b + 1] && pjobs[segs[e].piece].packed == form) ++e;
+                HotSeg first = hs[s];
+                first.pad0 = s;
+                first.pad1 = e;
+                (form ? wf : wf_raw).push_back(first);
+                s = e;
+            }
         }
+        bp->hot_wgs_packed = (uint32_t)wf.size();
+        wf.insert(wf.end(), wf_raw.begin(), wf_raw.end());
+        bp->hot_wgs = (uint32_t)wf.size();
         SPRS_TRY_HIP(alloc_block(bp->blocks, bp->wg_first, (wf.size() + 1) * sizeof(HotSeg)));
         SPRS_TRY_HIP(hipMemcpyAsync(bp->wg_first, wf.data(), wf.size() * sizeof(HotSeg), hipMemcpyHostToDevice, stream));
         SPRS_TRY_HIP(alloc_block(bp->blocks, bp->hsegs, (hs.size() + 1) * sizeof(HotSeg)));
@@ -847,7 +1021,37 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, OwnedBandPlan &out) 
         }
         bp->bytes += (uint64_t)counts[0] * sizeof(Spill);
     }
+    // ---- the records of the packed slices (after bp_spill_kernel: it reads the raw ids) ----------------------------------------
+    if (packed_tiles) {
+        SPRS_TRY_HIP(alloc_block(bp->blocks, bp->packed_hot, packed_tiles * PK_TILE_BYTES));
+        hipLaunchKernelGGL(bp_pack_kernel, dim3((max_hot_tiles + 3) / 4, (uint32_t)nh), dim3(256), 0, stream, (const PackJob *)pjobs_d.p,
+                           (const double *)bp->vals_hot, (const uint16_t *)bp->cid_hot, (const uint32_t *)keys_d.p, bp->packed_hot);
+        SPRS_TRY_HIP(hipGetLastError());
+        bp->bytes += packed_tiles * PK_TILE_BYTES;
+    }
     SPRS_TRY_HIP(hipStreamSynchronize(stream));   // plan complete, temporaries (and the host vectors above) may go
+    // the raw hot arrays: kept as they are when nothing was packed, gone when everything was; between the two the raw slices
+    // move into arrays of their own size (HotSeg::ent0 counts in those) and the packed slices' raw values are freed
+    if (!packed_tiles) {
+        bp->blocks.push_back(std::move(vals_hot_blk));
+        bp->blocks.push_back(std::move(cid_hot_blk));
+        bp->bytes += (hot_entries + WT) * 10;
+    } else if (raw_tiles) {
+        const double *v_all = bp->vals_hot;
+        const uint16_t *c_all = bp->cid_hot;
+        SPRS_TRY_HIP(alloc_block(bp->blocks, bp->vals_hot, (raw_tiles * WT + WT) * 8));
+        SPRS_TRY_HIP(alloc_block(bp->blocks, bp->cid_hot, (raw_tiles * WT + WT) * 2));
+        for (const PackJob &jb : pjobs) {
+            if (jb.packed || !jb.ntiles) continue;
+            SPRS_TRY_HIP(hipMemcpyAsync(bp->vals_hot + jb.rec0 * WT, v_all + jb.ent0, (uint64_t)jb.ntiles * WT * 8, hipMemcpyDeviceToDevice, stream));
+            SPRS_TRY_HIP(hipMemcpyAsync(bp->cid_hot + jb.rec0 * WT, c_all + jb.ent0, (uint64_t)jb.ntiles * WT * 2, hipMemcpyDeviceToDevice, stream));
+        }
+        SPRS_TRY_HIP(hipStreamSynchronize(stream));
+        bp->bytes += (raw_tiles * WT + WT) * 10;
+    } else {
+        bp->vals_hot = nullptr;
+        bp->cid_hot = nullptr;
+    }
     if (getenv("SPRS_HIP_DEBUG")) {
         uint64_t hot_nnz = 0, cold_nnz = 0, hot_pairs = 0, cold_pairs = 0;
         for (uint32_t k = 0; k < NP; ++k) {
@@ -941,8 +1145,10 @@ int32_t band_spmv(sprs_hip_csmat *a, BandPlan *bp, const double *x, double *y, b
             static std::unordered_map<int, bool> done;
             std::lock_guard<std::mutex> lock(mu);
             if (!done[a->device]) {
-                SPRS_TRY_HIP(hipFuncSetAttribute((const void *)band_hot_kernel<13>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hot_lds_bytes(13)));
-                SPRS_TRY_HIP(hipFuncSetAttribute((const void *)band_hot_kernel<14>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hot_lds_bytes(14)));
+                const void *k13[] = {(const void *)band_hot_kernel<13, 0>, (const void *)band_hot_kernel<13, 1>, (const void *)band_hot_kernel<13, 2>};
+                const void *k14[] = {(const void *)band_hot_kernel<14, 0>, (const void *)band_hot_kernel<14, 1>, (const void *)band_hot_kernel<14, 2>};
+                for (const void *k : k13) SPRS_TRY_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hot_lds_bytes(13)));
+                for (const void *k : k14) SPRS_TRY_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hot_lds_bytes(14)));
                 done[a->device] = true;
             }
         }
@@ -954,17 +1160,32 @@ int32_t band_spmv(sprs_hip_csmat *a, BandPlan *bp, const double *x, double *y, b
             prof = buf.as<unsigned long long>();
         }
         const uint32_t xcd_shares = options().spmv_band_xcd == 1 || (options().spmv_band_xcd == 0 && bp->small) ? 1u : 0u;
-        if (bp->xt_log2 == 13)
-            hipLaunchKernelGGL((band_hot_kernel<13>), dim3(bp->hot_wgs), dim3(HOT_THREADS), lds, stream, (const HotSeg *)bp->hsegs,
-                               (const HotSeg *)bp->wg_first,
-                               (const double *)bp->vals_hot, (const uint16_t *)bp->cid_hot, (const double *)sc->xp, sc->partial, sc->carry,
-                               (uint32_t)options().spmv_band_debug, prof, xcd_shares);
-        else
-            hipLaunchKernelGGL((band_hot_kernel<14>), dim3(bp->hot_wgs), dim3(HOT_THREADS), lds, stream, (const HotSeg *)bp->hsegs,
-                               (const HotSeg *)bp->wg_first,
-                               (const double *)bp->vals_hot, (const uint16_t *)bp->cid_hot, (const double *)sc->xp, sc->partial, sc->carry,
-                               (uint32_t)options().spmv_band_debug, prof, xcd_shares);
-        SPRS_TRY_HIP(hipGetLastError());
+        // the workgroups of the packed slices, then those of the raw ones (a plan usually has one of the two)
+        const uint32_t np = bp->hot_wgs_packed, nraw = bp->hot_wgs - np;
+        const HotSeg *wf = (const HotSeg *)bp->wg_first;
+        const uint32_t dbg = (uint32_t)options().spmv_band_debug;
+        if (np) {
+            // (a big plan's packed slices: two consecutive ranges per wave and turn, see band_hot_kernel)
+            auto launch_packed = [&](auto kernel) {
+                hipLaunchKernelGGL(kernel, dim3(np), dim3(HOT_THREADS), lds, stream, (const HotSeg *)bp->hsegs, wf, (const double *)bp->packed_hot,
+                                   (const uint16_t *)nullptr, (const double *)sc->xp, sc->partial, sc->carry, dbg, prof, xcd_shares);
+            };
+            if (bp->xt_log2 == 13 && bp->small) launch_packed(band_hot_kernel<13, 1>);
+            else if (bp->xt_log2 == 13) launch_packed(band_hot_kernel<13, 2>);
+            else if (bp->small) launch_packed(band_hot_kernel<14, 1>);
+            else launch_packed(band_hot_kernel<14, 2>);
+            SPRS_TRY_HIP(hipGetLastError());
+        }
+        if (nraw) {
+            unsigned long long *prof_raw = prof ? prof + 3ull * np : nullptr;
+            if (bp->xt_log2 == 13)
+                hipLaunchKernelGGL((band_hot_kernel<13, 0>), dim3(nraw), dim3(HOT_THREADS), lds, stream, (const HotSeg *)bp->hsegs, wf + np,
+                                   (const double *)bp->vals_hot, (const uint16_t *)bp->cid_hot, (const double *)sc->xp, sc->partial, sc->carry, dbg, prof_raw, xcd_shares);
+            else
+                hipLaunchKernelGGL((band_hot_kernel<14, 0>), dim3(nraw), dim3(HOT_THREADS), lds, stream, (const HotSeg *)bp->hsegs, wf + np,
+                                   (const double *)bp->vals_hot, (const uint16_t *)bp->cid_hot, (const double *)sc->xp, sc->partial, sc->carry, dbg, prof_raw, xcd_shares);
+            SPRS_TRY_HIP(hipGetLastError());
+        }
         if (DEVTOOLS && prof && getenv("SPRS_HIP_HOTPROF")) {      // (synchronous: a developer printout, not a timing run)
             std::vector<unsigned long long> t((size_t)bp->hot_wgs * 3);
             SPRS_TRY_HIP(copy_to_host(t.data(), prof, t.size() * 8, stream));

@@ -28,6 +28,7 @@ constexpr int HOT_THREADS = 1024;             // one workgroup per CU: 16 waves 
 constexpr int HOT_WAVES = HOT_THREADS / WAVE;
 constexpr int CNT = 256;                      // threads of a cold / short workgroup: 4 independent waves
 constexpr uint32_t ROW_START = 0x8000u;       // flag bit in a hot column id (14 bits of local column below it)
+constexpr uint32_t KEY_SEL = 0x4000u;         // packed hot slices: the entry's value takes the tile's key1 (clear: key0)
 constexpr uint32_t ROW_START32 = 0x80000000u; // flag bit in a cold label
 static_assert(WPASS == 4 && EPL == 8, "wave tile geometry");
 
@@ -56,12 +57,38 @@ struct Seg {
     uint32_t piece, tile0, ntiles, range0, run, pad0, pad1, pad2;
 };
 
+// PACKED hot slices.  A double is a 12-bit KEY (sign + exponent), the top 20 mantissa bits and the low 32 bits.  A wave tile
+// whose values use at most two keys is stored without them: bit 14 of an entry's id picks key0 or key1, and the tile's two
+// keys travel with its row word (TileWord) — 8.5 bytes per entry instead of 10, losslessly, whatever the bit patterns are.
+// One contiguous, 128-byte aligned RECORD of 4352 bytes per tile, transposed like the raw arrays so that every load of a lane
+// is coalesced and returns the lane's own eight entries:
+//   [   0, 2048)  low words:      entry 8 l + 4 p + e at dword 256 p + 4 l + e            (two 16-byte loads per lane)
+//   [2048, 3072)  dwords 0 .. 3 of the lane's 160-bit string of eight 20-bit fields (entry q at bits 20 q ..), 16 bytes per lane
+//   [3072, 3328)  dword 4 of that string, 4 bytes per lane
+//   [3328, 4352)  the ids, as in the raw array: entry 8 l + q at halfword 8 l + q           (one 16-byte load per lane)
+// A SLICE is packed when every one of its tiles can be; the others keep the raw arrays (separate launches of the two forms).
+constexpr uint32_t PK_TILE_BYTES = 4352, PK_MH = 2048, PK_MH4 = 3072, PK_ID = 3328;
+static_assert(PK_TILE_BYTES % 128 == 0 && PK_ID + WT * 2 == PK_TILE_BYTES, "packed record");
+
+// per hot tile (both forms): compact row of the first row that starts in the tile; packed slices: key0 | key1 << 12
+struct alignas(8) TileWord {
+    uint32_t row, keys;
+};
+static_assert(sizeof(TileWord) == 8, "the hot kernel loads a tile word as one 8-byte word");
+
+// the 20-bit field q of a lane's 160-bit string m[0 .. 4] (q is a compile-time constant after unrolling)
+__device__ __forceinline__ uint32_t pk_field(const uint32_t (&m)[5], int q) {
+    const int b = 20 * q, i = b >> 5, s = b & 31;
+    if (s + 20 <= 32) return (m[i] >> s) & 0xFFFFFu;
+    return ((m[i] >> s) | (m[i + 1] << (32 - s))) & 0xFFFFFu;
+}
+
 // What the hot kernel needs of a segment, in ONE 64-byte record (one scalar load): until round 6 a workgroup went
 // wg_seg -> segs[s] -> pieces[seg.piece] -> data, three dependent round trips in front of every x tile — nothing beside the
 // 2 180 tiles per CU of R-MAT 10M, a third of the time of a small plan whose workgroups hold 50 tiles in two or three segments.
 struct alignas(64) HotSeg {
-    uint64_t ent0, nnz;                 // of the slice: first entry in the hot arrays, entries
-    const uint32_t *tile_row;           // of the slice
+    uint64_t ent0, nnz;                 // of the slice: first entry in the hot arrays (packed: 512 x its first record), entries
+    const TileWord *tile_word;          // of the slice
     uint64_t out_off;                   // the slice's first partial sum in the scratch's array
     uint32_t x0, tile0, ntiles, range0; // first label of the slice; the segment's tiles; its first range
     uint32_t run, pad0, pad1, pad2;
@@ -264,13 +291,16 @@ __device__ __forceinline__ void band_cold_wave(const PieceView d, uint32_t r, ui
 // 8 fetched the first x tile: the short tile's chain of round trips, 13 us, then stood in front of every workgroup's first hot tile:
 // hot kernel 36.7 -> 45.7 us for a reduction alone of 12.4 instead of a 19.3 us tail, 0.0696 - 0.0702 against 0.0684 - 0.0689 ms on
 // R-MAT 1M, profiles/r15o.  Not kept.)
-template <int XT_LOG2>
+// PACK 0: raw slices.  PACK 1 / 2: packed slices — `vals` is the array of packed records (cid is not read), the values are rebuilt
+// in front of the products — walked PACK consecutive ranges per wave and turn.
+template <int XT_LOG2, int PACK>
 __global__ __launch_bounds__(HOT_THREADS) SPRS_HOT_WAVES_ATTR void band_hot_kernel(const HotSeg *__restrict__ hsegs,
                                                                const HotSeg *__restrict__ wg_first, const double *__restrict__ vals,
                                                                const uint16_t *__restrict__ cid, const double *__restrict__ xp,
                                                                double *__restrict__ partial, double *__restrict__ carry, uint32_t dbg,
                                                                unsigned long long *__restrict__ prof, uint32_t xcd_shares) {
     constexpr int XT = 1 << XT_LOG2;
+    constexpr bool PACKED = PACK != 0;
     // developer builds, option spmv_band_debug & 16 (env SPRS_HIP_HOTPROF): when does each workgroup start, see its first x tile,
     // and end (100 MHz wall clock) — is the hot kernel's time its work or its tail?
     if constexpr (DEVTOOLS) {
@@ -303,11 +333,11 @@ __global__ __launch_bounds__(HOT_THREADS) SPRS_HOT_WAVES_ATTR void band_hot_kern
         const HotSeg seg = nxt;
         if (s + 1 < s1) nxt = hsegs[s + 1];                              // (requested a whole segment before it is needed)
         struct {
-            const SPRS_GLOBAL_AS uint32_t *tile_row;
+            const SPRS_GLOBAL_AS uint64_t *tile_word;                    // TileWord as one 8-byte word: row | keys << 32
             SPRS_GLOBAL_AS double *out;
             uint64_t ent0, nnz;
             uint32_t x0;
-        } d{(const SPRS_GLOBAL_AS uint32_t *)seg.tile_row, (SPRS_GLOBAL_AS double *)(partial + seg.out_off), seg.ent0, seg.nnz, seg.x0};
+        } d{(const SPRS_GLOBAL_AS uint64_t *)seg.tile_word, (SPRS_GLOBAL_AS double *)(partial + seg.out_off), seg.ent0, seg.nnz, seg.x0};
         if (s != s0) __syncthreads();                                    // every wave is done with the previous x tile
         {   // x tile of the slice -> LDS (xp is padded to a whole number of tiles)
             const dbl2 *src = (const dbl2 *)(xp + d.x0);
@@ -321,15 +351,34 @@ __global__ __launch_bounds__(HOT_THREADS) SPRS_HOT_WAVES_ATTR void band_hot_kern
         const uint32_t run = seg.run, n = seg.ntiles;
         dbl2 av[WPASS];
         u32x4 cw = {0u, 0u, 0u, 0u};
-        uint32_t R0n = 0;
+        u32x4 plo[2], pmh;                                               // PACKED: low words, mantissa-high fields (dwords 0 .. 3, 4)
+        uint32_t pmh4 = 0;
+        uint32_t R0n = 0, Kn = 0;
         auto request = [&](uint32_t w) {
-            const uint64_t g = d.ent0 + (uint64_t)w * WT;
+            if constexpr (PACKED) {
+                const unsigned char *rec = (const unsigned char *)vals + (d.ent0 / WT + w) * (uint64_t)PK_TILE_BYTES;
 #pragma unroll
-            for (int p = 0; p < WPASS; ++p) av[p] = __builtin_nontemporal_load((const dbl2 *)(vals + g + p * (WAVE * 2) + lane * 2));
-            cw = __builtin_nontemporal_load((const u32x4 *)(cid + g + lane * EPL));
-            R0n = d.tile_row[w];
+                for (int p = 0; p < 2; ++p) plo[p] = __builtin_nontemporal_load((const u32x4 *)(rec + p * (WAVE * 16) + lane * 16));
+                pmh = __builtin_nontemporal_load((const u32x4 *)(rec + PK_MH + lane * 16));
+                pmh4 = __builtin_nontemporal_load((const uint32_t *)(rec + PK_MH4 + lane * 4));
+                cw = __builtin_nontemporal_load((const u32x4 *)(rec + PK_ID + lane * 16));
+                const uint64_t tw = d.tile_word[w];
+                R0n = (uint32_t)tw;
+                Kn = (uint32_t)(tw >> 32);
+            } else {
+                const uint64_t g = d.ent0 + (uint64_t)w * WT;
+#pragma unroll
+                for (int p = 0; p < WPASS; ++p) av[p] = __builtin_nontemporal_load((const dbl2 *)(vals + g + p * (WAVE * 2) + lane * 2));
+                cw = __builtin_nontemporal_load((const u32x4 *)(cid + g + lane * EPL));
+                R0n = (uint32_t)d.tile_word[w];
+            }
         };
-        uint32_t r = wave;                                               // current range
+        // Which wave walks which range is free (a range's sums do not depend on it).  Raw slices: r = wave, wave + 16, ...
+        // Packed slices of a big plan: G = 2 consecutive ranges per wave and turn, i.e. 8 records = 34 KiB in a row — with
+        // 4 (17 KiB) the packed kernel ran at 750 us in one SpMV and 925 us in the next beside the gather kernels, 901 us on
+        // average against 823 us raw, although ALONE it takes 569 against 641 us; with 8 in a row 804 us (profiles/r29a).
+        constexpr uint32_t G = PACKED ? (uint32_t)PACK : 1u;
+        uint32_t r = wave * G;                                           // current range
         uint32_t t = r * run;                                            // current tile, relative to the segment
         if (t < n) request(seg.tile0 + t);                               // the first tile is requested before the barrier
         __syncthreads();                                                 // xs complete
@@ -357,10 +406,23 @@ __global__ __launch_bounds__(HOT_THREADS) SPRS_HOT_WAVES_ATTR void band_hot_kern
                 fb |= ((c2 >> 15) & 1u) << (2 * p);
                 fb |= ((c2 >> 31) & 1u) << (2 * p + 1);
             }
+            if constexpr (PACKED) {
+                // the value of entry q: low word as stored; high word = the key that id bit 14 selects, over the 20-bit field
+                const uint32_t m[5] = {pmh[0], pmh[1], pmh[2], pmh[3], pmh4};
+                const uint32_t ks = (uint32_t)__builtin_amdgcn_readfirstlane((int)Kn);   // wave-uniform: the tile's word
+                const uint32_t k0 = ks << 20, k1 = (ks >> 12) << 20;
 #pragma unroll
-            for (int p = 0; p < WPASS; ++p) {
-                pr[2 * p] = av[p][0] * xv[2 * p];
-                pr[2 * p + 1] = av[p][1] * xv[2 * p + 1];
+                for (int q = 0; q < EPL; ++q) {
+                    const uint32_t sel = cw[q / 2] & (KEY_SEL << (16 * (q & 1)));
+                    const uint32_t hi = pk_field(m, q) | (sel ? k1 : k0);
+                    pr[q] = __hiloint2double((int)hi, (int)plo[q / 4][q % 4]) * xv[q];
+                }
+            } else {
+#pragma unroll
+                for (int p = 0; p < WPASS; ++p) {
+                    pr[2 * p] = av[p][0] * xv[2 * p];
+                    pr[2 * p + 1] = av[p][1] * xv[2 * p + 1];
+                }
             }
             if (cnt < (uint32_t)WT) {                                    // last tile of a slice (wave-uniform): the padding (value 0, id 0) must not
 #pragma unroll                                                           // turn an infinite x[first label] into a NaN
@@ -378,7 +440,8 @@ __global__ __launch_bounds__(HOT_THREADS) SPRS_HOT_WAVES_ATTR void band_hot_kern
             // the tile after this one: the next of the range, or the first of the wave's next range
             const uint32_t rend = (r + 1) * run < n ? (r + 1) * run : n;
             const bool range_ends = t + 1 >= rend;
-            const uint32_t tn = range_ends ? (r + HOT_WAVES) * run : t + 1;
+            const uint32_t rn = G > 1u && (r % G) + 1u < G ? r + 1u : r + 1u + (uint32_t)(HOT_WAVES - 1) * G;   // the wave's next range
+            const uint32_t tn = range_ends ? rn * run : t + 1;
             SPRS_GLOBAL_AS double *cslot = (SPRS_GLOBAL_AS double *)carry + seg.range0 + r;
             auto out = [&](uint32_t row, double v) {
                 if (DEVTOOLS && (dbg & 1u)) return;                      // no stores of the row sums
@@ -404,7 +467,7 @@ __global__ __launch_bounds__(HOT_THREADS) SPRS_HOT_WAVES_ATTR void band_hot_kern
                 }
                 open = 0.0;
                 mine = false;
-                r += HOT_WAVES;
+                r = rn;
             }
             t = tn;
         }
