@@ -902,7 +902,7 @@ int32_t sprs_hip_triplets_to_cs(uint64_t rows, uint64_t cols, uint64_t n, const 
  * name = "spmv_sort_tiles": 1: tiles of the sliced plan's copies are stored sorted by column (default 0: measured slower);
  * name = "spmv_tile":      nnz per workgroup tile: 0 auto (default), 2048 or 4096;
  * name = "spmv_band*":     the banded plan (hot columns from LDS): spmv_band 0 auto / 1 on / 2 off, spmv_band_hot (slices, default
- *                          128), spmv_band_tile (labels per slice: 16384 or 8192), spmv_band_split (row length from which a row
+ *                          128), spmv_band_tile (labels per slice: 16384 or 8192; f32 handles read spmv_f32_band_tile: 8192, 16384 or 32768), spmv_band_split (row length from which a row
  *                          is cut into pieces, default 24), spmv_band_rounds, spmv_band_hot_run, spmv_band_cold_tiles,
  *                          spmv_band_overlap, spmv_band_split_permute, spmv_band_phases, spmv_band_hot_cut, spmv_band_pack (2: the hot
  *                          slices keep 10 bytes per entry instead of the lossless 8.5-byte records);
@@ -958,11 +958,18 @@ int32_t sprs_hip_csmat_f32_download(const sprs_hip_csmat_f32 *m, void *indptr, v
 int32_t sprs_hip_csmat_f32_transpose_view(const sprs_hip_csmat_f32 *m, sprs_hip_csmat_f32 **out);
 /* drops the SpMV plan and the cached CSR form of a CSC handle after the wrapped arrays were modified in place */
 int32_t sprs_hip_csmat_f32_refresh(sprs_hip_csmat_f32 *m);
-/* Builds the SpMV plan now: the tile index over the handle's arrays and the carry array of `stream` (a CSC handle: of its CSR
- * form, made and cached here).  An f32 SpMV has ONE plan (no re-laid-out copies), so preparing changes no bits; it is what
- * lets an SpMV run on a stream that is being captured into a hipGraph: there the plan and THAT stream's carry array must
- * exist already (the build allocates and synchronises), else SPRS_HIP_INVALID_ARG. */
+/* Builds the SpMV plan now, with the per-stream arrays of `stream` (a CSC handle: of its CSR form, made and cached here): the
+ * banded plan where it applies (see sprs_hip_spmv_f32), else the tile index over the handle's arrays and `stream`'s carry array.
+ * An unprepared handle takes its FIRST multiply on the tile plan and builds the banded plan at the second, so on a matrix that
+ * takes the banded plan call 1 and call 2 may differ in bits (within the f32 bound below), as for the f64 handle; a prepared
+ * handle multiplies on one plan from the first call on.  On a matrix that stays on the tile plan preparing changes no bits.
+ * Preparing is also what lets an SpMV run on a stream that is being captured into a hipGraph: there the plan and THAT
+ * stream's arrays must exist already (the build allocates and synchronises), else SPRS_HIP_INVALID_ARG. */
 int32_t sprs_hip_csmat_f32_prepare(sprs_hip_csmat_f32 *m, void *stream);
+/* Which plan the handle's SpMV runs on (a CSC handle: its cached CSR form's): *kind = 0 none yet (no multiply, no prepare),
+ * 1 the nnz-tile index, 3 the banded copy (hot columns of x from LDS); there is no kind 2 (XCD-sliced) for f32.  *plan_bytes:
+ * device memory the plan holds, without per-stream scratch.  Either pointer may be NULL. */
+int32_t sprs_hip_csmat_f32_spmv_plan_info(const sprs_hip_csmat_f32 *m, int32_t *kind, uint64_t *plan_bytes);
 int32_t sprs_hip_csmat_f32_free(sprs_hip_csmat_f32 *m);
 /* Twin of to_other_storage (csmat.rs:1405-1426) for N = f32: every output row strictly increasing, the values travel with
  * their index (bit for bit).  Complete at return. */
@@ -975,12 +982,21 @@ int32_t sprs_hip_csmat_f32_to_f64(const sprs_hip_csmat_f32 *m, sprs_hip_csmat **
 
 /* Twin of prod::mul_acc_mat_vec_csr (prod.rs:103-127; accumulate != 0) and of `&A * &x` on a zeroed result (accumulate == 0)
  * for N = f32.  x_dev / y_dev: x_len / y_len floats.  SPRS_HIP_DIM_MISMATCH unless A.cols == x_len && A.rows == y_len, then
- * SPRS_HIP_STORAGE_MISMATCH unless A is CSR.  Asynchronous on `stream`.  Every product is rounded to f32, then added in f32.
- * A row (or the part of a row inside one 2048- / 4096-entry tile of the nnz axis) of fewer than 64 entries is summed left to
- * right from 0.0f — the reference's chain, bit for bit, when the row lies inside one tile; a longer one by a wave (tree); a
- * row that spans tiles adds its parts in tile order.  Deterministic run to run.  Empty rows: the accumulate form leaves
- * y[r] untouched, the other writes +0.0f.  Runs on the nnz-tile plan only (option spmv_tile applies; the banded and
- * XCD-sliced plans of the f64 SpMV do not exist for f32). */
+ * SPRS_HIP_STORAGE_MISMATCH unless A is CSR.  Asynchronous on `stream`.  Every product is rounded to f32, then added in f32;
+ * no float atomics: deterministic run to run on either plan.  Empty rows: the accumulate form leaves y[r] untouched, the other
+ * writes +0.0f.
+ * TILE plan (option spmv_tile): a row (or the part of a row inside one 2048- / 4096-entry tile of the nnz axis) of fewer than 64
+ * entries is summed left to right from 0.0f — the reference's chain, bit for bit, when the row lies inside one tile; a longer
+ * one by a wave (tree); a row that spans tiles adds its parts in tile order.  Only SHORT ROWS ON THE TILE PLAN keep the reference
+ * chain's bits.
+ * BANDED plan (the f64 SpMV's, with float values, x, partial sums and carries; hot slices of 8192, 16384 or 32768 labels: option
+ * spmv_f32_band_tile; the other spmv_band* options apply as for f64, spmv_band_pack is ignored): the sums of a row are formed
+ * in the plan's fixed order — entry order in a lane, lanes, tiles, ranges, pieces — and agree with the chain to the forward
+ * bound gamma_m * sum |a x| of m - 1 f32 additions, not bit for bit.  Taken when spmv_band = 1, or under spmv_band = 0 from the
+ * handle's second multiply (or sprs_hip_csmat_f32_prepare) on, for matrices with cols * 4 >= 4 MiB, nnz >= 2^22 and at least half
+ * the entries in long rows; dropped silently under auto when the memory for it is not there.  spmv_band = 2: tile plan only.
+ * So call 1 and call 2 of an unprepared handle may differ in bits on a matrix that takes the banded plan, as for f64.
+ * There is no XCD-sliced plan for f32. */
 int32_t sprs_hip_spmv_f32(const sprs_hip_csmat_f32 *a, const float *x_dev, uint64_t x_len,
                           float *y_dev, uint64_t y_len, int32_t accumulate, void *stream);
 /* the CSC accumulate form (prod.rs:74-99) and the either-storage operator `&A * &x`: a CSC handle multiplies through its CSR

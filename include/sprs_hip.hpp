@@ -1168,6 +1168,13 @@ public:
     const sprs_hip_csmat_f32 *handle() const { return h_; }
     void prepare(void *stream = nullptr) { check(sprs_hip_csmat_f32_prepare(h_, stream)); }
     void refresh() { check(sprs_hip_csmat_f32_refresh(h_)); }
+    // (kind, plan bytes): 0 none yet, 1 nnz tiles, 3 banded copy
+    std::pair<int32_t, uint64_t> spmv_plan_info() const {
+        int32_t kind = 0;
+        uint64_t bytes = 0;
+        check(sprs_hip_csmat_f32_spmv_plan_info(h_, &kind, &bytes));
+        return {kind, bytes};
+    }
     DeviceCsMatF32 transpose_view() const {          // shares this matrix's buffers: must not outlive it
         sprs_hip_csmat_f32 *t = nullptr;
         check(sprs_hip_csmat_f32_transpose_view(h_, &t));

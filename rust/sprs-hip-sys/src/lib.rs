@@ -392,6 +392,7 @@ extern "C" {
     pub fn sprs_hip_csmat_f32_transpose_view(m: *const sprs_hip_csmat_f32, out: *mut *mut sprs_hip_csmat_f32) -> i32;
     pub fn sprs_hip_csmat_f32_refresh(m: *mut sprs_hip_csmat_f32) -> i32;
     pub fn sprs_hip_csmat_f32_prepare(m: *mut sprs_hip_csmat_f32, stream: *mut c_void) -> i32;
+    pub fn sprs_hip_csmat_f32_spmv_plan_info(m: *const sprs_hip_csmat_f32, kind: *mut i32, plan_bytes: *mut u64) -> i32;
     pub fn sprs_hip_csmat_f32_free(m: *mut sprs_hip_csmat_f32) -> i32;
     pub fn sprs_hip_csmat_f32_to_other_storage(m: *const sprs_hip_csmat_f32, out: *mut *mut sprs_hip_csmat_f32) -> i32;
     pub fn sprs_hip_csmat_f32_from_f64(m: *const sprs_hip_csmat, out: *mut *mut sprs_hip_csmat_f32, stream: *mut c_void) -> i32;

@@ -1644,6 +1644,12 @@ pub mod single {
         pub fn refresh(&mut self) {
             unsafe { check(sys::sprs_hip_csmat_f32_refresh(self.h)) };
         }
+        /// (kind, plan bytes): 0 none yet, 1 nnz tiles, 3 banded copy
+        pub fn spmv_plan_info(&self) -> (i32, u64) {
+            let (mut kind, mut bytes) = (0i32, 0u64);
+            unsafe { check(sys::sprs_hip_csmat_f32_spmv_plan_info(self.h, &mut kind, &mut bytes)) };
+            (kind, bytes)
+        }
         /// `&A * &x` for either storage
         pub fn mul_vec(&self, x: &DeviceVecF32) -> DeviceVecF32 {
             let y = DeviceVecF32::zeros(self.rows());

@@ -176,6 +176,7 @@ SIGNATURES = {
     "sprs_hip_csmat_f32_transpose_view": (i32, [vp, P(vp)]),
     "sprs_hip_csmat_f32_refresh": (i32, [vp]),
     "sprs_hip_csmat_f32_prepare": (i32, [vp, vp]),
+    "sprs_hip_csmat_f32_spmv_plan_info": (i32, [vp, P(i32), P(u64)]),
     "sprs_hip_csmat_f32_free": (i32, [vp]),
     "sprs_hip_csmat_f32_to_other_storage": (i32, [vp, P(vp)]),
     "sprs_hip_csmat_f32_from_f64": (i32, [vp, P(vp), vp]),

@@ -157,9 +157,9 @@ using Value = typename H::value_type;
 template <typename H>
 constexpr bool IS_F32 = std::is_same<H, sprs_hip_csmat_f32>::value;
 
-// the f64 handle counts its multiplies (the copy plans are built at the second one); the f32 handle has no such policy
-static void copy_spmv_calls(sprs_hip_csmat *to, const sprs_hip_csmat *from) { to->spmv_calls = from->spmv_calls; }
-static void copy_spmv_calls(sprs_hip_csmat_f32 *, const sprs_hip_csmat_f32 *) {}
+// a handle counts its multiplies: the copy plans (banded, XCD-sliced) are built at the second one
+template <typename H>
+static void copy_spmv_calls(H *to, const H *from) { to->spmv_calls = from->spmv_calls; }
 
 // CsMat::new / new_csc on host arrays (the checks of the upload entries that follow their argument checks)
 template <typename H>
@@ -1131,6 +1131,8 @@ int32_t sprs_hip_set_option(const char *name, int64_t value) {
     // the few options whose legal values are not a range
     if (!strcmp(name, "spmv_tile") && value != 0 && value != 2048 && value != 4096) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "spmv_tile must be 0 (auto), 2048 or 4096");
     if (!strcmp(name, "spmv_band_tile") && value != 0 && value != 8192 && value != 16384) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "spmv_band_tile must be 0 (default), 8192 or 16384");
+    if (!strcmp(name, "spmv_f32_band_tile") && value != 0 && value != 8192 && value != 16384 && value != 32768)
+        SPRS_FAIL(SPRS_HIP_INVALID_ARG, "spmv_f32_band_tile must be 0 (default), 8192, 16384 or 32768");
     if (!strcmp(name, "spgemm_tokens") && value == 3) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "spgemm_tokens must be 1, 2 or 4");
     if (!strcmp(name, "spmv_band_split") && value == 1) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "spmv_band_split must be 0 (default) or >= 2");
     options().*(d->field) = value;
@@ -2344,6 +2346,25 @@ int32_t sprs_hip_csmat_f32_refresh(sprs_hip_csmat_f32 *m) {
 
 int32_t sprs_hip_csmat_f32_prepare(sprs_hip_csmat_f32 *m, void *stream) {
     return entry_prepare(m, stream);
+}
+
+int32_t sprs_hip_csmat_f32_spmv_plan_info(const sprs_hip_csmat_f32 *m, int32_t *kind, uint64_t *plan_bytes) {
+    clear_error();
+    if (!m) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    auto *mm = const_cast<sprs_hip_csmat_f32 *>(m);
+    std::lock_guard<std::recursive_mutex> lock(mm->mu);
+    // a CSC handle multiplies through its cached CSR form: the plan lives there
+    const sprs_hip_csmat_f32 *csr = m->storage == SPRS_HIP_CSC && m->as_other ? m->as_other : m;
+    const SpmvPlanF32 &pl = csr->plan;
+    int32_t k = 0;
+    uint64_t bytes = 0;
+    if (pl.built) {
+        k = pl.band ? 3 : 1;                   // (no XCD-sliced plan, kind 2, for f32)
+        bytes = pl.band ? band_plan_bytes(pl.band.get()) : (pl.ntiles + 1) * 8;
+    }
+    if (kind) *kind = k;
+    if (plan_bytes) *plan_bytes = bytes;
+    return SPRS_HIP_OK;
 }
 
 int32_t sprs_hip_csmat_f32_free(sprs_hip_csmat_f32 *m) {

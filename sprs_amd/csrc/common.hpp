@@ -64,6 +64,7 @@ constexpr bool DEVTOOLS = false;
     X(spmv_band, 0, 0, 2, 0)            /* banded plan (hot columns from LDS, spmv_band.hip): 0 auto (on), 1 on, 2 off */          \
     X(spmv_band_hot, 0, 0, 384, 0)      /* hot slices (0 = default 128) */                                                        \
     X(spmv_band_tile, 0, 0, 16384, 0)   /* labels per hot slice = doubles of the x tile in LDS: 8192 or 16384 (0 = default 16384) */ \
+    X(spmv_f32_band_tile, 0, 0, 32768, 0) /* f32 handles read this one instead: floats of the x tile in LDS, 8192, 16384 or 32768 (0 = default 16384) */ \
     X(spmv_band_phases, 0, 0, 8, 0)     /* label ranges of the cold rest (0 = default 1), 8 hash pieces each */                   \
     X(spmv_band_split, 0, 0, INT64_MAX, 0) /* rows with at least this many entries are cut into pieces (0 = default 24) */        \
     X(spmv_band_rounds, 0, 0, 64, 0)    /* workgroups of the hot kernel per CU, one after the other (0 = default 2) */ \
@@ -437,11 +438,14 @@ struct sprs_hip_csmat : sprs_hip::CsmatCore<double, sprs_hip_csmat> {
 
 // ---- single precision (spmv_f32.hpp) ----------------------------------------------------------------
 namespace sprs_hip {
-// The f32 SpMV runs on the plain nnz-tile plan only: the tile index over the handle's own arrays and one carry array per stream.
+// The f32 SpMV runs on the banded plan (spmv_band.hip, floats throughout) or on the plain nnz-tile plan: the tile index over the
+// handle's own arrays and one carry array per stream.
 struct SpmvPlanF32 {
     bool built = false;
+    bool light = false;                // built as the tile index although the banded plan would apply (first multiply of the handle): rebuilt at the next one
+    OwnedBandPlan band;                // banded plan: when set, nothing below is used
+    uint64_t opt_sig = 0;              // hash of the option values the plan was built with (f32_plan_signature, spmv_f32.hpp)
     uint32_t tile = 0;                 // nnz per tile: 2048 or 4096
-    int64_t opt_tile = 0;              // value of option spmv_tile the plan was built with
     uint64_t ntiles = 0;
     uint64_t *tile_row = nullptr;      // device, ntiles + 1: first row starting at/after tile c
     std::vector<DevBuf> blocks;        // the block behind tile_row
@@ -452,6 +456,7 @@ struct SpmvPlanF32 {
 // Device twin of CsMatBase for N = f32.  A type of its own, not a flag of sprs_hip_csmat: no entry that reads `double *data`
 // can be handed one (include/sprs_hip.h).  Index arrays are 4 or 8 bytes wide, on the host as on the device.
 struct sprs_hip_csmat_f32 : sprs_hip::CsmatCore<float, sprs_hip_csmat_f32> {
+    uint64_t spmv_calls = 0;   // multiplies so far, as in sprs_hip_csmat: the banded plan is built at the SECOND one (or by sprs_hip_csmat_f32_prepare)
     sprs_hip::SpmvPlanF32 plan;
     ~sprs_hip_csmat_f32();     // handle.hpp
 };
@@ -509,6 +514,9 @@ using OwnedCsmatF32 = Owned<sprs_hip_csmat_f32>;
 // spmv_band.hip
 int32_t band_build(sprs_hip_csmat *a, hipStream_t stream, OwnedBandPlan &out);   // out stays empty when the plan does not apply
 int32_t band_spmv(sprs_hip_csmat *a, BandPlan *bp, const double *x, double *y, bool accumulate, hipStream_t stream);
+int32_t band_build(sprs_hip_csmat_f32 *a, hipStream_t stream, OwnedBandPlan &out);   // the same plan with float values, x, partial sums and carries
+int32_t band_spmv(sprs_hip_csmat_f32 *a, BandPlan *bp, const float *x, float *y, bool accumulate, hipStream_t stream);
+int32_t band_prepare_stream(sprs_hip_csmat_f32 *a, BandPlan *bp, hipStream_t stream);   // makes `stream`'s scratch now (a capturing stream cannot)
 uint64_t band_plan_bytes(const BandPlan *bp);
 // spmv.hip
 int32_t spmv_prepare(sprs_hip_csmat *a, hipStream_t stream);   // builds the full SpMV plan now (sprs_hip_csmat_prepare)

@@ -289,7 +289,7 @@ void invalidate_caches(sprs_hip_csmat_f32 *m) {
 }  // namespace sprs_hip
 
 sprs_hip_csmat_f32::~sprs_hip_csmat_f32() {
-    // as for the f64 handle: a kernel in flight may still read the tile index, a carry array or the CSR copy
+    // as for the f64 handle: a kernel in flight (on the banded plan's second stream too) may still read the plan, a carry array or the CSR copy
     if (t_view || as_other || plan.built || mm.built) (void)hipDeviceSynchronize();
     sprs_hip::invalidate_caches(this);
 }

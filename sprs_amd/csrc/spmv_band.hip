@@ -24,6 +24,9 @@
 //   list; band_reduce_kernel adds the partials of a long row in piece order, finding them through
 //   per-(64 rows, piece) presence masks and base offsets.  No float atomics: bit-reproducible run to run.
 // The kernels and the wave-tile layout: spmv_band_kernels.hpp.
+// f32 HANDLES take the same plan with float values, x, partial sums and carries (BandPlan::vbytes = 4): a raw hot entry is 4 + 2
+// bytes, the x tile holds up to 32768 labels (option spmv_f32_band_tile), no slice is packed.  Build and launch code are templates
+// on the handle type; what does not touch a value is shared as it is.
 #include "spmv_band_kernels.hpp"
 
 #include <algorithm>
@@ -123,13 +126,13 @@ __device__ __forceinline__ uint64_t long_row_number(uint64_t j, uint64_t n_long)
 
 // mode 0: the row lists (s_rowidx, long_rows); mode 1: the entries in the wave-tile layout of band_cold_kernel and the
 // compact rows' positions (s_ptr), both in the layout `sb` describes
-template <typename IDX, typename PTR>
+template <typename IDX, typename PTR, typename T>
 __global__ void bp_fill_short_kernel(const PTR *__restrict__ indptr, const IDX *__restrict__ indices,
-                                     const double *__restrict__ data, uint64_t rows,
+                                     const T *__restrict__ data, uint64_t rows,
                                      const uint64_t *__restrict__ short_pos, const uint64_t *__restrict__ short_ptr,
                                      const uint64_t *__restrict__ long_pos, const uint32_t *__restrict__ perm,
                                      uint32_t *__restrict__ s_rowidx, uint32_t *__restrict__ s_ptr,
-                                     uint32_t *__restrict__ s_cid, double *__restrict__ s_val,
+                                     uint32_t *__restrict__ s_cid, T *__restrict__ s_val,
                                      uint32_t *__restrict__ long_rows, uint64_t split, int mode, ShortBuckets sb, uint64_t padded_total,
                                      uint64_t n_long) {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -157,7 +160,8 @@ __global__ void bp_fill_short_kernel(const PTR *__restrict__ indptr, const IDX *
         const uint32_t ll = t / EPL, q = t % EPL;
         const uint32_t label = perm[indices[p]];
         s_cid[tile * WT + (q / 4) * (WAVE * 4) + ll * 4 + (q & 3u)] = label | (p == s ? ROW_START32 : 0u);
-        s_val[tile * WT + (q / 2) * (WAVE * 2) + ll * 2 + (q & 1u)] = data[p];
+        if constexpr (sizeof(T) == 8) s_val[tile * WT + (q / 2) * (WAVE * 2) + ll * 2 + (q & 1u)] = data[p];
+        else s_val[band_val_at<T>(tile * WT, ll, q)] = data[p];
     }
 }
 
@@ -204,15 +208,15 @@ struct PieceBuild {          // host-computed placement of a piece, read by the 
 };
 
 // stable partition of every long row into its pieces (the entries keep their order inside the row)
-template <typename IDX, typename PTR>
+template <typename IDX, typename PTR, typename T>
 __global__ __launch_bounds__(256) void bp_scatter_kernel(const PTR *__restrict__ indptr, const IDX *__restrict__ indices,
-                                                         const double *__restrict__ data,
+                                                         const T *__restrict__ data,
                                                          const uint32_t *__restrict__ long_rows, uint64_t n_long,
                                                          const uint32_t *__restrict__ perm, SliceMap map, uint32_t npieces,
                                                          const uint64_t *__restrict__ pos,
                                                          const PieceBuild *__restrict__ pb,
-                                                         double *__restrict__ vals_hot, uint16_t *__restrict__ cid_hot,
-                                                         double *__restrict__ vals_cold, uint32_t *__restrict__ cid_cold) {
+                                                         T *__restrict__ vals_hot, uint16_t *__restrict__ cid_hot,
+                                                         T *__restrict__ vals_cold, uint32_t *__restrict__ cid_cold) {
     __shared__ uint32_t fill[4][MAX_PIECES];       // entries of the row already placed, per piece
     const uint32_t lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
     const unsigned long long below = (1ull << lane) - 1ull;
@@ -226,7 +230,7 @@ __global__ __launch_bounds__(256) void bp_scatter_kernel(const PTR *__restrict__
             const uint64_t p = p0 + lane;
             const bool valid = p < e;
             const uint32_t label = valid ? perm[indices[p]] : 0u;
-            const double v = valid ? data[p] : 0.0;
+            const T v = valid ? data[p] : (T)0.0;
             const uint32_t k = valid ? piece_of_label(map, label) : 0xFFFFFFFFu;
             // rank of the entry among the lanes of this batch that go to the same piece (lane order = row order)
             uint32_t rank = 0, group = 0;
@@ -250,16 +254,21 @@ __global__ __launch_bounds__(256) void bp_scatter_kernel(const PTR *__restrict__
                 const PieceBuild b = pb[k];
                 const uint64_t e_rel = pos[(uint64_t)k * n_long + j] - b.start + before + rank;   // entry number inside the piece
                 if (b.hot) {
-                    const uint64_t tile = e_rel / WT;              // wave tile; entry i = 8 l + 2 p + e of it belongs to lane l
+                    const uint64_t tile = e_rel / WT;              // wave tile; entry i = 8 l + q of it belongs to lane l (band_val_at)
                     const uint32_t i = (uint32_t)(e_rel % WT);
-                    const uint32_t ll = i / EPL, pp = (i % EPL) / 2, ee = i & 1u;
-                    vals_hot[b.ent0 + tile * WT + pp * (WAVE * 2) + ll * 2 + ee] = v;
+                    if constexpr (sizeof(T) == 8) {
+                        const uint32_t ll = i / EPL, pp = (i % EPL) / 2, ee = i & 1u;
+                        vals_hot[b.ent0 + tile * WT + pp * (WAVE * 2) + ll * 2 + ee] = v;
+                    } else {
+                        vals_hot[band_val_at<T>(b.ent0 + tile * WT, i / EPL, i % EPL)] = v;
+                    }
                     cid_hot[b.ent0 + e_rel] = (uint16_t)((label - b.x0) | (before + rank == 0 ? ROW_START : 0u));
                 } else {
                     const uint64_t tile = e_rel / WT;
                     const uint32_t i = (uint32_t)(e_rel % WT);
                     const uint32_t ll = i / EPL, q = i % EPL;
-                    vals_cold[b.ent0 + tile * WT + (q / 2) * (WAVE * 2) + ll * 2 + (q & 1u)] = v;
+                    if constexpr (sizeof(T) == 8) vals_cold[b.ent0 + tile * WT + (q / 2) * (WAVE * 2) + ll * 2 + (q & 1u)] = v;
+                    else vals_cold[band_val_at<T>(b.ent0 + tile * WT, ll, q)] = v;
                     cid_cold[b.ent0 + tile * WT + (q / 4) * (WAVE * 4) + ll * 4 + (q & 3u)] =
                         label | (before + rank == 0 ? ROW_START32 : 0u);
                 }
@@ -443,7 +452,7 @@ __global__ __launch_bounds__(256) void bp_pack_kernel(const PackJob *__restrict_
 // host side
 // ---------------------------------------------------------------------------------------------
 struct BandScratch {        // per stream; move-only: it owns its blocks, its stream and its events
-    double *partial = nullptr, *carry = nullptr, *xp = nullptr;
+    void *partial = nullptr, *carry = nullptr, *xp = nullptr;   // arrays of the plan's scalar (BandPlan::vbytes)
     BandPiece *pieces = nullptr;
     std::vector<DevBuf> blocks;                    // the blocks behind the arrays above
     // the gather-bound kernels (cold pieces, short rows: L2 -> L1 fills) run beside the HBM-bound hot kernel on a second stream
@@ -467,14 +476,15 @@ struct BandScratch {        // per stream; move-only: it owns its blocks, its st
 
 struct BandPlan {
     uint32_t nh = 0, phases = 1, npieces = 0;      // npieces = nh + 8 phases (the short piece comes after them)
-    uint32_t xt_log2 = 14;                         // labels per hot slice = doubles of the x tile in LDS
+    uint32_t xt_log2 = 14;                         // labels per hot slice = values of the x tile in LDS
+    uint32_t vbytes = 8;                           // the plan's scalar: 8 = double, 4 = float (values, xp, partial sums, carries)
     uint32_t n_long = 0, n_short_rows = 0;
     uint64_t cols = 0, cols_pad = 0;
     uint32_t *perm = nullptr, *long_rows = nullptr;
     uint32_t *inv_hot = nullptr;                   // inverse of the labelling for the labels of REFERENCED columns: inv_hot[l] = column
     uint32_t nref = 0;                             // referenced columns = labels in use ([nref, cols) are the columns nobody references)
     uint32_t hot_labels = 0;                       // nh << xt_log2, at most cols_pad
-    double *vals_hot = nullptr, *vals_cold = nullptr;  // vals_hot / cid_hot: the raw hot arrays; null when every hot slice is packed
+    void *vals_hot = nullptr, *vals_cold = nullptr;    // vals_hot / cid_hot: the raw hot arrays; null when every hot slice is packed
     uint16_t *cid_hot = nullptr;
     unsigned char *packed_hot = nullptr;           // the records of the packed hot slices
     TileWord *hot_tw = nullptr;                    // tile words of the hot slices (both forms)
@@ -510,8 +520,18 @@ void band_free(BandPlan *bp) { delete bp; }
 
 namespace {
 
-template <typename IDX, typename PTR>
-int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, OwnedBandPlan &out) {
+// option spmv_band_tile (f64 handles) / spmv_f32_band_tile (f32 handles: a float x tile of 128 KiB holds 32768 labels, and the raw
+// id has the bit for them — bit 14 is KEY_SEL only in packed slices, which f32 plans do not have)
+static uint32_t band_xt_log2(const sprs_hip_csmat *) { return options().spmv_band_tile == 8192 ? 13u : 14u; }
+static uint32_t band_xt_log2(const sprs_hip_csmat_f32 *) {
+    const int64_t t = options().spmv_f32_band_tile;
+    return t == 8192 ? 13u : t == 32768 ? 15u : 14u;
+}
+
+template <typename IDX, typename PTR, typename H>
+int32_t band_build_t(H *a, hipStream_t stream, OwnedBandPlan &out) {
+    using T = typename H::value_type;
+    constexpr uint64_t VB = sizeof(T);
     const Options &o = options();
     const uint64_t rows = a->rows, cols = a->cols, nnz = a->nnz;
     const PTR *ip = (const PTR *)a->indptr;
@@ -522,7 +542,7 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, OwnedBandPlan &out) 
     // (24 measured best on R-MAT 10M; a small matrix — fewer than ~400 hot tiles per CU, the `small` plans below — does better
     // with 8: R-MAT 1M 0.087 against 0.092 ms with two rounds of hot workgroups, profiles/r10u, r10v)
     const uint64_t split = o.spmv_band_split > 0 ? (uint64_t)o.spmv_band_split : (nnz < 400ull * 256ull * 512ull ? 8ull : 24ull);
-    const uint32_t xt_log2 = o.spmv_band_tile == 8192 ? 13u : 14u;
+    const uint32_t xt_log2 = band_xt_log2(a);
     const uint64_t XT = 1ull << xt_log2;
 
     // ---- row classes --------------------------------------------------------------------
@@ -551,6 +571,7 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, OwnedBandPlan &out) 
     OwnedBandPlan bp(new BandPlan());
     bp->cols = cols;
     bp->xt_log2 = xt_log2;
+    bp->vbytes = (uint32_t)VB;
     bp->cols_pad = (cols + XT - 1) / XT * XT + XT;
     bp->n_long = (uint32_t)n_long;
     bp->n_short_rows = (uint32_t)n_short_rows;
@@ -581,7 +602,7 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, OwnedBandPlan &out) 
     {
         size_t free_b = 0, total_b = 0;
         SPRS_TRY_HIP(hipMemGetInfo(&free_b, &total_b));
-        if (o.spmv_band == 0 && flat * 32 + nnz * 12 > free_b / 2) return SPRS_HIP_OK;
+        if (o.spmv_band == 0 && flat * 32 + nnz * (4 + VB) > free_b / 2) return SPRS_HIP_OK;
     }
 
     // ---- labels ---------------------------------------------------------------------------
@@ -611,9 +632,9 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, OwnedBandPlan &out) 
     DevBuf s_rowidx_t, s_ptr_t;
     SPRS_TRY_HIP(s_rowidx_t.alloc((n_short_rows + 1) * 4));
     SPRS_TRY_HIP(s_ptr_t.alloc((n_short_rows + 1) * 4));
-    hipLaunchKernelGGL((bp_fill_short_kernel<IDX, PTR>), dim3((unsigned)((rows + 256) / 256)), dim3(256), 0, stream, ip, ix,
-                       a->data, rows, short_pos.u64(), short_ptr.u64(), long_pos.u64(), bp->perm, (uint32_t *)s_rowidx_t.p,
-                       (uint32_t *)s_ptr_t.p, (uint32_t *)nullptr, (double *)nullptr, bp->long_rows, split, 0, ShortBuckets{nullptr, 1, 1}, 0ull, n_long);
+    hipLaunchKernelGGL((bp_fill_short_kernel<IDX, PTR, T>), dim3((unsigned)((rows + 256) / 256)), dim3(256), 0, stream, ip, ix,
+                       (const T *)a->data, rows, short_pos.u64(), short_ptr.u64(), long_pos.u64(), bp->perm, (uint32_t *)s_rowidx_t.p,
+                       (uint32_t *)s_ptr_t.p, (uint32_t *)nullptr, (T *)nullptr, bp->long_rows, split, 0, ShortBuckets{nullptr, 1, 1}, 0ull, n_long);
     SPRS_TRY_HIP(hipGetLastError());
     uint64_t wblocks = (n_long + 3) / 4;
     if (wblocks > 256 * 64) wblocks = 256 * 64;
@@ -712,28 +733,28 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, OwnedBandPlan &out) 
     const uint64_t hot_entries = hot_tiles * WT;
     // (the raw hot arrays join the plan's blocks at the end, unless every slice is packed)
     DevBuf vals_hot_blk, cid_hot_blk;
-    SPRS_TRY_HIP(vals_hot_blk.alloc((hot_entries + WT) * 8));
+    SPRS_TRY_HIP(vals_hot_blk.alloc((hot_entries + WT) * VB));
     SPRS_TRY_HIP(cid_hot_blk.alloc((hot_entries + WT) * 2));
-    bp->vals_hot = vals_hot_blk.as<double>();
+    bp->vals_hot = vals_hot_blk.p;
     bp->cid_hot = cid_hot_blk.as<uint16_t>();
-    SPRS_TRY_HIP(hipMemsetAsync(bp->vals_hot, 0, (hot_entries + WT) * 8, stream));
+    SPRS_TRY_HIP(hipMemsetAsync(bp->vals_hot, 0, (hot_entries + WT) * VB, stream));
     SPRS_TRY_HIP(hipMemsetAsync(bp->cid_hot, 0, (hot_entries + WT) * 2, stream));
-    SPRS_TRY_HIP(alloc_block(bp->blocks, bp->vals_cold, (cold_ent + WT) * 8));
+    SPRS_TRY_HIP(alloc_block(bp->blocks, bp->vals_cold, (cold_ent + WT) * VB));
     SPRS_TRY_HIP(alloc_block(bp->blocks, bp->cid_cold, (cold_ent + WT) * 4));
     // the padding of every piece — behind its last entry, and the gaps of the short piece — reads as (label `cols`, value 0):
     // xp[cols] is never written and stays 0.0, so a padding product is 0 * 0 whatever x holds
-    SPRS_TRY_HIP(hipMemsetAsync(bp->vals_cold, 0, (cold_ent + WT) * 8, stream));
+    SPRS_TRY_HIP(hipMemsetAsync(bp->vals_cold, 0, (cold_ent + WT) * VB, stream));
     SPRS_TRY_HIP(hipMemsetD32Async((hipDeviceptr_t)bp->cid_cold, (int)(uint32_t)cols, cold_ent + WT, stream));
     DevBuf ptr_all;                                                // entry offsets of the compact rows: only the build reads them
     SPRS_TRY_HIP(ptr_all.alloc((ptr_off + n_short_rows + 2) * 4));
     SPRS_TRY_HIP(alloc_block(bp->blocks, bp->rowidx_all, (row_off + n_short_rows + 1) * 4));
     SPRS_TRY_HIP(alloc_block(bp->blocks, bp->tile_row_all, (tile_off + 1) * 4));
-    bp->bytes = (cold_ent + WT) * 12 + (row_off + n_short_rows + tile_off) * 4 + cols * 4 + n_long * 4 +
+    bp->bytes = (cold_ent + WT) * (4 + VB) + (row_off + n_short_rows + tile_off) * 4 + cols * 4 + n_long * 4 +
                 ((uint64_t)bp->nref + 4) * 4;
     // short piece: its entries go straight into place (piece 0 of the cold arrays), its row lists are copied
-    hipLaunchKernelGGL((bp_fill_short_kernel<IDX, PTR>), dim3((unsigned)((rows + 256) / 256)), dim3(256), 0, stream, ip, ix,
-                       a->data, rows, short_pos.u64(), short_ptr.u64(), long_pos.u64(), bp->perm, (uint32_t *)nullptr,
-                       (uint32_t *)s_ptr_t.p, bp->cid_cold, bp->vals_cold, bp->long_rows, split, 1, sbk, nnz_short_padded, n_long);
+    hipLaunchKernelGGL((bp_fill_short_kernel<IDX, PTR, T>), dim3((unsigned)((rows + 256) / 256)), dim3(256), 0, stream, ip, ix,
+                       (const T *)a->data, rows, short_pos.u64(), short_ptr.u64(), long_pos.u64(), bp->perm, (uint32_t *)nullptr,
+                       (uint32_t *)s_ptr_t.p, bp->cid_cold, (T *)bp->vals_cold, bp->long_rows, split, 1, sbk, nnz_short_padded, n_long);
     SPRS_TRY_HIP(hipGetLastError());
     SPRS_TRY_HIP(hipMemcpyAsync((uint32_t *)ptr_all.p + ptr_off, s_ptr_t.p, (n_short_rows + 1) * 4, hipMemcpyDeviceToDevice, stream));
     if (n_short_rows)
@@ -741,9 +762,9 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, OwnedBandPlan &out) 
 
     SPRS_TRY_HIP(pb_d.alloc(NP * sizeof(PieceBuild)));
     SPRS_TRY_HIP(hipMemcpyAsync(pb_d.p, pb.data(), NP * sizeof(PieceBuild), hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL((bp_scatter_kernel<IDX, PTR>), dim3((unsigned)wblocks), dim3(256), 0, stream, ip, ix, a->data,
-                       bp->long_rows, n_long, bp->perm, map, NP, pos.u64(), (const PieceBuild *)pb_d.p, bp->vals_hot,
-                       bp->cid_hot, bp->vals_cold, bp->cid_cold);
+    hipLaunchKernelGGL((bp_scatter_kernel<IDX, PTR, T>), dim3((unsigned)wblocks), dim3(256), 0, stream, ip, ix, (const T *)a->data,
+                       bp->long_rows, n_long, bp->perm, map, NP, pos.u64(), (const PieceBuild *)pb_d.p, (T *)bp->vals_hot,
+                       bp->cid_hot, (T *)bp->vals_cold, bp->cid_cold);
     SPRS_TRY_HIP(hipGetLastError());
     hipLaunchKernelGGL(bp_rows_kernel, dim3((unsigned)((flat + 255) / 256)), dim3(256), 0, stream, cnt.u64(), pos.u64(),
                        pair.u64(), n_long, NP, (const PieceBuild *)pb_d.p, (uint32_t *)ptr_all.p, bp->rowidx_all);
@@ -796,7 +817,7 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, OwnedBandPlan &out) 
         }
         SPRS_TRY_HIP(pjobs_d.alloc(pjobs.size() * sizeof(PackJob)));
         SPRS_TRY_HIP(keys_d.alloc((hot_tiles + 1) * 4));
-        const bool want_pack = o.spmv_band_pack != 2;
+        const bool want_pack = o.spmv_band_pack != 2 && VB == 8;     // (no packed f32 slices: a float has no spare 1.5 bytes)
         if (want_pack) {
             SPRS_TRY_HIP(hipMemcpyAsync(pjobs_d.p, pjobs.data(), pjobs.size() * sizeof(PackJob), hipMemcpyHostToDevice, stream));
             hipLaunchKernelGGL(bp_tile_keys_kernel, dim3((max_hot_tiles + 3) / 4, (uint32_t)nh), dim3(256), 0, stream, (const PackJob *)pjobs_d.p,
@@ -1035,15 +1056,17 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, OwnedBandPlan &out) 
     if (!packed_tiles) {
         bp->blocks.push_back(std::move(vals_hot_blk));
         bp->blocks.push_back(std::move(cid_hot_blk));
-        bp->bytes += (hot_entries + WT) * 10;
+        bp->bytes += (hot_entries + WT) * (2 + VB);
     } else if (raw_tiles) {
-        const double *v_all = bp->vals_hot;
+        const double *v_all = (const double *)bp->vals_hot;           // (only plans of doubles hold packed slices)
         const uint16_t *c_all = bp->cid_hot;
-        SPRS_TRY_HIP(alloc_block(bp->blocks, bp->vals_hot, (raw_tiles * WT + WT) * 8));
+        double *v_raw = nullptr;
+        SPRS_TRY_HIP(alloc_block(bp->blocks, v_raw, (raw_tiles * WT + WT) * 8));
+        bp->vals_hot = v_raw;
         SPRS_TRY_HIP(alloc_block(bp->blocks, bp->cid_hot, (raw_tiles * WT + WT) * 2));
         for (const PackJob &jb : pjobs) {
             if (jb.packed || !jb.ntiles) continue;
-            SPRS_TRY_HIP(hipMemcpyAsync(bp->vals_hot + jb.rec0 * WT, v_all + jb.ent0, (uint64_t)jb.ntiles * WT * 8, hipMemcpyDeviceToDevice, stream));
+            SPRS_TRY_HIP(hipMemcpyAsync(v_raw + jb.rec0 * WT, v_all + jb.ent0, (uint64_t)jb.ntiles * WT * 8, hipMemcpyDeviceToDevice, stream));
             SPRS_TRY_HIP(hipMemcpyAsync(bp->cid_hot + jb.rec0 * WT, c_all + jb.ent0, (uint64_t)jb.ntiles * WT * 2, hipMemcpyDeviceToDevice, stream));
         }
         SPRS_TRY_HIP(hipStreamSynchronize(stream));
@@ -1072,13 +1095,22 @@ int32_t band_build_t(sprs_hip_csmat *a, hipStream_t stream, OwnedBandPlan &out) 
 int32_t band_scratch(BandPlan *bp, hipStream_t stream, BandScratch **out) {
     auto it = bp->scratch.find((void *)stream);
     if (it == bp->scratch.end()) {
+#ifndef SPRS_HIP_EMU
+        // a stream that is being captured into a hipGraph cannot allocate or synchronise: its scratch has to exist
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        const bool capturing = hipStreamIsCapturing(stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+        (void)hipGetLastError();
+        if (capturing && bp->vbytes == 4)              // (f64 handles: as before, the first multiply on a stream makes its scratch)
+            SPRS_FAIL(SPRS_HIP_INVALID_ARG, "SpMV on a capturing stream needs the handle's plan to exist: call sprs_hip_csmat_f32_prepare with this stream first");
+#endif
+        const uint64_t vb = bp->vbytes;
         BandScratch sc;                                // complete before it goes into the map: a failure on the way frees what it took
-        SPRS_TRY_HIP(alloc_block(sc.blocks, sc.partial, (bp->total_pairs + 1) * 8));   // every pair is written by every SpMV
-        SPRS_TRY_HIP(alloc_block(sc.blocks, sc.carry, ((uint64_t)bp->nranges + 1) * 8));
-        SPRS_TRY_HIP(alloc_block(sc.blocks, sc.xp, bp->cols_pad * 8));
-        SPRS_TRY_HIP(hipMemsetAsync(sc.xp, 0, bp->cols_pad * 8, stream));      // the padding behind the last column is read into LDS
+        SPRS_TRY_HIP(alloc_block(sc.blocks, sc.partial, (bp->total_pairs + 1) * vb));   // every pair is written by every SpMV
+        SPRS_TRY_HIP(alloc_block(sc.blocks, sc.carry, ((uint64_t)bp->nranges + 1) * vb));
+        SPRS_TRY_HIP(alloc_block(sc.blocks, sc.xp, bp->cols_pad * vb));
+        SPRS_TRY_HIP(hipMemsetAsync(sc.xp, 0, bp->cols_pad * vb, stream));      // the padding behind the last column is read into LDS
         std::vector<BandPiece> pcs = bp->host_pieces;
-        for (uint32_t k = 0; k <= bp->npieces; ++k) pcs[k].out = k < bp->npieces ? sc.partial + bp->pair_off[k] : nullptr;
+        for (uint32_t k = 0; k <= bp->npieces; ++k) pcs[k].out = k < bp->npieces ? (void *)((char *)sc.partial + bp->pair_off[k] * vb) : nullptr;
         SPRS_TRY_HIP(alloc_block(sc.blocks, sc.pieces, pcs.size() * sizeof(BandPiece)));
         SPRS_TRY_HIP(copy_to_device(sc.pieces, pcs.data(), pcs.size() * sizeof(BandPiece), stream));
         SPRS_TRY_HIP(hipStreamCreateWithFlags(&sc.aux, hipStreamNonBlocking));
@@ -1098,6 +1130,18 @@ int32_t band_build(sprs_hip_csmat *a, hipStream_t stream, OwnedBandPlan &out) {
         return band_build_t<typename decltype(i)::type, typename decltype(p)::type>(a, stream, out);
     });
 }
+int32_t band_build(sprs_hip_csmat_f32 *a, hipStream_t stream, OwnedBandPlan &out) {
+    return dispatch_widths(a->idx_bytes, a->iptr_bytes, [&](auto i, auto p) {
+        return band_build_t<typename decltype(i)::type, typename decltype(p)::type>(a, stream, out);
+    });
+}
+
+// `stream`'s scratch, made now (the prepare entry of an f32 handle: a capturing stream must find it)
+int32_t band_prepare_stream(sprs_hip_csmat_f32 *a, BandPlan *bp, hipStream_t stream) {
+    std::lock_guard<std::recursive_mutex> lock(a->mu);
+    BandScratch *sc = nullptr;
+    return band_scratch(bp, stream, &sc);
+}
 
 uint64_t band_plan_bytes(const BandPlan *bp) { return bp ? bp->bytes : 0; }
 
@@ -1112,7 +1156,40 @@ uint64_t band_plan_bytes(const BandPlan *bp) { return bp ? bp->bytes : 0; }
 // this SpMV mostly time-share the fabric — the sum of their times alone is 1 190 us, side by side they take 1 040 - 1 080
 // (profiles/r13c, r13d) — and holding part of the short rows back until the hot kernel is done, so that they run beside the
 // reduction, was SLOWER (1.11 - 1.16 against 1.07 ms, profiles/r13d: a small kernel like the carries then waits behind them).
-int32_t band_spmv(sprs_hip_csmat *a, BandPlan *bp, const double *x, double *y, bool acc, hipStream_t stream) {
+namespace {
+// the kernels of one scalar: the f64 ones under the names (and argument types) they always had, the f32 ones beside them
+template <typename T>
+struct BandK;
+template <>
+struct BandK<double> {
+    using Cold = ColdArgs;
+    using Reduce = ReduceArgs;
+    template <bool ACC, bool TOY>
+    static auto cold() { return &band_cold_kernel<ACC, TOY>; }
+    template <bool ACC>
+    static auto reduce() { return &band_reduce_kernel<ACC>; }
+    template <bool ACC>
+    static auto tail() { return &band_tail_kernel<ACC>; }
+    static auto permute() { return &band_permute_kernel; }
+};
+template <>
+struct BandK<float> {
+    using Cold = ColdArgsT<float>;
+    using Reduce = ReduceArgsT<float>;
+    template <bool ACC, bool TOY>
+    static auto cold() { return &band_cold_kernel_f32<ACC, TOY>; }
+    template <bool ACC>
+    static auto reduce() { return &band_reduce_kernel_f32<ACC>; }
+    template <bool ACC>
+    static auto tail() { return &band_tail_kernel_f32<ACC>; }
+    static auto permute() { return &band_permute_kernel_f32; }
+};
+
+template <typename H>
+int32_t band_spmv_t(H *a, BandPlan *bp, const typename H::value_type *x, typename H::value_type *y, bool acc, hipStream_t stream) {
+    using T = typename H::value_type;
+    using K = BandK<T>;
+    constexpr bool F32 = sizeof(T) == 4;
     BandScratch *sc = nullptr;
     {
         std::lock_guard<std::recursive_mutex> lock(a->mu);
@@ -1127,8 +1204,8 @@ int32_t band_spmv(sprs_hip_csmat *a, BandPlan *bp, const double *x, double *y, b
     auto launch_carry_y = [&](hipStream_t st) -> int32_t {
         const uint32_t n = bp->nspills_y;
         if (!n) return SPRS_HIP_OK;
-        hipLaunchKernelGGL(band_carry_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, st, (const Spill *)bp->spills_y, n, (const double *)sc->carry,
-                           sc->partial, y);
+        hipLaunchKernelGGL((band_carry_kernel<true, T>), dim3((n + 255) / 256), dim3(256), 0, st, (const Spill *)bp->spills_y, n, (const T *)sc->carry,
+                           (T *)sc->partial, y);
         SPRS_TRY_HIP(hipGetLastError());
         return SPRS_HIP_OK;
     };
@@ -1138,13 +1215,20 @@ int32_t band_spmv(sprs_hip_csmat *a, BandPlan *bp, const double *x, double *y, b
     const bool fused_tail = !overlap && bp->small && options().spmv_band_tail != 2 && bp->cold_blocks > cut;
     auto launch_hot = [&]() -> int32_t {
         if (!bp->hot_wgs) return SPRS_HIP_OK;
-        const uint32_t lds = hot_lds_bytes(bp->xt_log2);
+        const uint32_t lds = F32 ? hot_lds_bytes_f32(bp->xt_log2) : hot_lds_bytes(bp->xt_log2);
 #ifndef SPRS_HIP_EMU
         {   // more than 64 KiB of dynamic LDS has to be asked for, once per kernel and device
             static std::mutex mu;
             static std::unordered_map<int, bool> done;
             std::lock_guard<std::mutex> lock(mu);
-            if (!done[a->device]) {
+            if constexpr (F32) {
+                if (!done[a->device]) {
+                    SPRS_TRY_HIP(hipFuncSetAttribute((const void *)band_hot_kernel_f32<13, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hot_lds_bytes_f32(13)));
+                    SPRS_TRY_HIP(hipFuncSetAttribute((const void *)band_hot_kernel_f32<14, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hot_lds_bytes_f32(14)));
+                    SPRS_TRY_HIP(hipFuncSetAttribute((const void *)band_hot_kernel_f32<15, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hot_lds_bytes_f32(15)));
+                    done[a->device] = true;
+                }
+            } else if (!done[a->device]) {
                 const void *k13[] = {(const void *)band_hot_kernel<13, 0>, (const void *)band_hot_kernel<13, 1>, (const void *)band_hot_kernel<13, 2>};
                 const void *k14[] = {(const void *)band_hot_kernel<14, 0>, (const void *)band_hot_kernel<14, 1>, (const void *)band_hot_kernel<14, 2>};
                 for (const void *k : k13) SPRS_TRY_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hot_lds_bytes(13)));
@@ -1164,27 +1248,38 @@ int32_t band_spmv(sprs_hip_csmat *a, BandPlan *bp, const double *x, double *y, b
         const uint32_t np = bp->hot_wgs_packed, nraw = bp->hot_wgs - np;
         const HotSeg *wf = (const HotSeg *)bp->wg_first;
         const uint32_t dbg = (uint32_t)options().spmv_band_debug;
-        if (np) {
-            // (a big plan's packed slices: two consecutive ranges per wave and turn, see band_hot_kernel)
-            auto launch_packed = [&](auto kernel) {
-                hipLaunchKernelGGL(kernel, dim3(np), dim3(HOT_THREADS), lds, stream, (const HotSeg *)bp->hsegs, wf, (const double *)bp->packed_hot,
-                                   (const uint16_t *)nullptr, (const double *)sc->xp, sc->partial, sc->carry, dbg, prof, xcd_shares);
+        if constexpr (F32) {                                       // raw slices only: one launch
+            auto launch_raw = [&](auto kernel) {
+                hipLaunchKernelGGL(kernel, dim3(nraw), dim3(HOT_THREADS), lds, stream, (const HotSeg *)bp->hsegs, wf, (const float *)bp->vals_hot,
+                                   (const uint16_t *)bp->cid_hot, (const float *)sc->xp, (float *)sc->partial, (float *)sc->carry, dbg, prof, xcd_shares);
             };
-            if (bp->xt_log2 == 13 && bp->small) launch_packed(band_hot_kernel<13, 1>);
-            else if (bp->xt_log2 == 13) launch_packed(band_hot_kernel<13, 2>);
-            else if (bp->small) launch_packed(band_hot_kernel<14, 1>);
-            else launch_packed(band_hot_kernel<14, 2>);
+            if (bp->xt_log2 == 13) launch_raw(band_hot_kernel_f32<13, 0>);
+            else if (bp->xt_log2 == 15) launch_raw(band_hot_kernel_f32<15, 0>);
+            else launch_raw(band_hot_kernel_f32<14, 0>);
             SPRS_TRY_HIP(hipGetLastError());
-        }
-        if (nraw) {
-            unsigned long long *prof_raw = prof ? prof + 3ull * np : nullptr;
-            if (bp->xt_log2 == 13)
-                hipLaunchKernelGGL((band_hot_kernel<13, 0>), dim3(nraw), dim3(HOT_THREADS), lds, stream, (const HotSeg *)bp->hsegs, wf + np,
-                                   (const double *)bp->vals_hot, (const uint16_t *)bp->cid_hot, (const double *)sc->xp, sc->partial, sc->carry, dbg, prof_raw, xcd_shares);
-            else
-                hipLaunchKernelGGL((band_hot_kernel<14, 0>), dim3(nraw), dim3(HOT_THREADS), lds, stream, (const HotSeg *)bp->hsegs, wf + np,
-                                   (const double *)bp->vals_hot, (const uint16_t *)bp->cid_hot, (const double *)sc->xp, sc->partial, sc->carry, dbg, prof_raw, xcd_shares);
-            SPRS_TRY_HIP(hipGetLastError());
+        } else {
+            if (np) {
+                // (a big plan's packed slices: two consecutive ranges per wave and turn, see band_hot_kernel)
+                auto launch_packed = [&](auto kernel) {
+                    hipLaunchKernelGGL(kernel, dim3(np), dim3(HOT_THREADS), lds, stream, (const HotSeg *)bp->hsegs, wf, (const double *)bp->packed_hot,
+                                       (const uint16_t *)nullptr, (const double *)sc->xp, (double *)sc->partial, (double *)sc->carry, dbg, prof, xcd_shares);
+                };
+                if (bp->xt_log2 == 13 && bp->small) launch_packed(band_hot_kernel<13, 1>);
+                else if (bp->xt_log2 == 13) launch_packed(band_hot_kernel<13, 2>);
+                else if (bp->small) launch_packed(band_hot_kernel<14, 1>);
+                else launch_packed(band_hot_kernel<14, 2>);
+                SPRS_TRY_HIP(hipGetLastError());
+            }
+            if (nraw) {
+                unsigned long long *prof_raw = prof ? prof + 3ull * np : nullptr;
+                if (bp->xt_log2 == 13)
+                    hipLaunchKernelGGL((band_hot_kernel<13, 0>), dim3(nraw), dim3(HOT_THREADS), lds, stream, (const HotSeg *)bp->hsegs, wf + np,
+                                       (const double *)bp->vals_hot, (const uint16_t *)bp->cid_hot, (const double *)sc->xp, (double *)sc->partial, (double *)sc->carry, dbg, prof_raw, xcd_shares);
+                else
+                    hipLaunchKernelGGL((band_hot_kernel<14, 0>), dim3(nraw), dim3(HOT_THREADS), lds, stream, (const HotSeg *)bp->hsegs, wf + np,
+                                       (const double *)bp->vals_hot, (const uint16_t *)bp->cid_hot, (const double *)sc->xp, (double *)sc->partial, (double *)sc->carry, dbg, prof_raw, xcd_shares);
+                SPRS_TRY_HIP(hipGetLastError());
+            }
         }
         if (DEVTOOLS && prof && getenv("SPRS_HIP_HOTPROF")) {      // (synchronous: a developer printout, not a timing run)
             std::vector<unsigned long long> t((size_t)bp->hot_wgs * 3);
@@ -1214,14 +1309,17 @@ int32_t band_spmv(sprs_hip_csmat *a, BandPlan *bp, const double *x, double *y, b
     };
     // blocks [b0, b0 + nb) of the gather launch: cold pieces (partial sums out) below `cut`, short rows (y out) from there on
     auto cold_args = [&](uint32_t b0) {
-        return ColdArgs{sc->pieces, bp->groups, bp->ngroups, bp->vals_cold, bp->cid_cold, sc->xp, y, sc->carry, b0, bp->cold_tiles, 0u, BandPiece()};
+        typename K::Cold ca;
+        static_cast<ColdArgsT<T> &>(ca) = ColdArgsT<T>{sc->pieces, bp->groups, bp->ngroups, (const T *)bp->vals_cold, bp->cid_cold, (const T *)sc->xp, y, (T *)sc->carry,
+                                                       b0, bp->cold_tiles, 0u, BandPiece()};
+        return ca;
     };
     auto launch_gather = [&](uint32_t b0, uint32_t nb) -> int32_t {
         if (!nb) return SPRS_HIP_OK;
-        const ColdArgs ca = cold_args(b0);
-        if (b0 < cut) hipLaunchKernelGGL((band_cold_kernel<false, false>), dim3(nb), dim3(CNT), 0, cstream, ca);
-        else if (acc) hipLaunchKernelGGL((band_cold_kernel<true, true>), dim3(nb), dim3(CNT), 0, cstream, ca);
-        else hipLaunchKernelGGL((band_cold_kernel<false, true>), dim3(nb), dim3(CNT), 0, cstream, ca);
+        const typename K::Cold ca = cold_args(b0);
+        if (b0 < cut) hipLaunchKernelGGL((K::template cold<false, false>()), dim3(nb), dim3(CNT), 0, cstream, ca);
+        else if (acc) hipLaunchKernelGGL((K::template cold<true, true>()), dim3(nb), dim3(CNT), 0, cstream, ca);
+        else hipLaunchKernelGGL((K::template cold<false, true>()), dim3(nb), dim3(CNT), 0, cstream, ca);
         SPRS_TRY_HIP(hipGetLastError());
         return SPRS_HIP_OK;
     };
@@ -1232,8 +1330,8 @@ int32_t band_spmv(sprs_hip_csmat *a, BandPlan *bp, const double *x, double *y, b
     auto launch_xp = [&](uint32_t l0, uint32_t l1, bool clear_y, hipStream_t st, bool hot_only = false) -> int32_t {
         if (!by_gather && !hot_only) {                                   // the scatter form; a big plan's hot labels are always gathered
             const uint64_t span = clear_y ? std::max<uint64_t>(bp->cols, a->rows) : bp->cols;
-            hipLaunchKernelGGL(band_permute_kernel, dim3((unsigned)((span + 1023) / 1024)), dim3(256), 0, st, x, (const uint32_t *)bp->perm, bp->cols,
-                               sc->xp, clear_y ? y : (double *)nullptr, a->rows, l0, (uint32_t)bp->cols_pad);     // (every label from l0 on: leaving out the
+            hipLaunchKernelGGL((K::permute()), dim3((unsigned)((span + 1023) / 1024)), dim3(256), 0, st, x, (const uint32_t *)bp->perm, bp->cols,
+                               (T *)sc->xp, clear_y ? y : (T *)nullptr, a->rows, l0, (uint32_t)bp->cols_pad);     // (every label from l0 on: leaving out the
             // unreferenced columns' stores made R-MAT 10M 5 - 8 % SLOWER on average — 1.10 - 1.14 against 1.05 ms, same best step —, gpurun_out/r15x)
             SPRS_TRY_HIP(hipGetLastError());
             return SPRS_HIP_OK;
@@ -1241,11 +1339,11 @@ int32_t band_spmv(sprs_hip_csmat *a, BandPlan *bp, const double *x, double *y, b
         const uint64_t n4 = std::max<uint64_t>(l1 > l0 ? ((uint64_t)(l1 - l0) + 3) / 4 : 0, clear_y ? (a->rows + 3) / 4 : 0);
         if (!n4) return SPRS_HIP_OK;
         if (clear_y)
-            hipLaunchKernelGGL(band_gather_kernel<true>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, x, (const uint32_t *)bp->inv_hot, l0,
-                               l1 > l0 ? l1 : l0, sc->xp, y, a->rows);
+            hipLaunchKernelGGL((band_gather_kernel<true, T>), dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, x, (const uint32_t *)bp->inv_hot, l0,
+                               l1 > l0 ? l1 : l0, (T *)sc->xp, y, a->rows);
         else
-            hipLaunchKernelGGL(band_gather_kernel<false>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, x, (const uint32_t *)bp->inv_hot, l0,
-                               l1 > l0 ? l1 : l0, sc->xp, (double *)nullptr, a->rows);
+            hipLaunchKernelGGL((band_gather_kernel<false, T>), dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, x, (const uint32_t *)bp->inv_hot, l0,
+                               l1 > l0 ? l1 : l0, (T *)sc->xp, (T *)nullptr, a->rows);
         SPRS_TRY_HIP(hipGetLastError());
         return SPRS_HIP_OK;
     };
@@ -1270,24 +1368,33 @@ int32_t band_spmv(sprs_hip_csmat *a, BandPlan *bp, const double *x, double *y, b
     const uint32_t nwb = (bp->n_long + WAVE - 1) / WAVE;
     const uint32_t per_xcd = (nwb + 7) / 8;
     const dim3 rg(((per_xcd + 3) / 4) * 8), rb(256);                 // reduction: one wave per block of 64 long rows, XCD by XCD
-    const ReduceArgs ra{sc->partial, bp->wmask, bp->wbase, bp->long_rows, (const RSpill *)bp->rspills, bp->nspills ? bp->rsp_off : nullptr,
-                        sc->carry, y, bp->n_long, bp->np_pad, nwb};
+    typename K::Reduce ra;
+    static_cast<ReduceArgsT<T> &>(ra) = ReduceArgsT<T>{(const T *)sc->partial, bp->wmask, bp->wbase, bp->long_rows, (const RSpill *)bp->rspills,
+                                                       bp->nspills ? bp->rsp_off : nullptr, (const T *)sc->carry, y, bp->n_long, bp->np_pad, nwb};
     if (fused_tail) {
-        ColdArgs ca = cold_args(cut);
+        typename K::Cold ca = cold_args(cut);
         ca.direct = 1u;                                         // the short piece by value: the blocks from `cut` on walk only it
         ca.piece = bp->host_pieces[bp->npieces];
         const dim3 tg(rg.x + (bp->cold_blocks - cut));
-        if (acc) hipLaunchKernelGGL(band_tail_kernel<true>, tg, rb, 0, stream, ra, rg.x, ca);
-        else hipLaunchKernelGGL(band_tail_kernel<false>, tg, rb, 0, stream, ra, rg.x, ca);
+        if (acc) hipLaunchKernelGGL((K::template tail<true>()), tg, rb, 0, stream, ra, rg.x, ca);
+        else hipLaunchKernelGGL((K::template tail<false>()), tg, rb, 0, stream, ra, rg.x, ca);
         SPRS_TRY_HIP(hipGetLastError());
         SPRS_TRY(launch_carry_y(stream));                       // (no records unless the short rows are long enough to forbid the gapped layout)
     } else {
-        if (acc) hipLaunchKernelGGL(band_reduce_kernel<true>, rg, rb, 0, stream, ra);
-        else hipLaunchKernelGGL(band_reduce_kernel<false>, rg, rb, 0, stream, ra);
+        if (acc) hipLaunchKernelGGL((K::template reduce<true>()), rg, rb, 0, stream, ra);
+        else hipLaunchKernelGGL((K::template reduce<false>()), rg, rb, 0, stream, ra);
         SPRS_TRY_HIP(hipGetLastError());
     }
     if (early_reduce) SPRS_TRY_HIP(hipStreamWaitEvent(stream, sc->join, 0));   // the short rows and their carries
     return SPRS_HIP_OK;
+}
+}  // namespace
+
+int32_t band_spmv(sprs_hip_csmat *a, BandPlan *bp, const double *x, double *y, bool acc, hipStream_t stream) {
+    return band_spmv_t(a, bp, x, y, acc, stream);
+}
+int32_t band_spmv(sprs_hip_csmat_f32 *a, BandPlan *bp, const float *x, float *y, bool acc, hipStream_t stream) {
+    return band_spmv_t(a, bp, x, y, acc, stream);
 }
 
 }  // namespace sprs_hip

@@ -5,7 +5,8 @@
 // Geometry shared by every piece of the plan (hot slices, cold pieces, the short rows):
 //   * a WAVE TILE is 512 consecutive entries of a piece; lane l owns the 8 consecutive entries 8 l .. 8 l + 7;
 //   * values are stored transposed so that the four coalesced 16-byte loads of a lane return its own entries:
-//     entry 8 l + 2 p + e of tile w at vals[512 w + 128 p + 2 l + e];
+//     entry 8 l + 2 p + e of tile w at vals[512 w + 128 p + 2 l + e]; f32 plans (BandT<float>): two loads of four floats,
+//     entry 8 l + 4 p + e at vals[512 w + 256 p + 4 l + e] — the arrangement of the cold labels and the packed low words;
 //   * the row structure travels with the column ids: a flag bit marks the first entry of a row inside the piece,
 //     tile_row[w] is the compact row (position in the piece's row list) of the first row starting in tile w;
 //   * a RANGE is a run of consecutive tiles walked by ONE wave: the sum of the row that is open at the end of a tile stays
@@ -20,6 +21,7 @@ namespace sprs_hip {
 namespace {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef float flt4 __attribute__((ext_vector_type(4)));
 
 constexpr int WT = 512;                       // entries per wave tile
 constexpr int WPASS = WT / (WAVE * 2);        // 16-byte value loads per lane and tile
@@ -32,11 +34,35 @@ constexpr uint32_t KEY_SEL = 0x4000u;         // packed hot slices: the entry's 
 constexpr uint32_t ROW_START32 = 0x80000000u; // flag bit in a cold label
 static_assert(WPASS == 4 && EPL == 8, "wave tile geometry");
 
+// The scalar of a plan: values, x, partial sums, carries and y are all T.  A 16-byte load holds VW values, a lane takes NV of them
+// per tile; entry 8 l + VW p + e of tile w sits at vals[512 w + 64 VW p + VW l + e].  Everything that does not touch a value (labels,
+// row tables, segments, ranges, spill records, the schedule) is the same for both scalars.
+template <typename T>
+struct BandT;
+template <>
+struct BandT<double> {
+    typedef dbl2 vec;
+    static constexpr int VW = 2, NV = WPASS;
+};
+template <>
+struct BandT<float> {
+    typedef flt4 vec;
+    static constexpr int VW = 4, NV = EPL / 4;
+};
+// position of entry q of lane ll in the transposed value array of the wave tile that starts at `base`.  (The plan build spells the
+// f64 form out where it stores: through this function the same sum compiles to other instructions, and the f64 device code is
+// held to the instruction — scripts/device_code_diff.py.)
+template <typename T>
+__device__ __forceinline__ uint64_t band_val_at(uint64_t base, uint32_t ll, uint32_t q) {
+    constexpr int VW = BandT<T>::VW;
+    return base + (q / VW) * (WAVE * VW) + ll * VW + (q % VW);
+}
+
 // One piece of the plan, as the kernels see it.
 struct BandPiece {
     const uint32_t *rowidx;     // nr: long-row number (short piece: row of y) of compact row r
     const uint32_t *tile_row;   // ntiles + 1: first compact row starting at / after tile c
-    double *out;                // nr partial sums, one per compact row, in row-list order (null for the short piece: it writes y)
+    void *out;                  // nr partial sums (of the plan's scalar), one per compact row, in row-list order (null for the short piece: it writes y)
     uint64_t ent0;              // first entry of the piece in the value / column-id arrays of its class
     uint64_t nnz;
     uint32_t nr, ntiles;
@@ -108,14 +134,15 @@ struct ColdGroup {              // a run of blocks of the cold launch
 #define SPRS_GLOBAL_AS __attribute__((address_space(1)))
 #define SPRS_HOT_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(5, 5)))
 #endif
+template <typename T>
 struct PieceView {
     const SPRS_GLOBAL_AS uint32_t *rowidx, *tile_row;
-    SPRS_GLOBAL_AS double *out;
+    SPRS_GLOBAL_AS T *out;
     uint64_t ent0, nnz;
     uint32_t nr, ntiles, x0, to_y, range0;
     __device__ __forceinline__ PieceView(const BandPiece &p)
         : rowidx((const SPRS_GLOBAL_AS uint32_t *)p.rowidx), tile_row((const SPRS_GLOBAL_AS uint32_t *)p.tile_row),
-          out((SPRS_GLOBAL_AS double *)p.out), ent0(p.ent0), nnz(p.nnz), nr(p.nr), ntiles(p.ntiles), x0(p.x0), to_y(p.to_y),
+          out((SPRS_GLOBAL_AS T *)p.out), ent0(p.ent0), nnz(p.nnz), nr(p.nr), ntiles(p.ntiles), x0(p.x0), to_y(p.to_y),
           range0(p.range0) {}
 };
 
@@ -146,7 +173,18 @@ __device__ __forceinline__ void band_seg_step(double &S, uint32_t &F) {
     F |= fs;
 }
 
-__device__ __forceinline__ void band_seg_scan(double &S, uint32_t &F, uint32_t lane) {
+// (a float travels in one DPP move)
+template <int CTRL, int ROW_MASK, bool BOUND>
+__device__ __forceinline__ void band_seg_step(float &S, uint32_t &F) {
+    const int vb = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, S), CTRL, ROW_MASK, 0xf, BOUND);
+    const uint32_t fs = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)F, CTRL, ROW_MASK, 0xf, BOUND);
+    const float vs = __builtin_bit_cast(float, vb);
+    S = F ? S : vs + S;
+    F |= fs;
+}
+
+template <typename T>
+__device__ __forceinline__ void band_seg_scan(T &S, uint32_t &F, uint32_t lane) {
     (void)lane;
     band_seg_step<0x111, 0xf, true>(S, F);
     band_seg_step<0x112, 0xf, true>(S, F);
@@ -164,10 +202,28 @@ __device__ __forceinline__ double band_lane_below(double S, uint32_t lane) {
     return __hiloint2double(hi, lo);
 }
 
+__device__ __forceinline__ float band_lane_below(float S, uint32_t lane) {
+    (void)lane;
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, S), 0x138, 0xf, 0xf, true));
+}
+
 __device__ __forceinline__ double band_read_lane63(double v) {
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), WAVE - 1);
     const int hi = __builtin_amdgcn_readlane(__double2hiint(v), WAVE - 1);
     return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ float band_read_lane63(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), WAVE - 1));
+}
+
+// the value lane `src` (wave-uniform) holds
+__device__ __forceinline__ double band_read_lane(double v, int src) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), src);
+    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
+    return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ float band_read_lane(float v, int src) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), src));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -197,6 +253,7 @@ __device__ __forceinline__ void wave_lds_fence() {
 
 constexpr int STG = 128;
 constexpr uint32_t hot_lds_bytes(uint32_t xt_log2) { return ((1u << xt_log2) + (uint32_t)HOT_WAVES * 128u) * 8u; }     // doubles of a wave's staging window: hot 16 x 1 KiB + x tile 128 KiB leave 16 KiB of LDS to the cold workgroups
+constexpr uint32_t hot_lds_bytes_f32(uint32_t xt_log2) { return ((1u << xt_log2) + (uint32_t)HOT_WAVES * 128u) * 4u; }   // floats: 32768 labels take 128 KiB + 8 KiB of windows
 
 // What band_tile_sums leaves in the wave's LDS window for a LATER flush: the hot kernel writes a tile's sums out after it
 // has waited for the next tile's loads — a store issued right before that wait is waited for as well (loads and stores
@@ -207,10 +264,10 @@ struct Pending {
     bool first_to_carry = false;   // the first one belongs to the row that was open when the range began
 };
 
-template <typename Out>
-__device__ __forceinline__ void band_flush(Pending &pd, uint32_t lane, SPRS_GLOBAL_AS double *carry, const double *stage, Out out) {
+template <typename T, typename Out>
+__device__ __forceinline__ void band_flush(Pending &pd, uint32_t lane, SPRS_GLOBAL_AS T *carry, const T *stage, Out out) {
     for (uint32_t j = lane; j < pd.cnt; j += WAVE) {
-        const double v = stage[j];
+        const T v = stage[j];
         if (j == 0 && pd.first_to_carry) *carry = v;
         else out(pd.row0 + j, v);
     }
@@ -219,16 +276,16 @@ __device__ __forceinline__ void band_flush(Pending &pd, uint32_t lane, SPRS_GLOB
 }
 
 // DEFER: the last window of the tile stays parked (pd) for band_flush; otherwise everything is written out here.
-template <bool DEFER, typename Out>
-__device__ __forceinline__ void band_tile_sums(const double (&pr)[EPL], uint32_t fb, uint32_t lane, uint32_t R0, double &open, bool &mine,
-                                               uint32_t &last, SPRS_GLOBAL_AS double *carry, double *stage, Pending &pd, Out out) {
+template <bool DEFER, typename T, typename Out>
+__device__ __forceinline__ void band_tile_sums(const T (&pr)[EPL], uint32_t fb, uint32_t lane, uint32_t R0, T &open, bool &mine,
+                                               uint32_t &last, SPRS_GLOBAL_AS T *carry, T *stage, Pending &pd, Out out) {
     const uint32_t nfl = (uint32_t)__popc(fb);                          // rows starting in this lane
     const uint32_t incl = band_scan_incl_u32(nfl, lane);
     const uint32_t prefix = incl - nfl;                                 // rows starting in lower lanes
     const uint32_t nf = (uint32_t)__builtin_amdgcn_readlane((int)incl, WAVE - 1);
     // ---- serial fold of the lane's entries: ev[q] = sum of the run that ends at the row start of entry q ------------
-    double ev[EPL];
-    double run = 0.0, head = 0.0;
+    T ev[EPL];
+    T run = 0.0, head = 0.0;
     uint32_t seen = 0;
 #pragma unroll
     for (int q = 0; q < EPL; ++q) {
@@ -241,12 +298,12 @@ __device__ __forceinline__ void band_tile_sums(const double (&pr)[EPL], uint32_t
         run += pr[q];
     }
     // ---- runs that cross lanes -------------------------------------------------------------------------------------
-    double S = run;
+    T S = run;
     uint32_t F = seen ? 1u : 0u;
     band_seg_scan(S, F, lane);
-    double before = band_lane_below(S, lane);                           // open run at the end of the lane below
+    T before = band_lane_below(S, lane);                           // open run at the end of the lane below
     if (prefix == 0) before = open + before;                            // no row has started in the tile so far: the range's open row
-    const double vhead = before + head;                                 // the run that ends at this lane's first row start
+    const T vhead = before + head;                                 // the run that ends at this lane's first row start
     // ---- out, window by window: row end number o of the tile (o = 0: the range's open row) is compact row R0 - 1 + o ----
     for (uint32_t lo = 0; lo < nf; lo += STG) {                         // wave-uniform
 #pragma unroll
@@ -263,7 +320,7 @@ __device__ __forceinline__ void band_tile_sums(const double (&pr)[EPL], uint32_t
         pd.first_to_carry = lo == 0 && !mine;                           // ... began before the range
         if (!DEFER || lo + STG < nf) band_flush(pd, lane, carry, stage, out);
     }
-    const double s63 = band_read_lane63(S);
+    const T s63 = band_read_lane63(S);
     open = nf ? s63 : open + s63;
     if (nf) {
         mine = true;
@@ -282,10 +339,10 @@ __device__ __forceinline__ void band_tile_sums(const double (&pr)[EPL], uint32_t
 // ---------------------------------------------------------------------------------------------
 // 96 VGPRs: the 4 waves per SIMD of this kernel then leave room for TWO 64-register waves of the gather kernels beside them
 // (at 98 it was one, and the cold launch crawled beside the hot one: 370 us instead of 86 alone, profiles/r05h)
-template <bool ACC, bool TOY>
-__device__ __forceinline__ void band_cold_wave(const PieceView d, uint32_t r, uint32_t ct, const double *__restrict__ vals,
-                                               const uint32_t *__restrict__ cid, const double *__restrict__ xp, double *__restrict__ y,
-                                               double *__restrict__ carry, double *stage, uint32_t lane);
+template <bool ACC, bool TOY, typename T>
+__device__ __forceinline__ void band_cold_wave(const PieceView<T> d, uint32_t r, uint32_t ct, const T *__restrict__ vals,
+                                               const uint32_t *__restrict__ cid, const T *__restrict__ xp, T *__restrict__ y,
+                                               T *__restrict__ carry, T *stage, uint32_t lane);
 
 // (Round 6 also ran the short rows in THIS kernel's prologue — the upper 8 waves of a workgroup walking short-row ranges while the lower
 // 8 fetched the first x tile: the short tile's chain of round trips, 13 us, then stood in front of every workgroup's first hot tile:
@@ -293,197 +350,11 @@ __device__ __forceinline__ void band_cold_wave(const PieceView d, uint32_t r, ui
 // R-MAT 1M, profiles/r15o.  Not kept.)
 // PACK 0: raw slices.  PACK 1 / 2: packed slices — `vals` is the array of packed records (cid is not read), the values are rebuilt
 // in front of the products — walked PACK consecutive ranges per wave and turn.
-template <int XT_LOG2, int PACK>
-__global__ __launch_bounds__(HOT_THREADS) SPRS_HOT_WAVES_ATTR void band_hot_kernel(const HotSeg *__restrict__ hsegs,
-                                                               const HotSeg *__restrict__ wg_first, const double *__restrict__ vals,
-                                                               const uint16_t *__restrict__ cid, const double *__restrict__ xp,
-                                                               double *__restrict__ partial, double *__restrict__ carry, uint32_t dbg,
-                                                               unsigned long long *__restrict__ prof, uint32_t xcd_shares) {
-    constexpr int XT = 1 << XT_LOG2;
-    constexpr bool PACKED = PACK != 0;
-    // developer builds, option spmv_band_debug & 16 (env SPRS_HIP_HOTPROF): when does each workgroup start, see its first x tile,
-    // and end (100 MHz wall clock) — is the hot kernel's time its work or its tail?
-    if constexpr (DEVTOOLS) {
-        if (prof && threadIdx.x == 0) prof[3 * blockIdx.x] = (unsigned long long)wall_clock64();
-    }
-    // dynamic LDS (hot_lds_bytes): with the size known at compile time the compiler sees that only 4 waves per SIMD fit and
-    // spends up to 128 registers; it is asked for 5 (96 registers) so that two gather waves fit beside each hot wave
-#ifdef SPRS_HIP_EMU
-    static double lds[XT + HOT_WAVES * STG];
-#else
-    extern __shared__ __attribute__((aligned(16))) double lds[];
-#endif
-    double *xs = lds;                                                    // XT doubles: the x tile
-    const uint32_t tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-    double *stage = lds + XT + wave * STG;                              // the wave's window for outgoing sums
-    // share of this workgroup.  xcd_shares: block b runs on XCD b % 8 (observed dispatch order; only speed depends on it) and every
-    // XCD takes a CONTIGUOUS run of shares — the workgroups that stream one slice then sit behind one L2, which serves its x tile
-    // to all but the first of them (dealt round-robin, every XCD's L2 fetched every slice: 256 workgroups x 128 KiB = 32 MB through
-    // the fabric in the first microseconds of a small plan's hot kernel).
-    uint32_t share = blockIdx.x;
-    if (xcd_shares) {
-        const uint32_t nq = gridDim.x >> 3, rem = gridDim.x & 7u, k = blockIdx.x & 7u;
-        share = k * nq + (k < rem ? k : rem) + (blockIdx.x >> 3);
-    }
-    // the share's FIRST segment comes with its segment range in one record (wg_first[share]: pad0 / pad1 = first segment, end) —
-    // one round trip in front of the first x tile instead of two (wg_seg -> hsegs)
-    HotSeg nxt = wg_first[share];
-    const uint32_t s0 = nxt.pad0, s1 = nxt.pad1;
-    for (uint32_t s = s0; s < s1; ++s) {
-        const HotSeg seg = nxt;
-        if (s + 1 < s1) nxt = hsegs[s + 1];                              // (requested a whole segment before it is needed)
-        struct {
-            const SPRS_GLOBAL_AS uint64_t *tile_word;                    // TileWord as one 8-byte word: row | keys << 32
-            SPRS_GLOBAL_AS double *out;
-            uint64_t ent0, nnz;
-            uint32_t x0;
-        } d{(const SPRS_GLOBAL_AS uint64_t *)seg.tile_word, (SPRS_GLOBAL_AS double *)(partial + seg.out_off), seg.ent0, seg.nnz, seg.x0};
-        if (s != s0) __syncthreads();                                    // every wave is done with the previous x tile
-        {   // x tile of the slice -> LDS (xp is padded to a whole number of tiles)
-            const dbl2 *src = (const dbl2 *)(xp + d.x0);
-            dbl2 v[XT / (2 * HOT_THREADS)];
-#pragma unroll
-            for (int q = 0; q < XT / (2 * HOT_THREADS); ++q) v[q] = src[q * HOT_THREADS + tid];
-#pragma unroll
-            for (int q = 0; q < XT / (2 * HOT_THREADS); ++q) *(dbl2 *)&xs[2 * (q * HOT_THREADS + tid)] = v[q];
-        }
-        // the wave's tiles, in the order it walks them: ranges r = wave, wave + 16, ...; inside a range tile after tile
-        const uint32_t run = seg.run, n = seg.ntiles;
-        dbl2 av[WPASS];
-        u32x4 cw = {0u, 0u, 0u, 0u};
-        u32x4 plo[2], pmh;                                               // PACKED: low words, mantissa-high fields (dwords 0 .. 3, 4)
-        uint32_t pmh4 = 0;
-        uint32_t R0n = 0, Kn = 0;
-        auto request = [&](uint32_t w) {
-            if constexpr (PACKED) {
-                const unsigned char *rec = (const unsigned char *)vals + (d.ent0 / WT + w) * (uint64_t)PK_TILE_BYTES;
-#pragma unroll
-                for (int p = 0; p < 2; ++p) plo[p] = __builtin_nontemporal_load((const u32x4 *)(rec + p * (WAVE * 16) + lane * 16));
-                pmh = __builtin_nontemporal_load((const u32x4 *)(rec + PK_MH + lane * 16));
-                pmh4 = __builtin_nontemporal_load((const uint32_t *)(rec + PK_MH4 + lane * 4));
-                cw = __builtin_nontemporal_load((const u32x4 *)(rec + PK_ID + lane * 16));
-                const uint64_t tw = d.tile_word[w];
-                R0n = (uint32_t)tw;
-                Kn = (uint32_t)(tw >> 32);
-            } else {
-                const uint64_t g = d.ent0 + (uint64_t)w * WT;
-#pragma unroll
-                for (int p = 0; p < WPASS; ++p) av[p] = __builtin_nontemporal_load((const dbl2 *)(vals + g + p * (WAVE * 2) + lane * 2));
-                cw = __builtin_nontemporal_load((const u32x4 *)(cid + g + lane * EPL));
-                R0n = (uint32_t)d.tile_word[w];
-            }
-        };
-        // Which wave walks which range is free (a range's sums do not depend on it).  Raw slices: r = wave, wave + 16, ...
-        // Packed slices of a big plan: G = 2 consecutive ranges per wave and turn, i.e. 8 records = 34 KiB in a row — with
-        // 4 (17 KiB) the packed kernel ran at 750 us in one SpMV and 925 us in the next beside the gather kernels, 901 us on
-        // average against 823 us raw, although ALONE it takes 569 against 641 us; with 8 in a row 804 us (profiles/r29a).
-        constexpr uint32_t G = PACKED ? (uint32_t)PACK : 1u;
-        uint32_t r = wave * G;                                           // current range
-        uint32_t t = r * run;                                            // current tile, relative to the segment
-        if (t < n) request(seg.tile0 + t);                               // the first tile is requested before the barrier
-        __syncthreads();                                                 // xs complete
-        if constexpr (DEVTOOLS) {
-            if (prof && threadIdx.x == 0 && s == s0) prof[3 * blockIdx.x + 1] = (unsigned long long)wall_clock64();
-        }
-        double open = 0.0;
-        bool mine = false;
-        uint32_t last = 0;
-        Pending pd;
-        SPRS_GLOBAL_AS double *pd_slot = (SPRS_GLOBAL_AS double *)carry;
-        while (t < n) {                                                  // wave-uniform
-            const uint32_t w = seg.tile0 + t;
-            const uint64_t base = (uint64_t)w * WT;
-            const uint32_t cnt = d.nnz - base < (uint64_t)WT ? (uint32_t)(d.nnz - base) : (uint32_t)WT;
-            double pr[EPL], xv[EPL];
-            uint32_t fb = 0;
-            // all eight LDS gathers are issued before the first product needs one (a conditional read per entry compiles to
-            // eight branches with a full LDS wait each)
-#pragma unroll
-            for (int p = 0; p < WPASS; ++p) {
-                const uint32_t c2 = cw[p];
-                xv[2 * p] = xs[c2 & (XT - 1)];
-                xv[2 * p + 1] = xs[(c2 >> 16) & (XT - 1)];
-                fb |= ((c2 >> 15) & 1u) << (2 * p);
-                fb |= ((c2 >> 31) & 1u) << (2 * p + 1);
-            }
-            if constexpr (PACKED) {
-                // the value of entry q: low word as stored; high word = the key that id bit 14 selects, over the 20-bit field
-                const uint32_t m[5] = {pmh[0], pmh[1], pmh[2], pmh[3], pmh4};
-                const uint32_t ks = (uint32_t)__builtin_amdgcn_readfirstlane((int)Kn);   // wave-uniform: the tile's word
-                const uint32_t k0 = ks << 20, k1 = (ks >> 12) << 20;
-#pragma unroll
-                for (int q = 0; q < EPL; ++q) {
-                    const uint32_t sel = cw[q / 2] & (KEY_SEL << (16 * (q & 1)));
-                    const uint32_t hi = pk_field(m, q) | (sel ? k1 : k0);
-                    pr[q] = __hiloint2double((int)hi, (int)plo[q / 4][q % 4]) * xv[q];
-                }
-            } else {
-#pragma unroll
-                for (int p = 0; p < WPASS; ++p) {
-                    pr[2 * p] = av[p][0] * xv[2 * p];
-                    pr[2 * p + 1] = av[p][1] * xv[2 * p + 1];
-                }
-            }
-            if (cnt < (uint32_t)WT) {                                    // last tile of a slice (wave-uniform): the padding (value 0, id 0) must not
-#pragma unroll                                                           // turn an infinite x[first label] into a NaN
-                for (int q = 0; q < EPL; ++q) pr[q] = lane * EPL + q < cnt ? pr[q] : 0.0;
-            }
-            // tile_row[w] is the LAST load of the tile's request: taken here, in front of the flush, so that its wait covers only
-            // loads issued a whole tile ago.  (Until round 5 the compiler sank this copy behind the flush's stores, and on gfx950
-            // loads and stores count on ONE in-order vmcnt: the wave then waited for the acknowledgement of its stores with no
-            // load in flight, once per tile — `s_waitcnt vmcnt(0)` between the flush and the next request in the ISA; the probe
-            // scripts/probes/stream_store.hip prices such a drain at 1.0 - 2.3 us per tile.)
-            uint32_t R0 = R0n;
-#ifndef SPRS_HIP_EMU
-            asm volatile("" : "+v"(R0)::"memory");
-#endif
-            // the tile after this one: the next of the range, or the first of the wave's next range
-            const uint32_t rend = (r + 1) * run < n ? (r + 1) * run : n;
-            const bool range_ends = t + 1 >= rend;
-            const uint32_t rn = G > 1u && (r % G) + 1u < G ? r + 1u : r + 1u + (uint32_t)(HOT_WAVES - 1) * G;   // the wave's next range
-            const uint32_t tn = range_ends ? rn * run : t + 1;
-            SPRS_GLOBAL_AS double *cslot = (SPRS_GLOBAL_AS double *)carry + seg.range0 + r;
-            auto out = [&](uint32_t row, double v) {
-                if (DEVTOOLS && (dbg & 1u)) return;                      // no stores of the row sums
-                __builtin_nontemporal_store(v, &d.out[row]);              // read again by the reduction, a few GB of traffic later
-
-            };
-            if (pd.cnt) band_flush(pd, lane, pd_slot, stage, out);        // the previous tile's sums, before this tile's loads are asked for
-            if (tn < n) request(seg.tile0 + tn);                         // streams while this tile is summed
-            if constexpr (DEVTOOLS) {                                    // timing experiments (option spmv_band_debug): WRONG results
-                if (dbg & 2u) fb &= 0x01u;                               // at most one row start per lane
-                if (dbg & 4u) fb = 0;                                    // no row starts at all
-            }
-            if (DEVTOOLS && (dbg & 8u)) {
-                band_tile_sums<false>(pr, fb, lane, R0, open, mine, last, cslot, stage, pd, out);
-            } else {
-                band_tile_sums<true>(pr, fb, lane, R0, open, mine, last, cslot, stage, pd, out);
-                pd_slot = cslot;
-            }
-            if (range_ends) {
-                if (lane == 0) {
-                    if (mine) d.out[last] = open;                        // the row still open at the end of the range: its sum so far
-                    else *cslot = open;                                  // no row starts in the whole range: all of it belongs to an earlier row
-                }
-                open = 0.0;
-                mine = false;
-                r = rn;
-            }
-            t = tn;
-        }
-        if (pd.cnt) band_flush(pd, lane, pd_slot, stage, [&](uint32_t row, double v) {
-            if (DEVTOOLS && (dbg & 1u)) return;
-            d.out[row] = v;
-        });
-    }
-    if constexpr (DEVTOOLS) {
-        if (prof) {
-            __syncthreads();
-            if (threadIdx.x == 0) prof[3 * blockIdx.x + 2] = (unsigned long long)wall_clock64();
-        }
-    }
-}
-
+// The kernel exists once per scalar: its text is spmv_band_twins.inc, compiled for double as band_hot_kernel<XT_LOG2, PACK> and for
+// float as band_hot_kernel_f32<XT_LOG2, 0> (raw slices only, up to 32768 labels — the local id then takes bits 0 .. 14, KEY_SEL's bit
+// included — and the x tile and the windows are floats).  Not a template on the scalar over a shared __device__ body: the f64
+// kernel's instructions are held to what they were (scripts/device_code_diff.py), and a body inlined into a wrapper compiles to
+// other ones.
 // ---------------------------------------------------------------------------------------------
 // cold pieces and the short rows: x gathered through L1 / L2 from xp, 32-bit labels.
 //
@@ -495,32 +366,34 @@ __global__ __launch_bounds__(HOT_THREADS) SPRS_HOT_WAVES_ATTR void band_hot_kern
 // ---------------------------------------------------------------------------------------------
 // 8 waves per SIMD (64 VGPRs, 20 bytes of scratch): the gathers live on the number of waves in flight, and two such waves fit
 // beside each wave of the hot kernel.  (Non-temporal and device-scope gathers were measured slower in round 2.)
-struct ColdArgs {
+template <typename T>
+struct ColdArgsT {
     const BandPiece *pieces;
     const ColdGroup *groups;
     uint32_t ngroups;
-    const double *vals;
+    const T *vals;
     const uint32_t *cid;
-    const double *xp;
-    double *y, *carry;
+    const T *xp;
+    T *y, *carry;
     uint32_t block0, ct;
     uint32_t direct;             // 1: the launch walks ONE piece, given by value below (no look-up of group and piece in memory:
     BandPiece piece;             //    two dependent round trips less in front of the first tile — the short rows of a small plan)
 };
+struct ColdArgs : ColdArgsT<double> {};      // (the f64 kernels keep the argument type, and with it the names, they had before the f32 ones came)
 
-template <bool ACC, bool TOY>
-__device__ __forceinline__ void band_cold_body(const ColdArgs &ca, uint32_t block, double (*stage_s)[STG]) {
+template <bool ACC, bool TOY, typename T>
+__device__ __forceinline__ void band_cold_body(const ColdArgsT<T> &ca, uint32_t block, T (*stage_s)[STG]) {
     constexpr int WPB = CNT / WAVE;
     const BandPiece *__restrict__ pieces = ca.pieces;
     const ColdGroup *__restrict__ groups = ca.groups;
     const uint32_t ngroups = ca.ngroups, ct = ca.ct;
-    const double *__restrict__ vals = ca.vals;
+    const T *__restrict__ vals = ca.vals;
     const uint32_t *__restrict__ cid = ca.cid;
-    const double *__restrict__ xp = ca.xp;
-    double *__restrict__ y = ca.y;
-    double *__restrict__ carry = ca.carry;
+    const T *__restrict__ xp = ca.xp;
+    T *__restrict__ y = ca.y;
+    T *__restrict__ carry = ca.carry;
     const uint32_t tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-    double *stage = stage_s[wave];
+    T *stage = stage_s[wave];
     const uint32_t bid = block + ca.block0;
     uint32_t r;                                                          // range of the piece (= of its segment)
     BandPiece pc;
@@ -536,18 +409,20 @@ __device__ __forceinline__ void band_cold_body(const ColdArgs &ca, uint32_t bloc
         r = (cg.npieces == 1 ? lb : (lb >> 3)) * WPB + wave;
         pc = pieces[pi];
     }
-    band_cold_wave<ACC, TOY>(PieceView(pc), r, ct, vals, cid, xp, y, carry, stage, lane);
+    band_cold_wave<ACC, TOY, T>(PieceView<T>(pc), r, ct, vals, cid, xp, y, carry, stage, lane);
 }
 
 // one wave, one range (ct consecutive tiles) of a gather piece
-template <bool ACC, bool TOY>
-__device__ __forceinline__ void band_cold_wave(const PieceView d, uint32_t r, uint32_t ct, const double *__restrict__ vals,
-                                               const uint32_t *__restrict__ cid, const double *__restrict__ xp, double *__restrict__ y,
-                                               double *__restrict__ carry, double *stage, uint32_t lane) {
+template <bool ACC, bool TOY, typename T>
+__device__ __forceinline__ void band_cold_wave(const PieceView<T> d, uint32_t r, uint32_t ct, const T *__restrict__ vals,
+                                               const uint32_t *__restrict__ cid, const T *__restrict__ xp, T *__restrict__ y,
+                                               T *__restrict__ carry, T *stage, uint32_t lane) {
+    typedef typename BandT<T>::vec vecT;
+    constexpr int VW = BandT<T>::VW, NV = BandT<T>::NV;
     const uint32_t t0 = r * ct;
     if (t0 >= d.ntiles) return;                                          // wave-uniform; no workgroup barrier below
     const uint32_t tend = t0 + ct < d.ntiles ? t0 + ct : d.ntiles;
-    dbl2 av[WPASS];
+    vecT av[NV];
     u32x4 lw[2];
     uint32_t R0n = 0;
     auto request = [&](uint32_t w) {
@@ -555,20 +430,20 @@ __device__ __forceinline__ void band_cold_wave(const PieceView d, uint32_t r, ui
 #pragma unroll
         for (int p = 0; p < 2; ++p) lw[p] = __builtin_nontemporal_load((const u32x4 *)(cid + gpos + p * (WAVE * 4) + lane * 4));
 #pragma unroll
-        for (int p = 0; p < WPASS; ++p) av[p] = __builtin_nontemporal_load((const dbl2 *)(vals + gpos + p * (WAVE * 2) + lane * 2));
+        for (int p = 0; p < NV; ++p) av[p] = __builtin_nontemporal_load((const vecT *)(vals + gpos + p * (WAVE * VW) + lane * VW));
         R0n = d.tile_row[w];
     };
     request(t0);
-    double open = 0.0;
+    T open = 0.0;
     bool mine = false;
     uint32_t last = 0;
-    SPRS_GLOBAL_AS double *cslot = (SPRS_GLOBAL_AS double *)carry + d.range0 + r;
+    SPRS_GLOBAL_AS T *cslot = (SPRS_GLOBAL_AS T *)carry + d.range0 + r;
     // Where a short row's sum goes (rowidx) is known as soon as the tile's first row is: the rows that end in a tile are the compact
     // rows R0 - 1 + o, o = lane + 64 m — requested for m < 4 (256 row ends; R-MAT's short rows: ~195 per tile) beside the gathers
     // instead of one dependent load per flush pass (a short tile was a chain of six round trips, four of them these: 13 us on
     // R-MAT 1M whichever launch it ran in, profiles/r15n).
     uint32_t yr_pre[4] = {0u, 0u, 0u, 0u}, yr_base = 0;
-    auto emit_y = [&](uint32_t row, double v) {
+    auto emit_y = [&](uint32_t row, T v) {
         const uint32_t m = (row - yr_base) >> 6;                         // wave-uniform inside a flush pass; lane 0's last row: whatever
         uint32_t yr;
         if (TOY && m < 4u && ((row - yr_base) & 63u) == lane) yr = m == 0 ? yr_pre[0] : m == 1 ? yr_pre[1] : m == 2 ? yr_pre[2] : yr_pre[3];
@@ -576,11 +451,11 @@ __device__ __forceinline__ void band_cold_wave(const PieceView d, uint32_t r, ui
         if constexpr (ACC) y[yr] = y[yr] + v;                            // every compact row has entries: empty rows are never touched (prod.rs:120-126)
         else y[yr] = v;
     };
-    auto emit_p = [&](uint32_t row, double v) { d.out[row] = v; };
+    auto emit_p = [&](uint32_t row, T v) { d.out[row] = v; };
     for (uint32_t w = t0; w < tend; ++w) {
         const uint64_t base = (uint64_t)w * WT;
         const uint32_t cnt = d.nnz - base < (uint64_t)WT ? (uint32_t)(d.nnz - base) : (uint32_t)WT;
-        double xv[EPL];
+        T xv[EPL];
         uint32_t fb = 0;
 #pragma unroll
         for (int q = 0; q < EPL; ++q) {
@@ -596,12 +471,12 @@ __device__ __forceinline__ void band_cold_wave(const PieceView d, uint32_t r, ui
                 yr_pre[m] = d.rowidx[rr < d.nr ? rr : d.nr - 1u];
             }
         }
-        double pr[EPL];
+        T pr[EPL];
 #pragma unroll
-        for (int q = 0; q < EPL; ++q) pr[q] = av[q / 2][q % 2] * xv[q];
+        for (int q = 0; q < EPL; ++q) pr[q] = av[q / VW][q % VW] * xv[q];
         if (cnt < (uint32_t)WT) {                                        // last tile of the piece (wave-uniform): see band_hot_kernel
 #pragma unroll
-            for (int q = 0; q < EPL; ++q) pr[q] = lane * EPL + q < cnt ? pr[q] : 0.0;
+            for (int q = 0; q < EPL; ++q) pr[q] = lane * EPL + q < cnt ? pr[q] : (T)0.0;
         }
         // (no prefetch of the next tile here: its 24 registers would halve the waves per SIMD, and the gathers live on those)
         Pending pd;
@@ -619,7 +494,12 @@ __device__ __forceinline__ void band_cold_wave(const PieceView d, uint32_t r, ui
 template <bool ACC, bool TOY>
 __global__ __launch_bounds__(CNT, 8) void band_cold_kernel(ColdArgs ca) {
     __shared__ __attribute__((aligned(16))) double stage_s[CNT / WAVE][STG];
-    band_cold_body<ACC, TOY>(ca, blockIdx.x, stage_s);
+    band_cold_body<ACC, TOY, double>(ca, blockIdx.x, stage_s);
+}
+template <bool ACC, bool TOY>
+__global__ __launch_bounds__(CNT, 8) void band_cold_kernel_f32(ColdArgsT<float> ca) {
+    __shared__ __attribute__((aligned(16))) float stage_s[CNT / WAVE][STG];
+    band_cold_body<ACC, TOY, float>(ca, blockIdx.x, stage_s);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -699,14 +579,14 @@ __global__ __launch_bounds__(256) void bp_spill_kernel(const Seg *__restrict__ s
 
 // per SpMV: the heads of a record's ranges are added to the row's sum in range order.  Two launches: the short rows' records
 // (TO_Y: into y, behind the short rows on their stream) and the long rows' (into the partial sums, in front of the reduction).
-template <bool TO_Y>
-__global__ __launch_bounds__(256) void band_carry_kernel(const Spill *__restrict__ spills, uint32_t nspills, const double *__restrict__ carry,
-                                                         double *__restrict__ partial, double *__restrict__ y) {
+template <bool TO_Y, typename T>
+__global__ __launch_bounds__(256) void band_carry_kernel(const Spill *__restrict__ spills, uint32_t nspills, const T *__restrict__ carry,
+                                                         T *__restrict__ partial, T *__restrict__ y) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nspills) return;
     const Spill sp = spills[i];
-    double *dst = (TO_Y ? y : partial) + sp.dst;
-    double acc = *dst;
+    T *dst = (TO_Y ? y : partial) + sp.dst;
+    T acc = *dst;
     for (uint32_t k = 0; k < sp.n; ++k) acc += carry[sp.first + k];
     *dst = acc;
 }
@@ -723,23 +603,28 @@ __global__ __launch_bounds__(256) void band_carry_kernel(const Spill *__restrict
 // gathers of x cost the fabric more lines than the scatter's stores once most columns take part; R-MAT 1M equal.  So: the gather
 // when at most a third of the columns are referenced, the scatter over all columns otherwise.
 // (CLEAR_Y tells the two launches of a big plan apart in a profile: <false> the hot labels, <true> the rest and y)
-template <bool CLEAR_Y>
-__global__ __launch_bounds__(256) void band_gather_kernel(const double *__restrict__ x, const uint32_t *__restrict__ inv, uint32_t l0,
-                                                          uint32_t l1, double *__restrict__ xp, double *__restrict__ y_zero, uint64_t rows) {
+// four consecutive values of xp / y from a 16-byte aligned address on: two stores of doubles, one of floats
+__device__ __forceinline__ void band_store4(double *p, double a0, double a1, double a2, double a3) {
+    *(dbl2 *)p = dbl2{a0, a1};
+    *(dbl2 *)(p + 2) = dbl2{a2, a3};
+}
+__device__ __forceinline__ void band_store4(float *p, float a0, float a1, float a2, float a3) { *(flt4 *)p = flt4{a0, a1, a2, a3}; }
+
+template <bool CLEAR_Y, typename T>
+__global__ __launch_bounds__(256) void band_gather_kernel(const T *__restrict__ x, const uint32_t *__restrict__ inv, uint32_t l0,
+                                                          uint32_t l1, T *__restrict__ xp, T *__restrict__ y_zero, uint64_t rows) {
     const uint64_t t4 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     const uint64_t l = (uint64_t)l0 + t4;
     if (l + 4 <= (uint64_t)l1 && (l0 & 3u) == 0) {
         const u32x4 j = *(const u32x4 *)(inv + l);
-        const double a0 = x[j[0]], a1 = x[j[1]], a2 = x[j[2]], a3 = x[j[3]];
-        *(dbl2 *)(xp + l) = dbl2{a0, a1};
-        *(dbl2 *)(xp + l + 2) = dbl2{a2, a3};
+        const T a0 = x[j[0]], a1 = x[j[1]], a2 = x[j[2]], a3 = x[j[3]];
+        band_store4(xp + l, a0, a1, a2, a3);
     } else {
         for (uint64_t q = l; q < (uint64_t)l1 && q < l + 4; ++q) xp[q] = x[inv[q]];
     }
     if (CLEAR_Y && y_zero) {
         if (t4 + 4 <= rows && ((uintptr_t)y_zero & 15) == 0) {
-            *(dbl2 *)(y_zero + t4) = dbl2{0.0, 0.0};
-            *(dbl2 *)(y_zero + t4 + 2) = dbl2{0.0, 0.0};
+            band_store4(y_zero + t4, (T)0.0, (T)0.0, (T)0.0, (T)0.0);
         } else {
             for (uint64_t r = t4; r < rows && r < t4 + 4; ++r) y_zero[r] = 0.0;
         }
@@ -749,33 +634,7 @@ __global__ __launch_bounds__(256) void band_gather_kernel(const double *__restri
 // The scatter form: xp[label[c]] = x[c] for the labels in [first_label, nref) — the labels below were gathered (hot labels of a big
 // plan); the caller passes nref = every label — and y cleared: four consecutive columns / rows per thread
 // (16-byte loads; one column per thread left this kernel latency-bound beside the hot kernel: 360 us instead of 50, profiles/r05e)
-__global__ __launch_bounds__(256) void band_permute_kernel(const double *__restrict__ x, const uint32_t *__restrict__ perm,
-                                                           uint64_t cols, double *__restrict__ xp, double *__restrict__ y_zero,
-                                                           uint64_t rows, uint32_t first_label, uint32_t nref) {
-    const uint64_t j = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    const uint32_t span = nref - first_label;                            // label in range <=> label - first_label < span
-    if (j + 4 <= cols && (((uintptr_t)x | (uintptr_t)perm) & 15) == 0) {
-        const u32x4 l = *(const u32x4 *)(perm + j);
-        const dbl2 a = *(const dbl2 *)(x + j), b = *(const dbl2 *)(x + j + 2);
-        if (l[0] - first_label < span) xp[l[0]] = a[0];
-        if (l[1] - first_label < span) xp[l[1]] = a[1];
-        if (l[2] - first_label < span) xp[l[2]] = b[0];
-        if (l[3] - first_label < span) xp[l[3]] = b[1];
-    } else {
-        for (uint64_t c = j; c < cols && c < j + 4; ++c) {
-            const uint32_t l = perm[c];
-            if (l - first_label < span) xp[l] = x[c];
-        }
-    }
-    if (y_zero) {
-        if (j + 4 <= rows && ((uintptr_t)y_zero & 15) == 0) {
-            *(dbl2 *)(y_zero + j) = dbl2{0.0, 0.0};
-            *(dbl2 *)(y_zero + j + 2) = dbl2{0.0, 0.0};
-        } else {
-            for (uint64_t r = j; r < rows && r < j + 4; ++r) y_zero[r] = 0.0;
-        }
-    }
-}
+// (the kernel: spmv_band_twins.inc, band_permute_kernel / band_permute_kernel_f32)
 
 // ---------------------------------------------------------------------------------------------
 // y[long_rows[j]] (+)= sum of the row's partials, pieces in ascending order (a fixed order: deterministic).
@@ -806,24 +665,26 @@ __device__ __forceinline__ uint32_t band_mask_rank(uint32_t m_lo, uint32_t m_hi,
 // Round 6 tried TWO lanes per row for small plans (a wave per 32 rows, lane l / l + 32 summing the lower / upper 32 pieces of a
 // chunk, half the dependent groups per wave, twice the waves): R-MAT 1M 21.6 us against 15.4 us alone, 28.6 against 21.7 us
 // inside the tail launch (profiles/r15l) — not a chain of round trips either.)
-struct ReduceArgs {
-    const double *partial;
+template <typename T>
+struct ReduceArgsT {
+    const T *partial;
     const unsigned long long *wmask;
     const uint32_t *wbase, *long_rows;
     const RSpill *rsp;           // the heads of rows that run on from one range into the next (sorted by long row), or null
     const uint32_t *rsp_off;     // nwb + 1: the records of row block wb are rsp[rsp_off[wb]] .. rsp[rsp_off[wb + 1] - 1]
-    const double *carry;
-    double *y;
+    const T *carry;
+    T *y;
     uint32_t n_long, np_pad, nwb;
 };
+struct ReduceArgs : ReduceArgsT<double> {};  // (as ColdArgs: the f64 kernels' argument type)
 
-template <bool ACC>
-__device__ __forceinline__ void band_reduce_body(const ReduceArgs &ra, uint32_t block, uint32_t nblocks) {
-    const double *__restrict__ partial = ra.partial;
+template <bool ACC, typename T>
+__device__ __forceinline__ void band_reduce_body(const ReduceArgsT<T> &ra, uint32_t block, uint32_t nblocks) {
+    const T *__restrict__ partial = ra.partial;
     const unsigned long long *__restrict__ wmask = ra.wmask;
     const uint32_t *__restrict__ wbase = ra.wbase;
     const uint32_t *__restrict__ long_rows = ra.long_rows;
-    double *__restrict__ y = ra.y;
+    T *__restrict__ y = ra.y;
     const uint32_t n_long = ra.n_long, np_pad = ra.np_pad, nwb = ra.nwb;
     const uint32_t lane = threadIdx.x & (WAVE - 1);
     // wave -> row block: block b runs on XCD b % 8 (observed; only speed depends on it): every XCD gets a CONTIGUOUS range
@@ -846,7 +707,7 @@ __device__ __forceinline__ void band_reduce_body(const ReduceArgs &ra, uint32_t 
             se = ra.rsp_off[wb + 1];
         }
         uint32_t h_jl = 0xFFFFFFFFu, h_first = 0, h_n = 0;
-        double h_c = 0.0;
+        T h_c = 0.0;
         if (sb + lane < se) {
             const RSpill rec = ra.rsp[sb + lane];
             h_jl = rec.j & (WAVE - 1);
@@ -854,7 +715,7 @@ __device__ __forceinline__ void band_reduce_body(const ReduceArgs &ra, uint32_t 
             h_n = rec.n;
             h_c = ra.carry[h_first];                                    // n >= 1
         }
-        double s = 0.0;
+        T s = 0.0;
         const unsigned long long *mrow = wmask + (uint64_t)wb * np_pad;
         const uint32_t *brow = wbase + (uint64_t)wb * np_pad;
         unsigned long long mk_n = lane < np_pad ? mrow[lane] : 0ull;     // lane l: the table row of piece l (np_pad is a multiple of 16)
@@ -871,13 +732,13 @@ __device__ __forceinline__ void band_reduce_body(const ReduceArgs &ra, uint32_t 
 #pragma unroll
             for (int kk = 0; kk < WAVE; kk += RU) {
                 if (k0 + kk >= np_pad) break;                            // wave-uniform
-                double v[RU];
+                T v[RU];
 #pragma unroll
                 for (int u = 0; u < RU; ++u) {
                     const uint32_t m_lo = (uint32_t)__builtin_amdgcn_readlane((int)mk_lo, kk + u);
                     const uint32_t m_hi = (uint32_t)__builtin_amdgcn_readlane((int)mk_hi, kk + u);
                     const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)bs, kk + u);
-                    v[u] = band_mask_bit(m_lo, m_hi, lane) ? partial[b + band_mask_rank(m_lo, m_hi, lane)] : 0.0;
+                    v[u] = band_mask_bit(m_lo, m_hi, lane) ? partial[b + band_mask_rank(m_lo, m_hi, lane)] : (T)0.0;
                 }
 #pragma unroll
                 for (int u = 0; u < RU; ++u) s += v[u];              // ascending pieces (absent ones add +0.0)
@@ -902,9 +763,8 @@ __device__ __forceinline__ void band_reduce_body(const ReduceArgs &ra, uint32_t 
             const uint32_t cnt = se - i0 < (uint32_t)WAVE ? se - i0 : (uint32_t)WAVE;
             for (uint32_t t = 0; t < cnt; ++t) {                         // wave-uniform
                 const uint32_t tj = (uint32_t)__builtin_amdgcn_readlane((int)h_jl, (int)t);
-                const int lo = __builtin_amdgcn_readlane(__double2loint(h_c), (int)t);
-                const int hi = __builtin_amdgcn_readlane(__double2hiint(h_c), (int)t);
-                if (lane == tj) s += __hiloint2double(hi, lo);
+                const T hv = band_read_lane(h_c, (int)t);
+                if (lane == tj) s += hv;
             }
         }
         if (j < n_long) {
@@ -916,7 +776,11 @@ __device__ __forceinline__ void band_reduce_body(const ReduceArgs &ra, uint32_t 
 
 template <bool ACC>
 __global__ __launch_bounds__(256) void band_reduce_kernel(ReduceArgs ra) {
-    band_reduce_body<ACC>(ra, blockIdx.x, gridDim.x);
+    band_reduce_body<ACC, double>(ra, blockIdx.x, gridDim.x);
+}
+template <bool ACC>
+__global__ __launch_bounds__(256) void band_reduce_kernel_f32(ReduceArgsT<float> ra) {
+    band_reduce_body<ACC, float>(ra, blockIdx.x, gridDim.x);
 }
 
 // SMALL PLANS (a few tiles per wave: R-MAT 1M, a rank's block of an 8-way cut): every launch of such an SpMV is a few
@@ -928,9 +792,27 @@ __global__ __launch_bounds__(256) void band_reduce_kernel(ReduceArgs ra) {
 template <bool ACC>
 __global__ __launch_bounds__(CNT, 8) void band_tail_kernel(ReduceArgs ra, uint32_t reduce_blocks, ColdArgs ca) {
     __shared__ __attribute__((aligned(16))) double stage_s[CNT / WAVE][STG];
-    if (blockIdx.x < reduce_blocks) band_reduce_body<ACC>(ra, blockIdx.x, reduce_blocks);
-    else band_cold_body<ACC, true>(ca, blockIdx.x - reduce_blocks, stage_s);
+    if (blockIdx.x < reduce_blocks) band_reduce_body<ACC, double>(ra, blockIdx.x, reduce_blocks);
+    else band_cold_body<ACC, true, double>(ca, blockIdx.x - reduce_blocks, stage_s);
 }
+template <bool ACC>
+__global__ __launch_bounds__(CNT, 8) void band_tail_kernel_f32(ReduceArgsT<float> ra, uint32_t reduce_blocks, ColdArgsT<float> ca) {
+    __shared__ __attribute__((aligned(16))) float stage_s[CNT / WAVE][STG];
+    if (blockIdx.x < reduce_blocks) band_reduce_body<ACC, float>(ra, blockIdx.x, reduce_blocks);
+    else band_cold_body<ACC, true, float>(ca, blockIdx.x - reduce_blocks, stage_s);
+}
+
+// ---- the kernels that exist once per scalar under names of their own -------------------------------------------------------
+#define BAND_T double
+#define BAND_KERNEL(name) name
+#include "spmv_band_twins.inc"
+#undef BAND_T
+#undef BAND_KERNEL
+#define BAND_T float
+#define BAND_KERNEL(name) name##_f32
+#include "spmv_band_twins.inc"
+#undef BAND_T
+#undef BAND_KERNEL
 
 }  // namespace
 }  // namespace sprs_hip

@@ -18,8 +18,11 @@
 // of the last one, LONG_SEG, SEG_CHUNK = 2048 staged row boundaries, and tile_of_block's runs of tiles per XCD.
 //
 // THE PLAN is the tile index over the handle's own arrays (build_tile_rows) and one carry array per stream, built at the
-// first multiply or by sprs_hip_csmat_f32_prepare.  There is NO banded plan and NO XCD-sliced plan for f32 in this file:
-// options spmv_band / spmv_xcs do not apply to f32 handles; spmv_tile does.
+// first multiply or by sprs_hip_csmat_f32_prepare — or the BANDED plan of spmv_band.hip with float values, x, partial sums and
+// carries (hot slices of up to 32768 labels: option spmv_f32_band_tile).  The policy is the f64 handle's (spmv.hip): a forced plan
+// (spmv_band = 1) at once; under auto the first multiply on the tile plan and the banded plan from the second one on, or from
+// sprs_hip_csmat_f32_prepare, for matrices of at least 2^22 entries whose x takes 4 MiB (cols * 4) and whose long rows hold half
+// the entries; spmv_band = 2 keeps the tile plan.  There is no XCD-sliced plan for f32: spmv_xcs does not apply.
 #pragma once
 #include "spmv_shared.hpp"
 
@@ -296,27 +299,63 @@ static bool f32_capturing(hipStream_t stream) {
 static bool f32_capturing(hipStream_t) { return false; }
 #endif
 
-// (a->mu held) the tile index for the current value of spmv_tile and `stream`'s carry array.  Building either allocates and
-// synchronises, which a stream that is being captured into a hipGraph cannot do.
+// the options an f32 plan depends on: a handle rebuilds its plan when one of them changes
+static uint64_t f32_plan_signature(const Options &o) {
+    const int64_t v[] = {o.spmv_tile, o.spmv_band, o.spmv_band_hot, o.spmv_f32_band_tile, o.spmv_band_phases, o.spmv_band_split, o.spmv_band_rounds,
+                         o.spmv_band_cold_tiles, o.spmv_band_hot_run, o.spmv_band_share, o.spmv_band_balance};
+    uint64_t h = 0xcbf29ce484222325ull;
+    for (int64_t x : v) h = (h ^ (uint64_t)x) * 0x100000001b3ull;
+    return h | 1ull;
+}
+
+// Does the automatic rule (spmv_band = 0) hand big power-law f32 matrices to the banded plan?  Decided by measurement
+// (DESIGN 4.16): it stays on only while the f32 banded plan beats the f32 tile plan by more than the spread of the runs.
+constexpr bool F32_BAND_AUTO = true;
+
+// (a->mu held) the plan for the current option values — the banded plan or the tile index — and, for the tile plan, `stream`'s
+// carry array.  Building either allocates and synchronises, which a stream that is being captured into a hipGraph cannot do.
+// light: the handle's first multiply — the banded plan is not built yet unless the options force it; pl.light then says that the
+// next multiply should come back here (build_plan, spmv.hip).
 template <typename PTR>
-static int32_t f32_plan(sprs_hip_csmat_f32 *a, hipStream_t stream, float **carry) {
+static int32_t f32_plan(sprs_hip_csmat_f32 *a, hipStream_t stream, float **carry, bool light) {
     SpmvPlanF32 &pl = a->plan;
-    if (!pl.built || pl.opt_tile != options().spmv_tile) {
+    const Options &o = options();
+    if (!pl.built || pl.opt_sig != f32_plan_signature(o) || (pl.light && !light)) {
         if (f32_capturing(stream))
             SPRS_FAIL(SPRS_HIP_INVALID_ARG, "SpMV on a capturing stream needs the handle's plan to exist: call sprs_hip_csmat_f32_prepare first");
         pl = SpmvPlanF32();
-        pl.opt_tile = options().spmv_tile;
-        pl.tile = f32_tile_for(a);
-        pl.ntiles = (a->nnz + pl.tile - 1) / pl.tile;
-        if (pl.ntiles > 0x7fffffffull) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "too many tiles for one launch");
-        SPRS_TRY_HIP(alloc_block(pl.blocks, pl.tile_row, (pl.ntiles + 1) * sizeof(uint64_t)));
-        const uint64_t n = pl.ntiles + 1;
-        hipLaunchKernelGGL(build_tile_rows<PTR>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const PTR *)a->indptr, a->rows,
-                           pl.ntiles, pl.tile, pl.tile_row);
-        SPRS_TRY_HIP(hipGetLastError());
-        SPRS_TRY_HIP(hipStreamSynchronize(stream));   // plan complete and visible to every stream
+        pl.opt_sig = f32_plan_signature(o);
+        // auto: the f64 rule for 4-byte x — x larger than one L2 (4 MiB) and a matrix big enough to amortise the copy
+        bool want_band = o.spmv_band == 1 || (F32_BAND_AUTO && o.spmv_band == 0 && a->cols * 4 >= (4ull << 20) && a->nnz >= (1ull << 22));
+        if (light && want_band && o.spmv_band != 1) {
+            pl.light = true;
+            want_band = false;
+        }
+        if (want_band) {
+            const int32_t st = band_build(a, stream, pl.band);
+            // auto mode: a matrix the banded plan cannot be built for (its temporaries did not fit) keeps the tile plan;
+            // an explicit spmv_band = 1 reports the failure
+            if (st == SPRS_HIP_OUT_OF_MEMORY && o.spmv_band == 0) {
+                (void)hipGetLastError();
+                clear_error();
+            } else if (st != SPRS_HIP_OK) {
+                return st;
+            }
+        }
+        if (!pl.band) {
+            pl.tile = f32_tile_for(a);
+            pl.ntiles = (a->nnz + pl.tile - 1) / pl.tile;
+            if (pl.ntiles > 0x7fffffffull) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "too many tiles for one launch");
+            SPRS_TRY_HIP(alloc_block(pl.blocks, pl.tile_row, (pl.ntiles + 1) * sizeof(uint64_t)));
+            const uint64_t n = pl.ntiles + 1;
+            hipLaunchKernelGGL(build_tile_rows<PTR>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const PTR *)a->indptr, a->rows,
+                               pl.ntiles, pl.tile, pl.tile_row);
+            SPRS_TRY_HIP(hipGetLastError());
+            SPRS_TRY_HIP(hipStreamSynchronize(stream));   // plan complete and visible to every stream
+        }
         pl.built = true;
     }
+    if (pl.band) return SPRS_HIP_OK;                      // (its per-stream scratch: band_spmv / band_prepare_stream)
     auto it = pl.carry.find((void *)stream);
     if (it == pl.carry.end()) {
         if (f32_capturing(stream))
@@ -347,7 +386,9 @@ int32_t spmv_f32_prepare(sprs_hip_csmat_f32 *a, hipStream_t stream) {
     a->prepared = true;
     if (a->rows == 0 || a->nnz == 0) return SPRS_HIP_OK;
     float *carry = nullptr;
-    return dispatch_width(a->iptr_bytes, [&](auto p) { return f32_plan<typename decltype(p)::type>(a, stream, &carry); });
+    SPRS_TRY(dispatch_width(a->iptr_bytes, [&](auto p) { return f32_plan<typename decltype(p)::type>(a, stream, &carry, false); }));
+    if (a->plan.band) return band_prepare_stream(a, a->plan.band.get(), stream);
+    return SPRS_HIP_OK;
 }
 
 int32_t spmv_f32(sprs_hip_csmat_f32 *a, const float *x, float *y, bool accumulate, hipStream_t stream) {
@@ -363,8 +404,11 @@ int32_t spmv_f32(sprs_hip_csmat_f32 *a, const float *x, float *y, bool accumulat
         using IDX = typename decltype(i)::type;
         using PTR = typename decltype(p)::type;
         float *carry = nullptr;
-        SPRS_TRY(f32_plan<PTR>(a, stream, &carry));
+        const bool defer = options().spmv_plan_defer != 0 && a->spmv_calls == 0 && !a->prepared;
+        SPRS_TRY(f32_plan<PTR>(a, stream, &carry, defer));
+        ++a->spmv_calls;
         const SpmvPlanF32 &pl = a->plan;
+        if (pl.band) return band_spmv(a, pl.band.get(), x, y, accumulate, stream);
         const TileArgsF32 ta{a->indptr, a->indices, a->data, pl.tile_row, carry, y, a->nnz, pl.ntiles};
         if (pl.tile == 2048) return f32_launch<IDX, PTR, 2048>(ta, x, accumulate, stream);
         return f32_launch<IDX, PTR, 4096>(ta, x, accumulate, stream);

@@ -434,7 +434,7 @@ class DeviceCsMatF32(_DeviceCsMatBase):
     `&A * &x` and the two mul_acc forms with DeviceVecF32, `&A * &B` and the four mulacc_dense forms with prod.DeviceMatF32,
     prod.dense_dot_csmat (prod.py), `&A * &B` with another DeviceCsMatF32 and the smmp functions (smmp.py), BiCGSTAB
     (linalg.py); `to_f64()` reaches every other
-    operation.  Index arrays are 4 or 8 bytes wide (no 2-byte ones)."""
+    operation.  The SpMV runs on the nnz-tile plan or on the banded plan (`spmv_plan_info()`, option spmv_f32_band_tile).  Index arrays are 4 or 8 bytes wide (no 2-byte ones)."""
     _dtype, _container, _suffix = np.float32, "sprs_hip_csmat_f32_", "f32"
 
     @classmethod
@@ -443,6 +443,13 @@ class DeviceCsMatF32(_DeviceCsMatBase):
         if data_t.element_size() != 4 or not data_t.is_floating_point():
             raise TypeError("float32 data expected")
         return cls._wrap_torch(shape, indptr_t, indices_t, data_t, storage)
+
+    def spmv_plan_info(self):
+        """-> (kind, plan_bytes): 0 none yet, 1 nnz tiles, 3 banded copy (hot columns from LDS, float throughout); a CSC handle
+        reports the plan of its cached CSR form."""
+        kind, nbytes = C.c_int32(), C.c_uint64()
+        check(lib.sprs_hip_csmat_f32_spmv_plan_info(self._h, C.byref(kind), C.byref(nbytes)))
+        return kind.value, nbytes.value
 
     def to_f64(self, stream=None):
         """CsMat::map(|&v| v as f64): exact."""
