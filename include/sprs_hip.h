@@ -1095,6 +1095,27 @@ int32_t sprs_hip_spgemm_plan_numeric_f32(sprs_hip_spgemm_plan *plan, const sprs_
 int32_t sprs_hip_csmat_mul_csmat_f32(const sprs_hip_csmat_f32 *lhs, const sprs_hip_csmat_f32 *rhs,
                                      sprs_hip_csmat_f32 **out);
 
+/* ---- f32 triangular solves, Gauss-Seidel and diag_solve -----------------------------------------------------------------
+ * The recurrences of the reference are generic over the scalar (trisolve.rs:30-262 over N: Num; the heat example's
+ * gauss_seidel and linalg::diag_solve alike).  The three entries below are the f32 twins of sprs_hip_trisolve_f64,
+ * sprs_hip_gauss_seidel_f64 and sprs_hip_diag_solve_f64: the same argument order, checks, statuses, texts and info structs,
+ * on a sprs_hip_csmat_f32 handle and arrays of n floats.  Every product, every subtraction / addition and the division are
+ * rounded to f32 (multiply and add unfused, IEEE division, subnormals kept), in the reference's entry order: the solutions
+ * and the iterates are the reference's f32 bits — an f64 solve rounded at the end is NOT that.  The level plans are the f64
+ * ones (they read structure only), kept in the f32 handle and dropped by _refresh / _free; a CSC handle is solved on its
+ * cached CSR form.  On the device a value is handed from row to row as one 4-byte word that is both value and "ready".
+ * Singular: a stored diagonal == 0.0f (-0.0f counts, NaN does not) or one that is not stored, reported as for f64.
+ * Gauss-Seidel: eps is an f32 value that TRAVELS AS double and is narrowed by a plain cast; the convergence scalar is
+ * sqrt(sum_i ((A x)_i - rhs_i)) in f32 — A x by sprs_hip_spmv_f32 on the handle's own plan, then a fixed tree sum — and
+ * info->error holds it widened exactly.  Option gauss_seidel_chain > 1 (the band schedule) is f64-only: an f32 sweep with it
+ * set returns SPRS_HIP_INVALID_ARG.  There is no f32 LDL^T and no f32 sparse-rhs solve. */
+int32_t sprs_hip_trisolve_f32(sprs_hip_csmat_f32 *a, int32_t uplo, float *x_dev, uint64_t n,
+                              sprs_hip_trisolve_info *info, void *stream);
+int32_t sprs_hip_gauss_seidel_f32(sprs_hip_csmat_f32 *a, float *x_dev, const float *rhs_dev, uint64_t n,
+                                  uint64_t max_iter, double eps, sprs_hip_gauss_seidel_info *info,
+                                  void *stream);
+int32_t sprs_hip_diag_solve_f32(const float *d_dev, float *x_dev, uint64_t n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1391,6 +1391,45 @@ private:
     DeviceVecF32 x_;
     sprs_hip_bicgstab_info info_{};
 };
+
+// gauss_seidel::<f32> of the heat example, the four dense-rhs triangular solves and diag_solve for N = f32: overloads of the f64
+// functions above on DeviceCsMatF32 / DeviceVecF32 (sprs_hip_gauss_seidel_f32, sprs_hip_trisolve_f32, sprs_hip_diag_solve_f32).
+// Iterates and solutions are the reference's f32 bits; GaussSeidelResult::error holds the f32 scalar widened.
+inline GaussSeidelResult gauss_seidel(const DeviceCsMatF32 &mat, DeviceVecF32 &x, const DeviceVecF32 &rhs, uint64_t max_iter, float eps) {
+    if (x.dim() != rhs.dim()) throw Error(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    sprs_hip_gauss_seidel_info info{};
+    check(sprs_hip_gauss_seidel_f32(const_cast<sprs_hip_csmat_f32 *>(mat.handle()), x.ptr(), rhs.ptr(), x.dim(), max_iter, (double)eps,
+                                    &info, nullptr));
+    return GaussSeidelResult{info.converged != 0, info.iterations, info.error, info.levels};
+}
+namespace detail {
+inline TriSolveResult trisolve(const DeviceCsMatF32 &mat, DeviceVecF32 &rhs, bool csr, int32_t uplo) {
+    if (mat.rows() != mat.cols()) throw Error(SPRS_HIP_DIM_MISMATCH, "Non square matrix passed to solver");
+    if (mat.cols() != rhs.dim()) throw Error(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    if (mat.is_csr() != csr) throw Error(SPRS_HIP_STORAGE_MISMATCH, "Storage mismatch");
+    sprs_hip_trisolve_info info{};
+    const int32_t status = sprs_hip_trisolve_f32(const_cast<sprs_hip_csmat_f32 *>(mat.handle()), uplo, rhs.ptr(), rhs.dim(), &info, nullptr);
+    if (status == SPRS_HIP_SINGULAR_MATRIX) throw SingularMatrix(sprs_hip_last_error(), info.singular_index, info.singular_reason);
+    check(status);
+    return TriSolveResult{info.levels};
+}
+}  // namespace detail
+inline TriSolveResult lsolve_csr_dense_rhs(const DeviceCsMatF32 &lower_tri_mat, DeviceVecF32 &rhs) {
+    return detail::trisolve(lower_tri_mat, rhs, true, SPRS_HIP_LOWER);
+}
+inline TriSolveResult lsolve_csc_dense_rhs(const DeviceCsMatF32 &lower_tri_mat, DeviceVecF32 &rhs) {
+    return detail::trisolve(lower_tri_mat, rhs, false, SPRS_HIP_LOWER);
+}
+inline TriSolveResult usolve_csc_dense_rhs(const DeviceCsMatF32 &upper_tri_mat, DeviceVecF32 &rhs) {
+    return detail::trisolve(upper_tri_mat, rhs, false, SPRS_HIP_UPPER);
+}
+inline TriSolveResult usolve_csr_dense_rhs(const DeviceCsMatF32 &upper_tri_mat, DeviceVecF32 &rhs) {
+    return detail::trisolve(upper_tri_mat, rhs, true, SPRS_HIP_UPPER);
+}
+inline void diag_solve(const DeviceVecF32 &d, DeviceVecF32 &x, void *stream = nullptr) {
+    if (d.dim() != x.dim()) throw Error(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    check(sprs_hip_diag_solve_f32(d.ptr(), x.ptr(), x.dim(), stream));
+}
 }  // namespace linalg
 
 }  // namespace sprs_hip

@@ -410,6 +410,11 @@ extern "C" {
         a: *mut sprs_hip_csmat_f32, x0_dev: *const f32, b_dev: *const f32, n: u64, tol: f64, max_iter: u64, soft_restart_threshold: f64,
         x_dev: *mut f32, info: *mut sprs_hip_bicgstab_info, stream: *mut c_void,
     ) -> i32;
+    pub fn sprs_hip_trisolve_f32(a: *mut sprs_hip_csmat_f32, uplo: i32, x_dev: *mut f32, n: u64,
+                                 info: *mut sprs_hip_trisolve_info, stream: *mut c_void) -> i32;
+    pub fn sprs_hip_gauss_seidel_f32(a: *mut sprs_hip_csmat_f32, x_dev: *mut f32, rhs_dev: *const f32, n: u64, max_iter: u64,
+                                     eps: f64, info: *mut sprs_hip_gauss_seidel_info, stream: *mut c_void) -> i32;
+    pub fn sprs_hip_diag_solve_f32(d_dev: *const f32, x_dev: *mut f32, n: u64, stream: *mut c_void) -> i32;
     pub fn sprs_hip_spmm_rowmaj_f32(
         a: *const sprs_hip_csmat_f32, rhs_dev: *const f32, rhs_rows: u64, k: u64, ld_rhs: u64,
         out_dev: *mut f32, out_rows: u64, ld_out: u64, accumulate: i32, stream: *mut c_void,

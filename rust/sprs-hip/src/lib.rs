@@ -1546,7 +1546,7 @@ pub mod construct {
 }
 
 /// Single precision: `CsMat<f32>` on the device, `&A * &x`, the dense products (`&A * &M`, `M.dot(&A)`, the four `mulacc_dense`
-/// functions) and `BiCGSTAB::<f32>` — what the reference instantiates for f32 on
+/// functions), `BiCGSTAB::<f32>`, the four dense-rhs triangular solves, `gauss_seidel` and `diag_solve` — what the reference instantiates for f32 on
 /// the product path (bicgstab.rs:304-305; MulAcc, mul_acc.rs:17-31).  Types of their own over a handle type of its own: the
 /// compiler rejects a product of mixed precision.  Every other operation is reached through `to_f64` / `from_f64`, on the device.
 pub mod single {
@@ -1858,5 +1858,69 @@ pub mod single {
         pub fn err(&self) -> f32 { self.info.err as f32 }
         pub fn rho(&self) -> f32 { self.info.rho as f32 }
         pub fn x(&self) -> &DeviceVecF32 { &self.x }
+    }
+
+    /// `gauss_seidel::<f32>` of the reference's heat example (examples/heat.rs:103-139): every iterate in the reference's f32
+    /// bits; `Ok((iterations, error))` / `Err(error)` like the reference.
+    pub fn gauss_seidel(mat: &DeviceCsMatF32, x: &mut DeviceVecF32, rhs: &DeviceVecF32, max_iter: usize, eps: f32)
+        -> Result<(usize, f32), f32> {
+        assert_eq!(x.len, rhs.len, "Dimension mismatch");
+        let mut info = sys::sprs_hip_gauss_seidel_info::default();
+        unsafe {
+            check(sys::sprs_hip_gauss_seidel_f32(mat.h, x.ptr, rhs.ptr, x.len as u64, max_iter as u64, eps as f64, &mut info,
+                                                 std::ptr::null_mut()));
+        }
+        if info.converged != 0 { Ok((info.iterations as usize, info.error as f32)) } else { Err(info.error as f32) }
+    }
+
+    /// The four dense-rhs solves of `sprs::linalg::trisolve` for N = f32, in place on a device-resident `rhs`: the same panics
+    /// and the same `Err(LinalgError::SingularMatrix)` as the f64 twins, solutions in the reference's f32 bits.
+    fn trisolve(mat: &DeviceCsMatF32, rhs: &mut DeviceVecF32, csr: bool, uplo: i32, csr_reason: &'static str)
+        -> Result<(), sprs::errors::LinalgError> {
+        let (rows, cols, _, _, _, st) = mat.info();
+        assert_eq!(cols, rows, "Non square matrix passed to solver");
+        assert_eq!(cols as usize, rhs.len, "Dimension mismatch");
+        assert!((st == sys::SPRS_HIP_CSR) == csr, "Storage mismatch");
+        let mut info = sys::sprs_hip_trisolve_info::default();
+        let status = unsafe { sys::sprs_hip_trisolve_f32(mat.h, uplo, rhs.ptr, rhs.len as u64, &mut info, std::ptr::null_mut()) };
+        if status == sys::SPRS_HIP_SINGULAR_MATRIX {
+            let reason = match (csr, info.singular_reason) {
+                (true, _) => csr_reason,
+                (false, 2) => "diagonal element is a structural 0",
+                (false, _) => "diagonal element is a numeric 0",
+            };
+            return Err(sprs::errors::LinalgError::SingularMatrix(sprs::errors::SingularMatrixInfo {
+                index: info.singular_index as usize,
+                reason,
+            }));
+        }
+        check(status);
+        Ok(())
+    }
+
+    /// `lsolve_csr_dense_rhs::<f32>` (trisolve.rs:30-73)
+    pub fn lsolve_csr_dense_rhs(lower_tri_mat: &DeviceCsMatF32, rhs: &mut DeviceVecF32) -> Result<(), sprs::errors::LinalgError> {
+        trisolve(lower_tri_mat, rhs, true, sys::SPRS_HIP_LOWER, "diagonal element is 0")
+    }
+
+    /// `lsolve_csc_dense_rhs::<f32>` (trisolve.rs:85-149)
+    pub fn lsolve_csc_dense_rhs(lower_tri_mat: &DeviceCsMatF32, rhs: &mut DeviceVecF32) -> Result<(), sprs::errors::LinalgError> {
+        trisolve(lower_tri_mat, rhs, false, sys::SPRS_HIP_LOWER, "")
+    }
+
+    /// `usolve_csc_dense_rhs::<f32>` (trisolve.rs:161-210)
+    pub fn usolve_csc_dense_rhs(upper_tri_mat: &DeviceCsMatF32, rhs: &mut DeviceVecF32) -> Result<(), sprs::errors::LinalgError> {
+        trisolve(upper_tri_mat, rhs, false, sys::SPRS_HIP_UPPER, "")
+    }
+
+    /// `usolve_csr_dense_rhs::<f32>` (trisolve.rs:219-262)
+    pub fn usolve_csr_dense_rhs(upper_tri_mat: &DeviceCsMatF32, rhs: &mut DeviceVecF32) -> Result<(), sprs::errors::LinalgError> {
+        trisolve(upper_tri_mat, rhs, true, sys::SPRS_HIP_UPPER, "diagonal element is a numeric 0")
+    }
+
+    /// `linalg::diag_solve::<f32>` (sprs/src/sparse/linalg.rs:17-29): `x[i] /= diag[i]`
+    pub fn diag_solve(diag: &DeviceVecF32, x: &mut DeviceVecF32) {
+        assert_eq!(diag.len, x.len);
+        unsafe { check(sys::sprs_hip_diag_solve_f32(diag.ptr as *const f32, x.ptr, x.len as u64, std::ptr::null_mut())) };
     }
 }

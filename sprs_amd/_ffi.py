@@ -185,6 +185,9 @@ SIGNATURES = {
     "sprs_hip_mul_acc_mat_vec_csc_f32": (i32, [vp, vp, u64, vp, u64, vp]),
     "sprs_hip_csmat_mul_vec_f32": (i32, [vp, vp, u64, vp, u64, vp]),
     "sprs_hip_bicgstab_f32": (i32, [vp, vp, vp, u64, C.c_double, u64, C.c_double, vp, vp, vp]),
+    "sprs_hip_trisolve_f32": (i32, [vp, i32, vp, u64, vp, vp]),
+    "sprs_hip_gauss_seidel_f32": (i32, [vp, vp, vp, u64, u64, C.c_double, vp, vp]),
+    "sprs_hip_diag_solve_f32": (i32, [vp, vp, u64, vp]),
     "sprs_hip_spmm_rowmaj_f32": (i32, [vp, vp, u64, u64, u64, vp, u64, u64, i32, vp]),
     "sprs_hip_csmat_mulacc_dense_f32": (i32, [vp, vp, u64, u64, i32, u64, vp, u64, i32, u64, i32, vp]),
     "sprs_hip_csmat_mul_dense_f32": (i32, [vp, vp, u64, u64, i32, u64, vp, P(i32), vp]),

@@ -519,6 +519,46 @@ static int32_t entry_bicgstab(H *a, const Value<H> *x0_dev, const Value<H> *b_de
     return bicgstab(a, x0_dev, b_dev, n, tol_t, max_iter, threshold_t, x_dev, info, (hipStream_t)stream);
 }
 
+template <typename H>
+static int32_t entry_gauss_seidel(H *a, Value<H> *x_dev, const Value<H> *rhs_dev, uint64_t n, uint64_t max_iter, double eps,
+                                  sprs_hip_gauss_seidel_info *info, void *stream) {
+    clear_error();
+    if (!a) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if (a->rows != a->cols || a->rows != n) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");   // heat.rs:109-110
+    if (a->storage != SPRS_HIP_CSR) SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "Gauss-Seidel sweeps the rows of a CSR matrix");
+    if (n && (!x_dev || !rhs_dev)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL vector");
+    if (x_dev && x_dev == rhs_dev) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "x_dev may not alias rhs_dev");
+    return gauss_seidel(a, x_dev, rhs_dev, n, max_iter, eps, info, (hipStream_t)stream);
+}
+
+// The four dense-rhs solves of sprs::linalg::trisolve behind one entry: the handle's storage selects the CSR or CSC function, uplo
+// lsolve or usolve.  A CSC handle is solved on its CSR form (the as_other copy above), where the row orders then live; a->mu is
+// held for the whole (blocking) call, so a refresh on another thread cannot drop that copy under the solve.
+template <typename H>
+static int32_t entry_trisolve(H *a, int32_t uplo, Value<H> *x_dev, uint64_t n, sprs_hip_trisolve_info *info, void *stream) {
+    clear_error();
+    if (!a) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
+    if (uplo != SPRS_HIP_LOWER && uplo != SPRS_HIP_UPPER) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "uplo must be SPRS_HIP_LOWER or SPRS_HIP_UPPER");
+    // check_solver_dimensions, trisolve.rs:10-21
+    if (a->rows != a->cols) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Non square matrix passed to solver");
+    if (a->cols != n) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
+    if (n && !x_dev) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL vector");
+    if (n >= (1ull << 32)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "triangular solve: 2^32 rows or more are not supported");
+    if (info) *info = sprs_hip_trisolve_info{0, UINT64_MAX, 0};
+    if (n == 0) return SPRS_HIP_OK;
+    std::lock_guard<std::recursive_mutex> lock(a->mu);
+    H *csr = nullptr;
+    SPRS_TRY(csr_form(a, &csr));
+    return trisolve(csr, uplo == SPRS_HIP_UPPER, a->storage == SPRS_HIP_CSC, x_dev, n, info, (hipStream_t)stream);
+}
+
+template <typename T>
+static int32_t entry_diag_solve(const T *d_dev, T *x_dev, uint64_t n, void *stream) {
+    clear_error();
+    if (n && (!d_dev || !x_dev)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL vector");
+    return diag_solve(d_dev, x_dev, n, (hipStream_t)stream);
+}
+
 extern "C" {
 
 const char *sprs_hip_last_error(void) { return tl_msg.c_str(); }
@@ -907,13 +947,7 @@ int32_t sprs_hip_bicgstab_f64(sprs_hip_csmat *a, const double *x0_dev, const dou
 
 int32_t sprs_hip_gauss_seidel_f64(sprs_hip_csmat *a, double *x_dev, const double *rhs_dev, uint64_t n, uint64_t max_iter,
                                   double eps, sprs_hip_gauss_seidel_info *info, void *stream) {
-    clear_error();
-    if (!a) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
-    if (a->rows != a->cols || a->rows != n) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");   // heat.rs:109-110
-    if (a->storage != SPRS_HIP_CSR) SPRS_FAIL(SPRS_HIP_STORAGE_MISMATCH, "Gauss-Seidel sweeps the rows of a CSR matrix");
-    if (n && (!x_dev || !rhs_dev)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL vector");
-    if (x_dev && x_dev == rhs_dev) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "x_dev may not alias rhs_dev");
-    return gauss_seidel_f64(a, x_dev, rhs_dev, n, max_iter, eps, info, (hipStream_t)stream);
+    return entry_gauss_seidel(a, x_dev, rhs_dev, n, max_iter, eps, info, stream);
 }
 
 int32_t sprs_hip_spgemm_f64(const sprs_hip_csmat *a, const sprs_hip_csmat *b, sprs_hip_csmat **c) {
@@ -970,24 +1004,8 @@ int32_t sprs_hip_csmat_prepare(sprs_hip_csmat *m, void *stream) {
     return entry_prepare(m, stream);
 }
 
-// The four dense-rhs solves of sprs::linalg::trisolve behind one entry: the handle's storage selects the CSR or CSC function, uplo
-// lsolve or usolve.  A CSC handle is solved on its CSR form (the as_other copy above), where the row orders then live; a->mu is
-// held for the whole (blocking) call, so a refresh on another thread cannot drop that copy under the solve.
 int32_t sprs_hip_trisolve_f64(sprs_hip_csmat *a, int32_t uplo, double *x_dev, uint64_t n, sprs_hip_trisolve_info *info, void *stream) {
-    clear_error();
-    if (!a) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL handle");
-    if (uplo != SPRS_HIP_LOWER && uplo != SPRS_HIP_UPPER) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "uplo must be SPRS_HIP_LOWER or SPRS_HIP_UPPER");
-    // check_solver_dimensions, trisolve.rs:10-21
-    if (a->rows != a->cols) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Non square matrix passed to solver");
-    if (a->cols != n) SPRS_FAIL(SPRS_HIP_DIM_MISMATCH, "Dimension mismatch");
-    if (n && !x_dev) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL vector");
-    if (n >= (1ull << 32)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "triangular solve: 2^32 rows or more are not supported");
-    if (info) *info = sprs_hip_trisolve_info{0, UINT64_MAX, 0};
-    if (n == 0) return SPRS_HIP_OK;
-    std::lock_guard<std::recursive_mutex> lock(a->mu);
-    sprs_hip_csmat *csr = nullptr;
-    SPRS_TRY(csr_form(a, &csr));
-    return trisolve_f64(csr, uplo == SPRS_HIP_UPPER, a->storage == SPRS_HIP_CSC, x_dev, n, info, (hipStream_t)stream);
+    return entry_trisolve(a, uplo, x_dev, n, info, stream);
 }
 
 // lsolve_csc_sparse_rhs (trisolve.rs:286-358): the reach over l's own columns, the solve on its CSR form (where the level plan
@@ -1996,9 +2014,7 @@ int32_t sprs_hip_ldl_lsolve_f64(sprs_hip_csmat *l, double *x_dev, uint64_t n, vo
 int32_t sprs_hip_ldl_ltsolve_f64(sprs_hip_csmat *l, double *x_dev, uint64_t n, void *stream) { return ldl_tri_entry(l, true, x_dev, n, stream); }
 
 int32_t sprs_hip_diag_solve_f64(const double *d_dev, double *x_dev, uint64_t n, void *stream) {
-    clear_error();
-    if (n && (!d_dev || !x_dev)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "NULL vector");
-    return diag_solve_f64(d_dev, x_dev, n, (hipStream_t)stream);
+    return entry_diag_solve(d_dev, x_dev, n, stream);
 }
 
 }  // extern "C"
@@ -2425,6 +2441,19 @@ int32_t sprs_hip_csmat_mul_vec_f32(const sprs_hip_csmat_f32 *a, const float *x_d
 int32_t sprs_hip_bicgstab_f32(sprs_hip_csmat_f32 *a, const float *x0_dev, const float *b_dev, uint64_t n, double tol, uint64_t max_iter,
                               double soft_restart_threshold, float *x_dev, sprs_hip_bicgstab_info *info, void *stream) {
     return entry_bicgstab(a, x0_dev, b_dev, n, tol, max_iter, soft_restart_threshold, x_dev, info, stream);
+}
+
+int32_t sprs_hip_trisolve_f32(sprs_hip_csmat_f32 *a, int32_t uplo, float *x_dev, uint64_t n, sprs_hip_trisolve_info *info, void *stream) {
+    return entry_trisolve(a, uplo, x_dev, n, info, stream);
+}
+
+int32_t sprs_hip_gauss_seidel_f32(sprs_hip_csmat_f32 *a, float *x_dev, const float *rhs_dev, uint64_t n, uint64_t max_iter, double eps,
+                                  sprs_hip_gauss_seidel_info *info, void *stream) {
+    return entry_gauss_seidel(a, x_dev, rhs_dev, n, max_iter, eps, info, stream);
+}
+
+int32_t sprs_hip_diag_solve_f32(const float *d_dev, float *x_dev, uint64_t n, void *stream) {
+    return entry_diag_solve(d_dev, x_dev, n, stream);
 }
 
 int32_t sprs_hip_spmm_rowmaj_f32(const sprs_hip_csmat_f32 *a, const float *rhs_dev, uint64_t rhs_rows, uint64_t k, uint64_t ld_rhs,

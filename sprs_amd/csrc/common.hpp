@@ -458,6 +458,8 @@ struct SpmvPlanF32 {
 struct sprs_hip_csmat_f32 : sprs_hip::CsmatCore<float, sprs_hip_csmat_f32> {
     uint64_t spmv_calls = 0;   // multiplies so far, as in sprs_hip_csmat: the banded plan is built at the SECOND one (or by sprs_hip_csmat_f32_prepare)
     sprs_hip::SpmvPlanF32 plan;
+    sprs_hip::GsPlan gs;                 // as in sprs_hip_csmat: the level plans read structure only, so they are the same type
+    sprs_hip::GsPlan tri_upper;
     ~sprs_hip_csmat_f32();     // handle.hpp
 };
 
@@ -598,8 +600,12 @@ int32_t bicgstab_f32(sprs_hip_csmat_f32 *a, const float *x0, const float *b, uin
 // gauss_seidel.hip
 int32_t gauss_seidel_f64(sprs_hip_csmat *a, double *x, const double *rhs, uint64_t n, uint64_t max_iter, double eps,
                          sprs_hip_gauss_seidel_info *info, hipStream_t stream);
+// (eps is rounded to f32 first; info->error is the f32 value widened; no band schedule)
+int32_t gauss_seidel_f32(sprs_hip_csmat_f32 *a, float *x, const float *rhs, uint64_t n, uint64_t max_iter, double eps,
+                         sprs_hip_gauss_seidel_info *info, hipStream_t stream);
 // trisolve.hpp (compiled in gauss_seidel.hip): csr = the CSR form of the caller's handle, csc = that handle is CSC
 int32_t trisolve_f64(sprs_hip_csmat *csr, bool upper, bool csc, double *x, uint64_t n, sprs_hip_trisolve_info *info, hipStream_t stream);
+int32_t trisolve_f32(sprs_hip_csmat_f32 *csr, bool upper, bool csc, float *x, uint64_t n, sprs_hip_trisolve_info *info, hipStream_t stream);
 // sptrisolve.hpp (compiled in gauss_seidel.hip): lsolve_csc_sparse_rhs; l = the caller's CSC handle (its columns are the graph
 // of the reach), csr = its CSR form (plan, scratch, the rows the solve walks).  Complete on `stream` at return
 int32_t sptrisolve_f64(sprs_hip_csmat *l, sprs_hip_csmat *csr, const sprs_hip_csvec *rhs, OwnedCsvec &out, sprs_hip_sptrisolve_info *info,
@@ -612,6 +618,7 @@ int32_t ldl_solve_f64(sprs_hip_ldl_num *num, const double *b, double *x, hipStre
 // ldl_lsolve (transposed = false) / ldl_ltsolve (true) on the arrays of a CSC handle (csr = its CSR form, for lsolve)
 int32_t ldl_tri_f64(sprs_hip_csmat *l, sprs_hip_csmat *csr, bool transposed, double *x, hipStream_t stream);
 int32_t diag_solve_f64(const double *d, double *x, uint64_t n, hipStream_t stream);
+int32_t diag_solve_f32(const float *d, float *x, uint64_t n, hipStream_t stream);
 int32_t slice_outer(const sprs_hip_csmat *m, uint64_t start, uint64_t end, OwnedCsmat &out);
 // csvec.hpp (compiled in spmv.hip)
 // the invariants of CsVec::try_new on the device; `info` (may be null): the kind of the finding (a vector is its one slice, 0)
@@ -693,6 +700,22 @@ inline int32_t spmm_strided(sprs_hip_csmat_f32 *a, const float *rhs, uint64_t k,
                             uint64_t cs_out, bool accumulate, hipStream_t stream) {
     return spmm_strided_f32(a, rhs, k, rs_rhs, cs_rhs, out, rs_out, cs_out, accumulate, stream);
 }
+inline int32_t gauss_seidel(sprs_hip_csmat *a, double *x, const double *rhs, uint64_t n, uint64_t max_iter, double eps, sprs_hip_gauss_seidel_info *info,
+                            hipStream_t stream) {
+    return gauss_seidel_f64(a, x, rhs, n, max_iter, eps, info, stream);
+}
+inline int32_t gauss_seidel(sprs_hip_csmat_f32 *a, float *x, const float *rhs, uint64_t n, uint64_t max_iter, double eps, sprs_hip_gauss_seidel_info *info,
+                            hipStream_t stream) {
+    return gauss_seidel_f32(a, x, rhs, n, max_iter, eps, info, stream);
+}
+inline int32_t trisolve(sprs_hip_csmat *csr, bool upper, bool csc, double *x, uint64_t n, sprs_hip_trisolve_info *info, hipStream_t stream) {
+    return trisolve_f64(csr, upper, csc, x, n, info, stream);
+}
+inline int32_t trisolve(sprs_hip_csmat_f32 *csr, bool upper, bool csc, float *x, uint64_t n, sprs_hip_trisolve_info *info, hipStream_t stream) {
+    return trisolve_f32(csr, upper, csc, x, n, info, stream);
+}
+inline int32_t diag_solve(const double *d, double *x, uint64_t n, hipStream_t stream) { return diag_solve_f64(d, x, n, stream); }
+inline int32_t diag_solve(const float *d, float *x, uint64_t n, hipStream_t stream) { return diag_solve_f32(d, x, n, stream); }
 inline int32_t bicgstab(sprs_hip_csmat *a, const double *x0, const double *b, uint64_t n, double tol, uint64_t max_iter, double threshold, double *x,
                         sprs_hip_bicgstab_info *info, hipStream_t stream) {
     return bicgstab_f64(a, x0, b, n, tol, max_iter, threshold, x, info, stream);

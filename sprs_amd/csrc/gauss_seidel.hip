@@ -30,6 +30,7 @@
 #include "scan.hpp"
 
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 namespace sprs_hip {
@@ -55,6 +56,31 @@ constexpr uint64_t SUM_CHUNK = 8192;
 __device__ __forceinline__ unsigned long long gs_peek(const unsigned long long *p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+__device__ __forceinline__ uint32_t gs_peek(const uint32_t *p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The hand-off word of a scalar type: value and "ready" are ONE naturally aligned granule of the scalar's own size, polled with
+// gs_peek and published with one relaxed agent-scope store.  PENDING is what memset 0xFF leaves (a NaN no arithmetic yields from
+// non-NaN inputs), ABSENT the second such NaN (the SPARSE form of tri_solve_kernel), QNAN what a computed result whose bits
+// equal either is published as.  The sweep and the triangular solves are written against this struct; double keeps the words
+// and constants it always had.
+template <typename T>
+struct GsWord;
+template <>
+struct GsWord<double> {
+    using word = unsigned long long;
+    static constexpr word PENDING = GS_PENDING, ABSENT = ~0ull - 1ull, QNAN = GS_QNAN;
+    static __device__ __forceinline__ word bits(double v) { return (word)__double_as_longlong(v); }
+    static __device__ __forceinline__ double value(word b) { return __longlong_as_double((long long)b); }
+};
+template <>
+struct GsWord<float> {
+    using word = uint32_t;
+    static constexpr word PENDING = 0xFFFFFFFFu, ABSENT = 0xFFFFFFFEu, QNAN = 0x7FC00000u;
+    static __device__ __forceinline__ word bits(float v) { return __builtin_bit_cast(word, v); }      // (a compiler builtin: the same in the host build of the emulator)
+    static __device__ __forceinline__ float value(word b) { return __builtin_bit_cast(float, b); }
+};
 
 // the next 64 positions of the order a kernel walks: one atomic per wave, handed to its lanes (shared by the sweep, the level
 // recurrence and the triangular solves of trisolve.hpp)
@@ -105,13 +131,17 @@ __device__ __forceinline__ uint32_t gs_xcc_id() {
 // published with a plain store (it stays in that L2, dirty) and the 8-byte L1-bypassing loads of the pollers are served
 // from there instead of from the fabric: a shorter hop for matrices whose sweep is a long chain of narrow levels.  Which
 // XCD a wave is on is read from the hardware (never assumed from blockIdx), so only speed depends on the dispatcher.
-template <typename IDX, typename PTR, bool ONE_XCD>
+// T = the scalar of the values, the vectors and the arithmetic.  x_new is declared as the f64 code always had it (its symbols must
+// not move); what it addresses is one GsWord<T>::word per row: 8-byte words for double, 4-byte words for float.
+template <typename IDX, typename PTR, bool ONE_XCD, typename T = double>
 __global__ __launch_bounds__(GS_BLOCK) void gs_sweep_kernel(const PTR *__restrict__ indptr, const IDX *__restrict__ indices,
-                                                            const double *__restrict__ data,
+                                                            const T *__restrict__ data,
                                                             const uint32_t *__restrict__ order,
-                                                            const double *__restrict__ x_old, unsigned long long *x_new,
-                                                            const double *__restrict__ rhs, uint64_t n,
+                                                            const T *__restrict__ x_old, unsigned long long *x_new,
+                                                            const T *__restrict__ rhs, uint64_t n,
                                                             unsigned int *next_chunk, unsigned int *status, uint32_t max_naps) {
+    using W = GsWord<T>;
+    typename W::word *const next = (typename W::word *)x_new;
     const uint32_t lane = threadIdx.x & 63u;
     if (ONE_XCD && gs_xcc_id() != 0u) return;
     for (uint64_t base = gs_draw(next_chunk, lane); base < n; base = gs_draw(next_chunk, lane)) {
@@ -119,17 +149,17 @@ __global__ __launch_bounds__(GS_BLOCK) void gs_sweep_kernel(const PTR *__restric
         bool done = pos >= n;
         uint32_t row = 0;
         uint64_t p = 0, end = 0;
-        double b = 0.0;
+        T b = T(0);
         if (!done) {
             row = order[pos];
             p = (uint64_t)indptr[row];
             end = (uint64_t)indptr[row + 1];
             b = rhs[row];
         }
-        double sigma = 0.0, diag = 0.0;
+        T sigma = T(0), diag = T(0);
         bool has_diag = false;
         uint32_t col[GS_B];
-        double val[GS_B], xv[GS_B];
+        T val[GS_B], xv[GS_B];
         uint32_t nb = 0, pend = 0, spins = 0;
         bool loaded = false, more = true;
         while (more) {
@@ -165,14 +195,14 @@ __global__ __launch_bounds__(GS_BLOCK) void gs_sweep_kernel(const PTR *__restric
                 }
                 // the poll: this sweep's values that have not arrived yet, all requested together — kept short, it is what a
                 // waiting wave executes over and over and what stands between a published value and its use
-                unsigned long long bits[GS_B];
+                typename W::word bits[GS_B];
 #pragma unroll
                 for (int u = 0; u < GS_B; ++u)
-                    if ((pend >> u) & 1u) bits[u] = gs_peek(x_new + col[u]);
+                    if ((pend >> u) & 1u) bits[u] = gs_peek(next + col[u]);
 #pragma unroll
                 for (int u = 0; u < GS_B; ++u)
-                    if (((pend >> u) & 1u) && bits[u] != GS_PENDING) {
-                        xv[u] = __longlong_as_double((long long)bits[u]);
+                    if (((pend >> u) & 1u) && bits[u] != W::PENDING) {
+                        xv[u] = W::value(bits[u]);
                         pend &= ~(1u << u);
                         moved = true;
                     }
@@ -184,21 +214,21 @@ __global__ __launch_bounds__(GS_BLOCK) void gs_sweep_kernel(const PTR *__restric
                                 diag = val[u];
                                 has_diag = true;
                             } else {
-                                const double prod = val[u] * xv[u];
+                                const T prod = val[u] * xv[u];
                                 sigma = sigma + prod;
                             }
                         }
                     loaded = false;
                     moved = true;
                     if (p == end) {
-                        double xr = (b - sigma) / diag;         // heat.rs:128-130
-                        unsigned long long out = (unsigned long long)__double_as_longlong(xr);
+                        T xr = (b - sigma) / diag;              // heat.rs:128-130
+                        typename W::word out = W::bits(xr);
                         if (!has_diag) {                        // diag.unwrap() of None: the host turns this into an error
                             atomicOr(status, GS_NO_DIAG);
-                            out = GS_QNAN;
+                            out = W::QNAN;
                         }
-                        if (out == GS_PENDING) out = GS_QNAN;   // (a NaN payload handed through from rhs / x: still a NaN, but not "pending")
-                        __hip_atomic_store(x_new + row, out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // agent scope in both modes: the pollers sit on other CUs
+                        if (out == W::PENDING) out = W::QNAN;   // (a NaN payload handed through from rhs / x: still a NaN, but not "pending")
+                        __hip_atomic_store(next + row, out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // agent scope in both modes: the pollers sit on other CUs
                         done = true;
                     }
                 }
@@ -212,42 +242,45 @@ __global__ __launch_bounds__(GS_BLOCK) void gs_sweep_kernel(const PTR *__restric
 // residual sum of the reference's convergence test: sum_i (v_i - rhs_i), v = A x.  Fixed two-level tree (chunks of 8192:
 // thread t adds elements t, t + 256, ... in order, then the lanes and the waves in a fixed shape): deterministic, rounded
 // differently from ndarray's eight running sums.
-__global__ __launch_bounds__(GS_BLOCK) void gs_resid_partial_kernel(const double *__restrict__ v, const double *__restrict__ rhs,
-                                                                    uint64_t n, double *__restrict__ partial) {
-    __shared__ double lds[GS_BLOCK / 64];
-    const uint64_t lo = (uint64_t)blockIdx.x * SUM_CHUNK;
-    const uint64_t hi = lo + SUM_CHUNK < n ? lo + SUM_CHUNK : n;
-    double s = 0.0;
-    for (uint64_t i = lo + threadIdx.x; i < hi; i += GS_BLOCK) {
-        const double r = v[i] - rhs[i];
-        s = s + r;
+// One body for both precisions, as a macro and not as a template: the f64 kernels keep their plain (non-template) symbols and
+// their instructions (a shared inlined device function gave the same arithmetic with the two loads of the loop swapped).
+#define GS_RESID_KERNELS(T)                                                                                                          \
+    __global__ __launch_bounds__(GS_BLOCK) void gs_resid_partial_kernel(const T *__restrict__ v, const T *__restrict__ rhs,          \
+                                                                        uint64_t n, T *__restrict__ partial) {                      \
+        __shared__ T lds[GS_BLOCK / 64];                                                                                             \
+        const uint64_t lo = (uint64_t)blockIdx.x * SUM_CHUNK;                                                                        \
+        const uint64_t hi = lo + SUM_CHUNK < n ? lo + SUM_CHUNK : n;                                                                 \
+        T s = 0.0;                                                                                                                   \
+        for (uint64_t i = lo + threadIdx.x; i < hi; i += GS_BLOCK) {                                                                 \
+            const T r = v[i] - rhs[i];                                                                                               \
+            s = s + r;                                                                                                               \
+        }                                                                                                                            \
+        _Pragma("unroll") for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);                                       \
+        if ((threadIdx.x & 63u) == 0) lds[threadIdx.x >> 6] = s;                                                                     \
+        __syncthreads();                                                                                                             \
+        if (threadIdx.x == 0) {                                                                                                      \
+            T t = lds[0];                                                                                                            \
+            for (int w = 1; w < GS_BLOCK / 64; ++w) t = t + lds[w];                                                                  \
+            partial[blockIdx.x] = t;                                                                                                 \
+        }                                                                                                                            \
+    }                                                                                                                                \
+    __global__ __launch_bounds__(GS_BLOCK) void gs_resid_final_kernel(const T *__restrict__ partial, uint64_t nchunks,               \
+                                                                      T *__restrict__ out) {                                        \
+        __shared__ T lds[GS_BLOCK / 64];                                                                                             \
+        T s = 0.0;                                                                                                                   \
+        for (uint64_t i = threadIdx.x; i < nchunks; i += GS_BLOCK) s = s + partial[i];                                               \
+        _Pragma("unroll") for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);                                       \
+        if ((threadIdx.x & 63u) == 0) lds[threadIdx.x >> 6] = s;                                                                     \
+        __syncthreads();                                                                                                             \
+        if (threadIdx.x == 0) {                                                                                                      \
+            T t = lds[0];                                                                                                            \
+            for (int w = 1; w < GS_BLOCK / 64; ++w) t = t + lds[w];                                                                  \
+            out[0] = t;                                                                                                              \
+        }                                                                                                                            \
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-    if ((threadIdx.x & 63u) == 0) lds[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = lds[0];
-        for (int w = 1; w < GS_BLOCK / 64; ++w) t = t + lds[w];
-        partial[blockIdx.x] = t;
-    }
-}
-
-__global__ __launch_bounds__(GS_BLOCK) void gs_resid_final_kernel(const double *__restrict__ partial, uint64_t nchunks,
-                                                                  double *__restrict__ out) {
-    __shared__ double lds[GS_BLOCK / 64];
-    double s = 0.0;
-    for (uint64_t i = threadIdx.x; i < nchunks; i += GS_BLOCK) s = s + partial[i];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-    if ((threadIdx.x & 63u) == 0) lds[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = lds[0];
-        for (int w = 1; w < GS_BLOCK / 64; ++w) t = t + lds[w];
-        out[0] = t;
-    }
-}
+GS_RESID_KERNELS(double)
+GS_RESID_KERNELS(float)
+#undef GS_RESID_KERNELS
 
 // The level order ON THE DEVICE, once per handle: level(i) = 1 + max level(c) over the stored c < i, rows sorted by (level, row).
 // The levels are themselves a recurrence over the rows, and the sweep's own trick computes them: the waves draw rows in
@@ -340,8 +373,9 @@ __global__ void gs_order_kernel(const uint64_t *__restrict__ vals, uint64_t n, u
     if (i < n) order[i] = (uint32_t)vals[i];
 }
 
-template <typename IDX, typename PTR, bool UPPER>
-int32_t gs_plan_build(sprs_hip_csmat *a, GsPlan &pl) {
+// (reads structure only: H is either matrix handle)
+template <typename IDX, typename PTR, bool UPPER, typename H>
+int32_t gs_plan_build(H *a, GsPlan &pl) {
     const uint64_t n = a->rows;
     hipStream_t stream = nullptr;
     DevBuf level, words, keys, vals;
@@ -659,9 +693,14 @@ __global__ __launch_bounds__(GB_BLOCK) void gs_band_kernel(const PTR *__restrict
     }
 }
 
-template <typename IDX, typename PTR>
-int32_t gs_impl(sprs_hip_csmat *a, double *x, const double *rhs, uint64_t n, uint64_t max_iter, double eps,
+// H = the matrix handle, T its scalar: the sweep, the residual and the convergence test run in T (eps is rounded to T first, as
+// tol is in the f32 BiCGSTAB; info->error is the T value widened).  The band schedule exists for double only.
+template <typename IDX, typename PTR, typename H>
+int32_t gs_impl(H *a, typename H::value_type *x, const typename H::value_type *rhs, uint64_t n, uint64_t max_iter, double eps,
                 sprs_hip_gauss_seidel_info *info, hipStream_t stream) {
+    using T = typename H::value_type;
+    constexpr bool F64 = std::is_same<T, double>::value;
+    const T eps_t = (T)eps;
     // held for the whole solve: the level order (and the SpMV plan of the residual) must outlive every launch that reads them;
     // sprs_hip_csmat_refresh / _free on another thread wait (recursive: the SpMV of the residual locks again)
     std::lock_guard<std::recursive_mutex> lock(a->mu);
@@ -670,7 +709,11 @@ int32_t gs_impl(sprs_hip_csmat *a, double *x, const double *rhs, uint64_t n, uin
     const uint64_t nlevels = a->gs.nlevels, no_diag_row = a->gs.no_diag_row;
     // ---- the band schedule, when the matrix fits one ----
     uint64_t chain_S = 0;
-    {
+    if constexpr (!F64) {
+        if (options().gauss_seidel_chain > 1)
+            SPRS_FAIL(SPRS_HIP_INVALID_ARG, "gauss_seidel_chain = %lld: the band schedule is built for f64 matrices only (set the option to 0 for an f32 sweep)",
+                      (long long)options().gauss_seidel_chain);
+    } else {
         const int64_t opt = options().gauss_seidel_chain;
         uint64_t want = opt > 1 ? (uint64_t)opt : 0;
         // (auto = level order: the band schedule is correct and bit-identical but NOT faster as built — 1.6 us per step on the
@@ -706,21 +749,21 @@ int32_t gs_impl(sprs_hip_csmat *a, double *x, const double *rhs, uint64_t n, uin
 
     const uint64_t nchunks = (n + SUM_CHUNK - 1) / SUM_CHUNK;
     unsigned int sweep_words[2] = {0, 0};
-    double h_sum = 0.0;
+    T h_sum = T(0);
     DevBuf buf, words;
     StreamDrain drain{stream};                  // declared last, so it runs first: an early return must not leave copies into this
                                                 // frame's variables (sweep_words) or kernels on buf / words in flight
-    SPRS_TRY_HIP(buf.alloc((2 * n + nchunks + 8) * sizeof(double)));
+    SPRS_TRY_HIP(buf.alloc((2 * n + nchunks + 8) * sizeof(T)));
     SPRS_TRY_HIP(words.alloc(64));
-    double *other = buf.as<double>(), *v = other + n, *partial = v + n, *scal = partial + nchunks;
+    T *other = buf.as<T>(), *v = other + n, *partial = v + n, *scal = partial + nchunks;
     unsigned int *next_chunk = words.as<unsigned int>(), *status = next_chunk + 1;
 
-    auto residual_error = [&](const double *xc, double &err) -> int32_t {      // (&mat * &x - rhs).sum().sqrt()
-        SPRS_TRY(spmv_f64(a, xc, v, false, stream));
-        hipLaunchKernelGGL(gs_resid_partial_kernel, dim3((unsigned)nchunks), dim3(GS_BLOCK), 0, stream, v, rhs, n, partial);
-        hipLaunchKernelGGL(gs_resid_final_kernel, dim3(1), dim3(GS_BLOCK), 0, stream, partial, nchunks, scal);
+    auto residual_error = [&](const T *xc, T &err) -> int32_t {      // (&mat * &x - rhs).sum().sqrt()
+        SPRS_TRY(spmv(a, xc, v, false, stream));
+        hipLaunchKernelGGL(gs_resid_partial_kernel, dim3((unsigned)nchunks), dim3(GS_BLOCK), 0, stream, (const T *)v, rhs, n, partial);
+        hipLaunchKernelGGL(gs_resid_final_kernel, dim3(1), dim3(GS_BLOCK), 0, stream, (const T *)partial, nchunks, scal);
         SPRS_TRY_HIP(hipGetLastError());
-        SPRS_TRY_HIP(copy_to_host(&h_sum, scal, sizeof(double), stream));
+        SPRS_TRY_HIP(copy_to_host(&h_sum, scal, sizeof(T), stream));
         err = std::sqrt(h_sum);
         return SPRS_HIP_OK;
     };
@@ -740,31 +783,33 @@ int32_t gs_impl(sprs_hip_csmat *a, double *x, const double *rhs, uint64_t n, uin
     if (one_xcd && options().gauss_seidel_blocks == 0) grid = (uint64_t)(ncu > 8 ? ncu / 8 : 1) < need ? (uint64_t)(ncu > 8 ? ncu / 8 : 1) : need;
     const uint32_t max_naps = options().gauss_seidel_naps > 0 ? (uint32_t)options().gauss_seidel_naps : 1u;
 
-    double error = 0.0;
+    T error = T(0);
     int32_t converged = 0;
     uint64_t iterations = max_iter;
-    double *cur = x, *nxt = other;
+    T *cur = x, *nxt = other;
     if (max_iter == 0) SPRS_TRY(residual_error(cur, error));                   // heat.rs:111: what Err(error) holds then
     for (uint64_t it = 0; it < max_iter; ++it) {
-        SPRS_TRY_HIP(hipMemsetAsync(nxt, 0xFF, n * sizeof(double), stream));   // every row of the next iterate "pending"
+        SPRS_TRY_HIP(hipMemsetAsync(nxt, 0xFF, n * sizeof(T), stream));   // every row of the next iterate "pending"
         SPRS_TRY_HIP(hipMemsetAsync(words.p, 0, 64, stream));
         if (chain_S) {     // one workgroup per band, bands drawn in order
+          if constexpr (F64) {     // (gs_band_kernel exists for double only; chain_S stays 0 for float)
             uint64_t nbands = (n + 64 * chain_S - 1) / (64 * chain_S);
             if (nbands > (uint64_t)(ncu > 0 ? ncu : 1)) nbands = (uint64_t)(ncu > 0 ? ncu : 1);
             hipLaunchKernelGGL((gs_band_kernel<IDX, PTR>), dim3((unsigned)nbands), dim3(GB_BLOCK), 0, stream, (const PTR *)a->indptr,
                                (const IDX *)a->indices, (const double *)a->data, (const double *)cur, (unsigned long long *)nxt, rhs, n, chain_S,
                                next_chunk, status, DEVTOOLS ? (uint32_t)options().gauss_seidel_debug : 0u);
+          }
         } else if (one_xcd)       // 8 x the workgroups: an eighth of them lands on XCD 0 and stays
-            hipLaunchKernelGGL((gs_sweep_kernel<IDX, PTR, true>), dim3((unsigned)(grid * 8)), dim3(GS_BLOCK), 0, stream, (const PTR *)a->indptr,
-                               (const IDX *)a->indices, (const double *)a->data, order, (const double *)cur,
+            hipLaunchKernelGGL((gs_sweep_kernel<IDX, PTR, true, T>), dim3((unsigned)(grid * 8)), dim3(GS_BLOCK), 0, stream, (const PTR *)a->indptr,
+                               (const IDX *)a->indices, (const T *)a->data, order, (const T *)cur,
                                (unsigned long long *)nxt, rhs, n, next_chunk, status, max_naps);
         else
-            hipLaunchKernelGGL((gs_sweep_kernel<IDX, PTR, false>), dim3((unsigned)grid), dim3(GS_BLOCK), 0, stream, (const PTR *)a->indptr,
-                               (const IDX *)a->indices, (const double *)a->data, order, (const double *)cur,
+            hipLaunchKernelGGL((gs_sweep_kernel<IDX, PTR, false, T>), dim3((unsigned)grid), dim3(GS_BLOCK), 0, stream, (const PTR *)a->indptr,
+                               (const IDX *)a->indices, (const T *)a->data, order, (const T *)cur,
                                (unsigned long long *)nxt, rhs, n, next_chunk, status, max_naps);
         SPRS_TRY_HIP(hipGetLastError());
         SPRS_TRY_HIP(hipMemcpyAsync(sweep_words, words.p, sizeof(sweep_words), hipMemcpyDeviceToHost, stream));   // [0] chunks drawn, [1] status
-        double *t = cur;
+        T *t = cur;
         cur = nxt;
         nxt = t;
         SPRS_TRY(residual_error(cur, error));                                  // (drains the stream: the two words are valid after it)
@@ -777,17 +822,17 @@ int32_t gs_impl(sprs_hip_csmat *a, double *x, const double *rhs, uint64_t n, uin
         if (st & GS_TIMEOUT)
             SPRS_FAIL(SPRS_HIP_HIP_ERROR, "Gauss-Seidel sweep: a row waited for a value that was never published (level order broken)");
         if (st & GS_NO_DIAG) SPRS_FAIL(SPRS_HIP_BAD_STRUCTURE, "Gauss-Seidel: a row has no stored diagonal entry");
-        if (error < eps) {                                                     // heat.rs:134-136
+        if (error < eps_t) {                                                     // heat.rs:134-136
             converged = 1;
             iterations = it;
             break;
         }
     }
-    if (cur != x) SPRS_TRY_HIP(hipMemcpyAsync(x, cur, n * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    if (cur != x) SPRS_TRY_HIP(hipMemcpyAsync(x, cur, n * sizeof(T), hipMemcpyDeviceToDevice, stream));
     SPRS_TRY_HIP(hipStreamSynchronize(stream));
     if (info) {
         info->iterations = iterations;
-        info->error = error;
+        info->error = (double)error;
         info->converged = converged;
         info->levels = nlevels;
     }
@@ -808,16 +853,30 @@ int32_t gs_impl(sprs_hip_csmat *a, double *x, const double *rhs, uint64_t n, uin
 // plans and tri_solve_kernel
 #include "ldl.hpp"
 
-int32_t gauss_seidel_f64(sprs_hip_csmat *a, double *x, const double *rhs, uint64_t n, uint64_t max_iter, double eps,
-                         sprs_hip_gauss_seidel_info *info, hipStream_t stream) {
+namespace {
+template <typename H>
+int32_t gs_entry(H *a, typename H::value_type *x, const typename H::value_type *rhs, uint64_t n, uint64_t max_iter, double eps,
+                 sprs_hip_gauss_seidel_info *info, hipStream_t stream) {
+    using T = typename H::value_type;
     if (n >= (1ull << 32)) SPRS_FAIL(SPRS_HIP_INVALID_ARG, "Gauss-Seidel: 2^32 rows or more are not supported");
     if (n == 0) {                      // an empty sum: error = sqrt(0) = 0
-        if (info) *info = sprs_hip_gauss_seidel_info{max_iter && !(0.0 < eps) ? max_iter : 0, 0.0, (max_iter && 0.0 < eps) ? 1 : 0, 0};
+        const bool passes = max_iter && T(0) < (T)eps;
+        if (info) *info = sprs_hip_gauss_seidel_info{passes ? 0 : max_iter, 0.0, passes ? 1 : 0, 0};
         return SPRS_HIP_OK;
     }
     return dispatch_widths(a->idx_bytes, a->iptr_bytes, [&](auto i, auto p) {
         return gs_impl<typename decltype(i)::type, typename decltype(p)::type>(a, x, rhs, n, max_iter, eps, info, stream);
     });
+}
+}  // namespace
+
+int32_t gauss_seidel_f64(sprs_hip_csmat *a, double *x, const double *rhs, uint64_t n, uint64_t max_iter, double eps,
+                         sprs_hip_gauss_seidel_info *info, hipStream_t stream) {
+    return gs_entry(a, x, rhs, n, max_iter, eps, info, stream);
+}
+int32_t gauss_seidel_f32(sprs_hip_csmat_f32 *a, float *x, const float *rhs, uint64_t n, uint64_t max_iter, double eps,
+                         sprs_hip_gauss_seidel_info *info, hipStream_t stream) {
+    return gs_entry(a, x, rhs, n, max_iter, eps, info, stream);
 }
 
 }  // namespace sprs_hip

@@ -283,6 +283,8 @@ void invalidate_caches(sprs_hip_csmat *m) {
 
 void invalidate_caches(sprs_hip_csmat_f32 *m) {
     m->plan = SpmvPlanF32();
+    m->gs = GsPlan();
+    m->tri_upper = GsPlan();
     drop_shared_caches(m);
 }
 

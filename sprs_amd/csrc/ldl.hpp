@@ -182,6 +182,10 @@ __global__ void ldl_diag_kernel(const double *__restrict__ d, double *__restrict
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) x[i] = x[i] / d[i];                              // linalg.rs:26
 }
+__global__ void ldl_diag_kernel(const float *__restrict__ d, float *__restrict__ x, uint64_t n) {      // diag_solve::<f32>
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) x[i] = x[i] / d[i];
+}
 
 // ldl_numeric (lib.rs:502-593), one wave per row
 template <typename IDX, typename PTR>
@@ -504,12 +508,15 @@ int32_t ldl_export_l(const sprs_hip_ldl_num *num, OwnedCsmat &out, hipStream_t s
     return SPRS_HIP_OK;
 }
 
-int32_t diag_solve_f64(const double *d, double *x, uint64_t n, hipStream_t stream) {
+template <typename T>
+static int32_t diag_solve_any(const T *d, T *x, uint64_t n, hipStream_t stream) {
     if (!n) return SPRS_HIP_OK;
     hipLaunchKernelGGL(ldl_diag_kernel, dim3(ldl_grid(n)), dim3(256), 0, stream, d, x, n);
     SPRS_TRY_HIP(hipGetLastError());
     return SPRS_HIP_OK;
 }
+int32_t diag_solve_f64(const double *d, double *x, uint64_t n, hipStream_t stream) { return diag_solve_any(d, x, n, stream); }
+int32_t diag_solve_f32(const float *d, float *x, uint64_t n, hipStream_t stream) { return diag_solve_any(d, x, n, stream); }
 
 // LdlNumeric::solve (lib.rs:403-409): P b, lsolve, diag_solve, ltsolve, P^-1 x
 int32_t ldl_solve_f64(sprs_hip_ldl_num *num, const double *b, double *x, hipStream_t stream) {

@@ -6,7 +6,8 @@
 // Included by gauss_seidel.hip, inside namespace sprs_hip and after its helpers (one translation unit of the library and of the
 // emulator build, tests/emu): a Gauss-Seidel sweep is a lower triangular solve with extra terms from the previous iterate, and
 // this is that sweep without them.  Shared with it: the level plan (gs_plan_build; lower = the sweep's own order, upper = its
-// mirror), gs_peek / gs_draw / gs_spin_guard, the batch of GS_B operands requested together, the data-tagged 8-byte hand-off.
+// mirror), gs_peek / gs_draw / gs_spin_guard, the batch of GS_B operands requested together, the data-tagged hand-off (GsWord<T>:
+// 8-byte granules for f64, 4-byte granules for f32).
 //
 // ONE ROW-ORIENTED KERNEL FOR THE FOUR SOLVES.  Every solve gives unknown r the chain
 //     x_r = (b_r - v_1 x_c1 - v_2 x_c2 - ...) / diag_r        (each product rounded, then each subtraction: trisolve.rs:62, 140)
@@ -34,7 +35,7 @@
 namespace {
 
 constexpr unsigned int TS_SINGULAR = 4u;                      // status bit beside GS_NO_DIAG / GS_TIMEOUT
-constexpr unsigned long long TS_ABSENT = ~0ull - 1ull;       // SPARSE: "this unknown is not part of the solve" (a second NaN no arithmetic yields)
+constexpr unsigned long long TS_ABSENT = GsWord<double>::ABSENT;      // SPARSE: "this unknown is not part of the solve" (a second NaN no arithmetic yields)
 
 // UNIT: the diagonal is 1 and not stored (the factor L of ldl.hpp: ldl_lsolve / ldl_ltsolve, sprs-ldl/src/lib.rs:595-626); a row
 // is then its chain of subtractions, never divided and never singular.
@@ -42,31 +43,36 @@ constexpr unsigned long long TS_ABSENT = ~0ull - 1ull;       // SPARSE: "this un
 // tells three states apart: GS_PENDING (in the subset, not solved yet), a value, and TS_ABSENT (not in the subset: the unknown
 // is exactly zero).  An absent operand counts as arrived and its product is SKIPPED — not multiplied by 0.0, which would turn
 // a stored inf or NaN of that column into a NaN.  Off, the kernel compiles to what it was.
-template <typename IDX, typename PTR, bool UPPER, bool BACKWARD, bool UNIT = false, bool SPARSE = false>
+// T = the scalar of the values, of x and of the arithmetic: every product, every subtraction and the division are rounded to T.
+// `work` is declared as the f64 code always had it (its symbols must not move); what it addresses is one GsWord<T>::word per
+// unknown: 8-byte words for double, 4-byte words for float.  UNIT and SPARSE are instantiated for double only.
+template <typename IDX, typename PTR, bool UPPER, bool BACKWARD, bool UNIT = false, bool SPARSE = false, typename T = double>
 __global__ __launch_bounds__(GS_BLOCK) void tri_solve_kernel(const PTR *__restrict__ indptr, const IDX *__restrict__ indices,
-                                                             const double *__restrict__ data, const uint32_t *__restrict__ order,
-                                                             double *x, unsigned long long *work, uint64_t n,
+                                                             const T *__restrict__ data, const uint32_t *__restrict__ order,
+                                                             T *x, unsigned long long *work, uint64_t n,
                                                              unsigned int *next_chunk, unsigned int *status,
                                                              unsigned long long *singular, uint32_t structural) {
     // sorted rows: the wanted triangle ends at the first entry on or past the diagonal in walk direction
     constexpr bool STOP_AT_DIAG = UPPER == BACKWARD;
+    using W = GsWord<T>;
+    typename W::word *const granule = (typename W::word *)work;
     const uint32_t lane = threadIdx.x & 63u;
     for (uint64_t base = gs_draw(next_chunk, lane); base < n; base = gs_draw(next_chunk, lane)) {
         const uint64_t pos = base + lane;
         bool done = pos >= n;
         uint32_t row = 0;
         uint64_t p = 0, end = 0;                               // entries not walked yet: [p, end), taken from the front (BACKWARD: from the back)
-        double acc = 0.0;
+        T acc = T(0);
         if (!done) {
             row = order[pos];
             p = (uint64_t)indptr[row];
             end = (uint64_t)indptr[row + 1];
             acc = x[row];                                      // b_r (trisolve.rs:53, 133, 192, 242)
         }
-        double diag = 0.0;
+        T diag = T(0);
         bool has_diag = false, last = false;
         uint32_t col[GS_B];
-        double val[GS_B], xv[GS_B];
+        T val[GS_B], xv[GS_B];
         uint32_t nb = 0, pend = 0, spins = 0, absent = 0;
         bool loaded = false, more = true;
         while (more) {
@@ -97,15 +103,15 @@ __global__ __launch_bounds__(GS_BLOCK) void tri_solve_kernel(const PTR *__restri
                     moved = true;
                 }
                 // the poll: the operands of the batch that have not arrived yet, all requested together
-                unsigned long long bits[GS_B];
+                typename W::word bits[GS_B];
 #pragma unroll
                 for (int u = 0; u < GS_B; ++u)
-                    if ((pend >> u) & 1u) bits[u] = gs_peek(work + col[u]);
+                    if ((pend >> u) & 1u) bits[u] = gs_peek(granule + col[u]);
 #pragma unroll
                 for (int u = 0; u < GS_B; ++u)
-                    if (((pend >> u) & 1u) && bits[u] != GS_PENDING) {
-                        xv[u] = __longlong_as_double((long long)bits[u]);
-                        if (SPARSE && bits[u] == TS_ABSENT) absent |= 1u << u;
+                    if (((pend >> u) & 1u) && bits[u] != W::PENDING) {
+                        xv[u] = W::value(bits[u]);
+                        if (SPARSE && bits[u] == W::ABSENT) absent |= 1u << u;
                         pend &= ~(1u << u);
                         moved = true;
                     }
@@ -118,7 +124,7 @@ __global__ __launch_bounds__(GS_BLOCK) void tri_solve_kernel(const PTR *__restri
                                 diag = val[u];
                                 has_diag = true;
                             } else if ((UPPER ? c > row : c < row) && !(SPARSE && ((absent >> u) & 1u))) {
-                                const double prod = val[u] * xv[u];
+                                const T prod = val[u] * xv[u];
                                 acc = acc - prod;
                             }
                             if (STOP_AT_DIAG && (UPPER ? c <= row : c >= row)) last = true;
@@ -126,19 +132,19 @@ __global__ __launch_bounds__(GS_BLOCK) void tri_solve_kernel(const PTR *__restri
                     loaded = false;
                     moved = true;
                     if (last || p == end) {
-                        const double xr = UNIT ? acc : acc / diag;   // trisolve.rs:70, 134, 193, 259
-                        unsigned long long out = (unsigned long long)__double_as_longlong(xr);
-                        if (!UNIT && (!has_diag || diag == 0.0)) {
+                        const T xr = UNIT ? acc : acc / diag;   // trisolve.rs:70, 134, 193, 259
+                        typename W::word out = W::bits(xr);
+                        if (!UNIT && (!has_diag || diag == T(0))) {
                             const unsigned long long word = ((unsigned long long)row << 1) | (has_diag ? 0ull : (unsigned long long)structural);
                             if (UPPER) atomicMax(singular, word);
                             else atomicMin(singular, word);
                             atomicOr(status, TS_SINGULAR);
-                            out = GS_QNAN;
+                            out = W::QNAN;
                         } else {
                             x[row] = xr;
                         }
-                        if (out == GS_PENDING || (SPARSE && out == TS_ABSENT)) out = GS_QNAN;   // (a NaN payload handed through from b: still a NaN, but not "pending")
-                        __hip_atomic_store(work + row, out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        if (out == W::PENDING || (SPARSE && out == W::ABSENT)) out = W::QNAN;   // (a NaN payload handed through from b: still a NaN, but not "pending")
+                        __hip_atomic_store(granule + row, out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         done = true;
                     }
                 }
@@ -151,14 +157,15 @@ __global__ __launch_bounds__(GS_BLOCK) void tri_solve_kernel(const PTR *__restri
 
 // one solve over arrays in CSR form, rows taken in `order`: the launch and the read-back of the status words into hw
 // ([0] chunks drawn, [1] status, [2..3] the singular word)
-template <typename IDX, typename PTR>
-int32_t tri_run(const void *indptr, const void *indices, const double *data, const uint32_t *order, bool upper, bool csc, bool unit,
-                double *x, uint64_t n, unsigned int *hw, hipStream_t stream) {
+// (T is deduced from the values; the unit-diagonal form is LDL^T's and exists for double only)
+template <typename IDX, typename PTR, typename T>
+int32_t tri_run(const void *indptr, const void *indices, const T *data, const uint32_t *order, bool upper, bool csc, bool unit,
+                T *x, uint64_t n, unsigned int *hw, hipStream_t stream) {
     DevBuf work, words;
     StreamDrain drain{stream};
-    SPRS_TRY_HIP(work.alloc(n * sizeof(double)));
+    SPRS_TRY_HIP(work.alloc(n * sizeof(T)));
     SPRS_TRY_HIP(words.alloc(64));
-    SPRS_TRY_HIP(hipMemsetAsync(work.p, 0xFF, n * sizeof(double), stream));      // every unknown "pending"
+    SPRS_TRY_HIP(hipMemsetAsync(work.p, 0xFF, n * sizeof(T), stream));      // every unknown "pending"
     SPRS_TRY_HIP(hipMemsetAsync(words.p, 0, 64, stream));
     if (!upper) SPRS_TRY_HIP(hipMemsetAsync(words.as<unsigned int>() + 2, 0xFF, 8, stream));   // atomicMin starts from the top
     unsigned int *w = words.as<unsigned int>();
@@ -175,18 +182,22 @@ int32_t tri_run(const void *indptr, const void *indices, const double *data, con
                            (unsigned long long *)work.p, n, w, w + 1, (unsigned long long *)(w + 2), csc ? 1u : 0u);
     };
     if (unit) {
-        if (!upper) launch(tri_solve_kernel<IDX, PTR, false, false, true>);
-        else launch(tri_solve_kernel<IDX, PTR, true, false, true>);
-    } else if (!upper) launch(tri_solve_kernel<IDX, PTR, false, false>);
-    else if (csc) launch(tri_solve_kernel<IDX, PTR, true, true>);
-    else launch(tri_solve_kernel<IDX, PTR, true, false>);
+        if constexpr (std::is_same<T, double>::value) {
+            if (!upper) launch(tri_solve_kernel<IDX, PTR, false, false, true>);
+            else launch(tri_solve_kernel<IDX, PTR, true, false, true>);
+        } else {
+            SPRS_FAIL(SPRS_HIP_INVALID_ARG, "triangular solve: the unit-diagonal form is built for f64 only");
+        }
+    } else if (!upper) launch(tri_solve_kernel<IDX, PTR, false, false, false, false, T>);
+    else if (csc) launch(tri_solve_kernel<IDX, PTR, true, true, false, false, T>);
+    else launch(tri_solve_kernel<IDX, PTR, true, false, false, false, T>);
     SPRS_TRY_HIP(hipGetLastError());
     SPRS_TRY_HIP(copy_to_host(hw, words.p, 4 * sizeof(unsigned int), stream));
     return SPRS_HIP_OK;
 }
 
-template <typename IDX, typename PTR>
-int32_t trisolve_impl(sprs_hip_csmat *a, bool upper, bool csc, double *x, uint64_t n, sprs_hip_trisolve_info *info, hipStream_t stream) {
+template <typename IDX, typename PTR, typename H>
+int32_t trisolve_impl(H *a, bool upper, bool csc, typename H::value_type *x, uint64_t n, sprs_hip_trisolve_info *info, hipStream_t stream) {
     // held from the look-up of the row order to the end of the (blocking) solve, the way gs_impl holds it
     std::lock_guard<std::recursive_mutex> lock(a->mu);
     GsPlan &pl = upper ? a->tri_upper : a->gs;                 // lower: exactly the Gauss-Seidel order
@@ -194,7 +205,7 @@ int32_t trisolve_impl(sprs_hip_csmat *a, bool upper, bool csc, double *x, uint64
     if (info) info->levels = pl.nlevels;
 
     unsigned int hw[4] = {0, 0, 0, 0};
-    SPRS_TRY((tri_run<IDX, PTR>(a->indptr, a->indices, a->data, pl.order, upper, csc, false, x, n, hw, stream)));
+    SPRS_TRY((tri_run<IDX, PTR>(a->indptr, a->indices, (const typename H::value_type *)a->data, pl.order, upper, csc, false, x, n, hw, stream)));
     if ((uint64_t)hw[0] * 64u < n)
         SPRS_FAIL(SPRS_HIP_HIP_ERROR, "triangular solve: only %llu of %llu rows were solved", (unsigned long long)hw[0] * 64ull, (unsigned long long)n);
     if (hw[1] & GS_TIMEOUT)
@@ -217,10 +228,18 @@ int32_t trisolve_impl(sprs_hip_csmat *a, bool upper, bool csc, double *x, uint64
     return SPRS_HIP_OK;
 }
 
-}  // namespace
-
-int32_t trisolve_f64(sprs_hip_csmat *csr, bool upper, bool csc, double *x, uint64_t n, sprs_hip_trisolve_info *info, hipStream_t stream) {
+template <typename H>
+int32_t trisolve_entry(H *csr, bool upper, bool csc, typename H::value_type *x, uint64_t n, sprs_hip_trisolve_info *info, hipStream_t stream) {
     return dispatch_widths(csr->idx_bytes, csr->iptr_bytes, [&](auto i, auto p) {
         return trisolve_impl<typename decltype(i)::type, typename decltype(p)::type>(csr, upper, csc, x, n, info, stream);
     });
+}
+
+}  // namespace
+
+int32_t trisolve_f64(sprs_hip_csmat *csr, bool upper, bool csc, double *x, uint64_t n, sprs_hip_trisolve_info *info, hipStream_t stream) {
+    return trisolve_entry(csr, upper, csc, x, n, info, stream);
+}
+int32_t trisolve_f32(sprs_hip_csmat_f32 *csr, bool upper, bool csc, float *x, uint64_t n, sprs_hip_trisolve_info *info, hipStream_t stream) {
+    return trisolve_entry(csr, upper, csc, x, n, info, stream);
 }

@@ -3,7 +3,8 @@ sprs::linalg::bicgstab (sprs/src/sparse/linalg/bicgstab.rs) behind `sprs_hip_bic
 in HBM: two SpMVs, four fused element-wise kernels and three dot launches per iteration) and the Gauss-Seidel
 solver of the heat example (sprs/examples/heat.rs:103-139) behind `sprs_hip_gauss_seidel_f64`; and of the four dense-rhs
 triangular solves of sprs::linalg::trisolve (sprs/src/sparse/linalg/trisolve.rs) behind `sprs_hip_trisolve_f64`, and of its
-sparse-rhs solve behind `sprs_hip_lsolve_csc_sparse_rhs_f64`."""
+sparse-rhs solve behind `sprs_hip_lsolve_csc_sparse_rhs_f64`.  BiCGSTAB, Gauss-Seidel, the dense-rhs triangular solves and
+diag_solve dispatch on the operand class: a DeviceCsMatF32 with DeviceVecF32 vectors runs the `_f32` entry."""
 import ctypes as C
 
 from . import _ffi
@@ -96,15 +97,25 @@ class GaussSeidelResult:
         return ("Ok((%d, %r))" % (self.iterations, self.error)) if self.converged else "Err(%r)" % self.error
 
 
+def _same_precision(mat, *vecs):
+    """The vectors of an operation on `mat` are of its precision: DeviceVecF32 with a DeviceCsMatF32 and with no other matrix."""
+    from .device import DeviceCsMatF32, DeviceVecF32
+    f32 = isinstance(mat, DeviceCsMatF32)
+    if any(isinstance(v, DeviceVecF32) != f32 for v in vecs):
+        raise TypeError("matrix and vectors must have the same precision")
+
+
 def gauss_seidel(mat, x, rhs, max_iter, eps, stream=None):
     """gauss_seidel(mat, x, rhs, max_iter, eps) (heat.rs:103-139): mat a square CSR DeviceCsMat, x (start vector,
     overwritten with the result like the reference's `mut x`) and rhs DeviceVecs.  Dimension mismatch and a row
-    without a diagonal entry raise, like the reference's asserts / `diag.unwrap()`."""
+    without a diagonal entry raise, like the reference's asserts / `diag.unwrap()`.  A DeviceCsMatF32 with DeviceVecF32
+    vectors runs gauss_seidel::<f32> (sprs_hip_gauss_seidel_f32): eps is rounded to f32 first, `error` is the f32 value."""
+    _same_precision(mat, x, rhs)
     if x.n != rhs.n:
         raise _ffi.SprsHipError(_ffi.DIM_MISMATCH, "Dimension mismatch")
     info = _GsInfo()
-    check(lib.sprs_hip_gauss_seidel_f64(mat._h, C.c_void_p(x.ptr), C.c_void_p(rhs.ptr), x.n, int(max_iter), float(eps),
-                                        C.byref(info), C.c_void_p(int(stream) if stream else 0)))
+    check(mat._op("gauss_seidel")(mat._h, C.c_void_p(x.ptr), C.c_void_p(rhs.ptr), x.n, int(max_iter), float(mat._dtype(eps)),
+                                  C.byref(info), C.c_void_p(int(stream) if stream else 0)))
     return GaussSeidelResult(info)
 
 
@@ -127,11 +138,12 @@ _SINGULAR_REASONS = {1: "numeric", 2: "structural"}
 
 
 def _trisolve(mat, rhs, storage, uplo, stream):
+    _same_precision(mat, rhs)
     if mat.storage() != storage:                    # assert!(mat.is_csr() / is_csc(), "Storage mismatch"): trisolve.rs:42, 98, 174, 232
         raise _ffi.SprsHipError(_ffi.STORAGE_MISMATCH, "Storage mismatch")
     info = _TriInfo()
-    status = lib.sprs_hip_trisolve_f64(mat._h, uplo, C.c_void_p(rhs.ptr), rhs.n, C.byref(info),
-                                       C.c_void_p(int(stream) if stream else 0))
+    status = mat._op("trisolve")(mat._h, uplo, C.c_void_p(rhs.ptr), rhs.n, C.byref(info),
+                                 C.c_void_p(int(stream) if stream else 0))
     if status == _ffi.SINGULAR_MATRIX:              # Err(LinalgError::SingularMatrix(SingularMatrixInfo { index, reason }))
         err = _ffi.SprsHipError(status, lib.sprs_hip_last_error().decode("utf-8", "replace"))
         err.index = int(info.singular_index)
@@ -144,7 +156,9 @@ def _trisolve(mat, rhs, storage, uplo, stream):
 def lsolve_csr_dense_rhs(mat, rhs, stream=None):
     """lsolve_csr_dense_rhs(lower_tri_mat, rhs) (trisolve.rs:30-73): mat a square CSR DeviceCsMat (its upper triangle is
     ignored), rhs a DeviceVec solved in place.  Raises SprsHipError: DIM_MISMATCH / STORAGE_MISMATCH like the reference's
-    asserts, SINGULAR_MATRIX (with `.index` and `.reason`, "numeric" or "structural") where it returns Err."""
+    asserts, SINGULAR_MATRIX (with `.index` and `.reason`, "numeric" or "structural") where it returns Err.  All four solves take
+    a DeviceCsMatF32 with a DeviceVecF32 as well (sprs_hip_trisolve_f32: the reference's f32 bits); a vector of the other
+    precision raises TypeError."""
     return _trisolve(mat, rhs, _ffi.CSR, _ffi.LOWER, stream)
 
 
@@ -193,8 +207,13 @@ def lsolve_csc_sparse_rhs(mat, rhs, stream=None):
 
 
 def diag_solve(diag, x, stream=None):
-    """linalg::diag_solve (sprs/src/sparse/linalg.rs:17-29): x[i] /= diag[i], in place on the DeviceVec x."""
+    """linalg::diag_solve (sprs/src/sparse/linalg.rs:17-29): x[i] /= diag[i], in place on the DeviceVec x; two DeviceVecF32
+    run diag_solve::<f32>."""
+    from .device import DeviceVecF32
+    if isinstance(diag, DeviceVecF32) != isinstance(x, DeviceVecF32):
+        raise TypeError("diag and x must have the same precision")
     if diag.n != x.n:                               # assert_eq!(diag.len(), x.len())
         raise _ffi.SprsHipError(_ffi.DIM_MISMATCH, "Dimension mismatch")
-    check(lib.sprs_hip_diag_solve_f64(C.c_void_p(diag.ptr), C.c_void_p(x.ptr), x.n, C.c_void_p(int(getattr(stream, "cuda_stream", stream)) if stream else 0)))
+    entry = lib.sprs_hip_diag_solve_f32 if isinstance(x, DeviceVecF32) else lib.sprs_hip_diag_solve_f64
+    check(entry(C.c_void_p(diag.ptr), C.c_void_p(x.ptr), x.n, C.c_void_p(int(getattr(stream, "cuda_stream", stream)) if stream else 0)))
     return x
